@@ -1,7 +1,7 @@
 """Headline benchmark of the hot path (BASELINE.json): frames/s end-to-end for chunk creation + overlap alignment at
 chunk_length=100, overlap=20, 512x384 input (-> 308x406 by the reference's calculate_target_size rule).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 N > 1 runs one rank per GPU over RCCL either way: under `python -m torch.distributed.run --nproc-per-node N bench.py
 --gpus N ...` (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment), or started as a plain process, in which
 case this file launches its own N ranks BEFORE anything touches the GPU (launch_ranks below) and relays rank 0's line.
@@ -14,8 +14,14 @@ from the decoded uint8 frames in pinned host memory, as SURVEY.md §8(d) defines
 (N > 1: one chunk per rank per step, then the wave alignment: RCCL all-gather of the boundary blocks, each rank's own
 solve, a 136-byte all-gather of the transforms, prefix composition, application).  The stages of consecutive chunks
 overlap exactly as in production (copy stream / compute stream / host), so the K timed steps include one pipeline fill.
-Prints ONE JSON line on rank 0.  Extra keys (N = 1): per-stage milliseconds, the 378x504 and K=400 variants, the
-from-disk rate of process_and_save(), and the CPU baseline of the whole path.
+Prints ONE JSON line on rank 0: the headline, per-stage milliseconds and the roofline figures read from HIP events of
+the timed steps.  A plain run does nothing else: set-up, warm-up, the K timed steps, the outputs (--dump-outputs) and
+the line.  --full adds what takes runs of its own (N = 1): the all-online-max step, the 378x504 and K=400 variants, the
+from-disk rate of process_and_save() and the other extras, the APE proxy, the second metric and the CPU baseline of the
+whole path (--no-extras / --no-cpu-baseline leave parts of it out).
+--dump-outputs DIR: after the timed steps, rank 0 writes the chunk dictionary its last timed step handed back (after the
+alignment) as DIR/<key>.npy, float32 (float64 for the accumulated similarity): the inputs are seeded, so two builds can
+be compared output for output.
 """
 from __future__ import annotations
 
@@ -164,16 +170,61 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)     # 10 x 0.4 s: the pipeline's fill + drain (~14 ms) is 0.35 % of the region
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--cpu-frames", type=int, default=32,
-                    help="frames of the CPU baseline sample (32 = BASELINE configs[0], ~80 s on the GPU box's 16 host threads; 8: ~30 s)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the 378x504 / K=400 / from-disk extras")
+                    help="frames of the CPU baseline sample of --full (32 = BASELINE configs[0], ~80 s on 16 host threads; 8: ~30 s)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the all-online-max step and the 378x504 / K=400 / from-disk extras")
     ap.add_argument("--no-moge", action="store_true", help="diagnostic only: leave the MoGe metric scale out (the line then says "
                     "moge_metric_scale_in_timed_region: false and is not the headline workload)")
     ap.add_argument("--launch-check", action="store_true",
                     help="rendezvous only: every rank joins the process group, one all-gather, rank 0 prints the comm "
                          "record; no chunk is processed (with PI3_DIST_BACKEND=gloo it needs no GPU)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also the measurements that take runs of their own (N = 1): all-online-max "
+                         "step, extras, APE proxy, second metric, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's chunk dictionary as DIR/<key>.npy (float32 / float64)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, chunk: dict, extra: dict = None) -> dict:
+    """The arrays of one chunk dictionary (nested dicts flattened to 'a.b', masks as 0 / 1) as out_dir/<name>.npy, float32
+    (float64 where the product holds float64).  An array that would take the total past DUMP_BUDGET_BYTES is replaced by
+    a fixed, seeded sample of its flattened elements (the same indices on every run)."""
+    import numpy as np
+    arrays = {}
+
+    def walk(prefix, obj):
+        if isinstance(obj, dict):
+            for k, v in obj.items():
+                if not str(k).startswith("_metrics"):
+                    walk(f"{prefix}.{str(k).lstrip('_')}" if prefix else str(k).lstrip("_"), v)
+        elif isinstance(obj, torch.Tensor):
+            t = obj.detach().cpu()
+            arrays[prefix] = t.double().numpy() if t.dtype == torch.float64 else t.float().numpy()
+        elif isinstance(obj, np.ndarray) and obj.dtype.kind in "biuf":
+            arrays[prefix] = obj.astype(np.float64 if obj.dtype == np.float64 else np.float32)
+
+    walk("", chunk)
+    walk("", extra or {})
+    os.makedirs(out_dir, exist_ok=True)
+    left, written = DUMP_BUDGET_BYTES, {}
+    for i, name in enumerate(sorted(arrays, key=lambda n: arrays[n].nbytes)):
+        a = np.ascontiguousarray(arrays[name])
+        share = left // (len(arrays) - i)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=max(1, share // a.itemsize), replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes
+        written[name] = list(a.shape)
+    return written
 
 
 def launch_ranks(n: int, argv) -> int:
@@ -387,6 +438,7 @@ def main(args) -> None:
     attn_events = []
     kernel_events = {}          # {kernel name: [(start, end)]} of three sampled blocks per step (engine.forward)
     last_wave = {"Gs": []}      # the global transforms of the most recent wave (the stub run prints them to be checked)
+    last_out = {}               # the chunk dictionary of the most recent step, aligned (--dump-outputs)
 
     class _EventedModel:   # HIP events on the launch stream around the dominant kernel (global attention)
         def __init__(self, eng, events, kevents=None):
@@ -428,6 +480,7 @@ def main(args) -> None:
             m = dict(chunk["_metrics"])
             m["align_host_s"] = time.perf_counter() - t0
             stats.append(m)
+            last_out["chunk"] = chunk
         if not stub:
             cr.model = engine
         return stats
@@ -459,10 +512,13 @@ def main(args) -> None:
         dt = time.perf_counter() - t0
         if not stub:
             ops.attention_path_counters(None)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_out["chunk"],
+                     {"wave_global_transforms": torch.stack(last_wave["Gs"])} if last_wave["Gs"] else None)
     n_headline_events = len(attn_events)
     headline_kernel_events = {k: list(v) for k, v in kernel_events.items()}
     online_max = None
-    if world == 1 and not grouped and not args.no_extras:
+    if world == 1 and not grouped and args.full and not args.no_extras:
         # the same step with every wave on the online-max loop (knob attn_nomax = 0): the worst case for real weights.
         # (--no-extras skips it: the rocprofv3 kernel-trace of the bench command must average the headline launches only,
         # the two loops being one kernel instance)
@@ -570,14 +626,15 @@ def main(args) -> None:
             # what ONE GPU takes for the same step, to cross-check this N-rank line against the N = 1 line: the committed
             # N = 1 record and, live, every rank's own wall time per step and forward time by GPU events (comm.per_rank)
             line["n1_reference_ms_per_step"] = N1_REFERENCE
-        line["second_metric"] = second_metric(dev) if world == 1 else {
-            "metric": "7-Scenes APE", "value": None, "note": "reported by the N = 1 run"}
+        if args.full:
+            line["second_metric"] = second_metric(dev) if world == 1 else {
+                "metric": "7-Scenes APE", "value": None, "note": "reported by the N = 1 run"}
         proxy = None
-        if world == 1 and not args.no_extras and not stub:
+        if world == 1 and args.full and not args.no_extras and not stub:
             with contextlib.redirect_stdout(sys.stderr):
                 line["extras"] = extras(engine, moge, make_creator, run, dev)
                 proxy = ape_proxy_product(dev)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(cfg, args.cpu_frames)
             if proxy is not None and "dir" in proxy:      # the CPU side of the proxy: the fp64 oracle over the same 13 files
                 with contextlib.redirect_stdout(sys.stderr):
@@ -1037,7 +1094,10 @@ if __name__ == "__main__":
     _args = parse_args()
     if _args.gpus > 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1 and "RANK" not in os.environ:
         # plain `python bench.py --gpus N`: become the launcher.  Nothing above has touched the GPU (module imports only).
-        sys.exit(launch_ranks(_args.gpus, sys.argv[1:]))
+        _argv = sys.argv[1:]
+        if _args.dump_outputs:        # the ranks run in the repository root: hand them the directory as an absolute path
+            _argv += ["--dump-outputs", os.path.abspath(_args.dump_outputs)]
+        sys.exit(launch_ranks(_args.gpus, _argv))
     # stdout carries exactly ONE line, the JSON record of rank 0; the pipeline's progress prints (per-chunk inference
     # FPS etc., on every rank) go to stderr
     _REAL_STDOUT = sys.stdout

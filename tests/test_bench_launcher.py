@@ -106,3 +106,27 @@ def test_full_main_control_flow_with_stub_engine(world, how):
     for r_, c in enumerate(range(world, 2 * world)):
         want = np.linalg.inv(S(0)) @ S(c)
         assert np.abs(got[r_] - want).max() < 2e-2, (c, got[r_], want)      # fp16 chunk-file points: ~1e-3 relative
+
+
+def test_dump_outputs_with_stub_engine(tmp_path):
+    """`--dump-outputs DIR` writes the chunk dictionary of the last timed step (after the wave alignment) as float32 /
+    float64 .npy files, the same bits for the same arguments; a relative DIR is taken from the caller's directory even
+    though the self-launched ranks run in the repository root.  --steps sets the number of timed steps."""
+    import numpy as np
+    outs = []
+    for run in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+               "--dump-outputs", "dump_" + run]
+        r = subprocess.run(cmd, env=_env(PI3_BENCH_STUB="1"), capture_output=True, text=True, timeout=600, cwd=tmp_path)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        rec = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+        assert rec["steps"] == 3 and rec["ms_per_step"] > 0
+        assert "cpu_baseline" not in rec and "extras" not in rec and "second_metric" not in rec     # --full only
+        d = tmp_path / ("dump_" + run)
+        files = {p.name: np.load(p) for p in sorted(d.glob("*.npy"))}
+        assert {"points.npy", "camera_poses.npy", "keypoints.npy", "sim3_global.npy", "wave_global_transforms.npy"} <= set(files)
+        assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+        assert sum(a.nbytes for a in files.values()) <= 64 << 20
+        assert files["points.npy"].shape == (100, 200, 3) and files["wave_global_transforms.npy"].shape == (2, 4, 4)
+        outs.append(files)
+    assert all(np.array_equal(outs[0][k], outs[1][k]) for k in outs[0])

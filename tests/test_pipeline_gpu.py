@@ -435,6 +435,34 @@ def test_bench_nccl_branch_with_a_forced_one_rank_group(built_lib):
     assert rec["value"] > 30 and 0 < rec["roofline"]["frac"] < 1 and len(comm["per_rank"]) == 1
 
 
+def test_bench_plain_run_dumps_the_last_step(tmp_path, built_lib):
+    """The plain one-GPU bench: the headline keys, nothing of --full, and --dump-outputs writing the aligned chunk
+    dictionary of the last timed step (float32 / float64, finite where the chunk file is)."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "PI3_DIST_BACKEND", "PI3_DIST_FORCE",
+              "PI3_BENCH_LAUNCHER", "PI3_BENCH_STUB"):
+        env.pop(k, None)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path / "out")], env=env, capture_output=True, text=True, timeout=600,
+                       cwd=root)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    rec = json.loads(lines[0])
+    assert rec["steps"] == 2 and rec["unit"] == "frames/s" and rec["higher_is_better"] is True and rec["dtype"] == "bf16"
+    assert rec["value"] == pytest.approx(100 * 2 / (rec["ms_per_step"] * 2e-3), rel=1e-6)
+    assert not {"cpu_baseline", "extras", "second_metric", "comm"} & set(rec)
+    files = {p.name[:-4]: np.load(p) for p in (tmp_path / "out").glob("*.npy")}
+    assert {"points", "local_points", "conf", "keypoints", "colors", "masks", "camera_poses", "sim3_global"} <= set(files)
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert sum(a.nbytes for a in files.values()) <= 64 << 20
+    assert files["points"].shape[:2] == (100, 200) and files["sim3_global"].shape == (4, 4)
+    assert np.isfinite(files["camera_poses"]).all() and np.isfinite(files["sim3_global"]).all()
+
+
 def test_rccl_branch_with_a_one_rank_group(tmp_path, built_lib):
     """The nccl (= RCCL) branch of the chunk-parallel code on the hardware that is available: ONE rank on this box's GPU
     (two ranks cannot share a card under RCCL).  Device-resident boundary blocks, all-gathers of device tensors,

@@ -352,6 +352,35 @@ int pi3_ba_outlier_tracks(const double* points, const double* poses, const doubl
                           const unsigned char* valid, int N, int K, double max_reprojection_px,
                           double min_triangulation_angle_deg, unsigned char* estimated, void* stream);
 
+/* ---- dense voxel map (csrc/voxel.hip): confidence-filtered fusion of the dense pointmaps into an open-addressing hash
+ * table of voxels.  table: caller-owned DEVICE memory of 64 bytes per slot (key, W, U[3], C[3] as uint64), capacity a
+ * power of two >= 2 x the candidate points fused since the last clear (the table never fills; no probe loop can run
+ * for ever).  Integer accumulators only: results are bitwise reproducible whatever order the atomics land in.
+ * Per point and axis (fp32, no contraction): s = p * inv_voxel, k = floor(s), u = min(trunc((s - k) * 2^24), 2^24 - 1);
+ * the key packs k + 2^20 of x, y, z at 21 bits each (x << 42 | y << 21 | z).  Points that are not finite or have
+ * |k| >= 2^20 are dropped and counted.  stats: DEVICE uint64 [4] = dropped, table overflows (0 under the capacity
+ * rule), voxels written by the last extract, voxels the last extract could not store.
+ * pi3_voxel_clear: every slot empty, stats zeroed. */
+int pi3_voxel_clear(void* table, long capacity, unsigned long long* stats, void* stream);
+/* One chunk's maps: points f32 [N][H][W][3], conf f32 logits [N][H][W] (or NULL), masks uint8 [N][H][W] (or NULL), imgs
+ * f32 [N][3][H][W] in [0, 1] (or NULL: black).  A pixel counts when mask != 0 and conf > conf_logit_thr; weight 1;
+ * colour = the keypoint colour rule, uint8 truncation of 255 c (saturated).  capacity >= 2 N H W. */
+int pi3_voxel_fuse_pixels(void* table, long capacity, const float* points, const float* conf, const unsigned char* masks,
+                          const float* imgs, int N, int H, int W, float conf_logit_thr, float inv_voxel,
+                          unsigned long long* stats, void* stream);
+/* A point list: points f32 [n][3], colors uint8 [n][3] (or NULL), weights int32 [n] (or NULL = 1; w <= 0 skips the
+ * point).  Each point adds w, w u and w rgb to its voxel.  capacity >= 2 n. */
+int pi3_voxel_fuse_points(void* table, long capacity, const float* points, const unsigned char* colors,
+                          const int* weights, long n, float inv_voxel, unsigned long long* stats, void* stream);
+/* Move every occupied slot of src into dst (a larger, cleared table): growth without losing the integer sums. */
+int pi3_voxel_rehash(const void* src_table, long src_capacity, void* dst_table, long dst_capacity,
+                     unsigned long long* stats, void* stream);
+/* Every occupied slot -> keys uint64 [V], centroid f32 [V][3] = voxel_size (k + U / (W 2^24)) (f64 arithmetic),
+ * colors uint8 [V][3] = (C + W / 2) / W, weights int32 [V] = min(W, 2^31 - 1), at most max_out entries; V lands in stats[2].  The order
+ * of the entries is not defined (sort by key on the host). */
+int pi3_voxel_extract(const void* table, long capacity, double voxel_size, unsigned long long* keys, float* points,
+                      unsigned char* colors, int* weights, long max_out, unsigned long long* stats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

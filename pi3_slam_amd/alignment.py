@@ -209,6 +209,7 @@ def align_and_refine_reconstructions(chunk_ref: Dict, chunk_qry: Dict, view_grap
                 print(f"   Bundle adjustment completed: Success=True, Final cost={ba['final_cost']:.6f}; "
                       f"removed {ba['removed_tracks']} tracks")
                 chunk_qry["_chunk_frame"] = {"points": chunk_qry["points"], "camera_poses": chunk_qry["camera_poses"]}
+                chunk_qry["_sim3_dense"] = chunk_qry["_sim3_global"]     # the dense cloud keeps the closed-form similarity
                 chunk_qry["_sim3_global"] = torch.eye(4, dtype=torch.float64)
             else:    # rejected by the sanity gate or failed numerically: the chunk keeps its closed-form alignment
                      # (points / poses untouched, frame bookkeeping unchanged); the caller sees it in the info dict

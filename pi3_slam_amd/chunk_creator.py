@@ -63,6 +63,9 @@ class OfflineCreatorConfig:
     overlap_stages: bool = True             # False: stage-in, launch and finish of a chunk run back to back (A/B knob)
     reuse_overlap_encoder: bool = False     # a chunk whose first `overlap` paths are the previous chunk's last ones takes
                                             # their (frame-local) encoder output from that chunk: bit-identical results
+    dense_voxel_size: Optional[float] = None  # set: every chunk also carries 'dense_cloud', its masked dense pointmap fused
+                                              # into voxels of this edge length (dense_map.py; chunk frame)
+    dense_conf_threshold: float = 0.5         # a pixel enters the dense cloud when sigmoid(conf) > this (and its mask)
 
 
 _UV_CACHE: Dict = {}
@@ -110,6 +113,7 @@ class _InFlight:
     dense: Optional[Dict[str, torch.Tensor]]  # device tensors of the no-keypoint fallback (copied in finish)
     meta: Dict
     t_launch: float = 0.0
+    dense_job: Optional[object] = None       # Future of the dense voxel cloud's host copy + key sort (_dense_host)
 
 
 class OfflineChunkCreator:
@@ -163,6 +167,17 @@ class OfflineChunkCreator:
         self._moge_stream = torch.cuda.Stream(self.device)
         self._d2h_stream = torch.cuda.Stream(self.device)
         self._pinned_pool: Dict[int, List[torch.Tensor]] = {}
+        # dense voxel map (opt-in): one device table, cleared and refilled per chunk on the compute stream
+        self._dense_fuser = None
+        if config.dense_voxel_size is not None:
+            from .dense_map import VoxelFuser
+            # two output sets: chunk k's is read on the host while chunk k+1's extraction is queued (finish(k) always
+            # completes before launch(k+2))
+            self._dense_fuser = VoxelFuser(config.dense_voxel_size, self.device, out_sets=2)
+            # the cloud's copy + key sort run on this thread as soon as the chunk's extraction is done, beside the host's
+            # launch of the next chunk instead of in front of it
+            self._dense_pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="dense-cloud")
+            self._dense_stream = torch.cuda.Stream(self.device)
 
     @staticmethod
     def _optional(what: str, make):
@@ -356,6 +371,18 @@ class OfflineChunkCreator:
             med = self._ratio_median(moge_depth, pi3["local_points"][0, 0][..., 2], masks[0])
             ops.apply_scale(med[:1], pi3["local_points"], pi3["points"], pi3["camera_poses"])
             out["_scale"] = med                         # [median, masked pixel count]: checked on the host
+        dense_job = None
+        if self._dense_fuser is not None:
+            # the metric points, queued before the next graph replay can reuse the static outputs; the extract writes
+            # into fresh buffers that finish() copies out, the voxel count rides in the packed D2H
+            fz = self._dense_fuser
+            fz.clear()
+            fz.fuse_pixels(pi3["points"][0].contiguous(), pi3["conf"][0].contiguous(), masks.contiguous(),
+                           imgs[0].contiguous(), cfg.dense_conf_threshold)
+            bufs, out["_dense_stats"] = fz.extract_async()
+            extracted = torch.cuda.Event()
+            extracted.record(cur)
+            dense_job = self._dense_pool.submit(self._dense_host, bufs, out["_dense_stats"], extracted)
         if cfg.estimate_camera_params:
             try:
                 for k, v in self._estimate_camera_parameters(pi3).items():
@@ -413,7 +440,7 @@ class OfflineChunkCreator:
         if trace is not None:
             print("   [trace] launch: " + ", ".join(f"{b[0]} +{(b[1] - a[1]) * 1e3:.1f} ms" for a, b in zip(trace, trace[1:])))
         return _InFlight(packed, layout, done, ev, host, dense, dict(st.meta, paths=st.paths, num_frames=N),
-                         t_launch=time.time())
+                         t_launch=time.time(), dense_job=dense_job)
 
     # ------------------------------------------------------------------ finish
     def _finish(self, fl: _InFlight) -> Dict:
@@ -469,7 +496,34 @@ class OfflineChunkCreator:
                     result[k] = v.cpu()
         if cam:
             result["intrinsics"] = cam.get("intrinsics")
+        if fl.dense_job is not None:
+            result["dense_cloud"] = self._dense_cloud(fl.dense_job.result(), got["_dense_stats"], metrics)
+            fl.dense_job = None
         return result
+
+    def _dense_host(self, bufs: tuple, stats_dev: torch.Tensor, extracted: torch.cuda.Event) -> Dict:
+        """(dense-cloud thread) Wait for the extraction, copy the first V rows into pinned memory on a stream of its own
+        (a copy into pageable memory would wait for the next chunk's forward) and sort them by key."""
+        from .dense_map import sort_by_key
+        with torch.cuda.device(self.device), torch.cuda.stream(self._dense_stream):
+            extracted.synchronize()
+            V = int(stats_dev[2].item())
+            h = [torch.empty((V,) + tuple(t.shape[1:]), dtype=t.dtype, pin_memory=True) for t in bufs]
+            for dst, src in zip(h, bufs):
+                dst.copy_(src[:V], non_blocking=True)
+            self._dense_stream.synchronize()
+        return sort_by_key(*(t.numpy() for t in h))
+
+    def _dense_cloud(self, s: Dict, stats: torch.Tensor, metrics: Dict) -> Dict:
+        """The chunk's voxel cloud from the sorted host rows; stats = the packed D2H copy of the table's counters."""
+        dropped, overflow, V, lost = (int(x) for x in stats.tolist())
+        if overflow or lost:
+            raise RuntimeError(f"dense voxel table overflow ({overflow} / {lost}): capacity rule violated")
+        assert len(s["keys"]) == V
+        metrics["dense_voxels"], metrics["dense_dropped"] = V, dropped
+        return {"points": torch.from_numpy(s["points"]), "colors": torch.from_numpy(s["colors"]),
+                "weights": torch.from_numpy(s["weights"]), "voxel_size": float(self.config.dense_voxel_size),
+                "conf_threshold": float(self.config.dense_conf_threshold)}
 
     # ------------------------------------------------------------------ one chunk, start to end (reference surface)
     def _process_single_chunk(self, chunk_images: torch.Tensor, chunk_paths: List[str]) -> Dict:

@@ -37,6 +37,9 @@ CREATE_FLAGS: Sequence[Tuple[str, Dict]] = (
     # this build's additions
     ("--moge-model-path", dict(default=None, help="local MoGe-2 model.pt; 'recipe' = synthetic weights")),
     ("--keypoint-seed", dict(type=int, default=0, help="seed of the grid subsampling, -1 = unseeded")),
+    ("--dense-voxel-size", dict(type=float, default=None, help="also fuse each chunk's dense pointmap into voxels of this "
+                                                               "edge length (metres): chunk['dense_cloud']")),
+    ("--dense-conf-threshold", dict(type=float, default=0.5, help="pixels with sigmoid(conf) above this enter the dense map")),
 )
 CREATE_SWITCHES = (("--device-resize", "Resize + ToTensor on the GPU (loader workers decode only)"),
                    ("--hip-graph", "replay the per-chunk forward as one captured hipGraph"),
@@ -88,6 +91,8 @@ ONLINE_FLAGS: Sequence[Tuple[str, Dict]] = (
     # this build's additions
     ("--moge_model_path", dict(default=None, help="local MoGe-2 model.pt; 'recipe' = synthetic weights")),
     ("--num_workers", dict(type=int, default=4, help="decode threads")),
+    ("--dense_voxel_size", dict(type=float, default=None, help="write dense_points.ply: the dense maps filtered by "
+                                                               "--conf_threshold, fused into voxels of this size (metres)")),
 )
 ONLINE_SWITCHES = (("--save_chunk_reconstructions", "save each chunk reconstruction to disk"),
                    ("--save_transformed_reconstructions", "save transformed reconstructions as PLY files"),
@@ -149,7 +154,8 @@ def run_create(a: argparse.Namespace) -> None:
         keypoint_detection_threshold=a.kp_threshold, estimate_camera_params=a.estimate_intrinsics,
         num_loader_workers=a.num_workers, cam_dist_path=a.cam_dist_path, moge_model_path=a.moge_model_path,
         keypoint_seed=None if a.keypoint_seed < 0 else a.keypoint_seed, device_resize=a.device_resize,
-        hip_graph=a.hip_graph, reuse_overlap_encoder=a.reuse_overlap_encoder)
+        hip_graph=a.hip_graph, reuse_overlap_encoder=a.reuse_overlap_encoder, dense_voxel_size=a.dense_voxel_size,
+        dense_conf_threshold=a.dense_conf_threshold)
     OfflineChunkCreator(cfg).process_and_save(paths[lo:hi])
 
 
@@ -200,7 +206,7 @@ def run_online(a: argparse.Namespace) -> None:
         do_metric_depth=a.do_metric_depth, model_path=a.model_path,
         use_inverse_depth=a.use_inverse_depth, moge_model_path=a.moge_model_path, hip_graph=not a.no_hip_graph,
         output_dir=out_dir, num_loader_workers=a.num_workers, bundle_adjust=not a.no_bundle_adjust,
-        reuse_overlap_encoder=a.reuse_overlap_encoder)
+        reuse_overlap_encoder=a.reuse_overlap_encoder, dense_voxel_size=a.dense_voxel_size)
     slam.save_transformed_reconstructions = a.save_transformed_reconstructions
     slam.save_debug_reconstructions = a.save_debug_reconstructions
     slam.process_chunks(paths)
@@ -214,6 +220,8 @@ def run_online(a: argparse.Namespace) -> None:
     if a.save_tum:
         slam.save_trajectory_tum(tum, integer_timestamp=a.tum_integer_timestamp)
     print(f"💾 Saved {ply}" + (f" and {tum}" if a.save_tum else ""))
+    if a.dense_voxel_size is not None:
+        slam.save_dense_map(os.path.join(out_dir or ".", "dense_points.ply"))
 
 
 def main(argv=None) -> None:

@@ -1,0 +1,347 @@
+// Dense voxel map: confidence-filtered fusion of pi3's per-pixel pointmaps (and of whole chunk clouds) into one
+// open-addressing hash table of voxels on the device.
+//
+// Slot layout (64 B, 8 x uint64): key | W | U0 U1 U2 | C0 C1 C2.
+//   key   the three voxel indices, each biased by 2^20 and packed at 21 bits (x << 42 | y << 21 | z); all ones = empty.
+//         Slots are claimed with a 64-bit CAS, collisions probe linearly.
+//   W     summed integer weight;  U = sum w * u with u = the fixed-point offset inside the voxel (24 fraction bits);
+//   C     sum w * rgb (uint8 colours).
+// Integer accumulators only: the sums do not depend on the order in which the atomics land, so a run is bitwise
+// reproducible and a float32 numpy oracle (tests/dense_map_ref.py) reproduces it bit for bit.
+//
+// Quantisation of one point p (per axis, fp32, no contraction):  s = p * inv_v;  k = floor(s);  f = s - k (exact);
+//   u = min(trunc(f * 2^24), 2^24 - 1)   (an exact integer whenever |s| >= 1; the clamp catches s in (-2^-24, 0), where
+//   s - k rounds to 1).  A point is dropped (and counted) when it is not finite or |k| >= 2^20.
+// Extraction: centroid = v * (k + U / (W * 2^24)) in f64, stored fp32;  colour = (C + W/2) / W;  weight = min(W, 2^31-1).
+//
+// Contention: a wave's 64 lanes hold 64 consecutive candidates (for the pixel form: 64 neighbouring pixels of a row,
+// which at 1-6 m depth and centimetre voxels mostly share voxels).  Runs of equal keys are merged in registers by a
+// segmented inclusive scan over the wave; only the last lane of each run touches the table (one probe + up to seven
+// 64-bit atomic adds).  Capacity is a power of two >= 2 x the candidates since the last clear (the caller's rule), so
+// the table never fills; every probe loop is bounded by the capacity anyway, and a candidate that finds no slot is
+// counted in stats[1] instead of looping.
+//
+// stats (caller-owned device memory, 4 x uint64): [0] dropped points, [1] table overflows (0 under the capacity rule),
+// [2] voxels written by the last extract, [3] voxels the last extract could not store (max_out too small).
+#include "common.h"
+
+#include <stdint.h>
+
+namespace {
+
+typedef unsigned long long u64;
+
+constexpr u64 kEmpty = ~0ull;
+constexpr int kBias = 1 << 20;
+constexpr float kFix = 16777216.0f;    // 2^24
+
+__device__ __forceinline__ u64 mix64(u64 x) {     // splitmix64 finaliser: neighbouring keys land far apart
+  x ^= x >> 30;
+  x *= 0xbf58476d1ce4e5b9ull;
+  x ^= x >> 27;
+  x *= 0x94d049bb133111ebull;
+  x ^= x >> 31;
+  return x;
+}
+
+// one axis: voxel index (biased) and fixed-point offset; false = drop
+__device__ __forceinline__ bool quantise(float p, float inv_v, uint32_t& kb, uint32_t& u) {
+#pragma clang fp contract(off)
+  if (!__builtin_isfinite(p)) return false;
+  float s = p * inv_v;
+  asm volatile("" : "+v"(s));          // the rounded product, never an fma with the subtraction below
+  const float k = floorf(s);
+  if (!(fabsf(k) < 1048576.0f)) return false;
+  const float f = s - k;
+  const float uf = f * kFix;
+  uint32_t ui = (uint32_t)uf;
+  u = ui > 0xFFFFFFu ? 0xFFFFFFu : ui;
+  kb = (uint32_t)((int)k + kBias);
+  return true;
+}
+
+// add (w, U, C) to the slot of `key`; false when no slot was found within `capacity` probes
+__device__ __forceinline__ bool slot_add(u64* __restrict__ table, u64 mask, u64 key, u64 w, u64 u0, u64 u1, u64 u2,
+                                         u64 c0, u64 c1, u64 c2) {
+  u64 h = mix64(key) & mask;
+  for (u64 probe = 0; probe <= mask; ++probe) {
+    u64* s = table + 8 * h;
+    u64 cur = __hip_atomic_load(s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (cur == kEmpty) {
+      const u64 old = atomicCAS(s, kEmpty, key);
+      cur = old == kEmpty ? key : old;
+    }
+    if (cur == key) {
+      atomicAdd(s + 1, w);
+      if (u0) atomicAdd(s + 2, u0);
+      if (u1) atomicAdd(s + 3, u1);
+      if (u2) atomicAdd(s + 4, u2);
+      if (c0) atomicAdd(s + 5, c0);
+      if (c1) atomicAdd(s + 6, c1);
+      if (c2) atomicAdd(s + 7, c2);
+      return true;
+    }
+    h = (h + 1) & mask;
+  }
+  return false;
+}
+
+// Every lane of the wave calls this (invalid lanes with valid = false).  Consecutive lanes with the same key are summed
+// in registers; the last lane of each run adds the run's totals to the table.
+__device__ __forceinline__ void wave_fuse(u64* __restrict__ table, u64 mask, bool valid, u64 key, u64 w, u64 v[6],
+                                          bool dropped, u64* __restrict__ stats) {
+  const int lane = (int)(threadIdx.x & 63);
+  if (!valid) key = kEmpty;
+  const u64 prev = __shfl_up(key, 1, 64);
+  const u64 next = __shfl_down(key, 1, 64);
+  const bool head = lane == 0 || prev != key;
+  const bool tail = lane == 63 || next != key;
+  const u64 heads = __ballot(head);
+  const u64 upto = lane == 63 ? ~0ull : ((2ull << lane) - 1ull);
+  const int seg = 63 - __clzll(heads & upto);          // first lane of this lane's run
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int oseg = __shfl_up(seg, d, 64);
+    const u64 ow = __shfl_up(w, d, 64);
+    u64 ov[6];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) ov[j] = __shfl_up(v[j], d, 64);
+    if (lane >= d && oseg == seg) {
+      w += ow;
+#pragma unroll
+      for (int j = 0; j < 6; ++j) v[j] += ov[j];
+    }
+  }
+  bool lost = false;
+  if (valid && tail) lost = !slot_add(table, mask, key, w, v[0], v[1], v[2], v[3], v[4], v[5]);
+  const u64 nd = __ballot(dropped), nl = __ballot(lost);
+  if (lane == 0) {
+    if (nd) atomicAdd(stats + 0, (u64)__popcll(nd));
+    if (nl) atomicAdd(stats + 1, (u64)__popcll(nl));
+  }
+}
+
+__device__ __forceinline__ uint32_t colour_u8(float c) {
+  const float v = c * 255.0f;            // then truncation, as the keypoint colours (post.hip, gather_keypoints)
+  return v >= 255.0f ? 255u : (v > 0.0f ? (uint32_t)v : 0u);
+}
+
+__global__ __launch_bounds__(256) void voxel_clear_kernel(u64* __restrict__ table, long capacity,
+                                                          u64* __restrict__ stats) {
+  const long stride = (long)gridDim.x * 256;
+  for (long s = (long)blockIdx.x * 256 + threadIdx.x; s < capacity; s += stride) {
+    ulonglong2* p = reinterpret_cast<ulonglong2*>(table + 8 * s);
+    p[0] = make_ulonglong2(kEmpty, 0ull);
+    p[1] = make_ulonglong2(0ull, 0ull);
+    p[2] = make_ulonglong2(0ull, 0ull);
+    p[3] = make_ulonglong2(0ull, 0ull);
+  }
+  if (stats && blockIdx.x == 0 && threadIdx.x < 4) stats[threadIdx.x] = 0ull;
+}
+
+__global__ __launch_bounds__(256) void voxel_fuse_pixels_kernel(
+    u64* __restrict__ table, u64 mask, const float* __restrict__ points, const float* __restrict__ conf,
+    const unsigned char* __restrict__ masks, const float* __restrict__ imgs, long n, long HW, float conf_thr,
+    float inv_v, u64* __restrict__ stats) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  bool valid = false, dropped = false;
+  u64 key = kEmpty, v[6] = {0, 0, 0, 0, 0, 0};
+  if (i < n && (!masks || masks[i]) && (!conf || conf[i] > conf_thr)) {
+    uint32_t kx, ky, kz, ux, uy, uz;
+    const float px = points[3 * i], py = points[3 * i + 1], pz = points[3 * i + 2];
+    if (quantise(px, inv_v, kx, ux) && quantise(py, inv_v, ky, uy) && quantise(pz, inv_v, kz, uz)) {
+      valid = true;
+      key = ((u64)kx << 42) | ((u64)ky << 21) | (u64)kz;
+      v[0] = ux; v[1] = uy; v[2] = uz;
+      if (imgs) {
+        const long f = i / HW, p = i - f * HW;
+        const float* im = imgs + 3 * f * HW + p;
+        v[3] = colour_u8(im[0]);
+        v[4] = colour_u8(im[HW]);
+        v[5] = colour_u8(im[2 * HW]);
+      }
+    } else {
+      dropped = true;
+    }
+  }
+  wave_fuse(table, mask, valid, key, 1ull, v, dropped, stats);
+}
+
+__global__ __launch_bounds__(256) void voxel_fuse_points_kernel(
+    u64* __restrict__ table, u64 mask, const float* __restrict__ points, const unsigned char* __restrict__ colors,
+    const int* __restrict__ weights, long n, float inv_v, u64* __restrict__ stats) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  bool valid = false, dropped = false;
+  u64 key = kEmpty, w = 0, v[6] = {0, 0, 0, 0, 0, 0};
+  const int wi = (i < n) ? (weights ? weights[i] : 1) : 0;
+  if (wi > 0) {
+    uint32_t kx, ky, kz, ux, uy, uz;
+    const float px = points[3 * i], py = points[3 * i + 1], pz = points[3 * i + 2];
+    if (quantise(px, inv_v, kx, ux) && quantise(py, inv_v, ky, uy) && quantise(pz, inv_v, kz, uz)) {
+      valid = true;
+      w = (u64)wi;
+      key = ((u64)kx << 42) | ((u64)ky << 21) | (u64)kz;
+      v[0] = w * ux; v[1] = w * uy; v[2] = w * uz;
+      if (colors) {
+        v[3] = w * colors[3 * i];
+        v[4] = w * colors[3 * i + 1];
+        v[5] = w * colors[3 * i + 2];
+      }
+    } else {
+      dropped = true;
+    }
+  }
+  wave_fuse(table, mask, valid, key, w, v, dropped, stats);
+}
+
+__global__ __launch_bounds__(256) void voxel_rehash_kernel(const u64* __restrict__ src, long src_capacity,
+                                                           u64* __restrict__ dst, u64 dst_mask,
+                                                           u64* __restrict__ stats) {
+  const long s = (long)blockIdx.x * 256 + threadIdx.x;
+  if (s >= src_capacity) return;
+  const u64* q = src + 8 * s;
+  if (q[0] == kEmpty) return;
+  if (!slot_add(dst, dst_mask, q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7])) atomicAdd(stats + 1, 1ull);
+}
+
+constexpr int kExtractPer = 16;                 // slots per thread: one output-counter atomic per 4096 slots
+
+// Occupied slots -> output rows.  Each workgroup covers 256 x 16 slots (coalesced: slot = base + j * 256 + tid), counts
+// its occupied ones, claims its rows with ONE atomic on the counter (a per-wave atomic on one address serialised the
+// kernel at ~700 k voxels) and writes them; the order of the rows is arbitrary (the host sorts by key).
+__global__ __launch_bounds__(256) void voxel_extract_kernel(const u64* __restrict__ table, long capacity,
+                                                            double vsize, u64* __restrict__ keys,
+                                                            float* __restrict__ points, unsigned char* __restrict__ colors,
+                                                            int* __restrict__ weights, long max_out,
+                                                            u64* __restrict__ stats) {
+#pragma clang fp contract(off)
+  __shared__ u64 wave_tot[4];
+  __shared__ u64 block_base;
+  const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const long s0 = (long)blockIdx.x * (256L * kExtractPer) + tid;
+  uint32_t occ = 0;
+#pragma unroll
+  for (int j = 0; j < kExtractPer; ++j) {
+    const long s = s0 + 256L * j;
+    if (s < capacity && table[8 * s] != kEmpty) occ |= 1u << j;
+  }
+  const u64 cnt = (u64)__popc(occ);
+  u64 incl = cnt;                                  // inclusive prefix over the wave
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const u64 o = __shfl_up(incl, d, 64);
+    if (lane >= d) incl += o;
+  }
+  if (lane == 63) wave_tot[wv] = incl;
+  __syncthreads();
+  if (tid == 0) {
+    const u64 tot = wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
+    block_base = tot ? atomicAdd(stats + 2, tot) : 0ull;
+  }
+  __syncthreads();
+  u64 at = block_base + incl - cnt;
+  for (int w = 0; w < wv; ++w) at += wave_tot[w];
+#pragma unroll 1
+  for (int j = 0; j < kExtractPer; ++j) {
+    if (!(occ >> j & 1u)) continue;
+    if ((long)at >= max_out) {
+      atomicAdd(stats + 3, 1ull);
+      ++at;
+      continue;
+    }
+    const u64* q = table + 8 * (s0 + 256L * j);
+    const u64 key = q[0], W = q[1];
+    const double den = (double)W * 16777216.0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      const int k = (int)((key >> (42 - 21 * a)) & 0x1FFFFFull) - kBias;
+      const double frac = (double)q[2 + a] / den;
+      points[3 * at + a] = (float)(vsize * ((double)k + frac));
+      colors[3 * at + a] = (unsigned char)((q[5 + a] + W / 2) / W);
+    }
+    keys[at] = key;
+    weights[at] = W > 0x7FFFFFFFull ? 0x7FFFFFFF : (int)W;     // saturated (the centroid and colour use the full W)
+    ++at;
+  }
+}
+
+bool pow2(long c) { return c > 0 && (c & (c - 1)) == 0; }
+
+unsigned blocks_for(long n) { return (unsigned)((n + 255) / 256); }
+
+}  // namespace
+
+extern "C" int pi3_voxel_clear(void* table, long capacity, unsigned long long* stats, void* stream) {
+  if (!table || !pow2(capacity)) {
+    pi3_set_error("pi3_voxel_clear: bad arguments (capacity %ld must be a power of two)", capacity);
+    return PI3_ERR_ARG;
+  }
+  long nb = (capacity + 255) / 256;
+  if (nb > 65536) nb = 65536;
+  hipLaunchKernelGGL(voxel_clear_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, (u64*)table, capacity,
+                     (u64*)stats);
+  return pi3_check_launch("voxel_clear");
+}
+
+extern "C" int pi3_voxel_fuse_pixels(void* table, long capacity, const float* points, const float* conf,
+                                     const unsigned char* masks, const float* imgs, int N, int H, int W,
+                                     float conf_logit_thr, float inv_voxel, unsigned long long* stats, void* stream) {
+  const long n = (long)N * H * W;
+  if (!table || !pow2(capacity) || (n > 0 && !points) || !stats || N < 0 || H <= 0 || W <= 0 || capacity < 2 * n ||
+      !(inv_voxel > 0.0f) || !__builtin_isfinite(inv_voxel)) {
+    pi3_set_error("pi3_voxel_fuse_pixels: bad arguments N=%d H=%d W=%d capacity=%ld inv_voxel=%g", N, H, W, capacity,
+                  (double)inv_voxel);
+    return PI3_ERR_ARG;
+  }
+  if (n == 0) return PI3_OK;
+  hipLaunchKernelGGL(voxel_fuse_pixels_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, (u64*)table,
+                     (u64)(capacity - 1), points, conf, masks, imgs, n, (long)H * W, conf_logit_thr, inv_voxel,
+                     (u64*)stats);
+  return pi3_check_launch("voxel_fuse_pixels");
+}
+
+extern "C" int pi3_voxel_fuse_points(void* table, long capacity, const float* points, const unsigned char* colors,
+                                     const int* weights, long n, float inv_voxel, unsigned long long* stats,
+                                     void* stream) {
+  if (!table || !pow2(capacity) || (n > 0 && !points) || !stats || n < 0 || capacity < 2 * n ||
+      !(inv_voxel > 0.0f) || !__builtin_isfinite(inv_voxel)) {
+    pi3_set_error("pi3_voxel_fuse_points: bad arguments n=%ld capacity=%ld inv_voxel=%g", n, capacity,
+                  (double)inv_voxel);
+    return PI3_ERR_ARG;
+  }
+  if (n == 0) return PI3_OK;
+  hipLaunchKernelGGL(voxel_fuse_points_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, (u64*)table,
+                     (u64)(capacity - 1), points, colors, weights, n, inv_voxel, (u64*)stats);
+  return pi3_check_launch("voxel_fuse_points");
+}
+
+extern "C" int pi3_voxel_rehash(const void* src_table, long src_capacity, void* dst_table, long dst_capacity,
+                                unsigned long long* stats, void* stream) {
+  if (!src_table || !dst_table || !stats || !pow2(src_capacity) || !pow2(dst_capacity) ||
+      dst_capacity < src_capacity || src_table == dst_table) {
+    pi3_set_error("pi3_voxel_rehash: bad arguments %ld -> %ld", src_capacity, dst_capacity);
+    return PI3_ERR_ARG;
+  }
+  hipLaunchKernelGGL(voxel_rehash_kernel, dim3(blocks_for(src_capacity)), dim3(256), 0, (hipStream_t)stream,
+                     (const u64*)src_table, src_capacity, (u64*)dst_table, (u64)(dst_capacity - 1), (u64*)stats);
+  return pi3_check_launch("voxel_rehash");
+}
+
+extern "C" int pi3_voxel_extract(const void* table, long capacity, double voxel_size, unsigned long long* keys,
+                                 float* points, unsigned char* colors, int* weights, long max_out,
+                                 unsigned long long* stats, void* stream) {
+  if (!table || !pow2(capacity) || !keys || !points || !colors || !weights || !stats || max_out < 0 ||
+      !(voxel_size > 0.0) || !__builtin_isfinite(voxel_size)) {
+    pi3_set_error("pi3_voxel_extract: bad arguments capacity=%ld max_out=%ld", capacity, max_out);
+    return PI3_ERR_ARG;
+  }
+  if (hipMemsetAsync(stats + 2, 0, 2 * sizeof(unsigned long long), (hipStream_t)stream) != hipSuccess) {
+    pi3_set_error("pi3_voxel_extract: hipMemsetAsync failed");
+    return PI3_ERR_LAUNCH;
+  }
+  const long span = 256L * kExtractPer;
+  hipLaunchKernelGGL(voxel_extract_kernel, dim3((unsigned)((capacity + span - 1) / span)), dim3(256), 0, (hipStream_t)stream,
+                     (const u64*)table, capacity, voxel_size, (u64*)keys, points, colors, weights, max_out,
+                     (u64*)stats);
+  return pi3_check_launch("voxel_extract");
+}

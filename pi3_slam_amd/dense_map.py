@@ -1,0 +1,170 @@
+"""Dense, confidence-filtered voxel map of a sequence (csrc/voxel.hip).
+
+pi3 predicts a point and a confidence for every pixel of every frame; the sparse outputs keep only the grid-keypoint
+tracks.  Here the dense maps are fused on the device into one voxel per occupied cell of a regular grid:
+
+  stage 1   OfflineChunkCreator (dense_voxel_size set): each chunk's metric pointmap, masked by the creator's masks and
+            `conf > logit(dense_conf_threshold)`, becomes chunk['dense_cloud'] = {points f32 (V,3), colors u8 (V,3),
+            weights i32 (V,), voxel_size, conf_threshold} in the chunk's own frame (VoxelFuser.fuse_pixels);
+  stage 2   fuse_chunk_clouds: every cloud moved by its chunk's accumulated similarity (ops.sim3_apply) and fused again,
+            weighted by W, into the world frame (= chunk 0's frame) -> dense_points.ply.
+
+The accumulators are integers, so a map is bitwise reproducible and tests/dense_map_ref.py reproduces it bit for bit.
+Limitation: a cloud follows its chunk's similarity; per-view corrections of a bundle adjustment do not reach it.
+"""
+from __future__ import annotations
+
+import math
+from typing import Dict, Iterable, Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import ops
+from .alignment import upload
+
+
+def conf_logit_threshold(conf_threshold: float) -> float:
+    """sigmoid(c) > thr  <=>  c > logit(thr): the fp32 logit the pixel test compares the raw confidences with."""
+    t = float(conf_threshold)
+    if t <= 0.0:
+        return float("-inf")
+    if t >= 1.0:
+        return float("inf")
+    return float(np.float32(math.log(t / (1.0 - t))))
+
+
+def inverse_voxel(voxel_size: float) -> float:
+    v = float(voxel_size)
+    if not (v > 0.0 and math.isfinite(v)):
+        raise ValueError(f"voxel size must be a positive finite length, got {voxel_size!r}")
+    return float(np.float32(1.0 / v))
+
+
+def sort_by_key(keys: np.ndarray, points: np.ndarray, colors: np.ndarray, weights: np.ndarray) -> Dict[str, np.ndarray]:
+    """The extract output in ascending key order (the device writes it in slot-claim order)."""
+    order = np.argsort(keys.view(np.uint64))        # keys are unique: every sort kind gives this order
+    return dict(keys=keys[order], points=points[order], colors=colors[order], weights=weights[order])
+
+
+class VoxelFuser:
+    """A device voxel table: fuse_pixels / fuse_points accumulate, extract() returns the sorted voxels.  The table
+    (64 B per slot) is allocated on first use, re-used after clear(), and grows (keeping its contents) when the points
+    fused since the last clear would fill more than half of it."""
+
+    def __init__(self, voxel_size: float, device="cuda", out_sets: int = 1):
+        self.voxel_size = float(voxel_size)
+        self.inv_voxel = inverse_voxel(voxel_size)
+        self.device = torch.device(device)
+        self.table: Optional[torch.Tensor] = None
+        self.capacity = 0
+        self.bound = 0          # candidate points fused since the last clear: an upper bound of the occupied slots
+        self.stats = torch.zeros(4, dtype=torch.int64, device=self.device)
+        # extract output buffers, allocated once and re-used in turn: a caller that reads set k on the host while the
+        # extraction into the next one is queued (the pipelined creator) asks for 2
+        self._outs = [None] * max(1, int(out_sets))
+        self._turn = 0
+
+    def reserve(self, n_more: int) -> None:
+        need = ops.voxel_capacity(self.bound + int(n_more))
+        if self.table is not None and need <= self.capacity:
+            return
+        table = torch.empty(need * 8, dtype=torch.int64, device=self.device)
+        if self.table is None:
+            ops.voxel_clear(table, self.stats)
+        else:
+            keep = self.stats.clone()
+            ops.voxel_clear(table, self.stats)
+            if self.bound > 0:
+                ops.voxel_rehash(self.table, table, self.stats)
+            self.stats.add_(keep)
+        self.table, self.capacity = table, need
+
+    def clear(self) -> None:
+        if self.table is not None:
+            ops.voxel_clear(self.table, self.stats)
+        else:
+            self.stats.zero_()
+        self.bound = 0
+
+    def fuse_pixels(self, points: torch.Tensor, conf: Optional[torch.Tensor], masks: Optional[torch.Tensor],
+                    imgs: Optional[torch.Tensor], conf_threshold: float) -> None:
+        """points (N,H,W,3) f32, conf logits (N,H,W[,1]), masks (N,H,W), imgs (N,3,H,W) f32 in [0, 1]."""
+        n = points.numel() // 3
+        self.reserve(n)
+        if masks is not None and masks.dtype == torch.bool:
+            masks = masks.view(torch.uint8)
+        ops.voxel_fuse_pixels(self.table, self.stats, points, conf, masks, imgs, conf_logit_threshold(conf_threshold),
+                              self.inv_voxel)
+        self.bound += n
+
+    def fuse_points(self, points: torch.Tensor, colors: Optional[torch.Tensor], weights: Optional[torch.Tensor]) -> None:
+        """points (n,3) f32, colors (n,3) uint8, weights (n,) int32 (None: 1)."""
+        n = points.numel() // 3
+        if n == 0:
+            return
+        self.reserve(n)
+        ops.voxel_fuse_points(self.table, self.stats, points, colors, weights, self.inv_voxel)
+        self.bound += n
+
+    def extract_async(self):
+        """Queue the extraction; -> (keys, points, colors, weights) device buffers of self.bound rows and a device copy
+        of the stats (stats[2] = the number of valid rows, stats[0] = dropped points)."""
+        if self.table is None:
+            self.reserve(0)
+        i = self._turn
+        self._turn = (i + 1) % len(self._outs)
+        rows = max(self.bound, 1)
+        if self._outs[i] is None or self._outs[i][0].shape[0] < rows:
+            self._outs[i] = None                 # free the smaller set first
+            self._outs[i] = ops.voxel_empty_outputs(rows, self.device)
+        keys, pts, cols, w = self._outs[i]
+        ops.voxel_extract(self.table, self.stats, self.voxel_size, self.bound, out=(keys, pts, cols, w))
+        return (keys, pts, cols, w), self.stats.clone()
+
+    def extract(self) -> Dict[str, np.ndarray]:
+        """Host arrays in ascending key order: keys u64, points f32 (V,3), colors u8 (V,3), weights i32 (V,); also
+        sets self.last_stats = {'voxels', 'dropped', 'overflow'}."""
+        (keys, pts, cols, w), stats = self.extract_async()
+        st = stats.cpu().numpy()
+        V = int(st[2])
+        self.last_stats = {"voxels": V, "dropped": int(st[0]), "overflow": int(st[1]) + int(st[3])}
+        if self.last_stats["overflow"]:
+            raise RuntimeError(f"voxel table overflow: {self.last_stats}")
+        return sort_by_key(keys[:V].cpu().numpy(), pts[:V].cpu().numpy(), cols[:V].cpu().numpy(), w[:V].cpu().numpy())
+
+
+def chunk_transform(chunk: Dict) -> torch.Tensor:
+    """The 4x4 f64 similarity that moves a chunk's dense cloud into the world frame: the closed-form similarity the
+    chunk was aligned with (kept as '_sim3_dense' when a bundle adjustment re-based the chunk's frame), else its
+    accumulated '_sim3_global', else the identity (chunk 0 / an unaligned chunk: the frame its sparse points are in)."""
+    G = chunk.get("_sim3_dense")
+    if G is None:
+        G = chunk.get("_sim3_global")
+    return torch.eye(4, dtype=torch.float64) if G is None else torch.as_tensor(G, dtype=torch.float64).reshape(4, 4)
+
+
+def fuse_chunk_clouds(chunks: Iterable[Dict], voxel_size: float, device="cuda") -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Every chunk's dense_cloud moved by chunk_transform() and fused, weighted by its voxel weights ->
+    (points f32 (V,3), colors u8 (V,3), weights i32 (V,)) in ascending key order.  Chunks without a cloud are skipped."""
+    device = torch.device(device)
+    clouds = [(c["dense_cloud"], chunk_transform(c)) for c in chunks if c.get("dense_cloud") is not None]
+    fuser = VoxelFuser(voxel_size, device)
+    fuser.reserve(sum(int(cl["points"].shape[0]) for cl, _ in clouds))
+    for cl, G in clouds:
+        if int(cl["points"].shape[0]) == 0:
+            continue
+        pts = upload(torch.as_tensor(cl["points"]).reshape(-1, 3), device, torch.float32).contiguous()
+        if pts.data_ptr() == torch.as_tensor(cl["points"]).data_ptr():
+            pts = pts.clone()
+        ops.sim3_apply(upload(G.reshape(16).contiguous(), device).contiguous(), pts, None)
+        cols = upload(torch.as_tensor(cl["colors"]).reshape(-1, 3), device).contiguous()
+        w = upload(torch.as_tensor(cl["weights"]).reshape(-1), device).contiguous()
+        fuser.fuse_points(pts, cols, w)
+    out = fuser.extract()
+    return out["points"], out["colors"], out["weights"]
+
+
+def write_dense_ply(points: np.ndarray, colors: np.ndarray, path: str) -> None:
+    from .reconstructor import write_ply
+    write_ply(points, np.asarray(colors, np.uint8), path)

@@ -63,6 +63,11 @@ SIGNATURES = {
     "pi3_bundle_adjust_homogeneous": [_vp] * 7 + [_i, _i, _d, _i, _vp, _vp, _vp, _d, _d, _vp, _vp, _l, _vp],
     "pi3_bundle_adjust_inverse_depth": [_vp] * 7 + [_i, _i, _d, _i, _vp, _vp, _vp, _d, _d, _vp, _vp, _l, _vp],
     "pi3_ba_outlier_tracks": [_vp] * 5 + [_i, _i, _d, _d, _vp, _vp],
+    "pi3_voxel_clear": [_vp, _l, _vp, _vp],
+    "pi3_voxel_fuse_pixels": [_vp, _l, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp],
+    "pi3_voxel_fuse_points": [_vp, _l, _vp, _vp, _vp, _l, _f, _vp, _vp],
+    "pi3_voxel_rehash": [_vp, _l, _vp, _l, _vp, _vp],
+    "pi3_voxel_extract": [_vp, _l, _d, _vp, _vp, _vp, _vp, _l, _vp, _vp],
     "pi3_set_knob": [C.c_char_p, _l],
     "pi3_get_knob": [C.c_char_p, C.POINTER(_l)],
     "pi3_unset_knob": [C.c_char_p],

@@ -62,7 +62,8 @@ class Pi3SLAMOnline:
                  do_metric_depth: bool = False, save_debug_projections: bool = False, model_path: Optional[str] = None,
                  use_inverse_depth: bool = False, moge_model=None, moge_model_path: Optional[str] = None,
                  hip_graph: bool = True, output_dir: Optional[str] = None, num_loader_workers: int = 0,
-                 bundle_adjust: bool = True, reuse_overlap_encoder: bool = False):
+                 bundle_adjust: bool = True, reuse_overlap_encoder: bool = False,
+                 dense_voxel_size: Optional[float] = None):
         self.use_inverse_depth = bool(use_inverse_depth)   # online_reconstructor.py:246,1018,1235
         self.chunk_length, self.overlap = int(chunk_length), int(overlap)
         self.pixel_limit = 255000 // 2
@@ -73,7 +74,8 @@ class Pi3SLAMOnline:
             max_num_keypoints=max_num_keypoints, keypoint_detection_threshold=keypoint_detection_threshold,
             estimate_camera_params=estimate_camera_params, num_loader_workers=num_loader_workers,
             pin_memory=num_loader_workers > 0, moge_model_path=moge_model_path, device_resize=True, hip_graph=hip_graph,
-            reuse_overlap_encoder=reuse_overlap_encoder)
+            reuse_overlap_encoder=reuse_overlap_encoder, dense_voxel_size=dense_voxel_size,
+            dense_conf_threshold=conf_threshold)     # --conf_threshold filters the dense map's pixels
         self._creator = OfflineChunkCreator(cfg, model=model, moge_model=moge_model)
         self._creator.undistortion_maps = undistortion_maps
         self.rank, self.world = self._creator.rank, self._creator.world
@@ -204,7 +206,8 @@ class Pi3SLAMOnline:
         stream = self._creator.process_chunks(self._items(ds, mine))
         drain = InOrderDrain()
         results, t_start, frames_before = [], time.time(), len(self.timestamps)
-        keep = ("points", "colors", "keypoints", "masks", "camera_poses", "image_paths", "intrinsics", "_metrics")
+        keep = ("points", "colors", "keypoints", "masks", "camera_poses", "image_paths", "intrinsics", "_metrics",
+                "dense_cloud", "_sim3_global", "_sim3_dense")
         for w0 in range(0, n, world):
             c = w0 + rank
             chunk = None
@@ -292,3 +295,12 @@ class Pi3SLAMOnline:
             sel = np.random.default_rng(0).choice(pts.shape[0], max_points, replace=False)
             pts, cols = pts[sel], (cols[sel] if cols.size else cols)
         write_ply(pts, cols if cols.size else np.ones_like(pts), save_path)
+
+    def save_dense_map(self, save_path: str) -> int:
+        """The chunks' dense clouds (dense_voxel_size set) fused in the world frame -> a PLY; returns the voxel count."""
+        if not any(c.get("dense_cloud") is not None for c in self.chunk_reconstructions):
+            raise RuntimeError("no dense clouds: construct Pi3SLAMOnline with dense_voxel_size")
+        rec = self._exporter()
+        rec.device = str(self.device)
+        n = rec._write_dense_map(save_path)
+        return int(n or 0)

@@ -604,6 +604,85 @@ def ba_outlier_tracks(points: torch.Tensor, poses: torch.Tensor, intr: torch.Ten
     return est.view(N, K).bool()
 
 
+# ---------------------------------------------------------------------------------------------------- voxel map
+VOXEL_SLOT_BYTES = 64       # key, W, U[3], C[3] as uint64 (csrc/voxel.hip)
+
+
+def voxel_capacity(n_candidates: int) -> int:
+    """Slots for n candidate points: the next power of two >= 2 n (the table is never more than half full)."""
+    need = max(2 * int(n_candidates), 1)
+    return 1 << (need - 1).bit_length()
+
+
+def voxel_clear(table: torch.Tensor, stats: torch.Tensor) -> None:
+    lib = _L.load()
+    assert table.dtype == torch.int64 and table.is_contiguous() and table.numel() % 8 == 0
+    assert stats.dtype == torch.int64 and stats.numel() >= 4
+    _L.check(lib.pi3_voxel_clear(table.data_ptr(), table.numel() // 8, stats.data_ptr(), _L.stream_ptr()),
+             "pi3_voxel_clear")
+
+
+def voxel_fuse_pixels(table: torch.Tensor, stats: torch.Tensor, points: torch.Tensor, conf: Optional[torch.Tensor],
+                      masks: Optional[torch.Tensor], imgs: Optional[torch.Tensor], conf_logit_thr: float,
+                      inv_voxel: float) -> None:
+    """points f32 (N,H,W,3), conf f32 logits (N,H,W[,1]), masks uint8/bool (N,H,W), imgs f32 (N,3,H,W)."""
+    lib = _L.load()
+    N, H, W = points.shape[:3]
+    assert points.dtype == torch.float32 and points.is_contiguous() and points.shape[3] == 3
+    assert table.dtype == torch.int64 and table.is_contiguous() and stats.dtype == torch.int64
+    if conf is not None:
+        assert conf.dtype == torch.float32 and conf.is_contiguous() and conf.numel() == N * H * W
+    if masks is not None:
+        assert masks.dtype in (torch.uint8, torch.bool) and masks.is_contiguous() and masks.numel() == N * H * W
+    if imgs is not None:
+        assert imgs.dtype == torch.float32 and imgs.is_contiguous() and tuple(imgs.shape) == (N, 3, H, W)
+    rc = lib.pi3_voxel_fuse_pixels(table.data_ptr(), table.numel() // 8, points.data_ptr(), _L.ptr(conf),
+                                   _L.ptr(masks), _L.ptr(imgs), N, H, W, float(conf_logit_thr), float(inv_voxel),
+                                   stats.data_ptr(), _L.stream_ptr())
+    _L.check(rc, "pi3_voxel_fuse_pixels")
+
+
+def voxel_fuse_points(table: torch.Tensor, stats: torch.Tensor, points: torch.Tensor, colors: Optional[torch.Tensor],
+                      weights: Optional[torch.Tensor], inv_voxel: float) -> None:
+    """points f32 (n,3), colors uint8 (n,3), weights int32 (n,)."""
+    lib = _L.load()
+    assert points.dtype == torch.float32 and points.is_contiguous() and points.shape[-1] == 3
+    n = points.numel() // 3
+    if colors is not None:
+        assert colors.dtype == torch.uint8 and colors.is_contiguous() and colors.numel() == 3 * n
+    if weights is not None:
+        assert weights.dtype == torch.int32 and weights.is_contiguous() and weights.numel() == n
+    rc = lib.pi3_voxel_fuse_points(table.data_ptr(), table.numel() // 8, points.data_ptr(), _L.ptr(colors),
+                                   _L.ptr(weights), n, float(inv_voxel), stats.data_ptr(), _L.stream_ptr())
+    _L.check(rc, "pi3_voxel_fuse_points")
+
+
+def voxel_rehash(src: torch.Tensor, dst: torch.Tensor, stats: torch.Tensor) -> None:
+    lib = _L.load()
+    assert src.dtype == torch.int64 and dst.dtype == torch.int64 and src.is_contiguous() and dst.is_contiguous()
+    _L.check(lib.pi3_voxel_rehash(src.data_ptr(), src.numel() // 8, dst.data_ptr(), dst.numel() // 8, stats.data_ptr(),
+                                  _L.stream_ptr()), "pi3_voxel_rehash")
+
+
+def voxel_empty_outputs(rows: int, device):
+    """Output buffers of voxel_extract: keys int64 (rows,), points f32 (rows,3), colors uint8 (rows,3), weights int32."""
+    m = max(int(rows), 1)
+    return (torch.empty(m, device=device, dtype=torch.int64), torch.empty(m, 3, device=device, dtype=torch.float32),
+            torch.empty(m, 3, device=device, dtype=torch.uint8), torch.empty(m, device=device, dtype=torch.int32))
+
+
+def voxel_extract(table: torch.Tensor, stats: torch.Tensor, voxel_size: float, max_out: int, out=None):
+    """-> device (keys int64, points f32 (,3), colors uint8 (,3), weights int32) with >= max_out rows (`out`, or fresh
+    buffers), unordered; the number of valid entries lands in stats[2]."""
+    lib = _L.load()
+    keys, pts, cols, w = out if out is not None else voxel_empty_outputs(max_out, table.device)
+    assert keys.shape[0] >= max_out and pts.shape[0] >= max_out and cols.shape[0] >= max_out and w.shape[0] >= max_out
+    rc = lib.pi3_voxel_extract(table.data_ptr(), table.numel() // 8, float(voxel_size), keys.data_ptr(), pts.data_ptr(),
+                               cols.data_ptr(), w.data_ptr(), int(max_out), stats.data_ptr(), _L.stream_ptr())
+    _L.check(rc, "pi3_voxel_extract")
+    return keys, pts, cols, w
+
+
 # ---------------------------------------------------------------------------------------------------- device guard
 # Every wrapper launches on torch's CURRENT stream, i.e. on the current device.  A tensor that lives on another card
 # (e.g. 'cuda:0' data in a rank bound to cuda:3) would hand that card's pointers to a kernel running elsewhere: fail

@@ -31,12 +31,16 @@ def _view_name(p) -> str:
 
 
 def write_ply(points: np.ndarray, colors: np.ndarray, path: str) -> None:
-    """Binary little-endian PLY with float xyz + uchar rgb (the layout pi3/utils/basic.py:377-460 writes)."""
+    """Binary little-endian PLY with float xyz + uchar rgb (the layout pi3/utils/basic.py:377-460 writes).  Float colours
+    in [0, 1] are scaled by 255; uint8 colours are written as they are."""
     points = np.asarray(points, np.float32).reshape(-1, 3)
-    colors = np.asarray(colors, np.float32).reshape(-1, 3)
-    if colors.size and colors.max() <= 1.0:
-        colors = colors * 255.0
-    rgb = np.clip(colors, 0, 255).astype(np.uint8)
+    if np.asarray(colors).dtype == np.uint8:
+        rgb = np.asarray(colors).reshape(-1, 3)
+    else:
+        colors = np.asarray(colors, np.float32).reshape(-1, 3)
+        if colors.size and colors.max() <= 1.0:
+            colors = colors * 255.0
+        rgb = np.clip(colors, 0, 255).astype(np.uint8)
     with open(path, "wb") as f:
         f.write((f"ply\nformat binary_little_endian 1.0\nelement vertex {len(points)}\nproperty float x\n"
                  "property float y\nproperty float z\nproperty uchar red\nproperty uchar green\n"
@@ -204,6 +208,23 @@ class OfflineReconstructor:
             self._save_trajectory_tum(os.path.join(self.output_dir, "trajectory_tum.txt"), integer_timestamp=True)
         except Exception as e:  # noqa: BLE001
             print(f"❌ Failed to save TUM trajectory: {e}")
+        try:
+            self._write_dense_map(os.path.join(self.output_dir, "dense_points.ply"))
+        except Exception as e:  # noqa: BLE001
+            print(f"❌ Failed to save the dense map: {e}")
+
+    def _write_dense_map(self, path: str) -> Optional[int]:
+        """dense_points.ply from the chunks' dense clouds (chunks created with a dense voxel size); nothing when no chunk
+        carries one.  The voxel size is chunk 0's: the world frame is chunk 0's frame."""
+        with_cloud = [d for d in self.reconstructions if d.get("dense_cloud") is not None]
+        if not with_cloud:
+            return None
+        from .dense_map import fuse_chunk_clouds, write_dense_ply
+        voxel = float(with_cloud[0]["dense_cloud"]["voxel_size"])
+        pts, cols, _ = fuse_chunk_clouds(self.reconstructions, voxel, getattr(self, "device", "cuda"))
+        write_dense_ply(pts, cols, path)
+        print(f"✅ Saved dense map with {len(pts)} voxels ({voxel} m) to: {path}")
+        return len(pts)
 
     def _run_distributed(self, rank: int, world: int, solve=None) -> None:
         """Chunk-parallel alignment: chunk c lives on rank c % world.  Per wave of `world` chunks:
@@ -250,7 +271,8 @@ class OfflineReconstructor:
                     self._save_chunk(data, c)
                 if self.save_observations:
                     self._save_observations(data, c)
-        keep = ("points", "colors", "keypoints", "masks", "camera_poses", "image_paths", "chunk_order", "alignment_ok")
+        keep = ("points", "colors", "keypoints", "masks", "camera_poses", "image_paths", "chunk_order", "alignment_ok",
+                "dense_cloud", "_sim3_global", "_sim3_dense")
         parts = gather_objects([{k: d[k] for k in keep if k in d} for d in mine])
         if rank == 0:
             self.reconstructions = sorted((d for part in parts for d in part), key=lambda d: d["chunk_order"])
@@ -270,7 +292,8 @@ class OfflineReconstructor:
         self.refinement_stages = ["per_chunk_bundle_adjust", "closed_form_sim3", "prior_constrained_bundle_adjust"]
         print(f"🔄 Reconstructing {n_chunks} chunks from {self.chunk_dir} on {world} ranks (rank {rank}), sequential "
               f"refinement chain (bundle adjustment on)")
-        keep = ("points", "colors", "keypoints", "masks", "camera_poses", "image_paths", "chunk_order", "alignment_ok")
+        keep = ("points", "colors", "keypoints", "masks", "camera_poses", "image_paths", "chunk_order", "alignment_ok",
+                "dense_cloud", "_sim3_global", "_sim3_dense")
         own: Dict[int, Dict] = {}
         done: List[Dict] = []
 

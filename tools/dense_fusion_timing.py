@@ -1,0 +1,141 @@
+"""Cost of the dense voxel map (pi3_slam_amd/dense_map.py, csrc/voxel.hip) at the bench workload.
+
+  1. the kernels of one 100 x 308 x 406 chunk (the chess-room scene's maps with the creator's masks, 2 cm voxels):
+     clear / fuse_pixels / extract, HIP events, median of 20 after 3 warm-up runs;
+  2. creator frames/s with the dense map on and off: two OfflineChunkCreators on the same recipe engine (bench.py's
+     mask edit, device resize of 512x384 uint8 frames, grid keypoints), alternated in one process, 4 chunks per leg after
+     one warm-up chunk per creator, 3 rounds (dense confidence threshold 0.05: see --conf-threshold).
+
+Prints one JSON line.  Usage: python tools/dense_fusion_timing.py [--voxel 0.02] [--rounds 3] [--chunks 4]"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+CL, OV, SRC_H, SRC_W, H, W, KP = 100, 20, 384, 512, 308, 406, 200
+
+
+def synthetic_frames_u8(n: int, h: int, w: int, seed: int) -> torch.Tensor:
+    """bench.py's frames: smooth low-frequency structure + noise, uint8 [n, h, w, 3], pinned."""
+    g = torch.Generator().manual_seed(seed)
+    yy = torch.linspace(0, 1, h)[None, :, None, None]
+    xx = torch.linspace(0, 1, w)[None, None, :, None]
+    ph = torch.rand(n, 1, 1, 3, generator=g) * 6.28
+    img = 0.5 + 0.25 * torch.sin(7 * xx + 3 * yy + ph) * torch.cos(5 * yy - ph) + 0.1 * torch.rand(n, h, w, 3, generator=g)
+    return (img.clamp(0, 1) * 255).to(torch.uint8).contiguous().pin_memory()
+
+
+def kernel_times(voxel: float, dev: str, reps: int = 20):
+    import synth_sequence as ss
+    from pi3_slam_amd.chunk_creator import OfflineChunkCreator
+    from pi3_slam_amd.dense_map import VoxelFuser
+    seq = ss.SyntheticSequence(os.path.join(ROOT, "tests", "golden", "gt_7scenes_chess.txt"), noise=dict(ss.NOISE_BF16))
+    imgs = seq.frames(1, dev)
+    out = ss.SceneEngine(seq)(imgs)
+    masks = OfflineChunkCreator._compute_masks(out)[0].contiguous()
+    pts, conf, im = out["points"][0].contiguous(), out["conf"][0].contiguous(), imgs[0].contiguous()
+    fz = VoxelFuser(voxel, dev)
+    ev = lambda: torch.cuda.Event(enable_timing=True)   # noqa: E731
+    t = {"clear_ms": [], "fuse_pixels_ms": [], "extract_ms": []}
+    for i in range(3 + reps):
+        e = [ev() for _ in range(4)]
+        e[0].record()
+        fz.clear()
+        e[1].record()
+        fz.fuse_pixels(pts, conf, masks, im, 0.5)
+        e[2].record()
+        fz.extract_async()
+        e[3].record()
+        torch.cuda.synchronize()
+        if i >= 3:
+            for k, (a, b) in zip(t, zip(e, e[1:])):
+                t[k].append(a.elapsed_time(b))
+    res = fz.extract()
+    return {k: float(np.median(v)) for k, v in t.items()} | {
+        "voxels": len(res["keys"]), "pixels": int(pts.numel() // 3), "masked_in": int(masks.sum()),
+        "table_slots": fz.capacity, "table_bytes": fz.capacity * 64}
+
+
+def creator_fps(voxel: float, dev: str, rounds: int, chunks: int, conf_threshold: float):
+    from pi3_slam_amd.chunk_creator import OfflineChunkCreator, OfflineCreatorConfig
+    from pi3_slam_amd.engine import Pi3Engine
+    from pi3_slam_amd.weights import Pi3Config
+    engine = Pi3Engine(Pi3Config(), dev)
+    with torch.no_grad():      # bench.py's edit of the plain recipe weights: non-empty masks
+        w_, b_ = engine.w["point_head.proj.weight"], engine.w["point_head.proj.bias"]
+        w_[392:588] = 0.05 * w_[392:393].clone()
+        b_[392:588] = b_[392].clone()
+        engine.w["conf_head.proj.bias"][:196] -= 2.2
+    frames = synthetic_frames_u8(CL, SRC_H, SRC_W, 1234)
+    tmp = tempfile.mkdtemp(prefix="dense_timing_")
+    creators = {}
+    for name, vs in (("off", None), ("on", voxel)):
+        cc = OfflineCreatorConfig(model_path="recipe", output_dir=os.path.join(tmp, name), chunk_length=CL, overlap=OV,
+                                  device=dev, do_metric_depth=False, keypoint_type="grid", max_num_keypoints=KP,
+                                  num_loader_workers=0, device_resize=True, dense_voxel_size=vs,
+                                  dense_conf_threshold=conf_threshold)
+        cr = OfflineChunkCreator(cc, model=engine)
+        cr.target_size = (H, W)
+        creators[name] = cr
+    paths = [[f"frame_{i:06d}.png"] for i in range(CL)]
+
+    def leg(cr, n):
+        items = ({"frames": frames, "kind": "u8", "paths": paths, "meta": {"chunk_index": i}} for i in range(n))
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        voxels = [ch.get("dense_cloud", {}).get("points", torch.zeros(0, 3)).shape[0] for _, ch in cr.process_chunks(items)]
+        torch.cuda.synchronize()
+        return n * CL / (time.perf_counter() - t0), voxels, {k: v / n for k, v in cr.host_seconds.items()}
+
+    for cr in creators.values():
+        leg(cr, 1)                                            # warm-up: first-use allocations, the 2 GiB table
+    fps = {"off": [], "on": []}
+    host = {"off": [], "on": []}
+    voxels = []
+    for _ in range(rounds):
+        for name in ("off", "on"):
+            f, v, hs = leg(creators[name], chunks)
+            fps[name].append(f)
+            host[name].append(hs)
+            if name == "on":
+                voxels = v
+    off, on = float(np.median(fps["off"])), float(np.median(fps["on"]))
+    # host seconds per chunk of the creator's pipeline thread (OfflineChunkCreator.host_seconds): launch = queueing one
+    # chunk's kernels, finish = waiting for its results and building its dict (with the map on: the dense cloud's
+    # copy + key sort, which runs on a thread of its own from the end of the chunk's extraction)
+    host_ms = {name: {k: 1e3 * float(np.median([h[k] for h in host[name]])) for k in host[name][0]} for name in host}
+    return {"fps_off": fps["off"], "fps_on": fps["on"], "median_fps_off": off, "median_fps_on": on,
+            "cost_pct": 100.0 * (off - on) / off, "voxels_per_chunk": voxels[:1], "host_ms_per_chunk": host_ms}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--voxel", type=float, default=0.02)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--chunks", type=int, default=4)
+    ap.add_argument("--conf-threshold", type=float, default=0.05,
+                    help="creator leg: the edited recipe weights put few pixels above sigmoid 0.5; 0.05 lets the "
+                         "creator's masked pixels through, so the fusion does real work")
+    ap.add_argument("--kernels-only", action="store_true")
+    a = ap.parse_args()
+    dev = "cuda:0"
+    torch.cuda.set_device(0)
+    out = {"voxel_size": a.voxel, "kernels": kernel_times(a.voxel, dev)}
+    if not a.kernels_only:
+        out["creator"] = creator_fps(a.voxel, dev, a.rounds, a.chunks, a.conf_threshold)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

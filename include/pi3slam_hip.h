@@ -381,6 +381,28 @@ int pi3_voxel_rehash(const void* src_table, long src_capacity, void* dst_table, 
 int pi3_voxel_extract(const void* table, long capacity, double voxel_size, unsigned long long* keys, float* points,
                       unsigned char* colors, int* weights, long max_out, unsigned long long* stats, void* stream);
 
+/* ---- dense map -> camera views (csrc/render.hip): a z-buffered splat renderer for the voxel map.
+ * points f32 [V][3] (the voxel centroids, in ascending key order), weights int32 [V] (or NULL: every voxel counts),
+ * cams f64 [M][20] = world->camera 3x4 row-major (12), fx, fy, cx, cy, ortho flag (0 / 1), 3 spare.  zbuf uint64
+ * [M][H][W]: filled with all ones (= empty) first; then every voxel does, per camera (f64, no contraction):
+ *   skip when a coordinate is not finite or weights[i] < min_weight;
+ *   xc = ((r00 x + r01 y) + r02 z) + t0, likewise yc, zc;  skip unless near < zc <= far;
+ *   perspective:  u = fx (xc / zc) + cx, v = fy (yc / zc) + cy, r = splat_scale voxel_size fx / zc;
+ *   orthographic: u = fx xc + cx,        v = fy yc + cy,        r = splat_scale voxel_size fx;
+ *   r = min(max(r, 0.5), 16) (a clamp at 16 adds one to stats[1]);
+ *   x0 = max(ceil(u - r), 0), x1 = min(floor(u + r), W - 1), same for y: pixel i has its centre at i; an empty range
+ *   adds one to stats[0];
+ *   every pixel of the footprint: zbuf = min(zbuf, float_bits((float)zc) << 32 | i)   (64-bit atomic).
+ * The image does not depend on the order in which the atomics land.  V < 2^31, M <= 65535.  stats: DEVICE uint64 [4],
+ * accumulated (the caller zeroes them): voxels without a pixel, radius clamps, non-empty pixels (resolve), spare. */
+int pi3_render_splat(const float* points, const int* weights, long V, const double* cams, int M, int H, int W,
+                     double voxel_size, double splat_scale, int min_weight, double near, double far,
+                     unsigned long long* zbuf, unsigned long long* stats, void* stream);
+/* zbuf [M][H][W] + colors uint8 [V][3] -> depth f32 [M][H][W] (0 where empty), color uint8 [M][H][W][3] (0 where
+ * empty), index int32 [M][H][W] (the voxel's row, -1 where empty); stats[2] += the number of non-empty pixels. */
+int pi3_render_resolve(const unsigned long long* zbuf, const unsigned char* colors, long V, int M, int H, int W,
+                       float* depth, unsigned char* color, int* index, unsigned long long* stats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

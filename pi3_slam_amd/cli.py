@@ -52,8 +52,14 @@ RECON_FLAGS: Sequence[Tuple[str, Dict]] = (
     ("--overlap", dict(type=int, default=None)),
     ("--max-observations-per-track", dict(type=int, default=5)),
     ("--device", dict(default="cuda")),
+    # this build's additions
+    ("--render-every", dict(type=int, default=None, help="write renders/depth_<frame>.png (16 bit, millimetres) and "
+                                                         "color_<frame>.png of the dense map for every N-th view")),
+    ("--render-min-weight", dict(type=int, default=1, help="voxels below this fused weight are not drawn")),
+    ("--render-splat-scale", dict(type=float, default=1.0, help="half-width of a drawn voxel in voxel sizes")),
 )
 RECON_SWITCHES = (("--save-per-chunk", "per-chunk ply files as well"),
+                  ("--render-overview", "write renders/overview.png: the dense map from above with the trajectory in red"),
                   ("--use-inverse-depth", "one inverse depth per track along its reference keypoint's ray in both bundle "
                                          "adjustments (utils/chunk_reconstruction.py:187-204; pi3_bundle_adjust_inverse_depth)"),
                   ("--save-observations", "also write the projected track observations"),
@@ -93,6 +99,8 @@ ONLINE_FLAGS: Sequence[Tuple[str, Dict]] = (
     ("--num_workers", dict(type=int, default=4, help="decode threads")),
     ("--dense_voxel_size", dict(type=float, default=None, help="write dense_points.ply: the dense maps filtered by "
                                                                "--conf_threshold, fused into voxels of this size (metres)")),
+    ("--render_every", dict(type=int, default=None, help="with --dense_voxel_size: renders/ with depth and colour images "
+                                                         "of the dense map for every N-th view and an overview")),
 )
 ONLINE_SWITCHES = (("--save_chunk_reconstructions", "save each chunk reconstruction to disk"),
                    ("--save_transformed_reconstructions", "save transformed reconstructions as PLY files"),
@@ -166,7 +174,9 @@ def run_reconstruct(a: argparse.Namespace) -> None:
                          max_observations_per_track=a.max_observations_per_track, save_per_chunk=a.save_per_chunk,
                          use_inverse_depth=a.use_inverse_depth, device=a.device,
                          save_observations=a.save_observations, bundle_adjust=not a.no_bundle_adjust,
-                         ba_sanity_gate=not a.no_ba_sanity_gate).run()
+                         ba_sanity_gate=not a.no_ba_sanity_gate, render_every=a.render_every,
+                         render_overview=a.render_overview, render_min_weight=a.render_min_weight,
+                         render_splat_scale=a.render_splat_scale).run()
 
 
 def online_image_paths(a: argparse.Namespace) -> List[str]:
@@ -222,6 +232,11 @@ def run_online(a: argparse.Namespace) -> None:
     print(f"💾 Saved {ply}" + (f" and {tum}" if a.save_tum else ""))
     if a.dense_voxel_size is not None:
         slam.save_dense_map(os.path.join(out_dir or ".", "dense_points.ply"))
+    if a.render_every is not None:
+        if a.dense_voxel_size is None:
+            print("--render_every needs --dense_voxel_size: no renders")
+        else:
+            slam.save_renders(os.path.join(out_dir or ".", "renders"), every=a.render_every, overview=True)
 
 
 def main(argv=None) -> None:

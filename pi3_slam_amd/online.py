@@ -207,7 +207,7 @@ class Pi3SLAMOnline:
         drain = InOrderDrain()
         results, t_start, frames_before = [], time.time(), len(self.timestamps)
         keep = ("points", "colors", "keypoints", "masks", "camera_poses", "image_paths", "intrinsics", "_metrics",
-                "dense_cloud", "_sim3_global", "_sim3_dense")
+                "dense_cloud", "_sim3_global", "_sim3_dense", "original_width", "original_height")
         for w0 in range(0, n, world):
             c = w0 + rank
             chunk = None
@@ -304,3 +304,13 @@ class Pi3SLAMOnline:
         rec.device = str(self.device)
         n = rec._write_dense_map(save_path)
         return int(n or 0)
+
+    def save_renders(self, out_dir: str, every: Optional[int] = 10, overview: bool = True, min_weight: int = 1,
+                     splat_scale: float = 1.0) -> int:
+        """Depth / colour images of the dense map from every `every`-th view, overview.png and cameras.json under
+        `out_dir` (OfflineReconstructor._write_renders); returns the number of rendered views."""
+        if not any(c.get("dense_cloud") is not None for c in self.chunk_reconstructions):
+            raise RuntimeError("no dense clouds: construct Pi3SLAMOnline with dense_voxel_size")
+        rec = self._exporter()
+        rec.device = str(self.device)
+        return int(rec._write_renders(out_dir, every, overview, min_weight, splat_scale) or 0)

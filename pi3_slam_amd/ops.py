@@ -683,6 +683,57 @@ def voxel_extract(table: torch.Tensor, stats: torch.Tensor, voxel_size: float, m
     return keys, pts, cols, w
 
 
+# ---------------------------------------------------------------------------------------------------- map renderer
+RENDER_CAM_DOUBLES = 20     # world->camera 3x4 row-major, fx, fy, cx, cy, ortho flag, 3 spare (csrc/render.hip)
+
+
+def render_splat(points: torch.Tensor, weights: Optional[torch.Tensor], cams: torch.Tensor, zbuf: torch.Tensor,
+                 stats: torch.Tensor, H: int, W: int, voxel_size: float, splat_scale: float = 1.0, min_weight: int = 1,
+                 near: float = 0.05, far: float = float("inf")) -> None:
+    """points f32 (V,3), weights int32 (V,) or None, cams f64 (M,20) -> zbuf int64 (>= M H W words, the first M H W are
+    cleared and written); stats int64 (4,) accumulates [0] voxels without a pixel and [1] radius clamps."""
+    lib = _L.load()
+    assert points.dtype == torch.float32 and points.is_contiguous() and points.ndim == 2 and points.shape[1] == 3
+    V = int(points.shape[0])
+    if weights is not None:
+        assert weights.dtype == torch.int32 and weights.is_contiguous() and weights.numel() == V
+        assert weights.device == points.device
+    assert cams.dtype == torch.float64 and cams.is_contiguous() and cams.ndim == 2 and cams.shape[1] == RENDER_CAM_DOUBLES
+    M = int(cams.shape[0])
+    assert zbuf.dtype == torch.int64 and zbuf.is_contiguous() and zbuf.numel() >= M * int(H) * int(W)
+    assert stats.dtype == torch.int64 and stats.is_contiguous() and stats.numel() >= 4
+    assert cams.device == points.device and zbuf.device == points.device and stats.device == points.device
+    rc = lib.pi3_render_splat(points.data_ptr(), _L.ptr(weights), V, cams.data_ptr(), M, int(H), int(W), float(voxel_size),
+                              float(splat_scale), int(min_weight), float(near), float(far),
+                              zbuf.data_ptr(), stats.data_ptr(), _L.stream_ptr())
+    _L.check(rc, "pi3_render_splat")
+
+
+def render_resolve(zbuf: torch.Tensor, colors: torch.Tensor, stats: torch.Tensor, M: int, H: int, W: int, out=None):
+    """zbuf int64 (>= M H W) + colors uint8 (V,3) -> (depth f32 (M,H,W), color uint8 (M,H,W,3), index int32 (M,H,W)),
+    `out` or fresh buffers; stats[2] accumulates the non-empty pixels."""
+    lib = _L.load()
+    M, H, W = int(M), int(H), int(W)
+    assert zbuf.dtype == torch.int64 and zbuf.is_contiguous() and zbuf.numel() >= M * H * W
+    assert colors.dtype == torch.uint8 and colors.is_contiguous() and colors.ndim == 2 and colors.shape[1] == 3
+    assert stats.dtype == torch.int64 and stats.is_contiguous() and stats.numel() >= 4
+    assert colors.device == zbuf.device and stats.device == zbuf.device
+    if out is None:
+        out = (torch.empty(M, H, W, device=zbuf.device, dtype=torch.float32),
+               torch.empty(M, H, W, 3, device=zbuf.device, dtype=torch.uint8),
+               torch.empty(M, H, W, device=zbuf.device, dtype=torch.int32))
+    depth, color, index = out
+    assert depth.dtype == torch.float32 and depth.is_contiguous() and depth.numel() == M * H * W
+    assert color.dtype == torch.uint8 and color.is_contiguous() and color.numel() == 3 * M * H * W
+    assert index.dtype == torch.int32 and index.is_contiguous() and index.numel() == M * H * W
+    assert depth.device == zbuf.device and color.device == zbuf.device and index.device == zbuf.device
+    rc = lib.pi3_render_resolve(zbuf.data_ptr(), colors.data_ptr() if colors.numel() else None, int(colors.shape[0]), M, H,
+                                W, depth.data_ptr(), color.data_ptr(), index.data_ptr(), stats.data_ptr(),
+                                _L.stream_ptr())
+    _L.check(rc, "pi3_render_resolve")
+    return depth, color, index
+
+
 # ---------------------------------------------------------------------------------------------------- device guard
 # Every wrapper launches on torch's CURRENT stream, i.e. on the current device.  A tensor that lives on another card
 # (e.g. 'cuda:0' data in a rank bound to cuda:3) would hand that card's pointers to a kernel running elsewhere: fail

@@ -54,8 +54,17 @@ class OfflineReconstructor:
     def __init__(self, chunk_dir: str, output_dir: str, chunk_length: Optional[int] = None,
                  overlap: Optional[int] = None, max_observations_per_track: int = 5, save_per_chunk: bool = False,
                  use_inverse_depth: bool = False, device: str = "cuda", save_observations: bool = False,
-                 bundle_adjust: bool = True, ba_sanity_gate: bool = True, align_estimated_tracks_only: bool = False):
+                 bundle_adjust: bool = True, ba_sanity_gate: bool = True, align_estimated_tracks_only: bool = False,
+                 render_every: Optional[int] = None, render_overview: bool = False, render_min_weight: int = 1,
+                 render_splat_scale: float = 1.0):
         self.chunk_dir, self.output_dir = chunk_dir, output_dir
+        # render_every / render_overview: after dense_points.ply, depth + colour images of the dense map from every N-th
+        # view of the trajectory and a top-down overview, under <output>/renders (pi3_slam_amd/render.py); off by default
+        if render_every is not None and int(render_every) <= 0:
+            raise ValueError(f"render_every must be a positive number of views, got {render_every!r}")
+        self.render_every = int(render_every) if render_every is not None else None
+        self.render_overview = bool(render_overview)
+        self.render_min_weight, self.render_splat_scale = int(render_min_weight), float(render_splat_scale)
         loaded_cl = loaded_ov = None
         try:  # offline_reconstructor.py:32-46
             meta_path = os.path.join(self.chunk_dir, "chunk_metadata.json")
@@ -212,6 +221,12 @@ class OfflineReconstructor:
             self._write_dense_map(os.path.join(self.output_dir, "dense_points.ply"))
         except Exception as e:  # noqa: BLE001
             print(f"❌ Failed to save the dense map: {e}")
+        if getattr(self, "render_every", None) is not None or getattr(self, "render_overview", False):
+            try:
+                self._write_renders(os.path.join(self.output_dir, "renders"), self.render_every, self.render_overview,
+                                    self.render_min_weight, self.render_splat_scale)
+            except Exception as e:  # noqa: BLE001
+                print(f"❌ Failed to save the renders of the dense map: {e}")
 
     def _write_dense_map(self, path: str) -> Optional[int]:
         """dense_points.ply from the chunks' dense clouds (chunks created with a dense voxel size); nothing when no chunk
@@ -221,10 +236,102 @@ class OfflineReconstructor:
             return None
         from .dense_map import fuse_chunk_clouds, write_dense_ply
         voxel = float(with_cloud[0]["dense_cloud"]["voxel_size"])
-        pts, cols, _ = fuse_chunk_clouds(self.reconstructions, voxel, getattr(self, "device", "cuda"))
+        pts, cols, w = fuse_chunk_clouds(self.reconstructions, voxel, getattr(self, "device", "cuda"))
+        self._dense_map = (pts, cols, w, voxel)      # _write_renders draws the same arrays
         write_dense_ply(pts, cols, path)
         print(f"✅ Saved dense map with {len(pts)} voxels ({voxel} m) to: {path}")
         return len(pts)
+
+    def _render_views(self) -> List[Dict]:
+        """The de-duplicated trajectory (first occurrence of a view name wins, as in the TUM export) with what a render
+        needs: name, cam->world pose, the chunk's intrinsics moved to index coordinates, image size."""
+        views, seen = [], set()
+        for d in self.reconstructions:
+            poses = d["camera_poses"].double().numpy()
+            paths = d.get("image_paths") or [f"frame_{i}" for i in range(len(poses))]
+            K = d.get("intrinsics")
+            for i, P in enumerate(poses):
+                name = _view_name(paths[i]) if i < len(paths) else f"view_{i}"
+                if name in seen:
+                    continue
+                seen.add(name)
+                view = {"name": name, "pose": P, "K": None, "H": d.get("original_height"), "W": d.get("original_width")}
+                if K is not None and view["H"] is not None and view["W"] is not None:
+                    Ki = torch.as_tensor(K).double().reshape(-1, 3, 3)[min(i, len(K) - 1)].numpy().copy()
+                    # the chunk says W // 2: the image centre in corner-based coordinates; pixel i has its centre at
+                    # i + 0.5 there and at i in the index coordinates the renderer (and the keypoints) use
+                    Ki[0, 2] -= 0.5
+                    Ki[1, 2] -= 0.5
+                    view["K"], view["H"], view["W"] = Ki, int(view["H"]), int(view["W"])
+                views.append(view)
+        return views
+
+    def _write_renders(self, out_dir: str, every: Optional[int], overview: bool, min_weight: int = 1,
+                       splat_scale: float = 1.0) -> Optional[int]:
+        """<out_dir>/depth_<frame>.png (16 bit, millimetres, 0 = empty) and color_<frame>.png of the dense map for every
+        `every`-th view of the de-duplicated trajectory, overview.png (a top-down orthographic view with the trajectory
+        in red) and cameras.json.  Without dense clouds in the chunks: one line, no directory."""
+        if not any(d.get("dense_cloud") is not None for d in self.reconstructions):
+            print("   ℹ️  No dense clouds in the chunks (create them with a dense voxel size): no renders")
+            return None
+        from .render import DEPTH_PNG_SCALE, MapRenderer, pack_cameras, render_overview, write_color_png, write_depth_png
+        device = getattr(self, "device", "cuda")
+        if getattr(self, "_dense_map", None) is None:
+            from .dense_map import fuse_chunk_clouds
+            voxel = float(next(d for d in self.reconstructions if d.get("dense_cloud") is not None)["dense_cloud"]["voxel_size"])
+            self._dense_map = fuse_chunk_clouds(self.reconstructions, voxel, device) + (voxel,)
+        pts, cols, w, voxel = self._dense_map
+        views = self._render_views()
+        chosen = [v for v in views[:: int(every)] if v["K"] is not None] if every else []
+        if every and not chosen:
+            print("   ℹ️  The chunks carry no intrinsics / image size: no per-view renders")
+        os.makedirs(out_dir, exist_ok=True)
+        t0, t_png = time.time(), 0.0
+        record = {"depth_scale": DEPTH_PNG_SCALE, "voxel_size": voxel, "min_weight": int(min_weight),
+                  "splat_scale": float(splat_scale), "near": 0.05, "views": [], "overview": None}
+        renderer = MapRenderer(pts, cols, w, voxel, device) if chosen else None
+        for size in sorted({(v["H"], v["W"]) for v in chosen}):
+            group = [v for v in chosen if (v["H"], v["W"]) == size]
+            cams = pack_cameras(np.stack([v["pose"] for v in group]), np.stack([v["K"] for v in group]))
+            out = renderer.render(cams, size[0], size[1], min_weight=min_weight, splat_scale=splat_scale, near=0.05)
+            for j, v in enumerate(group):
+                stem = os.path.splitext(v["name"])[0]
+                v["depth"], v["color"] = f"depth_{stem}.png", f"color_{stem}.png"
+                t1 = time.time()
+                write_depth_png(out["depth"][j], os.path.join(out_dir, v["depth"]))
+                write_color_png(out["color"][j], os.path.join(out_dir, v["color"]))
+                t_png += time.time() - t1
+        for v in chosen:
+            K = v["K"]
+            record["views"].append({"frame": v["name"], "pose": [[float(x) for x in row] for row in v["pose"]],
+                                    "fx": float(K[0, 0]), "fy": float(K[1, 1]), "cx": float(K[0, 2]), "cy": float(K[1, 2]),
+                                    "H": v["H"], "W": v["W"], "depth": v["depth"], "color": v["color"]})
+        if overview and views:
+            sized = next((v for v in views if v["K"] is not None), None)
+            H, W = (sized["H"], sized["W"]) if sized else (480, 640)
+            ov = render_overview(pts, cols, w, voxel, np.stack([v["pose"] for v in views]), H, W, min_weight=min_weight,
+                                 splat_scale=splat_scale, device=device)
+            t1 = time.time()
+            write_color_png(ov["color"], os.path.join(out_dir, "overview.png"))
+            t_png += time.time() - t1
+            record["overview"] = {"color": "overview.png", "ortho": True, "near": ov["near"], "H": H, "W": W,
+                                  "pose": [[float(x) for x in row] for row in ov["pose"]],
+                                  "fx": float(ov["K"][0, 0]), "fy": float(ov["K"][1, 1]), "cx": float(ov["K"][0, 2]),
+                                  "cy": float(ov["K"][1, 2])}
+        with open(os.path.join(out_dir, "cameras.json"), "w") as f:
+            json.dump(record, f, indent=1)
+        print(f"✅ Saved {len(chosen)} depth / colour renders" + (" and the overview" if record["overview"] else "")
+              + f" of the dense map to: {out_dir} ({time.time() - t0:.2f}s, {t_png:.2f}s of it PNG encoding)")
+        self.render_seconds = {"total": time.time() - t0, "png": t_png}
+        return len(chosen)
+
+    def _keep_keys(self) -> Tuple[str, ...]:
+        """What rank 0 collects of every chunk; a render also needs the intrinsics and the image size."""
+        keep = ("points", "colors", "keypoints", "masks", "camera_poses", "image_paths", "chunk_order", "alignment_ok",
+                "dense_cloud", "_sim3_global", "_sim3_dense")
+        if self.render_every is not None or self.render_overview:
+            keep += ("intrinsics", "original_width", "original_height")
+        return keep
 
     def _run_distributed(self, rank: int, world: int, solve=None) -> None:
         """Chunk-parallel alignment: chunk c lives on rank c % world.  Per wave of `world` chunks:
@@ -271,8 +378,7 @@ class OfflineReconstructor:
                     self._save_chunk(data, c)
                 if self.save_observations:
                     self._save_observations(data, c)
-        keep = ("points", "colors", "keypoints", "masks", "camera_poses", "image_paths", "chunk_order", "alignment_ok",
-                "dense_cloud", "_sim3_global", "_sim3_dense")
+        keep = self._keep_keys()
         parts = gather_objects([{k: d[k] for k in keep if k in d} for d in mine])
         if rank == 0:
             self.reconstructions = sorted((d for part in parts for d in part), key=lambda d: d["chunk_order"])
@@ -292,8 +398,7 @@ class OfflineReconstructor:
         self.refinement_stages = ["per_chunk_bundle_adjust", "closed_form_sim3", "prior_constrained_bundle_adjust"]
         print(f"🔄 Reconstructing {n_chunks} chunks from {self.chunk_dir} on {world} ranks (rank {rank}), sequential "
               f"refinement chain (bundle adjustment on)")
-        keep = ("points", "colors", "keypoints", "masks", "camera_poses", "image_paths", "chunk_order", "alignment_ok",
-                "dense_cloud", "_sim3_global", "_sim3_dense")
+        keep = self._keep_keys()
         own: Dict[int, Dict] = {}
         done: List[Dict] = []
 

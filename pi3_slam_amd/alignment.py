@@ -45,6 +45,13 @@ def upload(t: torch.Tensor, device, dtype: Optional[torch.dtype] = None) -> torc
     return out if dtype is None or out.dtype == dtype else out.to(dtype)
 
 
+def fresh_upload(t: torch.Tensor, device, dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """A contiguous copy of `t` on `device` that a kernel may overwrite: upload(), cloned when that handed back the
+    source's own memory (a tensor that already sits on `device` in `dtype`)."""
+    out = upload(t, device, dtype).contiguous()
+    return out.clone() if out.data_ptr() == t.data_ptr() else out
+
+
 def _overlap_block(chunk: Dict[str, torch.Tensor], frames: List[int], device) -> Dict[str, torch.Tensor]:
     src = _chunk_frame(chunk)
     out = {}
@@ -152,12 +159,8 @@ def transform_chunk(chunk: Dict, M4: torch.Tensor, device="cuda:0", absolute: bo
         G = ops.sim3_compose_prefix(torch.stack([M4.reshape(16), upload(chunk["_sim3_global"], device).reshape(16)])
                                     .contiguous())[1].reshape(4, 4)
     src = chunk["_chunk_frame"]
-    pts = upload(src["points"], device, torch.float32).contiguous()      # fresh fp32 copies of the originals
-    poses = upload(src["camera_poses"], device, torch.float32).contiguous()
-    if pts.data_ptr() == src["points"].data_ptr():
-        pts = pts.clone()
-    if poses.data_ptr() == src["camera_poses"].data_ptr():
-        poses = poses.clone()
+    pts = fresh_upload(src["points"], device, torch.float32)      # fresh fp32 copies of the originals
+    poses = fresh_upload(src["camera_poses"], device, torch.float32)
     ops.sim3_apply(G.contiguous(), pts, poses)
     chunk["_sim3_global"] = G.cpu()
     chunk["points"] = pts.to(src["points"].device)

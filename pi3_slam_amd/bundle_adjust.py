@@ -174,6 +174,22 @@ def bundle_adjust_chunk(chunk: Dict, W: int, H: int, max_observations_per_track:
     return info
 
 
+def chunk_ba_args(chunk: Dict, max_observations_per_track: int, **settings) -> Optional[Dict]:
+    """What both adjustments of a chunk need besides the chunk (the `bundle_adjust` argument of
+    alignment.align_and_refine_reconstructions); None for a chunk without keypoints.  `settings` override the stage's."""
+    if chunk.get("keypoints") is None:
+        return None
+    # offline_reconstructor.py:66-67: 1920x1080 when a chunk file does not carry its size
+    return {"width": int(chunk.get("original_width", 1920)), "height": int(chunk.get("original_height", 1080)),
+            "max_observations_per_track": max_observations_per_track, "settings": settings}
+
+
+def bundle_adjust_new_chunk(chunk: Dict, args: Dict, device) -> Dict:
+    """The per-chunk stage (PER_CHUNK) with what chunk_ba_args() returned."""
+    return bundle_adjust_chunk(chunk, args["width"], args["height"], args["max_observations_per_track"], device,
+                               dict(PER_CHUNK, **args["settings"]))
+
+
 def overlap_priors(chunk_ref: Dict, view_graph_matches: List[Tuple[int, int]]) -> Dict[int, torch.Tensor]:
     """Pose priors for the query chunk's overlap views = the reference chunk's poses of the same images
     (reconstruction_alignment.py:110-132)."""

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .alignment import upload
+from .alignment import fresh_upload, upload
 
 
 def conf_logit_threshold(conf_threshold: float) -> float:
@@ -154,9 +154,7 @@ def fuse_chunk_clouds(chunks: Iterable[Dict], voxel_size: float, device="cuda") 
     for cl, G in clouds:
         if int(cl["points"].shape[0]) == 0:
             continue
-        pts = upload(torch.as_tensor(cl["points"]).reshape(-1, 3), device, torch.float32).contiguous()
-        if pts.data_ptr() == torch.as_tensor(cl["points"]).data_ptr():
-            pts = pts.clone()
+        pts = fresh_upload(torch.as_tensor(cl["points"]).reshape(-1, 3), device, torch.float32)
         ops.sim3_apply(upload(G.reshape(16).contiguous(), device).contiguous(), pts, None)
         cols = upload(torch.as_tensor(cl["colors"]).reshape(-1, 3), device).contiguous()
         w = upload(torch.as_tensor(cl["weights"]).reshape(-1), device).contiguous()
@@ -166,5 +164,5 @@ def fuse_chunk_clouds(chunks: Iterable[Dict], voxel_size: float, device="cuda") 
 
 
 def write_dense_ply(points: np.ndarray, colors: np.ndarray, path: str) -> None:
-    from .reconstructor import write_ply
+    from .export import write_ply
     write_ply(points, np.asarray(colors, np.uint8), path)

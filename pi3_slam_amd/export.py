@@ -1,0 +1,246 @@
+"""Stage-2 outputs: free functions over a list of aligned chunk dicts (OfflineReconstructor.reconstructions,
+Pi3SLAMOnline.chunk_reconstructions).  Files and formats mirror slam/offline_reconstructor.py:136-255:
+
+  final_points.ply        every track of every chunk (sparse_points_colors)
+  final_camera_poses.ply  every view's camera centre, overlap views twice (all_views)
+  trajectory_tum.txt      the de-duplicated trajectory: first occurrence of a view name wins (unique_views)
+  dense_points.ply        the chunks' dense clouds fused in the world frame (fuse_dense_map; dense_map.py)
+  renders/                depth / colour images of that map, overview.png, cameras.json (write_renders; render.py)
+
+write_outputs writes them all, in that order.  A chunk needs dist.COLLECT_KEYS for it, nothing else."""
+from __future__ import annotations
+
+import json
+import os
+import time
+from typing import Dict, Iterator, List, NamedTuple, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+
+def view_name(p) -> str:
+    """image_paths entries are str, 1-lists or 1-tuples depending on the DataLoader collate/pin path."""
+    while isinstance(p, (list, tuple)):
+        p = p[0] if p else "frame"
+    return os.path.basename(str(p))
+
+
+def write_ply(points: np.ndarray, colors: np.ndarray, path: str) -> None:
+    """Binary little-endian PLY with float xyz + uchar rgb (the layout pi3/utils/basic.py:377-460 writes).  Float colours
+    in [0, 1] are scaled by 255; uint8 colours are written as they are."""
+    points = np.asarray(points, np.float32).reshape(-1, 3)
+    if np.asarray(colors).dtype == np.uint8:
+        rgb = np.asarray(colors).reshape(-1, 3)
+    else:
+        colors = np.asarray(colors, np.float32).reshape(-1, 3)
+        if colors.size and colors.max() <= 1.0:
+            colors = colors * 255.0
+        rgb = np.clip(colors, 0, 255).astype(np.uint8)
+    with open(path, "wb") as f:
+        f.write((f"ply\nformat binary_little_endian 1.0\nelement vertex {len(points)}\nproperty float x\n"
+                 "property float y\nproperty float z\nproperty uchar red\nproperty uchar green\n"
+                 "property uchar blue\nend_header\n").encode())
+        rec = np.empty(len(points), dtype=[("xyz", "<f4", 3), ("rgb", "u1", 3)])
+        rec["xyz"], rec["rgb"] = points, rgb
+        f.write(rec.tobytes())
+
+
+class View(NamedTuple):
+    name: str
+    pose: np.ndarray        # cam->world (4,4) f64
+    chunk: Dict
+    index: int              # of the view in its chunk
+
+
+def all_views(chunks: Sequence[Dict]) -> Iterator[View]:
+    """Every view of every chunk in chunk order; the views two chunks share come once per chunk."""
+    for d in chunks:
+        poses = d["camera_poses"].double().numpy()
+        paths = d.get("image_paths") or [f"frame_{i}" for i in range(len(poses))]
+        for i, P in enumerate(poses):
+            yield View(view_name(paths[i]) if i < len(paths) else f"view_{i}", P, d, i)
+
+
+def unique_views(chunks: Sequence[Dict]) -> Iterator[View]:
+    """First occurrence of each view name wins (offline_reconstructor.py:218-229)."""
+    seen = set()
+    for v in all_views(chunks):
+        if v.name not in seen:
+            seen.add(v.name)
+            yield v
+
+
+def sparse_points_colors(chunks: Sequence[Dict]) -> Tuple[np.ndarray, np.ndarray]:
+    """offline_reconstructor.py:170-193: every track of every chunk (no de-duplication)."""
+    pts, cols = [], []
+    for d in chunks:
+        if "keypoints" not in d:
+            continue
+        pts.append(d["points"].float().reshape(-1, 3).numpy())
+        if "colors" in d and d["colors"] is not None:
+            cols.append(d["colors"].float().reshape(-1, 3).numpy())
+    if not pts:
+        return np.array([]), np.array([])
+    P = np.concatenate(pts, 0)
+    C = np.concatenate(cols, 0) if cols else np.array([])
+    if C.size > 0 and C.max() > 1.0:
+        C = C / 255.0
+    return P.astype(np.float32), C.astype(np.float32)
+
+
+def save_trajectory_tum(chunks: Sequence[Dict], save_path: str, integer_timestamp: bool = True) -> None:
+    """TUM format of offline_reconstructor.py:231-255 ("{i} {x:.6f} ... {qw:.6f}"), from fp32 poses."""
+    from scipy.spatial.transform import Rotation
+    poses = [v.pose.astype(np.float32) for v in unique_views(chunks)]
+    if not poses:
+        print("No camera trajectory available to save from reconstructions")
+        return
+    os.makedirs(os.path.dirname(save_path) or ".", exist_ok=True)
+    with open(save_path, "w") as f:
+        f.write("# timestamp tx ty tz qx qy qz qw\n")
+        for i, P in enumerate(poses):
+            x, y, z = P[:3, 3]
+            qx, qy, qz, qw = Rotation.from_matrix(P[:3, :3].astype(np.float64)).as_quat()
+            ts = f"{i}" if integer_timestamp else f"{float(i):.9f}"
+            f.write(f"{ts} {x:.6f} {y:.6f} {z:.6f} {qx:.6f} {qy:.6f} {qz:.6f} {qw:.6f}\n")
+    print(f"✅ Saved trajectory with {len(poses)} poses to: {save_path}")
+
+
+def render_views(chunks: Sequence[Dict]) -> List[Dict]:
+    """The de-duplicated trajectory with what a render needs: name, cam->world pose, the chunk's intrinsics moved to
+    index coordinates, image size."""
+    views = []
+    for name, P, d, i in unique_views(chunks):
+        K = d.get("intrinsics")
+        view = {"name": name, "pose": P, "K": None, "H": d.get("original_height"), "W": d.get("original_width")}
+        if K is not None and view["H"] is not None and view["W"] is not None:
+            Ki = torch.as_tensor(K).double().reshape(-1, 3, 3)[min(i, len(K) - 1)].numpy().copy()
+            # the chunk says W // 2: the image centre in corner-based coordinates; pixel i has its centre at
+            # i + 0.5 there and at i in the index coordinates the renderer (and the keypoints) use
+            Ki[0, 2] -= 0.5
+            Ki[1, 2] -= 0.5
+            view["K"], view["H"], view["W"] = Ki, int(view["H"]), int(view["W"])
+        views.append(view)
+    return views
+
+
+class DenseMap(NamedTuple):
+    points: np.ndarray      # f32 (V,3), ascending key order
+    colors: np.ndarray      # u8 (V,3)
+    weights: np.ndarray     # i32 (V,)
+    voxel_size: float
+
+
+def fuse_dense_map(chunks: Sequence[Dict], device) -> Optional[DenseMap]:
+    """The chunks' dense clouds (chunks created with a dense voxel size) fused in the world frame; None when no chunk
+    carries one.  The voxel size is the first cloud's: the world frame is chunk 0's frame."""
+    first = next((d["dense_cloud"] for d in chunks if d.get("dense_cloud") is not None), None)
+    if first is None:
+        return None
+    from .dense_map import fuse_chunk_clouds
+    voxel = float(first["voxel_size"])
+    return DenseMap(*fuse_chunk_clouds(chunks, voxel, device), voxel)
+
+
+def write_dense_points(dense: DenseMap, path: str) -> int:
+    """dense_points.ply; returns the voxel count."""
+    write_ply(dense.points, np.asarray(dense.colors, np.uint8), path)
+    print(f"✅ Saved dense map with {len(dense.points)} voxels ({dense.voxel_size} m) to: {path}")
+    return len(dense.points)
+
+
+def write_renders(chunks: Sequence[Dict], dense: Optional[DenseMap], out_dir: str, every: Optional[int], overview: bool,
+                  min_weight: int = 1, splat_scale: float = 1.0, device="cuda") -> Optional[Tuple[int, Dict[str, float]]]:
+    """<out_dir>/depth_<frame>.png (16 bit, millimetres, 0 = empty) and color_<frame>.png of the dense map for every
+    `every`-th view of the de-duplicated trajectory, overview.png (a top-down orthographic view with the trajectory
+    in red) and cameras.json -> (rendered views, {'total', 'png'} seconds).  `dense`: the map a caller has already fused
+    (else it is fused here).  Without dense clouds in the chunks: one line, no directory, None."""
+    if dense is None:
+        dense = fuse_dense_map(chunks, device)
+    if dense is None:
+        print("   ℹ️  No dense clouds in the chunks (create them with a dense voxel size): no renders")
+        return None
+    from .render import DEPTH_PNG_SCALE, MapRenderer, pack_cameras, render_overview, write_color_png, write_depth_png
+    pts, cols, w, voxel = dense
+    views = render_views(chunks)
+    chosen = [v for v in views[:: int(every)] if v["K"] is not None] if every else []
+    if every and not chosen:
+        print("   ℹ️  The chunks carry no intrinsics / image size: no per-view renders")
+    os.makedirs(out_dir, exist_ok=True)
+    t0, t_png = time.time(), 0.0
+    record = {"depth_scale": DEPTH_PNG_SCALE, "voxel_size": voxel, "min_weight": int(min_weight),
+              "splat_scale": float(splat_scale), "near": 0.05, "views": [], "overview": None}
+    renderer = MapRenderer(pts, cols, w, voxel, device) if chosen else None
+    for size in sorted({(v["H"], v["W"]) for v in chosen}):
+        group = [v for v in chosen if (v["H"], v["W"]) == size]
+        cams = pack_cameras(np.stack([v["pose"] for v in group]), np.stack([v["K"] for v in group]))
+        out = renderer.render(cams, size[0], size[1], min_weight=min_weight, splat_scale=splat_scale, near=0.05)
+        for j, v in enumerate(group):
+            stem = os.path.splitext(v["name"])[0]
+            v["depth"], v["color"] = f"depth_{stem}.png", f"color_{stem}.png"
+            t1 = time.time()
+            write_depth_png(out["depth"][j], os.path.join(out_dir, v["depth"]))
+            write_color_png(out["color"][j], os.path.join(out_dir, v["color"]))
+            t_png += time.time() - t1
+    for v in chosen:
+        K = v["K"]
+        record["views"].append({"frame": v["name"], "pose": [[float(x) for x in row] for row in v["pose"]],
+                                "fx": float(K[0, 0]), "fy": float(K[1, 1]), "cx": float(K[0, 2]), "cy": float(K[1, 2]),
+                                "H": v["H"], "W": v["W"], "depth": v["depth"], "color": v["color"]})
+    if overview and views:
+        sized = next((v for v in views if v["K"] is not None), None)
+        H, W = (sized["H"], sized["W"]) if sized else (480, 640)
+        ov = render_overview(pts, cols, w, voxel, np.stack([v["pose"] for v in views]), H, W, min_weight=min_weight,
+                             splat_scale=splat_scale, device=device)
+        t1 = time.time()
+        write_color_png(ov["color"], os.path.join(out_dir, "overview.png"))
+        t_png += time.time() - t1
+        record["overview"] = {"color": "overview.png", "ortho": True, "near": ov["near"], "H": H, "W": W,
+                              "pose": [[float(x) for x in row] for row in ov["pose"]],
+                              "fx": float(ov["K"][0, 0]), "fy": float(ov["K"][1, 1]), "cx": float(ov["K"][0, 2]),
+                              "cy": float(ov["K"][1, 2])}
+    with open(os.path.join(out_dir, "cameras.json"), "w") as f:
+        json.dump(record, f, indent=1)
+    print(f"✅ Saved {len(chosen)} depth / colour renders" + (" and the overview" if record["overview"] else "")
+          + f" of the dense map to: {out_dir} ({time.time() - t0:.2f}s, {t_png:.2f}s of it PNG encoding)")
+    return len(chosen), {"total": time.time() - t0, "png": t_png}
+
+
+def write_outputs(chunks: Sequence[Dict], output_dir: str, device="cuda", render_every: Optional[int] = None,
+                  render_overview: bool = False, render_min_weight: int = 1,
+                  render_splat_scale: float = 1.0) -> Optional[Dict[str, float]]:
+    """Every output file of stage 2 under output_dir; a file that fails is reported and the others are still written.
+    Returns the seconds of write_renders when renders were written."""
+    try:
+        pts, cols = sparse_points_colors(chunks)
+        if pts.size > 0:
+            write_ply(pts, cols if cols.size else np.ones_like(pts), os.path.join(output_dir, "final_points.ply"))
+    except Exception as e:  # noqa: BLE001
+        print(f"❌ Failed to save final PLY: {e}")
+    try:
+        cam = np.asarray([v.pose[:3, 3] for v in all_views(chunks)], np.float32)
+        if len(cam):
+            write_ply(cam, np.tile(np.array([[1.0, 0.0, 0.0]], np.float32), (len(cam), 1)),
+                      os.path.join(output_dir, "final_camera_poses.ply"))
+    except Exception as e:  # noqa: BLE001
+        print(f"❌ Failed to save camera trajectory PLY: {e}")
+    try:
+        save_trajectory_tum(chunks, os.path.join(output_dir, "trajectory_tum.txt"), integer_timestamp=True)
+    except Exception as e:  # noqa: BLE001
+        print(f"❌ Failed to save TUM trajectory: {e}")
+    dense = None
+    try:
+        dense = fuse_dense_map(chunks, device)
+        if dense is not None:
+            write_dense_points(dense, os.path.join(output_dir, "dense_points.ply"))
+    except Exception as e:  # noqa: BLE001
+        print(f"❌ Failed to save the dense map: {e}")
+    if render_every is not None or render_overview:
+        try:       # the renders draw the map that was just fused for the PLY
+            done = write_renders(chunks, dense, os.path.join(output_dir, "renders"), render_every, render_overview,
+                                 render_min_weight, render_splat_scale, device)
+            return done[1] if done else None
+        except Exception as e:  # noqa: BLE001
+            print(f"❌ Failed to save the renders of the dense map: {e}")
+    return None

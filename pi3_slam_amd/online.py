@@ -24,10 +24,11 @@ from typing import Dict, Iterator, List, Optional, Tuple
 import numpy as np
 import torch
 
+from . import export
 from .alignment import align_and_refine_reconstructions, create_view_graph_matches, transform_chunk
+from .bundle_adjust import bundle_adjust_new_chunk, chunk_ba_args
 from .chunk_creator import OfflineChunkCreator, OfflineCreatorConfig
 from .image_io import ChunkImageDataset, calculate_target_size
-from .reconstructor import OfflineReconstructor
 
 
 class InOrderDrain:
@@ -114,21 +115,17 @@ class Pi3SLAMOnline:
         return self._consume(chunk)
 
     def _ba_args(self, chunk: Dict) -> Optional[Dict]:
-        if not self.bundle_adjust or chunk.get("keypoints") is None:
+        if not self.bundle_adjust:
             return None
-        return {"width": int(chunk.get("original_width", 1920)), "height": int(chunk.get("original_height", 1080)),
-                "max_observations_per_track": self.max_observations_per_track,
-                "settings": {"inverse_depth": self.use_inverse_depth}}
+        return chunk_ba_args(chunk, self.max_observations_per_track, inverse_depth=self.use_inverse_depth)
 
     def _refine_new_chunk(self, chunk: Dict) -> None:
         args = self._ba_args(chunk)
         if args is None:
             return
-        from .bundle_adjust import PER_CHUNK, bundle_adjust_chunk
         t0 = time.time()
         with torch.cuda.stream(self._align_stream):
-            bundle_adjust_chunk(chunk, args["width"], args["height"], args["max_observations_per_track"],
-                                str(self.device), dict(PER_CHUNK, **args["settings"]))
+            bundle_adjust_new_chunk(chunk, args, str(self.device))
         self._record_timing("bundle_adjust_chunk", time.time() - t0)
 
     def _consume(self, chunk: Dict) -> Dict:
@@ -198,7 +195,7 @@ class Pi3SLAMOnline:
         in chunk order."""
         import torch.distributed as dist
 
-        from .dist import WaveAligner, chain_payload, chain_step, gather_objects
+        from .dist import COLLECT_KEYS, WaveAligner, chain_payload, chain_step, gather_objects
         rank, world, n = self.rank, self.world, len(ds)
         aligner = WaveAligner(rank, world, self.overlap, self.chunk_length, str(self.device))
         prev_payload: Optional[Dict] = None        # bundle adjustment on: the refined predecessor (dist.chain_step)
@@ -206,8 +203,6 @@ class Pi3SLAMOnline:
         stream = self._creator.process_chunks(self._items(ds, mine))
         drain = InOrderDrain()
         results, t_start, frames_before = [], time.time(), len(self.timestamps)
-        keep = ("points", "colors", "keypoints", "masks", "camera_poses", "image_paths", "intrinsics", "_metrics",
-                "dense_cloud", "_sim3_global", "_sim3_dense", "original_width", "original_height")
         for w0 in range(0, n, world):
             c = w0 + rank
             chunk = None
@@ -239,7 +234,7 @@ class Pi3SLAMOnline:
                     Gs, oks = aligner.step(chunk, w0, n)
                     if chunk is not None:
                         transform_chunk(chunk, Gs[rank], device=str(self.device), absolute=True)
-            payload = None if chunk is None else (c, {k: chunk[k] for k in keep if k in chunk}, bool(oks[rank]),
+            payload = None if chunk is None else (c, {k: chunk[k] for k in COLLECT_KEYS if k in chunk}, bool(oks[rank]),
                                                   Gs[rank])
             parts = gather_objects(payload)
             if rank == 0:
@@ -279,38 +274,30 @@ class Pi3SLAMOnline:
         return {"num_chunks": len(self.chunk_reconstructions), "num_frames": len(self.timestamps),
                 "timing": self.get_timing_statistics()}
 
-    def _exporter(self) -> OfflineReconstructor:
-        rec = OfflineReconstructor.__new__(OfflineReconstructor)
-        rec.reconstructions, rec.output_dir = self.chunk_reconstructions, self.output_dir
-        return rec
-
     def save_trajectory_tum(self, save_path: str, timestamps: Optional[List[float]] = None,
                             integer_timestamp: bool = False) -> None:
-        self._exporter()._save_trajectory_tum(save_path, integer_timestamp=integer_timestamp)
+        export.save_trajectory_tum(self.chunk_reconstructions, save_path, integer_timestamp=integer_timestamp)
 
     def save_final_result(self, save_path: str, max_points: int = 1000000) -> None:
-        from .reconstructor import write_ply
-        pts, cols = self._exporter()._extract_points_colors()
+        pts, cols = export.sparse_points_colors(self.chunk_reconstructions)
         if pts.shape[0] > max_points:
             sel = np.random.default_rng(0).choice(pts.shape[0], max_points, replace=False)
             pts, cols = pts[sel], (cols[sel] if cols.size else cols)
-        write_ply(pts, cols if cols.size else np.ones_like(pts), save_path)
+        export.write_ply(pts, cols if cols.size else np.ones_like(pts), save_path)
+
+    def _fused_map(self) -> export.DenseMap:
+        dense = export.fuse_dense_map(self.chunk_reconstructions, str(self.device))
+        if dense is None:
+            raise RuntimeError("no dense clouds: construct Pi3SLAMOnline with dense_voxel_size")
+        return dense
 
     def save_dense_map(self, save_path: str) -> int:
         """The chunks' dense clouds (dense_voxel_size set) fused in the world frame -> a PLY; returns the voxel count."""
-        if not any(c.get("dense_cloud") is not None for c in self.chunk_reconstructions):
-            raise RuntimeError("no dense clouds: construct Pi3SLAMOnline with dense_voxel_size")
-        rec = self._exporter()
-        rec.device = str(self.device)
-        n = rec._write_dense_map(save_path)
-        return int(n or 0)
+        return export.write_dense_points(self._fused_map(), save_path)
 
     def save_renders(self, out_dir: str, every: Optional[int] = 10, overview: bool = True, min_weight: int = 1,
                      splat_scale: float = 1.0) -> int:
         """Depth / colour images of the dense map from every `every`-th view, overview.png and cameras.json under
-        `out_dir` (OfflineReconstructor._write_renders); returns the number of rendered views."""
-        if not any(c.get("dense_cloud") is not None for c in self.chunk_reconstructions):
-            raise RuntimeError("no dense clouds: construct Pi3SLAMOnline with dense_voxel_size")
-        rec = self._exporter()
-        rec.device = str(self.device)
-        return int(rec._write_renders(out_dir, every, overview, min_weight, splat_scale) or 0)
+        `out_dir` (export.write_renders); returns the number of rendered views."""
+        return export.write_renders(self.chunk_reconstructions, self._fused_map(), out_dir, every, overview,
+                                    min_weight, splat_scale, str(self.device))[0]

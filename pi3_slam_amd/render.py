@@ -31,13 +31,17 @@ ZBUF_BATCH_BYTES = 64 << 20
 DEPTH_PNG_SCALE = 1000.0
 
 
+def _np(x, dtype) -> np.ndarray:
+    """A tensor (any device) or an array-like as a host array of `dtype`."""
+    return np.asarray(x.detach().cpu().numpy() if torch.is_tensor(x) else x, dtype)
+
+
 def pack_cameras(poses_c2w, K, ortho=False) -> np.ndarray:
     """cam->world poses (M,4,4) (or one (4,4)), K (3,3) or (M,3,3) in index coordinates -> f64 (M,20): world->camera
     3x4 row-major, fx, fy, cx, cy, ortho flag, 3 spare.  A scale in the 3x3 block (a pose that went through a
     similarity) is divided out, so world->camera is rigid and depths are in map units."""
-    P = np.asarray(torch.as_tensor(poses_c2w).detach().cpu().numpy() if torch.is_tensor(poses_c2w) else poses_c2w,
-                   np.float64).reshape(-1, 4, 4)
-    Km = np.asarray(torch.as_tensor(K).detach().cpu().numpy() if torch.is_tensor(K) else K, np.float64)
+    P = _np(poses_c2w, np.float64).reshape(-1, 4, 4)
+    Km = _np(K, np.float64)
     M = P.shape[0]
     Km = np.broadcast_to(Km.reshape(-1, 3, 3), (M, 3, 3))
     A = P[:, :3, :3]
@@ -121,10 +125,8 @@ def overview_camera(poses_c2w, points, H: int, W: int, near: float = 0.05, margi
     the map in the image plane, widened to hold every camera centre, at one scale for both axes.  Seen from above, a
     room shows its ceiling first: the camera sits so that its `near` plane lies `margin` above the highest camera
     centre, which cuts away everything over the trajectory (render with the same `near`)."""
-    P = np.asarray(torch.as_tensor(poses_c2w).detach().cpu().numpy() if torch.is_tensor(poses_c2w) else poses_c2w,
-                   np.float64).reshape(-1, 4, 4)
-    X = np.asarray(torch.as_tensor(points).detach().cpu().numpy() if torch.is_tensor(points) else points,
-                   np.float64).reshape(-1, 3)
+    P = _np(poses_c2w, np.float64).reshape(-1, 4, 4)
+    X = _np(points, np.float64).reshape(-1, 3)
     X = X[np.isfinite(X).all(1)]
     C = P[:, :3, 3]
     down = P[:, :3, 1] / np.maximum(np.linalg.norm(P[:, :3, 1], axis=1, keepdims=True), 1e-300)
@@ -156,8 +158,7 @@ def render_overview(points, colors, weights, voxel_size: float, poses_c2w, H: in
                     splat_scale: float = 1.0, near: float = 0.05, device="cuda") -> Dict:
     """The map seen through overview_camera, with the camera centres appended as red voxels of weight `min_weight` (so
     the trajectory is drawn by the same kernel) -> {'color' u8 (H,W,3), 'depth', 'index', 'pose', 'K', 'near'}."""
-    P = np.asarray(torch.as_tensor(poses_c2w).detach().cpu().numpy() if torch.is_tensor(poses_c2w) else poses_c2w,
-                   np.float64).reshape(-1, 4, 4)
+    P = _np(poses_c2w, np.float64).reshape(-1, 4, 4)
     pts = np.asarray(points, np.float32).reshape(-1, 3)
     pose, K = overview_camera(P, pts, H, W, near=near)
     n = len(P)
@@ -175,7 +176,7 @@ def render_overview(points, colors, weights, voxel_size: float, poses_c2w, H: in
 def depth_to_u16(depth, scale: float = DEPTH_PNG_SCALE) -> np.ndarray:
     """depth (H,W) in map units -> uint16 of round(depth * scale) (half to even, f64), saturating at 65535; empty
     pixels (0, or not finite) stay 0."""
-    d = np.asarray(torch.as_tensor(depth).detach().cpu().numpy() if torch.is_tensor(depth) else depth, np.float64)
+    d = _np(depth, np.float64)
     d = np.where(np.isfinite(d) & (d > 0.0), d, 0.0)
     return np.minimum(np.rint(d * float(scale)), 65535.0).astype(np.uint16)
 
@@ -188,5 +189,5 @@ def write_depth_png(depth, path: str, scale: float = DEPTH_PNG_SCALE) -> None:
 
 def write_color_png(color, path: str) -> None:
     from PIL import Image
-    c = np.asarray(torch.as_tensor(color).detach().cpu().numpy() if torch.is_tensor(color) else color, np.uint8)
+    c = _np(color, np.uint8)
     Image.fromarray(np.ascontiguousarray(c.reshape(c.shape[0], c.shape[1], 3))).save(path, format="PNG")

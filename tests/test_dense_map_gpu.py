@@ -223,7 +223,7 @@ def _oracle_world(chunks, voxel):
 
 
 def _ply_bytes(points, colors, path):
-    from pi3_slam_amd.reconstructor import write_ply
+    from pi3_slam_amd.export import write_ply
     write_ply(points, np.asarray(colors, np.uint8), path)
     return open(path, "rb").read()
 

@@ -136,8 +136,8 @@ def test_overlapped_stages_write_the_same_chunk_files(tmp_path, built_lib):
                 assert ca[k].dtype == cb[k].dtype and torch.equal(ca[k], cb[k]), k
         for k in ca["camera_params"]:
             assert torch.equal(ca["camera_params"][k], cb["camera_params"][k]), k
-        from pi3_slam_amd.reconstructor import _view_name      # 1-tuples (collate) vs 1-lists (collate + pin): SURVEY §8b
-        assert [_view_name(p) for p in ca["image_paths"]] == [_view_name(p) for p in cb["image_paths"]]
+        from pi3_slam_amd.export import view_name      # 1-tuples (collate) vs 1-lists (collate + pin): SURVEY §8b
+        assert [view_name(p) for p in ca["image_paths"]] == [view_name(p) for p in cb["image_paths"]]
         assert ca["chunk_index"] == cb["chunk_index"]
         assert ca["_metrics"]["metric_scale"] == cb["_metrics"]["metric_scale"]
 
@@ -312,7 +312,7 @@ def test_reconstruct_with_bundle_adjust_under_torchrun_equals_single_process(tmp
     """`reconstruct` under torch.distributed.run with bundle adjustment on (the default).  The reference's flow is
     strictly sequential (slam/offline_reconstructor.py:130-133: align chunk c to the already refined chunk c-1, then the
     prior-constrained BA of utils/reconstruction_alignment.py:107-171), so the chunk-parallel run takes the ranks in
-    turn for that chain (reconstructor._run_distributed_chain: per-chunk BA in parallel, then alignment + prior BA in
+    turn for that chain (reconstructor._run_chain: per-chunk BA in parallel, then alignment + prior BA in
     chunk order, the refined chunk handed to the next owner): all three stages run and the trajectory equals the
     single-process one (round 2 skipped the prior-constrained stage under torchrun and differed silently).  Five
     overlapping cuts of one synthetic scene, each in its own similarity frame; both recover the ground truth."""

@@ -346,7 +346,8 @@ def test_stage_two_without_dense_clouds_writes_no_renders(tmp_path, capsys):
     assert os.path.exists(tmp_path / "out" / "trajectory_tum.txt")
     assert not os.path.exists(tmp_path / "out" / "renders") and not os.path.exists(tmp_path / "out" / "dense_points.ply")
     assert "no renders" in capsys.readouterr().out
-    views = rec._render_views()
+    from pi3_slam_amd import export
+    views = export.render_views(rec.reconstructions)
     assert len(views) == 80 and views[0]["H"] == seq.H and views[0]["W"] == seq.W
     assert views[3]["K"][0, 2] == seq.W // 2 - 0.5 == seq.cx and views[3]["K"][1, 2] == seq.H // 2 - 0.5 == seq.cy
 

@@ -21,7 +21,8 @@
 // exceed it take the online-max loop, so the result is the same softmax for every input.  max |k|^2 per (batch, head)
 // comes from a ~30 us pre-pass over K (a64_knorm_kernel).
 //
-// What the loop is bound by (s_memtime stamps, build with -DPI3_ATTN_STAMPS; 2.05 GHz under load): per tile and SIMD,
+// What the loop is bound by (s_memtime stamps around the phases of a tile, 2.05 GHz under load; the stamp code is gone,
+// the row "where a workgroup's 24.5 us go" of profiles/EXPERIMENTS.md names the last tree that has it): per tile and SIMD,
 // QK^T of the two resident waves = 32 MFMAs = 1012 cycles with the VALU idle, then softmax + PV = ~2400 cycles bound by
 // VALU issue (64 v_exp at 8 cycles, 32 cvt_pk, MFMA issue slots) with the matrix pipe half idle.  Tried and measured
 // slower than this kernel, so not kept: (a) ping-pong halves (waves 0-3 in QK^T while waves 4-7 are in softmax + PV,
@@ -41,30 +42,9 @@
 // what this form could still give.
 #include "common.h"
 #include <stdlib.h>
-#include <stdio.h>
 
 #include "attn64_params.h"
-#ifndef A64_ABL   // development builds only (-DA64_ABL=n, a separate .so): timing ablations with WRONG results.
-#define A64_ABL 0   // 1 no exp, 3 no P.V MFMAs, 4 no Q.K^T MFMAs, 5 no barrier / DMA wait, 6 no row-sum MFMAs, 7 one LDS fragment reused
-#endif
 #define A64_BOUND2 8100.0f   // (90)^2: p in [2^-90, 2^90], l <= 2^106, O <= 2^110: inside fp32 / bf16 range
-#ifdef PI3_ATTN_STAMPS
-__device__ __forceinline__ unsigned long long a64_stamp() {
-  unsigned long long t;
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  __builtin_amdgcn_sched_barrier(0);
-  return t;
-}
-__device__ __forceinline__ unsigned long long a64_realtime() {
-  unsigned long long t;
-  asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  return t;
-}
-#define A64_STAMP(T, I) if (p.dbg && blockIdx.x == 8 && lane == 0 && (T) >= 200 && (T) < 208) p.dbg[(wave * 8 + ((T) - 200)) * 8 + (I)] = a64_stamp();
-#else
-#define A64_STAMP(T, I)
-#endif
 
 #define A64_QB 256
 #define A64_KT 64
@@ -162,15 +142,15 @@ __device__ __forceinline__ void a64_softmax(f32x16 (&sc)[2], float& m, f32x16 (&
         u32x4 pw;
 #pragma unroll
         for (int jj = 0; jj < 4; ++jj) {
-          const float p0 = A64_ABL == 1 ? sc[kt][8 * s2 + 2 * jj] : __builtin_amdgcn_exp2f(sc[kt][8 * s2 + 2 * jj]);
-          const float p1 = A64_ABL == 1 ? sc[kt][8 * s2 + 2 * jj + 1] : __builtin_amdgcn_exp2f(sc[kt][8 * s2 + 2 * jj + 1]);
+          const float p0 = __builtin_amdgcn_exp2f(sc[kt][8 * s2 + 2 * jj]);
+          const float p1 = __builtin_amdgcn_exp2f(sc[kt][8 * s2 + 2 * jj + 1]);
           if constexpr (!MSUM) {
             ps0 += p0;
             ps1 += p1;
           }
           pw[jj] = pack_bf16x2(p0, p1);
         }
-        if constexpr (MSUM && A64_ABL != 6) {
+        if constexpr (MSUM) {
           u32x2 lo2, hi2;
           lo2[0] = pw[0]; lo2[1] = pw[1]; hi2[0] = pw[2]; hi2[1] = pw[3];
           lacc = __builtin_amdgcn_mfma_f32_4x4x4bf16_1k(ones, __builtin_bit_cast(s16x4, lo2), lacc, 0, 0, 0);
@@ -337,12 +317,6 @@ __device__ __forceinline__ void a64_body(const Attn64Params& p, char* lds, const
       *(u32x4*)(lds + buf * 8192 + vw[i]) = vr[i];
     }
   };
-#ifdef PI3_ATTN_STAMPS
-  // phase stamps of a sample of workgroups (every 37th): [0] entry, [1] tile 0 staged + barrier, [2] key sweep done, [3] stores issued
-  const bool st_on = p.dbg && (blockIdx.x % 37) == 5 && tid == 0 && blockIdx.x / 37 < 100;
-  unsigned long long* st = p.dbg + 1100 + (blockIdx.x / 37) * 4;
-  if (st_on) st[0] = a64_realtime();
-#endif
   if constexpr (GLDS) {
     glds_tile(0, true, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the asm-issued DMA is invisible to the compiler's own waits
@@ -351,9 +325,6 @@ __device__ __forceinline__ void a64_body(const Attn64Params& p, char* lds, const
     write_tile(0);
   }
   __syncthreads();
-#ifdef PI3_ATTN_STAMPS
-  if (st_on) st[1] = a64_realtime();
-#endif
 
   const int kswz = (r >> 1) & 7;
   const int krow_off = r * 128;
@@ -381,7 +352,6 @@ __device__ __forceinline__ void a64_body(const Attn64Params& p, char* lds, const
 #define A64_TILE(T, BUF, FIRST, LAST, CLAMPNEXT, NOMAX, NB, NKT)                                                  \
   {                                                                                                               \
     const int buf = (BUF);                                                                                        \
-    A64_STAMP(T, 0)                                                                                               \
     if (!(LAST)) { if constexpr (GLDS) glds_tile((T) + 1, CLAMPNEXT, buf ^ 1); else load_tile((T) + 1, CLAMPNEXT); } \
     f32x16 scA[2], scB[2];                                                                                        \
     bf16x8 pfA[2][2], pfB[2][2];                                                                                  \
@@ -400,9 +370,8 @@ __device__ __forceinline__ void a64_body(const Attn64Params& p, char* lds, const
           if ((NB) == 2) scB[1] = a64_mfma<F16>(a1, qfB[0], (f32x16)(0.f));    \
         }                                                                                                         \
       }                                                                                                           \
-      if (A64_ABL != 4)                                                                                           \
       _Pragma("unroll") for (int s = 1; s < 4; ++s) {                                                             \
-        const int off = A64_ABL == 7 ? ((h ^ kswz) << 4) : (((2 * s + h) ^ kswz) << 4);                           \
+        const int off = ((2 * s + h) ^ kswz) << 4;                                                                \
         const bf16x8 a0 = *(const bf16x8*)(kl + off);                                                             \
         scA[0] = a64_mfma<F16>(a0, qfA[s], scA[0]);                            \
         if ((NB) == 2) scB[0] = a64_mfma<F16>(a0, qfB[s], scB[0]);             \
@@ -413,7 +382,6 @@ __device__ __forceinline__ void a64_body(const Attn64Params& p, char* lds, const
         }                                                                                                         \
       }                                                                                                           \
       if (masktail) { A64_MASK(T, scA, NKT) if ((NB) == 2) { A64_MASK(T, scB, NKT) } }                            \
-      A64_STAMP(T, 1)                                                                                             \
       a64_softmax<FIRST, NOMAX, MSUM, NKT, F16>(scA, mA, oA, lA, laccA, pfA);                                          \
       if ((NB) == 2) a64_softmax<FIRST, NOMAX, MSUM, NKT, F16>(scB, mB, oB, lB, laccB, pfB);                           \
       _Pragma("unroll") for (int kt = 0; kt < (NKT); ++kt)                                                        \
@@ -421,8 +389,7 @@ __device__ __forceinline__ void a64_body(const Attn64Params& p, char* lds, const
         const int row0 = 32 * kt + 16 * s2 + vrow_l;                                                              \
         _Pragma("unroll") for (int dt = 0; dt < 2; ++dt) {                                                        \
           const int ch = (4 * dt + vch_l) ^ vswz;                                                                 \
-          const char* a = A64_ABL == 7 ? vl + vrow_l * 128 + (vch_l << 4) + vin_l : vl + row0 * 128 + (ch << 4) + vin_l; \
-          if (A64_ABL == 3) { asm volatile("" ::"v"(pfA[kt][s2]), "v"(pfB[kt][s2])); continue; }                  \
+          const char* a = vl + row0 * 128 + (ch << 4) + vin_l;                                                    \
           const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(                                             \
               (__attribute__((address_space(3))) bf16x4*)LDS_PTR(a));                                             \
           const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(                                             \
@@ -433,13 +400,10 @@ __device__ __forceinline__ void a64_body(const Attn64Params& p, char* lds, const
         }                                                                                                         \
       }                                                                                                           \
     }                                                                                                             \
-    A64_STAMP(T, 2)                                                                                               \
     if (!(LAST)) {                                                                                                \
       if constexpr (!GLDS) write_tile(buf ^ 1);                                                                   \
-      else if (A64_ABL != 5) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                     \
-      A64_STAMP(T, 3)                                                                                             \
-      if (A64_ABL != 5) __syncthreads();                                                                          \
-      A64_STAMP(T, 4)                                                                                             \
+      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                       \
+      __syncthreads();                                                                                            \
     }                                                                                                             \
   }
 
@@ -458,9 +422,6 @@ __device__ __forceinline__ void a64_body(const Attn64Params& p, char* lds, const
   }
 
   const bool tail = (S & (A64_KT - 1)) != 0;
-#ifdef PI3_ATTN_STAMPS
-  if (p.dbg && blockIdx.x == 8 && tid == 0) { p.dbg[1000] = a64_stamp(); p.dbg[1001] = a64_realtime(); }
-#endif
   // the last tile holds S - 64 (nt - 1) keys: when that is <= 32 its second 32-key half is skipped (frame-wise
   // sequences: 643 = 10 x 64 + 3); long sequences keep one code path (their last tile is one of a thousand)
   const bool half_last = (NW <= 4) && p.tailopt && (S - (nt - 1) * A64_KT <= 32);
@@ -498,12 +459,6 @@ __device__ __forceinline__ void a64_body(const Attn64Params& p, char* lds, const
     A64_SWEEP(true, 0)
   }
 
-#ifdef PI3_ATTN_STAMPS
-  if (p.dbg && blockIdx.x == 8 && tid == 0) { p.dbg[1002] = a64_stamp(); p.dbg[1003] = a64_realtime(); p.dbg[1004] = fast; }
-#endif
-#ifdef PI3_ATTN_STAMPS
-  if (st_on) st[2] = a64_realtime();
-#endif
   if (!F16 && p.optim && !p.redo) {     // acceptance test of the optimistic bounded-score loop (workgroup-uniform branch)
     bool bad = false;
     if (nb > 0 && !sure) bad = a64_reject(lA + laccA[0], oA);
@@ -533,9 +488,6 @@ __device__ __forceinline__ void a64_body(const Attn64Params& p, char* lds, const
         }
     }
   }
-#ifdef PI3_ATTN_STAMPS
-  if (st_on) st[3] = a64_realtime();
-#endif
   // which softmax loop this wave ran (diagnostic, off unless the caller registered a counter block): one no-return
   // atomic per wave after its stores, spread over 32 slots so that same-address atomics do not queue up in L2
   if (p.stats && lane == 0 && nb > 0)
@@ -578,37 +530,14 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_redo64_kernel(Attn64Params p)
     }
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
-// attn_fwd64a_kernel (round 5): the eight-wave kernel with a HAND-PLACED main loop for workgroups whose eight waves all
-// pass the bounded-score test (recipe weights: every workgroup of the global attention, bench.py `softmax_paths`).
-// The loop body is one inline-asm block generated by tools/gen_attn_asm.py (attn64a_loop.inc; its header explains the
-// quarter-tile software pipeline and the register map).  C++ around it: prologue, tile 0, the last three tiles (the
-// partial one with its clamped DMA and key mask among them), finalisation and stores - the code of a64_body with the
-// K ring three slots deep (slot t % 3 at LDS offsets 0 / 8 192 / 32 768; V ring two slots at 16 384 + 8 192 (t & 1)):
-// the pipelined loop computes Q.K^T of tile t + 1 during tile t, so K is staged two tiles ahead, V one.
-// A workgroup with a wave outside the bound, or a sequence of fewer than eight tiles, runs a64_body unchanged
-// (workgroup-uniform choice before anything is staged, so the two LDS protocols never meet).
-// ---------------------------------------------------------------------------------------------------------------------
-#ifdef PI3_DEV_VARIANTS
-#include <attn64a_loop.inc>   // -I. (the Makefile); tools/build_attn_variants.sh puts a variant directory in front
-#endif
+// Staging ring and tile macros of the hand-placed kernels: attn_fwd64b_kernel below and, in development builds,
+// attn_fwd64a_kernel (attn64a_kernel.inc).  They expand inside the kernels, next to the locals they name.  The
+// pipelined loop computes Q.K^T of tile t + 1 during tile t, so K is staged two tiles ahead and V one: the K ring is three
+// slots deep (slot t % 3 at LDS offsets 0 / 8 192 / 32 768), the V ring two (16 384 + 8 192 (t & 1)).  A64A_BLOCK is one
+// 32-row query block on one 64-key tile in C++ (the bounded-score form of a64_body's tile): tile 0 and the last three.
 #define A64A_KSLOT(T) (((T) % 3) == 0 ? 0 : (((T) % 3) == 1 ? 8192 : 32768))
 #define A64A_VSLOT(T) (16384 + ((T) & 1) * 8192)
 #define A64A_LDSADDR(P) ((unsigned)(__UINTPTR_TYPE__)((__attribute__((address_space(3))) void*)(P)))
-// (macros shared by attn_fwd64a_kernel and attn_fwd64b_kernel; they expand inside the kernels, next to the locals they name)
-#define A64A_LANE_CONSTS(LANE)                                                                                     \
-  {                                                                                                               \
-    r_ = (LANE) & 31; h_ = (LANE) >> 5;                                                                           \
-    drow = wave * 8 + ((LANE) >> 3); dpos = (LANE) & 7;                                                           \
-    kswz = (r_ >> 1) & 7;                                                                                         \
-    krow_off = r_ * 128;                                                                                          \
-    const int gi = (LANE) & 15, gg = ((LANE) >> 4) & 1;                                                           \
-    vrow_l = 4 * h_ + (gi >> 2);                                                                                  \
-    const int vcol_l = 16 * gg + 4 * (gi & 3);                                                                    \
-    vch_l = vcol_l >> 3;                                                                                          \
-    vin_l = (vcol_l & 7) * 2;                                                                                     \
-    vswz = ((vrow_l >> 1) & 1) << 2;                                                                              \
-  }
 #define A64A_BLOCK(T, FIRST, LAST, QF, OACC, LSUM, LACC, MREF)                                                      \
   {                                                                                                               \
     f32x16 sc[2];                                                                                                 \
@@ -635,173 +564,9 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_redo64_kernel(Attn64Params p)
       }                                                                                                           \
     }                                                                                                             \
   }
-#define A64A_TILE(T, FIRST, LAST)                                                                                  \
-  {                                                                                                               \
-    if ((T) + 1 < nt) dma_v((T) + 1);                                                                             \
-    if ((T) + 2 < nt) dma_k((T) + 2);                                                                             \
-    const char* kl = lds + A64A_KSLOT(T) + krow_off;                                                              \
-    const char* vl = lds + A64A_VSLOT(T);                                                                         \
-    A64A_BLOCK(T, FIRST, LAST, qfA, oA, lA, laccA, mA)                                                            \
-    __builtin_amdgcn_sched_barrier(0);                                                                            \
-    A64A_BLOCK(T, FIRST, LAST, qfB, oB, lB, laccB, mB)                                                            \
-    if (!(LAST)) {                                                                                                \
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                            \
-      __syncthreads();                                                                                            \
-    }                                                                                                             \
-  }
 
 #ifdef PI3_DEV_VARIANTS   // knob attn_asm = 1 (development builds): measured 2.5 % behind attn_fwd64b_kernel, bit-identical
-__global__ __launch_bounds__(512, 2) void attn_fwd64a_kernel(Attn64Params p) {
-  __shared__ __attribute__((aligned(16))) char lds[40960];
-  constexpr bool F16 = false;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int r = lane & 31, h = lane >> 5;
-  const int nwg = p.nqb * p.H * p.B;
-  const int id = xcd_remap(blockIdx.x, nwg);
-  const int qb = id % p.nqb;
-  const int head = (id / p.nqb) % p.H;
-  const int b = id / (p.nqb * p.H);
-  const int S = p.S;
-  const int nt = (S + A64_KT - 1) / A64_KT;
-  const int q0 = qb * 512 + wave * 64;
-  bf16x8 qfA[4], qfB[4];
-  {
-    const int ra = min(q0 + r, S - 1), rb = min(q0 + 32 + r, S - 1);
-    const bf16_t* pa = p.q + (long)b * p.batch_stride + (long)ra * p.tok_stride + head * 64;
-    const bf16_t* pb = p.q + (long)b * p.batch_stride + (long)rb * p.tok_stride + head * 64;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      qfA[s] = *(const bf16x8*)(pa + 16 * s + 8 * h);
-      qfB[s] = *(const bf16x8*)(pb + 16 * s + 8 * h);
-    }
-  }
-  bool fast = false;
-  if (p.k2max) {
-    const float k2 = p.k2max[b * p.H + head];
-    float qa = 0.f, qbn = 0.f;
-#pragma unroll
-    for (int s = 0; s < 4; ++s)
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float fa = (float)qfA[s][e], fb = (float)qfB[s][e];
-        qa += fa * fa;
-        qbn += fb * fb;
-      }
-    qa += __shfl_xor(qa, 32, 64);
-    qbn += __shfl_xor(qbn, 32, 64);
-    fast = __all(fmaxf(qa, qbn) * k2 <= A64_BOUND2);
-  }
-  const bool sure = __syncthreads_and(fast) != 0;               // every wave inside the a-priori bound (workgroup-uniform)
-  if (!(nt >= 8 && (p.optim || sure))) {
-    a64_body<8, true, true, false>(p, lds, blockIdx.x);
-    return;
-  }
-
-  f32x16 oA[2], oB[2];
-  oA[0] = oA[1] = oB[0] = oB[1] = (f32x16)(0.f);
-  float mA = 0.f, mB = 0.f, lA = 0.f, lB = 0.f;
-  f32x4 laccA = (f32x4)(0.f), laccB = (f32x4)(0.f);
-  const bf16_t* kbase = p.k + (long)b * p.batch_stride + head * 64;
-  const bf16_t* vbase = p.v + (long)b * p.batch_stride + head * 64;
-  const long tile_bytes = (long)A64_KT * p.tok_stride * 2;
-  const bool tail = (S & (A64_KT - 1)) != 0;
-  // this wave's LDS-DMA piece of a tile: rows 8 wave .. 8 wave + 7, lane -> (row, 16-byte slot), swizzle on the source
-  int drow, dpos;                                    // (set by A64A_LANE_CONSTS)
-  auto dma_k = [&](int T) {
-    int grow = T * A64_KT + drow;
-    grow = grow < S ? grow : S - 1;                  // only the last, partial tile clamps
-    a64_glds16((const char*)(kbase + (long)grow * p.tok_stride) + ((dpos ^ ((drow >> 1) & 7)) << 4),
-               lds + A64A_KSLOT(T) + wave * 1024);
-  };
-  auto dma_v = [&](int T) {
-    int grow = T * A64_KT + drow;
-    grow = grow < S ? grow : S - 1;
-    a64_glds16((const char*)(vbase + (long)grow * p.tok_stride) + ((dpos ^ (((drow >> 1) & 1) << 2)) << 4),
-               lds + A64A_VSLOT(T) + wave * 1024);
-  };
-
-  // lane-derived fragment offsets.  They are recomputed from a laundered lane id behind the asm loop (A64A_LANE_CONSTS
-  // again, below): kept live across it they would have to sit below the loop's fixed registers beside O, Q and the row
-  // sums, and hipcc sent a dozen of them through scratch (53 MB of spill traffic per launch in the WRITE_SIZE counter)
-  int kswz, krow_off, vrow_l, vch_l, vin_l, vswz, r_, h_;
-  A64A_LANE_CONSTS(lane)
-  dma_k(0);
-  dma_v(0);
-  dma_k(1);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-
-  // one 64-key tile, bounded-score path (the C++ form of a64_body's tile on the three-slot K ring).  Four of ~1 000 tiles
-  // run here, so the two query blocks go one after the other: half the live score / probability registers, which keeps
-  // the values that live across the asm statement (O, Q, row sums: 104 registers below the loop's fixed v150..v255)
-  // out of scratch.
-
-  A64A_TILE(0, true, false)
-  {
-    // ---- tiles 1 .. nt - 4: the hand-placed loop.  Entry state of its registers (tools/gen_attn_asm.py): K fragment
-    // addresses in the slot of tile 1, V fragment addresses in the slot of tile 0 (the loop head steps them to tile 1)
-    const unsigned lds0 = A64A_LDSADDR(lds);
-    const unsigned ka0 = lds0 + 8192 + krow_off + (((0 + h_) ^ kswz) << 4), ka1 = lds0 + 8192 + krow_off + (((2 + h_) ^ kswz) << 4);
-    const unsigned ka2 = lds0 + 8192 + krow_off + (((4 + h_) ^ kswz) << 4), ka3 = lds0 + 8192 + krow_off + (((6 + h_) ^ kswz) << 4);
-    const unsigned va0 = lds0 + 16384 + vrow_l * 128 + (((0 + vch_l) ^ vswz) << 4) + vin_l;
-    const unsigned va1 = lds0 + 16384 + vrow_l * 128 + (((4 + vch_l) ^ vswz) << 4) + vin_l;
-    const unsigned ksrc = (unsigned)(drow * p.tok_stride * 2) + ((dpos ^ ((drow >> 1) & 7)) << 4);
-    const unsigned vsrc = (unsigned)(drow * p.tok_stride * 2) + ((dpos ^ (((drow >> 1) & 1) << 2)) << 4);
-    const unsigned cnt = (unsigned)(nt - 4);
-    const unsigned long long kg = (unsigned long long)(__UINTPTR_TYPE__)kbase + 3ull * (unsigned long long)tile_bytes;
-    const unsigned long long vg = (unsigned long long)(__UINTPTR_TYPE__)vbase + 2ull * (unsigned long long)tile_bytes;
-    const unsigned kg_lo = __builtin_amdgcn_readfirstlane((unsigned)kg), kg_hi = __builtin_amdgcn_readfirstlane((unsigned)(kg >> 32));
-    const unsigned vg_lo = __builtin_amdgcn_readfirstlane((unsigned)vg), vg_hi = __builtin_amdgcn_readfirstlane((unsigned)(vg >> 32));
-    const unsigned long long kgs = ((unsigned long long)kg_hi << 32) | kg_lo, vgs = ((unsigned long long)vg_hi << 32) | vg_lo;
-    const unsigned tb = __builtin_amdgcn_readfirstlane((unsigned)tile_bytes);
-    const unsigned kd0 = __builtin_amdgcn_readfirstlane(lds0 + wave * 1024);
-    asm volatile(A64A_LOOP_ASM
-                 : [oa0] "+v"(oA[0]), [oa1] "+v"(oA[1]), [ob0] "+v"(oB[0]), [ob1] "+v"(oB[1]), [lA] "+v"(laccA), [lB] "+v"(laccB)
-                 : [qa0] "v"(qfA[0]), [qa1] "v"(qfA[1]), [qa2] "v"(qfA[2]), [qa3] "v"(qfA[3]), [qb0] "v"(qfB[0]),
-                   [qb1] "v"(qfB[1]), [qb2] "v"(qfB[2]), [qb3] "v"(qfB[3]), [ka0] "v"(ka0), [ka1] "v"(ka1), [ka2] "v"(ka2),
-                   [ka3] "v"(ka3), [va0] "v"(va0), [va1] "v"(va1), [ksrc] "v"(ksrc), [vsrc] "v"(vsrc), [cnt] "s"(cnt),
-                   [kg] "s"(kgs), [vg] "s"(vgs), [tb] "s"(tb), [kd0] "s"(kd0)
-                 : "memory", "scc", "vcc", "m0", A64A_CLOBBER_V, A64A_CLOBBER_S);
-  }
-  {
-    int lane2 = (int)(threadIdx.x & 63);
-    asm volatile("" : "+v"(lane2));                    // opaque: nothing derived from the lane id before the loop stays live
-    A64A_LANE_CONSTS(lane2)
-  }
-#define h h_      /* A64_MASK reads `h`: the recomputed one from here on */
-  A64A_TILE(nt - 3, false, false)
-  A64A_TILE(nt - 2, false, false)
-  A64A_TILE(nt - 1, false, true)
-#undef h
-
-  if (p.optim && !sure) {       // acceptance test of the optimistic loop (a64_reject); workgroup-uniform
-    const bool bad = a64_reject(lA + laccA[0], oA) || a64_reject(lB + laccB[0], oB);
-    if (__syncthreads_or(bad)) {
-      if (tid == 0) *a64_mark_ptr(p, b, qb, head, 512) = A64_MARK;
-      return;
-    }
-  }
-  if (p.stats && (threadIdx.x & 63) == 0) atomicAdd(p.stats + 0 + (blockIdx.x & 31), 1u);      // eight-wave kernel, bounded-score loop
-#pragma unroll
-  for (int blk = 0; blk < 2; ++blk) {
-    const float lsum = blk ? lB + laccB[0] : lA + laccA[0];
-    const float inv = 1.0f / (lsum + __shfl_xor(lsum, 32, 64));
-    const int row = q0 + 32 * blk + r_;
-    if (row < S) {
-      bf16_t* optr = p.o + (long)b * p.o_batch_stride + (long)row * p.o_tok_stride + head * 64;
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const f32x16& ov = blk ? oB[dt] : oA[dt];
-          u32x2 w;
-          w[0] = pack_bf16x2(ov[4 * g + 0] * inv, ov[4 * g + 1] * inv);
-          w[1] = pack_bf16x2(ov[4 * g + 2] * inv, ov[4 * g + 3] * inv);
-          *(u32x2*)(optr + 32 * dt + 8 * g + 4 * h_) = w;
-        }
-    }
-  }
-}
+#include "attn64a_kernel.inc"
 #endif   // PI3_DEV_VARIANTS
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1121,13 +886,6 @@ int pi3_attention64_launch(const void* q, const void* k, const void* v, long tok
   p.prio = PI3_DEV_ENV_INT("PI3_ATTN_PRIO", 0);
   p.tailopt = PI3_DEV_ENV_INT("PI3_ATTN_TAILOPT", 1);
 
-#ifdef PI3_ATTN_STAMPS
-  static unsigned long long* dbgbuf = nullptr;
-  if (!dbgbuf) hipMalloc((void**)&dbgbuf, 2048 * 8);
-  hipMemsetAsync(dbgbuf, 0, 2048 * 8, stream);
-  static_assert(1100 + 100 * 4 <= 2048, "phase stamps fit the debug buffer");
-  p.dbg = dbgbuf;
-#endif
   if (f16) {      // IEEE-half operands: LDS-DMA staging, online-max loop, eight- or four-wave workgroups
     p.stats = nullptr;     // not a choice of path (half always takes the online-max loop): MoGe's launches stay out of pi3's counters
     if (nw == 4)
@@ -1198,30 +956,5 @@ int pi3_attention64_launch(const void* q, const void* k, const void* v, long tok
       launch(false);
     }
   }
-#ifdef PI3_ATTN_STAMPS
-  {
-    static int printed = 0;
-    hipStreamSynchronize(stream);
-    if (printed++ == 3) {
-      static unsigned long long hb[2048];
-      hipMemcpy(hb, dbgbuf, sizeof(hb), hipMemcpyDeviceToHost);
-      fprintf(stderr, "STAMPS kernel: cycles %llu realtime(100MHz) %llu fast %llu -> clock %.1f MHz\n", hb[1002] - hb[1000],
-              hb[1003] - hb[1001], hb[1004], 100.0 * (double)(hb[1002] - hb[1000]) / (double)(hb[1003] - hb[1001]));
-      if (nw <= 4)     // frame-wise launches: per-workgroup phases in 10 ns ticks (s_memrealtime), sampled workgroups
-        for (int k = 0; k < 100 && (long)(37 * k + 5) < nwg; ++k) {
-          const unsigned long long* e = hb + 1100 + 4 * k;
-          fprintf(stderr, "PHASES wg %d start %llu prologue %llu sweep %llu tail %llu (x10 ns)\n", 37 * k + 5, e[0] - hb[1100],
-                  e[1] - e[0], e[2] - e[1], e[3] - e[2]);
-        }
-      for (int w = 0; w < 8 && nw == 8; ++w)
-        for (int t = 0; t < 8; ++t) {
-          const unsigned long long* e = hb + (w * 8 + t) * 8;
-          fprintf(stderr, "STAMPS w%d t%d start %llu qk %llu smpv %llu wait %llu barrier %llu\n", w, t, e[0] - hb[0], e[1] - e[0],
-                  e[2] - e[1], e[3] - e[2], e[4] - e[3]);
-      // (ping-pong kernel: the columns are  phase1 work | wait+barrier | phase2 work | wait+barrier)
-        }
-    }
-  }
-#endif
   return pi3_check_launch("attn_fwd64");
 }

@@ -8,31 +8,31 @@
 // output = 8 x 4 MFMA 16x16x32 tiles = 128 accumulator registers.  LDS = 2 K-tile buffers x {act half 0, act half 1,
 // W half 0, W half 1} x 16 KiB = 128 KiB; a wave reads exactly one act half (wm) and one W half (wn >> 1) per K tile.
 //
-// Per K tile u (buffer u & 1), the shipped form (G2_TWO_PHASE == 1, round 3) has two phases, each: fragment ds_reads ->
-// two half-tile LDS-DMA prefetches (4 x global_load_lds_dwordx4 per thread) -> s_waitcnt -> [s_barrier] -> 32 MFMAs (a
-// 64 x 64 half of the wave's block, K = 64) -> s_barrier:
+// Per K tile u (buffer u & 1) there are two phases, each: fragment ds_reads -> two half-tile LDS-DMA prefetches (4 x
+// global_load_lds_dwordx4 per thread) -> s_waitcnt -> [s_barrier] -> 32 MFMAs at wave priority 1 (a 64 x 64 half of the
+// wave's block, K = 64) -> s_barrier:
 //   phase ab: read W(nh0)[4] + W(nh1)[4] + act(mh0)[8]   prefetch act halves 0, 1 of tile u+1   MFMA (mh0, nh0), (mh0, nh1)
 //   phase cd: read act(mh1)[8]   prefetch W halves 0, 1 of tile u+2, then s_waitcnt vmcnt(4)    MFMA (mh1, nh1), (mh1, nh0)
+// The prologue stages tile 0 and the W halves of tile 1 and waits with vmcnt(4): tile 0 complete, W(1) in flight.
 // Hazards: a buffer region is re-staged only after the barrier that follows its last fragment read (W halves and act
 // half 0 after phase ab, act half 1 after phase cd); staged data is read in the phase AFTER the counted wait + barrier
 // that retires it (cd's vmcnt(4) leaves only the two newest half-tiles, W(u+2), in flight: tile u+1 is complete).  The
-// second wave of every SIMD runs one barrier behind the first (STAG, below); since a region is now re-staged ONE phase
+// second wave of every SIMD runs one barrier behind the first (STAG, below); since a region is re-staged ONE phase
 // after its last read, a wave's fragment reads must have RETURNED (s_waitcnt lgkmcnt(0)) and its counted vmcnt wait
 // must have been executed before the mid barrier of the phase, not merely issued before it.
-// The round-2 form (G2_TWO_PHASE == 0) splits each of these in two (16 MFMAs and one half-tile prefetch per phase):
-//   phase a: read W(nh0)[4] + act(mh0)[8]   MFMA (mh0, nh0)   prefetch act half 0 of tile u+1
-//   phase b: read W(nh1)[4]                 MFMA (mh0, nh1)   prefetch act half 1 of tile u+1
-//   phase c: read act(mh1)[8]               MFMA (mh1, nh1)   prefetch W half 0 of tile u+2   (W of this buffer is dead)
-//   phase d: (all fragments in registers)   MFMA (mh1, nh0)   prefetch W half 1 of tile u+2, then s_waitcnt vmcnt(4)
+// The LDS-DMA is issued from inline asm (g4_glds16) with per-tile 32-bit lane offsets: hipcc does not see the LDS write
+// and places no vmcnt(0) of its own in the loop, and eight offset dwords replace nine 64-bit staging pointers (no vector
+// spills).  The 32-bit offsets bound the operand footprint: pi3_gemm256_try declines matrices of 4 GiB and more.
+//
+// Forms that lost, one line each; the numbers are in the "GEMM family" table of profiles/EXPERIMENTS.md:
+//   four phases per K tile (round 2), two phases with every operand staged three phases ahead: row "four phases per K tile"
+//   staging through the LDS-DMA builtin with a 64-bit pointer per piece: row "LDS-DMA of the K loop from inline asm"
+//   two LDS-DMA pieces behind one write of M0: row "two LDS-DMA pieces behind one write of M0"
+//   no wave priorities / the load segment at priority 1: row "wave priorities of the ping-pong loop"
+//   plain instead of non-temporal stores of the bf16 output: row "non-temporal stores of the bf16 output rows"
+// Development builds (make dev) add the variants of gemm256_dev.inc and the STAG = false / ILVK / M32 instances.
 #include "gemm_common.h"
 #include <stdlib.h>
-// K-loop form (compile-time, -DG2_TWO_PHASE=n; measured on M = 64 300, three interleaved rounds, qkv / proj / fc1 / fc2 ms):
-//   0  four phases per K tile (16 MFMAs per phase, the round-2 form)          0.440 / 0.224 / 0.630 / 0.520 = 1.814
-//   1  two phases per K tile (32 MFMAs per phase, half the barriers): DEFAULT  0.421 / 0.217 / 0.613 / 0.498 = 1.749
-//   2  two phases, every operand staged three phases ahead                     0.424 / 0.227 / 0.606 / 0.527 = 1.784
-#ifndef G2_TWO_PHASE
-#define G2_TWO_PHASE 1
-#endif
 
 #define G2_BM 256
 #define G2_BN 256
@@ -64,50 +64,6 @@ __device__ __forceinline__ float g2_sum_rows4(float s) {
 __device__ __forceinline__ void g4_glds16(const char* sbase, unsigned voff, unsigned lds_dst) {
   asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(lds_dst)
                : "memory", "m0");
-}
-
-// two pieces 1 KiB apart in LDS behind ONE write of M0 (development switch G2_DMA_PAIR): the second load carries
-// `offset:1024`, which the hardware adds to the global AND the LDS address - the caller passes its lane offset less 1 024
-__device__ __forceinline__ void g4_glds16x2(const char* sbase, unsigned voff0, unsigned voff1_less_1k, unsigned lds_dst) {
-  asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %2\n\tglobal_load_lds_dwordx4 %1, %2 offset:1024"
-               ::"v"(voff0), "v"(voff1_less_1k), "s"(sbase), "s"(lds_dst)
-               : "memory", "m0");
-}
-#ifndef G2_DMA_PAIR
-#define G2_DMA_PAIR 0
-#endif
-#ifndef G2_NT_STORES
-#define G2_NT_STORES 1     // bf16 output rows stored with the non-temporal hint (round 4: qkv -3.8 %, fused qkv -4.8 %, fc1 -3.5 %
-                           // in alternating processes on one card, 3-4 ms per chunk end to end: the 0.4-0.5 GB an output takes
-                           // no longer passes through the L2 the operand panels live in; the f32 outputs gain nothing: the
-                           // LayerNorm that follows reads them) - profiles/r04_gemm_ab_nontemporal_stores.log
-#endif
-
-// G2_ASM_DMA = 1 (shipped since round 4): gemm256_kernel's K loop stages through g4_glds16 with per-tile 32-bit lane
-// offsets instead of the builtin with a 64-bit pointer per piece.  Bit-identical output; 230-235 VGPRs and no vector
-// spills where the builtin form sat at 256 with 2-8 spills (nine 64-bit staging pointers become eight dwords, the wave
-// index and the LDS destinations are scalars), no compiler-placed vmcnt(0) at the top of the K loop; block GEMMs
-// 1.615 / 1.630 -> 1.580 / 1.573 ms in alternating processes on one card (profiles/r04_gemm_asm_dma_ab.log; round 3
-// measured the same idea on the four-phase loop as 2 % slower).  -DG2_ASM_DMA=0 builds the builtin form for A/B.
-// The 32-bit offsets bound the operand footprint: pi3_gemm256_try declines matrices of 4 GiB and more.
-#ifndef G2_ASM_DMA
-#define G2_ASM_DMA 1
-#endif
-
-// stage one half-tile (128 rows x 128 B) of a row-major bf16 matrix: 16 segments of 1 KiB, 2 per wave (builtin form).
-__device__ __forceinline__ void g2_stage_half(const char* gbase, long ld_bytes, int row0, int rows, long k_bytes,
-                                              char* lds_half, int wave, int lane) {
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int seg = wave * 2 + i;
-    const int row = seg * 8 + (lane >> 3);
-    const int pos = lane & 7;
-    const int c = pos ^ ((row >> 1) & 7);
-    int grow = row0 + row;
-    grow = grow < rows ? grow : rows - 1;
-    const char* src = gbase + (long)grow * ld_bytes + k_bytes + c * 16;
-    __builtin_amdgcn_global_load_lds(GLB_PTR(src), LDS_PTR(lds_half + seg * 1024), 16, 0, 0);
-  }
 }
 
 // Epilogue through LDS (all pipeline buffers are dead after the last barrier): each wave transposes its 128 (m) x 64 (n)
@@ -330,11 +286,9 @@ __device__ __forceinline__ void g2_epilogue_lds(const GemmParams& p, f32x4 (&acc
       }
       if constexpr (OUT_BF16) {
         const u32x4 v = *(const u32x4*)(wl + lrow * PITCH + ch * 16);
-#if G2_NT_STORES
+        // non-temporal: the 0.4-0.5 GB an output takes stay out of the L2 the operand panels live in (the f32 outputs
+        // keep plain stores: the LayerNorm that follows reads them)
         __builtin_nontemporal_store(v, (u32x4*)((bf16_t*)p.out + orow * p.ldo + n_base + ch * 8));
-#else
-        *(u32x4*)((bf16_t*)p.out + orow * p.ldo + n_base + ch * 8) = v;
-#endif
       } else {
         f32x4 v = *(const f32x4*)(wl + lrow * PITCH + ch * 16);
         const int n0 = n_base + ch * 4;
@@ -372,13 +326,9 @@ __device__ __forceinline__ void g2_epilogue_lds(const GemmParams& p, f32x4 (&acc
 template <bool OUT_BF16, int ACT, bool NOEPI = false, bool STAG = false, bool QK = false, bool ILVK = false, bool M32 = false>
 __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-#if G2_ASM_DMA
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const unsigned lds0 = __builtin_amdgcn_readfirstlane(
       (unsigned)(__UINTPTR_TYPE__)((__attribute__((address_space(3))) void*)(smem)));
-#else
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#endif
   const int wm = wave >> 2, wn = wave & 3;
 
   const int nbm = (p.M + G2_BM - 1) / G2_BM, nbn = p.N / G2_BN;
@@ -463,7 +413,6 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmParams p) {
         for (int v = 0; v < 16; ++v) acc32[i][t][v] = 0.f;
   }
 
-#if G2_ASM_DMA
   // 32-bit staging offsets of this tile: piece (half h, i) = rows h * 128 + (wave * 2 + i) * 8 .. + 7
   unsigned aoff[4], woff[4];
 #pragma unroll
@@ -478,18 +427,6 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmParams p) {
       aoff[h * 2 + i] = (unsigned)((long)ga * lda_b + c * 16);
       woff[h * 2 + i] = (unsigned)((long)gw * ldw_b + c * 16);
     }
-#if G2_DMA_PAIR
-#define STAGE_A(U, HALF)                                                                  \
-  {                                                                                       \
-    const unsigned sb_ = lds0 + ((U) & 1) * G2_BUF + (HALF) * G2_HALF + wave * 2048;      \
-    g4_glds16x2(Ab + (long)(U) * 128, aoff[(HALF) * 2], aoff[(HALF) * 2 + 1] - 1024u, sb_); \
-  }
-#define STAGE_W(U, HALF)                                                                  \
-  {                                                                                       \
-    const unsigned sb_ = lds0 + ((U) & 1) * G2_BUF + (2 + (HALF)) * G2_HALF + wave * 2048; \
-    g4_glds16x2(Wb + (long)(U) * 128, woff[(HALF) * 2], woff[(HALF) * 2 + 1] - 1024u, sb_); \
-  }
-#else
 #define STAGE_A(U, HALF)                                                                  \
   {                                                                                       \
     const unsigned sb_ = lds0 + ((U) & 1) * G2_BUF + (HALF) * G2_HALF + wave * 2048;      \
@@ -502,16 +439,8 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmParams p) {
     g4_glds16(Wb + (long)(U) * 128, woff[(HALF) * 2], sb_);                               \
     g4_glds16(Wb + (long)(U) * 128, woff[(HALF) * 2 + 1], sb_ + 1024);                    \
   }
-#endif
-#else
-#define STAGE_A(U, HALF) g2_stage_half(Ab, lda_b, bm * G2_BM + (HALF) * 128, p.M, (long)(U) * 128, \
-                                       smem + ((U) & 1) * G2_BUF + (HALF) * G2_HALF, wave, lane)
-#define STAGE_W(U, HALF) g2_stage_half(Wb, ldw_b, bn * G2_BN + (HALF) * 128, p.N, (long)(U) * 128, \
-                                       smem + ((U) & 1) * G2_BUF + (2 + (HALF)) * G2_HALF, wave, lane)
-#endif
 
   if constexpr (ILVK) {
-#if G2_ASM_DMA
     // ---- Interleaved K loop (knob gemm_ilv, round 4 experiment): no ping-pong between the two waves of a SIMD.  A K tile
     // is two phases of 32 MFMAs, one per 32-deep half (kk); every accumulator gets one MFMA per phase.  The fragments of a
     // phase (8 act + 4 W, 48 registers) are double-buffered: while the MFMAs of phase kk0 run, the 12 fragment reads of
@@ -609,25 +538,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmParams p) {
 #undef GI_RD2
 #undef GI_MF4
 #undef GI_DMA
-#endif
   } else {
-#if G2_TWO_PHASE == 2
-  // prologue: tile 0 complete; W(1) and act(1) half 0 in flight (what cd(-1) would have staged)
-  STAGE_A(0, 0);
-  STAGE_A(0, 1);
-  STAGE_W(0, 0);
-  STAGE_W(0, 1);
-  if (nk > 1) {
-    STAGE_W(1, 0);
-    STAGE_W(1, 1);
-    STAGE_A(1, 0);
-    asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-  } else {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  }
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-#else
   // prologue: tile 0 complete, W halves of tile 1 in flight
   STAGE_A(0, 0);
   STAGE_A(0, 1);
@@ -642,7 +553,6 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmParams p) {
   }
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
-#endif
 
   const int frow = lane & 15;
   const int swz = (lane >> 1) & 7;
@@ -680,21 +590,8 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmParams p) {
     fa[i][0] = *(const bf16x8*)((BUFP) + a_base + (4 * (MH) + i) * 2048 + off0);          \
     fa[i][1] = *(const bf16x8*)((BUFP) + a_base + (4 * (MH) + i) * 2048 + off1);          \
   }
-#ifndef G2_PRIO
-#define G2_PRIO 0      // development switch: 0 = MFMA segment at priority 1 (shipped), 1 = no priorities, 2 = load segment at priority 1
-#endif
-#if G2_PRIO == 0
-#define G2_PRIO_MFMA_ON() __builtin_amdgcn_s_setprio(1);
-#define G2_PRIO_MFMA_OFF() __builtin_amdgcn_s_setprio(0);
-#elif G2_PRIO == 1
-#define G2_PRIO_MFMA_ON()
-#define G2_PRIO_MFMA_OFF()
-#else
-#define G2_PRIO_MFMA_ON() __builtin_amdgcn_s_setprio(0);
-#define G2_PRIO_MFMA_OFF() __builtin_amdgcn_s_setprio(1);
-#endif
 #define MFMA_Q(MH, NH)                                                                                   \
-  G2_PRIO_MFMA_ON()                                                                                      \
+  __builtin_amdgcn_s_setprio(1);                                                                         \
   if constexpr (M32) {                                                                                   \
     _Pragma("unroll") for (int ks = 0; ks < 4; ++ks)                                                      \
     _Pragma("unroll") for (int t = 0; t < 2; ++t)                                                         \
@@ -706,7 +603,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmParams p) {
   _Pragma("unroll") for (int j = 0; j < 4; ++j)                                                           \
     acc[2 * (NH) + i][4 * (MH) + j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(                            \
         fw[2 * (NH) + i][kk], fa[j][kk], acc[2 * (NH) + i][4 * (MH) + j], 0, 0, 0);                       \
-  G2_PRIO_MFMA_OFF()
+  __builtin_amdgcn_s_setprio(0);
 // raw barrier (no vmcnt drain); the empty asm statements with a memory clobber stop the compiler from moving LDS reads /
 // LDS-DMA issues across it (s_barrier itself is not a memory operation to LLVM)
 #define PHASE_END()                            \
@@ -718,51 +615,6 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmParams p) {
   if constexpr (STAG) {
     if (wm == 1) { PHASE_END() }
   }
-#if G2_TWO_PHASE == 2
-  // Two phases per K tile (round 3 experiment): 32 MFMAs per phase, half the barriers, every operand staged three phases
-  // before it is read:
-  //   phase ab(u): read W(u) both halves + act(u) half 0;  stage act(u+1) half 1;           MFMA (mh0, nh0), (mh0, nh1)
-  //   phase cd(u): read act(u) half 1;  stage W(u+2) both halves + act(u+2) half 0;          MFMA (mh1, nh1), (mh1, nh0)
-  // A region is re-staged one phase after its last read and a staged operand is read two phases after the counted wait
-  // that retires it; with the half-phase lag of waves 4-7 that needs the fragment reads returned (lgkmcnt(0)) and the
-  // counted wait executed BEFORE the phase's mid barrier.  Counted waits: loads retire in issue order, so "everything
-  // up to the previous phase of the same kind" = allow what was issued since (2 + 6 half-tile segments per thread).
-  for (int u = 0; u < nk; ++u) {
-    const char* bp = smem + (u & 1) * G2_BUF;
-    const bool pre1 = (u + 1 < nk), pre2 = (u + 2 < nk);
-    READ_W(bp, 0)
-    READ_W(bp, 1)
-    READ_A(bp, 0)
-    if (pre1) {
-      STAGE_A(u + 1, 1);
-      asm volatile("s_waitcnt vmcnt(8)" ::: "memory");      // act(u) half 1 (staged in ab(u-1)) is there for cd(u)
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    PHASE_MID()
-    MFMA_Q(0, 0)
-    MFMA_Q(0, 1)
-    PHASE_END()
-    READ_A(bp, 1)
-    if (pre2) {
-      STAGE_W(u + 2, 0);
-      STAGE_W(u + 2, 1);
-      STAGE_A(u + 2, 0);
-      asm volatile("s_waitcnt vmcnt(8)" ::: "memory");      // W(u+1), act(u+1) half 0 (staged in cd(u-1)) are there for ab(u+1)
-    } else if (pre1) {
-      asm volatile("s_waitcnt vmcnt(2)" ::: "memory");      // only act(u+1) half 1 may still be in flight
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    PHASE_MID()
-    MFMA_Q(1, 1)
-    MFMA_Q(1, 0)
-    PHASE_END()
-  }
-#elif G2_TWO_PHASE == 1
-  // (simple form: the four-phase staging schedule with phases a+b and c+d merged)
   // Residual touch (knob gemm_rpref, f32 output + residual, no row remap): the epilogue's residual read is the one
   // HBM stream of this kernel that does not depend on the accumulators.  During K tiles nk-6 .. nk-3 every lane loads
   // ONE dword of one 128-byte line of the wave's 128 x 64 residual block (256 lines = 4 instructions per wave) into a
@@ -829,41 +681,6 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmParams p) {
   }
 #ifdef PI3_DEV_VARIANTS
   asm volatile("" ::"v"(pf_sink));
-#endif
-#else
-  for (int u = 0; u < nk; ++u) {
-    const char* bp = smem + (u & 1) * G2_BUF;
-    const bool pre1 = (u + 1 < nk), pre2 = (u + 2 < nk);
-    // ---- phase a
-    READ_W(bp, 0)
-    READ_A(bp, 0)
-    if (pre1) STAGE_A(u + 1, 0);
-    PHASE_MID()
-    MFMA_Q(0, 0)
-    PHASE_END()
-    // ---- phase b
-    READ_W(bp, 1)
-    if (pre1) STAGE_A(u + 1, 1);
-    PHASE_MID()
-    MFMA_Q(0, 1)
-    PHASE_END()
-    // ---- phase c
-    READ_A(bp, 1)
-    if (pre2) STAGE_W(u + 2, 0);
-    PHASE_MID()
-    MFMA_Q(1, 1)
-    PHASE_END()
-    // ---- phase d
-    if (pre2) {
-      STAGE_W(u + 2, 1);
-      asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    PHASE_MID()
-    MFMA_Q(1, 0)
-    PHASE_END()
-  }
 #endif
   if constexpr (STAG) {
     if (wm == 0) { PHASE_END() }   // barrier counts match again; nobody touches the epilogue LDS before everyone is out
@@ -937,395 +754,7 @@ static int launch256(const GemmParams& p, hipStream_t stream) {
 }
 
 #ifdef PI3_DEV_VARIANTS   // gemm3_kernel (PI3_GEMM_IMPL=3) and gemm4w_kernel (knob gemm_4w): measured slower, bit-identical - development builds
-// ---------------------------------------------------------------------------------------------------------------
-// Two-workgroups-per-CU form (PI3_GEMM_IMPL=3 / per-shape choice): 128 (m) x 256 (n) tile, 256 threads = 4 waves, each
-// wave the same 128 x 64 output block (and therefore the same epilogues) as in gemm256_kernel, BK = 32, a 3-stage
-// LDS-DMA ring of 24 KiB stages (72 KiB per workgroup: two workgroups fit a CU's 160 KiB, their 4 + 4 waves give every
-// SIMD one wave of each).  The two workgroups of a CU are independent, so one's epilogue (an HBM-rate store stream the
-// 256 x 256 kernel cannot hide at one workgroup per CU) runs under the other's main loop, and barrier / LDS-latency
-// stalls of one are filled by the other.  Price: 1.5 x the L2 -> LDS bytes per flop of the 256 x 256 tile.
-// MEASURED (round 2, M = 64300): qkv 0.525 / proj 0.257 / fc1 0.702 / fc2 0.657 ms against 0.439 / 0.222 / 0.640 / 0.510 ms
-// of gemm256_kernel on the same box, tile-group sizes 4...64 within 5 % of each other: the epilogue does overlap, but
-// the main loop drops from ~1.25 to ~0.85 PF/s (LDS array busy 75 % of the MFMA time instead of 62 %: the same
-// fragment reads plus 1.5 x the DMA writes, and one barrier per 32 MFMAs).  Kept as a correct A/B variant, not default.
-//   stage image: act 128 rows x 64 B, then W 256 rows x 64 B; 16-byte chunk c of row r sits at c ^ F[(r >> 2) & 3],
-//   F = {0, 2, 3, 1}: conflict-free for the ds_read_b128 fragment pattern on 64-byte rows (each 16-lane group of the
-//   instruction then covers one whole 256-byte bank row).
-//   iteration u: s_waitcnt vmcnt(6) (stage u landed, stage u+1 may fly) -> s_barrier -> LDS-DMA of stage u+2 (its slot
-//   was last read in iteration u-1, which every wave has left) -> 12 fragment reads -> 32 MFMAs.
-// ---------------------------------------------------------------------------------------------------------------
-#define G3_BM 128
-#define G3_BN 256
-#define G3_STAGE 24576
-#define G3_LDS (3 * G3_STAGE)        // 72 KiB; the epilogue reuses it (4 waves x 18 KiB)
-
-template <bool OUT_BF16, int ACT, bool QK = false>
-__global__ __launch_bounds__(256, 2) void gemm3_kernel(GemmParams p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-
-  const int nbm = (p.M + G3_BM - 1) / G3_BM, nbn = p.N / G3_BN;
-  const int nwg = nbm * nbn;
-  const int id = xcd_remap(blockIdx.x, nwg);
-  const int GM = p.tile_gm > 0 ? p.tile_gm : 16;
-  const int per_group = GM * nbn;
-  const int g = id / per_group;
-  const int gm = min(GM, nbm - g * GM);
-  const int rem = id - g * per_group;
-  const int bm = g * GM + rem % gm;
-  const int bn = rem / gm;
-
-  const char* Ab = (const char*)p.A;
-  const char* Wb = (const char*)p.W;
-  const long lda_b = p.lda * 2, ldw_b = p.ldw * 2;
-  const int nk = p.K >> 5;
-
-  // swizzle table F = {0, 2, 3, 1} packed 2 bits each: 0b01'11'10'00 = 0x78
-  auto F = [](int q) { return (0x78 >> (2 * q)) & 3; };
-
-  // ---- staging addresses: lane i of a 1 KiB segment covers row i >> 2 (16 rows), slot i & 3
-  const int srow = lane >> 2, spos = lane & 3;
-  const char* a_src[2];
-  const char* w_src[4];
-  int a_dst[2], w_dst[4];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int seg = wave * 2 + i, row = seg * 16 + srow;
-    int grow = bm * G3_BM + row;
-    grow = grow < p.M ? grow : p.M - 1;
-    a_src[i] = Ab + (long)grow * lda_b + ((spos ^ F((row >> 2) & 3)) << 4);
-    a_dst[i] = seg * 1024;
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int seg = wave * 4 + i, row = seg * 16 + srow;
-    w_src[i] = Wb + (long)(bn * G3_BN + row) * ldw_b + ((spos ^ F((row >> 2) & 3)) << 4);
-    w_dst[i] = 8192 + seg * 1024;
-  }
-#define G3_STAGE_IN(U)                                                                                    \
-  {                                                                                                       \
-    char* sb = smem + ((U) % 3) * G3_STAGE;                                                               \
-    const long kb = (long)(U) * 64;                                                                       \
-    _Pragma("unroll") for (int i = 0; i < 2; ++i)                                                         \
-      __builtin_amdgcn_global_load_lds(GLB_PTR(a_src[i] + kb), LDS_PTR(sb + a_dst[i]), 16, 0, 0);        \
-    _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                         \
-      __builtin_amdgcn_global_load_lds(GLB_PTR(w_src[i] + kb), LDS_PTR(sb + w_dst[i]), 16, 0, 0);        \
-  }
-
-  f32x4 acc[4][8];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-  // fragment addresses inside a stage: rows mi*16 + frow (act) / wave*64 + ni*16 + frow (W), chunk lane >> 4
-  const int frow = lane & 15;
-  const int foff = frow * 64 + (((lane >> 4) ^ F((frow >> 2) & 3)) << 4);
-  const int w_base = 8192 + wave * 64 * 64 + foff;
-
-  G3_STAGE_IN(0)
-  if (nk > 1) G3_STAGE_IN(1)
-
-  for (int u = 0; u < nk; ++u) {
-    if (u + 1 < nk) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    if (u + 2 < nk) G3_STAGE_IN(u + 2)
-    const char* sb = smem + (u % 3) * G3_STAGE;
-    bf16x8 fw[4], fa[8];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) fw[i] = *(const bf16x8*)(sb + w_base + i * 1024);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) fa[j] = *(const bf16x8*)(sb + foff + j * 1024);
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[i], fa[j], acc[i][j], 0, 0, 0);
-    __builtin_amdgcn_s_setprio(0);
-  }
-  // every wave must be out of its last fragment reads before the epilogue reuses the ring
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-
-  if constexpr (OUT_BF16)
-    g2_epilogue_lds<OUT_BF16, ACT, QK>(p, acc, bm * G3_BM, bn * G3_BN + wave * 64, smem + wave * G2_EPI_WAVE, lane);
-  else
-    gemm_epilogue<OUT_BF16, ACT, 4, 8>(p, acc, bm * G3_BM, bn * G3_BN + wave * 64, lane);
-#undef G3_STAGE_IN
-}
-
-template <bool OUT_BF16, int ACT, bool QK = false>
-static int launch3(const GemmParams& p, hipStream_t stream) {
-  const int nbm = (p.M + G3_BM - 1) / G3_BM, nbn = p.N / G3_BN;
-  auto kern = gemm3_kernel<OUT_BF16, ACT, QK>;
-  static unsigned long long optin = 0;
-  if (int rc = pi3_lds_optin((const void*)kern, G3_LDS, &optin, "gemm3")) return rc;
-  hipLaunchKernelGGL(kern, dim3(nbm * nbn), dim3(256), G3_LDS, stream, p);
-  return pi3_check_launch("gemm3");
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// Four-wave form (round 4 experiment, knob gemm_4w = 1): the same 256 x 256 x 64 tile, LDS image, swizzle and persistent
-// tile walk, but ONE wave per SIMD, each owning a 128 (m) x 128 (n) block = 8 x 8 MFMA tiles = 256 accumulator registers
-// (the wave may use 512: accumulators in AGPRs).  Why: gemm256_kernel is bound by the LDS port - per K tile its eight
-// waves read 8 x 24 KB of fragments beside the 64 KB the LDS-DMA writes, 2 048 cycles of the 128 B/clk port against 2 048
-// cycles of MFMA.  A 128 x 128 wave block reads (128 + 128) rows x 128 B = 32 KB per wave and K tile: 4 x 32 + 64 = 192 KB
-// per K tile, 1 536 port cycles against the same 2 048 MFMA cycles.  Price: no partner wave to cover a wave's waits, so
-// the K loop is software-pipelined inside the wave: a K tile is two 32-deep halves, the fragments of the NEXT half are
-// read while the 64 MFMAs of the current one run, one barrier per K tile:
-//   half A(u): read frags (u, kk=1);   64 MFMAs on (u, kk=0);   vmcnt(0) [DMA(u+1) landed], lgkmcnt(0);   s_barrier
-//   half B(u): read frags (u+1, kk=0) from the other buffer;   LDS-DMA of tile u+2 into this buffer;   64 MFMAs on (u, kk=1)
-// Hazards: buffer (u & 1) is re-staged after the barrier that follows every wave's last read of it (its kk=1 fragments,
-// returned: lgkmcnt(0) before the barrier); DMA(u+1) is waited for by the issuing wave before the same barrier and read
-// after it.  The LDS-DMA is issued from inline asm (M0 = wave-uniform LDS base), so hipcc's waitcnt pass puts no
-// vmcnt(0) in front of later ds_reads; the only vmcnt waits are the ones written here.
-// ---------------------------------------------------------------------------------------------------------------
-// LDS-DMA with a scalar base and a 32-bit lane offset: one VGPR per staged segment instead of a 64-bit pointer (with
-// 16 segments per wave and K tile the 64-bit pointers were hoisted out of the K loop, spilled, and their scratch reloads
-// brought vmcnt(0) waits in front of every DMA)
-
-// fragment read from inline asm (immediate offset), so that its place between the asm MFMAs is the place it is issued
-// at: a C++ load may be hoisted by the scheduler to the top of the block, which is what leaves a lone wave's MFMAs waiting
-// behind a burst of 16 reads + 16 LDS-DMA issues.  The consumer waits with an explicit s_waitcnt lgkmcnt(0).
-template <int OFF>
-__device__ __forceinline__ void g4_lds_read(bf16x8& d, unsigned addr) {
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF));
-}
-
-template <bool OUT_BF16, int ACT, bool QK = false, bool ILV = false>
-__global__ __launch_bounds__(256) void gemm4w_kernel(GemmParams p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // scalar: LDS-DMA destinations (M0) are SALU arithmetic
-  const int wm = wave >> 1, wn = wave & 1;
-  const int nbm = (p.M + G2_BM - 1) / G2_BM, nbn = p.N / G2_BN;
-  const int nwg = nbm * nbn;
-  const char* Ab = (const char*)p.A;
-  const char* Wb = (const char*)p.W;
-  const long lda_b = p.lda * 2, ldw_b = p.ldw * 2;
-  const int nk = p.K >> 6;
-  const int GM = p.tile_gm > 0 ? p.tile_gm : 8;
-  const int per_group = GM * nbn;
-
-  const int* pos_l = nullptr;
-  const float* cs_l = nullptr;
-  if constexpr (QK) {      // RoPE tables -> LDS once per workgroup (as gemm256_kernel)
-    if (p.qk_pos && p.qk_T * 8 + 16 <= G2_TAB_BYTES) {
-      int* scratch = (int*)(smem + G2_LDS_TOTAL);
-      int* pl = scratch + 4;
-      if (tid == 0) scratch[0] = 0;
-      __syncthreads();
-      int mx = 0;
-      for (int i = tid; i < 2 * p.qk_T; i += 256) {
-        const int v = p.qk_pos[i];
-        pl[i] = v;
-        mx = max(mx, v);
-      }
-      mx = (int)wave_max((float)mx);
-      if (lane == 0) atomicMax(scratch, mx);
-      __syncthreads();
-      const int npos = scratch[0] + 1;
-      const int tab0 = 16 + ((p.qk_T * 8 + 15) & ~15);
-      if (tab0 + npos * 128 <= G2_TAB_BYTES) {
-        float* cl = (float*)(smem + G2_LDS_TOTAL + tab0);
-        for (int i = tid; i < npos * 32; i += 256) cl[i] = p.qk_cs[i];
-        pos_l = pl;
-        cs_l = cl;
-      }
-      __syncthreads();
-    }
-  }
-
-  const int frow = lane & 15;
-  const int swz = (lane >> 1) & 7;
-  const int cq = lane >> 4;
-  const int off0 = ((cq) ^ swz) << 4, off1 = ((cq + 4) ^ swz) << 4;
-  const int a_base = wm * G2_HALF + frow * 128;
-  const int w_base = (2 + wn) * G2_HALF + frow * 128;
-  const unsigned lds0 = __builtin_amdgcn_readfirstlane(
-      (unsigned)(__UINTPTR_TYPE__)((__attribute__((address_space(3))) void*)(smem)));
-
-  for (int vb = blockIdx.x; vb < nwg; vb += gridDim.x) {
-    const int id = xcd_remap(vb, nwg);
-    const int g = id / per_group;
-    const int gm = min(GM, nbm - g * GM);
-    const int rem = id - g * per_group;
-    const int bm = p.tile_order ? g * GM + rem / nbn : g * GM + rem % gm;
-    const int bn = p.tile_order ? rem % nbn : rem / gm;
-
-    f32x4 acc[8][8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-    // staging offsets of this tile: segment (half h, i) = rows h * 128 + (wave * 4 + i) * 8 .. + 7, lane -> (row, 16-byte chunk)
-    unsigned aoff[8], woff[8];
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int row = (wave * 4 + i) * 8 + (lane >> 3);
-        const int c = (lane & 7) ^ ((row >> 1) & 7);
-        int ga = bm * G2_BM + h * 128 + row, gw = bn * G2_BN + h * 128 + row;
-        ga = ga < p.M ? ga : p.M - 1;
-        gw = gw < p.N ? gw : p.N - 1;
-        aoff[h * 4 + i] = (unsigned)((long)ga * lda_b + c * 16);
-        woff[h * 4 + i] = (unsigned)((long)gw * ldw_b + c * 16);
-      }
-#define G4_STAGE(U)                                                                                     \
-  {                                                                                                     \
-    const unsigned sb = lds0 + ((U) & 1) * G2_BUF + wave * 4096;                                        \
-    const char* sa = Ab + (long)(U) * 128;                                                              \
-    const char* sw = Wb + (long)(U) * 128;                                                              \
-    _Pragma("unroll") for (int h = 0; h < 2; ++h)                                                       \
-    _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                     \
-      g4_glds16(sa, aoff[h * 4 + i], sb + h * G2_HALF + i * 1024);                                      \
-      g4_glds16(sw, woff[h * 4 + i], sb + (2 + h) * G2_HALF + i * 1024);                                \
-    }                                                                                                   \
-  }
-#define G4_READ(FA, FW, BUFP, OFF)                                                         \
-  _Pragma("unroll") for (int i = 0; i < 8; ++i) {                                           \
-    FW[i] = *(const bf16x8*)((BUFP) + w_base + i * 2048 + (OFF));                           \
-    FA[i] = *(const bf16x8*)((BUFP) + a_base + i * 2048 + (OFF));                           \
-  }
-// MFMAs from inline asm with the accumulators constrained to AGPRs ("+a"): left to the builtin, hipcc treats the 512
-// registers as one pool, parks fragments and addresses in AGPRs and shuttles accumulators through v_accvgpr_read / mov in
-// the K loop (seen in the ISA).  With the constraint the 256 accumulators stay in a0-a255 and the 256 VGPRs hold the two
-// fragment sets (128), the staging offsets and the addressing.
-#define G4_MFMA(FA, FW)                                                                     \
-  _Pragma("unroll") for (int i = 0; i < 8; ++i)                                             \
-  _Pragma("unroll") for (int j = 0; j < 8; ++j)                                             \
-    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc[i][j]) : "v"(FW[i]), "v"(FA[j]));
-#define G4_BARRIER()                  \
-  asm volatile("" ::: "memory");      \
-  __builtin_amdgcn_s_barrier();       \
-  asm volatile("" ::: "memory");
-
-    bf16x8 fa0[8], fw0[8], fa1[8], fw1[8];
-    // prologue: tile 0 landed (16 DMA per wave and K tile), tile 1 in flight
-    G4_STAGE(0)
-    if (nk > 1) {
-      G4_STAGE(1)
-      asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    G4_BARRIER()
-    if constexpr (ILV) {
-      // Interleaved form: every half is eight groups of {2 fragment reads of the NEXT half, (half B) 2 LDS-DMA issues of
-      // tile u + 2, 8 MFMAs of the current half}, all inline asm and therefore issued in exactly this order: the matrix
-      // pipe never waits behind a burst of issue-only instructions (a 16x16x32 MFMA holds the vector issue for 8 of its 16
-      // cycles; the reads and DMA issues ride in the other 8).
-      const unsigned abase0 = lds0 + a_base, wbase0 = lds0 + w_base;
-#define G4_RD1(FA, FW, AB, WB, I) g4_lds_read<(I) * 2048>(FW[I], WB); g4_lds_read<(I) * 2048>(FA[I], AB);
-#define G4_MF8(FA, FW, I)                                                                  \
-  _Pragma("unroll") for (int j = 0; j < 8; ++j)                                            \
-    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc[I][j]) : "v"(FW[I]), "v"(FA[j]));
-#define G4_ST2(U, I)                                                                       \
-  {                                                                                        \
-    const unsigned sb = lds0 + ((U) & 1) * G2_BUF + wave * 4096;                           \
-    const char* sa = Ab + (long)(U) * 128;                                                 \
-    const char* sw = Wb + (long)(U) * 128;                                                 \
-    g4_glds16(sa, aoff[I], sb + ((I) >> 2) * G2_HALF + ((I) & 3) * 1024);                  \
-    g4_glds16(sw, woff[I], sb + (2 + ((I) >> 2)) * G2_HALF + ((I) & 3) * 1024);            \
-  }
-#define G4_GROUP_A(I) G4_RD1(fa1, fw1, ab + off1, wb + off1, I) G4_MF8(fa0, fw0, I)
-// (the 16 DMA issues of tile u + 2 sit in the FIRST four groups: the last one then has 1.75 halves to land instead of 1)
-#define G4_GROUP_B(I)                                                                      \
-  if (more1) { G4_RD1(fa0, fw0, abn + off0, wbn + off0, I) }                               \
-  if (more2 && (I) < 4) { G4_ST2(u + 2, 2 * (I)) G4_ST2(u + 2, 2 * (I) + 1) }              \
-  G4_MF8(fa1, fw1, I)
-      {
-        const unsigned ab = abase0, wb = wbase0;
-        G4_RD1(fa0, fw0, ab + off0, wb + off0, 0) G4_RD1(fa0, fw0, ab + off0, wb + off0, 1)
-        G4_RD1(fa0, fw0, ab + off0, wb + off0, 2) G4_RD1(fa0, fw0, ab + off0, wb + off0, 3)
-        G4_RD1(fa0, fw0, ab + off0, wb + off0, 4) G4_RD1(fa0, fw0, ab + off0, wb + off0, 5)
-        G4_RD1(fa0, fw0, ab + off0, wb + off0, 6) G4_RD1(fa0, fw0, ab + off0, wb + off0, 7)
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      }
-      for (int u = 0; u < nk; ++u) {
-        const unsigned ab = abase0 + (u & 1) * G2_BUF, wb = wbase0 + (u & 1) * G2_BUF;
-        const unsigned abn = abase0 + ((u + 1) & 1) * G2_BUF, wbn = wbase0 + ((u + 1) & 1) * G2_BUF;
-        const bool more1 = u + 1 < nk, more2 = u + 2 < nk;
-        // ---- half A: reads of (u, kk = 1) under the MFMAs of (u, kk = 0)
-        G4_GROUP_A(0) G4_GROUP_A(1) G4_GROUP_A(2) G4_GROUP_A(3) G4_GROUP_A(4) G4_GROUP_A(5) G4_GROUP_A(6) G4_GROUP_A(7)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // DMA(u + 1) landed
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // the reads of buffer (u & 1) returned
-        G4_BARRIER()
-        // ---- half B: reads of (u + 1, kk = 0) and the DMA of tile u + 2 under the MFMAs of (u, kk = 1)
-        G4_GROUP_B(0) G4_GROUP_B(1) G4_GROUP_B(2) G4_GROUP_B(3) G4_GROUP_B(4) G4_GROUP_B(5) G4_GROUP_B(6) G4_GROUP_B(7)
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // fa0 / fw0 for the next half A
-      }
-#undef G4_RD1
-#undef G4_MF8
-#undef G4_ST2
-#undef G4_GROUP_A
-#undef G4_GROUP_B
-    } else {
-    G4_READ(fa0, fw0, smem, off0)
-    for (int u = 0; u < nk; ++u) {
-      const char* bp = smem + (u & 1) * G2_BUF;
-      const char* bq = smem + ((u + 1) & 1) * G2_BUF;
-      // ---- half A
-      G4_READ(fa1, fw1, bp, off1)
-      G4_MFMA(fa0, fw0)
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      G4_BARRIER()
-      // ---- half B
-      if (u + 1 < nk) { G4_READ(fa0, fw0, bq, off0) }
-      if (u + 2 < nk) { G4_STAGE(u + 2) }
-      G4_MFMA(fa1, fw1)
-    }
-    }   // !ILV
-    // the hazard recogniser does not see into the asm MFMAs: let the last ones retire before the epilogue reads AGPRs
-    asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) asm volatile("" : "+a"(acc[i][j]));     // pins the epilogue's reads behind the nops
-    // nobody reads the pipeline buffers after the last barrier: the epilogue may reuse them at once
-    const int m_base = bm * G2_BM + wm * 128, n_base = bn * G2_BN + wn * 128;
-    if constexpr (OUT_BF16) {
-      char* wl = smem + wave * G2_EPI_WAVE;
-      g2_epilogue_lds<OUT_BF16, ACT, QK>(p, *(f32x4(*)[4][8]) & acc[0], m_base, n_base, wl, lane, pos_l, cs_l);
-      g2_epilogue_lds<OUT_BF16, ACT, QK>(p, *(f32x4(*)[4][8]) & acc[4], m_base, n_base + 64, wl, lane, pos_l, cs_l);
-    } else {
-      gemm_epilogue<OUT_BF16, ACT, 8, 8>(p, acc, m_base, n_base, lane);
-    }
-    if (vb + (int)gridDim.x < nwg) { G4_BARRIER() }
-#undef G4_STAGE
-#undef G4_READ
-#undef G4_MFMA
-#undef G4_BARRIER
-  }
-}
-
-template <bool OUT_BF16, int ACT, bool QK = false, bool ILV = false>
-static int launch4w(const GemmParams& p, hipStream_t stream) {
-  const int nbm = (p.M + G2_BM - 1) / G2_BM, nbn = p.N / G2_BN;
-  auto kern = gemm4w_kernel<OUT_BF16, ACT, QK, ILV>;
-  static unsigned long long optin = 0;
-  constexpr int LDS_BYTES = QK ? G2_LDS_QK : G2_LDS_TOTAL;
-  if (int rc = pi3_lds_optin((const void*)kern, LDS_BYTES, &optin, "gemm4w")) return rc;
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-      ncu = prop.multiProcessorCount & ~7;
-    if (ncu <= 0) ncu = 256;
-  }
-  const int nwg = nbm * nbn;
-  hipLaunchKernelGGL(kern, dim3(nwg > ncu ? ncu : nwg), dim3(256), LDS_BYTES, stream, p);
-  return pi3_check_launch("gemm4w");
-}
-
+#include "gemm256_dev.inc"
 #endif   // PI3_DEV_VARIANTS
 
 // Used by pi3_gemm (gemm.hip) for bf16 operands when N % 256 == 0 and M is large.  Returns 1 if not applicable.
@@ -1367,7 +796,7 @@ int pi3_gemm256_try(const GemmParams& p, int out_dtype, int act, hipStream_t str
   {
     const int impl3 = PI3_DEV_ENV_INT("PI3_GEMM_IMPL", 0) == 3;
     const int impl4 = (int)PI3_KNOB("gemm_4w", 0);
-    const int ilv = G2_ASM_DMA ? (int)PI3_KNOB("gemm_ilv", 0) : 0;
+    const int ilv = (int)PI3_KNOB("gemm_ilv", 0);
     if (p.qk_mode) {
       if (impl4 == 2) return launch4w<true, 0, true, true>(p, stream);
       if (impl4) return launch4w<true, 0, true>(p, stream);

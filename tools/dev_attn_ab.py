@@ -3,7 +3,7 @@ of the library loaded side by side in ONE process (cards of the pool differ by +
 
     python tools/dev_attn_ab.py name=path.so[:knob=v,...] [name=path.so ...] [--rounds 6] [--online-max] [--k2-ready] [--outlier-key]
 
-Timing-only ablation builds (-DA64_ABL=n) compute wrong results by construction: never the product library."""
+Timing-only ablation builds compute wrong results by construction: never the product library."""
 import ctypes
 import os
 import sys

@@ -410,24 +410,25 @@ def focal_shift(local_points: torch.Tensor, conf: Optional[torch.Tensor], uvx: t
 
 # ----------------------------------------------------------------------------------------------- MoGe conv pyramid
 def conv3x3(img: torch.Tensor, H: int, W: int, C: int, wgt: torch.Tensor, bias: Optional[torch.Tensor],
-            out: torch.Tensor, resid: Optional[torch.Tensor] = None, act: int = ACT_NONE) -> torch.Tensor:
-    """img bf16 NHWC [H*W, ldc] (one image), wgt bf16 [N, 9*C] (C % 64 == 0) or [N, 10*32] (C == 32: ten tap slots, the
-    tenth zero); out [H*W, >=N] f32/bf16."""
+            out: torch.Tensor, resid: Optional[torch.Tensor] = None, act: int = ACT_NONE, *, B: int = 1) -> torch.Tensor:
+    """img bf16 NHWC [B*H*W, ldc] (B images, each replicate-padded on its own), wgt bf16 [N, 9*C] (C % 64 == 0) or [N, 10*32] (C == 32: ten tap slots, the
+    tenth zero); out [B*H*W, >=N] f32/bf16."""
     lib = _L.load()
     assert img.dtype in _16BIT and wgt.dtype == img.dtype and wgt.shape[1] == (320 if C == 32 else 9 * C)
-    rc = lib.pi3_conv3x3(img.data_ptr(), img.stride(0), 1, H, W, C, wgt.data_ptr(), wgt.shape[0], _L.ptr(bias),
+    rc = lib.pi3_conv3x3(img.data_ptr(), img.stride(0), B, H, W, C, wgt.data_ptr(), wgt.shape[0], _L.ptr(bias),
                          _L.ptr(resid), resid.stride(0) if resid is not None else 0, out.data_ptr(), out.stride(0),
                          _dt(img), _dt(out), act, _L.stream_ptr())
     _L.check(rc, "pi3_conv3x3")
     return out
 
 
-def groupnorm_stats(x: torch.Tensor, HW: int, C: int, G: int, stats: torch.Tensor) -> None:
+def groupnorm_stats(x: torch.Tensor, HW: int, C: int, G: int, stats: torch.Tensor, *, B: int = 1) -> None:
+    """x f32 [B*HW, ldx] -> stats f64 [B][G][2] (sum, sum of squares per group)."""
     lib = _L.load()
-    assert x.dtype == torch.float32 and stats.dtype == torch.float64 and stats.numel() >= 2 * G
-    n_ws = int(lib.pi3_groupnorm_ws_doubles(1, HW, C))
+    assert x.dtype == torch.float32 and stats.dtype == torch.float64 and stats.numel() >= 2 * B * G
+    n_ws = int(lib.pi3_groupnorm_ws_doubles(B, HW, C))
     ws = torch.empty(n_ws, device=x.device, dtype=torch.float64)     # per-block channel partials (deterministic sum)
-    rc = lib.pi3_groupnorm_stats(x.data_ptr(), x.stride(0), 1, HW, C, G, stats.data_ptr(), ws.data_ptr(), n_ws,
+    rc = lib.pi3_groupnorm_stats(x.data_ptr(), x.stride(0), B, HW, C, G, stats.data_ptr(), ws.data_ptr(), n_ws,
                                  _L.stream_ptr())
     _L.check(rc, "pi3_groupnorm_stats")
 
@@ -435,11 +436,11 @@ def groupnorm_stats(x: torch.Tensor, HW: int, C: int, G: int, stats: torch.Tenso
 ACT_LEAKY, ACT_SILU, ACT_ELU = 3, 4, 5
 
 
-def groupnorm_apply(x, HW, C, Cpad, G, stats, gamma, beta, eps, act, out) -> None:
-    """G = 0: no normalisation; gamma / beta None: no affine (InstanceNorm2d)."""
+def groupnorm_apply(x, HW, C, Cpad, G, stats, gamma, beta, eps, act, out, *, B: int = 1) -> None:
+    """G = 0: no normalisation; gamma / beta None: no affine (InstanceNorm2d).  x [B*HW, ldx], stats [B][G][2]."""
     lib = _L.load()
     assert out.dtype in _16BIT and out.shape[1] >= Cpad
-    rc = lib.pi3_groupnorm_apply(x.data_ptr(), x.stride(0), 1, HW, C, Cpad, G, _L.ptr(stats), _L.ptr(gamma),
+    rc = lib.pi3_groupnorm_apply(x.data_ptr(), x.stride(0), B, HW, C, Cpad, G, _L.ptr(stats), _L.ptr(gamma),
                                  _L.ptr(beta), float(eps), act, out.data_ptr(), out.stride(0), _dt(out), _L.stream_ptr())
     _L.check(rc, "pi3_groupnorm_apply")
 
@@ -451,18 +452,19 @@ def add_rows(x: torch.Tensor, y: torch.Tensor, rows: int, C: int) -> None:
     _L.check(rc, "pi3_add_rows")
 
 
-def convt_scatter(g: torch.Tensor, H: int, W: int, Cout: int, Cs: int, Cpad: int, out: torch.Tensor) -> None:
+def convt_scatter(g: torch.Tensor, H: int, W: int, Cout: int, Cs: int, Cpad: int, out: torch.Tensor, *,
+                  B: int = 1) -> None:
     lib = _L.load()
     assert g.dtype == torch.float32 and out.dtype in _16BIT
-    rc = lib.pi3_convt_scatter(g.data_ptr(), g.stride(0), 1, H, W, Cout, Cs, Cpad, out.data_ptr(), out.stride(0),
+    rc = lib.pi3_convt_scatter(g.data_ptr(), g.stride(0), B, H, W, Cout, Cs, Cpad, out.data_ptr(), out.stride(0),
                                _dt(out), _L.stream_ptr())
     _L.check(rc, "pi3_convt_scatter")
 
 
-def uv_affine(x, H, W, C, w, wofs, bias, uvx, uvy, accumulate: bool) -> None:
+def uv_affine(x, H, W, C, w, wofs, bias, uvx, uvy, accumulate: bool, *, B: int = 1) -> None:
     lib = _L.load()
     assert x.dtype == torch.float32 and w.dtype == torch.float32 and w.stride(1) == 1
-    rc = lib.pi3_uv_affine(x.data_ptr(), x.stride(0), 1, H, W, C, w.data_ptr(), w.stride(0), wofs, _L.ptr(bias),
+    rc = lib.pi3_uv_affine(x.data_ptr(), x.stride(0), B, H, W, C, w.data_ptr(), w.stride(0), wofs, _L.ptr(bias),
                            uvx.data_ptr(), uvy.data_ptr(), int(accumulate), _L.stream_ptr())
     _L.check(rc, "pi3_uv_affine")
 
@@ -486,7 +488,7 @@ def dense_vec(x, W, b, act, y) -> None:
 
 def moge_remap(pts, mask_logit, n, remap, mask) -> None:
     lib = _L.load()
-    rc = lib.pi3_moge_remap(pts.data_ptr(), _L.ptr(mask_logit), n, remap, mask.data_ptr(), _L.stream_ptr())
+    rc = lib.pi3_moge_remap(pts.data_ptr(), _L.ptr(mask_logit), n, remap, _L.ptr(mask), _L.stream_ptr())
     _L.check(rc, "pi3_moge_remap")
 
 

@@ -389,3 +389,68 @@ def test_overlap_block_takes_negative_view_indices_like_an_advanced_index():
             assert blk[k].shape[0] == len(frames) and torch.equal(blk[k], chunk[k][idx]), (frames, k)
         e = _and_estimated(None, chunk, frames, "cpu")
         assert torch.equal(e.bool(), chunk["track_estimated"][idx])
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# MoGe tap builders (pi3_slam_amd/moge.py) against F.interpolate on an fp32 identity: every MoGe depth goes through them
+# ---------------------------------------------------------------------------------------------------------------
+_TAP_PAIRS = [(518, 140), (476, 644), (84, 112), (112, 84), (37, 14), (64, 16), (16, 64), (23, 23), (5, 3), (3, 5), (8, 2),
+              (32, 8), (7, 1), (1, 4), (2, 1), (480, 308), (752, 406)]
+
+
+def _taps_dense(sc, w, n_in):
+    m = np.zeros((sc.shape[0], n_in), dtype=np.float64)
+    for i, (s, n) in enumerate(sc):
+        assert 0 <= s and n >= 1 and s + n <= n_in, (i, s, n)
+        m[i, s:s + n] = w[i, :n]
+        assert not w[i, n:].any()                                   # unused slots stay zero
+    return m
+
+
+def _interp_matrix(n_in, n_out, antialias):
+    """[out, in] matrix of F.interpolate(bilinear, align_corners=False) along one axis, from an fp32 identity."""
+    eye = torch.eye(n_in, dtype=torch.float32).view(1, n_in, 1, n_in)           # channel c = unit vector c along W
+    out = torch.nn.functional.interpolate(eye, size=(1, n_out), mode="bilinear", align_corners=False, antialias=antialias)
+    return out[0, :, 0, :].t().double().numpy()
+
+
+@pytest.mark.parametrize("n_in,n_out", _TAP_PAIRS)
+def test_linear_taps_antialias_equal_torchs_weights(n_in, n_out):
+    """Same fp32 formula as ATen's antialias kernel: within 2^-22 (measured worst 1.5e-8)."""
+    from pi3_slam_amd.moge import linear_taps
+    sc, w = linear_taps(n_in, n_out, True)
+    assert sc.dtype == np.int32 and w.dtype == np.float32 and sc.shape == (n_out, 2) and w.shape == (n_out, 8)
+    assert sc[:, 1].max() <= 8
+    m = _taps_dense(sc, w, n_in)
+    assert np.abs(m.sum(1) - 1.0).max() <= 2.0 ** -22
+    assert np.abs(m - _interp_matrix(n_in, n_out, True)).max() <= 2.0 ** -22
+
+
+def test_linear_taps_antialias_refuses_a_support_beyond_the_table():
+    from pi3_slam_amd.moge import linear_taps
+    with pytest.raises(AssertionError, match="antialias support exceeds the tap table"):
+        linear_taps(33, 8, True)
+
+
+@pytest.mark.parametrize("n_in,n_out", _TAP_PAIRS)
+def test_linear_taps_plain_equal_torchs_weights(n_in, n_out):
+    """Without antialias the weight is the fraction of the fp32 source coordinate; torch's CPU kernel forms it in another
+    order, so the two differ by up to the coordinate's rounding: one fp32 spacing at n_in (measured worst 3.05e-5 at
+    752 -> 406, spacing 6.1e-5)."""
+    from pi3_slam_amd.moge import linear_taps
+    sc, w = linear_taps(n_in, n_out, False)
+    assert set(np.unique(sc[:, 1])) <= {1, 2}
+    m = _taps_dense(sc, w, n_in)
+    assert np.abs(m - _interp_matrix(n_in, n_out, False)).max() <= float(np.spacing(np.float32(n_in)))
+
+
+@pytest.mark.parametrize("M,n", [(37, 22), (37, 29), (37, 37), (16, 6), (16, 8), (37, 50), (37, 60)])
+def test_bicubic_taps_dense_equal_torchs_scale_factor_path(M, n):
+    """The DINOv2 position-embedding resample: F.interpolate(scale_factor=(n + 0.1) / M, mode='bicubic') along one axis;
+    within 4e-6 (measured worst 2.3e-6)."""
+    from pi3_slam_amd.moge import bicubic_taps_dense
+    got = bicubic_taps_dense(M, n, M / (n + 0.1))
+    eye = torch.eye(M, dtype=torch.float32).view(1, M, 1, M)                    # channel c = unit vector c along W
+    out = torch.nn.functional.interpolate(eye, scale_factor=(1, (n + 0.1) / M), mode="bicubic")
+    assert out.shape[-1] == n and got.shape == (n, M) and got.dtype == np.float32
+    assert np.abs(got.astype(np.float64) - out[0, :, 0, :].t().double().numpy()).max() <= 4e-6

@@ -305,6 +305,29 @@ def test_conv3x3_narrow_and_wide_against_torch(built_lib, H, W, Ci, Co, fp32_out
     assert torch.equal(got[:, Co:], torch.zeros(H * W, Np - Co))       # padded columns: exact zeros, as the maps rely on
 
 
+@pytest.mark.parametrize("dt", DT16)
+def test_conv3x3_two_images_clamp_at_their_own_borders(built_lib, dt):
+    """B = 2 at H x W = 19 x 23: 437 pixels per image is no multiple of the 256-row tile, so the seam between the images
+    lies inside a tile; the last row of image 0 and the first of image 1 must replicate their own image, not read the
+    neighbour.  Same operands, reference and tolerance as the single-image test."""
+    from pi3_slam_amd import ops
+    dev = torch.device("cuda:0")
+    B, H, W, Ci, Co = 2, 19, 23, 32, 32
+    g = torch.Generator().manual_seed(1923)
+    x = torch.randn(B, H, W, Ci, generator=g)
+    x[1] += 2.0                                                     # a read across the seam is far outside the tolerance
+    w4 = torch.randn(Co, Ci, 3, 3, generator=g) / (3.0 * Ci ** 0.5)
+    bias = torch.randn(Co, generator=g)
+    img_bf = x.reshape(B * H * W, Ci).to(dt)
+    out = torch.full((B * H * W, Co), float("nan"), dtype=torch.float32, device=dev)
+    ops.conv3x3(img_bf.to(dev), H, W, 32, _conv_weight_rows(w4, 32, dt).to(dev), bias.to(dev), out, B=B)
+    xr = img_bf.float().reshape(B, H, W, Ci).permute(0, 3, 1, 2)
+    want = torch.nn.functional.conv2d(torch.nn.functional.pad(xr.double(), (1, 1, 1, 1), mode="replicate"),
+                                      w4.to(dt).double(), bias.double()).permute(0, 2, 3, 1).reshape(B * H * W, Co)
+    got = out.cpu().double()
+    assert torch.allclose(got, want, atol=2e-5 * max(1.0, float(want.abs().max())), rtol=0), float((got - want).abs().max())
+
+
 @pytest.mark.parametrize("M,N,K,out_bf16,act,resid", [(700, 32, 64, False, 0, True), (700, 64, 128, False, 2, False),
                                                        (513, 96, 64, True, 0, False), (257, 160, 192, True, 1, False),
                                                        (1, 32, 64, False, 0, False)])
@@ -331,37 +354,65 @@ def test_narrow_gemm_against_torch(built_lib, M, N, K, out_bf16, act, resid, dt)
     assert err <= tol * max(1.0, float(want.abs().max())), err
 
 
-@pytest.mark.parametrize("C,Cpad,G,affine,act,ld", [(32, 32, 1, True, 2, 32), (32, 64, 1, True, 4, 32), (64, 64, 2, True, 3, 64),
-                                                     (384, 384, 12, True, 2, 384), (20, 32, 20, False, 5, 32),
-                                                     (6, 32, 0, False, 2, 8), (96, 128, 3, True, 2, 96)])
+_GN_APPLY = [(32, 32, 1, True, 2, 32), (32, 64, 1, True, 4, 32), (64, 64, 2, True, 3, 64), (384, 384, 12, True, 2, 384),
+             (20, 32, 20, False, 5, 32), (6, 32, 0, False, 2, 8), (96, 128, 3, True, 2, 96)]
+# further cases: (C, Cpad, G, affine, act, ld, extra); extra: B images, `const` = a channel that holds one value `cval`
+# (2.5: sum and sum of squares are exact and the variance is exactly 0; 1.1: they round, and the variance is a rounding
+# residue of either sign that the clamp and eps absorb), `ldo` = row stride of the staging image when wider than Cpad
+_GN_APPLY_MORE = [
+    (64, 64, 2, True, 2, 72, dict(B=2, ldo=68)),
+    (20, 32, 20, False, 5, 32, dict(const=7)),                  # instance norm: y = act(0)
+    (20, 32, 20, True, 4, 24, dict(const=7, cval=1.1, ldo=36)),   # ... with an affine: y = act(beta); inexact sums
+    (6, 8, 3, True, 2, 8, dict()),                              # G > 0 with C % 4 != 0: the ragged quad under a norm
+]
+
+
+def _gn_id(case):
+    return "-".join(str(v) for v in case[:6]) + "".join(f"-{k}{v}" for k, v in (case[6] if len(case) > 6 else {}).items())
+
+
+@pytest.mark.parametrize("case", [c + (dict(),) for c in _GN_APPLY] + _GN_APPLY_MORE, ids=_gn_id)
 @pytest.mark.parametrize("dt", DT16)
-def test_groupnorm_apply_against_torch(built_lib, C, Cpad, G, affine, act, ld, dt):
+def test_groupnorm_apply_against_torch(built_lib, case, dt):
     """nn.GroupNorm(G, C) (G = C: InstanceNorm2d without affine; G = 0: no norm) + activation -> bf16 NHWC staging
-    image with zeroed pad channels."""
+    image with zeroed pad channels.  The map's pad columns [C, ld) hold NaN: neither kernel may read them."""
     from pi3_slam_amd import ops
+    C, Cpad, G, affine, act, ld, extra = case
+    B, const, ldo = extra.get("B", 1), extra.get("const"), extra.get("ldo", Cpad)
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(C * 7 + G)
     HW = 1531
-    x = torch.randn(HW, ld, generator=g) * 2 + 0.5
+    x = torch.randn(B * HW, ld, generator=g) * 2 + 0.5
+    if B > 1:
+        x[HW:] += 1.0                                               # every image its own statistics
+    if const is not None:
+        x[:, const] = extra.get("cval", 2.5)
+    x[:, C:] = float("nan")
     gamma, beta = torch.randn(C, generator=g), torch.randn(C, generator=g)
-    out = torch.full((HW, Cpad), float("nan"), dtype=dt, device=dev)
+    out = torch.full((B * HW, ldo), float("nan"), dtype=dt, device=dev)
     xd = x.to(dev)
     stats = None
     if G > 0:
-        stats = torch.empty(2 * G, device=dev, dtype=torch.float64)
-        ops.groupnorm_stats(xd, HW, C, G, stats)
+        stats = torch.empty(2 * B * G, device=dev, dtype=torch.float64)
+        ops.groupnorm_stats(xd, HW, C, G, stats, B=B)
     ops.groupnorm_apply(xd, HW, C, Cpad, G, stats, gamma.to(dev) if affine else None, beta.to(dev) if affine else None,
-                        1e-5, act, out)
-    v = x[:, :C].double().t().reshape(1, C, HW)
+                        1e-5, act, out, B=B)
+    v = x[:, :C].double().view(B, HW, C).transpose(1, 2)
     if G > 0:
         v = torch.nn.functional.group_norm(v, G, gamma.double() if affine else None, beta.double() if affine else None, 1e-5)
     fn = {2: torch.relu, 3: lambda t: torch.nn.functional.leaky_relu(t, 0.2), 4: torch.nn.functional.silu,
           5: torch.nn.functional.elu}[act]
-    want = fn(v)[0].t()
+    want = fn(v).transpose(1, 2).reshape(B * HW, C)
     got = out.float().cpu()
     tol = 1e-2 if dt == torch.bfloat16 else 1.5e-3
     assert torch.allclose(got[:, :C].double(), want, atol=tol * max(1.0, float(want.abs().max())), rtol=0)
-    assert torch.equal(got[:, C:], torch.zeros(HW, Cpad - C))
+    assert torch.equal(got[:, C:Cpad], torch.zeros(B * HW, Cpad - C))
+    assert torch.equal(out[:, Cpad:].cpu().view(torch.int16),
+                       torch.full((B * HW, ldo - Cpad), float("nan"), dtype=dt).view(torch.int16))
+    if const is not None:
+        flat = fn(beta[const].double() if affine else torch.zeros((), dtype=torch.float64))
+        assert torch.isfinite(got[:, const]).all()
+        assert torch.allclose(got[:, const].double(), flat.expand(B * HW), atol=tol * max(1.0, float(want.abs().max())), rtol=0)
 
 
 @pytest.mark.parametrize("dt", DT16)

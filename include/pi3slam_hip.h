@@ -381,6 +381,27 @@ int pi3_voxel_rehash(const void* src_table, long src_capacity, void* dst_table, 
 int pi3_voxel_extract(const void* table, long capacity, double voxel_size, unsigned long long* keys, float* points,
                       unsigned char* colors, int* weights, long max_out, unsigned long long* stats, void* stream);
 
+/* ---- multi-view depth consistency of one chunk's dense maps (csrc/dense_filter.hip): a pixel mask for
+ * pi3_voxel_fuse_pixels.  points f32 [N][H][W][3] (world), local_points f32 [N][H][W][3] (z = [..][2]), conf f32 logits
+ * [N][H][W] (or NULL), masks uint8 [N][H][W] (or NULL), poses f32 [N][4][4] cam->world row-major, fxfycxcy f32 [N][4].
+ * fp32, no contraction, every product and sum rounded on its own in the order written.
+ *   candidate: mask != 0, conf > conf_logit_thr, the three world coordinates finite, local z finite and > 0;
+ *   zplane (workspace f32 [N][H][W]) = local z of a candidate, else 0;
+ *   per candidate of frame i and neighbour j = i +- s stride (s = 1..radius, j in [0, N)), R, t = poses[j]:
+ *     d = X - t;  xc = (R00 dx + R10 dy) + R20 dz, yc and zc from columns 1 and 2;  no vote unless zc > 0 and all finite;
+ *     u = fx (xc / zc) + cx, v = fy (yc / zc) + cy;  pu = rintf(u), pv = rintf(v);  no vote unless 0 <= pu <= W - 1 and
+ *     0 <= pv <= H - 1;  zo = zplane[j][pv][pu], no vote when 0;  r = zc - zo, lim = rel_tol zo;
+ *     agree when |r| <= lim, conflict when r < -lim (view j saw through the point), else occluded: no vote;
+ *   out_mask uint8 [N][H][W] = agree >= min_views && conflict <= agree (0 for a non-candidate);
+ *   counts uint8 [N][H][W][2] = agree, conflict, saturated at 255 (or NULL);  stats: DEVICE uint64 [2] = candidates,
+ *   kept; zeroed by the call.
+ * radius in 1..16, stride >= 1, min_views in 1..2 radius, rel_tol finite and > 0, N H W < 2^31.  N == 0 zeroes stats
+ * and launches no kernel. */
+int pi3_dense_consistency(const float* points, const float* local_points, const float* conf, const unsigned char* masks,
+                          const float* poses, const float* fxfycxcy, int N, int H, int W, float conf_logit_thr,
+                          int radius, int stride, int min_views, float rel_tol, float* zplane, unsigned char* out_mask,
+                          unsigned char* counts, unsigned long long* stats, void* stream);
+
 /* ---- dense map -> camera views (csrc/render.hip): a z-buffered splat renderer for the voxel map.
  * points f32 [V][3] (the voxel centroids, in ascending key order), weights int32 [V] (or NULL: every voxel counts),
  * cams f64 [M][20] = world->camera 3x4 row-major (12), fx, fy, cx, cy, ortho flag (0 / 1), 3 spare.  zbuf uint64

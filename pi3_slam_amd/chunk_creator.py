@@ -66,6 +66,11 @@ class OfflineCreatorConfig:
     dense_voxel_size: Optional[float] = None  # set: every chunk also carries 'dense_cloud', its masked dense pointmap fused
                                               # into voxels of this edge length (dense_map.py; chunk frame)
     dense_conf_threshold: float = 0.5         # a pixel enters the dense cloud when sigmoid(conf) > this (and its mask)
+    dense_min_views: Optional[int] = None     # set (with dense_voxel_size): a pixel must also agree in depth with this many
+                                              # neighbouring frames of its chunk (dense_map.ConsistencyFilter)
+    dense_view_radius: int = 3                # neighbours i +- s * dense_view_stride, s = 1..dense_view_radius
+    dense_view_stride: int = 2
+    dense_depth_tolerance: float = 0.03       # relative depth difference that still counts as the same surface
 
 
 _UV_CACHE: Dict = {}
@@ -169,6 +174,14 @@ class OfflineChunkCreator:
         self._pinned_pool: Dict[int, List[torch.Tensor]] = {}
         # dense voxel map (opt-in): one device table, cleared and refilled per chunk on the compute stream
         self._dense_fuser = None
+        self._dense_filter = None
+        if config.dense_min_views is not None:
+            from .dense_map import ConsistencyFilter
+            self._dense_filter = ConsistencyFilter(config.dense_min_views, config.dense_view_radius,
+                                                   config.dense_view_stride, config.dense_depth_tolerance)
+            if config.dense_voxel_size is None:
+                print("⚠️  dense_min_views has no effect without dense_voxel_size: no dense cloud is built")
+        self._dense_filter_warned = False
         if config.dense_voxel_size is not None:
             from .dense_map import VoxelFuser
             # two output sets: chunk k's is read on the host while chunk k+1's extraction is queued (finish(k) always
@@ -249,6 +262,16 @@ class OfflineChunkCreator:
         fxy = r["fxfycxcy"]
         return dict(intrinsics=r["intrinsics"], focal=r["focal"][None], shift=r["shift"][None], fx=fxy[:, 0][None],
                     fy=fxy[:, 1][None], cx=fxy[:, 2][None], cy=fxy[:, 3][None])
+
+    def _queue_camera_parameters(self, pi3_result: Dict[str, torch.Tensor], out: Dict[str, torch.Tensor]) -> bool:
+        """Queue the intrinsics estimate into out['cam.*']; a failure is reported and the chunk goes on without."""
+        try:
+            for k, v in self._estimate_camera_parameters(pi3_result).items():
+                out["cam." + k] = v
+            return True
+        except Exception as e:  # noqa: BLE001
+            print(f"⚠️  Camera parameter estimation failed: {e}")
+            return False
 
     # ------------------------------------------------------------------ stage-in
     def _stage_in(self, frames, paths: List, meta: Optional[Dict] = None, kind: str = "float") -> _Staged:
@@ -372,23 +395,32 @@ class OfflineChunkCreator:
             ops.apply_scale(med[:1], pi3["local_points"], pi3["points"], pi3["camera_poses"])
             out["_scale"] = med                         # [median, masked pixel count]: checked on the host
         dense_job = None
+        cam_queued = False
         if self._dense_fuser is not None:
             # the metric points, queued before the next graph replay can reuse the static outputs; the extract writes
             # into fresh buffers that finish() copies out, the voxel count rides in the packed D2H
             fz = self._dense_fuser
             fz.clear()
-            fz.fuse_pixels(pi3["points"][0].contiguous(), pi3["conf"][0].contiguous(), masks.contiguous(),
-                           imgs[0].contiguous(), cfg.dense_conf_threshold)
+            points, conf, fuse_masks = pi3["points"][0].contiguous(), pi3["conf"][0].contiguous(), masks.contiguous()
+            if self._dense_filter is not None:
+                # the filter projects with the estimated intrinsics: their kernels go first (same stream, same results)
+                cam_queued = True
+                if cfg.estimate_camera_params and self._queue_camera_parameters(pi3, out):
+                    fxy = torch.stack([out["cam." + k][0] for k in ("fx", "fy", "cx", "cy")], dim=1)
+                    fuse_masks, out["_dense_filter_stats"] = self._dense_filter.apply(
+                        points, pi3["local_points"][0].contiguous(), conf, fuse_masks,
+                        pi3["camera_poses"][0].contiguous(), fxy, cfg.dense_conf_threshold)
+                elif not self._dense_filter_warned:      # once per run
+                    self._dense_filter_warned = True
+                    print("⚠️  dense consistency filter: no intrinsics (estimate_camera_params is off or the estimate "
+                          "failed); dense clouds without them are fused unfiltered")
+            fz.fuse_pixels(points, conf, fuse_masks, imgs[0].contiguous(), cfg.dense_conf_threshold)
             bufs, out["_dense_stats"] = fz.extract_async()
             extracted = torch.cuda.Event()
             extracted.record(cur)
             dense_job = self._dense_pool.submit(self._dense_host, bufs, out["_dense_stats"], extracted)
-        if cfg.estimate_camera_params:
-            try:
-                for k, v in self._estimate_camera_parameters(pi3).items():
-                    out["cam." + k] = v
-            except Exception as e:  # noqa: BLE001
-                print(f"⚠️  Camera parameter estimation failed: {e}")
+        if cfg.estimate_camera_params and not cam_queued:
+            self._queue_camera_parameters(pi3, out)
         out["camera_poses"] = pi3["camera_poses"][0]
         mark("scale+intrinsics queued")
 
@@ -497,7 +529,8 @@ class OfflineChunkCreator:
         if cam:
             result["intrinsics"] = cam.get("intrinsics")
         if fl.dense_job is not None:
-            result["dense_cloud"] = self._dense_cloud(fl.dense_job.result(), got["_dense_stats"], metrics)
+            result["dense_cloud"] = self._dense_cloud(fl.dense_job.result(), got["_dense_stats"], metrics,
+                                                      got.get("_dense_filter_stats"))
             fl.dense_job = None
         return result
 
@@ -514,16 +547,22 @@ class OfflineChunkCreator:
             self._dense_stream.synchronize()
         return sort_by_key(*(t.numpy() for t in h))
 
-    def _dense_cloud(self, s: Dict, stats: torch.Tensor, metrics: Dict) -> Dict:
-        """The chunk's voxel cloud from the sorted host rows; stats = the packed D2H copy of the table's counters."""
+    def _dense_cloud(self, s: Dict, stats: torch.Tensor, metrics: Dict,
+                     filter_stats: Optional[torch.Tensor] = None) -> Dict:
+        """The chunk's voxel cloud from the sorted host rows; stats = the packed D2H copy of the table's counters,
+        filter_stats = that of the consistency filter's [candidates, kept] when it ran."""
         dropped, overflow, V, lost = (int(x) for x in stats.tolist())
         if overflow or lost:
             raise RuntimeError(f"dense voxel table overflow ({overflow} / {lost}): capacity rule violated")
         assert len(s["keys"]) == V
         metrics["dense_voxels"], metrics["dense_dropped"] = V, dropped
-        return {"points": torch.from_numpy(s["points"]), "colors": torch.from_numpy(s["colors"]),
-                "weights": torch.from_numpy(s["weights"]), "voxel_size": float(self.config.dense_voxel_size),
-                "conf_threshold": float(self.config.dense_conf_threshold)}
+        cloud = {"points": torch.from_numpy(s["points"]), "colors": torch.from_numpy(s["colors"]),
+                 "weights": torch.from_numpy(s["weights"]), "voxel_size": float(self.config.dense_voxel_size),
+                 "conf_threshold": float(self.config.dense_conf_threshold)}
+        if filter_stats is not None:
+            metrics["dense_candidates"], metrics["dense_consistent"] = (int(x) for x in filter_stats.tolist())
+            cloud["consistency"] = self._dense_filter.settings()
+        return cloud
 
     # ------------------------------------------------------------------ one chunk, start to end (reference surface)
     def _process_single_chunk(self, chunk_images: torch.Tensor, chunk_paths: List[str]) -> Dict:

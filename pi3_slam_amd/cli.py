@@ -40,6 +40,11 @@ CREATE_FLAGS: Sequence[Tuple[str, Dict]] = (
     ("--dense-voxel-size", dict(type=float, default=None, help="also fuse each chunk's dense pointmap into voxels of this "
                                                                "edge length (metres): chunk['dense_cloud']")),
     ("--dense-conf-threshold", dict(type=float, default=0.5, help="pixels with sigmoid(conf) above this enter the dense map")),
+    ("--dense-min-views", dict(type=int, default=None, help="with --dense-voxel-size: keep a pixel only when this many "
+                                                            "neighbouring frames of its chunk agree with its depth")),
+    ("--dense-view-radius", dict(type=int, default=3, help="neighbours i +- s * stride, s = 1..radius (1..16)")),
+    ("--dense-view-stride", dict(type=int, default=2, help="frame step between the neighbours")),
+    ("--dense-depth-tolerance", dict(type=float, default=0.03, help="relative depth difference that still agrees")),
 )
 CREATE_SWITCHES = (("--device-resize", "Resize + ToTensor on the GPU (loader workers decode only)"),
                    ("--hip-graph", "replay the per-chunk forward as one captured hipGraph"),
@@ -99,6 +104,11 @@ ONLINE_FLAGS: Sequence[Tuple[str, Dict]] = (
     ("--num_workers", dict(type=int, default=4, help="decode threads")),
     ("--dense_voxel_size", dict(type=float, default=None, help="write dense_points.ply: the dense maps filtered by "
                                                                "--conf_threshold, fused into voxels of this size (metres)")),
+    ("--dense_min_views", dict(type=int, default=None, help="with --dense_voxel_size: keep a pixel only when this many "
+                                                            "neighbouring frames of its chunk agree with its depth")),
+    ("--dense_view_radius", dict(type=int, default=3, help="neighbours i +- s * stride, s = 1..radius (1..16)")),
+    ("--dense_view_stride", dict(type=int, default=2, help="frame step between the neighbours")),
+    ("--dense_depth_tolerance", dict(type=float, default=0.03, help="relative depth difference that still agrees")),
     ("--render_every", dict(type=int, default=None, help="with --dense_voxel_size: renders/ with depth and colour images "
                                                          "of the dense map for every N-th view and an overview")),
 )
@@ -163,7 +173,9 @@ def run_create(a: argparse.Namespace) -> None:
         num_loader_workers=a.num_workers, cam_dist_path=a.cam_dist_path, moge_model_path=a.moge_model_path,
         keypoint_seed=None if a.keypoint_seed < 0 else a.keypoint_seed, device_resize=a.device_resize,
         hip_graph=a.hip_graph, reuse_overlap_encoder=a.reuse_overlap_encoder, dense_voxel_size=a.dense_voxel_size,
-        dense_conf_threshold=a.dense_conf_threshold)
+        dense_conf_threshold=a.dense_conf_threshold, dense_min_views=a.dense_min_views,
+        dense_view_radius=a.dense_view_radius, dense_view_stride=a.dense_view_stride,
+        dense_depth_tolerance=a.dense_depth_tolerance)
     OfflineChunkCreator(cfg).process_and_save(paths[lo:hi])
 
 
@@ -216,7 +228,9 @@ def run_online(a: argparse.Namespace) -> None:
         do_metric_depth=a.do_metric_depth, model_path=a.model_path,
         use_inverse_depth=a.use_inverse_depth, moge_model_path=a.moge_model_path, hip_graph=not a.no_hip_graph,
         output_dir=out_dir, num_loader_workers=a.num_workers, bundle_adjust=not a.no_bundle_adjust,
-        reuse_overlap_encoder=a.reuse_overlap_encoder, dense_voxel_size=a.dense_voxel_size)
+        reuse_overlap_encoder=a.reuse_overlap_encoder, dense_voxel_size=a.dense_voxel_size,
+        dense_min_views=a.dense_min_views, dense_view_radius=a.dense_view_radius,
+        dense_view_stride=a.dense_view_stride, dense_depth_tolerance=a.dense_depth_tolerance)
     slam.save_transformed_reconstructions = a.save_transformed_reconstructions
     slam.save_debug_reconstructions = a.save_debug_reconstructions
     slam.process_chunks(paths)

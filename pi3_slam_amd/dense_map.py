@@ -9,12 +9,16 @@ tracks.  Here the dense maps are fused on the device into one voxel per occupied
   stage 2   fuse_chunk_clouds: every cloud moved by its chunk's accumulated similarity (ops.sim3_apply) and fused again,
             weighted by W, into the world frame (= chunk 0's frame) -> dense_points.ply.
 
+Optionally (ConsistencyFilter, csrc/dense_filter.hip) a pixel of stage 1 must also be confirmed by the depth maps of
+neighbouring frames of its chunk: the filter's pixel mask takes the place of the creator's in fuse_pixels.
+
 The accumulators are integers, so a map is bitwise reproducible and tests/dense_map_ref.py reproduces it bit for bit.
 Limitation: a cloud follows its chunk's similarity; per-view corrections of a bundle adjustment do not reach it.
 """
 from __future__ import annotations
 
 import math
+from dataclasses import dataclass
 from typing import Dict, Iterable, Optional, Tuple
 
 import numpy as np
@@ -45,6 +49,50 @@ def sort_by_key(keys: np.ndarray, points: np.ndarray, colors: np.ndarray, weight
     """The extract output in ascending key order (the device writes it in slot-claim order)."""
     order = np.argsort(keys.view(np.uint64))        # keys are unique: every sort kind gives this order
     return dict(keys=keys[order], points=points[order], colors=colors[order], weights=weights[order])
+
+
+@dataclass
+class ConsistencyFilter:
+    """Multi-view depth consistency within one chunk (csrc/dense_filter.hip): a candidate pixel of frame i is projected
+    into the frames i +- s * stride, s = 1..radius; a view whose depth there is within rel_tol agrees, a view that saw
+    a surface BEHIND the point conflicts (it looked through it), a view that saw one in front does not vote.  Kept:
+    agree >= min_views and conflict <= agree.  The defaults are a starting point, not measured optima; 0.03 is the
+    relative tolerance of the creator's depth-edge mask."""
+    min_views: int = 2
+    radius: int = 3
+    stride: int = 2
+    rel_tol: float = 0.03
+
+    def __post_init__(self):
+        for name in ("min_views", "radius", "stride"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or int(v) != v:
+                raise ValueError(f"{name} must be an integer, got {v!r}")
+            setattr(self, name, int(v))
+        self.rel_tol = float(self.rel_tol)
+        if not 1 <= self.radius <= 16:
+            raise ValueError(f"radius must be in 1..16, got {self.radius}")
+        if self.stride < 1:
+            raise ValueError(f"stride must be >= 1, got {self.stride}")
+        if not 1 <= self.min_views <= 2 * self.radius:
+            raise ValueError(f"min_views must be in 1..2*radius = 1..{2 * self.radius}, got {self.min_views}")
+        if not (self.rel_tol > 0.0 and math.isfinite(self.rel_tol)):
+            raise ValueError(f"rel_tol must be a positive finite number, got {self.rel_tol!r}")
+
+    def settings(self) -> Dict:
+        return {"min_views": self.min_views, "radius": self.radius, "stride": self.stride, "rel_tol": self.rel_tol}
+
+    def apply(self, points: torch.Tensor, local_points: torch.Tensor, conf: Optional[torch.Tensor],
+              masks: Optional[torch.Tensor], poses: torch.Tensor, fxfycxcy: torch.Tensor,
+              conf_threshold: float) -> Tuple[torch.Tensor, torch.Tensor]:
+        """One chunk's maps (N,H,W,..), poses (N,4,4) cam->world and intrinsics (N,4) on the device ->
+        (mask uint8 (N,H,W) for VoxelFuser.fuse_pixels, device stats int64 [candidates, kept])."""
+        if masks is not None and masks.dtype == torch.bool:
+            masks = masks.view(torch.uint8)
+        mask, _, stats = ops.dense_consistency(points, local_points, conf, masks, poses, fxfycxcy,
+                                               conf_logit_threshold(conf_threshold), self.radius, self.stride,
+                                               self.min_views, self.rel_tol)
+        return mask, stats
 
 
 class VoxelFuser:

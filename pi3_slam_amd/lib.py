@@ -68,6 +68,7 @@ SIGNATURES = {
     "pi3_voxel_fuse_points": [_vp, _l, _vp, _vp, _vp, _l, _f, _vp, _vp],
     "pi3_voxel_rehash": [_vp, _l, _vp, _l, _vp, _vp],
     "pi3_voxel_extract": [_vp, _l, _d, _vp, _vp, _vp, _vp, _l, _vp, _vp],
+    "pi3_dense_consistency": [_vp] * 6 + [_i, _i, _i, _f, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp],
     "pi3_render_splat": [_vp, _vp, _l, _vp, _i, _i, _i, _d, _d, _i, _d, _d, _vp, _vp, _vp],
     "pi3_render_resolve": [_vp, _vp, _l, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
     "pi3_set_knob": [C.c_char_p, _l],

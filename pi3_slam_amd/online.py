@@ -64,7 +64,8 @@ class Pi3SLAMOnline:
                  use_inverse_depth: bool = False, moge_model=None, moge_model_path: Optional[str] = None,
                  hip_graph: bool = True, output_dir: Optional[str] = None, num_loader_workers: int = 0,
                  bundle_adjust: bool = True, reuse_overlap_encoder: bool = False,
-                 dense_voxel_size: Optional[float] = None):
+                 dense_voxel_size: Optional[float] = None, dense_min_views: Optional[int] = None,
+                 dense_view_radius: int = 3, dense_view_stride: int = 2, dense_depth_tolerance: float = 0.03):
         self.use_inverse_depth = bool(use_inverse_depth)   # online_reconstructor.py:246,1018,1235
         self.chunk_length, self.overlap = int(chunk_length), int(overlap)
         self.pixel_limit = 255000 // 2
@@ -76,7 +77,9 @@ class Pi3SLAMOnline:
             estimate_camera_params=estimate_camera_params, num_loader_workers=num_loader_workers,
             pin_memory=num_loader_workers > 0, moge_model_path=moge_model_path, device_resize=True, hip_graph=hip_graph,
             reuse_overlap_encoder=reuse_overlap_encoder, dense_voxel_size=dense_voxel_size,
-            dense_conf_threshold=conf_threshold)     # --conf_threshold filters the dense map's pixels
+            dense_conf_threshold=conf_threshold,     # --conf_threshold filters the dense map's pixels
+            dense_min_views=dense_min_views, dense_view_radius=dense_view_radius, dense_view_stride=dense_view_stride,
+            dense_depth_tolerance=dense_depth_tolerance)
         self._creator = OfflineChunkCreator(cfg, model=model, moge_model=moge_model)
         self._creator.undistortion_maps = undistortion_maps
         self.rank, self.world = self._creator.rank, self._creator.world

@@ -685,6 +685,39 @@ def voxel_extract(table: torch.Tensor, stats: torch.Tensor, voxel_size: float, m
     return keys, pts, cols, w
 
 
+def dense_consistency(points: torch.Tensor, local_points: torch.Tensor, conf: Optional[torch.Tensor],
+                      masks: Optional[torch.Tensor], poses: torch.Tensor, fxfycxcy: torch.Tensor, conf_logit_thr: float,
+                      radius: int, stride: int, min_views: int, rel_tol: float, want_counts: bool = False):
+    """Multi-view depth consistency of one chunk (csrc/dense_filter.hip).  points / local_points f32 (N,H,W,3), conf f32
+    logits (N,H,W[,1]), masks uint8/bool (N,H,W), poses f32 (N,4,4) cam->world, fxfycxcy f32 (N,4) ->
+    (out_mask uint8 (N,H,W), counts uint8 (N,H,W,2) [agree, conflict] or None, stats int64 (2,) [candidates, kept])."""
+    lib = _L.load()
+    N, H, W = (int(x) for x in points.shape[:3])
+    dev = points.device
+    assert points.dtype == torch.float32 and points.is_contiguous() and points.ndim == 4 and points.shape[3] == 3
+    assert local_points.dtype == torch.float32 and local_points.is_contiguous() and local_points.shape == points.shape
+    assert poses.dtype == torch.float32 and poses.is_contiguous() and tuple(poses.shape) == (N, 4, 4)
+    assert fxfycxcy.dtype == torch.float32 and fxfycxcy.is_contiguous() and tuple(fxfycxcy.shape) == (N, 4)
+    assert local_points.device == dev and poses.device == dev and fxfycxcy.device == dev
+    if conf is not None:
+        assert conf.dtype == torch.float32 and conf.is_contiguous() and conf.numel() == N * H * W and conf.device == dev
+    if masks is not None:
+        assert masks.dtype in (torch.uint8, torch.bool) and masks.is_contiguous() and masks.numel() == N * H * W
+        assert masks.device == dev
+    zplane = torch.empty(N, H, W, device=dev, dtype=torch.float32)
+    out_mask = torch.empty(N, H, W, device=dev, dtype=torch.uint8)
+    counts = torch.empty(N, H, W, 2, device=dev, dtype=torch.uint8) if want_counts else None
+    stats = torch.zeros(2, device=dev, dtype=torch.int64)
+    if N * H * W == 0:          # empty tensors have no address to pass
+        return out_mask, counts, stats
+    rc = lib.pi3_dense_consistency(points.data_ptr(), local_points.data_ptr(), _L.ptr(conf), _L.ptr(masks),
+                                   poses.data_ptr(), fxfycxcy.data_ptr(), N, H, W, float(conf_logit_thr), int(radius),
+                                   int(stride), int(min_views), float(rel_tol), zplane.data_ptr(), out_mask.data_ptr(),
+                                   _L.ptr(counts), stats.data_ptr(), _L.stream_ptr())
+    _L.check(rc, "pi3_dense_consistency")
+    return out_mask, counts, stats
+
+
 # ---------------------------------------------------------------------------------------------------- map renderer
 RENDER_CAM_DOUBLES = 20     # world->camera 3x4 row-major, fx, fy, cx, cy, ortho flag, 3 spare (csrc/render.hip)
 

@@ -6,7 +6,14 @@
      mask edit, device resize of 512x384 uint8 frames, grid keypoints), alternated in one process, 4 chunks per leg after
      one warm-up chunk per creator, 3 rounds (dense confidence threshold 0.05: see --conf-threshold).
 
-Prints one JSON line.  Usage: python tools/dense_fusion_timing.py [--voxel 0.02] [--rounds 3] [--chunks 4]"""
+  3. --consistency: the multi-view depth consistency filter (csrc/dense_filter.hip) with its defaults on the same
+     100 x 308 x 406 chunk (the scene's true intrinsics), HIP events, median of 20 after 3 warm-up runs, with the bytes
+     it must move (pass A: mask 1 + conf 4 + points 12 + local z 4 read, zplane 4 written; pass B: zplane 4 read, mask 1
+     written, and per candidate its point 12 and one 4-byte gather per neighbour in range) and the rate that gives
+     against the 8 TB/s HBM figure of profiles/ - a lower bound of the traffic: local z sits at a 12-byte stride, so
+     whole lines of local_points are fetched (about 12 B per pixel, not 4), and a gather fetches a line, not 4 bytes; and the creator leg a third time with the filter on.
+
+Prints one JSON line.  Usage: python tools/dense_fusion_timing.py [--voxel 0.02] [--rounds 3] [--chunks 4] [--consistency]"""
 from __future__ import annotations
 
 import argparse
@@ -67,7 +74,42 @@ def kernel_times(voxel: float, dev: str, reps: int = 20):
         "table_slots": fz.capacity, "table_bytes": fz.capacity * 64}
 
 
-def creator_fps(voxel: float, dev: str, rounds: int, chunks: int, conf_threshold: float):
+def consistency_times(dev: str, reps: int = 20):
+    """pi3_dense_consistency at the bench chunk with ConsistencyFilter's defaults."""
+    import synth_sequence as ss
+    from pi3_slam_amd import ops
+    from pi3_slam_amd.chunk_creator import OfflineChunkCreator
+    from pi3_slam_amd.dense_map import ConsistencyFilter, conf_logit_threshold
+    seq = ss.SyntheticSequence(os.path.join(ROOT, "tests", "golden", "gt_7scenes_chess.txt"), noise=dict(ss.NOISE_BF16))
+    out = ss.SceneEngine(seq)(seq.frames(1, dev))
+    masks = OfflineChunkCreator._compute_masks(out)[0].contiguous().view(torch.uint8)
+    pts, lp, conf = (out[k][0].contiguous() for k in ("points", "local_points", "conf"))
+    poses = out["camera_poses"][0].contiguous()
+    N = int(pts.shape[0])
+    K = torch.tensor([seq.fx, seq.fy, seq.cx, seq.cy], dtype=torch.float32, device=dev).repeat(N, 1).contiguous()
+    f = ConsistencyFilter()
+    thr = conf_logit_threshold(0.5)
+    ms = []
+    for i in range(3 + reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        mask, _, stats = ops.dense_consistency(pts, lp, conf, masks, poses, K, thr, f.radius, f.stride, f.min_views, f.rel_tol)
+        b.record()
+        torch.cuda.synchronize()
+        if i >= 3:
+            ms.append(a.elapsed_time(b))
+    cand, kept = (int(x) for x in stats.tolist())
+    n = int(mask.numel())
+    # neighbours in range per frame (the gathers that are issued at most: a projection outside the image issues none)
+    nb = sum(0 <= i + sg * s * f.stride < N for i in range(N) for s in range(1, f.radius + 1) for sg in (-1, 1)) / N
+    bytes_moved = n * (1 + 4 + 12 + 4 + 4) + n * (4 + 1) + cand * (12 + 4 * nb)
+    t = float(np.median(ms))
+    return {"consistency_ms": t, "min_ms": float(np.min(ms)), "max_ms": float(np.max(ms)), "pixels": n, "candidates": cand,
+            "kept": kept, "neighbours_in_range_per_pixel": nb, "bytes": int(bytes_moved),
+            "achieved_TBps": bytes_moved / (t * 1e-3) / 1e12, "settings": f.settings()}
+
+
+def creator_fps(voxel: float, dev: str, rounds: int, chunks: int, conf_threshold: float, consistency: bool = False):
     from pi3_slam_amd.chunk_creator import OfflineChunkCreator, OfflineCreatorConfig
     from pi3_slam_amd.engine import Pi3Engine
     from pi3_slam_amd.weights import Pi3Config
@@ -80,11 +122,12 @@ def creator_fps(voxel: float, dev: str, rounds: int, chunks: int, conf_threshold
     frames = synthetic_frames_u8(CL, SRC_H, SRC_W, 1234)
     tmp = tempfile.mkdtemp(prefix="dense_timing_")
     creators = {}
-    for name, vs in (("off", None), ("on", voxel)):
+    legs = (("off", None, None), ("on", voxel, None)) + ((("filtered", voxel, 2),) if consistency else ())
+    for name, vs, mv in legs:
         cc = OfflineCreatorConfig(model_path="recipe", output_dir=os.path.join(tmp, name), chunk_length=CL, overlap=OV,
                                   device=dev, do_metric_depth=False, keypoint_type="grid", max_num_keypoints=KP,
                                   num_loader_workers=0, device_resize=True, dense_voxel_size=vs,
-                                  dense_conf_threshold=conf_threshold)
+                                  dense_conf_threshold=conf_threshold, dense_min_views=mv)
         cr = OfflineChunkCreator(cc, model=engine)
         cr.target_size = (H, W)
         creators[name] = cr
@@ -100,11 +143,11 @@ def creator_fps(voxel: float, dev: str, rounds: int, chunks: int, conf_threshold
 
     for cr in creators.values():
         leg(cr, 1)                                            # warm-up: first-use allocations, the 2 GiB table
-    fps = {"off": [], "on": []}
-    host = {"off": [], "on": []}
+    fps = {name: [] for name in creators}
+    host = {name: [] for name in creators}
     voxels = []
     for _ in range(rounds):
-        for name in ("off", "on"):
+        for name in creators:
             f, v, hs = leg(creators[name], chunks)
             fps[name].append(f)
             host[name].append(hs)
@@ -115,8 +158,12 @@ def creator_fps(voxel: float, dev: str, rounds: int, chunks: int, conf_threshold
     # chunk's kernels, finish = waiting for its results and building its dict (with the map on: the dense cloud's
     # copy + key sort, which runs on a thread of its own from the end of the chunk's extraction)
     host_ms = {name: {k: 1e3 * float(np.median([h[k] for h in host[name]])) for k in host[name][0]} for name in host}
-    return {"fps_off": fps["off"], "fps_on": fps["on"], "median_fps_off": off, "median_fps_on": on,
-            "cost_pct": 100.0 * (off - on) / off, "voxels_per_chunk": voxels[:1], "host_ms_per_chunk": host_ms}
+    res = {"fps_off": fps["off"], "fps_on": fps["on"], "median_fps_off": off, "median_fps_on": on,
+           "cost_pct": 100.0 * (off - on) / off, "voxels_per_chunk": voxels[:1], "host_ms_per_chunk": host_ms}
+    if consistency:
+        flt = float(np.median(fps["filtered"]))
+        res.update(fps_filtered=fps["filtered"], median_fps_filtered=flt, filter_cost_pct=100.0 * (on - flt) / on)
+    return res
 
 
 def main():
@@ -128,12 +175,16 @@ def main():
                     help="creator leg: the edited recipe weights put few pixels above sigmoid 0.5; 0.05 lets the "
                          "creator's masked pixels through, so the fusion does real work")
     ap.add_argument("--kernels-only", action="store_true")
+    ap.add_argument("--consistency", action="store_true", help="also time the multi-view consistency filter (kernel and "
+                                                               "a creator leg with it on)")
     a = ap.parse_args()
     dev = "cuda:0"
     torch.cuda.set_device(0)
     out = {"voxel_size": a.voxel, "kernels": kernel_times(a.voxel, dev)}
+    if a.consistency:
+        out["consistency"] = consistency_times(dev)
     if not a.kernels_only:
-        out["creator"] = creator_fps(a.voxel, dev, a.rounds, a.chunks, a.conf_threshold)
+        out["creator"] = creator_fps(a.voxel, dev, a.rounds, a.chunks, a.conf_threshold, a.consistency)
     print(json.dumps(out))
 
 

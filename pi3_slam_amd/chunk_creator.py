@@ -31,6 +31,7 @@ import torch
 from torch.utils.data import DataLoader
 
 from . import ops
+from .dense_map import ChunkCloudBuilder
 from .engine import Pi3Engine
 from .image_io import ChunkImageDataset, ThreadedChunkLoader, calculate_target_size, ingest_frames_device
 from .hostmem import clone_host, full_host, zeros_host
@@ -94,6 +95,30 @@ def _uv_tables_build(H: int, W: int, device) -> Tuple[torch.Tensor, torch.Tensor
     return u.to(device), v.to(device)
 
 
+_Layout = List[Tuple[str, torch.dtype, tuple, int, int]]       # (key, dtype, shape, offset, nbytes) per packed tensor
+
+
+def pack_results(out: Dict[str, torch.Tensor]) -> Tuple[torch.Tensor, _Layout]:
+    """Every tensor of `out` as bytes in ONE uint8 buffer on their device, each at a 16-byte aligned offset ->
+    (packed, layout in `out`'s order): one copy brings all of them to the host."""
+    layout, parts, off = [], [], 0
+    for k, t in out.items():
+        b = t.contiguous().view(torch.uint8).reshape(-1)
+        pad = (-b.numel()) % 16
+        layout.append((k, t.dtype, tuple(t.shape), off, b.numel()))
+        parts.append(b)
+        if pad:
+            parts.append(torch.zeros(pad, dtype=torch.uint8, device=b.device))
+        off += b.numel() + pad
+    return torch.cat(parts), layout
+
+
+def unpack_results(host_bytes: torch.Tensor, layout: _Layout) -> Dict[str, torch.Tensor]:
+    """The tensors of pack_results from a host copy of its buffer, each in storage of its own (memcpy, no ATen operator:
+    hostmem.py)."""
+    return {k: clone_host(host_bytes[off:off + nbytes]).view(dt).reshape(shape) for k, dt, shape, off, nbytes in layout}
+
+
 @dataclass
 class _Staged:
     """A chunk whose frames are on the device, or on their way there on the copy stream."""
@@ -111,14 +136,14 @@ class _InFlight:
     forward would sit at the head of the copy engine's queue for the whole forward and hold up every other device->host
     copy of the process (the alignment of the previous chunk waited 420 ms for its 33 doubles that way)."""
     packed: Optional[torch.Tensor]
-    layout: List[Tuple[str, torch.dtype, tuple, int, int]]
+    layout: _Layout
     done: torch.cuda.Event
     timing: Dict[str, torch.cuda.Event]
     host: Dict                               # values that never left the host (paths, zero descriptors, ...)
     dense: Optional[Dict[str, torch.Tensor]]  # device tensors of the no-keypoint fallback (copied in finish)
     meta: Dict
     t_launch: float = 0.0
-    dense_job: Optional[object] = None       # Future of the dense voxel cloud's host copy + key sort (_dense_host)
+    dense_job: Optional[object] = None       # the dense voxel cloud's host job (dense_map.ChunkCloudBuilder.queue)
 
 
 class OfflineChunkCreator:
@@ -172,25 +197,11 @@ class OfflineChunkCreator:
         self._moge_stream = torch.cuda.Stream(self.device)
         self._d2h_stream = torch.cuda.Stream(self.device)
         self._pinned_pool: Dict[int, List[torch.Tensor]] = {}
+        self._last_forward_end: Optional[torch.cuda.Event] = None
+        self.host_seconds: Dict[str, float] = {}     # of the last process_chunks: the pipeline thread's time per stage
+        self.last_run: Dict = {}                     # of the last process_and_save
         # dense voxel map (opt-in): one device table, cleared and refilled per chunk on the compute stream
-        self._dense_fuser = None
-        self._dense_filter = None
-        if config.dense_min_views is not None:
-            from .dense_map import ConsistencyFilter
-            self._dense_filter = ConsistencyFilter(config.dense_min_views, config.dense_view_radius,
-                                                   config.dense_view_stride, config.dense_depth_tolerance)
-            if config.dense_voxel_size is None:
-                print("⚠️  dense_min_views has no effect without dense_voxel_size: no dense cloud is built")
-        self._dense_filter_warned = False
-        if config.dense_voxel_size is not None:
-            from .dense_map import VoxelFuser
-            # two output sets: chunk k's is read on the host while chunk k+1's extraction is queued (finish(k) always
-            # completes before launch(k+2))
-            self._dense_fuser = VoxelFuser(config.dense_voxel_size, self.device, out_sets=2)
-            # the cloud's copy + key sort run on this thread as soon as the chunk's extraction is done, beside the host's
-            # launch of the next chunk instead of in front of it
-            self._dense_pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="dense-cloud")
-            self._dense_stream = torch.cuda.Stream(self.device)
+        self._dense = ChunkCloudBuilder.from_config(config, self.device)
 
     @staticmethod
     def _optional(what: str, make):
@@ -226,9 +237,8 @@ class OfflineChunkCreator:
                       mask: torch.Tensor) -> torch.Tensor:
         """Device tensor [median(moge/pi3 over the mask), number of masked pixels]."""
         assert pi3_metric_depth.stride(-1) in (1, 3)
-        m8 = mask.contiguous().view(torch.uint8) if mask.dtype == torch.bool else mask.contiguous()
         return ops.masked_ratio_median(moge_metric_depth.contiguous(), pi3_metric_depth, pi3_metric_depth.stride(-1),
-                                       m8, moge_metric_depth.numel())
+                                       mask.contiguous(), moge_metric_depth.numel())
 
     @classmethod
     def _get_scale_factor_for_pi3(cls, moge_metric_depth: torch.Tensor, pi3_metric_depth: torch.Tensor,
@@ -241,14 +251,12 @@ class OfflineChunkCreator:
     def _interpolate_world_points_for_keypoints(result_dense: Dict, keypoints: torch.Tensor) -> Dict[str, torch.Tensor]:
         """offline_chunk_creator.py:129-159 (+ the fp16 pack of :231-241), on the device."""
         dev = result_dense["points"].device
-        masks = result_dense["masks"]
-        m8 = masks.contiguous().view(torch.uint8) if masks.dtype == torch.bool else masks.contiguous()
         images = result_dense.get("images")
         if not keypoints.is_cuda:     # through pinned memory: an asynchronous upload, the host does not wait for the GPU
             kp_host = keypoints.to(torch.float32).contiguous()
             keypoints = (kp_host.pin_memory() if torch.cuda.is_available() else kp_host).to(dev, non_blocking=True)
         return ops.gather_keypoints(result_dense["points"].contiguous(), result_dense["local_points"].contiguous(),
-                                    result_dense["conf"].contiguous(), m8,
+                                    result_dense["conf"].contiguous(), result_dense["masks"].contiguous(),
                                     images.contiguous() if images is not None else None,
                                     keypoints.to(dev, torch.float32).contiguous())
 
@@ -263,15 +271,13 @@ class OfflineChunkCreator:
         return dict(intrinsics=r["intrinsics"], focal=r["focal"][None], shift=r["shift"][None], fx=fxy[:, 0][None],
                     fy=fxy[:, 1][None], cx=fxy[:, 2][None], cy=fxy[:, 3][None])
 
-    def _queue_camera_parameters(self, pi3_result: Dict[str, torch.Tensor], out: Dict[str, torch.Tensor]) -> bool:
+    def _queue_camera_parameters(self, pi3_result: Dict[str, torch.Tensor], out: Dict[str, torch.Tensor]) -> None:
         """Queue the intrinsics estimate into out['cam.*']; a failure is reported and the chunk goes on without."""
         try:
             for k, v in self._estimate_camera_parameters(pi3_result).items():
                 out["cam." + k] = v
-            return True
         except Exception as e:  # noqa: BLE001
             print(f"⚠️  Camera parameter estimation failed: {e}")
-            return False
 
     # ------------------------------------------------------------------ stage-in
     def _stage_in(self, frames, paths: List, meta: Optional[Dict] = None, kind: str = "float") -> _Staged:
@@ -301,20 +307,9 @@ class OfflineChunkCreator:
         return _Staged(imgs, ready, paths, meta, keep=(frames,))
 
     # ------------------------------------------------------------------ launch
-    def _pinned(self, nbytes: int) -> torch.Tensor:
-        pool = self._pinned_pool.setdefault(nbytes, [])
-        return pool.pop() if pool else torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
-
     def _launch(self, st: _Staged, chunk_images_for_kp: Optional[torch.Tensor] = None) -> _InFlight:
-        """Queue every kernel of one chunk plus the packed D2H; returns without waiting for the GPU."""
-        cfg, dev = self.config, self.device
-        trace = [] if os.environ.get("PI3_TRACE") else None
-
-        def mark(tag):
-            if trace is not None:
-                trace.append((tag, time.perf_counter()))
-        mark("begin")
-        cur = torch.cuda.current_stream(dev)
+        """Queue every kernel of one chunk and pack its small results; returns without waiting for the GPU."""
+        cur = torch.cuda.current_stream(self.device)
         if st.ready is not None:
             cur.wait_event(st.ready)
         imgs = st.imgs
@@ -322,181 +317,186 @@ class OfflineChunkCreator:
         N = int(imgs.shape[1])
         ev = {k: torch.cuda.Event(enable_timing=True) for k in ("f0", "f1", "post")}
 
-        # MoGe needs only the first frame: it runs beside the pi3 forward instead of after it (400 small
-        # single-image kernels that would otherwise run on an idle GPU)
-        moge_depth = None
-        if self.moge_model is not None:
-            if st.ready is not None:
-                self._moge_stream.wait_event(st.ready)
+        moge_depth = self._queue_moge(st, cur)
+        kp, kp_dev, kp_err = self._queue_keypoints(chunk_images_for_kp if chunk_images_for_kp is not None else imgs, cur)
+        reuse = self._overlap_reuse(st.paths, N)
+        ev["f0"].record(cur)
+        pi3 = self._queue_forward(imgs, reuse)
+        ev["f1"].record(cur)
+
+        out: Dict[str, torch.Tensor] = {}       # the small device tensors of the packed copy
+        masks = self._compute_masks(pi3)[0]
+        if moge_depth is not None:
+            self._queue_metric_scale(pi3, masks, moge_depth, cur, out)
+        if self.config.estimate_camera_params:
+            self._queue_camera_parameters(pi3, out)
+        dense_job = self._queue_dense_cloud(pi3, masks, imgs, out) if self._dense is not None else None
+        out["camera_poses"] = pi3["camera_poses"][0]
+        host = self._queue_gather(pi3, masks, imgs, kp, kp_dev, kp_err, out) if self.keypoint_extractor is not None else {}
+        dense = None if "points" in out else self._dense_fallback(pi3, masks)
+        ev["post"].record(cur)
+
+        packed, layout = pack_results(out)
+        done = torch.cuda.Event()
+        done.record(cur)
+        return _InFlight(packed, layout, done, ev, host, dense, dict(st.meta, paths=st.paths, num_frames=N),
+                         t_launch=time.time(), dense_job=dense_job)
+
+    def _queue_moge(self, st: _Staged, cur: torch.cuda.Stream) -> Optional[torch.Tensor]:
+        """MoGe needs only the first frame: it runs beside the pi3 forward instead of after it (400 small
+        single-image kernels that would otherwise run on an idle GPU).  -> its depth map, or None without MoGe."""
+        if self.moge_model is None:
+            return None
+        if st.ready is not None:
+            self._moge_stream.wait_event(st.ready)
+        else:
+            self._moge_stream.wait_stream(cur)
+        with torch.cuda.stream(self._moge_stream):
+            graphed = (self.config.hip_graph and hasattr(self.moge_model, "infer_graphed")
+                       and os.environ.get("PI3_MOGE_GRAPH", "1") != "0")
+            if graphed:
+                # the graph's output is ONE static buffer, and chunk k+1's replay is queued on this stream while
+                # chunk k's forward still runs on the compute stream (this stream waits for the stage-in only):
+                # without a private copy, chunk k's scale would be taken from chunk k+1's first frame.
+                # record_stream does not protect graph-pool memory, a copy does.
+                moge_depth = self.moge_model.infer_graphed(st.imgs[0, 0])["depth"].clone()
             else:
-                self._moge_stream.wait_stream(cur)
-            with torch.cuda.stream(self._moge_stream):
-                graphed = (cfg.hip_graph and hasattr(self.moge_model, "infer_graphed")
-                           and os.environ.get("PI3_MOGE_GRAPH", "1") != "0")
-                if graphed:
-                    # the graph's output is ONE static buffer, and chunk k+1's replay is queued on this stream while
-                    # chunk k's forward still runs on the compute stream (this stream waits for the stage-in only):
-                    # without a private copy, chunk k's scale would be taken from chunk k+1's first frame.
-                    # record_stream does not protect graph-pool memory, a copy does.
-                    moge_depth = self.moge_model.infer_graphed(imgs[0, 0])["depth"].clone()
-                else:
-                    moge_depth = self.moge_model.infer(imgs[0, 0])["depth"]
-            moge_depth.record_stream(cur)
-        mark("moge queued")
+                moge_depth = self.moge_model.infer(st.imgs[0, 0])["depth"]
+        moge_depth.record_stream(cur)
+        return moge_depth
 
-        # keypoints depend on the frame size only: extracted now and uploaded on the copy stream (idle at this point).
-        # Queued on the compute stream the upload would wait behind the forward at the head of the H2D engine's queue
-        # and hold up every other upload of the process, e.g. the previous chunk's alignment beside this forward.
-        kp = kp_dev = kp_err = None
-        if self.keypoint_extractor is not None:
-            try:
-                kp = self.keypoint_extractor.extract(chunk_images_for_kp if chunk_images_for_kp is not None else imgs)
-                kp_dev = kp["keypoints"]
-                if not kp_dev.is_cuda:
-                    kp_host = kp_dev.to(torch.float32).contiguous().pin_memory()
-                    with torch.cuda.stream(self._copy_stream):
-                        kp_dev = kp_host.to(dev, non_blocking=True)
-                        kp_ready = torch.cuda.Event()
-                        kp_ready.record(self._copy_stream)
-                    cur.wait_event(kp_ready)
-                    kp_dev.record_stream(cur)
-            except Exception as e:  # noqa: BLE001
-                kp_err = e
-        mark("keypoints queued")
+    def _queue_keypoints(self, images: torch.Tensor, cur: torch.cuda.Stream):
+        """Keypoints depend on the frame size only: extracted now and uploaded on the copy stream (idle at this point).
+        Queued on the compute stream the upload would wait behind the forward at the head of the H2D engine's queue
+        and hold up every other upload of the process, e.g. the previous chunk's alignment beside this forward.
+        -> (the extractor's dict, device keypoints, the exception that _queue_gather reports instead of gathering)."""
+        if self.keypoint_extractor is None:
+            return None, None, None
+        try:
+            kp = self.keypoint_extractor.extract(images)
+            kp_dev = kp["keypoints"]
+            if not kp_dev.is_cuda:
+                kp_host = kp_dev.to(torch.float32).contiguous().pin_memory()
+                with torch.cuda.stream(self._copy_stream):
+                    kp_dev = kp_host.to(self.device, non_blocking=True)
+                    kp_ready = torch.cuda.Event()
+                    kp_ready.record(self._copy_stream)
+                cur.wait_event(kp_ready)
+                kp_dev.record_stream(cur)
+            return kp, kp_dev, None
+        except Exception as e:  # noqa: BLE001
+            return None, None, e
 
-        # overlap reuse (opt-in): the SAME files at the head of this chunk as at the tail of the one launched before it
+    def _overlap_reuse(self, paths: Optional[List], N: int) -> Dict[str, int]:
+        """Overlap reuse (opt-in): the SAME files at the head of this chunk as at the tail of the one launched before
+        it.  -> the forward's keyword arguments, {} when nothing is reused or kept."""
         rh = kt = 0
-        ov = int(cfg.overlap)
-        if cfg.reuse_overlap_encoder and getattr(self.model, "supports_overlap_reuse", False) and 0 < ov < N \
-                and st.paths is not None and len(st.paths) == N:
-            names = [str(p) for p in st.paths]
+        ov = int(self.config.overlap)
+        if self.config.reuse_overlap_encoder and getattr(self.model, "supports_overlap_reuse", False) and 0 < ov < N \
+                and paths is not None and len(paths) == N:
+            names = [str(p) for p in paths]
             rh = ov if self._tail_paths == names[:ov] else 0
             kt, self._tail_paths = ov, names[-ov:]
         else:
             self._tail_paths = None
-        reuse = dict(reuse_head=rh, keep_tail=kt) if (rh or kt) else {}
         self.reused_frames += rh
+        return dict(reuse_head=rh, keep_tail=kt) if (rh or kt) else {}
 
-        ev["f0"].record(cur)
+    def _queue_forward(self, imgs: torch.Tensor, reuse: Dict[str, int]) -> Dict[str, torch.Tensor]:
         # the graph of a shape costs one eager run + one capture the first time: worth it for the nominal chunk shape, which
         # repeats, not for the ragged last chunk of a sequence (in a 4 000-frame stream its capture was 2.6 % of the run)
-        if cfg.hip_graph and hasattr(self.model, "forward_graphed") and N == int(cfg.chunk_length):
-            pi3 = self.model.forward_graphed(imgs, **reuse)     # static outputs: packed below, before the next replay
-        else:
-            pi3 = self.model(imgs, **reuse)
-        ev["f1"].record(cur)
-        mark("forward queued")
+        if self.config.hip_graph and hasattr(self.model, "forward_graphed") \
+                and int(imgs.shape[1]) == int(self.config.chunk_length):
+            return self.model.forward_graphed(imgs, **reuse)     # static outputs: packed before the next replay
+        return self.model(imgs, **reuse)
 
-        masks = self._compute_masks(pi3)[0]
-        out: Dict[str, torch.Tensor] = {}
-        if moge_depth is not None:
-            cur.wait_stream(self._moge_stream)
-            med = self._ratio_median(moge_depth, pi3["local_points"][0, 0][..., 2], masks[0])
-            ops.apply_scale(med[:1], pi3["local_points"], pi3["points"], pi3["camera_poses"])
-            out["_scale"] = med                         # [median, masked pixel count]: checked on the host
-        dense_job = None
-        cam_queued = False
-        if self._dense_fuser is not None:
-            # the metric points, queued before the next graph replay can reuse the static outputs; the extract writes
-            # into fresh buffers that finish() copies out, the voxel count rides in the packed D2H
-            fz = self._dense_fuser
-            fz.clear()
-            points, conf, fuse_masks = pi3["points"][0].contiguous(), pi3["conf"][0].contiguous(), masks.contiguous()
-            if self._dense_filter is not None:
-                # the filter projects with the estimated intrinsics: their kernels go first (same stream, same results)
-                cam_queued = True
-                if cfg.estimate_camera_params and self._queue_camera_parameters(pi3, out):
-                    fxy = torch.stack([out["cam." + k][0] for k in ("fx", "fy", "cx", "cy")], dim=1)
-                    fuse_masks, out["_dense_filter_stats"] = self._dense_filter.apply(
-                        points, pi3["local_points"][0].contiguous(), conf, fuse_masks,
-                        pi3["camera_poses"][0].contiguous(), fxy, cfg.dense_conf_threshold)
-                elif not self._dense_filter_warned:      # once per run
-                    self._dense_filter_warned = True
-                    print("⚠️  dense consistency filter: no intrinsics (estimate_camera_params is off or the estimate "
-                          "failed); dense clouds without them are fused unfiltered")
-            fz.fuse_pixels(points, conf, fuse_masks, imgs[0].contiguous(), cfg.dense_conf_threshold)
-            bufs, out["_dense_stats"] = fz.extract_async()
-            extracted = torch.cuda.Event()
-            extracted.record(cur)
-            dense_job = self._dense_pool.submit(self._dense_host, bufs, out["_dense_stats"], extracted)
-        if cfg.estimate_camera_params and not cam_queued:
-            self._queue_camera_parameters(pi3, out)
-        out["camera_poses"] = pi3["camera_poses"][0]
-        mark("scale+intrinsics queued")
+    def _queue_metric_scale(self, pi3: Dict[str, torch.Tensor], masks: torch.Tensor, moge_depth: torch.Tensor,
+                            cur: torch.cuda.Stream, out: Dict[str, torch.Tensor]) -> None:
+        """Rescale points, local points and poses in place by median(MoGe depth / pi3 depth) over frame 0's mask."""
+        cur.wait_stream(self._moge_stream)
+        med = self._ratio_median(moge_depth, pi3["local_points"][0, 0][..., 2], masks[0])
+        ops.apply_scale(med[:1], pi3["local_points"], pi3["points"], pi3["camera_poses"])
+        out["_scale"] = med                         # [median, masked pixel count]: checked on the host
 
-        host: Dict = {}
-        dense = None
-        if self.keypoint_extractor is not None:
-            try:
-                if kp_err is not None:
-                    raise kp_err
-                g = self._interpolate_world_points_for_keypoints(
-                    dict(points=pi3["points"][0], local_points=pi3["local_points"][0], conf=pi3["conf"][0],
-                         masks=masks, images=imgs[0]), kp_dev)
-                for k in ("points", "local_points", "conf", "keypoints", "colors"):
-                    out[k] = g[k]
-                out["masks"] = g["masks"].view(torch.uint8)
-                if kp.get("constant"):     # all-zero descriptors, all-one scores (keypoint_extraction.py:150-151)
-                    # fresh calloc'ed zeros / a small filled array per chunk (callers own and may mutate their chunk)
-                    host["descriptors"] = zeros_host(kp["descriptors"].shape, torch.float16)
-                    host["scores"] = full_host(kp["scores"].shape, 1.0, torch.float16)
-                else:
-                    host["descriptors"] = kp["descriptors"].to(torch.float16)
-                    host["scores"] = kp["scores"].to(torch.float16)
-            except Exception as e:  # noqa: BLE001
-                print(f"⚠️  Keypoint extraction failed: {e}")
-                for k in ("points", "local_points", "conf", "keypoints", "colors", "masks"):
-                    out.pop(k, None)
-                host = {}
-        if "points" not in out:   # no keypoints: the dense maps are the result (offline_chunk_creator.py:204-209)
-            dense = dict(points=pi3["points"][0], local_points=pi3["local_points"][0], conf=pi3["conf"][0], masks=masks)
-            if cfg.hip_graph:     # static graph outputs: the next replay would overwrite them before finish() reads
-                dense = {k: v.clone() for k, v in dense.items()}
-        ev["post"].record(cur)
-        mark("keypoints+gather queued")
+    def _queue_dense_cloud(self, pi3: Dict[str, torch.Tensor], masks: torch.Tensor, imgs: torch.Tensor,
+                           out: Dict[str, torch.Tensor]):
+        """The metric points into the dense cloud, queued before the next graph replay can reuse the static outputs.
+        Its consistency filter projects with the intrinsics that _queue_camera_parameters left in `out`."""
+        fxy = None
+        if self._dense.filter is not None and "cam.fx" in out:
+            fxy = torch.stack([out["cam." + k][0] for k in ("fx", "fy", "cx", "cy")], dim=1)
+        return self._dense.queue(pi3["points"][0], pi3["local_points"][0], pi3["conf"][0], masks, imgs[0],
+                                 pi3["camera_poses"][0], fxy, out)
 
-        # one packed D2H: every small result tensor, 16-byte aligned, through one pinned buffer
-        layout, parts, off = [], [], 0
-        for k, t in out.items():
-            b = t.contiguous().view(torch.uint8).reshape(-1)
-            pad = (-b.numel()) % 16
-            layout.append((k, t.dtype, tuple(t.shape), off, b.numel()))
-            parts.append(b)
-            if pad:
-                parts.append(torch.zeros(pad, dtype=torch.uint8, device=dev))
-            off += b.numel() + pad
-        packed = torch.cat(parts)
-        done = torch.cuda.Event()
-        done.record(cur)
-        mark("pack queued")
-        if trace is not None:
-            print("   [trace] launch: " + ", ".join(f"{b[0]} +{(b[1] - a[1]) * 1e3:.1f} ms" for a, b in zip(trace, trace[1:])))
-        return _InFlight(packed, layout, done, ev, host, dense, dict(st.meta, paths=st.paths, num_frames=N),
-                         t_launch=time.time(), dense_job=dense_job)
+    def _queue_gather(self, pi3: Dict[str, torch.Tensor], masks: torch.Tensor, imgs: torch.Tensor, kp: Optional[Dict],
+                      kp_dev: Optional[torch.Tensor], kp_err: Optional[Exception], out: Dict[str, torch.Tensor]) -> Dict:
+        """Sample the maps at the keypoints into `out`; -> the values that stay on the host (descriptors, scores).
+        A failure, of the extraction before the forward or here, is reported and leaves `out` without keypoint results."""
+        try:
+            if kp_err is not None:
+                raise kp_err
+            g = self._interpolate_world_points_for_keypoints(
+                dict(points=pi3["points"][0], local_points=pi3["local_points"][0], conf=pi3["conf"][0],
+                     masks=masks, images=imgs[0]), kp_dev)
+            for k in ("points", "local_points", "conf", "keypoints", "colors"):
+                out[k] = g[k]
+            out["masks"] = g["masks"].view(torch.uint8)
+            if kp.get("constant"):     # all-zero descriptors, all-one scores (keypoint_extraction.py:150-151)
+                # fresh calloc'ed zeros / a small filled array per chunk (callers own and may mutate their chunk)
+                return {"descriptors": zeros_host(kp["descriptors"].shape, torch.float16),
+                        "scores": full_host(kp["scores"].shape, 1.0, torch.float16)}
+            return {"descriptors": kp["descriptors"].to(torch.float16), "scores": kp["scores"].to(torch.float16)}
+        except Exception as e:  # noqa: BLE001
+            print(f"⚠️  Keypoint extraction failed: {e}")
+            for k in ("points", "local_points", "conf", "keypoints", "colors", "masks"):
+                out.pop(k, None)
+            return {}
+
+    def _dense_fallback(self, pi3: Dict[str, torch.Tensor], masks: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """No keypoints: the dense maps are the result (offline_chunk_creator.py:204-209)."""
+        dense = dict(points=pi3["points"][0], local_points=pi3["local_points"][0], conf=pi3["conf"][0], masks=masks)
+        if self.config.hip_graph:     # static graph outputs: the next replay would overwrite them before finish() reads
+            dense = {k: v.clone() for k, v in dense.items()}
+        return dense
 
     # ------------------------------------------------------------------ finish
     def _finish(self, fl: _InFlight) -> Dict:
         """Wait for one chunk's results and build its chunk-file dictionary (host tensors)."""
         fl.done.synchronize()
+        got = self._fetch_packed(fl)
+        metrics = self._chunk_metrics(fl, got)
+        result = self._chunk_result(fl, got, metrics)
+        if fl.dense_job is not None:
+            result["dense_cloud"] = self._dense.collect(fl.dense_job, got, metrics)
+            fl.dense_job = None
+        return result
+
+    def _pinned(self, nbytes: int) -> torch.Tensor:
+        pool = self._pinned_pool.setdefault(nbytes, [])
+        return pool.pop() if pool else torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+
+    def _fetch_packed(self, fl: _InFlight) -> Dict[str, torch.Tensor]:
+        """The packed copy (see _InFlight for why it is issued here, after `done`) -> host tensors by key."""
         pinned = self._pinned(fl.packed.numel())
         with torch.cuda.stream(self._d2h_stream):      # nothing else is ever queued on this stream
             pinned.copy_(fl.packed, non_blocking=True)
         self._d2h_stream.synchronize()
         fl.packed = None
-        got: Dict[str, torch.Tensor] = {}
-        for k, dt, shape, off, nbytes in fl.layout:
-            got[k] = clone_host(pinned[off:off + nbytes]).view(dt).reshape(shape)      # memcpy, no ATen operator (hostmem.py)
+        got = unpack_results(pinned, fl.layout)
         self._pinned_pool.setdefault(pinned.numel(), []).append(pinned)
+        return got
+
+    def _chunk_metrics(self, fl: _InFlight, got: Dict[str, torch.Tensor]) -> Dict:
+        """The chunk's '_metrics' from its timing events and the scale kernel's [median, count]."""
         N = fl.meta["num_frames"]
         infer_s = max(1e-6, fl.timing["f0"].elapsed_time(fl.timing["f1"]) / 1e3)
         post_s = fl.timing["f1"].elapsed_time(fl.timing["post"]) / 1e3
         fps = N / infer_s if N > 0 else 0.0
         print(f"   ⏱️ Inference: {infer_s:.3f}s for {N} frames  ->  {fps:.2f} FPS")
         metrics = {"infer_s": float(infer_s), "num_frames": int(N), "fps": float(fps), "post_s": float(post_s)}
-        last = self.__dict__.get("_last_forward_end")      # device idle between consecutive forwards (pipelined runs)
-        if last is not None:
+        if self._last_forward_end is not None:      # device idle between consecutive forwards (pipelined runs)
             try:
-                metrics["gap_before_forward_s"] = last.elapsed_time(fl.timing["f0"]) / 1e3
+                metrics["gap_before_forward_s"] = self._last_forward_end.elapsed_time(fl.timing["f0"]) / 1e3
             except RuntimeError:
                 pass
         self._last_forward_end = fl.timing["f1"]
@@ -509,6 +509,9 @@ class OfflineChunkCreator:
             metrics["metric_scale"] = med if ok else None
             if not ok:   # the reference would raise on an empty mask (torch.median of nothing); say so, keep pi3's scale
                 print(f"⚠️  metric scale not applied: median {med} over {cnt} masked pixels of frame 0")
+        return metrics
+
+    def _chunk_result(self, fl: _InFlight, got: Dict[str, torch.Tensor], metrics: Dict) -> Dict:
         result: Dict = {"camera_poses": got["camera_poses"], "image_paths": fl.meta["paths"], "_metrics": metrics}
         cam = {k[4:]: v for k, v in got.items() if k.startswith("cam.")}
         if cam:
@@ -528,41 +531,7 @@ class OfflineChunkCreator:
                     result[k] = v.cpu()
         if cam:
             result["intrinsics"] = cam.get("intrinsics")
-        if fl.dense_job is not None:
-            result["dense_cloud"] = self._dense_cloud(fl.dense_job.result(), got["_dense_stats"], metrics,
-                                                      got.get("_dense_filter_stats"))
-            fl.dense_job = None
         return result
-
-    def _dense_host(self, bufs: tuple, stats_dev: torch.Tensor, extracted: torch.cuda.Event) -> Dict:
-        """(dense-cloud thread) Wait for the extraction, copy the first V rows into pinned memory on a stream of its own
-        (a copy into pageable memory would wait for the next chunk's forward) and sort them by key."""
-        from .dense_map import sort_by_key
-        with torch.cuda.device(self.device), torch.cuda.stream(self._dense_stream):
-            extracted.synchronize()
-            V = int(stats_dev[2].item())
-            h = [torch.empty((V,) + tuple(t.shape[1:]), dtype=t.dtype, pin_memory=True) for t in bufs]
-            for dst, src in zip(h, bufs):
-                dst.copy_(src[:V], non_blocking=True)
-            self._dense_stream.synchronize()
-        return sort_by_key(*(t.numpy() for t in h))
-
-    def _dense_cloud(self, s: Dict, stats: torch.Tensor, metrics: Dict,
-                     filter_stats: Optional[torch.Tensor] = None) -> Dict:
-        """The chunk's voxel cloud from the sorted host rows; stats = the packed D2H copy of the table's counters,
-        filter_stats = that of the consistency filter's [candidates, kept] when it ran."""
-        dropped, overflow, V, lost = (int(x) for x in stats.tolist())
-        if overflow or lost:
-            raise RuntimeError(f"dense voxel table overflow ({overflow} / {lost}): capacity rule violated")
-        assert len(s["keys"]) == V
-        metrics["dense_voxels"], metrics["dense_dropped"] = V, dropped
-        cloud = {"points": torch.from_numpy(s["points"]), "colors": torch.from_numpy(s["colors"]),
-                 "weights": torch.from_numpy(s["weights"]), "voxel_size": float(self.config.dense_voxel_size),
-                 "conf_threshold": float(self.config.dense_conf_threshold)}
-        if filter_stats is not None:
-            metrics["dense_candidates"], metrics["dense_consistent"] = (int(x) for x in filter_stats.tolist())
-            cloud["consistency"] = self._dense_filter.settings()
-        return cloud
 
     # ------------------------------------------------------------------ one chunk, start to end (reference surface)
     def _process_single_chunk(self, chunk_images: torch.Tensor, chunk_paths: List[str]) -> Dict:
@@ -660,7 +629,7 @@ class OfflineChunkCreator:
             full = sorted(s[2] for s in stats if s[1] == cfg.chunk_length)
             if full:
                 print(f"   Steady-state FPS (full {cfg.chunk_length}-frame chunks, median): {full[len(full) // 2]:.2f} FPS")
-        hs = getattr(self, "host_seconds", {})
+        hs = self.host_seconds
         print("   host time: " + ", ".join(f"{k} {v:.2f} s" for k, v in hs.items()) + f" of {wall:.2f} s wall")
         self.last_run = {"frames": total_n, "wall_s": wall, "infer_s": total_t, "host_seconds": dict(hs),
                          "wall_after_first_chunk_decoded_s": max(1e-6, time.time() - (t_first[0] or t_all))}

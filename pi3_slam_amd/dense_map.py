@@ -5,7 +5,7 @@ tracks.  Here the dense maps are fused on the device into one voxel per occupied
 
   stage 1   OfflineChunkCreator (dense_voxel_size set): each chunk's metric pointmap, masked by the creator's masks and
             `conf > logit(dense_conf_threshold)`, becomes chunk['dense_cloud'] = {points f32 (V,3), colors u8 (V,3),
-            weights i32 (V,), voxel_size, conf_threshold} in the chunk's own frame (VoxelFuser.fuse_pixels);
+            weights i32 (V,), voxel_size, conf_threshold} in the chunk's own frame (ChunkCloudBuilder);
   stage 2   fuse_chunk_clouds: every cloud moved by its chunk's accumulated similarity (ops.sim3_apply) and fused again,
             weighted by W, into the world frame (= chunk 0's frame) -> dense_points.ply.
 
@@ -18,6 +18,7 @@ Limitation: a cloud follows its chunk's similarity; per-view corrections of a bu
 from __future__ import annotations
 
 import math
+from concurrent.futures import Future, ThreadPoolExecutor
 from dataclasses import dataclass
 from typing import Dict, Iterable, Optional, Tuple
 
@@ -87,8 +88,6 @@ class ConsistencyFilter:
               conf_threshold: float) -> Tuple[torch.Tensor, torch.Tensor]:
         """One chunk's maps (N,H,W,..), poses (N,4,4) cam->world and intrinsics (N,4) on the device ->
         (mask uint8 (N,H,W) for VoxelFuser.fuse_pixels, device stats int64 [candidates, kept])."""
-        if masks is not None and masks.dtype == torch.bool:
-            masks = masks.view(torch.uint8)
         mask, _, stats = ops.dense_consistency(points, local_points, conf, masks, poses, fxfycxcy,
                                                conf_logit_threshold(conf_threshold), self.radius, self.stride,
                                                self.min_views, self.rel_tol)
@@ -140,8 +139,6 @@ class VoxelFuser:
         """points (N,H,W,3) f32, conf logits (N,H,W[,1]), masks (N,H,W), imgs (N,3,H,W) f32 in [0, 1]."""
         n = points.numel() // 3
         self.reserve(n)
-        if masks is not None and masks.dtype == torch.bool:
-            masks = masks.view(torch.uint8)
         ops.voxel_fuse_pixels(self.table, self.stats, points, conf, masks, imgs, conf_logit_threshold(conf_threshold),
                               self.inv_voxel)
         self.bound += n
@@ -180,6 +177,91 @@ class VoxelFuser:
         if self.last_stats["overflow"]:
             raise RuntimeError(f"voxel table overflow: {self.last_stats}")
         return sort_by_key(keys[:V].cpu().numpy(), pts[:V].cpu().numpy(), cols[:V].cpu().numpy(), w[:V].cpu().numpy())
+
+
+class ChunkCloudBuilder:
+    """Stage 1 for the chunk creator: queue() fuses one chunk's maps into a voxel cloud on the current stream and starts
+    its host copy, collect() turns that into chunk['dense_cloud'].  The table's and the filter's counters travel in the
+    creator's packed copy (`out` / `got`), so a cloud costs the pipeline thread no synchronisation of its own."""
+
+    def __init__(self, voxel_size: float, conf_threshold: float, device, consistency: Optional[ConsistencyFilter] = None):
+        self.conf_threshold = float(conf_threshold)
+        self.filter = consistency
+        self.device = torch.device(device)
+        # two output sets: chunk k's is read on the host while chunk k+1's extraction is queued (the creator's finish(k)
+        # always completes before launch(k+2))
+        self.fuser = VoxelFuser(voxel_size, self.device, out_sets=2)
+        # the cloud's copy + key sort run on this thread as soon as the chunk's extraction is done, beside the host's
+        # launch of the next chunk instead of in front of it
+        self._pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="dense-cloud")
+        self._stream = torch.cuda.Stream(self.device)
+        self._warned = False
+
+    @classmethod
+    def from_config(cls, cfg, device) -> Optional["ChunkCloudBuilder"]:
+        """The builder an OfflineCreatorConfig asks for with its dense_* fields; None without dense_voxel_size."""
+        consistency = None
+        if cfg.dense_min_views is not None:
+            consistency = ConsistencyFilter(cfg.dense_min_views, cfg.dense_view_radius, cfg.dense_view_stride,
+                                            cfg.dense_depth_tolerance)
+            if cfg.dense_voxel_size is None:
+                print("⚠️  dense_min_views has no effect without dense_voxel_size: no dense cloud is built")
+        if cfg.dense_voxel_size is None:
+            return None
+        return cls(cfg.dense_voxel_size, cfg.dense_conf_threshold, device, consistency)
+
+    def queue(self, points: torch.Tensor, local_points: torch.Tensor, conf: torch.Tensor, masks: torch.Tensor,
+              imgs: torch.Tensor, poses: torch.Tensor, fxfycxcy: Optional[torch.Tensor],
+              out: Dict[str, torch.Tensor]) -> Future:
+        """One chunk's metric maps (N,H,W,..), masks (N,H,W), imgs (N,3,H,W), poses (N,4,4) and intrinsics (N,4) or
+        None.  Queues clear, [filter], fuse_pixels and extract on the current stream; the extract writes into buffers of
+        the fuser's own, so work queued behind it (the next graph replay) may overwrite the maps.  Puts the device
+        counters into out['_dense_stats'] / out['_dense_filter_stats'] and returns the host job for collect()."""
+        self.fuser.clear()
+        points, conf, masks = points.contiguous(), conf.contiguous(), masks.contiguous()
+        if self.filter is not None:
+            if fxfycxcy is not None:
+                masks, out["_dense_filter_stats"] = self.filter.apply(
+                    points, local_points.contiguous(), conf, masks, poses.contiguous(), fxfycxcy, self.conf_threshold)
+            elif not self._warned:      # once per run
+                self._warned = True
+                print("⚠️  dense consistency filter: no intrinsics (estimate_camera_params is off or the estimate "
+                      "failed); dense clouds without them are fused unfiltered")
+        self.fuser.fuse_pixels(points, conf, masks, imgs.contiguous(), self.conf_threshold)
+        bufs, out["_dense_stats"] = self.fuser.extract_async()
+        extracted = torch.cuda.Event()
+        extracted.record(torch.cuda.current_stream(self.device))
+        return self._pool.submit(self._host_rows, bufs, out["_dense_stats"], extracted)
+
+    def _host_rows(self, bufs: tuple, stats_dev: torch.Tensor, extracted: torch.cuda.Event) -> Dict[str, np.ndarray]:
+        """(dense-cloud thread) Wait for the extraction, copy the first V rows into pinned memory on a stream of its own
+        (a copy into pageable memory would wait for the next chunk's forward) and sort them by key."""
+        with torch.cuda.device(self.device), torch.cuda.stream(self._stream):
+            extracted.synchronize()
+            V = int(stats_dev[2].item())
+            h = [torch.empty((V,) + tuple(t.shape[1:]), dtype=t.dtype, pin_memory=True) for t in bufs]
+            for dst, src in zip(h, bufs):
+                dst.copy_(src[:V], non_blocking=True)
+            self._stream.synchronize()
+        return sort_by_key(*(t.numpy() for t in h))
+
+    def collect(self, job: Future, got: Dict[str, torch.Tensor], metrics: Dict) -> Dict:
+        """The chunk's voxel cloud from queue()'s job and the host copies of what queue() put into `out`:
+        _dense_stats = the table's [dropped, overflow, voxels, lost] (VoxelFuser.extract_async), _dense_filter_stats = the
+        filter's [candidates, kept] when it ran.  Adds the dense_* counts to `metrics`."""
+        s = job.result()
+        dropped, overflow, V, lost = (int(x) for x in got["_dense_stats"].tolist())
+        if overflow or lost:
+            raise RuntimeError(f"dense voxel table overflow ({overflow} / {lost}): capacity rule violated")
+        assert len(s["keys"]) == V
+        metrics["dense_voxels"], metrics["dense_dropped"] = V, dropped
+        cloud = {"points": torch.from_numpy(s["points"]), "colors": torch.from_numpy(s["colors"]),
+                 "weights": torch.from_numpy(s["weights"]), "voxel_size": self.fuser.voxel_size,
+                 "conf_threshold": self.conf_threshold}
+        if "_dense_filter_stats" in got:
+            metrics["dense_candidates"], metrics["dense_consistent"] = (int(x) for x in got["_dense_filter_stats"].tolist())
+            cloud["consistency"] = self.filter.settings()
+        return cloud
 
 
 def chunk_transform(chunk: Dict) -> torch.Tensor:

@@ -283,9 +283,9 @@ def compute_masks(conf: torch.Tensor, local_points: torch.Tensor, conf_thr: floa
 
 def masked_ratio_median(num: torch.Tensor, den: torch.Tensor, den_stride: int, mask: torch.Tensor,
                         n: int) -> torch.Tensor:
-    """-> device tensor [median, count] (f32).  den is addressed as den_ptr[i * den_stride]."""
+    """-> device tensor [median, count] (f32).  den is addressed as den_ptr[i * den_stride]; mask uint8/bool."""
     lib = _L.load()
-    assert num.dtype == torch.float32 and den.dtype == torch.float32 and mask.dtype == torch.uint8
+    assert num.dtype == torch.float32 and den.dtype == torch.float32 and mask.dtype in (torch.uint8, torch.bool)
     out = torch.empty(2, device=num.device, dtype=torch.float32)
     rc = lib.pi3_masked_ratio_median(num.data_ptr(), den.data_ptr(), den_stride, mask.data_ptr(), n, out.data_ptr(),
                                      _L.stream_ptr())
@@ -304,14 +304,15 @@ def apply_scale(scale_dev: torch.Tensor, local_points: torch.Tensor, points: tor
 
 
 def gather_keypoints(points, local_points, conf, masks, images, keypoints):
-    """Dense maps [F,H,W,*] + keypoints f32 [F,K,2] -> dict of packed per-keypoint tensors (fp16 / bool)."""
+    """Dense maps [F,H,W,*] (masks uint8/bool) + keypoints f32 [F,K,2] -> dict of packed per-keypoint tensors
+    (fp16 / bool)."""
     lib = _L.load()
     F, H, W = points.shape[:3]
     K = keypoints.shape[1]
     dev = points.device
     for t in (points, local_points, conf, masks, keypoints):
         assert t.is_contiguous()
-    assert keypoints.dtype == torch.float32 and masks.dtype == torch.uint8
+    assert keypoints.dtype == torch.float32 and masks.dtype in (torch.uint8, torch.bool)
     o_points = torch.empty(F, K, 3, device=dev, dtype=torch.float16)
     o_local = torch.empty(F, K, 3, device=dev, dtype=torch.float16)
     o_conf = torch.empty(F, K, 1, device=dev, dtype=torch.float16)

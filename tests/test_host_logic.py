@@ -374,6 +374,36 @@ def test_hostmem_byte_movers_equal_the_aten_operators():
         hostmem.memcpy_into(torch.empty(5, dtype=torch.float32), src)
 
 
+def test_packed_results_round_trip():
+    """chunk_creator.pack_results / unpack_results (one device buffer, one copy per chunk): offsets and length are
+    16-byte aligned, the layout keeps the insertion order, every tensor comes back equal in storage of its own."""
+    from pi3_slam_amd.chunk_creator import pack_results, unpack_results
+    g = torch.Generator().manual_seed(11)
+    out = {"_scale": torch.randn(2, generator=g), "cam.focal": torch.randn(1, 3, generator=g),
+           "f64": torch.randn(33, generator=g).double(), "_dense_stats": torch.randint(-9, 9, (4,), generator=g),
+           "masks": torch.randint(0, 255, (3, 5, 1), generator=g, dtype=torch.uint8),      # 15 bytes: padded
+           "points": torch.randn(3, 5, 3, generator=g).half(), "strided": torch.randn(4, 6, generator=g)[:, ::2],
+           "camera_poses": torch.randn(3, 4, 4, generator=g), "empty": torch.zeros(0, 3)}
+    assert not out["strided"].is_contiguous() and out["strided"].shape == (4, 3)
+    packed, layout = pack_results(out)
+    assert packed.dtype == torch.uint8 and packed.ndim == 1 and packed.numel() % 16 == 0
+    assert [e[0] for e in layout] == list(out)
+    end = 0
+    for k, dt, shape, off, nbytes in layout:
+        assert off % 16 == 0 and off >= end and nbytes == out[k].numel() * out[k].element_size()
+        end = off + nbytes
+    assert end <= packed.numel() < end + 16 and packed.numel() == 688
+    got = unpack_results(packed, layout)
+
+    def same():
+        assert list(got) == list(out)
+        for k, t in out.items():
+            assert got[k].dtype == t.dtype and got[k].shape == t.shape and torch.equal(got[k], t), k
+    same()
+    packed.fill_(0xA5)                          # the results do not alias the buffer (it goes back to a pool)
+    same()
+
+
 def test_overlap_block_takes_negative_view_indices_like_an_advanced_index():
     """A run of negative view indices that ends at -1 ([-20 .. -1]) is consecutive; as a slice it would read
     t[-20:0] = nothing.  The block must equal what the advanced index t[frames] returns."""

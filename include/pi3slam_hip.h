@@ -381,6 +381,43 @@ int pi3_voxel_rehash(const void* src_table, long src_capacity, void* dst_table, 
 int pi3_voxel_extract(const void* table, long capacity, double voxel_size, unsigned long long* keys, float* points,
                       unsigned char* colors, int* weights, long max_out, unsigned long long* stats, void* stream);
 
+/* pi3_voxel_extract for the occupied slots with keep[slot] != 0 only (keep: uint8 [capacity], see below); the rows
+ * are computed exactly alike. */
+int pi3_voxel_extract_kept(const void* table, long capacity, double voxel_size, unsigned long long* keys, float* points,
+                           unsigned char* colors, int* weights, long max_out, unsigned long long* stats,
+                           const unsigned char* keep, void* stream);
+
+/* ---- cleaning the fused map (csrc/voxel_clean.hip): a keep / drop decision per slot of a voxel table, integer
+ * arithmetic only.  The table is read only.  All arrays are caller-owned DEVICE memory with one entry per slot.
+ *   eligible: an occupied slot with W >= min_weight;
+ *   support(v): the eligible voxels u != v with max(|dx|, |dy|, |dz|) <= radius in voxel indices, radius 1 or 2; a
+ *   cell whose index on an axis leaves |k| < 2^20 does not exist (nothing wraps into a neighbouring field);
+ *   stage A survivors: eligible and support >= min_support (0 <= min_support <= (2 radius + 1)^3 - 1);
+ *   stage B: 26-connected components of the survivors, label = the smallest key, size = the voxel count; kept: size >=
+ *   min_component.  One pass of each, in this order.
+ * counters: DEVICE uint64 [8] = occupied slots, eligible, after support, after components, components found,
+ * components kept, 2 spare.
+ * pi3_voxel_support: zeroes counters, writes keep uint8 [capacity] (1 = stage-A survivor, else 0), support int32
+ * [capacity] (or NULL; -1 for a slot that is not eligible) and counters[0..2].  With min_support == 0 and support ==
+ * NULL no neighbour is probed. */
+int pi3_voxel_support(const void* table, long capacity, unsigned long long min_weight, int radius, int min_support,
+                      unsigned char* keep, int* support, unsigned long long* counters, void* stream);
+/* label uint64 [capacity] = the slot's key where keep != 0, all ones elsewhere. */
+int pi3_voxel_label_init(const void* table, long capacity, const unsigned char* keep, unsigned long long* label,
+                         void* stream);
+/* One labelling sweep: every survivor takes the minimum of its own and its 26 neighbours' labels, follows label[slot of
+ * m] a bounded number of hops, and atomicMins a smaller m into its own label and into its previous root's; *changed (a
+ * DEVICE int the caller zeroed) becomes 1 when a label was lowered.  Labels only decrease and always name a survivor of
+ * the same component; the caller repeats the sweep until one leaves *changed at 0: then every label is its component's
+ * smallest key, whatever order the atomics landed in.  At most (survivors) sweeps change anything. */
+int pi3_voxel_label_sweep(const void* table, long capacity, unsigned long long* label, int* changed, void* stream);
+/* size uint32 [capacity]: zeroed, then size[slot of label] += 1 per survivor (the converged labels). */
+int pi3_voxel_component_sizes(const void* table, long capacity, const unsigned long long* label, unsigned* size,
+                              void* stream);
+/* keep[slot] = 0 where the slot's component has size < min_component; writes counters[3..5]. */
+int pi3_voxel_component_filter(const void* table, long capacity, const unsigned long long* label, const unsigned* size,
+                               long min_component, unsigned char* keep, unsigned long long* counters, void* stream);
+
 /* ---- multi-view depth consistency of one chunk's dense maps (csrc/dense_filter.hip): a pixel mask for
  * pi3_voxel_fuse_pixels.  points f32 [N][H][W][3] (world), local_points f32 [N][H][W][3] (z = [..][2]), conf f32 logits
  * [N][H][W] (or NULL), masks uint8 [N][H][W] (or NULL), poses f32 [N][4][4] cam->world row-major, fxfycxcy f32 [N][4].

@@ -62,6 +62,17 @@ RECON_FLAGS: Sequence[Tuple[str, Dict]] = (
                                                          "color_<frame>.png of the dense map for every N-th view")),
     ("--render-min-weight", dict(type=int, default=1, help="voxels below this fused weight are not drawn")),
     ("--render-splat-scale", dict(type=float, default=1.0, help="half-width of a drawn voxel in voxel sizes")),
+    ("--dense-min-weight", dict(type=int, default=None, help="dense map: drop voxels whose fused weight is below N "
+                                                             "(from dense_points.ply and the renders; e.g. 2 as a "
+                                                             "starting point, not a measured optimum)")),
+    ("--dense-min-support", dict(type=int, default=None, help="dense map: drop voxels with fewer than N occupied cells "
+                                                              "among their neighbours (26 at radius 1; e.g. 4 as a "
+                                                              "starting point, not a measured optimum)")),
+    ("--dense-support-radius", dict(type=int, default=1, choices=(1, 2), help="neighbourhood of --dense-min-support "
+                                                                               "in voxels: 26 or 124 cells")),
+    ("--dense-min-component", dict(type=int, default=None, help="dense map: then drop 26-connected components of fewer "
+                                                                "than N voxels (e.g. 50 as a starting point, not a "
+                                                                "measured optimum)")),
 )
 RECON_SWITCHES = (("--save-per-chunk", "per-chunk ply files as well"),
                   ("--render-overview", "write renders/overview.png: the dense map from above with the trajectory in red"),
@@ -111,6 +122,17 @@ ONLINE_FLAGS: Sequence[Tuple[str, Dict]] = (
     ("--dense_depth_tolerance", dict(type=float, default=0.03, help="relative depth difference that still agrees")),
     ("--render_every", dict(type=int, default=None, help="with --dense_voxel_size: renders/ with depth and colour images "
                                                          "of the dense map for every N-th view and an overview")),
+    ("--dense_min_weight", dict(type=int, default=None, help="dense map: drop voxels whose fused weight is below N "
+                                                             "(from dense_points.ply and the renders; e.g. 2 as a "
+                                                             "starting point, not a measured optimum)")),
+    ("--dense_min_support", dict(type=int, default=None, help="dense map: drop voxels with fewer than N occupied cells "
+                                                              "among their neighbours (26 at radius 1; e.g. 4 as a "
+                                                              "starting point, not a measured optimum)")),
+    ("--dense_support_radius", dict(type=int, default=1, choices=(1, 2), help="neighbourhood of --dense_min_support "
+                                                                               "in voxels: 26 or 124 cells")),
+    ("--dense_min_component", dict(type=int, default=None, help="dense map: then drop 26-connected components of fewer "
+                                                                "than N voxels (e.g. 50 as a starting point, not a "
+                                                                "measured optimum)")),
 )
 ONLINE_SWITCHES = (("--save_chunk_reconstructions", "save each chunk reconstruction to disk"),
                    ("--save_transformed_reconstructions", "save transformed reconstructions as PLY files"),
@@ -188,7 +210,9 @@ def run_reconstruct(a: argparse.Namespace) -> None:
                          save_observations=a.save_observations, bundle_adjust=not a.no_bundle_adjust,
                          ba_sanity_gate=not a.no_ba_sanity_gate, render_every=a.render_every,
                          render_overview=a.render_overview, render_min_weight=a.render_min_weight,
-                         render_splat_scale=a.render_splat_scale).run()
+                         render_splat_scale=a.render_splat_scale, dense_min_weight=a.dense_min_weight,
+                         dense_min_support=a.dense_min_support, dense_support_radius=a.dense_support_radius,
+                         dense_min_component=a.dense_min_component).run()
 
 
 def online_image_paths(a: argparse.Namespace) -> List[str]:
@@ -230,7 +254,9 @@ def run_online(a: argparse.Namespace) -> None:
         output_dir=out_dir, num_loader_workers=a.num_workers, bundle_adjust=not a.no_bundle_adjust,
         reuse_overlap_encoder=a.reuse_overlap_encoder, dense_voxel_size=a.dense_voxel_size,
         dense_min_views=a.dense_min_views, dense_view_radius=a.dense_view_radius,
-        dense_view_stride=a.dense_view_stride, dense_depth_tolerance=a.dense_depth_tolerance)
+        dense_view_stride=a.dense_view_stride, dense_depth_tolerance=a.dense_depth_tolerance,
+        dense_min_weight=a.dense_min_weight, dense_min_support=a.dense_min_support,
+        dense_support_radius=a.dense_support_radius, dense_min_component=a.dense_min_component)
     slam.save_transformed_reconstructions = a.save_transformed_reconstructions
     slam.save_debug_reconstructions = a.save_debug_reconstructions
     slam.process_chunks(paths)

@@ -24,25 +24,15 @@
 // stats (caller-owned device memory, 4 x uint64): [0] dropped points, [1] table overflows (0 under the capacity rule),
 // [2] voxels written by the last extract, [3] voxels the last extract could not store (max_out too small).
 #include "common.h"
+#include "voxel_table.h"
 
 #include <stdint.h>
 
 namespace {
 
-typedef unsigned long long u64;
+using namespace voxel_table;      // u64, kEmpty, kBias, mix64, pack_key, pow2, blocks_for
 
-constexpr u64 kEmpty = ~0ull;
-constexpr int kBias = 1 << 20;
 constexpr float kFix = 16777216.0f;    // 2^24
-
-__device__ __forceinline__ u64 mix64(u64 x) {     // splitmix64 finaliser: neighbouring keys land far apart
-  x ^= x >> 30;
-  x *= 0xbf58476d1ce4e5b9ull;
-  x ^= x >> 27;
-  x *= 0x94d049bb133111ebull;
-  x ^= x >> 31;
-  return x;
-}
 
 // one axis: voxel index (biased) and fixed-point offset; false = drop
 __device__ __forceinline__ bool quantise(float p, float inv_v, uint32_t& kb, uint32_t& u) {
@@ -151,7 +141,7 @@ __global__ __launch_bounds__(256) void voxel_fuse_pixels_kernel(
     const float px = points[3 * i], py = points[3 * i + 1], pz = points[3 * i + 2];
     if (quantise(px, inv_v, kx, ux) && quantise(py, inv_v, ky, uy) && quantise(pz, inv_v, kz, uz)) {
       valid = true;
-      key = ((u64)kx << 42) | ((u64)ky << 21) | (u64)kz;
+      key = pack_key(kx, ky, kz);
       v[0] = ux; v[1] = uy; v[2] = uz;
       if (imgs) {
         const long f = i / HW, p = i - f * HW;
@@ -180,7 +170,7 @@ __global__ __launch_bounds__(256) void voxel_fuse_points_kernel(
     if (quantise(px, inv_v, kx, ux) && quantise(py, inv_v, ky, uy) && quantise(pz, inv_v, kz, uz)) {
       valid = true;
       w = (u64)wi;
-      key = ((u64)kx << 42) | ((u64)ky << 21) | (u64)kz;
+      key = pack_key(kx, ky, kz);
       v[0] = w * ux; v[1] = w * uy; v[2] = w * uz;
       if (colors) {
         v[3] = w * colors[3 * i];
@@ -209,9 +199,12 @@ constexpr int kExtractPer = 16;                 // slots per thread: one output-
 // Occupied slots -> output rows.  Each workgroup covers 256 x 16 slots (coalesced: slot = base + j * 256 + tid), counts
 // its occupied ones, claims its rows with ONE atomic on the counter (a per-wave atomic on one address serialised the
 // kernel at ~700 k voxels) and writes them; the order of the rows is arbitrary (the host sorts by key).
+// kMasked: only the occupied slots with keep[slot] != 0 (pi3_voxel_extract_kept); the rows themselves are computed alike.
+template <bool kMasked>
 __global__ __launch_bounds__(256) void voxel_extract_kernel(const u64* __restrict__ table, long capacity,
-                                                            double vsize, u64* __restrict__ keys,
-                                                            float* __restrict__ points, unsigned char* __restrict__ colors,
+                                                            const unsigned char* __restrict__ keep, double vsize,
+                                                            u64* __restrict__ keys, float* __restrict__ points,
+                                                            unsigned char* __restrict__ colors,
                                                             int* __restrict__ weights, long max_out,
                                                             u64* __restrict__ stats) {
 #pragma clang fp contract(off)
@@ -223,7 +216,7 @@ __global__ __launch_bounds__(256) void voxel_extract_kernel(const u64* __restric
 #pragma unroll
   for (int j = 0; j < kExtractPer; ++j) {
     const long s = s0 + 256L * j;
-    if (s < capacity && table[8 * s] != kEmpty) occ |= 1u << j;
+    if (s < capacity && table[8 * s] != kEmpty && (!kMasked || keep[s])) occ |= 1u << j;
   }
   const u64 cnt = (u64)__popc(occ);
   u64 incl = cnt;                                  // inclusive prefix over the wave
@@ -264,10 +257,6 @@ __global__ __launch_bounds__(256) void voxel_extract_kernel(const u64* __restric
     ++at;
   }
 }
-
-bool pow2(long c) { return c > 0 && (c & (c - 1)) == 0; }
-
-unsigned blocks_for(long n) { return (unsigned)((n + 255) / 256); }
 
 }  // namespace
 
@@ -327,21 +316,43 @@ extern "C" int pi3_voxel_rehash(const void* src_table, long src_capacity, void* 
   return pi3_check_launch("voxel_rehash");
 }
 
-extern "C" int pi3_voxel_extract(const void* table, long capacity, double voxel_size, unsigned long long* keys,
-                                 float* points, unsigned char* colors, int* weights, long max_out,
-                                 unsigned long long* stats, void* stream) {
-  if (!table || !pow2(capacity) || !keys || !points || !colors || !weights || !stats || max_out < 0 ||
-      !(voxel_size > 0.0) || !__builtin_isfinite(voxel_size)) {
-    pi3_set_error("pi3_voxel_extract: bad arguments capacity=%ld max_out=%ld", capacity, max_out);
+namespace {
+
+int extract_launch(const char* what, const void* table, long capacity, const unsigned char* keep, bool masked,
+                   double voxel_size, unsigned long long* keys, float* points, unsigned char* colors, int* weights,
+                   long max_out, unsigned long long* stats, void* stream) {
+  if (!table || !pow2(capacity) || (masked && !keep) || !keys || !points || !colors || !weights || !stats ||
+      max_out < 0 || !(voxel_size > 0.0) || !__builtin_isfinite(voxel_size)) {
+    pi3_set_error("%s: bad arguments capacity=%ld max_out=%ld", what, capacity, max_out);
     return PI3_ERR_ARG;
   }
   if (hipMemsetAsync(stats + 2, 0, 2 * sizeof(unsigned long long), (hipStream_t)stream) != hipSuccess) {
-    pi3_set_error("pi3_voxel_extract: hipMemsetAsync failed");
+    pi3_set_error("%s: hipMemsetAsync failed", what);
     return PI3_ERR_LAUNCH;
   }
   const long span = 256L * kExtractPer;
-  hipLaunchKernelGGL(voxel_extract_kernel, dim3((unsigned)((capacity + span - 1) / span)), dim3(256), 0, (hipStream_t)stream,
-                     (const u64*)table, capacity, voxel_size, (u64*)keys, points, colors, weights, max_out,
-                     (u64*)stats);
-  return pi3_check_launch("voxel_extract");
+  const dim3 grid((unsigned)((capacity + span - 1) / span));
+  if (masked)
+    hipLaunchKernelGGL(voxel_extract_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, (const u64*)table, capacity,
+                       keep, voxel_size, (u64*)keys, points, colors, weights, max_out, (u64*)stats);
+  else
+    hipLaunchKernelGGL(voxel_extract_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, (const u64*)table, capacity,
+                       keep, voxel_size, (u64*)keys, points, colors, weights, max_out, (u64*)stats);
+  return pi3_check_launch(what + 4);       // without the "pi3_" prefix, as the other entry points report
+}
+
+}  // namespace
+
+extern "C" int pi3_voxel_extract(const void* table, long capacity, double voxel_size, unsigned long long* keys,
+                                 float* points, unsigned char* colors, int* weights, long max_out,
+                                 unsigned long long* stats, void* stream) {
+  return extract_launch("pi3_voxel_extract", table, capacity, nullptr, false, voxel_size, keys, points, colors, weights,
+                        max_out, stats, stream);
+}
+
+extern "C" int pi3_voxel_extract_kept(const void* table, long capacity, double voxel_size, unsigned long long* keys,
+                                      float* points, unsigned char* colors, int* weights, long max_out,
+                                      unsigned long long* stats, const unsigned char* keep, void* stream) {
+  return extract_launch("pi3_voxel_extract_kept", table, capacity, keep, true, voxel_size, keys, points, colors, weights,
+                        max_out, stats, stream);
 }

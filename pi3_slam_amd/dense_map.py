@@ -11,6 +11,8 @@ tracks.  Here the dense maps are fused on the device into one voxel per occupied
 
 Optionally (ConsistencyFilter, csrc/dense_filter.hip) a pixel of stage 1 must also be confirmed by the depth maps of
 neighbouring frames of its chunk: the filter's pixel mask takes the place of the creator's in fuse_pixels.
+Optionally (MapCleaner, csrc/voxel_clean.hip) stage 2 drops voxels of the fused world-frame table before the extraction:
+a minimum weight, a minimum number of occupied neighbour cells, a minimum size of the connected component.
 
 The accumulators are integers, so a map is bitwise reproducible and tests/dense_map_ref.py reproduces it bit for bit.
 Limitation: a cloud follows its chunk's similarity; per-view corrections of a bundle adjustment do not reach it.
@@ -94,6 +96,120 @@ class ConsistencyFilter:
         return mask, stats
 
 
+@dataclass
+class MapCleaner:
+    """Keep / drop decisions on a fused voxel table (csrc/voxel_clean.hip; integer arithmetic, reproduced byte for byte
+    by tests/dense_clean_ref.py):
+
+      eligible    a voxel whose fused weight W >= min_weight;
+      stage A     support(v) = the eligible voxels u != v with max(|dx|, |dy|, |dz|) <= support_radius in voxel indices
+                  (26 cells at radius 1, 124 at radius 2; cells beyond the representable index range do not exist);
+                  survivors = eligible voxels with support >= min_support (0: every eligible voxel);
+      stage B     26-connected components of the survivors, size = the voxel count (not the weight); kept = survivors
+                  whose component has size >= min_component (<= 1: every survivor).
+
+    One pass of each stage, in this order: stage A is NOT repeated on what stage B leaves, so a kept voxel may end with
+    fewer than min_support kept neighbours.  All filters are off by default.  Limitation: a wall that a single frame saw
+    is as thin as a sheet of floaters; neither count tells them apart."""
+    min_weight: int = 1
+    min_support: int = 0
+    support_radius: int = 1
+    min_component: int = 0
+
+    SWEEPS_PER_READ = 4         # labelling sweeps queued between two reads of their `changed` words
+
+    def __post_init__(self):
+        for name in ("min_weight", "min_support", "support_radius", "min_component"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer, float)) or int(v) != v:
+                raise ValueError(f"{name} must be an integer, got {v!r}")
+            if v < 0:
+                raise ValueError(f"{name} must not be negative, got {v!r}")
+            setattr(self, name, int(v))
+        if self.support_radius not in (1, 2):
+            raise ValueError(f"support_radius must be 1 or 2, got {self.support_radius}")
+        cells = (2 * self.support_radius + 1) ** 3 - 1
+        if self.min_support > cells:
+            raise ValueError(f"min_support must be in 0..{cells} (the cells within radius {self.support_radius}), "
+                             f"got {self.min_support}")
+        if self.min_weight >= 1 << 63 or self.min_component >= 1 << 32:
+            raise ValueError("min_weight must fit 63 bits and min_component 32 bits")
+        self.last_stats: Optional[Dict[str, int]] = None
+        self.last_arrays: Optional[Dict[str, torch.Tensor]] = None
+
+    @classmethod
+    def from_options(cls, min_weight: Optional[int] = None, min_support: Optional[int] = None, support_radius: int = 1,
+                     min_component: Optional[int] = None) -> Optional["MapCleaner"]:
+        """The cleaner the dense_min_weight / dense_min_support / dense_support_radius / dense_min_component options
+        ask for; None when none of the three filters is set (the radius alone asks for nothing)."""
+        if min_weight is None and min_support is None and min_component is None:
+            return None
+        return cls(1 if min_weight is None else min_weight, 0 if min_support is None else min_support, support_radius,
+                   0 if min_component is None else min_component)
+
+    def settings(self) -> Dict:
+        return {"min_weight": self.min_weight, "min_support": self.min_support, "support_radius": self.support_radius,
+                "min_component": self.min_component}
+
+    def apply(self, fuser: "VoxelFuser", arrays: bool = False) -> torch.Tensor:
+        """-> the device keep mask, uint8 (capacity,), for fuser.extract(keep=...).  Sets last_stats = {voxels,
+        eligible, after_support, after_components, components, components_kept, sweeps}.  The components are labelled
+        only when min_component > 1 (or arrays=True): otherwise components / components_kept are None and sweeps is 0.
+        arrays=True (tests) also keeps last_arrays = {support int32, label int64, size int32} per slot, -1 / all ones /
+        0 where a slot has none."""
+        if fuser.table is None:
+            fuser.reserve(0)
+        table, cap, dev = fuser.table, fuser.capacity, fuser.device
+        keep = torch.empty(cap, dtype=torch.uint8, device=dev)
+        support = torch.empty(cap, dtype=torch.int32, device=dev) if arrays else None
+        counters = torch.zeros(8, dtype=torch.int64, device=dev)
+        ops.voxel_support(table, self.min_weight, self.support_radius, self.min_support, keep, support, counters)
+        sweeps, label, size = 0, None, None
+        labelled = self.min_component > 1 or arrays
+        if labelled:
+            label, sweeps = self.label_components(fuser, keep, int(counters[2].item()))
+            size = torch.empty(cap, dtype=torch.int32, device=dev)
+            ops.voxel_component_sizes(table, label, size)
+            ops.voxel_component_filter(table, label, size, self.min_component, keep, counters)
+        c = [int(x) for x in counters.tolist()]
+        st = dict(zip(ops.VOXEL_CLEAN_COUNTERS, c))
+        if not labelled:
+            st.update(after_components=st["after_support"], components=None, components_kept=None)
+        st["sweeps"] = sweeps
+        self.last_stats = st
+        self.last_arrays = {"support": support, "label": label, "size": size} if arrays else None
+        return keep
+
+    def label_components(self, fuser: "VoxelFuser", keep: torch.Tensor, survivors: int) -> Tuple[torch.Tensor, int]:
+        """Stage B's labels for the stage-A mask `keep` with `survivors` voxels set: -> (label int64 (capacity,): the
+        smallest key of the slot's component, all ones for a slot that did not survive; the sweeps run).  The kernels
+        only launch; the loop is here: SWEEPS_PER_READ sweeps, one read of their `changed` words, until a sweep changed
+        nothing.  Raises when that takes more sweeps than neighbour propagation alone can need."""
+        table, dev = fuser.table, fuser.device
+        label = torch.empty(fuser.capacity, dtype=torch.int64, device=dev)
+        ops.voxel_label_init(table, keep, label)
+        changed = torch.empty(self.SWEEPS_PER_READ, dtype=torch.int32, device=dev)
+        # a sweep moves a component's smallest key at least one voxel further along every path (it reads what the
+        # previous launch wrote, or something newer), so `survivors` sweeps reach the fixed point; one more sees no change
+        bound, sweeps = int(survivors) + 1, 0
+        while True:
+            changed.zero_()
+            for j in range(self.SWEEPS_PER_READ):
+                ops.voxel_label_sweep(table, label, changed[j:j + 1])
+            quiet = np.flatnonzero(changed.cpu().numpy() == 0)
+            if len(quiet):
+                return label, sweeps + int(quiet[0]) + 1
+            sweeps += self.SWEEPS_PER_READ
+            if sweeps > bound:
+                raise RuntimeError(f"component labelling did not settle in {sweeps} sweeps over {survivors} voxels")
+
+    def summary(self) -> str:
+        st = self.last_stats
+        return (f"{st['voxels']} voxels -> {st['eligible']} after weight >= {self.min_weight} -> {st['after_support']} "
+                f"after support >= {self.min_support} (radius {self.support_radius}) -> {st['after_components']} after "
+                f"components >= {self.min_component}")
+
+
 class VoxelFuser:
     """A device voxel table: fuse_pixels / fuse_points accumulate, extract() returns the sorted voxels.  The table
     (64 B per slot) is allocated on first use, re-used after clear(), and grows (keeping its contents) when the points
@@ -152,9 +268,9 @@ class VoxelFuser:
         ops.voxel_fuse_points(self.table, self.stats, points, colors, weights, self.inv_voxel)
         self.bound += n
 
-    def extract_async(self):
+    def extract_async(self, keep: Optional[torch.Tensor] = None):
         """Queue the extraction; -> (keys, points, colors, weights) device buffers of self.bound rows and a device copy
-        of the stats (stats[2] = the number of valid rows, stats[0] = dropped points)."""
+        of the stats (stats[2] = the number of valid rows, stats[0] = dropped points).  keep: MapCleaner.apply's mask."""
         if self.table is None:
             self.reserve(0)
         i = self._turn
@@ -164,13 +280,13 @@ class VoxelFuser:
             self._outs[i] = None                 # free the smaller set first
             self._outs[i] = ops.voxel_empty_outputs(rows, self.device)
         keys, pts, cols, w = self._outs[i]
-        ops.voxel_extract(self.table, self.stats, self.voxel_size, self.bound, out=(keys, pts, cols, w))
+        ops.voxel_extract(self.table, self.stats, self.voxel_size, self.bound, out=(keys, pts, cols, w), keep=keep)
         return (keys, pts, cols, w), self.stats.clone()
 
-    def extract(self) -> Dict[str, np.ndarray]:
+    def extract(self, keep: Optional[torch.Tensor] = None) -> Dict[str, np.ndarray]:
         """Host arrays in ascending key order: keys u64, points f32 (V,3), colors u8 (V,3), weights i32 (V,); also
-        sets self.last_stats = {'voxels', 'dropped', 'overflow'}."""
-        (keys, pts, cols, w), stats = self.extract_async()
+        sets self.last_stats = {'voxels', 'dropped', 'overflow'}.  keep (MapCleaner.apply): only the voxels it marks."""
+        (keys, pts, cols, w), stats = self.extract_async(keep)
         st = stats.cpu().numpy()
         V = int(st[2])
         self.last_stats = {"voxels": V, "dropped": int(st[0]), "overflow": int(st[1]) + int(st[3])}
@@ -274,9 +390,11 @@ def chunk_transform(chunk: Dict) -> torch.Tensor:
     return torch.eye(4, dtype=torch.float64) if G is None else torch.as_tensor(G, dtype=torch.float64).reshape(4, 4)
 
 
-def fuse_chunk_clouds(chunks: Iterable[Dict], voxel_size: float, device="cuda") -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+def fuse_chunk_clouds(chunks: Iterable[Dict], voxel_size: float, device="cuda",
+                      cleaner: Optional[MapCleaner] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """Every chunk's dense_cloud moved by chunk_transform() and fused, weighted by its voxel weights ->
-    (points f32 (V,3), colors u8 (V,3), weights i32 (V,)) in ascending key order.  Chunks without a cloud are skipped."""
+    (points f32 (V,3), colors u8 (V,3), weights i32 (V,)) in ascending key order.  Chunks without a cloud are skipped.
+    cleaner: its filters decide on the fused table which voxels are extracted (one line with the counts is printed)."""
     device = torch.device(device)
     clouds = [(c["dense_cloud"], chunk_transform(c)) for c in chunks if c.get("dense_cloud") is not None]
     fuser = VoxelFuser(voxel_size, device)
@@ -289,7 +407,11 @@ def fuse_chunk_clouds(chunks: Iterable[Dict], voxel_size: float, device="cuda") 
         cols = upload(torch.as_tensor(cl["colors"]).reshape(-1, 3), device).contiguous()
         w = upload(torch.as_tensor(cl["weights"]).reshape(-1), device).contiguous()
         fuser.fuse_points(pts, cols, w)
-    out = fuser.extract()
+    keep = None
+    if cleaner is not None:
+        keep = cleaner.apply(fuser)
+        print(f"   🧹 Dense map cleaned: {cleaner.summary()}")
+    out = fuser.extract(keep)
     return out["points"], out["colors"], out["weights"]
 
 

@@ -4,7 +4,8 @@ Pi3SLAMOnline.chunk_reconstructions).  Files and formats mirror slam/offline_rec
   final_points.ply        every track of every chunk (sparse_points_colors)
   final_camera_poses.ply  every view's camera centre, overlap views twice (all_views)
   trajectory_tum.txt      the de-duplicated trajectory: first occurrence of a view name wins (unique_views)
-  dense_points.ply        the chunks' dense clouds fused in the world frame (fuse_dense_map; dense_map.py)
+  dense_points.ply        the chunks' dense clouds fused in the world frame (fuse_dense_map; dense_map.py), cleaned by a
+                          dense_map.MapCleaner when one is given
   renders/                depth / colour images of that map, overview.png, cameras.json (write_renders; render.py)
 
 write_outputs writes them all, in that order.  A chunk needs dist.COLLECT_KEYS for it, nothing else."""
@@ -132,15 +133,16 @@ class DenseMap(NamedTuple):
     voxel_size: float
 
 
-def fuse_dense_map(chunks: Sequence[Dict], device) -> Optional[DenseMap]:
+def fuse_dense_map(chunks: Sequence[Dict], device, cleaner=None) -> Optional[DenseMap]:
     """The chunks' dense clouds (chunks created with a dense voxel size) fused in the world frame; None when no chunk
-    carries one.  The voxel size is the first cloud's: the world frame is chunk 0's frame."""
+    carries one.  The voxel size is the first cloud's: the world frame is chunk 0's frame.  cleaner: a
+    dense_map.MapCleaner whose filters choose the voxels of the map (None: all of them)."""
     first = next((d["dense_cloud"] for d in chunks if d.get("dense_cloud") is not None), None)
     if first is None:
         return None
     from .dense_map import fuse_chunk_clouds
     voxel = float(first["voxel_size"])
-    return DenseMap(*fuse_chunk_clouds(chunks, voxel, device), voxel)
+    return DenseMap(*fuse_chunk_clouds(chunks, voxel, device, cleaner), voxel)
 
 
 def write_dense_points(dense: DenseMap, path: str) -> int:
@@ -151,13 +153,14 @@ def write_dense_points(dense: DenseMap, path: str) -> int:
 
 
 def write_renders(chunks: Sequence[Dict], dense: Optional[DenseMap], out_dir: str, every: Optional[int], overview: bool,
-                  min_weight: int = 1, splat_scale: float = 1.0, device="cuda") -> Optional[Tuple[int, Dict[str, float]]]:
+                  min_weight: int = 1, splat_scale: float = 1.0, device="cuda",
+                  dense_cleaner=None) -> Optional[Tuple[int, Dict[str, float]]]:
     """<out_dir>/depth_<frame>.png (16 bit, millimetres, 0 = empty) and color_<frame>.png of the dense map for every
     `every`-th view of the de-duplicated trajectory, overview.png (a top-down orthographic view with the trajectory
     in red) and cameras.json -> (rendered views, {'total', 'png'} seconds).  `dense`: the map a caller has already fused
-    (else it is fused here).  Without dense clouds in the chunks: one line, no directory, None."""
+    (else it is fused here, through `dense_cleaner`).  Without dense clouds in the chunks: one line, no directory, None."""
     if dense is None:
-        dense = fuse_dense_map(chunks, device)
+        dense = fuse_dense_map(chunks, device, dense_cleaner)
     if dense is None:
         print("   ℹ️  No dense clouds in the chunks (create them with a dense voxel size): no renders")
         return None
@@ -209,9 +212,10 @@ def write_renders(chunks: Sequence[Dict], dense: Optional[DenseMap], out_dir: st
 
 def write_outputs(chunks: Sequence[Dict], output_dir: str, device="cuda", render_every: Optional[int] = None,
                   render_overview: bool = False, render_min_weight: int = 1,
-                  render_splat_scale: float = 1.0) -> Optional[Dict[str, float]]:
+                  render_splat_scale: float = 1.0, dense_cleaner=None) -> Optional[Dict[str, float]]:
     """Every output file of stage 2 under output_dir; a file that fails is reported and the others are still written.
-    Returns the seconds of write_renders when renders were written."""
+    Returns the seconds of write_renders when renders were written.  dense_cleaner (dense_map.MapCleaner): the dense
+    map of the PLY and of the renders is the cleaned one."""
     try:
         pts, cols = sparse_points_colors(chunks)
         if pts.size > 0:
@@ -231,7 +235,7 @@ def write_outputs(chunks: Sequence[Dict], output_dir: str, device="cuda", render
         print(f"❌ Failed to save TUM trajectory: {e}")
     dense = None
     try:
-        dense = fuse_dense_map(chunks, device)
+        dense = fuse_dense_map(chunks, device, dense_cleaner)
         if dense is not None:
             write_dense_points(dense, os.path.join(output_dir, "dense_points.ply"))
     except Exception as e:  # noqa: BLE001
@@ -239,7 +243,7 @@ def write_outputs(chunks: Sequence[Dict], output_dir: str, device="cuda", render
     if render_every is not None or render_overview:
         try:       # the renders draw the map that was just fused for the PLY
             done = write_renders(chunks, dense, os.path.join(output_dir, "renders"), render_every, render_overview,
-                                 render_min_weight, render_splat_scale, device)
+                                 render_min_weight, render_splat_scale, device, dense_cleaner)
             return done[1] if done else None
         except Exception as e:  # noqa: BLE001
             print(f"❌ Failed to save the renders of the dense map: {e}")

@@ -65,7 +65,13 @@ class Pi3SLAMOnline:
                  hip_graph: bool = True, output_dir: Optional[str] = None, num_loader_workers: int = 0,
                  bundle_adjust: bool = True, reuse_overlap_encoder: bool = False,
                  dense_voxel_size: Optional[float] = None, dense_min_views: Optional[int] = None,
-                 dense_view_radius: int = 3, dense_view_stride: int = 2, dense_depth_tolerance: float = 0.03):
+                 dense_view_radius: int = 3, dense_view_stride: int = 2, dense_depth_tolerance: float = 0.03,
+                 dense_min_weight: Optional[int] = None, dense_min_support: Optional[int] = None,
+                 dense_support_radius: int = 1, dense_min_component: Optional[int] = None):
+        from .dense_map import MapCleaner
+        # filters on the fused dense map of save_dense_map / save_renders (all off by default: no cleaner)
+        self.dense_cleaner = MapCleaner.from_options(dense_min_weight, dense_min_support, dense_support_radius,
+                                                     dense_min_component)
         self.use_inverse_depth = bool(use_inverse_depth)   # online_reconstructor.py:246,1018,1235
         self.chunk_length, self.overlap = int(chunk_length), int(overlap)
         self.pixel_limit = 255000 // 2
@@ -289,13 +295,14 @@ class Pi3SLAMOnline:
         export.write_ply(pts, cols if cols.size else np.ones_like(pts), save_path)
 
     def _fused_map(self) -> export.DenseMap:
-        dense = export.fuse_dense_map(self.chunk_reconstructions, str(self.device))
+        dense = export.fuse_dense_map(self.chunk_reconstructions, str(self.device), self.dense_cleaner)
         if dense is None:
             raise RuntimeError("no dense clouds: construct Pi3SLAMOnline with dense_voxel_size")
         return dense
 
     def save_dense_map(self, save_path: str) -> int:
-        """The chunks' dense clouds (dense_voxel_size set) fused in the world frame -> a PLY; returns the voxel count."""
+        """The chunks' dense clouds (dense_voxel_size set) fused in the world frame, cleaned by the dense_min_* options
+        when one is set -> a PLY; returns the voxel count."""
         return export.write_dense_points(self._fused_map(), save_path)
 
     def save_renders(self, out_dir: str, every: Optional[int] = 10, overview: bool = True, min_weight: int = 1,

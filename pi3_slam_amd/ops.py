@@ -674,16 +674,85 @@ def voxel_empty_outputs(rows: int, device):
             torch.empty(m, 3, device=device, dtype=torch.uint8), torch.empty(m, device=device, dtype=torch.int32))
 
 
-def voxel_extract(table: torch.Tensor, stats: torch.Tensor, voxel_size: float, max_out: int, out=None):
+def voxel_extract(table: torch.Tensor, stats: torch.Tensor, voxel_size: float, max_out: int, out=None,
+                  keep: Optional[torch.Tensor] = None):
     """-> device (keys int64, points f32 (,3), colors uint8 (,3), weights int32) with >= max_out rows (`out`, or fresh
-    buffers), unordered; the number of valid entries lands in stats[2]."""
+    buffers), unordered; the number of valid entries lands in stats[2].  keep uint8 (capacity,): only the slots it
+    marks (pi3_voxel_extract_kept)."""
     lib = _L.load()
     keys, pts, cols, w = out if out is not None else voxel_empty_outputs(max_out, table.device)
     assert keys.shape[0] >= max_out and pts.shape[0] >= max_out and cols.shape[0] >= max_out and w.shape[0] >= max_out
-    rc = lib.pi3_voxel_extract(table.data_ptr(), table.numel() // 8, float(voxel_size), keys.data_ptr(), pts.data_ptr(),
-                               cols.data_ptr(), w.data_ptr(), int(max_out), stats.data_ptr(), _L.stream_ptr())
-    _L.check(rc, "pi3_voxel_extract")
+    if keep is None:
+        rc = lib.pi3_voxel_extract(table.data_ptr(), table.numel() // 8, float(voxel_size), keys.data_ptr(),
+                                   pts.data_ptr(), cols.data_ptr(), w.data_ptr(), int(max_out), stats.data_ptr(),
+                                   _L.stream_ptr())
+        _L.check(rc, "pi3_voxel_extract")
+    else:
+        _slot_array(keep, table, torch.uint8)
+        rc = lib.pi3_voxel_extract_kept(table.data_ptr(), table.numel() // 8, float(voxel_size), keys.data_ptr(),
+                                        pts.data_ptr(), cols.data_ptr(), w.data_ptr(), int(max_out), stats.data_ptr(),
+                                        keep.data_ptr(), _L.stream_ptr())
+        _L.check(rc, "pi3_voxel_extract_kept")
     return keys, pts, cols, w
+
+
+# ---- cleaning the fused map (csrc/voxel_clean.hip): arrays with one entry per slot of the table
+VOXEL_CLEAN_COUNTERS = ("voxels", "eligible", "after_support", "after_components", "components", "components_kept")
+
+
+def _slot_array(t: torch.Tensor, table: torch.Tensor, dtype) -> None:
+    assert t.dtype == dtype and t.is_contiguous() and t.device == table.device and t.numel() == table.numel() // 8
+
+
+def voxel_support(table: torch.Tensor, min_weight: int, radius: int, min_support: int, keep: torch.Tensor,
+                  support: Optional[torch.Tensor], counters: torch.Tensor) -> None:
+    """Stage A: keep uint8 (capacity,), support int32 (capacity,) or None, counters int64 (8,) (zeroed by the call)."""
+    lib = _L.load()
+    assert table.dtype == torch.int64 and table.is_contiguous() and table.numel() % 8 == 0
+    _slot_array(keep, table, torch.uint8)
+    if support is not None:
+        _slot_array(support, table, torch.int32)
+    assert counters.dtype == torch.int64 and counters.is_contiguous() and counters.numel() >= 8
+    rc = lib.pi3_voxel_support(table.data_ptr(), table.numel() // 8, int(min_weight), int(radius), int(min_support),
+                               keep.data_ptr(), _L.ptr(support), counters.data_ptr(), _L.stream_ptr())
+    _L.check(rc, "pi3_voxel_support")
+
+
+def voxel_label_init(table: torch.Tensor, keep: torch.Tensor, label: torch.Tensor) -> None:
+    lib = _L.load()
+    _slot_array(keep, table, torch.uint8)
+    _slot_array(label, table, torch.int64)
+    _L.check(lib.pi3_voxel_label_init(table.data_ptr(), table.numel() // 8, keep.data_ptr(), label.data_ptr(),
+                                      _L.stream_ptr()), "pi3_voxel_label_init")
+
+
+def voxel_label_sweep(table: torch.Tensor, label: torch.Tensor, changed: torch.Tensor) -> None:
+    """One sweep; changed: one int32 on the device (a view of one element is fine), zeroed by the caller."""
+    lib = _L.load()
+    _slot_array(label, table, torch.int64)
+    assert changed.dtype == torch.int32 and changed.numel() == 1 and changed.device == table.device
+    _L.check(lib.pi3_voxel_label_sweep(table.data_ptr(), table.numel() // 8, label.data_ptr(), changed.data_ptr(),
+                                       _L.stream_ptr()), "pi3_voxel_label_sweep")
+
+
+def voxel_component_sizes(table: torch.Tensor, label: torch.Tensor, size: torch.Tensor) -> None:
+    lib = _L.load()
+    _slot_array(label, table, torch.int64)
+    _slot_array(size, table, torch.int32)
+    _L.check(lib.pi3_voxel_component_sizes(table.data_ptr(), table.numel() // 8, label.data_ptr(), size.data_ptr(),
+                                           _L.stream_ptr()), "pi3_voxel_component_sizes")
+
+
+def voxel_component_filter(table: torch.Tensor, label: torch.Tensor, size: torch.Tensor, min_component: int,
+                           keep: torch.Tensor, counters: torch.Tensor) -> None:
+    lib = _L.load()
+    _slot_array(label, table, torch.int64)
+    _slot_array(size, table, torch.int32)
+    _slot_array(keep, table, torch.uint8)
+    assert counters.dtype == torch.int64 and counters.is_contiguous() and counters.numel() >= 8
+    rc = lib.pi3_voxel_component_filter(table.data_ptr(), table.numel() // 8, label.data_ptr(), size.data_ptr(),
+                                        int(min_component), keep.data_ptr(), counters.data_ptr(), _L.stream_ptr())
+    _L.check(rc, "pi3_voxel_component_filter")
 
 
 def dense_consistency(points: torch.Tensor, local_points: torch.Tensor, conf: Optional[torch.Tensor],

@@ -33,8 +33,15 @@ class OfflineReconstructor:
                  use_inverse_depth: bool = False, device: str = "cuda", save_observations: bool = False,
                  bundle_adjust: bool = True, ba_sanity_gate: bool = True, align_estimated_tracks_only: bool = False,
                  render_every: Optional[int] = None, render_overview: bool = False, render_min_weight: int = 1,
-                 render_splat_scale: float = 1.0):
+                 render_splat_scale: float = 1.0, dense_min_weight: Optional[int] = None,
+                 dense_min_support: Optional[int] = None, dense_support_radius: int = 1,
+                 dense_min_component: Optional[int] = None):
         self.chunk_dir, self.output_dir = chunk_dir, output_dir
+        # dense_min_weight / dense_min_support / dense_min_component: filters on the fused dense map before it is written
+        # and rendered (dense_map.MapCleaner); all off by default, and then no cleaner exists
+        from .dense_map import MapCleaner
+        self.dense_cleaner = MapCleaner.from_options(dense_min_weight, dense_min_support, dense_support_radius,
+                                                     dense_min_component)
         # render_every / render_overview: after dense_points.ply, depth + colour images of the dense map from every N-th
         # view of the trajectory and a top-down overview, under <output>/renders (pi3_slam_amd/render.py); off by default
         if render_every is not None and int(render_every) <= 0:
@@ -168,7 +175,7 @@ class OfflineReconstructor:
         if rank == 0:
             self.reconstructions = done
             seconds = export.write_outputs(done, self.output_dir, self.device, self.render_every, self.render_overview,
-                                           self.render_min_weight, self.render_splat_scale)
+                                           self.render_min_weight, self.render_splat_scale, self.dense_cleaner)
             if seconds is not None:
                 self.render_seconds = seconds
         if grouped:

@@ -13,7 +13,14 @@
      against the 8 TB/s HBM figure of profiles/ - a lower bound of the traffic: local z sits at a 12-byte stride, so
      whole lines of local_points are fetched (about 12 B per pixel, not 4), and a gather fetches a line, not 4 bytes; and the creator leg a third time with the filter on.
 
-Prints one JSON line.  Usage: python tools/dense_fusion_timing.py [--voxel 0.02] [--rounds 3] [--chunks 4] [--consistency]"""
+  4. --clean: the map-cleaning filters (csrc/voxel_clean.hip, dense_map.MapCleaner) on the table of leg 1 and on a
+     synthetic map of about 1 M voxels (the six faces of a 410-voxel box and 1 % floaters inside it), HIP events, median
+     of 20 after 3 warm-up runs: the support kernel at radius 1 and 2 (min_support 4: it probes), the labelling in total
+     (label init, the host's sweep loop with its reads of the `changed` words, sizes, the component filter) with its
+     sweep count, and the masked extract; with the counted bytes of the support kernel (26 or 124 probes of a 64-byte
+     slot per eligible voxel, the first slot of each probe chain only) and the rate they give.
+
+Prints one JSON line.  Usage: python tools/dense_fusion_timing.py [--voxel 0.02] [--rounds 3] [--chunks 4] [--consistency] [--clean]"""
 from __future__ import annotations
 
 import argparse
@@ -43,7 +50,64 @@ def synthetic_frames_u8(n: int, h: int, w: int, seed: int) -> torch.Tensor:
     return (img.clamp(0, 1) * 255).to(torch.uint8).contiguous().pin_memory()
 
 
-def kernel_times(voxel: float, dev: str, reps: int = 20):
+def clean_times(fz, reps: int = 20):
+    """The cleaning stages on a filled VoxelFuser (min_support 4, min_component 50; starting points, not optima)."""
+    from pi3_slam_amd import ops
+    from pi3_slam_amd.dense_map import MapCleaner
+    cl = MapCleaner(min_support=4, min_component=50)
+    dev, cap = fz.device, fz.capacity
+    keep = torch.empty(cap, dtype=torch.uint8, device=dev)
+    counters = torch.zeros(8, dtype=torch.int64, device=dev)
+    size = torch.empty(cap, dtype=torch.int32, device=dev)
+    t = {"support_r1_ms": [], "support_r2_ms": [], "labelling_ms": [], "extract_kept_ms": []}
+    sweeps = 0
+    for i in range(3 + reps):
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
+        e[0].record()
+        ops.voxel_support(fz.table, 1, 2, 4, keep, None, counters)
+        e[1].record()
+        ops.voxel_support(fz.table, 1, 1, 4, keep, None, counters)
+        e[2].record()
+        label, sweeps = cl.label_components(fz, keep, int(counters[2].item()))
+        ops.voxel_component_sizes(fz.table, label, size)
+        ops.voxel_component_filter(fz.table, label, size, cl.min_component, keep, counters)
+        e[3].record()
+        fz.extract_async(keep)
+        e[4].record()
+        torch.cuda.synchronize()
+        if i >= 3:
+            for k, (a, b) in zip(("support_r2_ms", "support_r1_ms", "labelling_ms", "extract_kept_ms"), zip(e, e[1:])):
+                t[k].append(a.elapsed_time(b))
+    c = dict(zip(ops.VOXEL_CLEAN_COUNTERS, (int(x) for x in counters.tolist())))
+    res = {k: float(np.median(v)) for k, v in t.items()} | {k + "_minmax": [float(np.min(v)), float(np.max(v))]
+                                                           for k, v in t.items()}
+    for r, cells in ((1, 26), (2, 124)):
+        b = c["eligible"] * cells * 64 + cap * 16
+        res[f"support_r{r}_bytes"] = b
+        res[f"support_r{r}_TBps"] = b / (res[f"support_r{r}_ms"] * 1e-3) / 1e12
+    return res | {"sweeps": sweeps, "table_slots": cap, "side_bytes_per_slot": 1 + 8 + 4, **c}
+
+
+def synthetic_box_map(voxel: float, dev: str, side: int = 410, seed: int = 0):
+    """About 1 M voxels: the six faces of a box of `side` voxels, one point per voxel, and 1 % floaters inside."""
+    from pi3_slam_amd.dense_map import VoxelFuser
+    g = torch.Generator().manual_seed(seed)
+    a = torch.arange(side)
+    u, v = (x.reshape(-1) for x in torch.meshgrid(a, a, indexing="ij"))
+    faces = []
+    for axis in range(3):
+        for w in (0, side - 1):
+            f = [u, v]
+            f.insert(axis, torch.full_like(u, w))
+            faces.append(torch.stack(f, 1))
+    idx = torch.cat(faces + [torch.randint(1, side - 1, (6 * side * side // 100, 3), generator=g)]) - side // 2
+    pts = ((idx.double() + 0.5) * voxel).float().to(dev).contiguous()
+    fz = VoxelFuser(voxel, dev)
+    fz.fuse_points(pts, None, None)
+    return fz
+
+
+def kernel_times(voxel: float, dev: str, reps: int = 20, clean: bool = False):
     import synth_sequence as ss
     from pi3_slam_amd.chunk_creator import OfflineChunkCreator
     from pi3_slam_amd.dense_map import VoxelFuser
@@ -69,9 +133,12 @@ def kernel_times(voxel: float, dev: str, reps: int = 20):
             for k, (a, b) in zip(t, zip(e, e[1:])):
                 t[k].append(a.elapsed_time(b))
     res = fz.extract()
-    return {k: float(np.median(v)) for k, v in t.items()} | {
+    out = {k: float(np.median(v)) for k, v in t.items()} | {
         "voxels": len(res["keys"]), "pixels": int(pts.numel() // 3), "masked_in": int(masks.sum()),
         "table_slots": fz.capacity, "table_bytes": fz.capacity * 64}
+    if clean:
+        out["clean"] = clean_times(fz, reps)
+    return out
 
 
 def consistency_times(dev: str, reps: int = 20):
@@ -177,10 +244,14 @@ def main():
     ap.add_argument("--kernels-only", action="store_true")
     ap.add_argument("--consistency", action="store_true", help="also time the multi-view consistency filter (kernel and "
                                                                "a creator leg with it on)")
+    ap.add_argument("--clean", action="store_true", help="also time the map-cleaning filters on the chunk's table and on "
+                                                         "a synthetic map of about 1 M voxels")
     a = ap.parse_args()
     dev = "cuda:0"
     torch.cuda.set_device(0)
-    out = {"voxel_size": a.voxel, "kernels": kernel_times(a.voxel, dev)}
+    out = {"voxel_size": a.voxel, "kernels": kernel_times(a.voxel, dev, clean=a.clean)}
+    if a.clean:
+        out["clean_synthetic"] = clean_times(synthetic_box_map(a.voxel, dev))
     if a.consistency:
         out["consistency"] = consistency_times(dev)
     if not a.kernels_only:

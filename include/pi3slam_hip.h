@@ -461,6 +461,48 @@ int pi3_render_splat(const float* points, const int* weights, long V, const doub
 int pi3_render_resolve(const unsigned long long* zbuf, const unsigned char* colors, long V, int M, int H, int W,
                        float* depth, unsigned char* color, int* index, unsigned long long* stats, void* stream);
 
+/* ---- surface normals of the dense voxel map (csrc/voxel_normals.hip).  The table's slot is full, so the normals live
+ * beside it: nacc, caller-owned DEVICE memory of int64 [capacity][4] = Nx, Ny, Nz, cnt per slot, parallel to the table
+ * and zeroed by the caller.  Every update is a 64-bit integer atomic add: the sums do not depend on the order in which
+ * the atomics land.  Slots are looked up read-only; nothing here claims one, so the matching fusion call ran first on
+ * the same inputs.  Arithmetic is f64 from the fp32 inputs, no contraction, every operation rounded on its own.
+ * stats of the two fusion calls: DEVICE uint64 [4], accumulated (the caller zeroes them) = contributions, candidates
+ * that could not contribute, degenerate normals, contributions whose slot was not found (0 after the matching fusion).
+ *
+ * pi3_voxel_fuse_pixel_normals: after pi3_voxel_fuse_pixels on the same points / conf / masks / N H W / threshold /
+ * inv_voxel.  Pixel (f, y, x) is a candidate under that call's predicate (mask != 0, conf > conf_logit_thr, the three
+ * axes quantise).  It contributes when 1 <= x <= W - 2, 1 <= y <= H - 2 and its neighbours (y, x +- 1), (y +- 1, x) of
+ * the same frame are candidates too (else stats[1]):
+ *   a = P(y, x + 1) - P(y, x - 1),  b = P(y + 1, x) - P(y - 1, x),  n = b x a  (nx = by az - bz ay, ...; with x right,
+ *   y down, z forward it faces the camera);  l2 = (nx nx + ny ny) + nz nz;  no contribution unless l2 > 0 and finite
+ *   (stats[2]);  l = sqrt(l2);  q_a = (int64) rint((n_a / l) * 32768), half to even;  nacc[slot] += (qx, qy, qz, 1). */
+int pi3_voxel_fuse_pixel_normals(const void* table, long capacity, long long* nacc, const float* points,
+                                 const float* conf, const unsigned char* masks, int N, int H, int W,
+                                 float conf_logit_thr, float inv_voxel, unsigned long long* stats, void* stream);
+/* After pi3_voxel_fuse_points on the same points (f32 [n][3], already in the world frame).  normals f32 [n][3] in the
+ * cloud's own frame, nweights int32 [n], rot9 DEVICE f64 [9] row-major: the rotation of the cloud's similarity.  A row
+ * with nweights > 0, a finite non-zero normal (else stats[2]) and a quantisable point (else stats[1]) adds
+ *   nweights * q_a,  q_a = rint(((r_a0 nx + r_a1 ny) + r_a2 nz) * 32768) limited to +-2^31,  and nweights to cnt. */
+int pi3_voxel_fuse_point_normals(const void* table, long capacity, long long* nacc, const float* points,
+                                 const float* normals, const int* nweights, const double* rot9, long n, float inv_voxel,
+                                 unsigned long long* stats, void* stream);
+/* One row per occupied slot, or per occupied slot with keep_or_null[slot] != 0 (uint8 [capacity]): keys uint64 [V],
+ * normals f32 [V][3] = (float)(N_a / sqrt((Nx Nx + Ny Ny) + Nz Nz)), (0, 0, 0) when cnt == 0 or the three sums are 0,
+ * nweights int32 [V] = min(cnt, 2^31 - 1); at most max_out rows, in no defined order (sort by key on the host: that
+ * lines the rows up with pi3_voxel_extract's).  stats: DEVICE uint64 [4], zeroed by the call = rows, rows that did not
+ * fit max_out, stored rows with a non-zero normal, spare. */
+int pi3_voxel_extract_normals(const void* table, long capacity, const long long* nacc, const unsigned char* keep_or_null,
+                              unsigned long long* keys, float* normals, int* nweights, long max_out,
+                              unsigned long long* stats, void* stream);
+/* Element-wise over pi3_render_resolve's index int32 [M][H][W]; normals f32 [V][3] in the world frame, cams as
+ * pi3_render_splat's.  A pixel with 0 <= idx < V and a finite non-zero normal:
+ *   nc = R_wc n, nc_x = (c0 nx + c1 ny) + c2 nz, likewise nc_y (c4..c6) and nc_z (c8..c10);
+ *   normal_rgb uint8 [M][H][W][3] = clamp(rint((nc + 1) * 127.5), 0, 255) per axis;
+ *   shaded uint8 [M][H][W] = clamp(rint(255 * max(0, -nc_z)), 0, 255): a headlight along the optical axis.
+ * Every other pixel is 0 in both.  stats: DEVICE uint64 [>= 1], accumulated; stats[0] += the shaded pixels. */
+int pi3_render_shade(const int* index, const float* normals, long V, const double* cams, int M, int H, int W,
+                     unsigned char* normal_rgb, unsigned char* shaded, unsigned long long* stats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -72,6 +72,8 @@ class OfflineCreatorConfig:
     dense_view_radius: int = 3                # neighbours i +- s * dense_view_stride, s = 1..dense_view_radius
     dense_view_stride: int = 2
     dense_depth_tolerance: float = 0.03       # relative depth difference that still counts as the same surface
+    dense_normals: bool = False               # with dense_voxel_size: the cloud also carries 'normals' / 'normal_weights',
+                                              # a camera-facing surface normal per voxel (dense_map.NormalAccumulator)
 
 
 _UV_CACHE: Dict = {}

@@ -49,7 +49,9 @@ CREATE_FLAGS: Sequence[Tuple[str, Dict]] = (
 CREATE_SWITCHES = (("--device-resize", "Resize + ToTensor on the GPU (loader workers decode only)"),
                    ("--hip-graph", "replay the per-chunk forward as one captured hipGraph"),
                    ("--reuse-overlap-encoder", "overlap frames take their encoder output from the previous chunk "
-                                               "(bit-identical; single-GPU streams)"))
+                                               "(bit-identical; single-GPU streams)"),
+                   ("--dense-normals", "with --dense-voxel-size: every voxel of the dense cloud also gets a surface normal "
+                                       "facing the cameras that saw it (dense_points.ply with nx ny nz, shaded renders)"))
 RECON_FLAGS: Sequence[Tuple[str, Dict]] = (
     ("--chunks", dict(REQ, help="directory holding chunks/chunk_*.pt and chunk_metadata.json")),
     ("--output", dict(REQ, help="directory for trajectory_tum.txt and the ply files")),
@@ -139,6 +141,8 @@ ONLINE_SWITCHES = (("--save_chunk_reconstructions", "save each chunk reconstruct
                    ("--save_debug_reconstructions", "accepted for compatibility"),
                    ("--save_debug_projections", "accepted for compatibility"),
                    ("--use_inverse_depth", "inverse-depth parametrization in both bundle adjustments"),
+                   ("--dense_normals", "with --dense_voxel_size: surface normals in dense_points.ply (nx ny nz) and "
+                                       "normal / shaded images under renders/"),
                    ("--no_visualization", "accepted for compatibility (there is never a window)"),
                    ("--keep_viz_open", "accepted for compatibility"),
                    ("--save_tum", "save the trajectory in TUM format"),
@@ -197,7 +201,7 @@ def run_create(a: argparse.Namespace) -> None:
         hip_graph=a.hip_graph, reuse_overlap_encoder=a.reuse_overlap_encoder, dense_voxel_size=a.dense_voxel_size,
         dense_conf_threshold=a.dense_conf_threshold, dense_min_views=a.dense_min_views,
         dense_view_radius=a.dense_view_radius, dense_view_stride=a.dense_view_stride,
-        dense_depth_tolerance=a.dense_depth_tolerance)
+        dense_depth_tolerance=a.dense_depth_tolerance, dense_normals=a.dense_normals)
     OfflineChunkCreator(cfg).process_and_save(paths[lo:hi])
 
 
@@ -256,7 +260,8 @@ def run_online(a: argparse.Namespace) -> None:
         dense_min_views=a.dense_min_views, dense_view_radius=a.dense_view_radius,
         dense_view_stride=a.dense_view_stride, dense_depth_tolerance=a.dense_depth_tolerance,
         dense_min_weight=a.dense_min_weight, dense_min_support=a.dense_min_support,
-        dense_support_radius=a.dense_support_radius, dense_min_component=a.dense_min_component)
+        dense_support_radius=a.dense_support_radius, dense_min_component=a.dense_min_component,
+        dense_normals=a.dense_normals)
     slam.save_transformed_reconstructions = a.save_transformed_reconstructions
     slam.save_debug_reconstructions = a.save_debug_reconstructions
     slam.process_chunks(paths)

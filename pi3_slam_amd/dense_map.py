@@ -14,7 +14,13 @@ neighbouring frames of its chunk: the filter's pixel mask takes the place of the
 Optionally (MapCleaner, csrc/voxel_clean.hip) stage 2 drops voxels of the fused world-frame table before the extraction:
 a minimum weight, a minimum number of occupied neighbour cells, a minimum size of the connected component.
 
-The accumulators are integers, so a map is bitwise reproducible and tests/dense_map_ref.py reproduces it bit for bit.
+Optionally (NormalAccumulator, csrc/voxel_normals.hip; dense_normals) every voxel also gets a surface normal: the mean
+of its pixels' normals (cross products of the pointmap's central differences, facing the camera that saw them) in
+stage 1, the weighted mean of the clouds' rotated normals in stage 2.  A cloud then carries `normals` f32 (V,3) and
+`normal_weights` i32 (V,); points, colors and weights are what they are without the option.
+
+The accumulators are integers, so a map is bitwise reproducible and tests/dense_map_ref.py reproduces it bit for bit
+(tests/dense_normals_ref.py the normals).
 Limitation: a cloud follows its chunk's similarity; per-view corrections of a bundle adjustment do not reach it.
 """
 from __future__ import annotations
@@ -295,18 +301,123 @@ class VoxelFuser:
         return sort_by_key(keys[:V].cpu().numpy(), pts[:V].cpu().numpy(), cols[:V].cpu().numpy(), w[:V].cpu().numpy())
 
 
+def sort_normals_by_key(keys: np.ndarray, normals: np.ndarray, nweights: np.ndarray) -> Dict[str, np.ndarray]:
+    """The normal rows in ascending key order: row for row the voxels of sort_by_key."""
+    order = np.argsort(keys.view(np.uint64))
+    return dict(keys=keys[order], normals=normals[order], normal_weights=nweights[order])
+
+
+def similarity_rotation(G) -> np.ndarray:
+    """The rotation of a 4x4 similarity: its 3x3 block divided by the cube root of its determinant (f64)."""
+    A = np.asarray(torch.as_tensor(G, dtype=torch.float64).reshape(4, 4).numpy()[:3, :3], np.float64)
+    det = float(np.linalg.det(A))
+    if not (math.isfinite(det) and det > 0.0):
+        raise ValueError(f"a chunk's transform is not a similarity (determinant {det!r} of its 3x3 block)")
+    return A / np.cbrt(det)
+
+
+class NormalAccumulator:
+    """The normal sums of one VoxelFuser's table (csrc/voxel_normals.hip): nacc int64 (capacity,4) = Nx, Ny, Nz, cnt
+    per slot, 32 B beside the table's 64.  clear() sizes it to the fuser's capacity and zeroes it; add_pixels /
+    add_points follow the fuser's fuse_pixels / fuse_points on the same inputs.  The sums are bound to the table's
+    slots: a table that was reallocated after the first add raises (callers reserve up front; nacc is not rehashed)."""
+
+    def __init__(self, fuser: VoxelFuser, out_sets: int = 1):
+        self.fuser = fuser
+        self.nacc: Optional[torch.Tensor] = None
+        # [0:4] the fusion kernels' counters (ops.VOXEL_NORMAL_COUNTERS), [4:8] the last extract's: rows, rows that did
+        # not fit, rows with a non-zero normal, spare
+        self.stats = torch.zeros(8, dtype=torch.int64, device=fuser.device)
+        self._bound_to: Optional[Tuple[int, int]] = None      # (table address, capacity) at the first add
+        self._outs = [None] * max(1, int(out_sets))
+        self._turn = 0
+
+    def clear(self) -> None:
+        if self.fuser.table is None:
+            self.fuser.reserve(0)
+        words = ops.VOXEL_NACC_WORDS * self.fuser.capacity
+        if self.nacc is None or self.nacc.numel() != words:
+            self.nacc = None                     # free the other size first
+            self.nacc = torch.zeros(words, dtype=torch.int64, device=self.fuser.device)
+        else:
+            self.nacc.zero_()
+        self.stats.zero_()
+        self._bound_to = None
+
+    def _table(self) -> torch.Tensor:
+        if self.nacc is None:
+            self.clear()
+        now = (int(self.fuser.table.data_ptr()), int(self.fuser.capacity))
+        if self._bound_to is None:
+            if self.nacc.numel() != ops.VOXEL_NACC_WORDS * now[1]:
+                raise RuntimeError("the voxel table changed size since NormalAccumulator.clear(): reserve the table "
+                                   "before the first normal is added")
+            self._bound_to = now
+        elif self._bound_to != now:
+            raise RuntimeError("the voxel table was reallocated after normals were added: reserve it up front")
+        return self.fuser.table
+
+    def add_pixels(self, points: torch.Tensor, conf: Optional[torch.Tensor], masks: Optional[torch.Tensor],
+                   conf_threshold: float) -> None:
+        """After fuser.fuse_pixels(points, conf, masks, ...) with the same tensors and threshold."""
+        ops.voxel_fuse_pixel_normals(self._table(), self.nacc, self.stats[:4], points, conf, masks,
+                                     conf_logit_threshold(conf_threshold), self.fuser.inv_voxel)
+
+    def add_points(self, points: torch.Tensor, normals: torch.Tensor, nweights: torch.Tensor, rot9: torch.Tensor) -> None:
+        """After fuser.fuse_points(points, ...): the same world-frame points, the cloud's normals in its own frame, its
+        normal weights and the rotation into the world frame (f64 (9,) on the device)."""
+        if points.numel() == 0:
+            return
+        ops.voxel_fuse_point_normals(self._table(), self.nacc, self.stats[:4], points, normals, nweights, rot9,
+                                     self.fuser.inv_voxel)
+
+    def extract_async(self, keep: Optional[torch.Tensor] = None):
+        """Queue the extraction; -> (keys, normals, nweights) device buffers of fuser.bound rows and a device copy of
+        the stats (stats[4] = the number of valid rows)."""
+        table = self._table()
+        i = self._turn
+        self._turn = (i + 1) % len(self._outs)
+        rows = max(self.fuser.bound, 1)
+        if self._outs[i] is None or self._outs[i][0].shape[0] < rows:
+            self._outs[i] = None
+            self._outs[i] = ops.voxel_empty_normal_outputs(rows, self.fuser.device)
+        ops.voxel_extract_normals(table, self.nacc, self.stats[4:], self.fuser.bound, out=self._outs[i], keep=keep)
+        return self._outs[i], self.stats.clone()
+
+    @staticmethod
+    def check_stats(st) -> Dict[str, int]:
+        """The eight counters as a dict; raises when a contribution found no slot or a row did not fit."""
+        c = [int(x) for x in st]
+        d = dict(zip(ops.VOXEL_NORMAL_COUNTERS, c[:4]), rows=c[4], unstored=c[5], nonzero=c[6])
+        if d["lost"] or d["unstored"]:
+            raise RuntimeError(f"dense normals: {d['lost']} contributions found no voxel, {d['unstored']} rows did not "
+                               "fit (the normals must follow the fusion of the same inputs)")
+        return d
+
+    def extract(self, keep: Optional[torch.Tensor] = None) -> Dict[str, np.ndarray]:
+        """Host arrays in ascending key order (row for row VoxelFuser.extract's): keys u64, normals f32 (V,3),
+        normal_weights i32 (V,); sets self.last_stats."""
+        (keys, nrm, nw), stats = self.extract_async(keep)
+        self.last_stats = self.check_stats(stats.cpu().numpy())
+        V = self.last_stats["rows"]
+        return sort_normals_by_key(keys[:V].cpu().numpy(), nrm[:V].cpu().numpy(), nw[:V].cpu().numpy())
+
+
 class ChunkCloudBuilder:
     """Stage 1 for the chunk creator: queue() fuses one chunk's maps into a voxel cloud on the current stream and starts
     its host copy, collect() turns that into chunk['dense_cloud'].  The table's and the filter's counters travel in the
     creator's packed copy (`out` / `got`), so a cloud costs the pipeline thread no synchronisation of its own."""
 
-    def __init__(self, voxel_size: float, conf_threshold: float, device, consistency: Optional[ConsistencyFilter] = None):
+    def __init__(self, voxel_size: float, conf_threshold: float, device, consistency: Optional[ConsistencyFilter] = None,
+                 normals: bool = False):
         self.conf_threshold = float(conf_threshold)
         self.filter = consistency
         self.device = torch.device(device)
         # two output sets: chunk k's is read on the host while chunk k+1's extraction is queued (the creator's finish(k)
         # always completes before launch(k+2))
         self.fuser = VoxelFuser(voxel_size, self.device, out_sets=2)
+        # surface normals (opt-in): sums beside the table, extracted into two buffer sets of their own
+        self.normals = NormalAccumulator(self.fuser, out_sets=2) if normals else None
         # the cloud's copy + key sort run on this thread as soon as the chunk's extraction is done, beside the host's
         # launch of the next chunk instead of in front of it
         self._pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="dense-cloud")
@@ -322,9 +433,12 @@ class ChunkCloudBuilder:
                                             cfg.dense_depth_tolerance)
             if cfg.dense_voxel_size is None:
                 print("⚠️  dense_min_views has no effect without dense_voxel_size: no dense cloud is built")
+        normals = bool(getattr(cfg, "dense_normals", False))
+        if normals and cfg.dense_voxel_size is None:
+            print("⚠️  dense_normals has no effect without dense_voxel_size: no dense cloud is built")
         if cfg.dense_voxel_size is None:
             return None
-        return cls(cfg.dense_voxel_size, cfg.dense_conf_threshold, device, consistency)
+        return cls(cfg.dense_voxel_size, cfg.dense_conf_threshold, device, consistency, normals)
 
     def queue(self, points: torch.Tensor, local_points: torch.Tensor, conf: torch.Tensor, masks: torch.Tensor,
               imgs: torch.Tensor, poses: torch.Tensor, fxfycxcy: Optional[torch.Tensor],
@@ -344,22 +458,34 @@ class ChunkCloudBuilder:
                 print("⚠️  dense consistency filter: no intrinsics (estimate_camera_params is off or the estimate "
                       "failed); dense clouds without them are fused unfiltered")
         self.fuser.fuse_pixels(points, conf, masks, imgs.contiguous(), self.conf_threshold)
+        if self.normals is not None:        # the table has its final size now: the sums are laid out beside its slots
+            self.normals.clear()
+            self.normals.add_pixels(points, conf, masks, self.conf_threshold)
         bufs, out["_dense_stats"] = self.fuser.extract_async()
+        nbufs = ()
+        if self.normals is not None:
+            nbufs, out["_dense_normal_stats"] = self.normals.extract_async()
         extracted = torch.cuda.Event()
         extracted.record(torch.cuda.current_stream(self.device))
-        return self._pool.submit(self._host_rows, bufs, out["_dense_stats"], extracted)
+        return self._pool.submit(self._host_rows, bufs, out["_dense_stats"], extracted, nbufs)
 
-    def _host_rows(self, bufs: tuple, stats_dev: torch.Tensor, extracted: torch.cuda.Event) -> Dict[str, np.ndarray]:
+    def _host_rows(self, bufs: tuple, stats_dev: torch.Tensor, extracted: torch.cuda.Event,
+                   nbufs: tuple = ()) -> Dict[str, np.ndarray]:
         """(dense-cloud thread) Wait for the extraction, copy the first V rows into pinned memory on a stream of its own
-        (a copy into pageable memory would wait for the next chunk's forward) and sort them by key."""
+        (a copy into pageable memory would wait for the next chunk's forward) and sort them by key.  nbufs: the normal
+        rows (NormalAccumulator.extract_async), one per voxel as well; they are sorted by their own keys."""
         with torch.cuda.device(self.device), torch.cuda.stream(self._stream):
             extracted.synchronize()
             V = int(stats_dev[2].item())
-            h = [torch.empty((V,) + tuple(t.shape[1:]), dtype=t.dtype, pin_memory=True) for t in bufs]
-            for dst, src in zip(h, bufs):
+            h = [torch.empty((V,) + tuple(t.shape[1:]), dtype=t.dtype, pin_memory=True) for t in tuple(bufs) + tuple(nbufs)]
+            for dst, src in zip(h, tuple(bufs) + tuple(nbufs)):
                 dst.copy_(src[:V], non_blocking=True)
             self._stream.synchronize()
-        return sort_by_key(*(t.numpy() for t in h))
+        rows = sort_by_key(*(t.numpy() for t in h[:4]))
+        if nbufs:
+            nrm = sort_normals_by_key(*(t.numpy() for t in h[4:]))
+            rows["normal_keys"], rows["normals"], rows["normal_weights"] = nrm["keys"], nrm["normals"], nrm["normal_weights"]
+        return rows
 
     def collect(self, job: Future, got: Dict[str, torch.Tensor], metrics: Dict) -> Dict:
         """The chunk's voxel cloud from queue()'s job and the host copies of what queue() put into `out`:
@@ -377,6 +503,13 @@ class ChunkCloudBuilder:
         if "_dense_filter_stats" in got:
             metrics["dense_candidates"], metrics["dense_consistent"] = (int(x) for x in got["_dense_filter_stats"].tolist())
             cloud["consistency"] = self.filter.settings()
+        if "_dense_normal_stats" in got:
+            st = NormalAccumulator.check_stats(got["_dense_normal_stats"].tolist())
+            if st["rows"] != V or not np.array_equal(s["normal_keys"], s["keys"]):
+                raise RuntimeError(f"dense normals: {st['rows']} rows for {V} voxels, or other keys than the cloud's")
+            metrics["dense_normal_pixels"], metrics["dense_normal_voxels"] = st["contributions"], st["nonzero"]
+            cloud["normals"] = torch.from_numpy(s["normals"])
+            cloud["normal_weights"] = torch.from_numpy(s["normal_weights"])
         return cloud
 
 
@@ -390,15 +523,26 @@ def chunk_transform(chunk: Dict) -> torch.Tensor:
     return torch.eye(4, dtype=torch.float64) if G is None else torch.as_tensor(G, dtype=torch.float64).reshape(4, 4)
 
 
-def fuse_chunk_clouds(chunks: Iterable[Dict], voxel_size: float, device="cuda",
-                      cleaner: Optional[MapCleaner] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+def fuse_chunk_clouds_with_normals(chunks: Iterable[Dict], voxel_size: float, device="cuda",
+                                   cleaner: Optional[MapCleaner] = None
+                                   ) -> Tuple[np.ndarray, np.ndarray, np.ndarray, Optional[np.ndarray]]:
     """Every chunk's dense_cloud moved by chunk_transform() and fused, weighted by its voxel weights ->
-    (points f32 (V,3), colors u8 (V,3), weights i32 (V,)) in ascending key order.  Chunks without a cloud are skipped.
-    cleaner: its filters decide on the fused table which voxels are extracted (one line with the counts is printed)."""
+    (points f32 (V,3), colors u8 (V,3), weights i32 (V,), normals f32 (V,3) or None) in ascending key order.  Chunks
+    without a cloud are skipped.  cleaner: its filters decide on the fused table which voxels are extracted (one line
+    with the counts is printed).  Normals: when every cloud carries `normals`, each cloud's are rotated by its
+    similarity's rotation and fused weighted by its `normal_weights`; when only some do, one line says so and the map
+    has none."""
     device = torch.device(device)
     clouds = [(c["dense_cloud"], chunk_transform(c)) for c in chunks if c.get("dense_cloud") is not None]
     fuser = VoxelFuser(voxel_size, device)
     fuser.reserve(sum(int(cl["points"].shape[0]) for cl, _ in clouds))
+    with_normals = sum(1 for cl, _ in clouds if cl.get("normals") is not None)
+    acc = None
+    if with_normals and with_normals == len(clouds):
+        acc = NormalAccumulator(fuser)
+        acc.clear()
+    elif with_normals:
+        print(f"   ℹ️  Only {with_normals} of {len(clouds)} dense clouds carry normals: the dense map has none")
     for cl, G in clouds:
         if int(cl["points"].shape[0]) == 0:
             continue
@@ -407,12 +551,29 @@ def fuse_chunk_clouds(chunks: Iterable[Dict], voxel_size: float, device="cuda",
         cols = upload(torch.as_tensor(cl["colors"]).reshape(-1, 3), device).contiguous()
         w = upload(torch.as_tensor(cl["weights"]).reshape(-1), device).contiguous()
         fuser.fuse_points(pts, cols, w)
+        if acc is not None:
+            nrm = upload(torch.as_tensor(cl["normals"]).reshape(-1, 3), device).to(torch.float32).contiguous()
+            nw = upload(torch.as_tensor(cl["normal_weights"]).reshape(-1), device).to(torch.int32).contiguous()
+            rot = upload(torch.from_numpy(similarity_rotation(G).reshape(9).copy()), device).contiguous()
+            acc.add_points(pts, nrm, nw, rot)
     keep = None
     if cleaner is not None:
         keep = cleaner.apply(fuser)
         print(f"   🧹 Dense map cleaned: {cleaner.summary()}")
     out = fuser.extract(keep)
-    return out["points"], out["colors"], out["weights"]
+    normals = None
+    if acc is not None:
+        nout = acc.extract(keep)
+        if not np.array_equal(nout["keys"], out["keys"]):
+            raise RuntimeError("dense normals: the normal rows have other keys than the map's")
+        normals = nout["normals"]
+    return out["points"], out["colors"], out["weights"], normals
+
+
+def fuse_chunk_clouds(chunks: Iterable[Dict], voxel_size: float, device="cuda",
+                      cleaner: Optional[MapCleaner] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """fuse_chunk_clouds_with_normals without the normals: (points f32 (V,3), colors u8 (V,3), weights i32 (V,))."""
+    return fuse_chunk_clouds_with_normals(chunks, voxel_size, device, cleaner)[:3]
 
 
 def write_dense_ply(points: np.ndarray, colors: np.ndarray, path: str) -> None:

@@ -5,8 +5,9 @@ Pi3SLAMOnline.chunk_reconstructions).  Files and formats mirror slam/offline_rec
   final_camera_poses.ply  every view's camera centre, overlap views twice (all_views)
   trajectory_tum.txt      the de-duplicated trajectory: first occurrence of a view name wins (unique_views)
   dense_points.ply        the chunks' dense clouds fused in the world frame (fuse_dense_map; dense_map.py), cleaned by a
-                          dense_map.MapCleaner when one is given
-  renders/                depth / colour images of that map, overview.png, cameras.json (write_renders; render.py)
+                          dense_map.MapCleaner when one is given; with nx ny nz when the clouds carry normals
+  renders/                depth / colour images of that map, overview.png, cameras.json (write_renders; render.py); with
+                          normals also normal_<frame>.png, shaded_<frame>.png and overview_shaded.png
 
 write_outputs writes them all, in that order.  A chunk needs dist.COLLECT_KEYS for it, nothing else."""
 from __future__ import annotations
@@ -44,6 +45,29 @@ def write_ply(points: np.ndarray, colors: np.ndarray, path: str) -> None:
                  "property uchar blue\nend_header\n").encode())
         rec = np.empty(len(points), dtype=[("xyz", "<f4", 3), ("rgb", "u1", 3)])
         rec["xyz"], rec["rgb"] = points, rgb
+        f.write(rec.tobytes())
+
+
+def write_ply_normals(points: np.ndarray, normals: np.ndarray, colors: np.ndarray, path: str) -> None:
+    """Binary little-endian PLY with float xyz, float nx ny nz and uchar rgb per vertex (the property names MeshLab,
+    CloudCompare and Open3D read as normals).  Colours as in write_ply."""
+    points = np.asarray(points, np.float32).reshape(-1, 3)
+    normals = np.asarray(normals, np.float32).reshape(-1, 3)
+    if len(normals) != len(points):
+        raise ValueError(f"{len(normals)} normals for {len(points)} points")
+    if np.asarray(colors).dtype == np.uint8:
+        rgb = np.asarray(colors).reshape(-1, 3)
+    else:
+        colors = np.asarray(colors, np.float32).reshape(-1, 3)
+        if colors.size and colors.max() <= 1.0:
+            colors = colors * 255.0
+        rgb = np.clip(colors, 0, 255).astype(np.uint8)
+    with open(path, "wb") as f:
+        f.write((f"ply\nformat binary_little_endian 1.0\nelement vertex {len(points)}\nproperty float x\n"
+                 "property float y\nproperty float z\nproperty float nx\nproperty float ny\nproperty float nz\n"
+                 "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n").encode())
+        rec = np.empty(len(points), dtype=[("xyz", "<f4", 3), ("n", "<f4", 3), ("rgb", "u1", 3)])
+        rec["xyz"], rec["n"], rec["rgb"] = points, normals, rgb
         f.write(rec.tobytes())
 
 
@@ -133,38 +157,52 @@ class DenseMap(NamedTuple):
     voxel_size: float
 
 
-def fuse_dense_map(chunks: Sequence[Dict], device, cleaner=None) -> Optional[DenseMap]:
-    """The chunks' dense clouds (chunks created with a dense voxel size) fused in the world frame; None when no chunk
-    carries one.  The voxel size is the first cloud's: the world frame is chunk 0's frame.  cleaner: a
-    dense_map.MapCleaner whose filters choose the voxels of the map (None: all of them)."""
+def fuse_dense_map_normals(chunks: Sequence[Dict], device, cleaner=None) -> Tuple[Optional[DenseMap], Optional[np.ndarray]]:
+    """The chunks' dense clouds (chunks created with a dense voxel size) fused in the world frame -> (the map, its
+    normals f32 (V,3) row for row, or None when the clouds carry none); (None, None) when no chunk carries a cloud.
+    The voxel size is the first cloud's: the world frame is chunk 0's frame.  cleaner: a dense_map.MapCleaner whose
+    filters choose the voxels of the map (None: all of them)."""
     first = next((d["dense_cloud"] for d in chunks if d.get("dense_cloud") is not None), None)
     if first is None:
-        return None
-    from .dense_map import fuse_chunk_clouds
+        return None, None
+    from .dense_map import fuse_chunk_clouds_with_normals
     voxel = float(first["voxel_size"])
-    return DenseMap(*fuse_chunk_clouds(chunks, voxel, device, cleaner), voxel)
+    pts, cols, w, normals = fuse_chunk_clouds_with_normals(chunks, voxel, device, cleaner)
+    return DenseMap(pts, cols, w, voxel), normals
 
 
-def write_dense_points(dense: DenseMap, path: str) -> int:
-    """dense_points.ply; returns the voxel count."""
-    write_ply(dense.points, np.asarray(dense.colors, np.uint8), path)
-    print(f"✅ Saved dense map with {len(dense.points)} voxels ({dense.voxel_size} m) to: {path}")
+def fuse_dense_map(chunks: Sequence[Dict], device, cleaner=None) -> Optional[DenseMap]:
+    """fuse_dense_map_normals without the normals: the map, or None when no chunk carries a dense cloud."""
+    return fuse_dense_map_normals(chunks, device, cleaner)[0]
+
+
+def write_dense_points(dense: DenseMap, path: str, normals: Optional[np.ndarray] = None) -> int:
+    """dense_points.ply, with nx ny nz when the map has normals; returns the voxel count."""
+    if normals is None:
+        write_ply(dense.points, np.asarray(dense.colors, np.uint8), path)
+        print(f"✅ Saved dense map with {len(dense.points)} voxels ({dense.voxel_size} m) to: {path}")
+    else:
+        write_ply_normals(dense.points, normals, np.asarray(dense.colors, np.uint8), path)
+        print(f"✅ Saved dense map with {len(dense.points)} voxels ({dense.voxel_size} m) and normals to: {path}")
     return len(dense.points)
 
 
 def write_renders(chunks: Sequence[Dict], dense: Optional[DenseMap], out_dir: str, every: Optional[int], overview: bool,
                   min_weight: int = 1, splat_scale: float = 1.0, device="cuda",
-                  dense_cleaner=None) -> Optional[Tuple[int, Dict[str, float]]]:
+                  dense_cleaner=None, normals: Optional[np.ndarray] = None) -> Optional[Tuple[int, Dict[str, float]]]:
     """<out_dir>/depth_<frame>.png (16 bit, millimetres, 0 = empty) and color_<frame>.png of the dense map for every
     `every`-th view of the de-duplicated trajectory, overview.png (a top-down orthographic view with the trajectory
     in red) and cameras.json -> (rendered views, {'total', 'png'} seconds).  `dense`: the map a caller has already fused
-    (else it is fused here, through `dense_cleaner`).  Without dense clouds in the chunks: one line, no directory, None."""
+    (else it is fused here, through `dense_cleaner`).  Without dense clouds in the chunks: one line, no directory, None.
+    normals: that map's normals; then every view also gets normal_<frame>.png (the camera-frame normal as RGB) and
+    shaded_<frame>.png (headlight shading, greyscale), and the overview overview_shaded.png."""
     if dense is None:
-        dense = fuse_dense_map(chunks, device, dense_cleaner)
+        dense, normals = fuse_dense_map_normals(chunks, device, dense_cleaner)
     if dense is None:
         print("   ℹ️  No dense clouds in the chunks (create them with a dense voxel size): no renders")
         return None
-    from .render import DEPTH_PNG_SCALE, MapRenderer, pack_cameras, render_overview, write_color_png, write_depth_png
+    from .render import (DEPTH_PNG_SCALE, MapRenderer, pack_cameras, render_overview, write_color_png, write_depth_png,
+                         write_grey_png)
     pts, cols, w, voxel = dense
     views = render_views(chunks)
     chosen = [v for v in views[:: int(every)] if v["K"] is not None] if every else []
@@ -174,7 +212,7 @@ def write_renders(chunks: Sequence[Dict], dense: Optional[DenseMap], out_dir: st
     t0, t_png = time.time(), 0.0
     record = {"depth_scale": DEPTH_PNG_SCALE, "voxel_size": voxel, "min_weight": int(min_weight),
               "splat_scale": float(splat_scale), "near": 0.05, "views": [], "overview": None}
-    renderer = MapRenderer(pts, cols, w, voxel, device) if chosen else None
+    renderer = MapRenderer(pts, cols, w, voxel, device, normals=normals) if chosen else None
     for size in sorted({(v["H"], v["W"]) for v in chosen}):
         group = [v for v in chosen if (v["H"], v["W"]) == size]
         cams = pack_cameras(np.stack([v["pose"] for v in group]), np.stack([v["K"] for v in group]))
@@ -185,27 +223,38 @@ def write_renders(chunks: Sequence[Dict], dense: Optional[DenseMap], out_dir: st
             t1 = time.time()
             write_depth_png(out["depth"][j], os.path.join(out_dir, v["depth"]))
             write_color_png(out["color"][j], os.path.join(out_dir, v["color"]))
+            if normals is not None:
+                v["normal"], v["shaded"] = f"normal_{stem}.png", f"shaded_{stem}.png"
+                write_color_png(out["normal"][j], os.path.join(out_dir, v["normal"]))
+                write_grey_png(out["shaded"][j], os.path.join(out_dir, v["shaded"]))
             t_png += time.time() - t1
     for v in chosen:
         K = v["K"]
         record["views"].append({"frame": v["name"], "pose": [[float(x) for x in row] for row in v["pose"]],
                                 "fx": float(K[0, 0]), "fy": float(K[1, 1]), "cx": float(K[0, 2]), "cy": float(K[1, 2]),
                                 "H": v["H"], "W": v["W"], "depth": v["depth"], "color": v["color"]})
+        if normals is not None:
+            record["views"][-1].update(normal=v["normal"], shaded=v["shaded"])
     if overview and views:
         sized = next((v for v in views if v["K"] is not None), None)
         H, W = (sized["H"], sized["W"]) if sized else (480, 640)
         ov = render_overview(pts, cols, w, voxel, np.stack([v["pose"] for v in views]), H, W, min_weight=min_weight,
-                             splat_scale=splat_scale, device=device)
+                             splat_scale=splat_scale, device=device, normals=normals)
         t1 = time.time()
         write_color_png(ov["color"], os.path.join(out_dir, "overview.png"))
+        if normals is not None:
+            write_color_png(ov["shaded"], os.path.join(out_dir, "overview_shaded.png"))
         t_png += time.time() - t1
         record["overview"] = {"color": "overview.png", "ortho": True, "near": ov["near"], "H": H, "W": W,
                               "pose": [[float(x) for x in row] for row in ov["pose"]],
                               "fx": float(ov["K"][0, 0]), "fy": float(ov["K"][1, 1]), "cx": float(ov["K"][0, 2]),
                               "cy": float(ov["K"][1, 2])}
+        if normals is not None:
+            record["overview"]["shaded"] = "overview_shaded.png"
     with open(os.path.join(out_dir, "cameras.json"), "w") as f:
         json.dump(record, f, indent=1)
-    print(f"✅ Saved {len(chosen)} depth / colour renders" + (" and the overview" if record["overview"] else "")
+    print(f"✅ Saved {len(chosen)} depth / colour" + (" / normal / shaded" if normals is not None else "") + " renders"
+          + (" and the overview" if record["overview"] else "")
           + f" of the dense map to: {out_dir} ({time.time() - t0:.2f}s, {t_png:.2f}s of it PNG encoding)")
     return len(chosen), {"total": time.time() - t0, "png": t_png}
 
@@ -233,17 +282,17 @@ def write_outputs(chunks: Sequence[Dict], output_dir: str, device="cuda", render
         save_trajectory_tum(chunks, os.path.join(output_dir, "trajectory_tum.txt"), integer_timestamp=True)
     except Exception as e:  # noqa: BLE001
         print(f"❌ Failed to save TUM trajectory: {e}")
-    dense = None
+    dense = normals = None
     try:
-        dense = fuse_dense_map(chunks, device, dense_cleaner)
+        dense, normals = fuse_dense_map_normals(chunks, device, dense_cleaner)
         if dense is not None:
-            write_dense_points(dense, os.path.join(output_dir, "dense_points.ply"))
+            write_dense_points(dense, os.path.join(output_dir, "dense_points.ply"), normals)
     except Exception as e:  # noqa: BLE001
         print(f"❌ Failed to save the dense map: {e}")
     if render_every is not None or render_overview:
         try:       # the renders draw the map that was just fused for the PLY
             done = write_renders(chunks, dense, os.path.join(output_dir, "renders"), render_every, render_overview,
-                                 render_min_weight, render_splat_scale, device, dense_cleaner)
+                                 render_min_weight, render_splat_scale, device, dense_cleaner, normals)
             return done[1] if done else None
         except Exception as e:  # noqa: BLE001
             print(f"❌ Failed to save the renders of the dense map: {e}")

@@ -77,6 +77,10 @@ SIGNATURES = {
     "pi3_dense_consistency": [_vp] * 6 + [_i, _i, _i, _f, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp],
     "pi3_render_splat": [_vp, _vp, _l, _vp, _i, _i, _i, _d, _d, _i, _d, _d, _vp, _vp, _vp],
     "pi3_render_resolve": [_vp, _vp, _l, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
+    "pi3_voxel_fuse_pixel_normals": [_vp, _l, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp],
+    "pi3_voxel_fuse_point_normals": [_vp, _l, _vp, _vp, _vp, _vp, _vp, _l, _f, _vp, _vp],
+    "pi3_voxel_extract_normals": [_vp, _l, _vp, _vp, _vp, _vp, _vp, _l, _vp, _vp],
+    "pi3_render_shade": [_vp, _vp, _l, _vp, _i, _i, _i, _vp, _vp, _vp, _vp],
     "pi3_set_knob": [C.c_char_p, _l],
     "pi3_get_knob": [C.c_char_p, C.POINTER(_l)],
     "pi3_unset_knob": [C.c_char_p],

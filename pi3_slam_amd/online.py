@@ -67,7 +67,7 @@ class Pi3SLAMOnline:
                  dense_voxel_size: Optional[float] = None, dense_min_views: Optional[int] = None,
                  dense_view_radius: int = 3, dense_view_stride: int = 2, dense_depth_tolerance: float = 0.03,
                  dense_min_weight: Optional[int] = None, dense_min_support: Optional[int] = None,
-                 dense_support_radius: int = 1, dense_min_component: Optional[int] = None):
+                 dense_support_radius: int = 1, dense_min_component: Optional[int] = None, dense_normals: bool = False):
         from .dense_map import MapCleaner
         # filters on the fused dense map of save_dense_map / save_renders (all off by default: no cleaner)
         self.dense_cleaner = MapCleaner.from_options(dense_min_weight, dense_min_support, dense_support_radius,
@@ -85,7 +85,7 @@ class Pi3SLAMOnline:
             reuse_overlap_encoder=reuse_overlap_encoder, dense_voxel_size=dense_voxel_size,
             dense_conf_threshold=conf_threshold,     # --conf_threshold filters the dense map's pixels
             dense_min_views=dense_min_views, dense_view_radius=dense_view_radius, dense_view_stride=dense_view_stride,
-            dense_depth_tolerance=dense_depth_tolerance)
+            dense_depth_tolerance=dense_depth_tolerance, dense_normals=dense_normals)
         self._creator = OfflineChunkCreator(cfg, model=model, moge_model=moge_model)
         self._creator.undistortion_maps = undistortion_maps
         self.rank, self.world = self._creator.rank, self._creator.world
@@ -294,20 +294,23 @@ class Pi3SLAMOnline:
             pts, cols = pts[sel], (cols[sel] if cols.size else cols)
         export.write_ply(pts, cols if cols.size else np.ones_like(pts), save_path)
 
-    def _fused_map(self) -> export.DenseMap:
-        dense = export.fuse_dense_map(self.chunk_reconstructions, str(self.device), self.dense_cleaner)
+    def _fused_map(self):
+        """-> (the fused dense map, its normals or None: dense_normals)."""
+        dense, normals = export.fuse_dense_map_normals(self.chunk_reconstructions, str(self.device), self.dense_cleaner)
         if dense is None:
             raise RuntimeError("no dense clouds: construct Pi3SLAMOnline with dense_voxel_size")
-        return dense
+        return dense, normals
 
     def save_dense_map(self, save_path: str) -> int:
         """The chunks' dense clouds (dense_voxel_size set) fused in the world frame, cleaned by the dense_min_* options
-        when one is set -> a PLY; returns the voxel count."""
-        return export.write_dense_points(self._fused_map(), save_path)
+        when one is set -> a PLY (with normals under dense_normals); returns the voxel count."""
+        dense, normals = self._fused_map()
+        return export.write_dense_points(dense, save_path, normals)
 
     def save_renders(self, out_dir: str, every: Optional[int] = 10, overview: bool = True, min_weight: int = 1,
                      splat_scale: float = 1.0) -> int:
         """Depth / colour images of the dense map from every `every`-th view, overview.png and cameras.json under
         `out_dir` (export.write_renders); returns the number of rendered views."""
-        return export.write_renders(self.chunk_reconstructions, self._fused_map(), out_dir, every, overview,
-                                    min_weight, splat_scale, str(self.device))[0]
+        dense, normals = self._fused_map()
+        return export.write_renders(self.chunk_reconstructions, dense, out_dir, every, overview, min_weight, splat_scale,
+                                    str(self.device), normals=normals)[0]

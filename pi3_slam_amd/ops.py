@@ -839,6 +839,108 @@ def render_resolve(zbuf: torch.Tensor, colors: torch.Tensor, stats: torch.Tensor
     return depth, color, index
 
 
+# ------------------------------------------------------------------------------- normals of the voxel map, shading
+VOXEL_NACC_WORDS = 4        # Nx, Ny, Nz, cnt as int64 per slot, parallel to the table (csrc/voxel_normals.hip)
+VOXEL_NORMAL_COUNTERS = ("contributions", "skipped", "degenerate", "lost")
+
+
+def _nacc_check(table: torch.Tensor, nacc: torch.Tensor, stats: torch.Tensor) -> None:
+    assert table.dtype == torch.int64 and table.is_contiguous() and table.numel() % 8 == 0
+    assert nacc.dtype == torch.int64 and nacc.is_contiguous() and nacc.device == table.device
+    assert nacc.numel() == VOXEL_NACC_WORDS * (table.numel() // 8), "nacc must have 4 int64 per slot of the table"
+    assert stats.dtype == torch.int64 and stats.is_contiguous() and stats.numel() >= 4 and stats.device == table.device
+
+
+def voxel_fuse_pixel_normals(table: torch.Tensor, nacc: torch.Tensor, stats: torch.Tensor, points: torch.Tensor,
+                             conf: Optional[torch.Tensor], masks: Optional[torch.Tensor], conf_logit_thr: float,
+                             inv_voxel: float) -> None:
+    """After voxel_fuse_pixels on the same points f32 (N,H,W,3), conf, masks: the pixels' normals into nacc int64
+    (capacity,4); stats int64 (4,) accumulates VOXEL_NORMAL_COUNTERS."""
+    lib = _L.load()
+    _nacc_check(table, nacc, stats)
+    N, H, W = points.shape[:3]
+    assert points.dtype == torch.float32 and points.is_contiguous() and points.ndim == 4 and points.shape[3] == 3
+    if conf is not None:
+        assert conf.dtype == torch.float32 and conf.is_contiguous() and conf.numel() == N * H * W
+    if masks is not None:
+        assert masks.dtype in (torch.uint8, torch.bool) and masks.is_contiguous() and masks.numel() == N * H * W
+    rc = lib.pi3_voxel_fuse_pixel_normals(table.data_ptr(), table.numel() // 8, nacc.data_ptr(), points.data_ptr(),
+                                          _L.ptr(conf), _L.ptr(masks), N, H, W, float(conf_logit_thr), float(inv_voxel),
+                                          stats.data_ptr(), _L.stream_ptr())
+    _L.check(rc, "pi3_voxel_fuse_pixel_normals")
+
+
+def voxel_fuse_point_normals(table: torch.Tensor, nacc: torch.Tensor, stats: torch.Tensor, points: torch.Tensor,
+                             normals: torch.Tensor, nweights: torch.Tensor, rot9: torch.Tensor, inv_voxel: float) -> None:
+    """After voxel_fuse_points on the same (world-frame) points f32 (n,3): normals f32 (n,3) in the cloud's frame,
+    nweights int32 (n,), rot9 f64 (9,) on the device, the rotation into the world frame."""
+    lib = _L.load()
+    _nacc_check(table, nacc, stats)
+    assert points.dtype == torch.float32 and points.is_contiguous() and points.shape[-1] == 3
+    n = points.numel() // 3
+    assert normals.dtype == torch.float32 and normals.is_contiguous() and normals.numel() == 3 * n
+    assert nweights.dtype == torch.int32 and nweights.is_contiguous() and nweights.numel() == n
+    assert rot9.dtype == torch.float64 and rot9.is_contiguous() and rot9.numel() == 9
+    assert normals.device == table.device and nweights.device == table.device and rot9.device == table.device
+    if n == 0:          # empty tensors have no address to pass
+        return
+    rc = lib.pi3_voxel_fuse_point_normals(table.data_ptr(), table.numel() // 8, nacc.data_ptr(), points.data_ptr(),
+                                          normals.data_ptr(), nweights.data_ptr(), rot9.data_ptr(), n, float(inv_voxel),
+                                          stats.data_ptr(), _L.stream_ptr())
+    _L.check(rc, "pi3_voxel_fuse_point_normals")
+
+
+def voxel_empty_normal_outputs(rows: int, device):
+    """Output buffers of voxel_extract_normals: keys int64 (rows,), normals f32 (rows,3), nweights int32 (rows,)."""
+    m = max(int(rows), 1)
+    return (torch.empty(m, device=device, dtype=torch.int64), torch.empty(m, 3, device=device, dtype=torch.float32),
+            torch.empty(m, device=device, dtype=torch.int32))
+
+
+def voxel_extract_normals(table: torch.Tensor, nacc: torch.Tensor, stats: torch.Tensor, max_out: int, out=None,
+                          keep: Optional[torch.Tensor] = None):
+    """-> device (keys int64, normals f32 (,3), nweights int32) with >= max_out rows (`out`, or fresh buffers),
+    unordered.  stats int64 (4,), zeroed by the call: rows, rows that did not fit, rows with a non-zero normal, spare.
+    keep uint8 (capacity,): only the slots it marks."""
+    lib = _L.load()
+    _nacc_check(table, nacc, stats)
+    keys, nrm, nw = out if out is not None else voxel_empty_normal_outputs(max_out, table.device)
+    assert keys.dtype == torch.int64 and nrm.dtype == torch.float32 and nw.dtype == torch.int32
+    assert keys.is_contiguous() and nrm.is_contiguous() and nw.is_contiguous()
+    assert keys.shape[0] >= max_out and nrm.numel() >= 3 * max_out and nw.shape[0] >= max_out
+    if keep is not None:
+        _slot_array(keep, table, torch.uint8)
+    rc = lib.pi3_voxel_extract_normals(table.data_ptr(), table.numel() // 8, nacc.data_ptr(), _L.ptr(keep),
+                                       keys.data_ptr(), nrm.data_ptr(), nw.data_ptr(), int(max_out), stats.data_ptr(),
+                                       _L.stream_ptr())
+    _L.check(rc, "pi3_voxel_extract_normals")
+    return keys, nrm, nw
+
+
+def render_shade(index: torch.Tensor, normals: torch.Tensor, cams: torch.Tensor, stats: torch.Tensor, out=None):
+    """index int32 (M,H,W) of render_resolve, normals f32 (V,3) of the map, cams f64 (M,20) -> (normal_rgb uint8
+    (M,H,W,3), shaded uint8 (M,H,W)), `out` or fresh buffers; stats int64 (>= 1) accumulates the shaded pixels in [0]."""
+    lib = _L.load()
+    assert index.dtype == torch.int32 and index.is_contiguous() and index.ndim == 3
+    M, H, W = (int(x) for x in index.shape)
+    assert normals.dtype == torch.float32 and normals.is_contiguous() and normals.ndim == 2 and normals.shape[1] == 3
+    assert cams.dtype == torch.float64 and cams.is_contiguous() and tuple(cams.shape) == (M, RENDER_CAM_DOUBLES)
+    assert stats.dtype == torch.int64 and stats.is_contiguous() and stats.numel() >= 1
+    assert normals.device == index.device and cams.device == index.device and stats.device == index.device
+    if out is None:
+        out = (torch.empty(M, H, W, 3, device=index.device, dtype=torch.uint8),
+               torch.empty(M, H, W, device=index.device, dtype=torch.uint8))
+    rgb, shaded = out
+    assert rgb.dtype == torch.uint8 and rgb.is_contiguous() and rgb.numel() == 3 * M * H * W
+    assert shaded.dtype == torch.uint8 and shaded.is_contiguous() and shaded.numel() == M * H * W
+    assert rgb.device == index.device and shaded.device == index.device
+    rc = lib.pi3_render_shade(index.data_ptr(), normals.data_ptr() if normals.numel() else None, int(normals.shape[0]),
+                              cams.data_ptr(), M, H, W, rgb.data_ptr(), shaded.data_ptr(), stats.data_ptr(),
+                              _L.stream_ptr())
+    _L.check(rc, "pi3_render_shade")
+    return rgb, shaded
+
+
 # ---------------------------------------------------------------------------------------------------- device guard
 # Every wrapper launches on torch's CURRENT stream, i.e. on the current device.  A tensor that lives on another card
 # (e.g. 'cuda:0' data in a rank bound to cuda:3) would hand that card's pointers to a kernel running elsewhere: fail

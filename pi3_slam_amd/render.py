@@ -6,7 +6,8 @@ each pixel keeps the nearest voxel (64-bit atomicMin of depth bits | row).  The 
 which the atomics land; tests/render_ref.py reproduces it bit for bit.
 
   pack_cameras      cam->world poses + intrinsics (index coordinates: pixel i has its centre at i) -> f64 (M,20)
-  MapRenderer       uploads a map once, renders batches of cameras -> depth f32 / color u8 / index i32
+  MapRenderer       uploads a map once, renders batches of cameras -> depth f32 / color u8 / index i32; with the map's
+                    normals also normal u8 (camera-frame normal as RGB) / shaded u8 (csrc/voxel_normals.hip)
   overview_camera   an orthographic camera looking along the trajectory's mean image-down axis, framed on the map
   render_overview   the map + the camera centres as red voxels through that camera
   write_depth_png   16-bit PNG in millimetres (0 = empty), write_color_png
@@ -66,7 +67,7 @@ def default_batch(M: int, H: int, W: int) -> int:
 class MapRenderer:
     """A voxel map on the device (uploaded once) and a z-buffer that is re-used between batches of cameras."""
 
-    def __init__(self, points, colors, weights, voxel_size: float, device="cuda"):
+    def __init__(self, points, colors, weights, voxel_size: float, device="cuda", normals=None):
         v = float(voxel_size)
         if not (v > 0.0 and math.isfinite(v)):
             raise ValueError(f"voxel size must be a positive finite length, got {voxel_size!r}")
@@ -82,6 +83,12 @@ class MapRenderer:
                         else torch.as_tensor(weights).reshape(-1).to(self.device, torch.int32).contiguous())
         if int(self.colors.shape[0]) != V or (self.weights is not None and int(self.weights.shape[0]) != V):
             raise ValueError("points, colors and weights must have one row per voxel")
+        # world-frame unit normals f32 (V,3), (0,0,0) = none: render() then also shades (pi3_render_shade)
+        self.normals = (None if normals is None
+                        else torch.as_tensor(normals).reshape(-1, 3).to(self.device, torch.float32).contiguous())
+        if self.normals is not None and int(self.normals.shape[0]) != V:
+            raise ValueError("normals must have one row per voxel")
+        self.shade_stats = torch.zeros(1, dtype=torch.int64, device=self.device)
         self.stats = torch.zeros(4, dtype=torch.int64, device=self.device)
         self._zbuf: Optional[torch.Tensor] = None
         self.last_stats: Dict[str, int] = {}
@@ -89,7 +96,9 @@ class MapRenderer:
     def render(self, cams, H: int, W: int, min_weight: int = 1, splat_scale: float = 1.0, near: float = 0.05,
                far: float = float("inf"), batch: Optional[int] = None, to_host: bool = True) -> Dict[str, torch.Tensor]:
         """cams f64 (M,20) (pack_cameras) -> {'depth' f32 (M,H,W), 0 = empty; 'color' u8 (M,H,W,3); 'index' i32
-        (M,H,W), the voxel's row or -1}, on the host (to_host) or on the device.  Sets last_stats."""
+        (M,H,W), the voxel's row or -1}, on the host (to_host) or on the device.  Sets last_stats.  A renderer with
+        normals adds 'normal' u8 (M,H,W,3) = the camera-frame normal, (n + 1) * 127.5, and 'shaded' u8 (M,H,W) =
+        255 max(0, -n_z), a headlight along the optical axis; both 0 where empty, and last_stats['shaded'] pixels."""
         cams = torch.as_tensor(cams, dtype=torch.float64).reshape(-1, CAM_DOUBLES)
         M, H, W = int(cams.shape[0]), int(H), int(W)
         if M == 0:
@@ -102,17 +111,28 @@ class MapRenderer:
         depth = torch.empty(M, H, W, dtype=torch.float32, device=self.device)
         color = torch.empty(M, H, W, 3, dtype=torch.uint8, device=self.device)
         index = torch.empty(M, H, W, dtype=torch.int32, device=self.device)
+        nrgb = shaded = None
+        if self.normals is not None:
+            nrgb = torch.empty(M, H, W, 3, dtype=torch.uint8, device=self.device)
+            shaded = torch.empty(M, H, W, dtype=torch.uint8, device=self.device)
         with torch.cuda.device(self.device):
             self.stats.zero_()
+            self.shade_stats.zero_()
             for a in range(0, M, batch):
                 b = min(M, a + batch)
                 ops.render_splat(self.points, self.weights, cams_dev[a:b], self._zbuf, self.stats, H, W, self.voxel_size,
                                  splat_scale, min_weight, near, far)
                 ops.render_resolve(self._zbuf, self.colors, self.stats, b - a, H, W,
                                    out=(depth[a:b], color[a:b], index[a:b]))
+                if self.normals is not None:
+                    ops.render_shade(index[a:b], self.normals, cams_dev[a:b], self.shade_stats,
+                                     out=(nrgb[a:b], shaded[a:b]))
             st = self.stats.cpu().numpy()
         self.last_stats = {"culled": int(st[0]), "clamped": int(st[1]), "pixels": int(st[2]), "atomics": int(st[3])}
         out = {"depth": depth, "color": color, "index": index}
+        if self.normals is not None:
+            self.last_stats["shaded"] = int(self.shade_stats.cpu()[0])
+            out["normal"], out["shaded"] = nrgb, shaded
         return {k: t.cpu() for k, t in out.items()} if to_host else out
 
 
@@ -155,9 +175,11 @@ def overview_camera(poses_c2w, points, H: int, W: int, near: float = 0.05, margi
 
 
 def render_overview(points, colors, weights, voxel_size: float, poses_c2w, H: int, W: int, min_weight: int = 1,
-                    splat_scale: float = 1.0, near: float = 0.05, device="cuda") -> Dict:
+                    splat_scale: float = 1.0, near: float = 0.05, device="cuda", normals=None) -> Dict:
     """The map seen through overview_camera, with the camera centres appended as red voxels of weight `min_weight` (so
-    the trajectory is drawn by the same kernel) -> {'color' u8 (H,W,3), 'depth', 'index', 'pose', 'K', 'near'}."""
+    the trajectory is drawn by the same kernel) -> {'color' u8 (H,W,3), 'depth', 'index', 'pose', 'K', 'near'}.
+    normals (V,3): also 'shaded' u8 (H,W,3), the headlight shading in grey with the trajectory painted red (the camera
+    centres have no normal)."""
     P = _np(poses_c2w, np.float64).reshape(-1, 4, 4)
     pts = np.asarray(points, np.float32).reshape(-1, 3)
     pose, K = overview_camera(P, pts, H, W, near=near)
@@ -165,12 +187,20 @@ def render_overview(points, colors, weights, voxel_size: float, poses_c2w, H: in
     cols = np.zeros((len(pts), 3), np.uint8) if colors is None else np.asarray(colors, np.uint8).reshape(-1, 3)
     w = np.ones(len(pts), np.int32) if weights is None else np.asarray(weights, np.int32).reshape(-1)
     red = np.tile(np.array([[255, 0, 0]], np.uint8), (n, 1))
+    nrm = None if normals is None else np.concatenate(
+        [np.asarray(normals, np.float32).reshape(-1, 3), np.zeros((n, 3), np.float32)], 0)
     r = MapRenderer(np.concatenate([pts, P[:, :3, 3].astype(np.float32)], 0), np.concatenate([cols, red], 0),
-                    np.concatenate([w, np.full(n, int(min_weight), np.int32)], 0), voxel_size, device)
+                    np.concatenate([w, np.full(n, int(min_weight), np.int32)], 0), voxel_size, device, normals=nrm)
     out = r.render(pack_cameras(pose[None], K, ortho=True), H, W, min_weight=min_weight, splat_scale=splat_scale,
                    near=near)
-    return {"color": out["color"][0], "depth": out["depth"][0], "index": out["index"][0], "pose": pose, "K": K,
-            "near": float(near), "stats": r.last_stats}
+    res = {"color": out["color"][0], "depth": out["depth"][0], "index": out["index"][0], "pose": pose, "K": K,
+           "near": float(near), "stats": r.last_stats}
+    if nrm is not None:
+        grey = out["shaded"][0].numpy()
+        img = np.repeat(grey[:, :, None], 3, axis=2)
+        img[out["index"][0].numpy() >= len(pts)] = (255, 0, 0)
+        res["shaded"] = torch.from_numpy(img)
+    return res
 
 
 def depth_to_u16(depth, scale: float = DEPTH_PNG_SCALE) -> np.ndarray:
@@ -185,6 +215,13 @@ def write_depth_png(depth, path: str, scale: float = DEPTH_PNG_SCALE) -> None:
     """16-bit greyscale PNG: depth * scale (millimetres for metric maps), 0 = empty, 65535 = that far or farther."""
     from PIL import Image
     Image.fromarray(depth_to_u16(depth, scale).astype("<u2")).save(path, format="PNG")
+
+
+def write_grey_png(grey, path: str) -> None:
+    """8-bit greyscale PNG of a uint8 (H,W) image."""
+    from PIL import Image
+    g = _np(grey, np.uint8)
+    Image.fromarray(np.ascontiguousarray(g.reshape(g.shape[0], g.shape[1]))).save(path, format="PNG")
 
 
 def write_color_png(color, path: str) -> None:

@@ -20,7 +20,11 @@
      sweep count, and the masked extract; with the counted bytes of the support kernel (26 or 124 probes of a 64-byte
      slot per eligible voxel, the first slot of each probe chain only) and the rate they give.
 
-Prints one JSON line.  Usage: python tools/dense_fusion_timing.py [--voxel 0.02] [--rounds 3] [--chunks 4] [--consistency] [--clean]"""
+  5. --normals: the surface normals (csrc/voxel_normals.hip): fuse_pixel_normals and extract_normals beside fuse_pixels
+     and extract in the same run of leg 1 (the zeroing of the 32-byte-per-slot side array as well), with the counters;
+     and a creator leg with dense_normals on.
+
+Prints one JSON line.  Usage: python tools/dense_fusion_timing.py [--voxel 0.02] [--rounds 3] [--chunks 4] [--consistency] [--clean] [--normals]"""
 from __future__ import annotations
 
 import argparse
@@ -107,10 +111,10 @@ def synthetic_box_map(voxel: float, dev: str, side: int = 410, seed: int = 0):
     return fz
 
 
-def kernel_times(voxel: float, dev: str, reps: int = 20, clean: bool = False):
+def kernel_times(voxel: float, dev: str, reps: int = 20, clean: bool = False, normals: bool = False):
     import synth_sequence as ss
     from pi3_slam_amd.chunk_creator import OfflineChunkCreator
-    from pi3_slam_amd.dense_map import VoxelFuser
+    from pi3_slam_amd.dense_map import NormalAccumulator, VoxelFuser
     seq = ss.SyntheticSequence(os.path.join(ROOT, "tests", "golden", "gt_7scenes_chess.txt"), noise=dict(ss.NOISE_BF16))
     imgs = seq.frames(1, dev)
     out = ss.SceneEngine(seq)(imgs)
@@ -119,8 +123,11 @@ def kernel_times(voxel: float, dev: str, reps: int = 20, clean: bool = False):
     fz = VoxelFuser(voxel, dev)
     ev = lambda: torch.cuda.Event(enable_timing=True)   # noqa: E731
     t = {"clear_ms": [], "fuse_pixels_ms": [], "extract_ms": []}
+    if normals:
+        t.update(normals_clear_ms=[], fuse_pixel_normals_ms=[], extract_normals_ms=[])
+    acc = NormalAccumulator(fz) if normals else None
     for i in range(3 + reps):
-        e = [ev() for _ in range(4)]
+        e = [ev() for _ in range(7 if normals else 4)]
         e[0].record()
         fz.clear()
         e[1].record()
@@ -128,6 +135,13 @@ def kernel_times(voxel: float, dev: str, reps: int = 20, clean: bool = False):
         e[2].record()
         fz.extract_async()
         e[3].record()
+        if normals:
+            acc.clear()
+            e[4].record()
+            acc.add_pixels(pts, conf, masks, 0.5)
+            e[5].record()
+            acc.extract_async()
+            e[6].record()
         torch.cuda.synchronize()
         if i >= 3:
             for k, (a, b) in zip(t, zip(e, e[1:])):
@@ -136,6 +150,10 @@ def kernel_times(voxel: float, dev: str, reps: int = 20, clean: bool = False):
     out = {k: float(np.median(v)) for k, v in t.items()} | {
         "voxels": len(res["keys"]), "pixels": int(pts.numel() // 3), "masked_in": int(masks.sum()),
         "table_slots": fz.capacity, "table_bytes": fz.capacity * 64}
+    if normals:
+        acc.extract()
+        out["normals"] = dict(acc.last_stats, nacc_bytes=fz.capacity * 32,
+                              minmax_ms={k: [float(np.min(v)), float(np.max(v))] for k, v in t.items()})
     if clean:
         out["clean"] = clean_times(fz, reps)
     return out
@@ -176,7 +194,8 @@ def consistency_times(dev: str, reps: int = 20):
             "achieved_TBps": bytes_moved / (t * 1e-3) / 1e12, "settings": f.settings()}
 
 
-def creator_fps(voxel: float, dev: str, rounds: int, chunks: int, conf_threshold: float, consistency: bool = False):
+def creator_fps(voxel: float, dev: str, rounds: int, chunks: int, conf_threshold: float, consistency: bool = False,
+                normals: bool = False):
     from pi3_slam_amd.chunk_creator import OfflineChunkCreator, OfflineCreatorConfig
     from pi3_slam_amd.engine import Pi3Engine
     from pi3_slam_amd.weights import Pi3Config
@@ -189,12 +208,14 @@ def creator_fps(voxel: float, dev: str, rounds: int, chunks: int, conf_threshold
     frames = synthetic_frames_u8(CL, SRC_H, SRC_W, 1234)
     tmp = tempfile.mkdtemp(prefix="dense_timing_")
     creators = {}
-    legs = (("off", None, None), ("on", voxel, None)) + ((("filtered", voxel, 2),) if consistency else ())
+    legs = (("off", None, None), ("on", voxel, None)) + ((("filtered", voxel, 2),) if consistency else ()) \
+        + ((("normals", voxel, None),) if normals else ())
     for name, vs, mv in legs:
         cc = OfflineCreatorConfig(model_path="recipe", output_dir=os.path.join(tmp, name), chunk_length=CL, overlap=OV,
                                   device=dev, do_metric_depth=False, keypoint_type="grid", max_num_keypoints=KP,
                                   num_loader_workers=0, device_resize=True, dense_voxel_size=vs,
-                                  dense_conf_threshold=conf_threshold, dense_min_views=mv)
+                                  dense_conf_threshold=conf_threshold, dense_min_views=mv,
+                                  dense_normals=name == "normals")
         cr = OfflineChunkCreator(cc, model=engine)
         cr.target_size = (H, W)
         creators[name] = cr
@@ -230,6 +251,9 @@ def creator_fps(voxel: float, dev: str, rounds: int, chunks: int, conf_threshold
     if consistency:
         flt = float(np.median(fps["filtered"]))
         res.update(fps_filtered=fps["filtered"], median_fps_filtered=flt, filter_cost_pct=100.0 * (on - flt) / on)
+    if normals:
+        nrm = float(np.median(fps["normals"]))
+        res.update(fps_normals=fps["normals"], median_fps_normals=nrm, normals_cost_pct=100.0 * (on - nrm) / on)
     return res
 
 
@@ -246,16 +270,18 @@ def main():
                                                                "a creator leg with it on)")
     ap.add_argument("--clean", action="store_true", help="also time the map-cleaning filters on the chunk's table and on "
                                                          "a synthetic map of about 1 M voxels")
+    ap.add_argument("--normals", action="store_true", help="also time the surface-normal kernels beside fuse_pixels and "
+                                                           "extract, and a creator leg with dense_normals on")
     a = ap.parse_args()
     dev = "cuda:0"
     torch.cuda.set_device(0)
-    out = {"voxel_size": a.voxel, "kernels": kernel_times(a.voxel, dev, clean=a.clean)}
+    out = {"voxel_size": a.voxel, "kernels": kernel_times(a.voxel, dev, clean=a.clean, normals=a.normals)}
     if a.clean:
         out["clean_synthetic"] = clean_times(synthetic_box_map(a.voxel, dev))
     if a.consistency:
         out["consistency"] = consistency_times(dev)
     if not a.kernels_only:
-        out["creator"] = creator_fps(a.voxel, dev, a.rounds, a.chunks, a.conf_threshold, a.consistency)
+        out["creator"] = creator_fps(a.voxel, dev, a.rounds, a.chunks, a.conf_threshold, a.consistency, a.normals)
     print(json.dumps(out))
 
 

@@ -65,6 +65,9 @@ int pi3_lds_optin(const void* kern, int bytes, unsigned long long* done_mask, co
 #define PI3_DEV_KNOB(NAME, DFLT) ((long)(DFLT))
 #endif
 
+// doubles per camera record of the map renderer (layout: render.hip; also read by render_shade in voxel_normals.hip)
+constexpr int kCamDoubles = 20;
+
 __device__ __forceinline__ float bf16_bits_to_f32(uint16_t b) {
   return __uint_as_float(((uint32_t)b) << 16);
 }

@@ -26,6 +26,7 @@
 // depth test but touch no pixel, [1] radius clamps at 16, [2] non-empty pixels counted by pi3_render_resolve,
 // [3] atomics issued (development build only: the timing tool's issued-vs-skipped figure; 0 in the product).
 #include "common.h"
+#include "wave_block.h"
 
 #include <stdint.h>
 
@@ -34,7 +35,6 @@ namespace {
 typedef unsigned long long u64;
 
 constexpr u64 kEmptyPixel = ~0ull;
-constexpr int kCamDoubles = 20;
 constexpr double kMinRadius = 0.5, kMaxRadius = 16.0;
 
 __global__ __launch_bounds__(256) void render_splat_kernel(
@@ -119,9 +119,7 @@ __global__ __launch_bounds__(256) void render_resolve_kernel(const u64* __restri
                                                              const unsigned char* __restrict__ colors, long V, long n,
                                                              float* __restrict__ depth, unsigned char* __restrict__ color,
                                                              int* __restrict__ index, u64* __restrict__ stats) {
-  __shared__ unsigned wave_cnt[4];
-  const int tid = (int)threadIdx.x;
-  const long p0 = (long)blockIdx.x * (256L * kResolvePer) + tid;
+  const long p0 = (long)blockIdx.x * (256L * kResolvePer) + threadIdx.x;
   unsigned cnt = 0;
 #pragma unroll
   for (int j = 0; j < kResolvePer; ++j) {
@@ -148,14 +146,7 @@ __global__ __launch_bounds__(256) void render_resolve_kernel(const u64* __restri
     color[3 * p + 1] = g;
     color[3 * p + 2] = b;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
-  if ((tid & 63) == 0) wave_cnt[tid >> 6] = cnt;
-  __syncthreads();
-  if (tid == 0) {
-    const unsigned tot = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
-    if (tot) atomicAdd(stats + 2, (u64)tot);
-  }
+  wave_block::block_sum(cnt, stats + 2);
 }
 
 }  // namespace

@@ -1,54 +1,28 @@
 // Dense voxel map: confidence-filtered fusion of pi3's per-pixel pointmaps (and of whole chunk clouds) into one
-// open-addressing hash table of voxels on the device.
+// open-addressing hash table of voxels on the device (voxel_table.h: slot layout, quantisation, row claim).
 //
-// Slot layout (64 B, 8 x uint64): key | W | U0 U1 U2 | C0 C1 C2.
-//   key   the three voxel indices, each biased by 2^20 and packed at 21 bits (x << 42 | y << 21 | z); all ones = empty.
-//         Slots are claimed with a 64-bit CAS, collisions probe linearly.
-//   W     summed integer weight;  U = sum w * u with u = the fixed-point offset inside the voxel (24 fraction bits);
-//   C     sum w * rgb (uint8 colours).
 // Integer accumulators only: the sums do not depend on the order in which the atomics land, so a run is bitwise
 // reproducible and a float32 numpy oracle (tests/dense_map_ref.py) reproduces it bit for bit.
-//
-// Quantisation of one point p (per axis, fp32, no contraction):  s = p * inv_v;  k = floor(s);  f = s - k (exact);
-//   u = min(trunc(f * 2^24), 2^24 - 1)   (an exact integer whenever |s| >= 1; the clamp catches s in (-2^-24, 0), where
-//   s - k rounds to 1).  A point is dropped (and counted) when it is not finite or |k| >= 2^20.
 // Extraction: centroid = v * (k + U / (W * 2^24)) in f64, stored fp32;  colour = (C + W/2) / W;  weight = min(W, 2^31-1).
 //
-// Contention: a wave's 64 lanes hold 64 consecutive candidates (for the pixel form: 64 neighbouring pixels of a row,
-// which at 1-6 m depth and centimetre voxels mostly share voxels).  Runs of equal keys are merged in registers by a
-// segmented inclusive scan over the wave; only the last lane of each run touches the table (one probe + up to seven
-// 64-bit atomic adds).  Capacity is a power of two >= 2 x the candidates since the last clear (the caller's rule), so
-// the table never fills; every probe loop is bounded by the capacity anyway, and a candidate that finds no slot is
-// counted in stats[1] instead of looping.
+// Contention: runs of equal keys among a wave's 64 consecutive candidates are merged in registers (wave_block.h,
+// wave_merge_runs); the last lane of each run does one probe + up to seven 64-bit atomic adds.  Capacity is a power of
+// two >= 2 x the candidates since the last clear (the caller's rule), so the table never fills; every probe loop is
+// bounded by the capacity anyway, and a candidate that finds no slot is counted in stats[1] instead of looping.
 //
 // stats (caller-owned device memory, 4 x uint64): [0] dropped points, [1] table overflows (0 under the capacity rule),
 // [2] voxels written by the last extract, [3] voxels the last extract could not store (max_out too small).
 #include "common.h"
 #include "voxel_table.h"
+#include "wave_block.h"
 
 #include <stdint.h>
 
 namespace {
 
-using namespace voxel_table;      // u64, kEmpty, kBias, mix64, pack_key, pow2, blocks_for
-
-constexpr float kFix = 16777216.0f;    // 2^24
-
-// one axis: voxel index (biased) and fixed-point offset; false = drop
-__device__ __forceinline__ bool quantise(float p, float inv_v, uint32_t& kb, uint32_t& u) {
-#pragma clang fp contract(off)
-  if (!__builtin_isfinite(p)) return false;
-  float s = p * inv_v;
-  asm volatile("" : "+v"(s));          // the rounded product, never an fma with the subtraction below
-  const float k = floorf(s);
-  if (!(fabsf(k) < 1048576.0f)) return false;
-  const float f = s - k;
-  const float uf = f * kFix;
-  uint32_t ui = (uint32_t)uf;
-  u = ui > 0xFFFFFFu ? 0xFFFFFFu : ui;
-  kb = (uint32_t)((int)k + kBias);
-  return true;
-}
+using namespace voxel_table;      // u64, kEmpty, kBias, mix64, pack_key, quantise, claim_rows, pow2, blocks_for
+using wave_block::block_sum;
+using wave_block::wave_merge_runs;
 
 // add (w, U, C) to the slot of `key`; false when no slot was found within `capacity` probes
 __device__ __forceinline__ bool slot_add(u64* __restrict__ table, u64 mask, u64 key, u64 w, u64 u0, u64 u1, u64 u2,
@@ -76,36 +50,15 @@ __device__ __forceinline__ bool slot_add(u64* __restrict__ table, u64 mask, u64 
   return false;
 }
 
-// Every lane of the wave calls this (invalid lanes with valid = false).  Consecutive lanes with the same key are summed
-// in registers; the last lane of each run adds the run's totals to the table.
-__device__ __forceinline__ void wave_fuse(u64* __restrict__ table, u64 mask, bool valid, u64 key, u64 w, u64 v[6],
+// Every lane of the wave calls this (invalid lanes with valid = false).  v = w, U0 U1 U2, C0 C1 C2 of this lane's
+// candidate; the last lane of each run of equal keys adds the run's totals to the table.
+__device__ __forceinline__ void wave_fuse(u64* __restrict__ table, u64 mask, bool valid, u64 key, u64 (&v)[7],
                                           bool dropped, u64* __restrict__ stats) {
-  const int lane = (int)(threadIdx.x & 63);
-  if (!valid) key = kEmpty;
-  const u64 prev = __shfl_up(key, 1, 64);
-  const u64 next = __shfl_down(key, 1, 64);
-  const bool head = lane == 0 || prev != key;
-  const bool tail = lane == 63 || next != key;
-  const u64 heads = __ballot(head);
-  const u64 upto = lane == 63 ? ~0ull : ((2ull << lane) - 1ull);
-  const int seg = 63 - __clzll(heads & upto);          // first lane of this lane's run
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int oseg = __shfl_up(seg, d, 64);
-    const u64 ow = __shfl_up(w, d, 64);
-    u64 ov[6];
-#pragma unroll
-    for (int j = 0; j < 6; ++j) ov[j] = __shfl_up(v[j], d, 64);
-    if (lane >= d && oseg == seg) {
-      w += ow;
-#pragma unroll
-      for (int j = 0; j < 6; ++j) v[j] += ov[j];
-    }
-  }
+  const bool tail = wave_merge_runs(valid, key, kEmpty, v);
   bool lost = false;
-  if (valid && tail) lost = !slot_add(table, mask, key, w, v[0], v[1], v[2], v[3], v[4], v[5]);
+  if (valid && tail) lost = !slot_add(table, mask, key, v[0], v[1], v[2], v[3], v[4], v[5], v[6]);
   const u64 nd = __ballot(dropped), nl = __ballot(lost);
-  if (lane == 0) {
+  if ((threadIdx.x & 63) == 0) {
     if (nd) atomicAdd(stats + 0, (u64)__popcll(nd));
     if (nl) atomicAdd(stats + 1, (u64)__popcll(nl));
   }
@@ -135,26 +88,26 @@ __global__ __launch_bounds__(256) void voxel_fuse_pixels_kernel(
     float inv_v, u64* __restrict__ stats) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   bool valid = false, dropped = false;
-  u64 key = kEmpty, v[6] = {0, 0, 0, 0, 0, 0};
+  u64 key = kEmpty, v[7] = {1, 0, 0, 0, 0, 0, 0};
   if (i < n && (!masks || masks[i]) && (!conf || conf[i] > conf_thr)) {
     uint32_t kx, ky, kz, ux, uy, uz;
     const float px = points[3 * i], py = points[3 * i + 1], pz = points[3 * i + 2];
     if (quantise(px, inv_v, kx, ux) && quantise(py, inv_v, ky, uy) && quantise(pz, inv_v, kz, uz)) {
       valid = true;
       key = pack_key(kx, ky, kz);
-      v[0] = ux; v[1] = uy; v[2] = uz;
+      v[1] = ux; v[2] = uy; v[3] = uz;
       if (imgs) {
         const long f = i / HW, p = i - f * HW;
         const float* im = imgs + 3 * f * HW + p;
-        v[3] = colour_u8(im[0]);
-        v[4] = colour_u8(im[HW]);
-        v[5] = colour_u8(im[2 * HW]);
+        v[4] = colour_u8(im[0]);
+        v[5] = colour_u8(im[HW]);
+        v[6] = colour_u8(im[2 * HW]);
       }
     } else {
       dropped = true;
     }
   }
-  wave_fuse(table, mask, valid, key, 1ull, v, dropped, stats);
+  wave_fuse(table, mask, valid, key, v, dropped, stats);
 }
 
 __global__ __launch_bounds__(256) void voxel_fuse_points_kernel(
@@ -162,26 +115,27 @@ __global__ __launch_bounds__(256) void voxel_fuse_points_kernel(
     const int* __restrict__ weights, long n, float inv_v, u64* __restrict__ stats) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   bool valid = false, dropped = false;
-  u64 key = kEmpty, w = 0, v[6] = {0, 0, 0, 0, 0, 0};
+  u64 key = kEmpty, v[7] = {0, 0, 0, 0, 0, 0, 0};
   const int wi = (i < n) ? (weights ? weights[i] : 1) : 0;
   if (wi > 0) {
     uint32_t kx, ky, kz, ux, uy, uz;
     const float px = points[3 * i], py = points[3 * i + 1], pz = points[3 * i + 2];
     if (quantise(px, inv_v, kx, ux) && quantise(py, inv_v, ky, uy) && quantise(pz, inv_v, kz, uz)) {
       valid = true;
-      w = (u64)wi;
+      const u64 w = (u64)wi;
       key = pack_key(kx, ky, kz);
-      v[0] = w * ux; v[1] = w * uy; v[2] = w * uz;
+      v[0] = w;
+      v[1] = w * ux; v[2] = w * uy; v[3] = w * uz;
       if (colors) {
-        v[3] = w * colors[3 * i];
-        v[4] = w * colors[3 * i + 1];
-        v[5] = w * colors[3 * i + 2];
+        v[4] = w * colors[3 * i];
+        v[5] = w * colors[3 * i + 1];
+        v[6] = w * colors[3 * i + 2];
       }
     } else {
       dropped = true;
     }
   }
-  wave_fuse(table, mask, valid, key, w, v, dropped, stats);
+  wave_fuse(table, mask, valid, key, v, dropped, stats);
 }
 
 __global__ __launch_bounds__(256) void voxel_rehash_kernel(const u64* __restrict__ src, long src_capacity,
@@ -194,11 +148,7 @@ __global__ __launch_bounds__(256) void voxel_rehash_kernel(const u64* __restrict
   if (!slot_add(dst, dst_mask, q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7])) atomicAdd(stats + 1, 1ull);
 }
 
-constexpr int kExtractPer = 16;                 // slots per thread: one output-counter atomic per 4096 slots
-
-// Occupied slots -> output rows.  Each workgroup covers 256 x 16 slots (coalesced: slot = base + j * 256 + tid), counts
-// its occupied ones, claims its rows with ONE atomic on the counter (a per-wave atomic on one address serialised the
-// kernel at ~700 k voxels) and writes them; the order of the rows is arbitrary (the host sorts by key).
+// Occupied slots -> output rows (claim_rows: the workgroup's slots and its rows).
 // kMasked: only the occupied slots with keep[slot] != 0 (pi3_voxel_extract_kept); the rows themselves are computed alike.
 template <bool kMasked>
 __global__ __launch_bounds__(256) void voxel_extract_kernel(const u64* __restrict__ table, long capacity,
@@ -208,37 +158,15 @@ __global__ __launch_bounds__(256) void voxel_extract_kernel(const u64* __restric
                                                             int* __restrict__ weights, long max_out,
                                                             u64* __restrict__ stats) {
 #pragma clang fp contract(off)
-  __shared__ u64 wave_tot[4];
-  __shared__ u64 block_base;
-  const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const long s0 = (long)blockIdx.x * (256L * kExtractPer) + tid;
-  uint32_t occ = 0;
-#pragma unroll
-  for (int j = 0; j < kExtractPer; ++j) {
-    const long s = s0 + 256L * j;
-    if (s < capacity && table[8 * s] != kEmpty && (!kMasked || keep[s])) occ |= 1u << j;
-  }
-  const u64 cnt = (u64)__popc(occ);
-  u64 incl = cnt;                                  // inclusive prefix over the wave
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const u64 o = __shfl_up(incl, d, 64);
-    if (lane >= d) incl += o;
-  }
-  if (lane == 63) wave_tot[wv] = incl;
-  __syncthreads();
-  if (tid == 0) {
-    const u64 tot = wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
-    block_base = tot ? atomicAdd(stats + 2, tot) : 0ull;
-  }
-  __syncthreads();
-  u64 at = block_base + incl - cnt;
-  for (int w = 0; w < wv; ++w) at += wave_tot[w];
+  const long s0 = (long)blockIdx.x * (256L * kExtractPer) + threadIdx.x;
+  u64 at;
+  const uint32_t occ = claim_rows<kMasked>(s0, table, capacity, keep, stats + 2, at);
+  unsigned unstored = 0;
 #pragma unroll 1
   for (int j = 0; j < kExtractPer; ++j) {
     if (!(occ >> j & 1u)) continue;
     if ((long)at >= max_out) {
-      atomicAdd(stats + 3, 1ull);
+      ++unstored;
       ++at;
       continue;
     }
@@ -256,6 +184,7 @@ __global__ __launch_bounds__(256) void voxel_extract_kernel(const u64* __restric
     weights[at] = W > 0x7FFFFFFFull ? 0x7FFFFFFF : (int)W;     // saturated (the centroid and colour use the full W)
     ++at;
   }
+  block_sum(unstored, stats + 3);
 }
 
 }  // namespace

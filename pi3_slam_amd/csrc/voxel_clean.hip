@@ -32,37 +32,22 @@
 //
 // Sizes are uint32 atomic counts at the root's slot, so two runs give the same bytes.  Counters (caller-owned device
 // memory, 8 x uint64, zeroed by pi3_voxel_support): [0] occupied slots, [1] eligible, [2] after support, [3] after
-// components, [4] components found, [5] components kept.  Every counter is summed per workgroup in LDS and costs one
-// global atomic per workgroup (a per-wave atomic on one address once serialised voxel_extract).
+// components, [4] components found, [5] components kept.  Every counter is summed per workgroup (wave_block.h, block_count).
 #include "common.h"
 #include "voxel_table.h"
+#include "wave_block.h"
 
 #include <stdint.h>
 
 namespace {
 
 using namespace voxel_table;
+using wave_block::block_count;
 
 constexpr int kHops = 8;              // chain-shortening hops per sweep and slot
 
 __device__ __forceinline__ u64 load_relaxed(const u64* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// one workgroup's counts -> LDS -> one global atomic per counter (n counters, n <= 4)
-template <int N>
-__device__ __forceinline__ void block_count(const bool (&flag)[N], u64* __restrict__ counters, const int (&at)[N]) {
-  __shared__ unsigned tot[N];
-  const int tid = (int)threadIdx.x;
-  if (tid < N) tot[tid] = 0u;
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-    const u64 b = __ballot(flag[i]);
-    if ((tid & 63) == 0 && b) atomicAdd(&tot[i], (unsigned)__popcll(b));
-  }
-  __syncthreads();
-  if (tid < N && tot[tid]) atomicAdd(counters + at[tid], (u64)tot[tid]);
 }
 
 // Stage A.  kRadius = 1 or 2.  probe = false (min_support == 0 and nobody asks for the counts): eligibility only.

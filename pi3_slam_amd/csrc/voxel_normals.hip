@@ -19,9 +19,8 @@
 // multiply, divide and sqrt are correctly rounded on the device).  The Makefile compiles this file with
 // -ffp-contract=off: under the library's -ffp-contract=fast the pragma alone is ignored.
 //
-// Contention: as in voxel.hip a wave's 64 lanes hold 64 consecutive candidates; runs of equal keys are merged in
-// registers by a segmented scan of the four integers and only the last lane of a run looks its slot up (one probe + up
-// to four atomics).
+// Contention: runs of equal keys among a wave's 64 consecutive candidates are merged in registers (wave_block.h,
+// wave_merge_runs) and only the last lane of a run looks its slot up (one probe + up to four atomics).
 //
 // stats of the two fusion kernels (DEVICE uint64 [4], ACCUMULATED - the caller zeroes them): [0] contributions,
 // [1] candidates that could not contribute (pixels: no full 4-neighbourhood; points: the point does not quantise),
@@ -29,36 +28,19 @@
 // [3] contributions whose slot was not found (0 whenever the matching fusion of voxel.hip ran first).
 #include "common.h"
 #include "voxel_table.h"
+#include "wave_block.h"
 
 #include <stdint.h>
 
 namespace {
 
-using namespace voxel_table;      // u64, kEmpty, kBias, mix64, pack_key, slot_find, pow2, blocks_for
+using namespace voxel_table;      // u64, kEmpty, point_key, slot_find, claim_rows, kExtractPer, pow2, blocks_for
+using wave_block::block_sum;
+using wave_block::wave_merge_runs;
 
 typedef long long i64;
 
 constexpr double kUnit = 32768.0;      // 2^15: one unit normal's fixed-point length
-
-// voxel.hip's quantisation of one axis, the voxel index only (its asm barrier keeps the product rounded there too)
-__device__ __forceinline__ bool quantise_index(float p, float inv_v, uint32_t& kb) {
-#pragma clang fp contract(off)
-  if (!__builtin_isfinite(p)) return false;
-  float s = p * inv_v;
-  asm volatile("" : "+v"(s));
-  const float k = floorf(s);
-  if (!(fabsf(k) < 1048576.0f)) return false;
-  kb = (uint32_t)((int)k + kBias);
-  return true;
-}
-
-__device__ __forceinline__ bool point_key(const float* __restrict__ p, float inv_v, u64& key) {
-  uint32_t kx, ky, kz;
-  if (!(quantise_index(p[0], inv_v, kx) && quantise_index(p[1], inv_v, ky) && quantise_index(p[2], inv_v, kz)))
-    return false;
-  key = pack_key(kx, ky, kz);
-  return true;
-}
 
 // fuse_pixels' predicate: mask, conf > thr, all three axes quantise
 __device__ __forceinline__ bool candidate(const float* __restrict__ points, const float* __restrict__ conf,
@@ -69,40 +51,19 @@ __device__ __forceinline__ bool candidate(const float* __restrict__ points, cons
   return point_key(points + 3 * i, inv_v, key);
 }
 
-// Every lane of the wave calls this (lanes without a voxel with valid = false).  Consecutive lanes with the same key
-// are summed in registers; the last lane of a run with cnt > 0 adds the run's totals to its slot of nacc.
-// v = Nx, Ny, Nz, cnt (two's complement); contributes = this lane's pixel / row adds to cnt.
+// Every lane of the wave calls this (lanes without a voxel with valid = false).  v = Nx, Ny, Nz, cnt (two's complement)
+// of this lane's pixel / row and 1 when it contributes, else all 0: the fifth word sums to the contributing pixels /
+// rows of a run (cnt counts weights).  The last lane of a run of equal keys with one of them adds the run's totals to
+// its slot of nacc.
 __device__ __forceinline__ void wave_add_normals(const u64* __restrict__ table, u64 mask, u64* __restrict__ nacc,
-                                                 bool valid, u64 key, u64 v[4], bool contributes, bool skipped,
+                                                 bool valid, u64 key, u64 (&v)[5], bool contributes, bool skipped,
                                                  bool degenerate, u64* __restrict__ stats) {
-  const int lane = (int)(threadIdx.x & 63);
-  if (!valid) key = kEmpty;
-  const u64 prev = __shfl_up(key, 1, 64);
-  const u64 next = __shfl_down(key, 1, 64);
-  const bool head = lane == 0 || prev != key;
-  const bool tail = lane == 63 || next != key;
-  const u64 heads = __ballot(head);
-  const u64 upto = lane == 63 ? ~0ull : ((2ull << lane) - 1ull);
-  const int seg = 63 - __clzll(heads & upto);          // first lane of this lane's run
-  u64 rows = contributes ? 1ull : 0ull;                // contributing pixels / rows of the run (cnt counts weights)
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int oseg = __shfl_up(seg, d, 64);
-    const u64 orows = __shfl_up(rows, d, 64);
-    u64 ov[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) ov[j] = __shfl_up(v[j], d, 64);
-    if (lane >= d && oseg == seg) {
-      rows += orows;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) v[j] += ov[j];
-    }
-  }
+  const bool tail = wave_merge_runs(valid, key, kEmpty, v);
   u64 lost = 0;
-  if (valid && tail && rows) {
+  if (valid && tail && v[4]) {
     const long s = slot_find(table, mask, key);
     if (s < 0) {
-      lost = rows;
+      lost = v[4];
     } else {
       u64* q = nacc + 4 * s;
       if (v[0]) atomicAdd(q + 0, v[0]);
@@ -114,7 +75,7 @@ __device__ __forceinline__ void wave_add_normals(const u64* __restrict__ table, 
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) lost += __shfl_xor(lost, o, 64);
   const u64 nc = __ballot(contributes), ns = __ballot(skipped), nd = __ballot(degenerate);
-  if (lane == 0) {
+  if ((threadIdx.x & 63) == 0) {
     if (nc) atomicAdd(stats + 0, (u64)__popcll(nc));
     if (ns) atomicAdd(stats + 1, (u64)__popcll(ns));
     if (nd) atomicAdd(stats + 2, (u64)__popcll(nd));
@@ -129,7 +90,7 @@ __global__ __launch_bounds__(256) void fuse_pixel_normals_kernel(
 #pragma clang fp contract(off)
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   bool valid = false, contributes = false, skipped = false, degenerate = false;
-  u64 key = kEmpty, v[4] = {0, 0, 0, 0};
+  u64 key = kEmpty, v[5] = {0, 0, 0, 0, 0};
   if (i < n && candidate(points, conf, masks, i, conf_thr, inv_v, key)) {
     valid = true;
     // neighbours by (f, y, x): a wave may hold the end of one row and the start of the next, or of two frames
@@ -155,7 +116,7 @@ __global__ __launch_bounds__(256) void fuse_pixel_normals_kernel(
         v[0] = (u64)(i64)rint((nx / len) * kUnit);
         v[1] = (u64)(i64)rint((ny / len) * kUnit);
         v[2] = (u64)(i64)rint((nz / len) * kUnit);
-        v[3] = 1ull;
+        v[3] = v[4] = 1ull;
         contributes = true;
       } else {
         degenerate = true;
@@ -183,7 +144,7 @@ __global__ __launch_bounds__(256) void fuse_point_normals_kernel(
 #pragma clang fp contract(off)
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   bool valid = false, contributes = false, skipped = false, degenerate = false;
-  u64 key = kEmpty, v[4] = {0, 0, 0, 0};
+  u64 key = kEmpty, v[5] = {0, 0, 0, 0, 0};
   const int wi = i < n ? nweights[i] : 0;
   if (wi > 0) {
     const float fx = normals[3 * i], fy = normals[3 * i + 1], fz = normals[3 * i + 2];
@@ -200,16 +161,15 @@ __global__ __launch_bounds__(256) void fuse_point_normals_kernel(
       v[1] = (u64)(w * fixed_component((rot[3] * nx + rot[4] * ny) + rot[5] * nz));
       v[2] = (u64)(w * fixed_component((rot[6] * nx + rot[7] * ny) + rot[8] * nz));
       v[3] = (u64)w;
+      v[4] = 1ull;
     }
   }
   wave_add_normals(table, mask, nacc, valid, key, v, contributes, skipped, degenerate, stats);
 }
 
-constexpr int kExtractPer = 16;                 // slots per thread, as voxel_extract_kernel
-
-// Occupied (kMasked: and kept) slots -> rows, in voxel_extract_kernel's shape: a workgroup covers 256 x 16 slots, counts
-// its rows and claims them with ONE atomic on the counter.  stats: [0] rows, [1] rows that did not fit max_out, [2] stored
-// rows with a non-zero normal.
+// Occupied (kMasked: and kept) slots -> rows, claimed as voxel_extract_kernel's (claim_rows), so the two extractions
+// of one table give the same rows in the same order of slots.  stats: [0] rows, [1] rows that did not fit max_out,
+// [2] stored rows with a non-zero normal.
 template <bool kMasked>
 __global__ __launch_bounds__(256) void extract_normals_kernel(const u64* __restrict__ table, long capacity,
                                                               const i64* __restrict__ nacc,
@@ -218,33 +178,9 @@ __global__ __launch_bounds__(256) void extract_normals_kernel(const u64* __restr
                                                               int* __restrict__ nweights, long max_out,
                                                               u64* __restrict__ stats) {
 #pragma clang fp contract(off)
-  __shared__ u64 wave_tot[4];
-  __shared__ unsigned wave_nz[4];
-  __shared__ u64 block_base;
-  const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const long s0 = (long)blockIdx.x * (256L * kExtractPer) + tid;
-  uint32_t occ = 0;
-#pragma unroll
-  for (int j = 0; j < kExtractPer; ++j) {
-    const long s = s0 + 256L * j;
-    if (s < capacity && table[8 * s] != kEmpty && (!kMasked || keep[s])) occ |= 1u << j;
-  }
-  const u64 cnt = (u64)__popc(occ);
-  u64 incl = cnt;                                  // inclusive prefix over the wave
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const u64 o = __shfl_up(incl, d, 64);
-    if (lane >= d) incl += o;
-  }
-  if (lane == 63) wave_tot[wv] = incl;
-  __syncthreads();
-  if (tid == 0) {
-    const u64 tot = wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
-    block_base = tot ? atomicAdd(stats + 0, tot) : 0ull;
-  }
-  __syncthreads();
-  u64 at = block_base + incl - cnt;
-  for (int w = 0; w < wv; ++w) at += wave_tot[w];
+  const long s0 = (long)blockIdx.x * (256L * kExtractPer) + threadIdx.x;
+  u64 at;
+  const uint32_t occ = claim_rows<kMasked>(s0, table, capacity, keep, stats + 0, at);
   unsigned nonzero = 0, unstored = 0;
 #pragma unroll 1
   for (int j = 0; j < kExtractPer; ++j) {
@@ -273,23 +209,11 @@ __global__ __launch_bounds__(256) void extract_normals_kernel(const u64* __restr
     nweights[at] = c > 0x7FFFFFFFll ? 0x7FFFFFFF : (c < 0 ? 0 : (int)c);
     ++at;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    nonzero += __shfl_xor(nonzero, o, 64);
-    unstored += __shfl_xor(unstored, o, 64);
-  }
-  if (lane == 0) {
-    wave_nz[wv] = nonzero;
-    if (unstored) atomicAdd(stats + 1, (u64)unstored);
-  }
-  __syncthreads();
-  if (tid == 0) {
-    const unsigned tot = wave_nz[0] + wave_nz[1] + wave_nz[2] + wave_nz[3];
-    if (tot) atomicAdd(stats + 2, (u64)tot);
-  }
+  block_sum(nonzero, stats + 2);
+  __syncthreads();                              // block_sum's LDS words are read by thread 0 until here
+  block_sum(unstored, stats + 1);
 }
 
-constexpr int kCamDoubles = 20;             // render.hip's camera record
 constexpr int kShadePer = 8;                // pixels per thread: one counter atomic per 2048 pixels
 
 // v rounded to an integer already: 0 for v <= 0 and for NaN, 255 for v >= 255
@@ -304,9 +228,7 @@ __global__ __launch_bounds__(256) void render_shade_kernel(const int* __restrict
                                                            unsigned char* __restrict__ normal_rgb,
                                                            unsigned char* __restrict__ shaded, u64* __restrict__ stats) {
 #pragma clang fp contract(off)
-  __shared__ unsigned wave_cnt[4];
-  const int tid = (int)threadIdx.x;
-  const long p0 = (long)blockIdx.x * (256L * kShadePer) + tid;
+  const long p0 = (long)blockIdx.x * (256L * kShadePer) + threadIdx.x;
   unsigned cnt = 0;
 #pragma unroll
   for (int j = 0; j < kShadePer; ++j) {
@@ -336,14 +258,7 @@ __global__ __launch_bounds__(256) void render_shade_kernel(const int* __restrict
     normal_rgb[3 * p + 2] = b;
     shaded[p] = s;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
-  if ((tid & 63) == 0) wave_cnt[tid >> 6] = cnt;
-  __syncthreads();
-  if (tid == 0) {
-    const unsigned tot = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
-    if (tot) atomicAdd(stats + 0, (u64)tot);
-  }
+  block_sum(cnt, stats + 0);
 }
 
 }  // namespace

@@ -54,10 +54,40 @@ def inverse_voxel(voxel_size: float) -> float:
     return float(np.float32(1.0 / v))
 
 
-def sort_by_key(keys: np.ndarray, points: np.ndarray, colors: np.ndarray, weights: np.ndarray) -> Dict[str, np.ndarray]:
-    """The extract output in ascending key order (the device writes it in slot-claim order)."""
+def _key_sorted(keys: np.ndarray, *rows: np.ndarray) -> Tuple[np.ndarray, ...]:
+    """keys and every row array in ascending key order (the device writes the rows in slot-claim order)."""
     order = np.argsort(keys.view(np.uint64))        # keys are unique: every sort kind gives this order
-    return dict(keys=keys[order], points=points[order], colors=colors[order], weights=weights[order])
+    return tuple(a[order] for a in (keys,) + rows)
+
+
+def sort_by_key(keys: np.ndarray, points: np.ndarray, colors: np.ndarray, weights: np.ndarray) -> Dict[str, np.ndarray]:
+    """The extract output in ascending key order."""
+    return dict(zip(("keys", "points", "colors", "weights"), _key_sorted(keys, points, colors, weights)))
+
+
+def sort_normals_by_key(keys: np.ndarray, normals: np.ndarray, nweights: np.ndarray) -> Dict[str, np.ndarray]:
+    """The normal rows in ascending key order: row for row the voxels of sort_by_key."""
+    return dict(zip(("keys", "normals", "normal_weights"), _key_sorted(keys, normals, nweights)))
+
+
+class _ExtractBuffers:
+    """The output buffers of an extraction, allocated once and re-used in turn: a caller that reads set k on the host
+    while the extraction into the next one is queued (the pipelined creator) asks for 2 sets."""
+
+    def __init__(self, empty_outputs, sets: int = 1):
+        self._empty_outputs = empty_outputs         # (rows, device) -> a tuple of device buffers with `rows` rows
+        self._sets = [None] * max(1, int(sets))
+        self._turn = 0
+
+    def take(self, rows: int, device) -> tuple:
+        """This turn's set with at least `rows` rows (>= 1); the next call takes the next set."""
+        i = self._turn
+        self._turn = (i + 1) % len(self._sets)
+        rows = max(int(rows), 1)
+        if self._sets[i] is None or self._sets[i][0].shape[0] < rows:
+            self._sets[i] = None                    # free the smaller set first
+            self._sets[i] = self._empty_outputs(rows, device)
+        return self._sets[i]
 
 
 @dataclass
@@ -229,10 +259,7 @@ class VoxelFuser:
         self.capacity = 0
         self.bound = 0          # candidate points fused since the last clear: an upper bound of the occupied slots
         self.stats = torch.zeros(4, dtype=torch.int64, device=self.device)
-        # extract output buffers, allocated once and re-used in turn: a caller that reads set k on the host while the
-        # extraction into the next one is queued (the pipelined creator) asks for 2
-        self._outs = [None] * max(1, int(out_sets))
-        self._turn = 0
+        self._out = _ExtractBuffers(ops.voxel_empty_outputs, out_sets)
 
     def reserve(self, n_more: int) -> None:
         need = ops.voxel_capacity(self.bound + int(n_more))
@@ -279,15 +306,9 @@ class VoxelFuser:
         of the stats (stats[2] = the number of valid rows, stats[0] = dropped points).  keep: MapCleaner.apply's mask."""
         if self.table is None:
             self.reserve(0)
-        i = self._turn
-        self._turn = (i + 1) % len(self._outs)
-        rows = max(self.bound, 1)
-        if self._outs[i] is None or self._outs[i][0].shape[0] < rows:
-            self._outs[i] = None                 # free the smaller set first
-            self._outs[i] = ops.voxel_empty_outputs(rows, self.device)
-        keys, pts, cols, w = self._outs[i]
-        ops.voxel_extract(self.table, self.stats, self.voxel_size, self.bound, out=(keys, pts, cols, w), keep=keep)
-        return (keys, pts, cols, w), self.stats.clone()
+        out = self._out.take(self.bound, self.device)
+        ops.voxel_extract(self.table, self.stats, self.voxel_size, self.bound, out=out, keep=keep)
+        return out, self.stats.clone()
 
     def extract(self, keep: Optional[torch.Tensor] = None) -> Dict[str, np.ndarray]:
         """Host arrays in ascending key order: keys u64, points f32 (V,3), colors u8 (V,3), weights i32 (V,); also
@@ -299,12 +320,6 @@ class VoxelFuser:
         if self.last_stats["overflow"]:
             raise RuntimeError(f"voxel table overflow: {self.last_stats}")
         return sort_by_key(keys[:V].cpu().numpy(), pts[:V].cpu().numpy(), cols[:V].cpu().numpy(), w[:V].cpu().numpy())
-
-
-def sort_normals_by_key(keys: np.ndarray, normals: np.ndarray, nweights: np.ndarray) -> Dict[str, np.ndarray]:
-    """The normal rows in ascending key order: row for row the voxels of sort_by_key."""
-    order = np.argsort(keys.view(np.uint64))
-    return dict(keys=keys[order], normals=normals[order], normal_weights=nweights[order])
 
 
 def similarity_rotation(G) -> np.ndarray:
@@ -329,8 +344,7 @@ class NormalAccumulator:
         # not fit, rows with a non-zero normal, spare
         self.stats = torch.zeros(8, dtype=torch.int64, device=fuser.device)
         self._bound_to: Optional[Tuple[int, int]] = None      # (table address, capacity) at the first add
-        self._outs = [None] * max(1, int(out_sets))
-        self._turn = 0
+        self._out = _ExtractBuffers(ops.voxel_empty_normal_outputs, out_sets)
 
     def clear(self) -> None:
         if self.fuser.table is None:
@@ -375,14 +389,9 @@ class NormalAccumulator:
         """Queue the extraction; -> (keys, normals, nweights) device buffers of fuser.bound rows and a device copy of
         the stats (stats[4] = the number of valid rows)."""
         table = self._table()
-        i = self._turn
-        self._turn = (i + 1) % len(self._outs)
-        rows = max(self.fuser.bound, 1)
-        if self._outs[i] is None or self._outs[i][0].shape[0] < rows:
-            self._outs[i] = None
-            self._outs[i] = ops.voxel_empty_normal_outputs(rows, self.fuser.device)
-        ops.voxel_extract_normals(table, self.nacc, self.stats[4:], self.fuser.bound, out=self._outs[i], keep=keep)
-        return self._outs[i], self.stats.clone()
+        out = self._out.take(self.fuser.bound, self.fuser.device)
+        ops.voxel_extract_normals(table, self.nacc, self.stats[4:], self.fuser.bound, out=out, keep=keep)
+        return out, self.stats.clone()
 
     @staticmethod
     def check_stats(st) -> Dict[str, int]:
@@ -484,7 +493,7 @@ class ChunkCloudBuilder:
         rows = sort_by_key(*(t.numpy() for t in h[:4]))
         if nbufs:
             nrm = sort_normals_by_key(*(t.numpy() for t in h[4:]))
-            rows["normal_keys"], rows["normals"], rows["normal_weights"] = nrm["keys"], nrm["normals"], nrm["normal_weights"]
+            rows.update(normal_keys=nrm["keys"], normals=nrm["normals"], normal_weights=nrm["normal_weights"])
         return rows
 
     def collect(self, job: Future, got: Dict[str, torch.Tensor], metrics: Dict) -> Dict:

@@ -155,6 +155,81 @@ def test_fuse_points_weighted_and_growth_beyond_first_capacity():
     _same(got, ref.fuse_point_sets([(p1.numpy(), c1.numpy(), w1.numpy()), (p2.numpy(), c2.numpy(), w2.numpy())], 0.01))
 
 
+def _row_claim_case(n, seed, v=0.02):
+    """n distinct voxels with colours, weights and normals on the device, and the oracles' rows by ascending key."""
+    import dense_normals_ref as nref
+    from pi3_slam_amd.dense_map import NormalAccumulator, VoxelFuser
+    rng = np.random.default_rng(seed)
+    cells = np.unique(rng.integers(-40, 40, (3 * n, 3)), axis=0)
+    cells = cells[rng.permutation(len(cells))[:n]]
+    assert len(cells) == n
+    pts = ((cells + rng.uniform(0.1, 0.9, (n, 3))) * v).astype(np.float32)
+    cols = rng.integers(0, 256, (n, 3), dtype=np.uint8)
+    w = rng.integers(1, 6, n).astype(np.int32)
+    nr = rng.normal(size=(n, 3))
+    nr = (nr / np.linalg.norm(nr, axis=1, keepdims=True)).astype(np.float32)
+    eye9 = np.eye(3).reshape(9)
+    exp = ref.fuse_points(pts, cols, w, v)
+    assert len(exp["keys"]) == n
+    exp.update(nref.extract(exp["keys"], nref.accumulate([nref.point_normals(pts, nr, w, eye9, ref.inv_voxel(v))])))
+    fz = VoxelFuser(v, DEV)
+    P, Wt = torch.from_numpy(pts).to(DEV), torch.from_numpy(w).to(DEV)
+    fz.fuse_points(P, torch.from_numpy(cols).to(DEV), Wt)
+    acc = NormalAccumulator(fz)
+    acc.clear()
+    acc.add_points(P, torch.from_numpy(nr).to(DEV), Wt, torch.from_numpy(eye9.copy()).to(DEV))
+    return fz, acc, exp
+
+
+def test_row_claim_in_a_table_smaller_than_one_workgroup():
+    """Nine voxels in 32 slots: one workgroup of the extractions, most of its 256 x 16 slots past the capacity."""
+    fz, acc, exp = _row_claim_case(9, seed=21)
+    assert fz.capacity == 32
+    _same(fz.extract(), exp)
+    rows = acc.extract()
+    assert rows["keys"].view(np.uint64).tobytes() == exp["keys"].tobytes()
+    assert rows["normals"].tobytes() == exp["normals"].tobytes()
+    assert rows["normal_weights"].tobytes() == exp["normal_weights"].tobytes()
+    assert acc.last_stats["rows"] == 9 and acc.last_stats["nonzero"] == 9
+
+
+def test_rows_that_do_not_fit_are_counted_and_not_written():
+    """5000 voxels in 16384 slots (four workgroups of the extractions) into buffers of 1064 rows with max_out = 1000:
+    1000 rows are stored, each the oracle's row of its key, the other 4000 are counted and rows 1000 .. 1063 keep their
+    sentinel.  Then the same with a keep mask on every second occupied slot: 2500 rows, 1500 of them unstored."""
+    from pi3_slam_amd import ops
+    fz, acc, exp = _row_claim_case(5000, seed=22)
+    assert fz.capacity == 16384
+    occupied = torch.nonzero(fz.table.view(-1, 8)[:, 0] != -1).reshape(-1)
+    assert occupied.numel() == 5000
+    keep = torch.zeros(fz.capacity, dtype=torch.uint8, device=DEV)
+    keep[occupied[::2]] = 1
+    kept_keys = fz.table.view(-1, 8)[occupied[::2], 0].cpu().numpy().view(np.uint64)
+    fills = {torch.int64: -2, torch.float32: -7.0, torch.uint8: 0xAB, torch.int32: -5}
+    for mask, allowed, total in ((None, exp["keys"], 5000), (keep, kept_keys, 2500)):
+        cloud = tuple(t.fill_(fills[t.dtype]) for t in ops.voxel_empty_outputs(1064, DEV))
+        nrows = tuple(t.fill_(fills[t.dtype]) for t in ops.voxel_empty_normal_outputs(1064, DEV))
+        stats, nstats = fz.stats.clone(), torch.zeros(4, dtype=torch.int64, device=DEV)
+        ops.voxel_extract(fz.table, stats, fz.voxel_size, 1000, out=cloud, keep=mask)
+        ops.voxel_extract_normals(fz.table, acc.nacc, nstats, 1000, out=nrows, keep=mask)
+        stats, nstats = stats.tolist(), nstats.tolist()
+        print(f"keep {mask is not None}: cloud stats {stats}, normal stats {nstats}")
+        assert stats[2] == total and stats[3] == total - 1000 and stats[1] == 0
+        assert nstats[0] == total and nstats[1] == total - 1000
+        names = (("keys", "points", "colors", "weights"), ("keys", "normals", "normal_weights"))
+        for bufs, cols_ in zip((cloud, nrows), names):
+            host = [t.cpu().numpy() for t in bufs]
+            keys = host[0][:1000].view(np.uint64)
+            assert len(np.unique(keys)) == 1000 and np.isin(keys, allowed).all()
+            at = np.searchsorted(exp["keys"], keys)
+            assert (exp["keys"][at] == keys).all()
+            for h, k in zip(host[1:], cols_[1:]):
+                assert h.dtype == exp[k].dtype and h[:1000].tobytes() == exp[k][at].tobytes(), k
+            for h, t in zip(host, bufs):
+                assert (h[1000:] == np.asarray(fills[t.dtype], h.dtype)).all()
+        assert nstats[2] == 1000                    # every voxel holds one unit normal: each stored row is non-zero
+
+
 # ------------------------------------------------------------------------------------------------ creator / stage 2
 def _creator(seq, out_dir, **kw):
     import synth_sequence as ss

@@ -198,6 +198,82 @@ def test_point_normals_of_two_clouds_match_the_oracle_byte_for_byte():
     _same_rows(again, kept_rows)
 
 
+# The 512 points of the designed cloud (two workgroups of four waves), as runs of equal voxels: (voxel, first, last + 1).
+#   A one point | C a weight-0 point at 13 and a NaN point at 16: three runs of one key | D .. E .. D the same key again,
+#   not adjacent | F two opposite normals of weight 2 | H ends at lane 63 and goes on at lane 0 of the next wave: two
+#   partial sums | J exactly one wave | L 130 points over the workgroup boundary at 256 and two wave boundaries |
+#   N 65 points over the wave boundary at 384.
+_RUNS = (("A", 0, 1), ("B", 1, 10), ("C", 10, 20), ("D", 20, 25), ("E", 25, 30), ("D", 30, 35), ("F", 35, 37),
+         ("G", 37, 50), ("H", 50, 71), ("I", 71, 128), ("J", 128, 192), ("K", 192, 200), ("L", 200, 330),
+         ("M", 330, 341), ("N", 341, 406), ("O", 406, 461), ("P", 461, 512))
+# The summed weight per voxel, by hand: point i weighs 1 + i % 3 (F's two points 2 each), so three consecutive points
+# weigh 6.  E.g. J = 128 .. 191: 21 triples and the point 128 (weight 3) = 129; C = 10 .. 19 without 13 and 16:
+# (2+3+1) + (3+1) + (3+1+2) = 16; H = 50 .. 70: 7 triples = 42.
+_RUN_WEIGHTS = {"A": 1, "B": 18, "C": 16, "D": 19, "E": 11, "F": 4, "G": 26, "H": 42, "I": 114, "J": 129, "K": 15,
+                "L": 261, "M": 21, "N": 130, "O": 110, "P": 102}
+
+
+def test_designed_runs_through_both_wave_merges():
+    """fuse_points (7 summed words) and add_points (5) on one cloud whose order places every kind of run boundary (see
+    _RUNS).  The points are voxel centres at a voxel size of 2^-5, colours depend on the voxel only and the normals are
+    axis-aligned under the identity rotation: every sum is exact, so each voxel's weight is known by hand, and every
+    output byte equals the oracles'."""
+    from pi3_slam_amd.dense_map import NormalAccumulator, VoxelFuser
+    v = 0.03125
+    names = sorted(_RUN_WEIGHTS)
+    cell = {n: np.array([j - 7, 3 - 2 * j, 5 * j - 30], np.float64) for j, n in enumerate(names)}
+    pts, cols = np.empty((512, 3), np.float32), np.empty((512, 3), np.uint8)
+    w = (1 + np.arange(512) % 3).astype(np.int32)
+    nr = np.eye(3, dtype=np.float32)[np.arange(512) % 3]
+    at = 0
+    for n, a, b in _RUNS:
+        assert a == at and b > a
+        at = b
+        pts[a:b] = (cell[n] + 0.5) * v
+        cols[a:b] = (10 * names.index(n), 20 + names.index(n), 255 - names.index(n))
+    assert at == 512
+    w[35:37] = 2
+    nr[35], nr[36] = (1, 0, 0), (-1, 0, 0)
+    w[13] = 0
+    pts[16, 1] = np.nan
+    eye9 = np.eye(3).reshape(9)
+
+    exp_cloud = dm.fuse_points(pts, cols, w, v)
+    part = ref.point_normals(pts, nr, w, eye9, dm.inv_voxel(v))
+    exp = ref.extract(exp_cloud["keys"], ref.accumulate([part]))
+
+    def run():
+        fz = VoxelFuser(v, DEV)
+        P, Wt = torch.from_numpy(pts).to(DEV), torch.from_numpy(w).to(DEV)
+        fz.fuse_points(P, torch.from_numpy(cols).to(DEV), Wt)
+        acc = NormalAccumulator(fz)
+        acc.clear()
+        acc.add_points(P, torch.from_numpy(nr).to(DEV), Wt, torch.from_numpy(eye9.copy()).to(DEV))
+        return fz.extract(), acc.extract(), fz.last_stats, acc.last_stats
+
+    cloud, rows, cst, st = run()
+    assert len(cloud["keys"]) == len(names)
+    for k in ("keys", "points", "colors", "weights"):
+        assert cloud[k].dtype.itemsize == exp_cloud[k].dtype.itemsize and cloud[k].tobytes() == exp_cloud[k].tobytes(), k
+    _same_rows(rows, exp)
+    ok, keys, _ = dm.quantise(np.stack([(cell[n] + 0.5) * v for n in names]).astype(np.float32), dm.inv_voxel(v))
+    assert ok.all()
+    where = np.searchsorted(cloud["keys"].view(np.uint64), keys)
+    assert (cloud["keys"].view(np.uint64)[where] == keys).all()
+    got_w = dict(zip(names, cloud["weights"][where].tolist()))
+    got_nw = dict(zip(names, rows["normal_weights"][where].tolist()))
+    print(f"weights {got_w}, dropped {cst['dropped']}, normals {st}")
+    assert got_w == _RUN_WEIGHTS and got_nw == _RUN_WEIGHTS
+    assert not rows["normals"][where[names.index("F")]].any()           # the opposite pair cancels
+    assert cst["dropped"] == 1 and cst["overflow"] == 0                 # the NaN point; the weight-0 point is no candidate
+    assert (st["contributions"], st["skipped"], st["degenerate"], st["lost"]) == (510, 1, 0, 0)
+    assert part["stats"].tolist() == [510, 1, 0, 0] and exp_cloud["dropped"] == 1
+    cloud2, rows2, _, _ = run()
+    for k in ("keys", "points", "colors", "weights"):
+        assert cloud2[k].tobytes() == cloud[k].tobytes(), k
+    _same_rows(rows2, rows)
+
+
 def _pose_looking(eye, target):
     eye, target = np.asarray(eye, np.float64), np.asarray(target, np.float64)
     z = (target - eye) / np.linalg.norm(target - eye)

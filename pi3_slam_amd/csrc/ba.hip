@@ -17,6 +17,12 @@
 // One LM iteration = fixed sequence of kernels; accept / reject and the trust-region radius live in a device-side state
 // block (no host synchronisation inside the loop).  Every reduction has a fixed order: results do not depend on
 // scheduling.
+//
+// Order of the file: shared math - Euclidean / homogeneous passes - inverse depth - Schur complement - Cholesky - step,
+// decision, outliers - host (C ABI).  What exists once: ba_observe (residual, Jacobians, Huber weight of an observation),
+// ba_walk_track (a track's observations in camera order, for the thread-per-track kernels; the camera-major kernels
+// stride over tracks and call ba_observe), ba_cost_points (the cost of all three forms), ba_prior_residual,
+// ba_accumulate27 / ba_wjj / ba_wjr (normal-equation entries), ba_sym3_mul, ba_layout (the workspace's size and pointers).
 #include "common.h"
 
 #define BA_MAXN 128
@@ -90,7 +96,10 @@ __device__ __forceinline__ void ba_point_plus(const double X[3], const BaFrame& 
   if (nd == 0.0) { Xn[0] = X[0]; Xn[1] = X[1]; Xn[2] = X[2]; return; }
   const double sc = sin(0.5 * nd) / nd;
   double y[4] = {d[0] * sc, d[1] * sc, d[2] * sc, cos(0.5 * nd)};
-  const double vy = f.beta * (f.v[0] * y[0] + f.v[1] * y[1] + f.v[2] * y[2] + f.v[3] * y[3]);
+  double vy = f.beta * (f.v[0] * y[0] + f.v[1] * y[1] + f.v[2] * y[2] + f.v[3] * y[3]);
+  // vy is a rounded product in all four lines below: where the compiler knows v[3] = 1 it would otherwise contract
+  // y[3] - beta * (...) into one fma, and whether it knows depends on the code around the call (a value barrier, no code)
+  asm volatile("" : "+v"(vy));
 #pragma unroll
   for (int c = 0; c < 4; ++c) y[c] -= f.v[c] * vy;     // |h| = 1
   Xn[0] = y[0] / y[3]; Xn[1] = y[1] / y[3]; Xn[2] = y[2] / y[3];
@@ -133,86 +142,6 @@ __device__ __forceinline__ bool ba_project(const double* pose, const double* in4
   return true;
 }
 
-// deterministic block reduction of `n` values per thread (fixed tree through LDS); result valid in thread 0
-template <int NT>
-__device__ __forceinline__ double ba_block_sum(double v, double* red, int tid) {
-  v = wave_sum_f64(v);
-  __syncthreads();
-  if ((tid & 63) == 0) red[tid >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-  if (tid == 0)
-    for (int w = 0; w < NT / 64; ++w) s += red[w];
-  return s;
-}
-
-// ---- pass 1: per track: C_i = sum w Jp^T Jp, g_i = sum w Jp^T r, cost_i = sum rho   (thread per track)
-__global__ __launch_bounds__(256) void ba_linearize_points(BaProblem pb, const double* __restrict__ pts,
-                                                           const double* __restrict__ poses, double* __restrict__ Cblk,
-                                                           double* __restrict__ gp, double* __restrict__ cost_part,
-                                                           const BaState* st) {
-  __shared__ double red[4];
-  const int N = pb.N, K = pb.K, tid = threadIdx.x;
-  const long i = (long)blockIdx.x * 256 + tid;
-  double cost = 0.0;
-  if (st->done == 0.0 && i < (long)N * K) {
-    const int s = (int)(i / K), k = (int)(i - (long)s * K);
-    const double X[3] = {pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]};
-    double C[6] = {0, 0, 0, 0, 0, 0}, g[3] = {0, 0, 0};
-    BaFrame fr;
-    if (pb.homogeneous) ba_point_frame(X, fr);
-    for (int t = 0; t < N; ++t) {
-      const long o = ((long)s * N + t) * K + k;
-      if (!pb.valid[o]) continue;
-      double r[2], Jc[2][6], Jp[2][3];
-      if (!ba_project(poses + 12 * t, pb.intr + 4 * t, X, (double)pb.uv[2 * o], (double)pb.uv[2 * o + 1], r, Jc, Jp,
-                      pb.homogeneous ? fr.T : nullptr))
-        continue;
-      double w;
-      cost += huber_rho(r[0] * r[0] + r[1] * r[1], pb.huber, w);
-      C[0] += w * (Jp[0][0] * Jp[0][0] + Jp[1][0] * Jp[1][0]);
-      C[1] += w * (Jp[0][0] * Jp[0][1] + Jp[1][0] * Jp[1][1]);
-      C[2] += w * (Jp[0][0] * Jp[0][2] + Jp[1][0] * Jp[1][2]);
-      C[3] += w * (Jp[0][1] * Jp[0][1] + Jp[1][1] * Jp[1][1]);
-      C[4] += w * (Jp[0][1] * Jp[0][2] + Jp[1][1] * Jp[1][2]);
-      C[5] += w * (Jp[0][2] * Jp[0][2] + Jp[1][2] * Jp[1][2]);
-#pragma unroll
-      for (int c = 0; c < 3; ++c) g[c] += w * (Jp[0][c] * r[0] + Jp[1][c] * r[1]);
-    }
-#pragma unroll
-    for (int c = 0; c < 6; ++c) Cblk[6 * i + c] = C[c];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) gp[3 * i + c] = g[c];
-  }
-  const double tot = ba_block_sum<256>(cost, red, tid);
-  if (tid == 0) cost_part[blockIdx.x] = 0.5 * tot;
-}
-
-// cost only (candidate parameters)
-__global__ __launch_bounds__(256) void ba_cost_points(BaProblem pb, const double* __restrict__ pts,
-                                                      const double* __restrict__ poses, double* __restrict__ cost_part,
-                                                      const BaState* st) {
-  __shared__ double red[4];
-  const int N = pb.N, K = pb.K, tid = threadIdx.x;
-  const long i = (long)blockIdx.x * 256 + tid;
-  double cost = 0.0;
-  if (st->done == 0.0 && i < (long)N * K) {
-    const int s = (int)(i / K), k = (int)(i - (long)s * K);
-    const double X[3] = {pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]};
-    for (int t = 0; t < N; ++t) {
-      const long o = ((long)s * N + t) * K + k;
-      if (!pb.valid[o]) continue;
-      double r[2], Jc[2][6], Jp[2][3];
-      if (!ba_project(poses + 12 * t, pb.intr + 4 * t, X, (double)pb.uv[2 * o], (double)pb.uv[2 * o + 1], r, Jc, Jp))
-        continue;
-      double w;
-      cost += huber_rho(r[0] * r[0] + r[1] * r[1], pb.huber, w);
-    }
-  }
-  const double tot = ba_block_sum<256>(cost, red, tid);
-  if (tid == 0) cost_part[blockIdx.x] = 0.5 * tot;
-}
-
 // log map of a rotation matrix (row-major), angle-axis vector
 __device__ __forceinline__ void ba_log_so3(const double* R, double w[3]) {
   const double tr = R[0] + R[4] + R[8];
@@ -226,18 +155,67 @@ __device__ __forceinline__ void ba_log_so3(const double* R, double w[3]) {
   w[0] = f * vx; w[1] = f * vy; w[2] = f * vz;
 }
 
-// ---- inverse depth (the reference's --use-inverse-depth: reconstruction.InitializeInverseDepth() +
-// ba_options.use_inverse_depth_parametrization = True, utils/chunk_reconstruction.py:187-204,
-// utils/reconstruction_alignment.py:147-152).  A track (s, k) is ONE parameter, the inverse depth rho along the bearing b
-// of its keypoint in its reference view s (the first view that observed it: its own frame):
-//     X = C_s + R_s^T (b / rho),   b = ((u - cx) / fx, (v - cy) / fy, 1)
-// so every observation by another camera t depends on (pose_t, pose_s, rho) and the reference view's own observation is
-// met by construction (no residual).  The stored points stay Euclidean and ON their rays (snapped at the start, every
-// candidate built from the candidate pose and rho), so a kernel derives p_s = R_s (X - C_s) and rho = 1 / p_s.z from
-// them.  Chain rule through X: dX/dC_s = I, dX/dw_s = R_s^T [p_s]x (R_s <- exp([w]x) R_s), dX/drho = -(X - C_s) / rho.
-// The linear algebra reuses the Euclidean kernels with the scalar embedded in their 3 x 3 point blocks
-// (C_i = diag(c, 1, 1), g_i = (g, 0, 0), E_it = [e | 0 | 0]); what is new are the reference camera's entries in a track's
-// E row, its diagonal terms, and the direct camera-camera blocks w Ja^T Jt of the normal equations (ba_id_cross_blocks).
+// deterministic block reduction of `n` values per thread (fixed tree through LDS); result valid in thread 0
+template <int NT>
+__device__ __forceinline__ double ba_block_sum(double v, double* red, int tid) {
+  v = wave_sum_f64(v);
+  __syncthreads();
+  if ((tid & 63) == 0) red[tid >> 6] = v;
+  __syncthreads();
+  double s = 0.0;
+  if (tid == 0)
+    for (int w = 0; w < NT / 64; ++w) s += red[w];
+  return s;
+}
+
+// damped inverse of a track's 3x3 block: (C + D)^-1 with D = clamp(diag(C)) / radius; returns false if singular
+__device__ __forceinline__ bool ba_point_inverse(const double* C6, double radius, double Ci[6], double D[3]) {
+  double c00 = C6[0], c01 = C6[1], c02 = C6[2], c11 = C6[3], c12 = C6[4], c22 = C6[5];
+  D[0] = fmin(fmax(c00, 1e-6), 1e32) / radius;
+  D[1] = fmin(fmax(c11, 1e-6), 1e32) / radius;
+  D[2] = fmin(fmax(c22, 1e-6), 1e32) / radius;
+  c00 += D[0]; c11 += D[1]; c22 += D[2];
+  const double m0 = c11 * c22 - c12 * c12, m1 = c02 * c12 - c01 * c22, m2 = c01 * c12 - c02 * c11;
+  const double det = c00 * m0 + c01 * m1 + c02 * m2;
+  if (!(fabs(det) > 1e-300)) return false;
+  const double id = 1.0 / det;
+  Ci[0] = m0 * id; Ci[1] = m1 * id; Ci[2] = m2 * id;
+  Ci[3] = (c00 * c22 - c02 * c02) * id; Ci[4] = (c01 * c02 - c00 * c12) * id; Ci[5] = (c00 * c11 - c01 * c01) * id;
+  return true;
+}
+
+// v C for a symmetric 3 x 3 block packed as (00, 01, 02, 11, 12, 22): a row of E against a track's damped inverse, or that
+// inverse against the track's right-hand side.  The fused multiply-adds are spelled out: under -ffp-contract=fast the
+// compiler chooses which product of a sum stays a rounded product by the order it met the operands in, which moved
+// with the code around this expression; this is the form all three sites had.
+__device__ __forceinline__ void ba_sym3_mul(const double* C, double v0, double v1, double v2, double out[3]) {
+  out[0] = fma(v2, C[2], fma(v0, C[0], v1 * C[1]));
+  out[1] = fma(v2, C[4], fma(v0, C[1], v1 * C[3]));
+  out[2] = fma(v2, C[5], fma(v0, C[2], v1 * C[4]));
+}
+
+// one entry of a weighted normal-equation block: w (column p of Ja) . (column c of Jb), resp. . r, over the two residual rows
+template <int NA, int NB>
+__device__ __forceinline__ double ba_wjj(double w, const double (&Ja)[2][NA], int p, const double (&Jb)[2][NB], int c) {
+  return w * (Ja[0][p] * Jb[0][c] + Ja[1][p] * Jb[1][c]);
+}
+template <int NA>
+__device__ __forceinline__ double ba_wjr(double w, const double (&Ja)[2][NA], int p, const double r[2]) {
+  return w * (Ja[0][p] * r[0] + Ja[1][p] * r[1]);
+}
+// a camera's share of one observation: a[0..20] += w J^T J (packed upper triangle, row by row), a[21..26] += w J^T r
+__device__ __forceinline__ void ba_accumulate27(double a[27], double w, const double (&J)[2][6], const double r[2]) {
+  int q = 0;
+#pragma unroll
+  for (int p = 0; p < 6; ++p)
+#pragma unroll
+    for (int c = p; c < 6; ++c) a[q++] += ba_wjj(w, J, p, J, c);
+#pragma unroll
+  for (int p = 0; p < 6; ++p) a[21 + p] += ba_wjr(w, J, p, r);
+}
+
+// inverse depth (see that section): the chain rule through X = C_s + R_s^T (b / rho) for an observation of a track whose
+// reference view is camera s: Ja = d r / d pose_s (6 columns) and jr = d r / d rho from the point columns Jp
 __device__ __forceinline__ void ba_id_chain(const double* pose_s, const double X[3], const double Jp[2][3], double Ja[2][6],
                                             double jr[2]) {
   const double* R = pose_s;
@@ -265,7 +243,112 @@ __device__ __forceinline__ void ba_id_chain(const double* pose_s, const double X
   }
 }
 
-// ---- pass 2: per camera t: B_t = sum w Jc^T Jc (21 values), g_t = sum w Jc^T r, + pose priors.  One WG per camera.
+// observation o of a track at X by camera t, pixel uv[2 o]: residual, Jacobians (ba_project), Huber weight w and robust
+// cost rho.  Every residual / Jacobian site of the file goes through here.  Returns false when the point is behind.
+__device__ __forceinline__ bool ba_observe(const BaProblem& pb, const float* uv, const double* poses, int t, long o,
+                                           const double X[3], const double* T, double r[2], double Jc[2][6],
+                                           double Jp[2][3], double& w, double& rho) {
+  if (!ba_project(poses + 12 * t, pb.intr + 4 * t, X, (double)uv[2 * o], (double)uv[2 * o + 1], r, Jc, Jp, T)) return false;
+  rho = huber_rho(r[0] * r[0] + r[1] * r[1], pb.huber, w);
+  return true;
+}
+
+// THE per-track observation walk: cameras t = 0 .. N-1 of track (s, k) at X in ascending order, observation
+// o = (s N + t) K + k.  visit(t, o, r, Jc, Jp, w) is called for every observation that exists and lies in front of its
+// camera; missed(t, behind) for every other camera (behind = true: the observation exists and the point is not in front).
+//   T         the track's frame (ba_point_frame) or null: Jp then refers to the tangent step
+//   by_ref    inverse depth: no residual in the reference view t == s, none at all without a reference observation
+//   go        null, or a flag a callable clears to end the walk before the next camera
+// Returns the sum of the robust costs of the visited observations (twice the track's share of the objective).
+struct BaIgnoreMiss { __device__ __forceinline__ void operator()(int, bool, bool) const {} };
+template <class Visit, class Missed = BaIgnoreMiss>
+__device__ __forceinline__ double ba_walk_track(const BaProblem& pb, const double* poses, int s, int k, const double X[3],
+                                                const double* T, bool by_ref, Visit&& visit, Missed&& missed = Missed(),
+                                                const bool* go = nullptr) {
+  const int N = pb.N, K = pb.K;
+  const bool dead = by_ref && !pb.valid[((long)s * N + s) * K + k];
+  double cost = 0.0;
+  for (int t = 0; t < N && (!go || *go); ++t) {
+    const long o = ((long)s * N + t) * K + k;
+    const bool seen = !dead && !(by_ref && t == s) && pb.valid[o];
+    bool hit = false;
+    if (seen) {
+      double r[2], Jc[2][6], Jp[2][3], w, rho;
+      hit = ba_observe(pb, pb.uv, poses, t, o, X, T, r, Jc, Jp, w, rho);
+      if (hit) cost += rho, visit(t, o, r, Jc, Jp, w);
+    }
+    missed(t, seen, hit);
+  }
+  return cost;
+}
+
+// ------------------------------------------------------------------------------ Euclidean / homogeneous passes
+// ---- pass 1: per track: C_i = sum w Jp^T Jp, g_i = sum w Jp^T r, cost_i = sum rho   (thread per track)
+__global__ __launch_bounds__(256) void ba_linearize_points(BaProblem pb, const double* __restrict__ pts,
+                                                           const double* __restrict__ poses, double* __restrict__ Cblk,
+                                                           double* __restrict__ gp, double* __restrict__ cost_part,
+                                                           const BaState* st) {
+  __shared__ double red[4];
+  const int N = pb.N, K = pb.K, tid = threadIdx.x;
+  const long i = (long)blockIdx.x * 256 + tid;
+  double cost = 0.0;
+  if (st->done == 0.0 && i < (long)N * K) {
+    const int s = (int)(i / K), k = (int)(i - (long)s * K);
+    const double X[3] = {pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]};
+    double C[6] = {0, 0, 0, 0, 0, 0}, g[3] = {0, 0, 0};
+    BaFrame fr;
+    if (pb.homogeneous) ba_point_frame(X, fr);
+    cost = ba_walk_track(pb, poses, s, k, X, pb.homogeneous ? fr.T : nullptr, false,
+                         [&](int, long, auto& r, auto&, auto& Jp, double w) {
+                           int q = 0;
+#pragma unroll
+                           for (int p = 0; p < 3; ++p)
+#pragma unroll
+                             for (int c = p; c < 3; ++c) C[q++] += ba_wjj(w, Jp, p, Jp, c);
+#pragma unroll
+                           for (int c = 0; c < 3; ++c) g[c] += ba_wjr(w, Jp, c, r);
+                         });
+#pragma unroll
+    for (int c = 0; c < 6; ++c) Cblk[6 * i + c] = C[c];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) gp[3 * i + c] = g[c];
+  }
+  const double tot = ba_block_sum<256>(cost, red, tid);
+  if (tid == 0) cost_part[blockIdx.x] = 0.5 * tot;
+}
+
+// cost only (start and candidate parameters), all three forms.  Inverse depth leaves the reference-view observations
+// out: they are met by construction, but only up to rounding, and without them the cost is exactly the oracle's sum.
+__global__ __launch_bounds__(256) void ba_cost_points(BaProblem pb, const double* __restrict__ pts,
+                                                      const double* __restrict__ poses, double* __restrict__ cost_part,
+                                                      const BaState* st) {
+  __shared__ double red[4];
+  const int N = pb.N, K = pb.K, tid = threadIdx.x;
+  const long i = (long)blockIdx.x * 256 + tid;
+  double cost = 0.0;
+  if (st->done == 0.0 && i < (long)N * K) {
+    const int s = (int)(i / K), k = (int)(i - (long)s * K);
+    const double X[3] = {pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]};
+    cost = ba_walk_track(pb, poses, s, k, X, nullptr, pb.invdepth != 0, [](int, long, auto&, auto&, auto&, double) {});
+  }
+  const double tot = ba_block_sum<256>(cost, red, tid);
+  if (tid == 0) cost_part[blockIdx.x] = 0.5 * tot;
+}
+
+// pose prior of camera t (the caller has tested prior_flag[t]): rotation residual w3 = log(R R0^T), d w3 / dw ~ I, and
+// position residual dc = C - C0, both before their square-root information sqrt_info_rot / sqrt_info_pos
+__device__ __forceinline__ void ba_prior_residual(const BaProblem& pb, const double* poses, int t, double w3[3], double dc[3]) {
+  const double* R = poses + 12 * t;
+  const double* R0 = pb.prior_R + 9 * t;
+  double E[9];
+  for (int p = 0; p < 3; ++p)
+    for (int c = 0; c < 3; ++c) E[3 * p + c] = R[3 * p] * R0[3 * c] + R[3 * p + 1] * R0[3 * c + 1] + R[3 * p + 2] * R0[3 * c + 2];
+  ba_log_so3(E, w3);
+  for (int p = 0; p < 3; ++p) dc[p] = poses[12 * t + 9 + p] - pb.prior_C[3 * t + p];
+}
+
+// ---- pass 2: per camera t: B_t = sum w Jc^T Jc (21 values), g_t = sum w Jc^T r, + pose priors.  One WG per camera,
+// threads strided over the tracks (camera-major: not the track walk).
 __global__ __launch_bounds__(256) void ba_camera_blocks(BaProblem pb, const double* __restrict__ pts,
                                                         const double* __restrict__ poses, double* __restrict__ Bblk,
                                                         double* __restrict__ gc, double* __restrict__ prior_cost,
@@ -283,17 +366,9 @@ __global__ __launch_bounds__(256) void ba_camera_blocks(BaProblem pb, const doub
     if (!pb.valid[o]) continue;
     if (pb.invdepth && s == t) continue;      // a track's reference-view observation carries no residual
     const double X[3] = {pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]};
-    double r[2], Jc[2][6], Jp[2][3];
-    if (!ba_project(poses + 12 * t, pb.intr + 4 * t, X, (double)pb.uv[2 * o], (double)pb.uv[2 * o + 1], r, Jc, Jp)) continue;
-    double w;
-    huber_rho(r[0] * r[0] + r[1] * r[1], pb.huber, w);
-    int q = 0;
-#pragma unroll
-    for (int p = 0; p < 6; ++p)
-#pragma unroll
-      for (int c = p; c < 6; ++c) a[q++] += w * (Jc[0][p] * Jc[0][c] + Jc[1][p] * Jc[1][c]);
-#pragma unroll
-    for (int p = 0; p < 6; ++p) a[21 + p] += w * (Jc[0][p] * r[0] + Jc[1][p] * r[1]);
+    double r[2], Jc[2][6], Jp[2][3], w, rho;
+    if (!ba_observe(pb, pb.uv, poses, t, o, X, nullptr, r, Jc, Jp, w, rho)) continue;
+    ba_accumulate27(a, w, Jc, r);
   }
   if (pb.invdepth) {      // camera t as the REFERENCE view of its own tracks: every other observation of them moves with it
     for (long e = tid; e < (long)K * N; e += 256) {
@@ -303,18 +378,10 @@ __global__ __launch_bounds__(256) void ba_camera_blocks(BaProblem pb, const doub
       const long o = ((long)t * N + t2) * K + k;
       if (!pb.valid[o] || !pb.valid[((long)t * N + t) * K + k]) continue;
       const double X[3] = {pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]};
-      double r[2], Jc[2][6], Jp[2][3], Ja[2][6], jr[2];
-      if (!ba_project(poses + 12 * t2, pb.intr + 4 * t2, X, (double)pb.uv[2 * o], (double)pb.uv[2 * o + 1], r, Jc, Jp)) continue;
+      double r[2], Jc[2][6], Jp[2][3], Ja[2][6], jr[2], w, rho;
+      if (!ba_observe(pb, pb.uv, poses, t2, o, X, nullptr, r, Jc, Jp, w, rho)) continue;
       ba_id_chain(poses + 12 * t, X, Jp, Ja, jr);
-      double w;
-      huber_rho(r[0] * r[0] + r[1] * r[1], pb.huber, w);
-      int q = 0;
-#pragma unroll
-      for (int p = 0; p < 6; ++p)
-#pragma unroll
-        for (int c = p; c < 6; ++c) a[q++] += w * (Ja[0][p] * Ja[0][c] + Ja[1][p] * Ja[1][c]);
-#pragma unroll
-      for (int p = 0; p < 6; ++p) a[21 + p] += w * (Ja[0][p] * r[0] + Ja[1][p] * r[1]);
+      ba_accumulate27(a, w, Ja, r);
     }
   }
   for (int c = 0; c < 27; ++c) {
@@ -324,25 +391,18 @@ __global__ __launch_bounds__(256) void ba_camera_blocks(BaProblem pb, const doub
   __syncthreads();
   if (tid == 0) {
     double pc = 0.0;
-    if (pb.prior_flag && pb.prior_flag[t]) {
-      // orientation prior: r = sr * log(R R0^T), dr/dw ~ I;  position prior: r = sp * (C - C0)
-      const double* R = poses + 12 * t;
-      const double* R0 = pb.prior_R + 9 * t;
-      double E[9];
-      for (int p = 0; p < 3; ++p)
-        for (int c = 0; c < 3; ++c) E[3 * p + c] = R[3 * p] * R0[3 * c] + R[3 * p + 1] * R0[3 * c + 1] + R[3 * p + 2] * R0[3 * c + 2];
-      double w3[3];
-      ba_log_so3(E, w3);
+    if (pb.prior_flag && pb.prior_flag[t]) {      // r = sr w3 and r = sp dc: sr^2 I, sp^2 I on the diagonal
+      double w3[3], dc[3];
+      ba_prior_residual(pb, poses, t, w3, dc);
       const double sr2 = pb.sqrt_info_rot * pb.sqrt_info_rot, sp2 = pb.sqrt_info_pos * pb.sqrt_info_pos;
       const int dq[6] = {0, 6, 11, 15, 18, 20};   // packed index of the diagonal entries (p, p)
       for (int p = 0; p < 3; ++p) {
         acc[dq[p]] += sr2;
         acc[21 + p] += sr2 * w3[p];
         pc += 0.5 * sr2 * w3[p] * w3[p];
-        const double dcp = poses[12 * t + 9 + p] - pb.prior_C[3 * t + p];
         acc[dq[3 + p]] += sp2;
-        acc[24 + p] += sp2 * dcp;
-        pc += 0.5 * sp2 * dcp * dcp;
+        acc[24 + p] += sp2 * dc[p];
+        pc += 0.5 * sp2 * dc[p] * dc[p];
       }
     }
     for (int c = 0; c < 21; ++c) Bblk[21 * t + c] = acc[c];
@@ -358,35 +418,12 @@ __global__ void ba_prior_cost(BaProblem pb, const double* __restrict__ poses, do
   if (st->done != 0.0 || t >= pb.N) return;
   double pc = 0.0;
   if (pb.prior_flag && pb.prior_flag[t]) {
-    const double* R = poses + 12 * t;
-    const double* R0 = pb.prior_R + 9 * t;
-    double E[9], w3[3];
-    for (int p = 0; p < 3; ++p)
-      for (int c = 0; c < 3; ++c) E[3 * p + c] = R[3 * p] * R0[3 * c] + R[3 * p + 1] * R0[3 * c + 1] + R[3 * p + 2] * R0[3 * c + 2];
-    ba_log_so3(E, w3);
+    double w3[3], dc[3];
+    ba_prior_residual(pb, poses, t, w3, dc);
     const double sr2 = pb.sqrt_info_rot * pb.sqrt_info_rot, sp2 = pb.sqrt_info_pos * pb.sqrt_info_pos;
-    for (int p = 0; p < 3; ++p) {
-      const double dcp = poses[12 * t + 9 + p] - pb.prior_C[3 * t + p];
-      pc += 0.5 * sr2 * w3[p] * w3[p] + 0.5 * sp2 * dcp * dcp;
-    }
+    for (int p = 0; p < 3; ++p) pc += 0.5 * sr2 * w3[p] * w3[p] + 0.5 * sp2 * dc[p] * dc[p];
   }
   prior_cost[t] = pc;
-}
-
-// damped inverse of a track's 3x3 block: (C + D)^-1 with D = clamp(diag(C)) / radius; returns false if singular
-__device__ __forceinline__ bool ba_point_inverse(const double* C6, double radius, double Ci[6], double D[3]) {
-  double c00 = C6[0], c01 = C6[1], c02 = C6[2], c11 = C6[3], c12 = C6[4], c22 = C6[5];
-  D[0] = fmin(fmax(c00, 1e-6), 1e32) / radius;
-  D[1] = fmin(fmax(c11, 1e-6), 1e32) / radius;
-  D[2] = fmin(fmax(c22, 1e-6), 1e32) / radius;
-  c00 += D[0]; c11 += D[1]; c22 += D[2];
-  const double m0 = c11 * c22 - c12 * c12, m1 = c02 * c12 - c01 * c22, m2 = c01 * c12 - c02 * c11;
-  const double det = c00 * m0 + c01 * m1 + c02 * m2;
-  if (!(fabs(det) > 1e-300)) return false;
-  const double id = 1.0 / det;
-  Ci[0] = m0 * id; Ci[1] = m1 * id; Ci[2] = m2 * id;
-  Ci[3] = (c00 * c22 - c02 * c02) * id; Ci[4] = (c01 * c02 - c00 * c12) * id; Ci[5] = (c00 * c11 - c01 * c01) * id;
-  return true;
 }
 
 // ---- pass 3a: per observation (track i, camera t) the 6 x 3 block E_it = w Jc^T Jp of the normal equations, once per
@@ -403,25 +440,235 @@ __global__ __launch_bounds__(256) void ba_obs_blocks(BaProblem pb, const double*
   uint8_t good = 0;
   if (pb.validT[o]) {
     const double X[3] = {pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]};
-    double r[2], Jc[2][6], Jp[2][3], w;
+    double r[2], Jc[2][6], Jp[2][3], w, rho;
     BaFrame fr;
     if (pb.homogeneous) ba_point_frame(X, fr);
-    if (ba_project(poses + 12 * t, pb.intr + 4 * t, X, (double)pb.uvT[2 * o], (double)pb.uvT[2 * o + 1], r, Jc, Jp,
-                   pb.homogeneous ? fr.T : nullptr)) {
-      huber_rho(r[0] * r[0] + r[1] * r[1], pb.huber, w);
+    if (ba_observe(pb, pb.uvT, poses, t, o, X, pb.homogeneous ? fr.T : nullptr, r, Jc, Jp, w, rho)) {
       double* E = Eblk + 18 * o;
 #pragma unroll
-      for (int a = 0; a < 6; ++a) {
-        E[3 * a + 0] = w * (Jc[0][a] * Jp[0][0] + Jc[1][a] * Jp[1][0]);
-        E[3 * a + 1] = w * (Jc[0][a] * Jp[0][1] + Jc[1][a] * Jp[1][1]);
-        E[3 * a + 2] = w * (Jc[0][a] * Jp[0][2] + Jc[1][a] * Jp[1][2]);
-      }
+      for (int a = 0; a < 6; ++a)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) E[3 * a + c] = ba_wjj(w, Jc, a, Jp, c);
       good = 1;
     }
   }
   ok[o] = good;
 }
 
+// ---- pass 5: back-substitution for the points and candidate parameters; model decrease partials
+__global__ __launch_bounds__(256) void ba_backsub_points(BaProblem pb, const double* __restrict__ pts,
+                                                         const double* __restrict__ poses,
+                                                         const double* __restrict__ Cblk, const double* __restrict__ gp,
+                                                         const double* __restrict__ dcam, double* __restrict__ pts_new,
+                                                         double* __restrict__ model_part, const BaState* st) {
+  __shared__ double red[4];
+  const int N = pb.N, K = pb.K, tid = threadIdx.x;
+  const long i = (long)blockIdx.x * 256 + tid;
+  double model = 0.0;
+  if (st->done == 0.0 && i < (long)N * K) {
+    const int s = (int)(i / K), k = (int)(i - (long)s * K);
+    const double X[3] = {pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]};
+    double Ci[6], D[3];
+    double dx[3] = {0, 0, 0};
+    BaFrame fr;
+    if (pb.homogeneous) ba_point_frame(X, fr);
+    if (st->chol_fail == 0.0 && ba_point_inverse(Cblk + 6 * i, st->radius, Ci, D)) {
+      double v[3] = {gp[3 * i], gp[3 * i + 1], gp[3 * i + 2]};   // g_i + sum_t E_it^T dc_t
+      ba_walk_track(pb, poses, s, k, X, pb.homogeneous ? fr.T : nullptr, false,
+                    [&](int t, long, auto&, auto& Jc, auto& Jp, double w) {
+                      double jd[2] = {0.0, 0.0};      // Jc dc
+#pragma unroll
+                      for (int a = 0; a < 6; ++a) { jd[0] += Jc[0][a] * dcam[6 * t + a]; jd[1] += Jc[1][a] * dcam[6 * t + a]; }
+#pragma unroll
+                      for (int c = 0; c < 3; ++c) v[c] += ba_wjr(w, Jp, c, jd);
+                    });
+      ba_sym3_mul(Ci, v[0], v[1], v[2], dx);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) dx[c] = -dx[c];
+      // model decrease = -1/2 g^T d + 1/2 d^T D d
+#pragma unroll
+      for (int c = 0; c < 3; ++c) model += -0.5 * gp[3 * i + c] * dx[c] + 0.5 * D[c] * dx[c] * dx[c];
+    }
+    if (pb.homogeneous) {
+      double Xn[3];
+      ba_point_plus(X, fr, dx, Xn);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) pts_new[3 * i + c] = Xn[c];
+    } else {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) pts_new[3 * i + c] = X[c] + dx[c];
+    }
+  }
+  const double tot = ba_block_sum<256>(model, red, tid);
+  if (tid == 0) model_part[blockIdx.x] = tot;
+}
+
+// ------------------------------------------------------------------------------------------------ inverse depth
+// (the reference's --use-inverse-depth: reconstruction.InitializeInverseDepth() +
+// ba_options.use_inverse_depth_parametrization = True, utils/chunk_reconstruction.py:187-204,
+// utils/reconstruction_alignment.py:147-152).  A track (s, k) is ONE parameter, the inverse depth rho along the bearing b
+// of its keypoint in its reference view s (the first view that observed it: its own frame):
+//     X = C_s + R_s^T (b / rho),   b = ((u - cx) / fx, (v - cy) / fy, 1)
+// so every observation by another camera t depends on (pose_t, pose_s, rho) and the reference view's own observation is
+// met by construction (no residual).  The stored points stay Euclidean and ON their rays (snapped at the start, every
+// candidate built from the candidate pose and rho), so a kernel derives p_s = R_s (X - C_s) and rho = 1 / p_s.z from
+// them.  Chain rule through X: dX/dC_s = I, dX/dw_s = R_s^T [p_s]x (R_s <- exp([w]x) R_s), dX/drho = -(X - C_s) / rho.
+// The linear algebra reuses the Euclidean kernels with the scalar embedded in their 3 x 3 point blocks
+// (C_i = diag(c, 1, 1), g_i = (g, 0, 0), E_it = [e | 0 | 0]); what is new are the reference camera's entries in a track's
+// E row, its diagonal terms, and the direct camera-camera blocks w Ja^T Jt of the normal equations (ba_id_cross_blocks).
+__device__ __forceinline__ void ba_id_bearing(const BaProblem& pb, int s, int k, double b[3]) {
+  const long o = ((long)s * pb.N + s) * pb.K + k;
+  const double* in4 = pb.intr + 4 * s;
+  b[0] = ((double)pb.uv[2 * o] - in4[2]) / in4[0];
+  b[1] = ((double)pb.uv[2 * o + 1] - in4[3]) / in4[1];
+  b[2] = 1.0;
+}
+// X = C_s + R_s^T (b / rho): rho == nullptr -> the depth of pts in the reference view (InitializeInverseDepth: snap)
+__global__ __launch_bounds__(256) void ba_id_points(BaProblem pb, const double* __restrict__ poses,
+                                                    const double* __restrict__ rho, const double* __restrict__ pts_in,
+                                                    double* __restrict__ pts_out, const BaState* st) {
+  const int N = pb.N, K = pb.K;
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if ((st && st->done != 0.0) || i >= (long)N * K) return;
+  const int s = (int)(i / K), k = (int)(i - (long)s * K);
+  const double* P = poses + 12 * s;
+  if (!pb.valid[((long)s * N + s) * K + k]) {       // no reference observation: the track is left alone
+    if (pts_in != pts_out)
+      for (int c = 0; c < 3; ++c) pts_out[3 * i + c] = pts_in[3 * i + c];
+    return;
+  }
+  double b[3];
+  ba_id_bearing(pb, s, k, b);
+  double z;
+  if (rho) z = 1.0 / rho[i];
+  else z = P[6] * (pts_in[3 * i] - P[9]) + P[7] * (pts_in[3 * i + 1] - P[10]) + P[8] * (pts_in[3 * i + 2] - P[11]);
+  const double p[3] = {b[0] * z, b[1] * z, z};
+#pragma unroll
+  for (int c = 0; c < 3; ++c) pts_out[3 * i + c] = P[9 + c] + P[c] * p[0] + P[3 + c] * p[1] + P[6 + c] * p[2];
+}
+
+// per track: c = sum w jr.jr, g = sum w jr.r, cost, the E row (observing cameras + the reference camera), ok flags
+__global__ __launch_bounds__(256) void ba_id_linearize(BaProblem pb, const double* __restrict__ pts,
+                                                       const double* __restrict__ poses, double* __restrict__ Cblk,
+                                                       double* __restrict__ gp, double* __restrict__ Eblk,
+                                                       uint8_t* __restrict__ ok, double* __restrict__ cost_part,
+                                                       const BaState* st) {
+  __shared__ double red[4];
+  const int N = pb.N, K = pb.K, tid = threadIdx.x;
+  const long i = (long)blockIdx.x * 256 + tid;
+  double cost = 0.0;
+  if (st->done == 0.0 && i < (long)N * K) {
+    const int s = (int)(i / K), k = (int)(i - (long)s * K);
+    const double X[3] = {pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]};
+    double c = 0.0, g = 0.0, Ea[6] = {0, 0, 0, 0, 0, 0};
+    bool any = false;
+    cost = ba_walk_track(pb, poses, s, k, X, nullptr, true,
+                         [&](int t, long, auto& r, auto& Jc, auto& Jp, double w) {
+                           double Ja[2][6], jr[2];
+                           ba_id_chain(poses + 12 * s, X, Jp, Ja, jr);
+                           c += w * (jr[0] * jr[0] + jr[1] * jr[1]);
+                           g += w * (jr[0] * r[0] + jr[1] * r[1]);
+                           double* E = Eblk + 18 * (i * N + t);
+#pragma unroll
+                           for (int a = 0; a < 6; ++a) {
+                             E[3 * a] = ba_wjr(w, Jc, a, jr);
+                             E[3 * a + 1] = 0.0;
+                             E[3 * a + 2] = 0.0;
+                             Ea[a] += ba_wjr(w, Ja, a, jr);
+                           }
+                           any = true;
+                         },
+                         [&](int t, bool, bool hit) { if (t != s) ok[i * N + t] = hit; });
+    {
+      double* E = Eblk + 18 * (i * N + s);
+#pragma unroll
+      for (int a = 0; a < 6; ++a) { E[3 * a] = Ea[a]; E[3 * a + 1] = 0.0; E[3 * a + 2] = 0.0; }
+      ok[i * N + s] = any ? 1 : 0;
+    }
+    Cblk[6 * i] = c; Cblk[6 * i + 1] = 0.0; Cblk[6 * i + 2] = 0.0; Cblk[6 * i + 3] = 1.0; Cblk[6 * i + 4] = 0.0; Cblk[6 * i + 5] = 1.0;
+    gp[3 * i] = g; gp[3 * i + 1] = 0.0; gp[3 * i + 2] = 0.0;
+  }
+  const double tot = ba_block_sum<256>(cost, red, tid);
+  if (tid == 0) cost_part[blockIdx.x] = 0.5 * tot;
+}
+
+// direct camera-camera blocks: X[s][t] = sum_k w Ja(s, k, t)^T Jc(s, k, t)  (6 x 6; rows: reference camera s).  One wave
+// per (s, t), lanes strided over the keypoints (camera-major: not the track walk).
+__global__ __launch_bounds__(64) void ba_id_cross_blocks(BaProblem pb, const double* __restrict__ pts,
+                                                         const double* __restrict__ poses, double* __restrict__ Xblk,
+                                                         const BaState* st) {
+  const int N = pb.N, K = pb.K, s = blockIdx.y, t = blockIdx.x, lane = threadIdx.x;
+  if (st->done != 0.0) return;
+  double a[36];
+#pragma unroll
+  for (int c = 0; c < 36; ++c) a[c] = 0.0;
+  if (s != t)
+    for (int k = lane; k < K; k += 64) {
+      const long i = (long)s * K + k, o = ((long)s * N + t) * K + k;
+      if (!pb.valid[o] || !pb.valid[((long)s * N + s) * K + k]) continue;
+      const double X[3] = {pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]};
+      double r[2], Jc[2][6], Jp[2][3], Ja[2][6], jr[2], w, rho;
+      if (!ba_observe(pb, pb.uv, poses, t, o, X, nullptr, r, Jc, Jp, w, rho)) continue;
+      ba_id_chain(poses + 12 * s, X, Jp, Ja, jr);
+#pragma unroll
+      for (int p = 0; p < 6; ++p)
+#pragma unroll
+        for (int c = 0; c < 6; ++c) a[6 * p + c] += ba_wjj(w, Ja, p, Jc, c);
+    }
+#pragma unroll
+  for (int c = 0; c < 36; ++c) {
+    const double v = wave_sum_f64(a[c]);
+    if (lane == 0) Xblk[((long)s * N + t) * 36 + c] = v;
+  }
+}
+// S (lower triangle) += the cross blocks: H[tr][tc] = X[tr][tc] + X[tc][tr]^T
+__global__ __launch_bounds__(256) void ba_id_add_cross(int N, const double* __restrict__ Xblk, double* __restrict__ S,
+                                                       const BaState* st) {
+  if (st->done != 0.0) return;
+  const int n = 6 * N;
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (long)n * n) return;
+  const int r = (int)(e / n), c = (int)(e - (long)r * n);
+  const int tr = r / 6, tc = c / 6;
+  if (tr <= tc) return;
+  const int a = r - 6 * tr, b = c - 6 * tc;
+  S[e] += Xblk[((long)tr * N + tc) * 36 + 6 * a + b] + Xblk[((long)tc * N + tr) * 36 + 6 * b + a];
+}
+
+// d rho = -(g + sum_t E_it . dc_t) / (c + D): candidate inverse depths and the model decrease
+__global__ __launch_bounds__(256) void ba_id_backsub(BaProblem pb, const double* __restrict__ pts,
+                                                     const double* __restrict__ poses, const double* __restrict__ Cblk,
+                                                     const double* __restrict__ gp, const double* __restrict__ Eblk,
+                                                     const uint8_t* __restrict__ ok, const double* __restrict__ dcam,
+                                                     double* __restrict__ rho_new, double* __restrict__ model_part,
+                                                     const BaState* st) {
+  __shared__ double red[4];
+  const int N = pb.N, K = pb.K, tid = threadIdx.x;
+  const long i = (long)blockIdx.x * 256 + tid;
+  double model = 0.0;
+  if (st->done == 0.0 && i < (long)N * K) {
+    const int s = (int)(i / K);
+    const double* P = poses + 12 * s;
+    const double z = P[6] * (pts[3 * i] - P[9]) + P[7] * (pts[3 * i + 1] - P[10]) + P[8] * (pts[3 * i + 2] - P[11]);
+    double rho = 1.0 / z, Ci[6], D[3], dr = 0.0;
+    if (st->chol_fail == 0.0 && ba_point_inverse(Cblk + 6 * i, st->radius, Ci, D)) {
+      double v = gp[3 * i];
+      for (int t = 0; t < N; ++t) {
+        if (!ok[i * N + t]) continue;
+        const double* E = Eblk + 18 * (i * N + t);
+#pragma unroll
+        for (int a = 0; a < 6; ++a) v += E[3 * a] * dcam[6 * t + a];
+      }
+      dr = -Ci[0] * v;
+      model = -0.5 * gp[3 * i] * dr + 0.5 * D[0] * dr * dr;
+    }
+    rho_new[i] = rho + dr;
+  }
+  const double tot = ba_block_sum<256>(model, red, tid);
+  if (tid == 0) model_part[blockIdx.x] = tot;
+}
+
+// --------------------------------------------------------------------------------------------- Schur complement
 // ---- pass 3b: Schur complement rows.  WG (camera j, slice): lanes = cameras k' <= j (S is symmetric and only its lower
 // triangle is factored).  S_part[slice][6j+a][6k'+b] -= sum_i (E_ij Cinv_i) E_ik'^T and the slice's share of
 // rhs_j = -(g_j - sum_i E_ij Cinv_i g_i).  Per track of camera j: one broadcast read of E_ij, one 144-byte read per lane.
@@ -461,12 +708,7 @@ __global__ __launch_bounds__(BA_MAXN) void ba_schur_rows(BaProblem pb, const dou
       const double* Ej = Eblk + 18 * (i * N + j);     // uniform address: one broadcast load
       double Y[6][3];   // E_ij Cinv
 #pragma unroll
-      for (int a = 0; a < 6; ++a) {
-        const double e0 = Ej[3 * a], e1 = Ej[3 * a + 1], e2 = Ej[3 * a + 2];
-        Y[a][0] = e0 * Ci[0] + e1 * Ci[1] + e2 * Ci[2];
-        Y[a][1] = e0 * Ci[1] + e1 * Ci[3] + e2 * Ci[4];
-        Y[a][2] = e0 * Ci[2] + e1 * Ci[4] + e2 * Ci[5];
-      }
+      for (int a = 0; a < 6; ++a) ba_sym3_mul(Ci, Ej[3 * a], Ej[3 * a + 1], Ej[3 * a + 2], Y[a]);
       const double g0 = gp[3 * i], g1 = gp[3 * i + 1], g2 = gp[3 * i + 2];
 #pragma unroll
       for (int a = 0; a < 6; ++a) rj[a] += Y[a][0] * g0 + Y[a][1] * g1 + Y[a][2] * g2;
@@ -526,11 +768,7 @@ __global__ __launch_bounds__(256) void ba_y_blocks(long nobs, int N, double* __r
   double* E = Eblk + 3 * e;
   double* Y = Yblk + 3 * e;
   if (ok[o]) {
-    const double* ci = Cinv + 6 * (o / N);
-    const double e0 = E[0], e1 = E[1], e2 = E[2];
-    Y[0] = e0 * ci[0] + e1 * ci[1] + e2 * ci[2];
-    Y[1] = e0 * ci[1] + e1 * ci[3] + e2 * ci[4];
-    Y[2] = e0 * ci[2] + e1 * ci[4] + e2 * ci[5];
+    ba_sym3_mul(Cinv + 6 * (o / N), E[0], E[1], E[2], Y);
   } else {
     E[0] = 0.0; E[1] = 0.0; E[2] = 0.0;
     Y[0] = 0.0; Y[1] = 0.0; Y[2] = 0.0;
@@ -651,6 +889,7 @@ __global__ __launch_bounds__(64) void ba_schur_tiles(BaProblem pb, const double*
   }
 }
 
+// ------------------------------------------------------------------------------- reduced camera system, Cholesky
 // ---- pass 4: the reduced camera system.  S = sum of slices + B + D (lower triangle used), rhs = -(g_c - sum slices),
 // then a BLOCKED right-looking Cholesky (panels of BA_NB columns: factor the diagonal block in LDS, solve the panel rows
 // against it, rank-BA_NB update of the trailing matrix by a grid of tiles) and blocked triangular solves.  The factor
@@ -890,60 +1129,7 @@ __global__ __launch_bounds__(1024) void ba_chol_solve(int n, const double* __res
   for (int e = tid; e < n; e += 1024) dcam[e] = x[e];
 }
 
-// ---- pass 5: back-substitution for the points and candidate parameters; model decrease partials
-__global__ __launch_bounds__(256) void ba_backsub_points(BaProblem pb, const double* __restrict__ pts,
-                                                         const double* __restrict__ poses,
-                                                         const double* __restrict__ Cblk, const double* __restrict__ gp,
-                                                         const double* __restrict__ dcam, double* __restrict__ pts_new,
-                                                         double* __restrict__ model_part, const BaState* st) {
-  __shared__ double red[4];
-  const int N = pb.N, K = pb.K, tid = threadIdx.x;
-  const long i = (long)blockIdx.x * 256 + tid;
-  double model = 0.0;
-  if (st->done == 0.0 && i < (long)N * K) {
-    const int s = (int)(i / K), k = (int)(i - (long)s * K);
-    const double X[3] = {pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]};
-    double Ci[6], D[3];
-    double dx[3] = {0, 0, 0};
-    BaFrame fr;
-    if (pb.homogeneous) ba_point_frame(X, fr);
-    if (st->chol_fail == 0.0 && ba_point_inverse(Cblk + 6 * i, st->radius, Ci, D)) {
-      double v[3] = {gp[3 * i], gp[3 * i + 1], gp[3 * i + 2]};   // g_i + sum_t E_it^T dc_t
-      for (int t = 0; t < N; ++t) {
-        const long o = ((long)s * N + t) * K + k;
-        if (!pb.valid[o]) continue;
-        double r[2], Jc[2][6], Jp[2][3], w;
-        if (!ba_project(poses + 12 * t, pb.intr + 4 * t, X, (double)pb.uv[2 * o], (double)pb.uv[2 * o + 1], r, Jc, Jp,
-                        pb.homogeneous ? fr.T : nullptr))
-          continue;
-        huber_rho(r[0] * r[0] + r[1] * r[1], pb.huber, w);
-        double jd0 = 0.0, jd1 = 0.0;      // Jc dc
-#pragma unroll
-        for (int a = 0; a < 6; ++a) { jd0 += Jc[0][a] * dcam[6 * t + a]; jd1 += Jc[1][a] * dcam[6 * t + a]; }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) v[c] += w * (Jp[0][c] * jd0 + Jp[1][c] * jd1);
-      }
-      dx[0] = -(Ci[0] * v[0] + Ci[1] * v[1] + Ci[2] * v[2]);
-      dx[1] = -(Ci[1] * v[0] + Ci[3] * v[1] + Ci[4] * v[2]);
-      dx[2] = -(Ci[2] * v[0] + Ci[4] * v[1] + Ci[5] * v[2]);
-      // model decrease = -1/2 g^T d + 1/2 d^T D d
-#pragma unroll
-      for (int c = 0; c < 3; ++c) model += -0.5 * gp[3 * i + c] * dx[c] + 0.5 * D[c] * dx[c] * dx[c];
-    }
-    if (pb.homogeneous) {
-      double Xn[3];
-      ba_point_plus(X, fr, dx, Xn);
-#pragma unroll
-      for (int c = 0; c < 3; ++c) pts_new[3 * i + c] = Xn[c];
-    } else {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) pts_new[3 * i + c] = X[c] + dx[c];
-    }
-  }
-  const double tot = ba_block_sum<256>(model, red, tid);
-  if (tid == 0) model_part[blockIdx.x] = tot;
-}
-
+// ------------------------------------------------------------------------------------ step, decision, outliers
 __global__ void ba_update_cameras(int N, const double* __restrict__ poses, const double* __restrict__ dcam,
                                   const double* __restrict__ gc, const double* __restrict__ Dcam,
                                   double* __restrict__ poses_new, double* __restrict__ model_cam, const BaState* st) {
@@ -1033,15 +1219,9 @@ __global__ __launch_bounds__(256) void ba_outlier_tracks(BaProblem pb, const dou
   const int s = (int)(i / K), k = (int)(i - (long)s * K);
   const double X[3] = {pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]};
   bool ok = true;
-  int nobs = 0;
-  for (int t = 0; t < N && ok; ++t) {
-    const long o = ((long)s * N + t) * K + k;
-    if (!pb.valid[o]) continue;
-    double r[2], Jc[2][6], Jp[2][3];
-    if (!ba_project(poses + 12 * t, pb.intr + 4 * t, X, (double)pb.uv[2 * o], (double)pb.uv[2 * o + 1], r, Jc, Jp)) ok = false;
-    else if (r[0] * r[0] + r[1] * r[1] > max_px * max_px) ok = false;
-    ++nobs;
-  }
+  ba_walk_track(pb, poses, s, k, X, nullptr, false,
+                [&](int, long, auto& r, auto&, auto&, double) { if (r[0] * r[0] + r[1] * r[1] > max_px * max_px) ok = false; },
+                [&](int, bool seen, bool hit) { if (seen && !hit) ok = false; }, &ok);
   if (ok) {   // sufficient triangulation angle: some pair of rays with cos(angle) < cos(min angle)
     bool wide = false;
     for (int t = 0; t < N && !wide; ++t) {
@@ -1062,204 +1242,51 @@ __global__ __launch_bounds__(256) void ba_outlier_tracks(BaProblem pb, const dou
 }
 
 // ------------------------------------------------------------------------------------------------------------- C ABI
-// ---- inverse depth: kernels (thread per track unless stated)
-__device__ __forceinline__ void ba_id_bearing(const BaProblem& pb, int s, int k, double b[3]) {
-  const long o = ((long)s * pb.N + s) * pb.K + k;
-  const double* in4 = pb.intr + 4 * s;
-  b[0] = ((double)pb.uv[2 * o] - in4[2]) / in4[0];
-  b[1] = ((double)pb.uv[2 * o + 1] - in4[3]) / in4[1];
-  b[2] = 1.0;
-}
-// X = C_s + R_s^T (b / rho): rho == nullptr -> the depth of pts in the reference view (InitializeInverseDepth: snap)
-__global__ __launch_bounds__(256) void ba_id_points(BaProblem pb, const double* __restrict__ poses,
-                                                    const double* __restrict__ rho, const double* __restrict__ pts_in,
-                                                    double* __restrict__ pts_out, const BaState* st) {
-  const int N = pb.N, K = pb.K;
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if ((st && st->done != 0.0) || i >= (long)N * K) return;
-  const int s = (int)(i / K), k = (int)(i - (long)s * K);
-  const double* P = poses + 12 * s;
-  if (!pb.valid[((long)s * N + s) * K + k]) {       // no reference observation: the track is left alone
-    if (pts_in != pts_out)
-      for (int c = 0; c < 3; ++c) pts_out[3 * i + c] = pts_in[3 * i + c];
-    return;
-  }
-  double b[3];
-  ba_id_bearing(pb, s, k, b);
-  double z;
-  if (rho) z = 1.0 / rho[i];
-  else z = P[6] * (pts_in[3 * i] - P[9]) + P[7] * (pts_in[3 * i + 1] - P[10]) + P[8] * (pts_in[3 * i + 2] - P[11]);
-  const double p[3] = {b[0] * z, b[1] * z, z};
-#pragma unroll
-  for (int c = 0; c < 3; ++c) pts_out[3 * i + c] = P[9 + c] + P[c] * p[0] + P[3 + c] * p[1] + P[6 + c] * p[2];
-}
-
-// per track: c = sum w jr.jr, g = sum w jr.r, cost, the E row (observing cameras + the reference camera), ok flags
-__global__ __launch_bounds__(256) void ba_id_linearize(BaProblem pb, const double* __restrict__ pts,
-                                                       const double* __restrict__ poses, double* __restrict__ Cblk,
-                                                       double* __restrict__ gp, double* __restrict__ Eblk,
-                                                       uint8_t* __restrict__ ok, double* __restrict__ cost_part,
-                                                       const BaState* st) {
-  __shared__ double red[4];
-  const int N = pb.N, K = pb.K, tid = threadIdx.x;
-  const long i = (long)blockIdx.x * 256 + tid;
-  double cost = 0.0;
-  if (st->done == 0.0 && i < (long)N * K) {
-    const int s = (int)(i / K), k = (int)(i - (long)s * K);
-    const double X[3] = {pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]};
-    const bool has_ref = pb.valid[((long)s * N + s) * K + k] != 0;
-    double c = 0.0, g = 0.0, Ea[6] = {0, 0, 0, 0, 0, 0};
-    bool any = false;
-    for (int t = 0; t < N; ++t) {
-      const long o = ((long)s * N + t) * K + k, oT = i * N + t;
-      uint8_t good = 0;
-      if (t != s && has_ref && pb.valid[o]) {
-        double r[2], Jc[2][6], Jp[2][3], Ja[2][6], jr[2];
-        if (ba_project(poses + 12 * t, pb.intr + 4 * t, X, (double)pb.uv[2 * o], (double)pb.uv[2 * o + 1], r, Jc, Jp)) {
-          ba_id_chain(poses + 12 * s, X, Jp, Ja, jr);
-          double w;
-          cost += huber_rho(r[0] * r[0] + r[1] * r[1], pb.huber, w);
-          c += w * (jr[0] * jr[0] + jr[1] * jr[1]);
-          g += w * (jr[0] * r[0] + jr[1] * r[1]);
-          double* E = Eblk + 18 * oT;
-#pragma unroll
-          for (int a = 0; a < 6; ++a) {
-            E[3 * a] = w * (Jc[0][a] * jr[0] + Jc[1][a] * jr[1]);
-            E[3 * a + 1] = 0.0;
-            E[3 * a + 2] = 0.0;
-            Ea[a] += w * (Ja[0][a] * jr[0] + Ja[1][a] * jr[1]);
-          }
-          good = 1;
-          any = true;
-        }
-      }
-      if (t != s) ok[oT] = good;
-    }
-    {
-      double* E = Eblk + 18 * (i * N + s);
-#pragma unroll
-      for (int a = 0; a < 6; ++a) { E[3 * a] = Ea[a]; E[3 * a + 1] = 0.0; E[3 * a + 2] = 0.0; }
-      ok[i * N + s] = any ? 1 : 0;
-    }
-    Cblk[6 * i] = c; Cblk[6 * i + 1] = 0.0; Cblk[6 * i + 2] = 0.0; Cblk[6 * i + 3] = 1.0; Cblk[6 * i + 4] = 0.0; Cblk[6 * i + 5] = 1.0;
-    gp[3 * i] = g; gp[3 * i + 1] = 0.0; gp[3 * i + 2] = 0.0;
-  }
-  const double tot = ba_block_sum<256>(cost, red, tid);
-  if (tid == 0) cost_part[blockIdx.x] = 0.5 * tot;
-}
-
-// cost of candidate / start parameters without the reference-view observations (they are met by construction, but only
-// up to rounding: leaving them out keeps the cost exactly the oracle's sum)
-__global__ __launch_bounds__(256) void ba_id_cost(BaProblem pb, const double* __restrict__ pts,
-                                                  const double* __restrict__ poses, double* __restrict__ cost_part,
-                                                  const BaState* st) {
-  __shared__ double red[4];
-  const int N = pb.N, K = pb.K, tid = threadIdx.x;
-  const long i = (long)blockIdx.x * 256 + tid;
-  double cost = 0.0;
-  if (st->done == 0.0 && i < (long)N * K) {
-    const int s = (int)(i / K), k = (int)(i - (long)s * K);
-    const double X[3] = {pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]};
-    if (pb.valid[((long)s * N + s) * K + k])
-      for (int t = 0; t < N; ++t) {
-        const long o = ((long)s * N + t) * K + k;
-        if (t == s || !pb.valid[o]) continue;
-        double r[2], Jc[2][6], Jp[2][3];
-        if (!ba_project(poses + 12 * t, pb.intr + 4 * t, X, (double)pb.uv[2 * o], (double)pb.uv[2 * o + 1], r, Jc, Jp))
-          continue;
-        double w;
-        cost += huber_rho(r[0] * r[0] + r[1] * r[1], pb.huber, w);
-      }
-  }
-  const double tot = ba_block_sum<256>(cost, red, tid);
-  if (tid == 0) cost_part[blockIdx.x] = 0.5 * tot;
-}
-
-// direct camera-camera blocks: X[s][t] = sum_k w Ja(s, k, t)^T Jc(s, k, t)  (6 x 6; rows: reference camera s).  One wave per (s, t).
-__global__ __launch_bounds__(64) void ba_id_cross_blocks(BaProblem pb, const double* __restrict__ pts,
-                                                         const double* __restrict__ poses, double* __restrict__ Xblk,
-                                                         const BaState* st) {
-  const int N = pb.N, K = pb.K, s = blockIdx.y, t = blockIdx.x, lane = threadIdx.x;
-  if (st->done != 0.0) return;
-  double a[36];
-#pragma unroll
-  for (int c = 0; c < 36; ++c) a[c] = 0.0;
-  if (s != t)
-    for (int k = lane; k < K; k += 64) {
-      const long i = (long)s * K + k, o = ((long)s * N + t) * K + k;
-      if (!pb.valid[o] || !pb.valid[((long)s * N + s) * K + k]) continue;
-      const double X[3] = {pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]};
-      double r[2], Jc[2][6], Jp[2][3], Ja[2][6], jr[2];
-      if (!ba_project(poses + 12 * t, pb.intr + 4 * t, X, (double)pb.uv[2 * o], (double)pb.uv[2 * o + 1], r, Jc, Jp)) continue;
-      ba_id_chain(poses + 12 * s, X, Jp, Ja, jr);
-      double w;
-      huber_rho(r[0] * r[0] + r[1] * r[1], pb.huber, w);
-#pragma unroll
-      for (int p = 0; p < 6; ++p)
-#pragma unroll
-        for (int c = 0; c < 6; ++c) a[6 * p + c] += w * (Ja[0][p] * Jc[0][c] + Ja[1][p] * Jc[1][c]);
-    }
-#pragma unroll
-  for (int c = 0; c < 36; ++c) {
-    const double v = wave_sum_f64(a[c]);
-    if (lane == 0) Xblk[((long)s * N + t) * 36 + c] = v;
-  }
-}
-// S (lower triangle) += the cross blocks: H[tr][tc] = X[tr][tc] + X[tc][tr]^T
-__global__ __launch_bounds__(256) void ba_id_add_cross(int N, const double* __restrict__ Xblk, double* __restrict__ S,
-                                                       const BaState* st) {
-  if (st->done != 0.0) return;
-  const int n = 6 * N;
-  const long e = (long)blockIdx.x * 256 + threadIdx.x;
-  if (e >= (long)n * n) return;
-  const int r = (int)(e / n), c = (int)(e - (long)r * n);
-  const int tr = r / 6, tc = c / 6;
-  if (tr <= tc) return;
-  const int a = r - 6 * tr, b = c - 6 * tc;
-  S[e] += Xblk[((long)tr * N + tc) * 36 + 6 * a + b] + Xblk[((long)tc * N + tr) * 36 + 6 * b + a];
-}
-
-// d rho = -(g + sum_t E_it . dc_t) / (c + D): candidate inverse depths and the model decrease
-__global__ __launch_bounds__(256) void ba_id_backsub(BaProblem pb, const double* __restrict__ pts,
-                                                     const double* __restrict__ poses, const double* __restrict__ Cblk,
-                                                     const double* __restrict__ gp, const double* __restrict__ Eblk,
-                                                     const uint8_t* __restrict__ ok, const double* __restrict__ dcam,
-                                                     double* __restrict__ rho_new, double* __restrict__ model_part,
-                                                     const BaState* st) {
-  __shared__ double red[4];
-  const int N = pb.N, K = pb.K, tid = threadIdx.x;
-  const long i = (long)blockIdx.x * 256 + tid;
-  double model = 0.0;
-  if (st->done == 0.0 && i < (long)N * K) {
-    const int s = (int)(i / K);
-    const double* P = poses + 12 * s;
-    const double z = P[6] * (pts[3 * i] - P[9]) + P[7] * (pts[3 * i + 1] - P[10]) + P[8] * (pts[3 * i + 2] - P[11]);
-    double rho = 1.0 / z, Ci[6], D[3], dr = 0.0;
-    if (st->chol_fail == 0.0 && ba_point_inverse(Cblk + 6 * i, st->radius, Ci, D)) {
-      double v = gp[3 * i];
-      for (int t = 0; t < N; ++t) {
-        if (!ok[i * N + t]) continue;
-        const double* E = Eblk + 18 * (i * N + t);
-#pragma unroll
-        for (int a = 0; a < 6; ++a) v += E[3 * a] * dcam[6 * t + a];
-      }
-      dr = -Ci[0] * v;
-      model = -0.5 * gp[3 * i] * dr + 0.5 * D[0] * dr * dr;
-    }
-    rho_new[i] = rho + dr;
-  }
-  const double tot = ba_block_sum<256>(model, red, tid);
-  if (tid == 0) model_part[blockIdx.x] = tot;
-}
-
 static inline int ba_nblk(int N, int K) { return (int)(((long)N * K + 255) / 256); }
 
-extern "C" long pi3_ba_workspace_doubles(int N, int K) {
-  const long n6 = 6L * N, nk = (long)N * K;
-  return 16 /*state*/ + 6 * nk + 3 * nk + 3 * nk /*pts_new*/ + 12L * N /*poses_new*/ + 21L * N + 6L * N /*gc*/ +
-         6L * N /*dcam*/ + 6L * N /*Dcam*/ + BA_SLICES * n6 * n6 + BA_SLICES * n6 + 2 * n6 * n6 + 18 * nk * N + (nk * N + 7) / 8 + 3L * ba_nblk(N, K) +
-         3L * N + 64 + nk /*inverse depth: rho_new*/ + 36L * N * N /*cross blocks*/ + 6 * nk /*damped point inverses*/ + 18 * nk * N /*Y = E Cinv*/ + 256 /*tile reads past the last track of Y*/ + 144 /*the same past Eblk*/;
+// The workspace, laid out ONCE: ba_layout(N, K, nullptr).doubles is the size pi3_ba_workspace_doubles reports and
+// ba_layout(N, K, workspace) gives ba_run its arrays, so an array cannot be in one and missing from the other.
+struct BaWorkspace {
+  BaState* state;
+  double *Cblk, *gp, *pts_new, *poses_new, *Bblk, *gc, *dcam, *Dcam, *S_part, *rhs_part, *S, *Lfac, *Eblk;
+  uint8_t* obs_ok;
+  double *cost_part, *model_part, *cost_part2, *prior_cost, *model_cam, *prior_cost2, *rho_new, *Xblk, *Cinv, *Yblk;
+  long doubles;
+};
+static BaWorkspace ba_layout(int N, int K, double* base) {
+  const long n6 = 6L * N, nk = (long)N * K, nblk = ba_nblk(N, K);
+  BaWorkspace ws;
+  long at = 0;
+  auto take = [&](long n) {
+    double* p = base ? base + at : nullptr;
+    at += n;
+    return p;
+  };
+  ws.state = (BaState*)take(16);
+  ws.Cblk = take(6 * nk);  ws.gp = take(3 * nk);                              // per track: C_i (packed), g_i
+  ws.pts_new = take(3 * nk);  ws.poses_new = take(12L * N);                   // candidate parameters
+  ws.Bblk = take(21L * N);  ws.gc = take(6L * N);                             // per camera: B_t (packed), g_t
+  ws.dcam = take(6L * N);  ws.Dcam = take(6L * N);                            // camera step, LM diagonal
+  ws.S_part = take(BA_SLICES * n6 * n6);  ws.rhs_part = take(BA_SLICES * n6); // the slices' partial sums
+  ws.S = take(n6 * n6);  ws.Lfac = take(n6 * n6);                             // reduced camera system, its factor
+  // ba_schur_tiles loads at constant offsets from a track's run whatever the camera count: in the last block of 8
+  // cameras the lanes past the last camera read up to 126 doubles past the last track's run (and drop the value)
+  const long BA_EBLK_PAD = 144;
+  ws.Eblk = take(18 * nk * N + BA_EBLK_PAD);
+  ws.obs_ok = (uint8_t*)take((nk * N + 7) / 8);                               // one byte per observation
+  ws.cost_part = take(nblk);  ws.model_part = take(nblk);  ws.cost_part2 = take(nblk); // per block of 256 tracks
+  ws.prior_cost = take(N);  ws.model_cam = take(N);  ws.prior_cost2 = take(N);         // per camera
+  const long BA_SPARE = 64;      // unused: kept because the footprint a caller allocates is part of the interface
+  take(BA_SPARE);
+  ws.rho_new = take(nk);  ws.Xblk = take(36L * N * N);     // inverse depth: candidate parameters, camera-camera blocks
+  ws.Cinv = take(6 * nk);                                  // damped point inverses
+  const long BA_YBLK_PAD = 256;      // Y = E Cinv is read by the same lanes as Eblk, here up to the end of the buffer
+  ws.Yblk = take(18 * nk * N + BA_YBLK_PAD);
+  ws.doubles = at;
+  return ws;
 }
+
+extern "C" long pi3_ba_workspace_doubles(int N, int K) { return ba_layout(N, K, nullptr).doubles; }
 
 static int ba_run(double* points, double* poses, const double* intr, const float* uv, const unsigned char* valid,
                   const float* uvT, const unsigned char* validT, int N, int K, double huber_width, int max_iters,
@@ -1272,40 +1299,17 @@ static int ba_run(double* points, double* poses, const double* intr, const float
     pi3_set_error("pi3_bundle_adjust: bad arguments N=%d (<= %d) K=%d", N, BA_MAXN, K);
     return PI3_ERR_ARG;
   }
-  if (workspace_doubles < pi3_ba_workspace_doubles(N, K)) {
-    pi3_set_error("pi3_bundle_adjust: workspace of %ld doubles, need %ld", workspace_doubles, pi3_ba_workspace_doubles(N, K));
+  const BaWorkspace ws = ba_layout(N, K, workspace);
+  if (workspace_doubles < ws.doubles) {
+    pi3_set_error("pi3_bundle_adjust: workspace of %ld doubles, need %ld", workspace_doubles, ws.doubles);
     return PI3_ERR_WORKSPACE;
   }
   hipStream_t st = (hipStream_t)stream;
+  auto launch = [st](auto kernel, dim3 grid, int block, auto... args) {
+    hipLaunchKernelGGL(kernel, grid, dim3(block), 0, st, args...);
+  };
   const long n6 = 6L * N, nk = (long)N * K;
   const int nblk = ba_nblk(N, K);
-  double* w = workspace;
-  BaState* state = (BaState*)w; w += 16;
-  double* Cblk = w; w += 6 * nk;
-  double* gp = w; w += 3 * nk;
-  double* pts_new = w; w += 3 * nk;
-  double* poses_new = w; w += 12L * N;
-  double* Bblk = w; w += 21L * N;
-  double* gc = w; w += 6L * N;
-  double* dcam = w; w += 6L * N;
-  double* Dcam = w; w += 6L * N;
-  double* S_part = w; w += BA_SLICES * n6 * n6;
-  double* rhs_part = w; w += BA_SLICES * n6;
-  double* S = w; w += n6 * n6;
-  double* Lfac = w; w += n6 * n6;
-  double* Eblk = w; w += 18 * nk * N + 144;   // ba_schur_tiles prefetches up to 126 doubles past the last track's run
-  uint8_t* obs_ok = (uint8_t*)w; w += (nk * N + 7) / 8;
-  double* cost_part = w; w += nblk;
-  double* model_part = w; w += nblk;
-  double* cost_part2 = w; w += nblk;
-  double* prior_cost = w; w += N;
-  double* model_cam = w; w += N;
-  double* prior_cost2 = w; w += N;
-  w += 64;      // (the spare doubles of the size formula)
-  double* rho_new = w; w += nk;
-  double* Xblk = w; w += 36L * N * N;
-  double* Cinv = w; w += 6 * nk;
-  double* Yblk = w; w += 18 * nk * N;
   const bool invd = mode == 2;
   const bool schur_rows = (int)PI3_KNOB("ba_schur_rows", 0) != 0;     // 1: the round-3 row kernel (A/B)
   // track slices (partial sums added in slice order by ba_assemble_cameras).  The tile kernel runs two single-wave
@@ -1320,11 +1324,11 @@ static int ba_run(double* points, double* poses, const double* intr, const float
   }
   // the tile kernel writes the lower-triangle tiles only; the rest of S_part is read by ba_assemble_cameras and never
   // used by the factorisation: defined once
-  if (!schur_rows && hipMemsetAsync(S_part, 0, sizeof(double) * nsl * n6 * n6, st) != hipSuccess) {   // only nsl are read
+  if (!schur_rows && hipMemsetAsync(ws.S_part, 0, sizeof(double) * nsl * n6 * n6, st) != hipSuccess) {   // only nsl are read
     pi3_set_error("pi3_bundle_adjust: hipMemsetAsync failed");
     return PI3_ERR_LAUNCH;
   }
-  if (hipMemsetAsync(state, 0, 16 * sizeof(double), st) != hipSuccess) {
+  if (hipMemsetAsync(ws.state, 0, 16 * sizeof(double), st) != hipSuccess) {
     pi3_set_error("pi3_bundle_adjust: hipMemsetAsync failed");
     return PI3_ERR_LAUNCH;
   }
@@ -1335,71 +1339,64 @@ static int ba_run(double* points, double* poses, const double* intr, const float
   pb.homogeneous = mode == 1 ? 1 : 0;
   pb.invdepth = invd ? 1 : 0;
   if (invd)   // InitializeInverseDepth: every track onto the ray of its reference keypoint, at its current depth there
-    hipLaunchKernelGGL(ba_id_points, dim3(nblk), dim3(256), 0, st, pb, poses, (const double*)nullptr, points, points,
-                       (const BaState*)nullptr);
+    launch(ba_id_points, nblk, 256, pb, poses, (const double*)nullptr, points, points, (const BaState*)nullptr);
   // cost at the start
-  if (invd) hipLaunchKernelGGL(ba_id_cost, dim3(nblk), dim3(256), 0, st, pb, points, poses, cost_part, state);
-  else hipLaunchKernelGGL(ba_cost_points, dim3(nblk), dim3(256), 0, st, pb, points, poses, cost_part, state);
-  hipLaunchKernelGGL(ba_prior_cost, dim3((N + 63) / 64), dim3(64), 0, st, pb, poses, prior_cost, state);
-  hipLaunchKernelGGL(ba_decide, dim3(1), dim3(256), 0, st, nblk, N, 3 * nk, cost_part, prior_cost, model_part, model_cam, 1,
-                     points, pts_new, poses, poses_new, max_iters, state);
+  launch(ba_cost_points, nblk, 256, pb, points, poses, ws.cost_part, ws.state);
+  launch(ba_prior_cost, (N + 63) / 64, 64, pb, poses, ws.prior_cost, ws.state);
+  launch(ba_decide, 1, 256, nblk, N, 3 * nk, ws.cost_part, ws.prior_cost, ws.model_part, ws.model_cam, 1, points,
+         ws.pts_new, poses, ws.poses_new, max_iters, ws.state);
   for (int it = 0; it < max_iters; ++it) {
     if (invd) {
-      hipLaunchKernelGGL(ba_id_linearize, dim3(nblk), dim3(256), 0, st, pb, points, poses, Cblk, gp, Eblk, obs_ok, cost_part,
-                         state);
-      hipLaunchKernelGGL(ba_id_cross_blocks, dim3(N, N), dim3(64), 0, st, pb, points, poses, Xblk, state);
+      launch(ba_id_linearize, nblk, 256, pb, points, poses, ws.Cblk, ws.gp, ws.Eblk, ws.obs_ok, ws.cost_part, ws.state);
+      launch(ba_id_cross_blocks, dim3(N, N), 64, pb, points, poses, ws.Xblk, ws.state);
     } else {
-      hipLaunchKernelGGL(ba_linearize_points, dim3(nblk), dim3(256), 0, st, pb, points, poses, Cblk, gp, cost_part, state);
-      hipLaunchKernelGGL(ba_obs_blocks, dim3((unsigned)((nk * N + 255) / 256)), dim3(256), 0, st, pb, points, poses, Eblk,
-                         obs_ok, state);
+      launch(ba_linearize_points, nblk, 256, pb, points, poses, ws.Cblk, ws.gp, ws.cost_part, ws.state);
+      launch(ba_obs_blocks, (unsigned)((nk * N + 255) / 256), 256, pb, points, poses, ws.Eblk, ws.obs_ok, ws.state);
     }
-    hipLaunchKernelGGL(ba_camera_blocks, dim3(N), dim3(256), 0, st, pb, points, poses, Bblk, gc, prior_cost, state);
+    launch(ba_camera_blocks, N, 256, pb, points, poses, ws.Bblk, ws.gc, ws.prior_cost, ws.state);
     if (schur_rows) {
-      hipLaunchKernelGGL(ba_schur_rows, dim3(N, BA_SLICES), dim3(BA_MAXN), 0, st, pb, Eblk, obs_ok, Cblk, gp, S_part,
-                         rhs_part, state);
+      launch(ba_schur_rows, dim3(N, BA_SLICES), BA_MAXN, pb, ws.Eblk, ws.obs_ok, ws.Cblk, ws.gp, ws.S_part,
+             ws.rhs_part, ws.state);
     } else {
-      hipLaunchKernelGGL(ba_point_inverses, dim3(nblk), dim3(256), 0, st, nk, Cblk, Cinv, state);
-      hipLaunchKernelGGL(ba_y_blocks, dim3((unsigned)((6 * nk * N + 255) / 256)), dim3(256), 0, st, nk * N, N, Eblk, obs_ok,
-                         Cinv, Yblk, state);
-      hipLaunchKernelGGL(ba_schur_tiles, dim3(ntile, nsl), dim3(64), 0, st, pb, Eblk, Yblk, gp, S_part, rhs_part, nsl, state);
+      launch(ba_point_inverses, nblk, 256, nk, ws.Cblk, ws.Cinv, ws.state);
+      launch(ba_y_blocks, (unsigned)((6 * nk * N + 255) / 256), 256, nk * N, N, ws.Eblk, ws.obs_ok, ws.Cinv, ws.Yblk,
+             ws.state);
+      launch(ba_schur_tiles, dim3(ntile, nsl), 64, pb, ws.Eblk, ws.Yblk, ws.gp, ws.S_part, ws.rhs_part, nsl, ws.state);
     }
     const int n = (int)n6;
-    hipLaunchKernelGGL(ba_assemble_cameras, dim3((unsigned)((n6 * n6 + 255) / 256)), dim3(256), 0, st, N, S_part, rhs_part,
-                       Bblk, gc, S, dcam, Dcam, nsl, state);
+    launch(ba_assemble_cameras, (unsigned)((n6 * n6 + 255) / 256), 256, N, ws.S_part, ws.rhs_part, ws.Bblk, ws.gc,
+           ws.S, ws.dcam, ws.Dcam, nsl, ws.state);
     if (invd)
-      hipLaunchKernelGGL(ba_id_add_cross, dim3((unsigned)((n6 * n6 + 255) / 256)), dim3(256), 0, st, N, Xblk, S, state);
+      launch(ba_id_add_cross, (unsigned)((n6 * n6 + 255) / 256), 256, N, ws.Xblk, ws.S, ws.state);
     for (int c0 = 0; c0 < n; c0 += BA_NB) {
       const int nb = n - c0 < BA_NB ? n - c0 : BA_NB;
-      hipLaunchKernelGGL(ba_chol_diag, dim3(1), dim3(64), 0, st, n, c0, nb, S, Lfac, state);
+      launch(ba_chol_diag, 1, 64, n, c0, nb, ws.S, ws.Lfac, ws.state);
       const int below = n - c0 - nb;      // (+ 1: the right-hand side as row n)
-      hipLaunchKernelGGL(ba_chol_panel, dim3((below + 1 + 63) / 64), dim3(64), 0, st, n, c0, nb, S, (const double*)Lfac, Lfac,
-                         dcam, state);
+      launch(ba_chol_panel, (below + 1 + 63) / 64, 64, n, c0, nb, ws.S, (const double*)ws.Lfac, ws.Lfac, ws.dcam,
+             ws.state);
       if (below > 0) {
         const int nt = (below + BA_NB - 1) / BA_NB;
-        hipLaunchKernelGGL(ba_chol_update, dim3(nt, nt + 1), dim3(256), 0, st, n, c0, nb, S, Lfac, dcam, state);
+        launch(ba_chol_update, dim3(nt, nt + 1), 256, n, c0, nb, ws.S, ws.Lfac, ws.dcam, ws.state);
       }
     }
-    hipLaunchKernelGGL(ba_chol_solve, dim3(1), dim3(1024), 0, st, n, Lfac, dcam, state);
+    launch(ba_chol_solve, 1, 1024, n, ws.Lfac, ws.dcam, ws.state);
     if (invd)
-      hipLaunchKernelGGL(ba_id_backsub, dim3(nblk), dim3(256), 0, st, pb, points, poses, Cblk, gp, Eblk, obs_ok, dcam, rho_new,
-                         model_part, state);
+      launch(ba_id_backsub, nblk, 256, pb, points, poses, ws.Cblk, ws.gp, ws.Eblk, ws.obs_ok, ws.dcam, ws.rho_new,
+             ws.model_part, ws.state);
     else
-      hipLaunchKernelGGL(ba_backsub_points, dim3(nblk), dim3(256), 0, st, pb, points, poses, Cblk, gp, dcam, pts_new,
-                         model_part, state);
-    hipLaunchKernelGGL(ba_update_cameras, dim3((N + 63) / 64), dim3(64), 0, st, N, poses, dcam, gc, Dcam, poses_new,
-                       model_cam, state);
-    if (invd) {      // candidate points from the candidate reference poses and inverse depths
-      hipLaunchKernelGGL(ba_id_points, dim3(nblk), dim3(256), 0, st, pb, poses_new, rho_new, points, pts_new, state);
-      hipLaunchKernelGGL(ba_id_cost, dim3(nblk), dim3(256), 0, st, pb, pts_new, poses_new, cost_part2, state);
-    } else {
-      hipLaunchKernelGGL(ba_cost_points, dim3(nblk), dim3(256), 0, st, pb, pts_new, poses_new, cost_part2, state);
-    }
-    hipLaunchKernelGGL(ba_prior_cost, dim3((N + 63) / 64), dim3(64), 0, st, pb, poses_new, prior_cost2, state);
-    hipLaunchKernelGGL(ba_decide, dim3(1), dim3(256), 0, st, nblk, N, 3 * nk, cost_part2, prior_cost2, model_part, model_cam,
-                       0, points, pts_new, poses, poses_new, max_iters, state);
+      launch(ba_backsub_points, nblk, 256, pb, points, poses, ws.Cblk, ws.gp, ws.dcam, ws.pts_new, ws.model_part,
+             ws.state);
+    launch(ba_update_cameras, (N + 63) / 64, 64, N, poses, ws.dcam, ws.gc, ws.Dcam, ws.poses_new, ws.model_cam,
+           ws.state);
+    if (invd)      // candidate points from the candidate reference poses and inverse depths
+      launch(ba_id_points, nblk, 256, pb, ws.poses_new, ws.rho_new, points, ws.pts_new, ws.state);
+    launch(ba_cost_points, nblk, 256, pb, ws.pts_new, ws.poses_new, ws.cost_part2, ws.state);
+    launch(ba_prior_cost, (N + 63) / 64, 64, pb, ws.poses_new, ws.prior_cost2, ws.state);
+    launch(ba_decide, 1, 256, nblk, N, 3 * nk, ws.cost_part2, ws.prior_cost2, ws.model_part, ws.model_cam, 0, points,
+           ws.pts_new, poses, ws.poses_new, max_iters, ws.state);
   }
   // summary: initial cost, final cost, iterations, accepted steps, final radius
-  if (hipMemcpyAsync(summary_dev, state, sizeof(BaState), hipMemcpyDeviceToDevice, st) != hipSuccess) {
+  if (hipMemcpyAsync(summary_dev, ws.state, sizeof(BaState), hipMemcpyDeviceToDevice, st) != hipSuccess) {
     pi3_set_error("pi3_bundle_adjust: summary copy failed");
     return PI3_ERR_LAUNCH;
   }

@@ -43,6 +43,31 @@ def test_loads_without_gpu_and_reports_version(built_lib):
     assert isinstance(dll.pi3_last_error(), bytes)
 
 
+def test_ba_workspace_size_is_the_closed_form(built_lib):
+    """pi3_ba_workspace_doubles(N, K) is the sum of the bundle adjuster's arrays and their pads (csrc/ba.hip: ba_layout),
+    restated here term by term: the footprint a caller allocates is behaviour, and the function that reports it is the
+    same one that carves the buffer."""
+    from pi3_slam_amd import lib
+    dll = lib.load(require_gpu=False)
+    slices = 32
+    for N, K in ((1, 1), (5, 8), (66, 6), (100, 200), (128, 256)):
+        n6, nk, nblk = 6 * N, N * K, (N * K + 255) // 256
+        want = (16                                  # state
+                + 6 * nk + 3 * nk                   # Cblk, gp
+                + 3 * nk + 12 * N                   # pts_new, poses_new
+                + 21 * N + 6 * N + 6 * N + 6 * N    # Bblk, gc, dcam, Dcam
+                + slices * n6 * n6 + slices * n6    # S_part, rhs_part
+                + 2 * n6 * n6                       # S, L
+                + 18 * nk * N + 144                 # Eblk + the tile kernel's reads past its last track
+                + (nk * N + 7) // 8                 # observation flags (bytes)
+                + 3 * nblk + 3 * N                  # cost / model partials per block and per camera
+                + 64                                # spare
+                + nk + 36 * N * N                   # inverse depth: rho_new, cross blocks
+                + 6 * nk                            # damped point inverses
+                + 18 * nk * N + 256)                # Y = E Cinv + the tile kernel's reads past its last track
+        assert dll.pi3_ba_workspace_doubles(N, K) == want, (N, K)
+
+
 def test_knob_registry_refuses_names_of_development_variants(built_lib):
     """The product library knows four knobs; a development variant's name must be refused, not accepted and ignored."""
     import pytest

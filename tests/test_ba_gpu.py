@@ -74,15 +74,15 @@ def test_bundle_adjust_matches_oracle(dev, case):
 
 
 def _compare_with_schur_oracle(dev, pb, huber, iters, prior=None, cost_rtol=1e-9, atol_pose=1e-7, atol_pts=1e-6,
-                               homogeneous=False):
+                               homogeneous=False, oracle=None):
     """pi3_bundle_adjust (homogeneous: pi3_bundle_adjust_homogeneous) against oracle/ba_ref.bundle_adjust_schur on the same
-    problem: same number of iterations and accepted steps, costs to cost_rtol, parameters to atol.  Returns (device
-    summary, oracle summary)."""
+    problem: same number of iterations and accepted steps, costs to cost_rtol, parameters to atol.  oracle: that
+    function's result when the caller already has it.  Returns (device summary, oracle summary)."""
     from oracle import ba_ref
     from pi3_slam_amd import ops
     N = len(pb["R"])
-    R, C, X, s = ba_ref.bundle_adjust_schur(pb["R"], pb["C"], pb["intr"], pb["X"], pb["uv"], pb["valid"], huber, iters, prior,
-                                            homogeneous=homogeneous)
+    R, C, X, s = oracle or ba_ref.bundle_adjust_schur(pb["R"], pb["C"], pb["intr"], pb["X"], pb["uv"], pb["valid"], huber,
+                                                      iters, prior, homogeneous=homogeneous)
     pts, rc, intr, uv, valid = _to_dev(pb, dev)
     pr = pc = pf = None
     if prior is not None:
@@ -124,6 +124,88 @@ def test_multi_panel_with_pose_priors_matches_the_oracle(dev):
     flag = np.zeros(N, np.uint8); flag[:5] = 1
     prior = dict(R=pb["R_gt"].copy(), C=pb["C_gt"] + 0.03, flag=flag, sqrt_info_rot=0.5 ** 0.5, sqrt_info_pos=0.2)
     _compare_with_schur_oracle(dev, pb, 3.0, 8, prior)
+
+
+class _Chunk66:
+    """bench.synthetic_ba_problem(66, 6, seed=3, noise_px=0.5, perturb=1.0) with three LM iterations and its oracle
+    results, one per form, computed on first use.  66 cameras: 9 blocks of 8 cameras for ba_schur_tiles with a last
+    block of 2 (the lanes that load past the last camera are live, and with them the pads behind Eblk and Yblk), 396
+    unknowns = 8 1/4 Cholesky panels, and in ba_schur_rows cameras 64 and 65 sit in the second wave of the 128-lane
+    workgroup (wave_has_cams is true for it from row j = 64 on).  The oracle takes all three steps without a failed
+    factorisation in each form: cost 34056 -> 2906 (Euclidean, homogeneous), 27590 -> 4186 (inverse depth).
+    Tolerances: costs 1e-9, poses 1e-6, points 1e-5 - those of test_whole_chunk_matches_the_oracle for a
+    multi-iteration run on this generator."""
+    ITERS, TOL = 3, dict(cost_rtol=1e-9, atol_pose=1e-6, atol_pts=1e-5)
+
+    def __init__(self):
+        from bench import synthetic_ba_problem
+        self.pb = synthetic_ba_problem(66, 6, seed=3, noise_px=0.5, perturb=1.0)
+        self._oracle = {}
+
+    def oracle(self, form):
+        from oracle import ba_ref
+        if form not in self._oracle:
+            pb = self.pb
+            args = (pb["R"], pb["C"], pb["intr"], pb["X"], pb["uv"], pb["valid"], 2.0, self.ITERS)
+            self._oracle[form] = (ba_ref.bundle_adjust_inverse_depth(*args) if form == "inverse_depth" else
+                                  ba_ref.bundle_adjust_schur(*args, homogeneous=form == "homogeneous"))
+        return self._oracle[form]
+
+
+@pytest.fixture(scope="module")
+def chunk66():
+    return _Chunk66()
+
+
+def _run_chunk66(dev, chunk66, form):
+    """One form of the 66-camera problem on the device against its oracle; the Schur forms through
+    _compare_with_schur_oracle, inverse depth the way test_inverse_depth_parametrization_matches_the_oracle compares."""
+    from pi3_slam_amd import ops
+    pb, (R, C, X, s) = chunk66.pb, chunk66.oracle(form)
+    assert s.get("chol_failures", 0) == 0 and (s["iterations"], s["accepted_steps"]) == (3, 3), s
+    if form != "inverse_depth":
+        out, _ = _compare_with_schur_oracle(dev, pb, 2.0, chunk66.ITERS, homogeneous=form == "homogeneous",
+                                            oracle=(R, C, X, s), **chunk66.TOL)
+    else:
+        pts, rc, intr, uv, valid = _to_dev(pb, dev)
+        out = ops.bundle_adjust(pts, rc, intr, uv, valid, 2.0, chunk66.ITERS, inverse_depth=True).cpu().numpy()
+        torch.cuda.synchronize()
+        assert abs(out[8] - s["initial_cost"]) <= 1e-9 * s["initial_cost"], (out[8], s["initial_cost"])
+        assert (int(out[5]), int(out[6])) == (s["iterations"], s["accepted_steps"]), (out, s)
+        assert abs(out[0] - s["final_cost"]) <= 1e-9 * s["final_cost"], (out[0], s["final_cost"])
+        rcn = rc.cpu().numpy()
+        np.testing.assert_allclose(rcn[:, :9].reshape(66, 3, 3), R, atol=1e-6)
+        np.testing.assert_allclose(rcn[:, 9:], C, atol=1e-6)
+        np.testing.assert_allclose(pts.cpu().numpy(), X, atol=1e-5)
+    assert out[9] == 0 and out[0] < 0.2 * out[8], out
+
+
+@pytest.mark.parametrize("form", ["euclidean", "homogeneous", "inverse_depth"])
+def test_66_cameras_on_the_tile_path_match_the_oracle(dev, chunk66, form):
+    """The default matrix-core Schur kernel with a partial last block of cameras, all three forms (see _Chunk66)."""
+    from pi3_slam_amd import lib
+    assert not lib.get_knob("ba_schur_rows")
+    _run_chunk66(dev, chunk66, form)
+
+
+def test_row_form_schur_kernel_under_its_knob_matches_the_oracle(dev, chunk66):
+    """ba_schur_rows = 1 selects the row-form Schur kernel (one workgroup of 128 lanes per camera row and slice) in place
+    of ba_point_inverses + ba_y_blocks + ba_schur_tiles.  Two problems: N = 20, K = 12, where each of the 32 slices
+    holds 0 or 1 source frame and the factorisation has 3 panels - one iteration and six at the tolerances
+    test_multi_panel_cholesky_and_schur_slices_match_the_oracle uses for the same problem - and the 66-camera problem
+    (see _Chunk66), whose rows 64 and 65 put the workgroup's second wave to work, Euclidean and homogeneous."""
+    from pi3_slam_amd import lib
+    before = lib.get_knob("ba_schur_rows")
+    lib.set_knob("ba_schur_rows", 1)
+    try:
+        pb = make_problem(N=20, K=12, seed=120, noise_px=0.5, outlier_frac=0.03, perturb=0.5)
+        for iters in (1, 6):
+            out, s = _compare_with_schur_oracle(dev, pb, 2.0, iters)
+            assert out[9] == 0 and s["chol_failures"] == 0 and out[0] < out[8]
+        for form in ("euclidean", "homogeneous"):
+            _run_chunk66(dev, chunk66, form)
+    finally:
+        lib.restore_knob("ba_schur_rows", before)
 
 
 @pytest.mark.parametrize("iters,homogeneous", [(1, False), (10, False), (2, True)])

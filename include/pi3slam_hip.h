@@ -503,6 +503,32 @@ int pi3_voxel_extract_normals(const void* table, long capacity, const long long*
 int pi3_render_shade(const int* index, const float* normals, long V, const double* cams, int M, int H, int W,
                      unsigned char* normal_rgb, unsigned char* shaded, unsigned long long* stats, void* stream);
 
+/* ---- a triangle mesh of the fused voxel table (csrc/voxel_mesh.hip): an oriented-point signed field on the table's
+ * lattice, meshed by surface nets; f64 / integer arithmetic that tests/dense_mesh_ref.py reproduces byte for byte.
+ * table / capacity / nacc / keep_or_null as above.  A SOURCE voxel is an occupied (and kept) slot with W >= 1, cnt > 0
+ * and a non-zero normal sum.  The cell table is caller-owned DEVICE memory: cells uint64 [cell_capacity] (a power of
+ * two) and verts uint32 [cell_capacity][8].  stats: DEVICE uint64 [12]; every call zeroes the entries it writes.
+ *
+ * pi3_voxel_mesh_cells: clears `cells` and inserts the keys of the 27 cells around every source voxel.
+ *   stats[0] = source voxels, [1] = cells, [2] = inserts that found no slot within min(cell_capacity, 256)
+ *   probes (the table is too small: nothing was written for them; grow it and call again).  cells_or_null = NULL: stats[0] only.
+ * pi3_voxel_mesh_vertices: one vertex per cell with a sign change on one of its 12 edges -> verts.
+ *   stats[3] = vertices, [4] = quads, [5] = cell faces with four crossings (non-manifold edges).
+ * pi3_voxel_mesh_extract: vertex rows vkeys uint64 [V] (the cell's key), vxyz f32 [V][3] (metres), vnrm f32 [V][3],
+ *   vrgb uint8 [V][3], at most max_vertices; quad rows qkeys uint64 [Q] (the owner cell's key) and qcodes int32 [Q]
+ *   = axis | flip << 2, at most max_quads; in no defined order.  The quad of owner i along axis a joins the cells
+ *   i - e_b - e_c, i - e_c, i, i - e_b (b = (a + 1) % 3, c = (a + 2) % 3), counter-clockwise seen from +a, reversed
+ *   under flip.  stats[6] = vertex rows, [7] = quad rows, [8] / [9] = rows of either kind that did not fit. */
+int pi3_voxel_mesh_cells(const void* table, long capacity, const long long* nacc, const unsigned char* keep_or_null,
+                         unsigned long long* cells_or_null, long cell_capacity, unsigned long long* stats, void* stream);
+int pi3_voxel_mesh_vertices(const void* table, long capacity, const long long* nacc, const unsigned char* keep_or_null,
+                            const unsigned long long* cells, long cell_capacity, double voxel_size, unsigned* verts,
+                            unsigned long long* stats, void* stream);
+int pi3_voxel_mesh_extract(const unsigned long long* cells, long cell_capacity, const unsigned* verts,
+                           unsigned long long* vkeys, float* vxyz, float* vnrm, unsigned char* vrgb, long max_vertices,
+                           unsigned long long* qkeys, int* qcodes, long max_quads, unsigned long long* stats,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

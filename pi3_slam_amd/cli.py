@@ -77,6 +77,8 @@ RECON_FLAGS: Sequence[Tuple[str, Dict]] = (
                                                                 "measured optimum)")),
 )
 RECON_SWITCHES = (("--save-per-chunk", "per-chunk ply files as well"),
+                  ("--dense-mesh", "write dense_mesh.ply: a triangle mesh of the fused dense map (surface nets on its "
+                                   "voxel lattice; the chunks must have been created with --dense-normals)"),
                   ("--render-overview", "write renders/overview.png: the dense map from above with the trajectory in red"),
                   ("--use-inverse-depth", "one inverse depth per track along its reference keypoint's ray in both bundle "
                                          "adjustments (utils/chunk_reconstruction.py:187-204; pi3_bundle_adjust_inverse_depth)"),
@@ -143,6 +145,8 @@ ONLINE_SWITCHES = (("--save_chunk_reconstructions", "save each chunk reconstruct
                    ("--use_inverse_depth", "inverse-depth parametrization in both bundle adjustments"),
                    ("--dense_normals", "with --dense_voxel_size: surface normals in dense_points.ply (nx ny nz) and "
                                        "normal / shaded images under renders/"),
+                   ("--dense_mesh", "with --dense_voxel_size and --dense_normals: write dense_mesh.ply, a triangle mesh "
+                                    "of the fused dense map"),
                    ("--no_visualization", "accepted for compatibility (there is never a window)"),
                    ("--keep_viz_open", "accepted for compatibility"),
                    ("--save_tum", "save the trajectory in TUM format"),
@@ -216,7 +220,7 @@ def run_reconstruct(a: argparse.Namespace) -> None:
                          render_overview=a.render_overview, render_min_weight=a.render_min_weight,
                          render_splat_scale=a.render_splat_scale, dense_min_weight=a.dense_min_weight,
                          dense_min_support=a.dense_min_support, dense_support_radius=a.dense_support_radius,
-                         dense_min_component=a.dense_min_component).run()
+                         dense_min_component=a.dense_min_component, dense_mesh=a.dense_mesh).run()
 
 
 def online_image_paths(a: argparse.Namespace) -> List[str]:
@@ -277,6 +281,11 @@ def run_online(a: argparse.Namespace) -> None:
     print(f"💾 Saved {ply}" + (f" and {tum}" if a.save_tum else ""))
     if a.dense_voxel_size is not None:
         slam.save_dense_map(os.path.join(out_dir or ".", "dense_points.ply"))
+    if a.dense_mesh:
+        if a.dense_voxel_size is None:
+            print("--dense_mesh needs --dense_voxel_size: no dense mesh")
+        else:
+            slam.save_dense_mesh(os.path.join(out_dir or ".", "dense_mesh.ply"))
     if a.render_every is not None:
         if a.dense_voxel_size is None:
             print("--render_every needs --dense_voxel_size: no renders")

@@ -19,8 +19,11 @@ of its pixels' normals (cross products of the pointmap's central differences, fa
 stage 1, the weighted mean of the clouds' rotated normals in stage 2.  A cloud then carries `normals` f32 (V,3) and
 `normal_weights` i32 (V,); points, colors and weights are what they are without the option.
 
+Optionally (MapMesher, csrc/voxel_mesh.hip; dense_mesh) stage 2 also meshes the fused table: a signed field from the
+voxels' centroids and normals, surface nets on the table's lattice -> dense_mesh.ply.  It needs the normals.
+
 The accumulators are integers, so a map is bitwise reproducible and tests/dense_map_ref.py reproduces it bit for bit
-(tests/dense_normals_ref.py the normals).
+(tests/dense_normals_ref.py the normals, tests/dense_mesh_ref.py the mesh).
 Limitation: a cloud follows its chunk's similarity; per-view corrections of a bundle adjustment do not reach it.
 """
 from __future__ import annotations
@@ -412,6 +415,128 @@ class NormalAccumulator:
         return sort_normals_by_key(keys[:V].cpu().numpy(), nrm[:V].cpu().numpy(), nw[:V].cpu().numpy())
 
 
+def quad_faces(vertex_keys: np.ndarray, quad_keys: np.ndarray, quad_codes: np.ndarray) -> np.ndarray:
+    """Quad rows of voxel_mesh_extract -> triangles int32 (2 Q,3) into the ascending `vertex_keys`, in the order of the
+    rows.  The quad of owner cell i along axis a joins the cells q0 = i - e_b - e_c, q1 = i - e_c, q2 = i, q3 = i - e_b
+    (b = (a + 1) % 3, c = (a + 2) % 3; the kernel emits a quad only when those fields stay >= 1, so the subtraction
+    never borrows), counter-clockwise seen from +a; split on the diagonal q0 q2, reversed under code bit 2."""
+    if len(quad_keys) == 0:
+        return np.zeros((0, 3), np.int32)
+    qk = np.asarray(quad_keys).view(np.uint64)
+    axis = np.asarray(quad_codes, np.int64) & 3
+    flip = (np.asarray(quad_codes, np.int64) >> 2 & 1).astype(bool)
+    step = np.array([1 << 42, 1 << 21, 1], np.uint64)
+    sb, sc = step[(axis + 1) % 3], step[(axis + 2) % 3]
+    ring = np.stack([qk - sb - sc, qk - sc, qk, qk - sb], 1)
+    idx = np.searchsorted(vertex_keys, ring)
+    if len(vertex_keys) == 0 or not np.array_equal(vertex_keys[np.minimum(idx, len(vertex_keys) - 1)], ring):
+        raise RuntimeError("dense mesh: a quad names a cell without a vertex")
+    q0, q1, q2, q3 = idx[:, 0], idx[:, 1], idx[:, 2], idx[:, 3]
+    t1 = np.where(flip[:, None], np.stack([q0, q2, q1], 1), np.stack([q0, q1, q2], 1))
+    t2 = np.where(flip[:, None], np.stack([q0, q3, q2], 1), np.stack([q0, q2, q3], 1))
+    return np.stack([t1, t2], 1).reshape(-1, 3).astype(np.int32)
+
+
+class MapMesher:
+    """A triangle mesh of a fused voxel table (csrc/voxel_mesh.hip; f64 / integer arithmetic, reproduced byte for byte
+    by tests/dense_mesh_ref.py): an oriented-point signed field (Hoppe '92) from the voxels' centroids and normals,
+    f(corner) = the mean of n . (corner - centroid) over the source voxels among the 8 that touch the corner, meshed by
+    surface nets: one vertex per cell with a sign change on one of its edges (the mean of the crossings), one quad per
+    crossing edge, split on a fixed diagonal and wound counter-clockwise seen from the side the normals face.  A source
+    voxel is a kept voxel with a non-zero normal sum; a corner without one is undefined and crosses nothing.
+
+    The cell table (8 B key + 32 B vertex per slot) is sized by growing: a first pass counts the source voxels S, the
+    table starts at the power of two >= 8 S slots (a surface has about 3 cells per voxel) and doubles, re-inserting,
+    while an insert found no slot (within the kernel's 256 probes) or more than half of it is used; at the power of two
+    >= 54 S (27 cells per voxel, half full) it stops growing.  That is 320-640 B per source voxel in the common case.  cell_capacity fixes the size
+    instead: no growing, and an insert without a slot raises.
+
+    Limitations: a thin wall seen from both sides has cancelling normals and meshes badly; a cell face whose four
+    edges all cross gives a non-manifold edge (counted: ambiguous_faces); no hole filling, smoothing or decimation; like
+    the cloud, the mesh follows the chunks' similarities, not per-view corrections of a bundle adjustment."""
+
+    FIRST_CELLS_PER_SOURCE = 4      # the first table has >= 2 x this many slots per source voxel
+
+    def __init__(self, cell_capacity: Optional[int] = None):
+        if cell_capacity is not None:
+            c = int(cell_capacity)
+            if c <= 0 or c & (c - 1):
+                raise ValueError(f"cell_capacity must be a power of two, got {cell_capacity!r}")
+            cell_capacity = c
+        self.cell_capacity = cell_capacity
+        self.last_stats: Optional[Dict[str, int]] = None
+        self.error: Optional[Exception] = None      # try_apply's failure, for the caller that wanted the mesh
+
+    def _cell_table(self, table, nacc, keep, stats) -> torch.Tensor:
+        """The filled cell table; stats[:3] are its counters."""
+        if self.cell_capacity is not None:
+            ccap = limit = self.cell_capacity
+        else:
+            ops.voxel_mesh_cells(table, nacc, keep, None, stats)
+            sources = int(stats[0].item())
+            ccap = ops.voxel_capacity(self.FIRST_CELLS_PER_SOURCE * sources)
+            limit = ops.voxel_capacity(27 * sources)
+        while True:
+            cells = torch.empty(ccap, dtype=torch.int64, device=table.device)
+            ops.voxel_mesh_cells(table, nacc, keep, cells, stats)
+            _, used, overflow = (int(x) for x in stats[:3].tolist())
+            if ccap >= limit or not (overflow or 2 * used > ccap):
+                if overflow:
+                    raise RuntimeError(f"dense mesh: the cell table of {ccap} slots is too small: {overflow} inserts "
+                                       f"found no slot ({used} cells inserted)")
+                return cells
+            del cells
+            ccap *= 2
+
+    def apply(self, fuser: "VoxelFuser", normals_acc, keep: Optional[torch.Tensor] = None) -> Dict[str, np.ndarray]:
+        """fuser: the fused table; normals_acc: its NormalAccumulator (or the nacc tensor); keep: MapCleaner.apply's mask.
+        -> {vertices f32 (V,3), normals f32 (V,3), colors u8 (V,3), faces i32 (F,3), keys u64 (V,)}: the vertices in
+        ascending order of their cell keys, the faces by (owner cell key, axis), two per quad.  Sets last_stats =
+        {sources, cells, vertices, quads, overflow, ambiguous_faces, cell_capacity, cell_table_bytes}."""
+        if fuser.table is None:
+            fuser.reserve(0)
+        nacc = normals_acc.nacc if isinstance(normals_acc, NormalAccumulator) else normals_acc
+        if nacc is None:
+            raise ValueError("dense mesh: the normal sums are empty (NormalAccumulator.clear() was never called)")
+        table, dev = fuser.table, fuser.device
+        stats = torch.zeros(12, dtype=torch.int64, device=dev)
+        cells = self._cell_table(table, nacc, keep, stats)
+        ccap = int(cells.numel())
+        verts = torch.empty(ccap, ops.VOXEL_MESH_VERT_WORDS, dtype=torch.int32, device=dev)
+        ops.voxel_mesh_vertices(table, nacc, keep, cells, verts, fuser.voxel_size, stats)
+        V, Q = int(stats[3].item()), int(stats[4].item())
+        if V >= 1 << 31:
+            raise RuntimeError(f"dense mesh: {V} vertices do not fit int32 face indices")
+        vk, xyz, nrm, rgb, qk, qc = ops.voxel_mesh_extract(cells, verts, V, Q, stats)
+        st = dict(zip(ops.VOXEL_MESH_COUNTERS, (int(x) for x in stats.tolist())))
+        if (st["vertex_rows"], st["quad_rows"]) != (V, Q) or st["vertex_rows_unstored"] or st["quad_rows_unstored"]:
+            raise RuntimeError(f"dense mesh: the extraction does not match the vertex pass: {st}")
+        self.last_stats = {"sources": st["sources"], "cells": st["cells"], "vertices": V, "quads": Q,
+                           "overflow": st["overflow"], "ambiguous_faces": st["ambiguous_faces"], "cell_capacity": ccap,
+                           "cell_table_bytes": ccap * ops.VOXEL_MESH_CELL_BYTES}
+        keys, xyz, nrm, rgb = _key_sorted(vk.cpu().numpy().view(np.uint64), xyz.cpu().numpy(), nrm.cpu().numpy(),
+                                          rgb.cpu().numpy())
+        qk, qc = qk.cpu().numpy().view(np.uint64), qc.cpu().numpy()
+        order = np.lexsort((qc & 3, qk))
+        return {"vertices": xyz, "normals": nrm, "colors": rgb, "faces": quad_faces(keys, qk[order], qc[order]),
+                "keys": keys}
+
+    def try_apply(self, fuser: "VoxelFuser", normals_acc, keep: Optional[torch.Tensor] = None) -> Optional[Dict]:
+        """apply() for a caller that fuses the map and the mesh in one go: a failure is kept in self.error (None after
+        a success) and None returned, so the map is still delivered; whoever consumes the mesh raises it."""
+        self.error = None
+        try:
+            return self.apply(fuser, normals_acc, keep)
+        except Exception as e:  # noqa: BLE001
+            self.error = e
+            return None
+
+    def summary(self) -> str:
+        st = self.last_stats
+        return (f"{st['vertices']} vertices, {2 * st['quads']} triangles from {st['sources']} voxels "
+                f"({st['cells']} cells, {st['ambiguous_faces']} ambiguous faces)")
+
+
 class ChunkCloudBuilder:
     """Stage 1 for the chunk creator: queue() fuses one chunk's maps into a voxel cloud on the current stream and starts
     its host copy, collect() turns that into chunk['dense_cloud'].  The table's and the filter's counters travel in the
@@ -532,15 +657,16 @@ def chunk_transform(chunk: Dict) -> torch.Tensor:
     return torch.eye(4, dtype=torch.float64) if G is None else torch.as_tensor(G, dtype=torch.float64).reshape(4, 4)
 
 
-def fuse_chunk_clouds_with_normals(chunks: Iterable[Dict], voxel_size: float, device="cuda",
-                                   cleaner: Optional[MapCleaner] = None
-                                   ) -> Tuple[np.ndarray, np.ndarray, np.ndarray, Optional[np.ndarray]]:
+def fuse_chunk_clouds_with_mesh(chunks: Iterable[Dict], voxel_size: float, device="cuda",
+                                cleaner: Optional[MapCleaner] = None, mesher: Optional[MapMesher] = None
+                                ) -> Tuple[np.ndarray, np.ndarray, np.ndarray, Optional[np.ndarray], Optional[Dict]]:
     """Every chunk's dense_cloud moved by chunk_transform() and fused, weighted by its voxel weights ->
-    (points f32 (V,3), colors u8 (V,3), weights i32 (V,), normals f32 (V,3) or None) in ascending key order.  Chunks
-    without a cloud are skipped.  cleaner: its filters decide on the fused table which voxels are extracted (one line
-    with the counts is printed).  Normals: when every cloud carries `normals`, each cloud's are rotated by its
-    similarity's rotation and fused weighted by its `normal_weights`; when only some do, one line says so and the map
-    has none."""
+    (points f32 (V,3), colors u8 (V,3), weights i32 (V,), normals f32 (V,3) or None, mesh or None), the map in ascending
+    key order.  Chunks without a cloud are skipped.  cleaner: its filters decide on the fused table which voxels are
+    extracted (one line with the counts is printed).  Normals: when every cloud carries `normals`, each cloud's are
+    rotated by its similarity's rotation and fused weighted by its `normal_weights`; when only some do, one line says so
+    and the map has none.  mesher: MapMesher.apply's mesh of the same fused table, after the same keep mask; without
+    normals one line says so and the mesh is None; when the mesher fails the mesh is None and mesher.error holds why."""
     device = torch.device(device)
     clouds = [(c["dense_cloud"], chunk_transform(c)) for c in chunks if c.get("dense_cloud") is not None]
     fuser = VoxelFuser(voxel_size, device)
@@ -576,7 +702,22 @@ def fuse_chunk_clouds_with_normals(chunks: Iterable[Dict], voxel_size: float, de
         if not np.array_equal(nout["keys"], out["keys"]):
             raise RuntimeError("dense normals: the normal rows have other keys than the map's")
         normals = nout["normals"]
-    return out["points"], out["colors"], out["weights"], normals
+    mesh = None
+    if mesher is not None and acc is not None:
+        mesh = mesher.try_apply(fuser, acc, keep)
+        if mesh is not None:
+            print(f"   🕸️  Dense mesh: {mesher.summary()}")
+    elif mesher is not None:
+        print("   ℹ️  The dense clouds carry no normals (create the chunks with dense_normals): no dense mesh")
+    return out["points"], out["colors"], out["weights"], normals, mesh
+
+
+def fuse_chunk_clouds_with_normals(chunks: Iterable[Dict], voxel_size: float, device="cuda",
+                                   cleaner: Optional[MapCleaner] = None
+                                   ) -> Tuple[np.ndarray, np.ndarray, np.ndarray, Optional[np.ndarray]]:
+    """fuse_chunk_clouds_with_mesh without the mesh: (points f32 (V,3), colors u8 (V,3), weights i32 (V,), normals f32
+    (V,3) or None when the clouds carry none)."""
+    return fuse_chunk_clouds_with_mesh(chunks, voxel_size, device, cleaner)[:4]
 
 
 def fuse_chunk_clouds(chunks: Iterable[Dict], voxel_size: float, device="cuda",

@@ -6,6 +6,8 @@ Pi3SLAMOnline.chunk_reconstructions).  Files and formats mirror slam/offline_rec
   trajectory_tum.txt      the de-duplicated trajectory: first occurrence of a view name wins (unique_views)
   dense_points.ply        the chunks' dense clouds fused in the world frame (fuse_dense_map; dense_map.py), cleaned by a
                           dense_map.MapCleaner when one is given; with nx ny nz when the clouds carry normals
+  dense_mesh.ply          (dense_mesh) a triangle mesh of the same fused table, after the same cleaner
+                          (dense_map.MapMesher); needs the normals
   renders/                depth / colour images of that map, overview.png, cameras.json (write_renders; render.py); with
                           normals also normal_<frame>.png, shaded_<frame>.png and overview_shaded.png
 
@@ -69,6 +71,30 @@ def write_ply_normals(points: np.ndarray, normals: np.ndarray, colors: np.ndarra
         rec = np.empty(len(points), dtype=[("xyz", "<f4", 3), ("n", "<f4", 3), ("rgb", "u1", 3)])
         rec["xyz"], rec["n"], rec["rgb"] = points, normals, rgb
         f.write(rec.tobytes())
+
+
+def write_mesh_ply(vertices: np.ndarray, normals: np.ndarray, colors: np.ndarray, faces: np.ndarray, path: str) -> None:
+    """Binary little-endian PLY of a triangle mesh: vertex x y z nx ny nz (float) red green blue (uchar), then
+    `element face` with `property list uchar int vertex_indices`, three indices per face."""
+    vertices = np.asarray(vertices, np.float32).reshape(-1, 3)
+    normals = np.asarray(normals, np.float32).reshape(-1, 3)
+    rgb = np.asarray(colors, np.uint8).reshape(-1, 3)
+    faces = np.asarray(faces, np.int32).reshape(-1, 3)
+    if len(normals) != len(vertices) or len(rgb) != len(vertices):
+        raise ValueError(f"{len(normals)} normals and {len(rgb)} colours for {len(vertices)} vertices")
+    if faces.size and (faces.min() < 0 or faces.max() >= len(vertices)):
+        raise ValueError(f"a face indexes outside the {len(vertices)} vertices")
+    with open(path, "wb") as f:
+        f.write((f"ply\nformat binary_little_endian 1.0\nelement vertex {len(vertices)}\nproperty float x\n"
+                 "property float y\nproperty float z\nproperty float nx\nproperty float ny\nproperty float nz\n"
+                 "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+                 f"element face {len(faces)}\nproperty list uchar int vertex_indices\nend_header\n").encode())
+        rec = np.empty(len(vertices), dtype=[("xyz", "<f4", 3), ("n", "<f4", 3), ("rgb", "u1", 3)])
+        rec["xyz"], rec["n"], rec["rgb"] = vertices, normals, rgb
+        f.write(rec.tobytes())
+        tri = np.empty(len(faces), dtype=[("n", "u1"), ("v", "<i4", 3)])
+        tri["n"], tri["v"] = 3, faces
+        f.write(tri.tobytes())
 
 
 class View(NamedTuple):
@@ -157,18 +183,26 @@ class DenseMap(NamedTuple):
     voxel_size: float
 
 
-def fuse_dense_map_normals(chunks: Sequence[Dict], device, cleaner=None) -> Tuple[Optional[DenseMap], Optional[np.ndarray]]:
+def fuse_dense_map_mesh(chunks: Sequence[Dict], device, cleaner=None, mesher=None
+                        ) -> Tuple[Optional[DenseMap], Optional[np.ndarray], Optional[Dict]]:
     """The chunks' dense clouds (chunks created with a dense voxel size) fused in the world frame -> (the map, its
-    normals f32 (V,3) row for row, or None when the clouds carry none); (None, None) when no chunk carries a cloud.
-    The voxel size is the first cloud's: the world frame is chunk 0's frame.  cleaner: a dense_map.MapCleaner whose
-    filters choose the voxels of the map (None: all of them)."""
+    normals f32 (V,3) row for row, or None when the clouds carry none, the mesh); (None, None, None) when no chunk
+    carries a cloud.  The voxel size is the first cloud's: the world frame is chunk 0's frame.  cleaner: a
+    dense_map.MapCleaner whose filters choose the voxels of the map (None: all of them).  mesher: a dense_map.MapMesher;
+    the mesh is its apply() on the same fused table after the same filters, None without one, without normals (one
+    line says so) or when it failed (mesher.error)."""
     first = next((d["dense_cloud"] for d in chunks if d.get("dense_cloud") is not None), None)
     if first is None:
-        return None, None
-    from .dense_map import fuse_chunk_clouds_with_normals
+        return None, None, None
+    from .dense_map import fuse_chunk_clouds_with_mesh
     voxel = float(first["voxel_size"])
-    pts, cols, w, normals = fuse_chunk_clouds_with_normals(chunks, voxel, device, cleaner)
-    return DenseMap(pts, cols, w, voxel), normals
+    pts, cols, w, normals, mesh = fuse_chunk_clouds_with_mesh(chunks, voxel, device, cleaner, mesher)
+    return DenseMap(pts, cols, w, voxel), normals, mesh
+
+
+def fuse_dense_map_normals(chunks: Sequence[Dict], device, cleaner=None) -> Tuple[Optional[DenseMap], Optional[np.ndarray]]:
+    """fuse_dense_map_mesh without the mesh: (the map, its normals or None); (None, None) without dense clouds."""
+    return fuse_dense_map_mesh(chunks, device, cleaner)[:2]
 
 
 def fuse_dense_map(chunks: Sequence[Dict], device, cleaner=None) -> Optional[DenseMap]:
@@ -185,6 +219,13 @@ def write_dense_points(dense: DenseMap, path: str, normals: Optional[np.ndarray]
         write_ply_normals(dense.points, normals, np.asarray(dense.colors, np.uint8), path)
         print(f"✅ Saved dense map with {len(dense.points)} voxels ({dense.voxel_size} m) and normals to: {path}")
     return len(dense.points)
+
+
+def write_dense_mesh(mesh: Dict, path: str) -> int:
+    """dense_mesh.ply from MapMesher.apply's mesh; returns the triangle count."""
+    write_mesh_ply(mesh["vertices"], mesh["normals"], mesh["colors"], mesh["faces"], path)
+    print(f"✅ Saved dense mesh with {len(mesh['vertices'])} vertices and {len(mesh['faces'])} triangles to: {path}")
+    return len(mesh["faces"])
 
 
 def write_renders(chunks: Sequence[Dict], dense: Optional[DenseMap], out_dir: str, every: Optional[int], overview: bool,
@@ -261,10 +302,11 @@ def write_renders(chunks: Sequence[Dict], dense: Optional[DenseMap], out_dir: st
 
 def write_outputs(chunks: Sequence[Dict], output_dir: str, device="cuda", render_every: Optional[int] = None,
                   render_overview: bool = False, render_min_weight: int = 1,
-                  render_splat_scale: float = 1.0, dense_cleaner=None) -> Optional[Dict[str, float]]:
+                  render_splat_scale: float = 1.0, dense_cleaner=None,
+                  dense_mesh: bool = False) -> Optional[Dict[str, float]]:
     """Every output file of stage 2 under output_dir; a file that fails is reported and the others are still written.
     Returns the seconds of write_renders when renders were written.  dense_cleaner (dense_map.MapCleaner): the dense
-    map of the PLY and of the renders is the cleaned one."""
+    map of the PLY and of the renders is the cleaned one.  dense_mesh: also dense_mesh.ply, the mesh of that map."""
     try:
         pts, cols = sparse_points_colors(chunks)
         if pts.size > 0:
@@ -282,13 +324,28 @@ def write_outputs(chunks: Sequence[Dict], output_dir: str, device="cuda", render
         save_trajectory_tum(chunks, os.path.join(output_dir, "trajectory_tum.txt"), integer_timestamp=True)
     except Exception as e:  # noqa: BLE001
         print(f"❌ Failed to save TUM trajectory: {e}")
-    dense = normals = None
+    dense = normals = mesh = mesher = None
+    if dense_mesh:
+        from .dense_map import MapMesher
+        mesher = MapMesher()
     try:
-        dense, normals = fuse_dense_map_normals(chunks, device, dense_cleaner)
+        dense, normals, mesh = fuse_dense_map_mesh(chunks, device, dense_cleaner, mesher)
         if dense is not None:
             write_dense_points(dense, os.path.join(output_dir, "dense_points.ply"), normals)
     except Exception as e:  # noqa: BLE001
         print(f"❌ Failed to save the dense map: {e}")
+        if dense is None:
+            mesher = None       # the fusion itself failed: no table, no mesh, and the line above says why
+    if mesher is not None:
+        try:
+            if mesher.error is not None:
+                raise mesher.error
+            if mesh is not None:
+                write_dense_mesh(mesh, os.path.join(output_dir, "dense_mesh.ply"))
+            elif dense is None:
+                print("   ℹ️  No dense clouds in the chunks (create them with a dense voxel size): no dense mesh")
+        except Exception as e:  # noqa: BLE001
+            print(f"❌ Failed to save the dense mesh: {e}")
     if render_every is not None or render_overview:
         try:       # the renders draw the map that was just fused for the PLY
             done = write_renders(chunks, dense, os.path.join(output_dir, "renders"), render_every, render_overview,

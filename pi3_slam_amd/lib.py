@@ -81,6 +81,9 @@ SIGNATURES = {
     "pi3_voxel_fuse_point_normals": [_vp, _l, _vp, _vp, _vp, _vp, _vp, _l, _f, _vp, _vp],
     "pi3_voxel_extract_normals": [_vp, _l, _vp, _vp, _vp, _vp, _vp, _l, _vp, _vp],
     "pi3_render_shade": [_vp, _vp, _l, _vp, _i, _i, _i, _vp, _vp, _vp, _vp],
+    "pi3_voxel_mesh_cells": [_vp, _l, _vp, _vp, _vp, _l, _vp, _vp],
+    "pi3_voxel_mesh_vertices": [_vp, _l, _vp, _vp, _vp, _l, _d, _vp, _vp, _vp],
+    "pi3_voxel_mesh_extract": [_vp, _l, _vp, _vp, _vp, _vp, _vp, _l, _vp, _vp, _l, _vp, _vp],
     "pi3_set_knob": [C.c_char_p, _l],
     "pi3_get_knob": [C.c_char_p, C.POINTER(_l)],
     "pi3_unset_knob": [C.c_char_p],

@@ -307,6 +307,20 @@ class Pi3SLAMOnline:
         dense, normals = self._fused_map()
         return export.write_dense_points(dense, save_path, normals)
 
+    def save_dense_mesh(self, save_path: str) -> Optional[int]:
+        """A triangle mesh of the fused dense map (dense_map.MapMesher: surface nets on the voxel lattice, after the
+        dense_min_* filters) -> a PLY with vertex normals and colours; returns the triangle count.  The clouds must
+        carry normals (dense_normals): without them one line says so, no file is written and None is returned."""
+        from .dense_map import MapMesher
+        mesher = MapMesher()
+        dense, _, mesh = export.fuse_dense_map_mesh(self.chunk_reconstructions, str(self.device), self.dense_cleaner,
+                                                    mesher)
+        if dense is None:
+            raise RuntimeError("no dense clouds: construct Pi3SLAMOnline with dense_voxel_size")
+        if mesher.error is not None:
+            raise mesher.error
+        return export.write_dense_mesh(mesh, save_path) if mesh is not None else None
+
     def save_renders(self, out_dir: str, every: Optional[int] = 10, overview: bool = True, min_weight: int = 1,
                      splat_scale: float = 1.0) -> int:
         """Depth / colour images of the dense map from every `every`-th view, overview.png and cameras.json under

@@ -941,6 +941,75 @@ def render_shade(index: torch.Tensor, normals: torch.Tensor, cams: torch.Tensor,
     return rgb, shaded
 
 
+# ------------------------------------------------------------------------- surface mesh of the voxel map (voxel_mesh.hip)
+VOXEL_MESH_VERT_WORDS = 8   # x y z nx ny nz (fp32 bits), rgb | flags << 24, spare: uint32 per slot of the cell table
+VOXEL_MESH_CELL_BYTES = 8 + 4 * VOXEL_MESH_VERT_WORDS
+VOXEL_MESH_COUNTERS = ("sources", "cells", "overflow", "vertices", "quads", "ambiguous_faces", "vertex_rows", "quad_rows",
+                       "vertex_rows_unstored", "quad_rows_unstored")
+
+
+def _mesh_check(table: torch.Tensor, nacc: torch.Tensor, keep: Optional[torch.Tensor], stats: torch.Tensor) -> None:
+    _nacc_check(table, nacc, stats)
+    assert stats.numel() >= 12
+    if keep is not None:
+        _slot_array(keep, table, torch.uint8)
+
+
+def _mesh_cells_check(cells: torch.Tensor, device) -> int:
+    cap = int(cells.numel())
+    assert cells.dtype == torch.int64 and cells.is_contiguous() and cells.device == device
+    assert cap > 0 and cap & (cap - 1) == 0, "the cell table's capacity must be a power of two"
+    return cap
+
+
+def voxel_mesh_cells(table: torch.Tensor, nacc: torch.Tensor, keep: Optional[torch.Tensor],
+                     cells: Optional[torch.Tensor], stats: torch.Tensor) -> None:
+    """The cell table of the mesh: cells int64 (cell_capacity,) is cleared and gets the keys of the 27 cells around every
+    source voxel.  stats int64 (12,): [0] sources, [1] cells, [2] inserts that found no slot (the caller grows the table
+    and calls again; nothing is written out of bounds).  cells None: only [0] is counted."""
+    lib = _L.load()
+    _mesh_check(table, nacc, keep, stats)
+    ccap = _mesh_cells_check(cells, table.device) if cells is not None else 0
+    rc = lib.pi3_voxel_mesh_cells(table.data_ptr(), table.numel() // 8, nacc.data_ptr(), _L.ptr(keep), _L.ptr(cells),
+                                  ccap, stats.data_ptr(), _L.stream_ptr())
+    _L.check(rc, "pi3_voxel_mesh_cells")
+
+
+def voxel_mesh_vertices(table: torch.Tensor, nacc: torch.Tensor, keep: Optional[torch.Tensor], cells: torch.Tensor,
+                        verts: torch.Tensor, voxel_size: float, stats: torch.Tensor) -> None:
+    """One vertex per cell of voxel_mesh_cells' table with a sign change -> verts int32 (cell_capacity, 8); stats[3:6]
+    = vertices, quads, ambiguous faces."""
+    lib = _L.load()
+    _mesh_check(table, nacc, keep, stats)
+    ccap = _mesh_cells_check(cells, table.device)
+    assert verts.dtype == torch.int32 and verts.is_contiguous() and verts.device == table.device
+    assert verts.numel() == VOXEL_MESH_VERT_WORDS * ccap, "verts must have 8 int32 per slot of the cell table"
+    rc = lib.pi3_voxel_mesh_vertices(table.data_ptr(), table.numel() // 8, nacc.data_ptr(), _L.ptr(keep),
+                                     cells.data_ptr(), ccap, float(voxel_size), verts.data_ptr(), stats.data_ptr(),
+                                     _L.stream_ptr())
+    _L.check(rc, "pi3_voxel_mesh_vertices")
+
+
+def voxel_mesh_extract(cells: torch.Tensor, verts: torch.Tensor, max_vertices: int, max_quads: int, stats: torch.Tensor):
+    """-> device (vkeys int64 (V,), vxyz f32 (V,3), vnrm f32 (V,3), vrgb uint8 (V,3), qkeys int64 (Q,), qcodes int32 (Q,))
+    with V = max_vertices and Q = max_quads rows, unordered; stats[6:10] = vertex rows, quad rows and the rows of either
+    kind that did not fit."""
+    lib = _L.load()
+    ccap = _mesh_cells_check(cells, cells.device)
+    assert verts.dtype == torch.int32 and verts.is_contiguous() and verts.device == cells.device
+    assert verts.numel() == VOXEL_MESH_VERT_WORDS * ccap
+    assert stats.dtype == torch.int64 and stats.is_contiguous() and stats.numel() >= 12 and stats.device == cells.device
+    V, Q, dev = max(int(max_vertices), 0), max(int(max_quads), 0), cells.device
+    out = (torch.empty(V, device=dev, dtype=torch.int64), torch.empty(V, 3, device=dev, dtype=torch.float32),
+           torch.empty(V, 3, device=dev, dtype=torch.float32), torch.empty(V, 3, device=dev, dtype=torch.uint8),
+           torch.empty(Q, device=dev, dtype=torch.int64), torch.empty(Q, device=dev, dtype=torch.int32))
+    ptr = [t.data_ptr() if t.numel() else None for t in out]
+    rc = lib.pi3_voxel_mesh_extract(cells.data_ptr(), ccap, verts.data_ptr(), ptr[0], ptr[1], ptr[2], ptr[3], V, ptr[4],
+                                    ptr[5], Q, stats.data_ptr(), _L.stream_ptr())
+    _L.check(rc, "pi3_voxel_mesh_extract")
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------- device guard
 # Every wrapper launches on torch's CURRENT stream, i.e. on the current device.  A tensor that lives on another card
 # (e.g. 'cuda:0' data in a rank bound to cuda:3) would hand that card's pointers to a kernel running elsewhere: fail

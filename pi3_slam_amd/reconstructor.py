@@ -35,8 +35,11 @@ class OfflineReconstructor:
                  render_every: Optional[int] = None, render_overview: bool = False, render_min_weight: int = 1,
                  render_splat_scale: float = 1.0, dense_min_weight: Optional[int] = None,
                  dense_min_support: Optional[int] = None, dense_support_radius: int = 1,
-                 dense_min_component: Optional[int] = None):
+                 dense_min_component: Optional[int] = None, dense_mesh: bool = False):
         self.chunk_dir, self.output_dir = chunk_dir, output_dir
+        # dense_mesh: after dense_points.ply also dense_mesh.ply, a triangle mesh of the same fused (and cleaned) table
+        # (dense_map.MapMesher); the chunks must carry normals (created with dense_normals)
+        self.dense_mesh = bool(dense_mesh)
         # dense_min_weight / dense_min_support / dense_min_component: filters on the fused dense map before it is written
         # and rendered (dense_map.MapCleaner); all off by default, and then no cleaner exists
         from .dense_map import MapCleaner
@@ -175,7 +178,8 @@ class OfflineReconstructor:
         if rank == 0:
             self.reconstructions = done
             seconds = export.write_outputs(done, self.output_dir, self.device, self.render_every, self.render_overview,
-                                           self.render_min_weight, self.render_splat_scale, self.dense_cleaner)
+                                           self.render_min_weight, self.render_splat_scale, self.dense_cleaner,
+                                           self.dense_mesh)
             if seconds is not None:
                 self.render_seconds = seconds
         if grouped:

@@ -24,7 +24,15 @@
      and extract in the same run of leg 1 (the zeroing of the 32-byte-per-slot side array as well), with the counters;
      and a creator leg with dense_normals on.
 
-Prints one JSON line.  Usage: python tools/dense_fusion_timing.py [--voxel 0.02] [--rounds 3] [--chunks 4] [--consistency] [--clean] [--normals]"""
+  6. --mesh: the surface mesh (csrc/voxel_mesh.hip, dense_map.MapMesher) on the table of leg 1 with its pixel normals
+     and on the synthetic box map of leg 4 (outward normals on the faces, none on the floaters), HIP events, median of
+     20 after 3 warm-up runs: the cell insert (with the clearing of the cell table), the vertex kernel and the
+     extraction at the cell-table size MapMesher grows to, beside voxel_support at radius 1 on the same table; with the
+     counters, the cell table's bytes and, for the vertex kernel, the counted bytes (27 probes of a 64-byte slot per
+     cell, the first slot of each chain only, 32 B of normal sums per source found, the 8-byte key read and the 32-byte
+     vertex written per slot) and the rate they give.
+
+Prints one JSON line.  Usage: python tools/dense_fusion_timing.py [--voxel 0.02] [--rounds 3] [--chunks 4] [--consistency] [--clean] [--normals] [--mesh]"""
 from __future__ import annotations
 
 import argparse
@@ -92,9 +100,49 @@ def clean_times(fz, reps: int = 20):
     return res | {"sweeps": sweeps, "table_slots": cap, "side_bytes_per_slot": 1 + 8 + 4, **c}
 
 
-def synthetic_box_map(voxel: float, dev: str, side: int = 410, seed: int = 0):
-    """About 1 M voxels: the six faces of a box of `side` voxels, one point per voxel, and 1 % floaters inside."""
-    from pi3_slam_amd.dense_map import VoxelFuser
+def mesh_times(fz, nacc, reps: int = 20):
+    """The mesh kernels on a filled VoxelFuser with its normal sums, at the cell-table size MapMesher settles on."""
+    from pi3_slam_amd import ops
+    from pi3_slam_amd.dense_map import MapMesher
+    mesher = MapMesher()
+    mesher.apply(fz, nacc)
+    st = dict(mesher.last_stats)
+    dev, cap, ccap = fz.device, fz.capacity, st["cell_capacity"]
+    cells = torch.empty(ccap, dtype=torch.int64, device=dev)
+    verts = torch.empty(ccap, ops.VOXEL_MESH_VERT_WORDS, dtype=torch.int32, device=dev)
+    stats = torch.zeros(12, dtype=torch.int64, device=dev)
+    keep = torch.empty(cap, dtype=torch.uint8, device=dev)
+    counters = torch.zeros(8, dtype=torch.int64, device=dev)
+    t = {"cell_insert_ms": [], "vertices_ms": [], "extract_ms": [], "support_r1_ms": []}
+    for i in range(3 + reps):
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
+        e[0].record()
+        ops.voxel_mesh_cells(fz.table, nacc, None, cells, stats)
+        e[1].record()
+        ops.voxel_mesh_vertices(fz.table, nacc, None, cells, verts, fz.voxel_size, stats)
+        e[2].record()
+        ops.voxel_mesh_extract(cells, verts, st["vertices"], st["quads"], stats)
+        e[3].record()
+        ops.voxel_support(fz.table, 1, 1, 4, keep, None, counters)
+        e[4].record()
+        torch.cuda.synchronize()
+        if i >= 3:
+            for k, (a, b) in zip(t, zip(e, e[1:])):
+                t[k].append(a.elapsed_time(b))
+    res = {k: float(np.median(v)) for k, v in t.items()} | {k + "_minmax": [float(np.min(v)), float(np.max(v))]
+                                                           for k, v in t.items()}
+    c = dict(zip(ops.VOXEL_CLEAN_COUNTERS, (int(x) for x in counters.tolist())))
+    vb = st["cells"] * 27 * 64 + st["sources"] * 27 * 32 + ccap * (8 + 32)
+    sb = c["eligible"] * 26 * 64 + cap * 16
+    return res | st | {"table_slots": cap, "voxels": c["voxels"], "vertices_bytes": vb,
+                       "vertices_TBps": vb / (res["vertices_ms"] * 1e-3) / 1e12, "support_r1_bytes": sb,
+                       "support_r1_TBps": sb / (res["support_r1_ms"] * 1e-3) / 1e12}
+
+
+def synthetic_box_map(voxel: float, dev: str, side: int = 410, seed: int = 0, normals: bool = False):
+    """About 1 M voxels: the six faces of a box of `side` voxels, one point per voxel, and 1 % floaters inside.
+    normals: -> (the fuser, its NormalAccumulator) with the faces' outward normals; the floaters carry none."""
+    from pi3_slam_amd.dense_map import NormalAccumulator, VoxelFuser
     g = torch.Generator().manual_seed(seed)
     a = torch.arange(side)
     u, v = (x.reshape(-1) for x in torch.meshgrid(a, a, indexing="ij"))
@@ -108,10 +156,23 @@ def synthetic_box_map(voxel: float, dev: str, side: int = 410, seed: int = 0):
     pts = ((idx.double() + 0.5) * voxel).float().to(dev).contiguous()
     fz = VoxelFuser(voxel, dev)
     fz.fuse_points(pts, None, None)
-    return fz
+    if not normals:
+        return fz
+    n = side * side
+    nrm = torch.zeros(len(idx), 3)
+    for j in range(6):
+        nrm[j * n:(j + 1) * n, j // 2] = -1.0 if j % 2 == 0 else 1.0
+    nw = torch.zeros(len(idx), dtype=torch.int32)
+    nw[:6 * n] = 1
+    acc = NormalAccumulator(fz)
+    acc.clear()
+    acc.add_points(pts, nrm.to(dev).contiguous(), nw.to(dev).contiguous(),
+                   torch.eye(3, dtype=torch.float64, device=dev).reshape(9).contiguous())
+    return fz, acc
 
 
-def kernel_times(voxel: float, dev: str, reps: int = 20, clean: bool = False, normals: bool = False):
+def kernel_times(voxel: float, dev: str, reps: int = 20, clean: bool = False, normals: bool = False,
+                 mesh: bool = False):
     import synth_sequence as ss
     from pi3_slam_amd.chunk_creator import OfflineChunkCreator
     from pi3_slam_amd.dense_map import NormalAccumulator, VoxelFuser
@@ -156,6 +217,12 @@ def kernel_times(voxel: float, dev: str, reps: int = 20, clean: bool = False, no
                               minmax_ms={k: [float(np.min(v)), float(np.max(v))] for k, v in t.items()})
     if clean:
         out["clean"] = clean_times(fz, reps)
+    if mesh:
+        if acc is None:
+            acc = NormalAccumulator(fz)
+            acc.clear()
+            acc.add_pixels(pts, conf, masks, 0.5)
+        out["mesh"] = mesh_times(fz, acc.nacc, reps)
     return out
 
 
@@ -272,10 +339,15 @@ def main():
                                                          "a synthetic map of about 1 M voxels")
     ap.add_argument("--normals", action="store_true", help="also time the surface-normal kernels beside fuse_pixels and "
                                                            "extract, and a creator leg with dense_normals on")
+    ap.add_argument("--mesh", action="store_true", help="also time the surface-mesh kernels on the chunk's table and on "
+                                                        "a synthetic map of about 1 M voxels")
     a = ap.parse_args()
     dev = "cuda:0"
     torch.cuda.set_device(0)
-    out = {"voxel_size": a.voxel, "kernels": kernel_times(a.voxel, dev, clean=a.clean, normals=a.normals)}
+    out = {"voxel_size": a.voxel, "kernels": kernel_times(a.voxel, dev, clean=a.clean, normals=a.normals, mesh=a.mesh)}
+    if a.mesh:
+        fz, acc = synthetic_box_map(a.voxel, dev, normals=True)
+        out["mesh_synthetic"] = mesh_times(fz, acc.nacc)
     if a.clean:
         out["clean_synthetic"] = clean_times(synthetic_box_map(a.voxel, dev))
     if a.consistency:

@@ -402,6 +402,13 @@ int pi3_voxel_extract_kept(const void* table, long capacity, double voxel_size, 
  * NULL no neighbour is probed. */
 int pi3_voxel_support(const void* table, long capacity, unsigned long long min_weight, int radius, int min_support,
                       unsigned char* keep, int* support, unsigned long long* counters, void* stream);
+/* pi3_voxel_support with an exclude mask (uint8 [capacity]; the carved voxels of pi3_voxel_carve): an occupied slot
+ * with exclude[slot] != 0 is not eligible (keep 0, support -1) and is not counted as anybody's neighbour, so the
+ * components that follow are formed without it.  Everything else as above; also writes counters[6] = the occupied
+ * slots that exclude names (counters[0] still counts every occupied slot). */
+int pi3_voxel_support_excluding(const void* table, long capacity, unsigned long long min_weight, int radius,
+                                int min_support, unsigned char* keep, int* support, unsigned long long* counters,
+                                const unsigned char* exclude, void* stream);
 /* label uint64 [capacity] = the slot's key where keep != 0, all ones elsewhere. */
 int pi3_voxel_label_init(const void* table, long capacity, const unsigned char* keep, unsigned long long* label,
                          void* stream);
@@ -438,6 +445,38 @@ int pi3_dense_consistency(const float* points, const float* local_points, const 
                           const float* poses, const float* fxfycxcy, int N, int H, int W, float conf_logit_thr,
                           int radius, int stride, int min_views, float rel_tol, float* zplane, unsigned char* out_mask,
                           unsigned char* counts, unsigned long long* stats, void* stream);
+
+/* Depth keyframes of one chunk (csrc/dense_filter.hip), for pi3_voxel_carve: for the frames f = 0, every, 2 every, .. < N
+ * (Nk = ceil(N / every) of them) and the pixels (S y', S x') with S = pixel_stride in {1, 2, 4}, H' = ceil(H / S),
+ * W' = ceil(W / S):  depth[k][y'][x'] (fp16 bits, uint16 [Nk][H'][W']) = the local z of frame k every at that pixel,
+ * rounded to nearest even, when the pixel is a candidate of pi3_dense_consistency (mask != 0, conf > conf_logit_thr,
+ * world point finite, local z finite and > 0), else 0; a value that rounds to 0 or to inf is written as 0 ("this view
+ * has no opinion here").  *count (DEVICE uint64, zeroed by the call) = the non-zero samples.  conf and masks may be
+ * NULL.  N H W < 2^31; N == 0 zeroes the count and launches no kernel. */
+int pi3_dense_depth_planes(const float* points, const float* local_points, const float* conf, const unsigned char* masks,
+                           int N, int H, int W, float conf_logit_thr, int every, int pixel_stride,
+                           unsigned short* depth, unsigned long long* count, void* stream);
+
+/* ---- carving the fused map with depth keyframes (csrc/voxel_carve.hip): one decision per slot of a voxel table, f64
+ * without contraction, every product and sum rounded on its own in the order written.  The table is read only.
+ *   X = the centroid pi3_voxel_extract writes for the slot: voxel_size (k + U / (W 2^24)) in f64, rounded to fp32 and
+ *   widened again;
+ *   views f64 [M][20] in pi3_render_splat's camera layout (rigid world->camera 3x4 row-major r00 r01 r02 t0 .., fx, fy,
+ *   cx, cy, ortho flag = 0, 3 spare) with views[m][17] = s, the depth scale of view m (its plane's unit in map units);
+ *   planes fp16 bits [M][Hp][Wp] (pi3_dense_depth_planes), plane m for view m, S = pixel_stride in {1, 2, 4};
+ *   per view:  xc = ((r00 x + r01 y) + r02 z) + t0, likewise yc, zc;  no vote unless zc > 0 and all three finite;
+ *     u = fx (xc / zc) + cx, v = fy (yc / zc) + cy;  pu = rint(u / S), pv = rint(v / S) (half to even);  no vote unless
+ *     0 <= pu <= Wp - 1 and 0 <= pv <= Hp - 1;  zo = s (double)plane[pv][pu];  no vote when zo is 0 or not finite;
+ *     r = zc - zo, lim = rel_tol zo + margin;  agree when |r| <= lim, conflict when r < -lim (the view measured a
+ *     surface behind the voxel: it looked through it), else occluded: no vote;
+ *   carved uint8 [capacity] = conflict >= min_conflicts && conflict > agree (0 for an empty slot);
+ *   agree, conflict uint32 [capacity] (or NULL): the votes, not saturated;
+ *   counters: DEVICE uint64 [4] = occupied slots, carved, occupied slots no view voted on, spare; zeroed by the call.
+ * rel_tol finite and > 0, margin finite and >= 0, min_conflicts >= 1, M >= 0 (0: nothing is carved). */
+int pi3_voxel_carve(const void* table, long capacity, double voxel_size, const double* views, int M,
+                    const unsigned short* planes, int Hp, int Wp, int pixel_stride, double rel_tol, double margin,
+                    int min_conflicts, unsigned char* carved, unsigned* agree, unsigned* conflict,
+                    unsigned long long* counters, void* stream);
 
 /* ---- dense map -> camera views (csrc/render.hip): a z-buffered splat renderer for the voxel map.
  * points f32 [V][3] (the voxel centroids, in ascending key order), weights int32 [V] (or NULL: every voxel counts),

@@ -74,6 +74,10 @@ class OfflineCreatorConfig:
     dense_depth_tolerance: float = 0.03       # relative depth difference that still counts as the same surface
     dense_normals: bool = False               # with dense_voxel_size: the cloud also carries 'normals' / 'normal_weights',
                                               # a camera-facing surface normal per voxel (dense_map.NormalAccumulator)
+    dense_depth_every: Optional[int] = None   # set (with dense_voxel_size): the chunk also carries 'dense_depth', the fp16
+                                              # local z of every K-th frame's dense-map pixels, for stage 2's carving
+                                              # (dense_map.MapCarver); needs the intrinsics estimate
+    dense_depth_stride: int = 2               # those planes keep every S-th row and column (1, 2 or 4)
 
 
 _UV_CACHE: Dict = {}
@@ -423,9 +427,10 @@ class OfflineChunkCreator:
     def _queue_dense_cloud(self, pi3: Dict[str, torch.Tensor], masks: torch.Tensor, imgs: torch.Tensor,
                            out: Dict[str, torch.Tensor]):
         """The metric points into the dense cloud, queued before the next graph replay can reuse the static outputs.
-        Its consistency filter projects with the intrinsics that _queue_camera_parameters left in `out`."""
+        Its consistency filter projects with the intrinsics that _queue_camera_parameters left in `out`; its depth
+        keyframes are kept only when those exist."""
         fxy = None
-        if self._dense.filter is not None and "cam.fx" in out:
+        if (self._dense.filter is not None or self._dense.depth_every is not None) and "cam.fx" in out:
             fxy = torch.stack([out["cam." + k][0] for k in ("fx", "fy", "cx", "cy")], dim=1)
         return self._dense.queue(pi3["points"][0], pi3["local_points"][0], pi3["conf"][0], masks, imgs[0],
                                  pi3["camera_poses"][0], fxy, out)
@@ -470,6 +475,9 @@ class OfflineChunkCreator:
         result = self._chunk_result(fl, got, metrics)
         if fl.dense_job is not None:
             result["dense_cloud"] = self._dense.collect(fl.dense_job, got, metrics)
+            depth = self._dense.collect_depth(fl.dense_job, got, metrics)
+            if depth is not None:
+                result["dense_depth"] = depth
             fl.dense_job = None
         return result
 

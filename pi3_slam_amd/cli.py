@@ -45,6 +45,12 @@ CREATE_FLAGS: Sequence[Tuple[str, Dict]] = (
     ("--dense-view-radius", dict(type=int, default=3, help="neighbours i +- s * stride, s = 1..radius (1..16)")),
     ("--dense-view-stride", dict(type=int, default=2, help="frame step between the neighbours")),
     ("--dense-depth-tolerance", dict(type=float, default=0.03, help="relative depth difference that still agrees")),
+    ("--dense-depth-every", dict(type=int, default=None, help="with --dense-voxel-size: keep the depth of every K-th frame "
+                                                              "in the chunk file (chunk['dense_depth'], fp16) so that "
+                                                              "`reconstruct --dense-carve-min-conflicts` can carve the "
+                                                              "fused map with the views of every chunk")),
+    ("--dense-depth-stride", dict(type=int, default=2, choices=(1, 2, 4), help="those depth planes keep every S-th row "
+                                                                               "and column")),
 )
 CREATE_SWITCHES = (("--device-resize", "Resize + ToTensor on the GPU (loader workers decode only)"),
                    ("--hip-graph", "replay the per-chunk forward as one captured hipGraph"),
@@ -75,6 +81,18 @@ RECON_FLAGS: Sequence[Tuple[str, Dict]] = (
     ("--dense-min-component", dict(type=int, default=None, help="dense map: then drop 26-connected components of fewer "
                                                                 "than N voxels (e.g. 50 as a starting point, not a "
                                                                 "measured optimum)")),
+)
+# carving the fused dense map with the chunks' depth keyframes (dense_map.MapCarver): a table of its own beside the
+# cleaning flags above, added to the same sub-command
+RECON_CARVE_FLAGS: Sequence[Tuple[str, Dict]] = (
+    ("--dense-carve-min-conflicts", dict(type=int, default=None, help="dense map: first drop the voxels that at least N "
+                                                                      "depth keyframes of any chunk looked through, "
+                                                                      "and more than agree with them (chunks created "
+                                                                      "with --dense-depth-every; use with "
+                                                                      "--no-bundle-adjust; e.g. 3 as a starting point, "
+                                                                      "not a measured optimum)")),
+    ("--dense-carve-tolerance", dict(type=float, default=0.03, help="relative depth difference (plus one voxel size) "
+                                                                    "within which a keyframe agrees with a voxel")),
 )
 RECON_SWITCHES = (("--save-per-chunk", "per-chunk ply files as well"),
                   ("--dense-mesh", "write dense_mesh.ply: a triangle mesh of the fused dense map (surface nets on its "
@@ -138,6 +156,20 @@ ONLINE_FLAGS: Sequence[Tuple[str, Dict]] = (
                                                                 "than N voxels (e.g. 50 as a starting point, not a "
                                                                 "measured optimum)")),
 )
+ONLINE_CARVE_FLAGS: Sequence[Tuple[str, Dict]] = (
+    ("--dense_depth_every", dict(type=int, default=None, help="with --dense_voxel_size: every chunk keeps the depth of "
+                                                              "every K-th frame for --dense_carve_min_conflicts")),
+    ("--dense_depth_stride", dict(type=int, default=2, choices=(1, 2, 4), help="those depth planes keep every S-th row "
+                                                                               "and column")),
+    ("--dense_carve_min_conflicts", dict(type=int, default=None, help="dense map: first drop the voxels that at least N "
+                                                                      "depth keyframes of any chunk looked through, "
+                                                                      "and more than agree with them (needs "
+                                                                      "--dense_depth_every; use with --no_bundle_adjust; "
+                                                                      "e.g. 3 as a starting point, not a measured "
+                                                                      "optimum)")),
+    ("--dense_carve_tolerance", dict(type=float, default=0.03, help="relative depth difference (plus one voxel size) "
+                                                                    "within which a keyframe agrees with a voxel")),
+)
 ONLINE_SWITCHES = (("--save_chunk_reconstructions", "save each chunk reconstruction to disk"),
                    ("--save_transformed_reconstructions", "save transformed reconstructions as PLY files"),
                    ("--save_debug_reconstructions", "accepted for compatibility"),
@@ -169,8 +201,9 @@ def list_images(root: str) -> List[str]:
 def build_parser() -> argparse.ArgumentParser:
     top = argparse.ArgumentParser(prog="pi3_slam_amd.cli", description=__doc__.split("\n")[0])
     sub = top.add_subparsers(dest="command", required=True)
-    for name, flags, switches in (("create", CREATE_FLAGS, CREATE_SWITCHES), ("reconstruct", RECON_FLAGS, RECON_SWITCHES),
-                                  ("online", ONLINE_FLAGS, ONLINE_SWITCHES)):
+    for name, flags, switches in (("create", CREATE_FLAGS, CREATE_SWITCHES),
+                                  ("reconstruct", tuple(RECON_FLAGS) + tuple(RECON_CARVE_FLAGS), RECON_SWITCHES),
+                                  ("online", tuple(ONLINE_FLAGS) + tuple(ONLINE_CARVE_FLAGS), ONLINE_SWITCHES)):
         p = sub.add_parser(name)
         for flag, kw in flags:
             p.add_argument(flag, **kw)
@@ -205,7 +238,8 @@ def run_create(a: argparse.Namespace) -> None:
         hip_graph=a.hip_graph, reuse_overlap_encoder=a.reuse_overlap_encoder, dense_voxel_size=a.dense_voxel_size,
         dense_conf_threshold=a.dense_conf_threshold, dense_min_views=a.dense_min_views,
         dense_view_radius=a.dense_view_radius, dense_view_stride=a.dense_view_stride,
-        dense_depth_tolerance=a.dense_depth_tolerance, dense_normals=a.dense_normals)
+        dense_depth_tolerance=a.dense_depth_tolerance, dense_normals=a.dense_normals,
+        dense_depth_every=a.dense_depth_every, dense_depth_stride=a.dense_depth_stride)
     OfflineChunkCreator(cfg).process_and_save(paths[lo:hi])
 
 
@@ -220,7 +254,9 @@ def run_reconstruct(a: argparse.Namespace) -> None:
                          render_overview=a.render_overview, render_min_weight=a.render_min_weight,
                          render_splat_scale=a.render_splat_scale, dense_min_weight=a.dense_min_weight,
                          dense_min_support=a.dense_min_support, dense_support_radius=a.dense_support_radius,
-                         dense_min_component=a.dense_min_component, dense_mesh=a.dense_mesh).run()
+                         dense_min_component=a.dense_min_component, dense_mesh=a.dense_mesh,
+                         dense_carve_min_conflicts=a.dense_carve_min_conflicts,
+                         dense_carve_tolerance=a.dense_carve_tolerance).run()
 
 
 def online_image_paths(a: argparse.Namespace) -> List[str]:
@@ -265,7 +301,8 @@ def run_online(a: argparse.Namespace) -> None:
         dense_view_stride=a.dense_view_stride, dense_depth_tolerance=a.dense_depth_tolerance,
         dense_min_weight=a.dense_min_weight, dense_min_support=a.dense_min_support,
         dense_support_radius=a.dense_support_radius, dense_min_component=a.dense_min_component,
-        dense_normals=a.dense_normals)
+        dense_normals=a.dense_normals, dense_depth_every=a.dense_depth_every, dense_depth_stride=a.dense_depth_stride,
+        dense_carve_min_conflicts=a.dense_carve_min_conflicts, dense_carve_tolerance=a.dense_carve_tolerance)
     slam.save_transformed_reconstructions = a.save_transformed_reconstructions
     slam.save_debug_reconstructions = a.save_debug_reconstructions
     slam.process_chunks(paths)

@@ -21,7 +21,13 @@
 // a numpy float32 oracle (tests/dense_consistency_ref.py) reproduces mask, counts and stats byte for byte.  The Makefile
 // compiles this file with -ffp-contract=off: under the library's -ffp-contract=fast the compiler ignores
 // `#pragma clang fp contract(off)` and fuses the rotation's and the projection's multiply-adds.
+//
+// Depth keyframes (pi3_dense_depth_planes): the candidate test of pass A on every `every`-th frame and every
+// `pixel_stride`-th row and column, the local z written as fp16 (round to nearest even; 0 for a non-candidate and for a
+// value that rounds to 0 or inf).  Stage 2 carves the fused map with them (voxel_carve.hip);
+// tests/dense_carve_ref.py reproduces the planes byte for byte.
 #include "common.h"
+#include "wave_block.h"
 
 #include <stdint.h>
 
@@ -29,20 +35,49 @@ namespace {
 
 typedef unsigned long long u64;
 
-__global__ __launch_bounds__(256) void dense_candidates_kernel(
-    const float* __restrict__ points, const float* __restrict__ local_points, const float* __restrict__ conf,
-    const unsigned char* __restrict__ masks, long n, float conf_thr, float* __restrict__ zplane) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  float z = 0.0f;
+// the candidate test of both entry points: mask, confidence, a finite world point, a finite positive local z
+__device__ __forceinline__ float candidate_z(const float* __restrict__ points, const float* __restrict__ local_points,
+                                             const float* __restrict__ conf, const unsigned char* __restrict__ masks,
+                                             long i, float conf_thr) {
   if ((!masks || masks[i]) && (!conf || conf[i] > conf_thr)) {
     const float px = points[3 * i], py = points[3 * i + 1], pz = points[3 * i + 2];
     const float lz = local_points[3 * i + 2];
     if (__builtin_isfinite(px) && __builtin_isfinite(py) && __builtin_isfinite(pz) && __builtin_isfinite(lz) &&
         lz > 0.0f)
-      z = lz;
+      return lz;
   }
-  zplane[i] = z;
+  return 0.0f;
+}
+
+__global__ __launch_bounds__(256) void dense_candidates_kernel(
+    const float* __restrict__ points, const float* __restrict__ local_points, const float* __restrict__ conf,
+    const unsigned char* __restrict__ masks, long n, float conf_thr, float* __restrict__ zplane) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  zplane[i] = candidate_z(points, local_points, conf, masks, i, conf_thr);
+}
+
+// One thread per sample (k, y', x') of the planes: frame k * every, pixel (S y', S x').  fp16 bits through _Float16
+// (v_cvt_f16_f32: round to nearest even, overflow to inf, underflow through the subnormals to 0).
+__global__ __launch_bounds__(256) void dense_depth_planes_kernel(
+    const float* __restrict__ points, const float* __restrict__ local_points, const float* __restrict__ conf,
+    const unsigned char* __restrict__ masks, long n_out, int H, int W, int Hp, int Wp, int every, int S, float conf_thr,
+    unsigned short* __restrict__ depth, u64* __restrict__ count) {
+  const long o = (long)blockIdx.x * 256 + threadIdx.x;
+  unsigned nz = 0;
+  if (o < n_out) {
+    const long per = (long)Hp * Wp;
+    const long k = o / per, r = o - k * per;
+    const int yp = (int)(r / Wp), xp = (int)(r - (long)yp * Wp);
+    const long i = (k * every * H + (long)yp * S) * W + (long)xp * S;       // yp S <= H - 1, xp S <= W - 1
+    const float z = candidate_z(points, local_points, conf, masks, i, conf_thr);
+    const _Float16 h = (_Float16)z;
+    unsigned short bits = __builtin_bit_cast(unsigned short, h);
+    if (bits == 0x7C00u) bits = 0;                                         // rounded to inf: no opinion
+    depth[o] = bits;
+    nz = bits != 0;
+  }
+  wave_block::block_sum(nz, count);
 }
 
 enum { kNoVote = 0, kAgree = 1, kConflict = 2 };
@@ -154,4 +189,28 @@ extern "C" int pi3_dense_consistency(const float* points, const float* local_poi
                      (const float*)zplane, poses, fxfycxcy, n, N, H, W, radius, stride, min_views, rel_tol, out_mask,
                      counts, (u64*)stats);
   return pi3_check_launch("dense_consistency");
+}
+
+extern "C" int pi3_dense_depth_planes(const float* points, const float* local_points, const float* conf,
+                                      const unsigned char* masks, int N, int H, int W, float conf_logit_thr, int every,
+                                      int pixel_stride, unsigned short* depth, unsigned long long* count, void* stream) {
+  const long n = (long)N * H * W;
+  if (!points || !local_points || !depth || !count || N < 0 || H <= 0 || W <= 0 || n > 0x7fffffffL || every < 1 ||
+      (pixel_stride != 1 && pixel_stride != 2 && pixel_stride != 4)) {
+    pi3_set_error("pi3_dense_depth_planes: bad arguments N=%d H=%d W=%d every=%d (>= 1) pixel_stride=%d (1, 2 or 4), or "
+                  "a null pointer", N, H, W, every, pixel_stride);
+    return PI3_ERR_ARG;
+  }
+  if (hipMemsetAsync(count, 0, sizeof(unsigned long long), (hipStream_t)stream) != hipSuccess) {
+    pi3_set_error("pi3_dense_depth_planes: hipMemsetAsync failed");
+    return PI3_ERR_LAUNCH;
+  }
+  if (N == 0) return PI3_OK;
+  const int Nk = (int)(((long)N + every - 1) / every);
+  const int Hp = (H + pixel_stride - 1) / pixel_stride, Wp = (W + pixel_stride - 1) / pixel_stride;
+  const long n_out = (long)Nk * Hp * Wp;
+  hipLaunchKernelGGL(dense_depth_planes_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     points, local_points, conf, masks, n_out, H, W, Hp, Wp, every, pixel_stride, conf_logit_thr, depth,
+                     (u64*)count);
+  return pi3_check_launch("dense_depth_planes");
 }

@@ -32,7 +32,12 @@
 //
 // Sizes are uint32 atomic counts at the root's slot, so two runs give the same bytes.  Counters (caller-owned device
 // memory, 8 x uint64, zeroed by pi3_voxel_support): [0] occupied slots, [1] eligible, [2] after support, [3] after
-// components, [4] components found, [5] components kept.  Every counter is summed per workgroup (wave_block.h, block_count).
+// components, [4] components found, [5] components kept, [6] (pi3_voxel_support_excluding) the occupied slots its exclude
+// mask names.  Every counter is summed per workgroup (wave_block.h, block_count).
+//
+// Excluded slots (pi3_voxel_support_excluding; the carved voxels of voxel_carve.hip): exclude[slot] != 0 makes an occupied
+// slot not eligible and nobody's neighbour, so stage A counts its support without them, and stage B, which starts from
+// stage A's mask, its components.  The same kernel with a template flag.
 #include "common.h"
 #include "voxel_table.h"
 #include "wave_block.h"
@@ -51,18 +56,21 @@ __device__ __forceinline__ u64 load_relaxed(const u64* p) {
 }
 
 // Stage A.  kRadius = 1 or 2.  probe = false (min_support == 0 and nobody asks for the counts): eligibility only.
-template <int kRadius>
+// kExcl: the slots that `exclude` names are neither eligible nor counted as anybody's neighbour.
+template <int kRadius, bool kExcl>
 __global__ __launch_bounds__(256) void voxel_support_kernel(const u64* __restrict__ table, long capacity, u64 min_weight,
                                                             int min_support, bool probe,
+                                                            const unsigned char* __restrict__ exclude,
                                                             unsigned char* __restrict__ keep, int* __restrict__ support,
                                                             u64* __restrict__ counters) {
   const long s = (long)blockIdx.x * 256 + threadIdx.x;
   const u64 mask = (u64)capacity - 1;
-  bool occupied = false, eligible = false, kept = false;
+  bool occupied = false, eligible = false, kept = false, excluded = false;
   if (s < capacity) {
     const u64 key = table[8 * s];
     occupied = key != kEmpty;
-    eligible = occupied && table[8 * s + 1] >= min_weight;
+    if (kExcl) excluded = occupied && exclude[s];
+    eligible = occupied && !excluded && table[8 * s + 1] >= min_weight;
     int n = -1;
     if (eligible && probe) {
       const uint32_t kx = key_field(key, 0), ky = key_field(key, 1), kz = key_field(key, 2);
@@ -75,7 +83,7 @@ __global__ __launch_bounds__(256) void voxel_support_kernel(const u64* __restric
           for (int dz = -kRadius; dz <= kRadius; ++dz) {
             if ((dx | dy | dz) == 0 || !field_offset(kz, dz, nz)) continue;
             const long t = slot_find(table, mask, pack_key(nx, ny, nz));
-            if (t >= 0 && table[8 * t + 1] >= min_weight) ++n;
+            if (t >= 0 && table[8 * t + 1] >= min_weight && (!kExcl || !exclude[t])) ++n;
           }
         }
       }
@@ -84,9 +92,15 @@ __global__ __launch_bounds__(256) void voxel_support_kernel(const u64* __restric
     keep[s] = kept ? 1 : 0;
     if (support) support[s] = n;
   }
-  const bool flags[3] = {occupied, eligible, kept};
-  const int at[3] = {0, 1, 2};
-  block_count<3>(flags, counters, at);
+  if constexpr (kExcl) {
+    const bool flags[4] = {occupied, eligible, kept, excluded};
+    const int at[4] = {0, 1, 2, 6};
+    block_count<4>(flags, counters, at);
+  } else {
+    const bool flags[3] = {occupied, eligible, kept};
+    const int at[3] = {0, 1, 2};
+    block_count<3>(flags, counters, at);
+  }
 }
 
 __global__ __launch_bounds__(256) void voxel_label_init_kernel(const u64* __restrict__ table, long capacity,
@@ -220,27 +234,48 @@ __global__ __launch_bounds__(256) void voxel_component_filter_kernel(const u64* 
 
 }  // namespace
 
-extern "C" int pi3_voxel_support(const void* table, long capacity, unsigned long long min_weight, int radius,
-                                 int min_support, unsigned char* keep, int* support, unsigned long long* counters,
-                                 void* stream) {
+namespace {
+
+template <bool kExcl>
+int support_launch(const char* what, const void* table, long capacity, unsigned long long min_weight, int radius,
+                   int min_support, const unsigned char* exclude, unsigned char* keep, int* support,
+                   unsigned long long* counters, void* stream) {
   const int cells = (2 * radius + 1) * (2 * radius + 1) * (2 * radius + 1) - 1;
-  if (!table || !pow2(capacity) || !keep || !counters || (radius != 1 && radius != 2) || min_support < 0 ||
-      min_support > cells) {
-    pi3_set_error("pi3_voxel_support: bad arguments capacity=%ld radius=%d min_support=%d", capacity, radius, min_support);
+  if (!table || !pow2(capacity) || !keep || !counters || (kExcl && !exclude) || (radius != 1 && radius != 2) ||
+      min_support < 0 || min_support > cells) {
+    pi3_set_error("%s: bad arguments capacity=%ld radius=%d min_support=%d", what, capacity, radius, min_support);
     return PI3_ERR_ARG;
   }
   if (hipMemsetAsync(counters, 0, 8 * sizeof(unsigned long long), (hipStream_t)stream) != hipSuccess) {
-    pi3_set_error("pi3_voxel_support: hipMemsetAsync failed");
+    pi3_set_error("%s: hipMemsetAsync failed", what);
     return PI3_ERR_LAUNCH;
   }
   const bool probe = min_support > 0 || support != nullptr;
   if (radius == 1)
-    hipLaunchKernelGGL(voxel_support_kernel<1>, dim3(blocks_for(capacity)), dim3(256), 0, (hipStream_t)stream,
-                       (const u64*)table, capacity, (u64)min_weight, min_support, probe, keep, support, (u64*)counters);
+    hipLaunchKernelGGL((voxel_support_kernel<1, kExcl>), dim3(blocks_for(capacity)), dim3(256), 0, (hipStream_t)stream,
+                       (const u64*)table, capacity, (u64)min_weight, min_support, probe, exclude, keep, support,
+                       (u64*)counters);
   else
-    hipLaunchKernelGGL(voxel_support_kernel<2>, dim3(blocks_for(capacity)), dim3(256), 0, (hipStream_t)stream,
-                       (const u64*)table, capacity, (u64)min_weight, min_support, probe, keep, support, (u64*)counters);
-  return pi3_check_launch("voxel_support");
+    hipLaunchKernelGGL((voxel_support_kernel<2, kExcl>), dim3(blocks_for(capacity)), dim3(256), 0, (hipStream_t)stream,
+                       (const u64*)table, capacity, (u64)min_weight, min_support, probe, exclude, keep, support,
+                       (u64*)counters);
+  return pi3_check_launch(what + 4);       // without the "pi3_" prefix, as the other entry points report
+}
+
+}  // namespace
+
+extern "C" int pi3_voxel_support(const void* table, long capacity, unsigned long long min_weight, int radius,
+                                 int min_support, unsigned char* keep, int* support, unsigned long long* counters,
+                                 void* stream) {
+  return support_launch<false>("pi3_voxel_support", table, capacity, min_weight, radius, min_support, nullptr, keep,
+                               support, counters, stream);
+}
+
+extern "C" int pi3_voxel_support_excluding(const void* table, long capacity, unsigned long long min_weight, int radius,
+                                           int min_support, unsigned char* keep, int* support,
+                                           unsigned long long* counters, const unsigned char* exclude, void* stream) {
+  return support_launch<true>("pi3_voxel_support_excluding", table, capacity, min_weight, radius, min_support, exclude,
+                              keep, support, counters, stream);
 }
 
 extern "C" int pi3_voxel_label_init(const void* table, long capacity, const unsigned char* keep,

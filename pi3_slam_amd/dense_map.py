@@ -14,6 +14,10 @@ neighbouring frames of its chunk: the filter's pixel mask takes the place of the
 Optionally (MapCleaner, csrc/voxel_clean.hip) stage 2 drops voxels of the fused world-frame table before the extraction:
 a minimum weight, a minimum number of occupied neighbour cells, a minimum size of the connected component.
 
+Optionally (MapCarver, csrc/voxel_carve.hip) stage 2 first carves the fused table with depth keyframes that stage 1 kept
+per chunk (dense_depth_every; csrc/dense_filter.hip: pi3_dense_depth_planes): a voxel that enough views of ANY chunk
+looked through is dropped, before the cleaner counts neighbours and components.
+
 Optionally (NormalAccumulator, csrc/voxel_normals.hip; dense_normals) every voxel also gets a surface normal: the mean
 of its pixels' normals (cross products of the pointmap's central differences, facing the camera that saw them) in
 stage 1, the weighted mean of the clouds' rotated normals in stage 2.  A cloud then carries `normals` f32 (V,3) and
@@ -38,6 +42,7 @@ import torch
 
 from . import ops
 from .alignment import fresh_upload, upload
+from .hostmem import clone_host
 
 
 def conf_logit_threshold(conf_threshold: float) -> float:
@@ -190,19 +195,21 @@ class MapCleaner:
         return {"min_weight": self.min_weight, "min_support": self.min_support, "support_radius": self.support_radius,
                 "min_component": self.min_component}
 
-    def apply(self, fuser: "VoxelFuser", arrays: bool = False) -> torch.Tensor:
+    def apply(self, fuser: "VoxelFuser", arrays: bool = False, exclude: Optional[torch.Tensor] = None) -> torch.Tensor:
         """-> the device keep mask, uint8 (capacity,), for fuser.extract(keep=...).  Sets last_stats = {voxels,
         eligible, after_support, after_components, components, components_kept, sweeps}.  The components are labelled
         only when min_component > 1 (or arrays=True): otherwise components / components_kept are None and sweeps is 0.
         arrays=True (tests) also keeps last_arrays = {support int32, label int64, size int32} per slot, -1 / all ones /
-        0 where a slot has none."""
+        0 where a slot has none.  exclude (MapCarver.apply's mask, uint8 (capacity,)): the voxels it marks are not
+        eligible and nobody's neighbour, so support and components are counted without them; last_stats then also has
+        `carved`, their number (`voxels` still counts them)."""
         if fuser.table is None:
             fuser.reserve(0)
         table, cap, dev = fuser.table, fuser.capacity, fuser.device
         keep = torch.empty(cap, dtype=torch.uint8, device=dev)
         support = torch.empty(cap, dtype=torch.int32, device=dev) if arrays else None
         counters = torch.zeros(8, dtype=torch.int64, device=dev)
-        ops.voxel_support(table, self.min_weight, self.support_radius, self.min_support, keep, support, counters)
+        ops.voxel_support(table, self.min_weight, self.support_radius, self.min_support, keep, support, counters, exclude)
         sweeps, label, size = 0, None, None
         labelled = self.min_component > 1 or arrays
         if labelled:
@@ -215,6 +222,8 @@ class MapCleaner:
         if not labelled:
             st.update(after_components=st["after_support"], components=None, components_kept=None)
         st["sweeps"] = sweeps
+        if exclude is not None:
+            st["carved"] = c[6]
         self.last_stats = st
         self.last_arrays = {"support": support, "label": label, "size": size} if arrays else None
         return keep
@@ -247,6 +256,120 @@ class MapCleaner:
         return (f"{st['voxels']} voxels -> {st['eligible']} after weight >= {self.min_weight} -> {st['after_support']} "
                 f"after support >= {self.min_support} (radius {self.support_radius}) -> {st['after_components']} after "
                 f"components >= {self.min_component}")
+
+
+@dataclass
+class MapCarver:
+    """Carve a fused voxel table with the depth keyframes of every chunk (csrc/voxel_carve.hip; f64, reproduced byte
+    for byte by tests/dense_carve_ref.py).  Every voxel's centroid is projected into every keyframe of every chunk that
+    carries `dense_depth`; with zc its depth in that view and zo the view's own depth at the nearest sampled pixel
+    (scaled into map units by the chunk's similarity), the view agrees when |zc - zo| <= rel_tol zo + margin, conflicts
+    when zc - zo < -(rel_tol zo + margin) (it measured a surface BEHIND the voxel: it looked through it) and does not
+    vote otherwise (occluded, outside the image, no depth there).  Carved: conflict >= min_conflicts and conflict >
+    agree.  The views are not de-duplicated: an overlap frame votes once per chunk, with that chunk's plane and pose.
+
+    margin is MARGIN_VOXELS voxel sizes: a centroid and the depth sampled at the nearest pixel of a strided plane belong
+    to surface points up to about a voxel apart.  0.03 is the relative tolerance the consistency filter uses.
+    min_conflicts has no default: it switches the feature on (3 is a starting point, not a measured optimum).
+
+    Limitations: a view sits where its chunk's similarity puts it, so with bundle adjustment on the carving is as
+    misplaced as the map (use it without); a surface only ever seen from one side by one pass has nobody to contradict
+    it; the planes are nearest-sampled, not interpolated."""
+    min_conflicts: int
+    rel_tol: float = 0.03
+
+    MARGIN_VOXELS = 1.0         # the absolute part of the tolerance, in voxel sizes
+
+    def __post_init__(self):
+        v = self.min_conflicts
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer, float)) or int(v) != v:
+            raise ValueError(f"min_conflicts must be an integer, got {v!r}")
+        self.min_conflicts = int(v)
+        if not 1 <= self.min_conflicts < 1 << 31:
+            raise ValueError(f"min_conflicts must be in 1..2^31 - 1, got {self.min_conflicts}")
+        self.rel_tol = float(self.rel_tol)
+        if not (self.rel_tol > 0.0 and math.isfinite(self.rel_tol)):
+            raise ValueError(f"rel_tol must be a positive finite number, got {self.rel_tol!r}")
+        self.last_stats: Optional[Dict[str, int]] = None
+        self.last_arrays: Optional[Dict[str, torch.Tensor]] = None
+
+    @classmethod
+    def from_options(cls, min_conflicts: Optional[int] = None, rel_tol: float = 0.03) -> Optional["MapCarver"]:
+        """The carver the dense_carve_min_conflicts / dense_carve_tolerance options ask for; None without the first
+        (the tolerance alone asks for nothing)."""
+        return None if min_conflicts is None else cls(min_conflicts, rel_tol)
+
+    def settings(self) -> Dict:
+        return {"min_conflicts": self.min_conflicts, "rel_tol": self.rel_tol}
+
+    @staticmethod
+    def chunk_views(chunks: Iterable[Dict]) -> Tuple[np.ndarray, Optional[torch.Tensor], int]:
+        """Every (chunk, keyframe) of every chunk with `dense_depth` -> (views f64 (M,20): render.pack_cameras' rows of
+        the chunk's final camera_poses and the planes' own intrinsics, [17] = the chunk's depth scale, the cube root of
+        the determinant of chunk_transform's 3x3 block; planes fp16 (M,H',W') on the host, None when M = 0; the pixel
+        stride).  Raises ValueError when the chunks' planes differ in size or stride."""
+        from .render import pack_cameras
+        views, planes, layout = [], [], None
+        for i, d in enumerate(chunks):
+            dd = d.get("dense_depth")
+            if dd is None:
+                continue
+            depth = torch.as_tensor(dd["depth"])
+            this = (int(depth.shape[1]), int(depth.shape[2]), int(dd["pixel_stride"]))
+            if layout is None:
+                layout = this
+            elif this != layout:
+                raise ValueError(f"dense carving: the depth planes of chunk {d.get('chunk_index', i)} are H' x W' = "
+                                 f"{this[0]} x {this[1]} at pixel stride {this[2]}, those before it {layout[0]} x "
+                                 f"{layout[1]} at stride {layout[2]}: planes of differing size or stride are refused")
+            frames = np.asarray(torch.as_tensor(dd["frames"]).numpy(), np.int64)
+            if len(frames) == 0:
+                continue
+            f = np.asarray(torch.as_tensor(dd["fxfycxcy"]).numpy(), np.float64).reshape(-1, 4)
+            K = np.zeros((len(frames), 3, 3))
+            K[:, 0, 0], K[:, 1, 1], K[:, 0, 2], K[:, 1, 2], K[:, 2, 2] = f[:, 0], f[:, 1], f[:, 2], f[:, 3], 1.0
+            poses = torch.as_tensor(d["camera_poses"]).double().numpy().reshape(-1, 4, 4)[frames]
+            cams = pack_cameras(poses, K)
+            det = float(np.linalg.det(chunk_transform(d).numpy()[:3, :3]))
+            if not (math.isfinite(det) and det > 0.0):
+                raise ValueError(f"a chunk's transform is not a similarity (determinant {det!r} of its 3x3 block)")
+            cams[:, ops.CARVE_DEPTH_SCALE_AT] = np.cbrt(det)
+            views.append(cams)
+            planes.append(depth.to(torch.float16))
+        if not views:
+            return np.zeros((0, ops.CARVE_VIEW_DOUBLES)), None, (layout[2] if layout else 1)
+        return np.concatenate(views), torch.cat(planes).contiguous(), layout[2]
+
+    def apply(self, fuser: "VoxelFuser", chunks: Iterable[Dict], arrays: bool = False) -> Optional[torch.Tensor]:
+        """-> the device mask of the carved voxels, uint8 (capacity,), for MapCleaner.apply(exclude=...); None (after one
+        notice line) when no chunk carries depth planes.  Sets last_stats = {views, voxels, carved, unvoted};
+        arrays=True (tests) also keeps last_arrays = {agree, conflict} int32 per slot."""
+        if fuser.table is None:
+            fuser.reserve(0)
+        views, planes, stride = self.chunk_views(chunks)
+        self.last_arrays = None
+        if planes is None:
+            print("   ℹ️  No depth keyframes in the chunks (create them with dense_depth_every): nothing is carved")
+            self.last_stats = {"views": 0, "voxels": None, "carved": 0, "unvoted": None}
+            return None
+        dev, cap = fuser.device, fuser.capacity
+        carved = torch.empty(cap, dtype=torch.uint8, device=dev)
+        agree = torch.empty(cap, dtype=torch.int32, device=dev) if arrays else None
+        conflict = torch.empty(cap, dtype=torch.int32, device=dev) if arrays else None
+        counters = torch.zeros(4, dtype=torch.int64, device=dev)
+        ops.voxel_carve(fuser.table, fuser.voxel_size, upload(torch.from_numpy(views), dev).contiguous(),
+                        upload(planes, dev).contiguous(), stride, self.rel_tol, self.MARGIN_VOXELS * fuser.voxel_size,
+                        self.min_conflicts, carved, agree, conflict, counters)
+        st = dict(zip(ops.VOXEL_CARVE_COUNTERS, (int(x) for x in counters.tolist())))
+        self.last_stats = dict(views=int(len(views)), **st)
+        if arrays:
+            self.last_arrays = {"agree": agree, "conflict": conflict}
+        return carved
+
+    def summary(self) -> str:
+        st = self.last_stats
+        return (f"{st['views']} views, {st['carved']} of {st['voxels']} voxels carved (conflicts >= {self.min_conflicts}), "
+                f"{st['unvoted']} voxels no view voted on")
 
 
 class VoxelFuser:
@@ -543,10 +666,22 @@ class ChunkCloudBuilder:
     creator's packed copy (`out` / `got`), so a cloud costs the pipeline thread no synchronisation of its own."""
 
     def __init__(self, voxel_size: float, conf_threshold: float, device, consistency: Optional[ConsistencyFilter] = None,
-                 normals: bool = False):
+                 normals: bool = False, depth_every: Optional[int] = None, depth_stride: int = 2):
         self.conf_threshold = float(conf_threshold)
         self.filter = consistency
         self.device = torch.device(device)
+        # depth keyframes (opt-in): every depth_every-th frame's local z at every depth_stride-th pixel, fp16, for
+        # stage 2's MapCarver; in two buffers of the builder's own, like the extract buffers (allocated on first
+        # use).  Checked before anything touches the device
+        if depth_every is not None:
+            if isinstance(depth_every, bool) or int(depth_every) != depth_every or int(depth_every) < 1:
+                raise ValueError(f"dense_depth_every must be a positive integer, got {depth_every!r}")
+            if isinstance(depth_stride, bool) or depth_stride not in (1, 2, 4):
+                raise ValueError(f"dense_depth_stride must be 1, 2 or 4, got {depth_stride!r}")
+        self.depth_every = None if depth_every is None else int(depth_every)
+        self.depth_stride = int(depth_stride)
+        self._planes = _ExtractBuffers(lambda n, dev: (torch.empty(n, dtype=torch.float16, device=dev),), sets=2)
+        self._depth_warned = False
         # two output sets: chunk k's is read on the host while chunk k+1's extraction is queued (the creator's finish(k)
         # always completes before launch(k+2))
         self.fuser = VoxelFuser(voxel_size, self.device, out_sets=2)
@@ -570,9 +705,13 @@ class ChunkCloudBuilder:
         normals = bool(getattr(cfg, "dense_normals", False))
         if normals and cfg.dense_voxel_size is None:
             print("⚠️  dense_normals has no effect without dense_voxel_size: no dense cloud is built")
+        depth_every = getattr(cfg, "dense_depth_every", None)
+        if depth_every is not None and cfg.dense_voxel_size is None:
+            print("⚠️  dense_depth_every has no effect without dense_voxel_size: no dense cloud is built")
         if cfg.dense_voxel_size is None:
             return None
-        return cls(cfg.dense_voxel_size, cfg.dense_conf_threshold, device, consistency, normals)
+        return cls(cfg.dense_voxel_size, cfg.dense_conf_threshold, device, consistency, normals, depth_every,
+                   getattr(cfg, "dense_depth_stride", 2))
 
     def queue(self, points: torch.Tensor, local_points: torch.Tensor, conf: torch.Tensor, masks: torch.Tensor,
               imgs: torch.Tensor, poses: torch.Tensor, fxfycxcy: Optional[torch.Tensor],
@@ -592,6 +731,19 @@ class ChunkCloudBuilder:
                 print("⚠️  dense consistency filter: no intrinsics (estimate_camera_params is off or the estimate "
                       "failed); dense clouds without them are fused unfiltered")
         self.fuser.fuse_pixels(points, conf, masks, imgs.contiguous(), self.conf_threshold)
+        planes = None
+        if self.depth_every is not None:    # the mask fuse_pixels used: the filter's when it ran, else the creator's
+            if fxfycxcy is not None:
+                N, H, W = (int(x) for x in points.shape[:3])
+                shape = ops.depth_plane_shape(N, H, W, self.depth_every, self.depth_stride)
+                buf, = self._planes.take(shape[0] * shape[1] * shape[2], self.device)
+                planes, out["_dense_depth_stats"] = ops.dense_depth_planes(
+                    points, local_points.contiguous(), conf, masks, conf_logit_threshold(self.conf_threshold),
+                    self.depth_every, self.depth_stride, out=buf)
+            elif not self._depth_warned:    # once per run
+                self._depth_warned = True
+                print("⚠️  dense depth keyframes: no intrinsics (estimate_camera_params is off or the estimate failed); "
+                      "chunks without them carry no dense_depth")
         if self.normals is not None:        # the table has its final size now: the sums are laid out beside its slots
             self.normals.clear()
             self.normals.add_pixels(points, conf, masks, self.conf_threshold)
@@ -601,21 +753,31 @@ class ChunkCloudBuilder:
             nbufs, out["_dense_normal_stats"] = self.normals.extract_async()
         extracted = torch.cuda.Event()
         extracted.record(torch.cuda.current_stream(self.device))
-        return self._pool.submit(self._host_rows, bufs, out["_dense_stats"], extracted, nbufs)
+        return self._pool.submit(self._host_rows, bufs, out["_dense_stats"], extracted, nbufs, planes,
+                                 tuple(int(x) for x in points.shape[1:3]))
 
     def _host_rows(self, bufs: tuple, stats_dev: torch.Tensor, extracted: torch.cuda.Event,
-                   nbufs: tuple = ()) -> Dict[str, np.ndarray]:
+                   nbufs: tuple = (), planes: Optional[torch.Tensor] = None,
+                   image_hw: Tuple[int, int] = (0, 0)) -> Dict[str, np.ndarray]:
         """(dense-cloud thread) Wait for the extraction, copy the first V rows into pinned memory on a stream of its own
         (a copy into pageable memory would wait for the next chunk's forward) and sort them by key.  nbufs: the normal
-        rows (NormalAccumulator.extract_async), one per voxel as well; they are sorted by their own keys."""
+        rows (NormalAccumulator.extract_async), one per voxel as well; they are sorted by their own keys.  planes: the
+        depth keyframes of image_hw = (H, W) frames, copied as they are into 'depth_planes' beside 'image_hw'."""
         with torch.cuda.device(self.device), torch.cuda.stream(self._stream):
             extracted.synchronize()
             V = int(stats_dev[2].item())
             h = [torch.empty((V,) + tuple(t.shape[1:]), dtype=t.dtype, pin_memory=True) for t in tuple(bufs) + tuple(nbufs)]
             for dst, src in zip(h, tuple(bufs) + tuple(nbufs)):
                 dst.copy_(src[:V], non_blocking=True)
+            hp = None
+            if planes is not None:          # the depth keyframes ride on the same stream, beside the cloud's rows
+                hp = torch.empty(tuple(planes.shape), dtype=planes.dtype, pin_memory=True)
+                hp.copy_(planes, non_blocking=True)
             self._stream.synchronize()
         rows = sort_by_key(*(t.numpy() for t in h[:4]))
+        if hp is not None:
+            rows["depth_planes"] = clone_host(hp)       # out of the pinned block: the chunk keeps it
+            rows["image_hw"] = image_hw
         if nbufs:
             nrm = sort_normals_by_key(*(t.numpy() for t in h[4:]))
             rows.update(normal_keys=nrm["keys"], normals=nrm["normals"], normal_weights=nrm["normal_weights"])
@@ -646,6 +808,21 @@ class ChunkCloudBuilder:
             cloud["normal_weights"] = torch.from_numpy(s["normal_weights"])
         return cloud
 
+    def collect_depth(self, job: Future, got: Dict[str, torch.Tensor], metrics: Dict) -> Optional[Dict]:
+        """chunk['dense_depth'] from queue()'s job when the depth keyframes ran (None otherwise): depth fp16
+        (Nk,H',W'), frames int32 (Nk,), pixel_stride, height, width and fxfycxcy f32 (Nk,4), the rows of the
+        intrinsics the consistency filter projects with (got['cam.*']; full resolution, pixel i has its centre at i).
+        Adds dense_depth_samples, the non-zero samples, to `metrics`."""
+        if "_dense_depth_stats" not in got:
+            return None
+        rows = job.result()
+        depth, (height, width) = rows["depth_planes"], rows["image_hw"]
+        frames = torch.arange(int(depth.shape[0]), dtype=torch.int32) * self.depth_every
+        fxy = torch.stack([got["cam." + k].reshape(-1).float() for k in ("fx", "fy", "cx", "cy")], dim=1)
+        metrics["dense_depth_samples"] = int(got["_dense_depth_stats"][0])
+        return {"depth": depth, "frames": frames, "pixel_stride": self.depth_stride, "height": height, "width": width,
+                "fxfycxcy": fxy[frames.long()].contiguous()}
+
 
 def chunk_transform(chunk: Dict) -> torch.Tensor:
     """The 4x4 f64 similarity that moves a chunk's dense cloud into the world frame: the closed-form similarity the
@@ -658,7 +835,8 @@ def chunk_transform(chunk: Dict) -> torch.Tensor:
 
 
 def fuse_chunk_clouds_with_mesh(chunks: Iterable[Dict], voxel_size: float, device="cuda",
-                                cleaner: Optional[MapCleaner] = None, mesher: Optional[MapMesher] = None
+                                cleaner: Optional[MapCleaner] = None, mesher: Optional[MapMesher] = None,
+                                carver: Optional[MapCarver] = None
                                 ) -> Tuple[np.ndarray, np.ndarray, np.ndarray, Optional[np.ndarray], Optional[Dict]]:
     """Every chunk's dense_cloud moved by chunk_transform() and fused, weighted by its voxel weights ->
     (points f32 (V,3), colors u8 (V,3), weights i32 (V,), normals f32 (V,3) or None, mesh or None), the map in ascending
@@ -666,8 +844,12 @@ def fuse_chunk_clouds_with_mesh(chunks: Iterable[Dict], voxel_size: float, devic
     extracted (one line with the counts is printed).  Normals: when every cloud carries `normals`, each cloud's are
     rotated by its similarity's rotation and fused weighted by its `normal_weights`; when only some do, one line says so
     and the map has none.  mesher: MapMesher.apply's mesh of the same fused table, after the same keep mask; without
-    normals one line says so and the mesh is None; when the mesher fails the mesh is None and mesher.error holds why."""
+    normals one line says so and the mesh is None; when the mesher fails the mesh is None and mesher.error holds why.
+    carver: MapCarver.apply on the fused table with the chunks' depth keyframes, before the cleaner (one line with the
+    counts is printed, the cleaner's follows): a carved voxel is not extracted, is nobody's neighbour and belongs to no
+    component.  Without a cleaner the keep mask is "every voxel that was not carved"."""
     device = torch.device(device)
+    chunks = list(chunks)
     clouds = [(c["dense_cloud"], chunk_transform(c)) for c in chunks if c.get("dense_cloud") is not None]
     fuser = VoxelFuser(voxel_size, device)
     fuser.reserve(sum(int(cl["points"].shape[0]) for cl, _ in clouds))
@@ -691,10 +873,16 @@ def fuse_chunk_clouds_with_mesh(chunks: Iterable[Dict], voxel_size: float, devic
             nw = upload(torch.as_tensor(cl["normal_weights"]).reshape(-1), device).to(torch.int32).contiguous()
             rot = upload(torch.from_numpy(similarity_rotation(G).reshape(9).copy()), device).contiguous()
             acc.add_points(pts, nrm, nw, rot)
-    keep = None
+    keep = exclude = None
+    if carver is not None:
+        exclude = carver.apply(fuser, chunks)
+        if exclude is not None:
+            print(f"   🪓 Dense map carved: {carver.summary()}")
     if cleaner is not None:
-        keep = cleaner.apply(fuser)
+        keep = cleaner.apply(fuser, exclude=exclude)
         print(f"   🧹 Dense map cleaned: {cleaner.summary()}")
+    elif exclude is not None:
+        keep = MapCleaner(min_weight=1, min_support=0).apply(fuser, exclude=exclude)
     out = fuser.extract(keep)
     normals = None
     if acc is not None:
@@ -713,17 +901,18 @@ def fuse_chunk_clouds_with_mesh(chunks: Iterable[Dict], voxel_size: float, devic
 
 
 def fuse_chunk_clouds_with_normals(chunks: Iterable[Dict], voxel_size: float, device="cuda",
-                                   cleaner: Optional[MapCleaner] = None
+                                   cleaner: Optional[MapCleaner] = None, carver: Optional[MapCarver] = None
                                    ) -> Tuple[np.ndarray, np.ndarray, np.ndarray, Optional[np.ndarray]]:
     """fuse_chunk_clouds_with_mesh without the mesh: (points f32 (V,3), colors u8 (V,3), weights i32 (V,), normals f32
     (V,3) or None when the clouds carry none)."""
-    return fuse_chunk_clouds_with_mesh(chunks, voxel_size, device, cleaner)[:4]
+    return fuse_chunk_clouds_with_mesh(chunks, voxel_size, device, cleaner, carver=carver)[:4]
 
 
 def fuse_chunk_clouds(chunks: Iterable[Dict], voxel_size: float, device="cuda",
-                      cleaner: Optional[MapCleaner] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+                      cleaner: Optional[MapCleaner] = None, carver: Optional[MapCarver] = None
+                      ) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """fuse_chunk_clouds_with_normals without the normals: (points f32 (V,3), colors u8 (V,3), weights i32 (V,))."""
-    return fuse_chunk_clouds_with_normals(chunks, voxel_size, device, cleaner)[:3]
+    return fuse_chunk_clouds_with_normals(chunks, voxel_size, device, cleaner, carver)[:3]
 
 
 def write_dense_ply(points: np.ndarray, colors: np.ndarray, path: str) -> None:

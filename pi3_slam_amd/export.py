@@ -4,8 +4,9 @@ Pi3SLAMOnline.chunk_reconstructions).  Files and formats mirror slam/offline_rec
   final_points.ply        every track of every chunk (sparse_points_colors)
   final_camera_poses.ply  every view's camera centre, overlap views twice (all_views)
   trajectory_tum.txt      the de-duplicated trajectory: first occurrence of a view name wins (unique_views)
-  dense_points.ply        the chunks' dense clouds fused in the world frame (fuse_dense_map; dense_map.py), cleaned by a
-                          dense_map.MapCleaner when one is given; with nx ny nz when the clouds carry normals
+  dense_points.ply        the chunks' dense clouds fused in the world frame (fuse_dense_map; dense_map.py), carved by a
+                          dense_map.MapCarver and cleaned by a dense_map.MapCleaner when one is given; with nx ny nz
+                          when the clouds carry normals
   dense_mesh.ply          (dense_mesh) a triangle mesh of the same fused table, after the same cleaner
                           (dense_map.MapMesher); needs the normals
   renders/                depth / colour images of that map, overview.png, cameras.json (write_renders; render.py); with
@@ -183,31 +184,33 @@ class DenseMap(NamedTuple):
     voxel_size: float
 
 
-def fuse_dense_map_mesh(chunks: Sequence[Dict], device, cleaner=None, mesher=None
+def fuse_dense_map_mesh(chunks: Sequence[Dict], device, cleaner=None, mesher=None, carver=None
                         ) -> Tuple[Optional[DenseMap], Optional[np.ndarray], Optional[Dict]]:
     """The chunks' dense clouds (chunks created with a dense voxel size) fused in the world frame -> (the map, its
     normals f32 (V,3) row for row, or None when the clouds carry none, the mesh); (None, None, None) when no chunk
     carries a cloud.  The voxel size is the first cloud's: the world frame is chunk 0's frame.  cleaner: a
     dense_map.MapCleaner whose filters choose the voxels of the map (None: all of them).  mesher: a dense_map.MapMesher;
     the mesh is its apply() on the same fused table after the same filters, None without one, without normals (one
-    line says so) or when it failed (mesher.error)."""
+    line says so) or when it failed (mesher.error).  carver: a dense_map.MapCarver; the fused table is carved with the
+    chunks' depth keyframes before the cleaner sees it."""
     first = next((d["dense_cloud"] for d in chunks if d.get("dense_cloud") is not None), None)
     if first is None:
         return None, None, None
     from .dense_map import fuse_chunk_clouds_with_mesh
     voxel = float(first["voxel_size"])
-    pts, cols, w, normals, mesh = fuse_chunk_clouds_with_mesh(chunks, voxel, device, cleaner, mesher)
+    pts, cols, w, normals, mesh = fuse_chunk_clouds_with_mesh(chunks, voxel, device, cleaner, mesher, carver=carver)
     return DenseMap(pts, cols, w, voxel), normals, mesh
 
 
-def fuse_dense_map_normals(chunks: Sequence[Dict], device, cleaner=None) -> Tuple[Optional[DenseMap], Optional[np.ndarray]]:
+def fuse_dense_map_normals(chunks: Sequence[Dict], device, cleaner=None, carver=None
+                           ) -> Tuple[Optional[DenseMap], Optional[np.ndarray]]:
     """fuse_dense_map_mesh without the mesh: (the map, its normals or None); (None, None) without dense clouds."""
-    return fuse_dense_map_mesh(chunks, device, cleaner)[:2]
+    return fuse_dense_map_mesh(chunks, device, cleaner, carver=carver)[:2]
 
 
-def fuse_dense_map(chunks: Sequence[Dict], device, cleaner=None) -> Optional[DenseMap]:
+def fuse_dense_map(chunks: Sequence[Dict], device, cleaner=None, carver=None) -> Optional[DenseMap]:
     """fuse_dense_map_normals without the normals: the map, or None when no chunk carries a dense cloud."""
-    return fuse_dense_map_normals(chunks, device, cleaner)[0]
+    return fuse_dense_map_normals(chunks, device, cleaner, carver)[0]
 
 
 def write_dense_points(dense: DenseMap, path: str, normals: Optional[np.ndarray] = None) -> int:
@@ -230,15 +233,16 @@ def write_dense_mesh(mesh: Dict, path: str) -> int:
 
 def write_renders(chunks: Sequence[Dict], dense: Optional[DenseMap], out_dir: str, every: Optional[int], overview: bool,
                   min_weight: int = 1, splat_scale: float = 1.0, device="cuda",
-                  dense_cleaner=None, normals: Optional[np.ndarray] = None) -> Optional[Tuple[int, Dict[str, float]]]:
+                  dense_cleaner=None, normals: Optional[np.ndarray] = None, dense_carver=None
+                  ) -> Optional[Tuple[int, Dict[str, float]]]:
     """<out_dir>/depth_<frame>.png (16 bit, millimetres, 0 = empty) and color_<frame>.png of the dense map for every
     `every`-th view of the de-duplicated trajectory, overview.png (a top-down orthographic view with the trajectory
     in red) and cameras.json -> (rendered views, {'total', 'png'} seconds).  `dense`: the map a caller has already fused
-    (else it is fused here, through `dense_cleaner`).  Without dense clouds in the chunks: one line, no directory, None.
+    (else it is fused here, through `dense_carver` and `dense_cleaner`).  Without dense clouds in the chunks: one line, no directory, None.
     normals: that map's normals; then every view also gets normal_<frame>.png (the camera-frame normal as RGB) and
     shaded_<frame>.png (headlight shading, greyscale), and the overview overview_shaded.png."""
     if dense is None:
-        dense, normals = fuse_dense_map_normals(chunks, device, dense_cleaner)
+        dense, normals = fuse_dense_map_normals(chunks, device, dense_cleaner, dense_carver)
     if dense is None:
         print("   ℹ️  No dense clouds in the chunks (create them with a dense voxel size): no renders")
         return None
@@ -303,10 +307,11 @@ def write_renders(chunks: Sequence[Dict], dense: Optional[DenseMap], out_dir: st
 def write_outputs(chunks: Sequence[Dict], output_dir: str, device="cuda", render_every: Optional[int] = None,
                   render_overview: bool = False, render_min_weight: int = 1,
                   render_splat_scale: float = 1.0, dense_cleaner=None,
-                  dense_mesh: bool = False) -> Optional[Dict[str, float]]:
+                  dense_mesh: bool = False, dense_carver=None) -> Optional[Dict[str, float]]:
     """Every output file of stage 2 under output_dir; a file that fails is reported and the others are still written.
     Returns the seconds of write_renders when renders were written.  dense_cleaner (dense_map.MapCleaner): the dense
-    map of the PLY and of the renders is the cleaned one.  dense_mesh: also dense_mesh.ply, the mesh of that map."""
+    map of the PLY and of the renders is the cleaned one.  dense_mesh: also dense_mesh.ply, the mesh of that map.
+    dense_carver (dense_map.MapCarver): that map is first carved with the chunks' depth keyframes."""
     try:
         pts, cols = sparse_points_colors(chunks)
         if pts.size > 0:
@@ -329,7 +334,7 @@ def write_outputs(chunks: Sequence[Dict], output_dir: str, device="cuda", render
         from .dense_map import MapMesher
         mesher = MapMesher()
     try:
-        dense, normals, mesh = fuse_dense_map_mesh(chunks, device, dense_cleaner, mesher)
+        dense, normals, mesh = fuse_dense_map_mesh(chunks, device, dense_cleaner, mesher, dense_carver)
         if dense is not None:
             write_dense_points(dense, os.path.join(output_dir, "dense_points.ply"), normals)
     except Exception as e:  # noqa: BLE001
@@ -349,7 +354,7 @@ def write_outputs(chunks: Sequence[Dict], output_dir: str, device="cuda", render
     if render_every is not None or render_overview:
         try:       # the renders draw the map that was just fused for the PLY
             done = write_renders(chunks, dense, os.path.join(output_dir, "renders"), render_every, render_overview,
-                                 render_min_weight, render_splat_scale, device, dense_cleaner, normals)
+                                 render_min_weight, render_splat_scale, device, dense_cleaner, normals, dense_carver)
             return done[1] if done else None
         except Exception as e:  # noqa: BLE001
             print(f"❌ Failed to save the renders of the dense map: {e}")

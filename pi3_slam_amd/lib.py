@@ -70,11 +70,14 @@ SIGNATURES = {
     "pi3_voxel_extract": [_vp, _l, _d, _vp, _vp, _vp, _vp, _l, _vp, _vp],
     "pi3_voxel_extract_kept": [_vp, _l, _d, _vp, _vp, _vp, _vp, _l, _vp, _vp, _vp],
     "pi3_voxel_support": [_vp, _l, _u64, _i, _i, _vp, _vp, _vp, _vp],
+    "pi3_voxel_support_excluding": [_vp, _l, _u64, _i, _i, _vp, _vp, _vp, _vp, _vp],
     "pi3_voxel_label_init": [_vp, _l, _vp, _vp, _vp],
     "pi3_voxel_label_sweep": [_vp, _l, _vp, _vp, _vp],
     "pi3_voxel_component_sizes": [_vp, _l, _vp, _vp, _vp],
     "pi3_voxel_component_filter": [_vp, _l, _vp, _vp, _l, _vp, _vp, _vp],
     "pi3_dense_consistency": [_vp] * 6 + [_i, _i, _i, _f, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp],
+    "pi3_dense_depth_planes": [_vp] * 4 + [_i, _i, _i, _f, _i, _i, _vp, _vp, _vp],
+    "pi3_voxel_carve": [_vp, _l, _d, _vp, _i, _vp, _i, _i, _i, _d, _d, _i, _vp, _vp, _vp, _vp, _vp],
     "pi3_render_splat": [_vp, _vp, _l, _vp, _i, _i, _i, _d, _d, _i, _d, _d, _vp, _vp, _vp],
     "pi3_render_resolve": [_vp, _vp, _l, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
     "pi3_voxel_fuse_pixel_normals": [_vp, _l, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp],

@@ -55,6 +55,8 @@ class InOrderDrain:
 
 
 class Pi3SLAMOnline:
+    dense_carver = None     # class default: the export methods also serve objects whose __init__ did not run (tests)
+
     def __init__(self, model=None, chunk_length: int = 100, overlap: int = 10, device: str = "cuda",
                  conf_threshold: float = 0.5, undistortion_maps=None, cam_scale: float = 1.0,
                  visualization_port: int = 9090, estimate_camera_params: bool = False, keypoint_type: str = "grid",
@@ -67,8 +69,13 @@ class Pi3SLAMOnline:
                  dense_voxel_size: Optional[float] = None, dense_min_views: Optional[int] = None,
                  dense_view_radius: int = 3, dense_view_stride: int = 2, dense_depth_tolerance: float = 0.03,
                  dense_min_weight: Optional[int] = None, dense_min_support: Optional[int] = None,
-                 dense_support_radius: int = 1, dense_min_component: Optional[int] = None, dense_normals: bool = False):
-        from .dense_map import MapCleaner
+                 dense_support_radius: int = 1, dense_min_component: Optional[int] = None, dense_normals: bool = False,
+                 dense_depth_every: Optional[int] = None, dense_depth_stride: int = 2,
+                 dense_carve_min_conflicts: Optional[int] = None, dense_carve_tolerance: float = 0.03):
+        from .dense_map import MapCarver, MapCleaner
+        # dense_depth_every: the chunks keep depth keyframes; dense_carve_min_conflicts: the fused dense map of
+        # save_dense_map / save_dense_mesh / save_renders is carved with them first (dense_map.MapCarver; off by default)
+        self.dense_carver = MapCarver.from_options(dense_carve_min_conflicts, dense_carve_tolerance)
         # filters on the fused dense map of save_dense_map / save_renders (all off by default: no cleaner)
         self.dense_cleaner = MapCleaner.from_options(dense_min_weight, dense_min_support, dense_support_radius,
                                                      dense_min_component)
@@ -85,7 +92,8 @@ class Pi3SLAMOnline:
             reuse_overlap_encoder=reuse_overlap_encoder, dense_voxel_size=dense_voxel_size,
             dense_conf_threshold=conf_threshold,     # --conf_threshold filters the dense map's pixels
             dense_min_views=dense_min_views, dense_view_radius=dense_view_radius, dense_view_stride=dense_view_stride,
-            dense_depth_tolerance=dense_depth_tolerance, dense_normals=dense_normals)
+            dense_depth_tolerance=dense_depth_tolerance, dense_normals=dense_normals,
+            dense_depth_every=dense_depth_every, dense_depth_stride=dense_depth_stride)
         self._creator = OfflineChunkCreator(cfg, model=model, moge_model=moge_model)
         self._creator.undistortion_maps = undistortion_maps
         self.rank, self.world = self._creator.rank, self._creator.world
@@ -296,13 +304,15 @@ class Pi3SLAMOnline:
 
     def _fused_map(self):
         """-> (the fused dense map, its normals or None: dense_normals)."""
-        dense, normals = export.fuse_dense_map_normals(self.chunk_reconstructions, str(self.device), self.dense_cleaner)
+        dense, normals = export.fuse_dense_map_normals(self.chunk_reconstructions, str(self.device), self.dense_cleaner,
+                                                       self.dense_carver)
         if dense is None:
             raise RuntimeError("no dense clouds: construct Pi3SLAMOnline with dense_voxel_size")
         return dense, normals
 
     def save_dense_map(self, save_path: str) -> int:
-        """The chunks' dense clouds (dense_voxel_size set) fused in the world frame, cleaned by the dense_min_* options
+        """The chunks' dense clouds (dense_voxel_size set) fused in the world frame, carved with the chunks' depth
+        keyframes under dense_carve_min_conflicts, cleaned by the dense_min_* options
         when one is set -> a PLY (with normals under dense_normals); returns the voxel count."""
         dense, normals = self._fused_map()
         return export.write_dense_points(dense, save_path, normals)
@@ -314,7 +324,7 @@ class Pi3SLAMOnline:
         from .dense_map import MapMesher
         mesher = MapMesher()
         dense, _, mesh = export.fuse_dense_map_mesh(self.chunk_reconstructions, str(self.device), self.dense_cleaner,
-                                                    mesher)
+                                                    mesher, self.dense_carver)
         if dense is None:
             raise RuntimeError("no dense clouds: construct Pi3SLAMOnline with dense_voxel_size")
         if mesher.error is not None:

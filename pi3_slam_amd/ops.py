@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Optional
+from typing import Optional, Tuple
 
 import torch
 
@@ -705,17 +705,26 @@ def _slot_array(t: torch.Tensor, table: torch.Tensor, dtype) -> None:
 
 
 def voxel_support(table: torch.Tensor, min_weight: int, radius: int, min_support: int, keep: torch.Tensor,
-                  support: Optional[torch.Tensor], counters: torch.Tensor) -> None:
-    """Stage A: keep uint8 (capacity,), support int32 (capacity,) or None, counters int64 (8,) (zeroed by the call)."""
+                  support: Optional[torch.Tensor], counters: torch.Tensor, exclude: Optional[torch.Tensor] = None) -> None:
+    """Stage A: keep uint8 (capacity,), support int32 (capacity,) or None, counters int64 (8,) (zeroed by the call).
+    exclude uint8 (capacity,) (pi3_voxel_support_excluding): the slots it marks are neither eligible nor anybody's
+    neighbour, and counters[6] counts the occupied ones among them."""
     lib = _L.load()
     assert table.dtype == torch.int64 and table.is_contiguous() and table.numel() % 8 == 0
     _slot_array(keep, table, torch.uint8)
     if support is not None:
         _slot_array(support, table, torch.int32)
     assert counters.dtype == torch.int64 and counters.is_contiguous() and counters.numel() >= 8
-    rc = lib.pi3_voxel_support(table.data_ptr(), table.numel() // 8, int(min_weight), int(radius), int(min_support),
-                               keep.data_ptr(), _L.ptr(support), counters.data_ptr(), _L.stream_ptr())
-    _L.check(rc, "pi3_voxel_support")
+    if exclude is None:
+        rc = lib.pi3_voxel_support(table.data_ptr(), table.numel() // 8, int(min_weight), int(radius), int(min_support),
+                                   keep.data_ptr(), _L.ptr(support), counters.data_ptr(), _L.stream_ptr())
+        _L.check(rc, "pi3_voxel_support")
+    else:
+        _slot_array(exclude, table, torch.uint8)
+        rc = lib.pi3_voxel_support_excluding(table.data_ptr(), table.numel() // 8, int(min_weight), int(radius),
+                                             int(min_support), keep.data_ptr(), _L.ptr(support), counters.data_ptr(),
+                                             exclude.data_ptr(), _L.stream_ptr())
+        _L.check(rc, "pi3_voxel_support_excluding")
 
 
 def voxel_label_init(table: torch.Tensor, keep: torch.Tensor, label: torch.Tensor) -> None:
@@ -786,6 +795,89 @@ def dense_consistency(points: torch.Tensor, local_points: torch.Tensor, conf: Op
                                    _L.ptr(counts), stats.data_ptr(), _L.stream_ptr())
     _L.check(rc, "pi3_dense_consistency")
     return out_mask, counts, stats
+
+
+def depth_plane_shape(N: int, H: int, W: int, every: int, pixel_stride: int) -> Tuple[int, int, int]:
+    """(Nk, H', W') of the depth keyframes of an (N,H,W) chunk: frames 0, every, 2 every, .. and every pixel_stride-th
+    row and column, both starting at 0."""
+    return (int(N) + int(every) - 1) // int(every), -(-int(H) // int(pixel_stride)), -(-int(W) // int(pixel_stride))
+
+
+def dense_depth_planes(points: torch.Tensor, local_points: torch.Tensor, conf: Optional[torch.Tensor],
+                       masks: Optional[torch.Tensor], conf_logit_thr: float, every: int, pixel_stride: int,
+                       out: Optional[torch.Tensor] = None, count: Optional[torch.Tensor] = None):
+    """Depth keyframes of one chunk (csrc/dense_filter.hip: pi3_dense_depth_planes).  points / local_points f32
+    (N,H,W,3), conf f32 logits (N,H,W[,1]) or None, masks uint8/bool (N,H,W) or None -> (depth fp16 (Nk,H',W') with the
+    shape of depth_plane_shape: the local z of dense_consistency's candidates rounded to nearest even, 0 elsewhere and
+    where it rounds to 0 or inf; count int64 (1,): the non-zero samples).  out: a contiguous fp16 buffer with at least
+    Nk H' W' elements to write into (the result is a view of it); count: an int64 device tensor to write into."""
+    lib = _L.load()
+    N, H, W = (int(x) for x in points.shape[:3])
+    dev = points.device
+    every, pixel_stride = int(every), int(pixel_stride)
+    assert every >= 1 and pixel_stride in (1, 2, 4)
+    assert points.dtype == torch.float32 and points.is_contiguous() and points.ndim == 4 and points.shape[3] == 3
+    assert local_points.dtype == torch.float32 and local_points.is_contiguous() and local_points.shape == points.shape
+    assert local_points.device == dev
+    if conf is not None:
+        assert conf.dtype == torch.float32 and conf.is_contiguous() and conf.numel() == N * H * W and conf.device == dev
+    if masks is not None:
+        assert masks.dtype in (torch.uint8, torch.bool) and masks.is_contiguous() and masks.numel() == N * H * W
+        assert masks.device == dev
+    shape = depth_plane_shape(N, H, W, every, pixel_stride)
+    n_out = shape[0] * shape[1] * shape[2]
+    if out is None:
+        out = torch.empty(max(n_out, 1), device=dev, dtype=torch.float16)
+    assert out.dtype == torch.float16 and out.is_contiguous() and out.numel() >= n_out and out.device == dev
+    if count is None:
+        count = torch.zeros(1, device=dev, dtype=torch.int64)
+    assert count.dtype == torch.int64 and count.numel() >= 1 and count.device == dev
+    depth = out.reshape(-1)[:n_out].view(shape)
+    if N * H * W == 0:          # empty tensors have no address to pass
+        count.zero_()
+        return depth, count
+    rc = lib.pi3_dense_depth_planes(points.data_ptr(), local_points.data_ptr(), _L.ptr(conf), _L.ptr(masks), N, H, W,
+                                    float(conf_logit_thr), every, pixel_stride, out.data_ptr(), count.data_ptr(),
+                                    _L.stream_ptr())
+    _L.check(rc, "pi3_dense_depth_planes")
+    return depth, count
+
+
+# ---- carving the fused map with depth keyframes (csrc/voxel_carve.hip)
+VOXEL_CARVE_COUNTERS = ("voxels", "carved", "unvoted")
+CARVE_VIEW_DOUBLES = 20     # render.pack_cameras' row; [17] = the view's depth scale
+CARVE_DEPTH_SCALE_AT = 17
+
+
+def voxel_carve(table: torch.Tensor, voxel_size: float, views: torch.Tensor, planes: torch.Tensor, pixel_stride: int,
+                rel_tol: float, margin: float, min_conflicts: int, carved: torch.Tensor,
+                agree: Optional[torch.Tensor], conflict: Optional[torch.Tensor], counters: torch.Tensor) -> None:
+    """Per slot of the table: X = the extraction's centroid (f64 -> fp32 -> f64); per view m (views f64 (M,20): rigid
+    world->camera 3x4, fx fy cx cy, 0, [17] = depth scale s; planes fp16 (M,H',W')): xc = ((r00 x + r01 y) + r02 z) + t0,
+    likewise yc, zc; no vote unless zc > 0 and finite; u = fx (xc / zc) + cx, v = fy (yc / zc) + cy; pu = rint(u / S),
+    pv = rint(v / S), inside the plane; zo = s plane[m, pv, pu], no vote when 0 or not finite; r = zc - zo,
+    lim = rel_tol zo + margin; |r| <= lim agrees, r < -lim conflicts.  carved uint8 (capacity,) = conflict >=
+    min_conflicts and conflict > agree; agree / conflict int32 (capacity,) (the uint32 votes) or None; counters int64
+    (4,) = occupied, carved, no view voted (zeroed by the call)."""
+    lib = _L.load()
+    assert table.dtype == torch.int64 and table.is_contiguous() and table.numel() % 8 == 0
+    dev = table.device
+    assert views.dtype == torch.float64 and views.is_contiguous() and views.ndim == 2
+    assert views.shape[1] == CARVE_VIEW_DOUBLES and views.device == dev
+    M = int(views.shape[0])
+    assert planes.dtype == torch.float16 and planes.is_contiguous() and planes.ndim == 3 and planes.device == dev
+    assert int(planes.shape[0]) == M and M < 1 << 31
+    Hp, Wp = int(planes.shape[1]), int(planes.shape[2])
+    _slot_array(carved, table, torch.uint8)
+    for t in (agree, conflict):
+        if t is not None:
+            _slot_array(t, table, torch.int32)
+    assert counters.dtype == torch.int64 and counters.is_contiguous() and counters.numel() >= 4 and counters.device == dev
+    rc = lib.pi3_voxel_carve(table.data_ptr(), table.numel() // 8, float(voxel_size), views.data_ptr() if M else None, M,
+                             planes.data_ptr() if M else None, Hp, Wp, int(pixel_stride), float(rel_tol), float(margin),
+                             int(min_conflicts), carved.data_ptr(), _L.ptr(agree), _L.ptr(conflict), counters.data_ptr(),
+                             _L.stream_ptr())
+    _L.check(rc, "pi3_voxel_carve")
 
 
 # ---------------------------------------------------------------------------------------------------- map renderer

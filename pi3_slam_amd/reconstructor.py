@@ -35,16 +35,21 @@ class OfflineReconstructor:
                  render_every: Optional[int] = None, render_overview: bool = False, render_min_weight: int = 1,
                  render_splat_scale: float = 1.0, dense_min_weight: Optional[int] = None,
                  dense_min_support: Optional[int] = None, dense_support_radius: int = 1,
-                 dense_min_component: Optional[int] = None, dense_mesh: bool = False):
+                 dense_min_component: Optional[int] = None, dense_mesh: bool = False,
+                 dense_carve_min_conflicts: Optional[int] = None, dense_carve_tolerance: float = 0.03):
         self.chunk_dir, self.output_dir = chunk_dir, output_dir
         # dense_mesh: after dense_points.ply also dense_mesh.ply, a triangle mesh of the same fused (and cleaned) table
         # (dense_map.MapMesher); the chunks must carry normals (created with dense_normals)
         self.dense_mesh = bool(dense_mesh)
         # dense_min_weight / dense_min_support / dense_min_component: filters on the fused dense map before it is written
         # and rendered (dense_map.MapCleaner); all off by default, and then no cleaner exists
-        from .dense_map import MapCleaner
+        from .dense_map import MapCarver, MapCleaner
         self.dense_cleaner = MapCleaner.from_options(dense_min_weight, dense_min_support, dense_support_radius,
                                                      dense_min_component)
+        # dense_carve_min_conflicts: before those filters, drop the voxels of the fused map that this many depth keyframes
+        # (chunks created with dense_depth_every) looked through (dense_map.MapCarver); off by default: no carver.  The
+        # keyframes sit where the chunks' similarities put them: use it with bundle_adjust=False, like the map itself
+        self.dense_carver = MapCarver.from_options(dense_carve_min_conflicts, dense_carve_tolerance)
         # render_every / render_overview: after dense_points.ply, depth + colour images of the dense map from every N-th
         # view of the trajectory and a top-down overview, under <output>/renders (pi3_slam_amd/render.py); off by default
         if render_every is not None and int(render_every) <= 0:
@@ -179,7 +184,7 @@ class OfflineReconstructor:
             self.reconstructions = done
             seconds = export.write_outputs(done, self.output_dir, self.device, self.render_every, self.render_overview,
                                            self.render_min_weight, self.render_splat_scale, self.dense_cleaner,
-                                           self.dense_mesh)
+                                           self.dense_mesh, dense_carver=self.dense_carver)
             if seconds is not None:
                 self.render_seconds = seconds
         if grouped:

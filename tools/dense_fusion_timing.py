@@ -32,7 +32,13 @@
      cell, the first slot of each chain only, 32 B of normal sums per source found, the 8-byte key read and the 32-byte
      vertex written per slot) and the rate they give.
 
-Prints one JSON line.  Usage: python tools/dense_fusion_timing.py [--voxel 0.02] [--rounds 3] [--chunks 4] [--consistency] [--clean] [--normals] [--mesh]"""
+  7. --carve: the carving with depth keyframes (csrc/voxel_carve.hip, dense_map.MapCarver) on the table of leg 1 with
+     the planes of 500 views (the chunk's own 50 keyframes at K = 2, S = 2 and the scene's true intrinsics, ten times
+     over) and on the synthetic box map of leg 4 with 500 cameras inside the box that each see a constant-depth plane,
+     HIP events, median of 20 after 3 warm-up runs, beside voxel_support at radius 1 in the same run; the depth-plane
+     kernel (csrc/dense_filter.hip) on the chunk; and a creator leg with dense_depth_every = 2.
+
+Prints one JSON line.  Usage: python tools/dense_fusion_timing.py [--voxel 0.02] [--rounds 3] [--chunks 4] [--consistency] [--clean] [--normals] [--mesh] [--carve]"""
 from __future__ import annotations
 
 import argparse
@@ -139,6 +145,56 @@ def mesh_times(fz, nacc, reps: int = 20):
                        "support_r1_TBps": sb / (res["support_r1_ms"] * 1e-3) / 1e12}
 
 
+def carve_times(fz, views: np.ndarray, planes: torch.Tensor, stride: int, reps: int = 20):
+    """pi3_voxel_carve on a filled VoxelFuser (min_conflicts 3, MapCarver's tolerance and margin) beside voxel_support at
+    radius 1; views f64 (M,20) on the host, planes fp16 (M,H',W') on the device."""
+    from pi3_slam_amd import ops
+    from pi3_slam_amd.dense_map import MapCarver
+    dev, cap = fz.device, fz.capacity
+    v = torch.from_numpy(views).to(dev).contiguous()
+    carved = torch.empty(cap, dtype=torch.uint8, device=dev)
+    keep = torch.empty(cap, dtype=torch.uint8, device=dev)
+    cc = torch.zeros(4, dtype=torch.int64, device=dev)
+    counters = torch.zeros(8, dtype=torch.int64, device=dev)
+    t = {"carve_ms": [], "support_r1_ms": []}
+    for i in range(3 + reps):
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        e[0].record()
+        ops.voxel_carve(fz.table, fz.voxel_size, v, planes, stride, 0.03, MapCarver.MARGIN_VOXELS * fz.voxel_size, 3, carved,
+                        None, None, cc)
+        e[1].record()
+        ops.voxel_support(fz.table, 1, 1, 4, keep, None, counters)
+        e[2].record()
+        torch.cuda.synchronize()
+        if i >= 3:
+            for k, (a, b) in zip(t, zip(e, e[1:])):
+                t[k].append(a.elapsed_time(b))
+    res = {k: float(np.median(x)) for k, x in t.items()} | {k + "_minmax": [float(np.min(x)), float(np.max(x))]
+                                                           for k, x in t.items()}
+    st = dict(zip(ops.VOXEL_CARVE_COUNTERS, (int(x) for x in cc.tolist())))
+    return res | st | {"views": int(len(views)), "plane_shape": list(planes.shape[1:]), "pixel_stride": stride,
+                       "plane_stack_bytes": int(planes.numel()) * 2, "table_slots": cap,
+                       "ns_per_voxel_and_view": 1e6 * res["carve_ms"] / max(1, st["voxels"] * len(views))}
+
+
+def box_views(voxel: float, dev: str, side: int = 410, M: int = 500, Hp: int = 154, Wp: int = 203, seed: int = 1):
+    """M cameras inside the synthetic box, looking around its vertical axis, each with a constant-depth plane (a
+    quarter of the box's side): timing input only."""
+    from pi3_slam_amd import ops
+    from pi3_slam_amd.render import pack_cameras
+    rng = np.random.default_rng(seed)
+    half = 0.5 * side * voxel
+    poses = np.tile(np.eye(4), (M, 1, 1))
+    yaw = rng.uniform(0, 2 * np.pi, M)
+    poses[:, 0, 0], poses[:, 0, 2], poses[:, 2, 0], poses[:, 2, 2] = np.cos(yaw), np.sin(yaw), -np.sin(yaw), np.cos(yaw)
+    poses[:, :3, 3] = rng.uniform(-0.5 * half, 0.5 * half, (M, 3))
+    K = np.array([[0.9 * 2 * Wp, 0, Wp - 0.5], [0, 0.9 * 2 * Wp, Hp - 0.5], [0, 0, 1.0]])
+    views = pack_cameras(poses, K)
+    views[:, ops.CARVE_DEPTH_SCALE_AT] = 1.0
+    planes = torch.full((M, Hp, Wp), 0.5 * half, dtype=torch.float16, device=dev)
+    return views, planes
+
+
 def synthetic_box_map(voxel: float, dev: str, side: int = 410, seed: int = 0, normals: bool = False):
     """About 1 M voxels: the six faces of a box of `side` voxels, one point per voxel, and 1 % floaters inside.
     normals: -> (the fuser, its NormalAccumulator) with the faces' outward normals; the floaters carry none."""
@@ -172,7 +228,7 @@ def synthetic_box_map(voxel: float, dev: str, side: int = 410, seed: int = 0, no
 
 
 def kernel_times(voxel: float, dev: str, reps: int = 20, clean: bool = False, normals: bool = False,
-                 mesh: bool = False):
+                 mesh: bool = False, carve: bool = False):
     import synth_sequence as ss
     from pi3_slam_amd.chunk_creator import OfflineChunkCreator
     from pi3_slam_amd.dense_map import NormalAccumulator, VoxelFuser
@@ -223,6 +279,27 @@ def kernel_times(voxel: float, dev: str, reps: int = 20, clean: bool = False, no
             acc.clear()
             acc.add_pixels(pts, conf, masks, 0.5)
         out["mesh"] = mesh_times(fz, acc.nacc, reps)
+    if carve:
+        from pi3_slam_amd import ops
+        from pi3_slam_amd.dense_map import conf_logit_threshold
+        from pi3_slam_amd.render import pack_cameras
+        lp = ss.SceneEngine(seq)(imgs)["local_points"][0].contiguous()
+        m8 = masks.view(torch.uint8)
+        ms = []
+        for i in range(3 + reps):
+            a, b = ev(), ev()
+            a.record()
+            planes, count = ops.dense_depth_planes(pts, lp, conf, m8, conf_logit_threshold(0.5), 2, 2)
+            b.record()
+            torch.cuda.synchronize()
+            if i >= 3:
+                ms.append(a.elapsed_time(b))
+        K = np.array([[seq.fx, 0, seq.cx], [0, seq.fy, seq.cy], [0, 0, 1.0]])
+        views = pack_cameras(ss.SceneEngine(seq)(imgs)["camera_poses"][0, ::2].double().cpu().numpy(), K)
+        views[:, ops.CARVE_DEPTH_SCALE_AT] = 1.0
+        out["carve"] = carve_times(fz, np.tile(views, (10, 1)), planes.repeat(10, 1, 1).contiguous(), 2, reps)
+        out["carve"].update(depth_planes_ms=float(np.median(ms)), depth_planes_minmax=[float(np.min(ms)), float(np.max(ms))],
+                            depth_plane_samples=int(count), depth_plane_bytes_per_chunk=int(planes.numel()) * 2)
     return out
 
 
@@ -262,7 +339,7 @@ def consistency_times(dev: str, reps: int = 20):
 
 
 def creator_fps(voxel: float, dev: str, rounds: int, chunks: int, conf_threshold: float, consistency: bool = False,
-                normals: bool = False):
+                normals: bool = False, depth: bool = False):
     from pi3_slam_amd.chunk_creator import OfflineChunkCreator, OfflineCreatorConfig
     from pi3_slam_amd.engine import Pi3Engine
     from pi3_slam_amd.weights import Pi3Config
@@ -276,13 +353,13 @@ def creator_fps(voxel: float, dev: str, rounds: int, chunks: int, conf_threshold
     tmp = tempfile.mkdtemp(prefix="dense_timing_")
     creators = {}
     legs = (("off", None, None), ("on", voxel, None)) + ((("filtered", voxel, 2),) if consistency else ()) \
-        + ((("normals", voxel, None),) if normals else ())
+        + ((("normals", voxel, None),) if normals else ()) + ((("depth", voxel, None),) if depth else ())
     for name, vs, mv in legs:
         cc = OfflineCreatorConfig(model_path="recipe", output_dir=os.path.join(tmp, name), chunk_length=CL, overlap=OV,
                                   device=dev, do_metric_depth=False, keypoint_type="grid", max_num_keypoints=KP,
                                   num_loader_workers=0, device_resize=True, dense_voxel_size=vs,
                                   dense_conf_threshold=conf_threshold, dense_min_views=mv,
-                                  dense_normals=name == "normals")
+                                  dense_normals=name == "normals", dense_depth_every=2 if name == "depth" else None)
         cr = OfflineChunkCreator(cc, model=engine)
         cr.target_size = (H, W)
         creators[name] = cr
@@ -321,6 +398,9 @@ def creator_fps(voxel: float, dev: str, rounds: int, chunks: int, conf_threshold
     if normals:
         nrm = float(np.median(fps["normals"]))
         res.update(fps_normals=fps["normals"], median_fps_normals=nrm, normals_cost_pct=100.0 * (on - nrm) / on)
+    if depth:
+        dep = float(np.median(fps["depth"]))
+        res.update(fps_depth=fps["depth"], median_fps_depth=dep, depth_cost_pct=100.0 * (on - dep) / on)
     return res
 
 
@@ -341,19 +421,25 @@ def main():
                                                            "extract, and a creator leg with dense_normals on")
     ap.add_argument("--mesh", action="store_true", help="also time the surface-mesh kernels on the chunk's table and on "
                                                         "a synthetic map of about 1 M voxels")
+    ap.add_argument("--carve", action="store_true", help="also time the carve kernel with the planes of 500 views on the "
+                                                         "chunk's table and on a synthetic map of about 1 M voxels, the "
+                                                         "depth-plane kernel, and a creator leg with depth keyframes on")
     a = ap.parse_args()
     dev = "cuda:0"
     torch.cuda.set_device(0)
-    out = {"voxel_size": a.voxel, "kernels": kernel_times(a.voxel, dev, clean=a.clean, normals=a.normals, mesh=a.mesh)}
+    out = {"voxel_size": a.voxel, "kernels": kernel_times(a.voxel, dev, clean=a.clean, normals=a.normals, mesh=a.mesh,
+                                                        carve=a.carve)}
     if a.mesh:
         fz, acc = synthetic_box_map(a.voxel, dev, normals=True)
         out["mesh_synthetic"] = mesh_times(fz, acc.nacc)
     if a.clean:
         out["clean_synthetic"] = clean_times(synthetic_box_map(a.voxel, dev))
+    if a.carve:
+        out["carve_synthetic"] = carve_times(synthetic_box_map(a.voxel, dev), *box_views(a.voxel, dev), 2)
     if a.consistency:
         out["consistency"] = consistency_times(dev)
     if not a.kernels_only:
-        out["creator"] = creator_fps(a.voxel, dev, a.rounds, a.chunks, a.conf_threshold, a.consistency, a.normals)
+        out["creator"] = creator_fps(a.voxel, dev, a.rounds, a.chunks, a.conf_threshold, a.consistency, a.normals, a.carve)
     print(json.dumps(out))
 
 

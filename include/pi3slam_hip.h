@@ -478,6 +478,36 @@ int pi3_voxel_carve(const void* table, long capacity, double voxel_size, const d
                     int min_conflicts, unsigned char* carved, unsigned* agree, unsigned* conflict,
                     unsigned long long* counters, void* stream);
 
+/* ---- nearest neighbours between two point clouds (csrc/cloud_nn.hip): an exact radius-bounded search through a
+ * uniform grid of cells, for scoring a map against a reference cloud (map_eval.py).  The grid is a hash table of cells
+ * in the voxel table's form: `capacity` slots of 64 B (a power of two, at least 2 n: ops.voxel_capacity), keyed by the
+ * cell indices floor(fl(p * inv_cell)) per axis exactly as the voxel quantiser forms them (fp32 product, |k| < 2^20).
+ *   slot = key | count | start | fill | row cursor (slot 0 only) | 3 spare, as uint64;
+ *   cells: n rows of 16 B = x, y, z (f32 bits), the point's index in `points` (int32); the rows of one cell are
+ *   cells[start .. start + count).  The order of the rows in a cell and of the cells in the array is not defined.
+ * pi3_cloud_index_build: points f32 [n][3].  Clears the table, counts the points per cell, gives every occupied cell
+ * its rows (one atomic add per workgroup on the cursor) and writes the rows.  A point that is not finite or whose cell
+ * index has |k| >= 2^20 on an axis is dropped: counted, no row.  counters: DEVICE uint64 [4] = dropped points,
+ * occupied cells, points that found no slot (0 under the capacity rule; they get no row), the largest cell's count;
+ * zeroed by the call.  0 <= n < 2^31; n == 0 leaves an empty table and launches no pass; points and cells may then be
+ * NULL.  inv_cell finite and > 0.  No allocation, no synchronisation. */
+int pi3_cloud_index_build(const float* points, long n, float inv_cell, void* table, long capacity, void* cells,
+                          unsigned long long* counters, void* stream);
+/* pi3_cloud_nearest: table, cells, n and inv_cell as pi3_cloud_index_build left them; queries f32 [m][3].  A query visits
+ * the 27 cells around its own (a cell whose index leaves |k| < 2^20 does not exist) and for every row p of them
+ * computes, in f64 without contraction, every operation rounded on its own in this order:
+ *   dx = (double)qx - (double)px, likewise dy, dz;   d2 = (dx dx + dy dy) + dz dz;
+ *   a row is a candidate when d2 <= max_dist max_dist (inclusive; the product formed once in f64);
+ *   d2[i] f64, idx[i] int32 = the candidate with the smallest d2 and, among equal d2, the smallest original index:
+ *   independent of the row order, bitwise reproducible.  No candidate: d2 = +inf, idx = -1.  A query the quantiser
+ *   drops is counted and gets +inf / -1.  NaN is written nowhere.
+ * The result is the exact nearest neighbour within max_dist among the points the index holds when max_dist * inv_cell
+ * <= 0.9 (callers use cells of 1.25 max_dist: 0.8); a larger product is refused.
+ * counters: DEVICE uint64 [4] = dropped queries, matched, beyond (no candidate), distance evaluations; zeroed by the
+ * call.  m == 0 launches nothing; n == 0: every query is beyond (none is dropped), cells may be NULL. */
+int pi3_cloud_nearest(const void* table, long capacity, const void* cells, long n, float inv_cell, const float* queries,
+                      long m, double max_dist, double* d2, int* idx, unsigned long long* counters, void* stream);
+
 /* ---- dense map -> camera views (csrc/render.hip): a z-buffered splat renderer for the voxel map.
  * points f32 [V][3] (the voxel centroids, in ascending key order), weights int32 [V] (or NULL: every voxel counts),
  * cams f64 [M][20] = world->camera 3x4 row-major (12), fx, fy, cx, cy, ortho flag (0 / 1), 3 spare.  zbuf uint64

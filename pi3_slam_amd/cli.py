@@ -187,6 +187,27 @@ ONLINE_SWITCHES = (("--save_chunk_reconstructions", "save each chunk reconstruct
                    ("--no_hip_graph", "plain kernel launches instead of the captured per-chunk graph"),
                    ("--reuse_overlap_encoder", "overlap frames take their encoder output from the previous chunk"))
 
+# evaluate-map: this build's own sub-command (map_eval.py), no counterpart in the reference
+EVAL_FLAGS: Sequence[Tuple[str, Dict]] = (
+    ("--estimate", dict(REQ, help="the map to score: dense_points.ply, or dense_mesh.ply (its vertices)")),
+    ("--reference", dict(REQ, help="the reference cloud (PLY)")),
+    ("--thresholds", dict(REQ, type=float, nargs="+", help="distances at which precision / recall / F-score are taken")),
+    ("--max-dist", dict(type=float, default=None, help="search radius; farther points count as beyond "
+                                                       "(default: twice the largest threshold)")),
+    ("--voxel-size", dict(type=float, default=None, help="first resample both clouds to one point per voxel of this "
+                                                         "size, so dense regions do not outweigh sparse ones")),
+    ("--transform", dict(default=None, help="text file with a 4x4 similarity (16 numbers, row-major) applied to the "
+                                            "estimate")),
+    ("--estimate-trajectory", dict(default=None, help="TUM trajectory of the estimate: with --reference-trajectory the "
+                                                      "estimate is aligned as `tools/eval_ape.py` aligns it (Sim(3) "
+                                                      "Umeyama over associated stamps)")),
+    ("--reference-trajectory", dict(default=None, help="TUM trajectory of the reference")),
+    ("--error-ply", dict(default=None, help="write the (resampled, transformed) estimate coloured by its distance to "
+                                            "the reference: green 0, red max-dist, magenta beyond")),
+    ("--device", dict(default="cuda")),
+)
+EVAL_SWITCHES = (("--json", "print the result as one JSON line instead of the table"),)
+
 
 def list_images(root: str) -> List[str]:
     """Folder -> its png, jpg, jpeg, bmp files (each extension group sorted, groups in that order); file -> its
@@ -203,7 +224,8 @@ def build_parser() -> argparse.ArgumentParser:
     sub = top.add_subparsers(dest="command", required=True)
     for name, flags, switches in (("create", CREATE_FLAGS, CREATE_SWITCHES),
                                   ("reconstruct", tuple(RECON_FLAGS) + tuple(RECON_CARVE_FLAGS), RECON_SWITCHES),
-                                  ("online", tuple(ONLINE_FLAGS) + tuple(ONLINE_CARVE_FLAGS), ONLINE_SWITCHES)):
+                                  ("online", tuple(ONLINE_FLAGS) + tuple(ONLINE_CARVE_FLAGS), ONLINE_SWITCHES),
+                                  ("evaluate-map", EVAL_FLAGS, EVAL_SWITCHES)):
         p = sub.add_parser(name)
         for flag, kw in flags:
             p.add_argument(flag, **kw)
@@ -330,9 +352,40 @@ def run_online(a: argparse.Namespace) -> None:
             slam.save_renders(os.path.join(out_dir or ".", "renders"), every=a.render_every, overview=True)
 
 
+def evaluate_map_transform(a: argparse.Namespace):
+    """The similarity evaluate-map applies to the estimate: --transform, or the trajectory pair's alignment, or None."""
+    from . import map_eval
+    pair = (a.estimate_trajectory, a.reference_trajectory)
+    if a.transform and any(pair):
+        raise SystemExit("evaluate-map: give --transform or the trajectory pair, not both")
+    if any(pair) and not all(pair):
+        raise SystemExit("evaluate-map: --estimate-trajectory and --reference-trajectory go together")
+    if a.transform:
+        return map_eval.read_transform(a.transform)
+    if all(pair):
+        return map_eval.trajectory_alignment(a.estimate_trajectory, a.reference_trajectory)
+    return None
+
+
+def run_evaluate_map(a: argparse.Namespace) -> None:
+    import json
+
+    from . import map_eval
+    from .export import write_ply
+    est, _ = map_eval.read_ply_points(a.estimate)
+    ref, _ = map_eval.read_ply_points(a.reference)
+    res = map_eval.compare_clouds(est, ref, a.thresholds, max_dist=a.max_dist, transform=evaluate_map_transform(a),
+                                  voxel_size=a.voxel_size, device=a.device)
+    if a.error_ply:
+        write_ply(res["_points"]["estimate"],
+                  map_eval.error_colors(res["_distances"]["estimate"], res["settings"]["max_dist"]), a.error_ply)
+    print(json.dumps(map_eval.public(res)) if a.json else map_eval.format_table(res))
+
+
 def main(argv=None) -> None:
     a = build_parser().parse_args(argv)
-    {"create": run_create, "reconstruct": run_reconstruct, "online": run_online}[a.command](a)
+    {"create": run_create, "reconstruct": run_reconstruct, "online": run_online,
+     "evaluate-map": run_evaluate_map}[a.command](a)
 
 
 if __name__ == "__main__":

@@ -1,0 +1,337 @@
+"""Scoring a point cloud (dense_points.ply, the vertices of dense_mesh.ply) against a reference cloud: accuracy,
+completeness and precision / recall / F-score at distance thresholds, as the Tanks and Temples and 7-Scenes dense
+evaluations define them.
+
+  accuracy      the distances estimate -> reference (how far the map's points are from the true surface);
+  completeness  the distances reference -> estimate (how much of the true surface the map covers);
+  precision(t)  the share of the estimate's points within t of the reference;  recall(t) the share of the reference's
+                points within t of the estimate;  fscore = 2 P R / (P + R).
+
+The distances are exact nearest neighbours within `max_dist` (csrc/cloud_nn.hip: a uniform cell grid on the device,
+cells of 1.25 max_dist, f64 distances, ties to the smallest index); a point with no neighbour that close is "beyond" and
+carries inf.  The statistics are numpy f64 on the host.  There is no CPU fallback for the search.
+
+    python -m pi3_slam_amd.cli evaluate-map --estimate dense_points.ply --reference GT.ply --thresholds 0.02 0.05
+"""
+from __future__ import annotations
+
+import os
+from typing import Callable, Dict, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import ops
+
+BEYOND_COLOR = (255, 0, 255)
+
+
+def tau_key(t: float) -> str:
+    """The dictionary key of a threshold (a string, so that a result survives JSON unchanged)."""
+    return repr(float(t))
+
+
+# ------------------------------------------------------------------------------------------------------ the search
+class CloudIndex:
+    """The cell grid of a cloud on the device.  points (n,3) (array or tensor, any float type; used as fp32);
+    nearest(queries) -> (d2 f64 (M,), index int64 (M,)) device tensors: the squared distance to and the index of the
+    nearest point within max_dist, inf / -1 without one.  last_stats: the build's counters, then the last query's."""
+
+    def __init__(self, points, max_dist: float, device="cuda"):
+        self.device = torch.device(device)
+        self.max_dist = float(max_dist)
+        self.inv_cell = ops.cloud_inv_cell(self.max_dist)
+        self.points = _device_points(points, self.device)
+        n = int(self.points.shape[0])
+        self.table = torch.empty(ops.voxel_capacity(n) * 8, dtype=torch.int64, device=self.device)
+        self.cells = torch.empty((n, 4), dtype=torch.int32, device=self.device)
+        counters = torch.zeros(4, dtype=torch.int64, device=self.device)
+        ops.cloud_index_build(self.points, self.inv_cell, self.table, self.cells, counters)
+        self.build_stats = dict(zip(ops.CLOUD_INDEX_COUNTERS, (int(x) for x in counters.tolist())), points=n)
+        self.last_stats = dict(self.build_stats)
+        if self.build_stats["no_slot"]:
+            raise RuntimeError(f"cloud index: cell table overflow: {self.build_stats}")
+
+    def nearest(self, queries) -> Tuple[torch.Tensor, torch.Tensor]:
+        q = _device_points(queries, self.device)
+        m = int(q.shape[0])
+        d2 = torch.empty(m, dtype=torch.float64, device=self.device)
+        idx = torch.empty(m, dtype=torch.int32, device=self.device)
+        counters = torch.zeros(4, dtype=torch.int64, device=self.device)
+        ops.cloud_nearest(self.table, self.cells, self.inv_cell, q, self.max_dist, d2, idx, counters)
+        self.last_stats = dict(zip(ops.CLOUD_NEAREST_COUNTERS, (int(x) for x in counters.tolist())), queries=m)
+        return d2, idx.long()
+
+
+def _device_points(points, device) -> torch.Tensor:
+    t = points if torch.is_tensor(points) else torch.from_numpy(np.ascontiguousarray(np.asarray(points)))
+    if t.ndim != 2 or t.shape[1] != 3:
+        if t.numel() % 3:
+            raise ValueError(f"a point cloud is (n, 3), got {tuple(t.shape)}")
+        t = t.reshape(-1, 3)
+    return t.to(device=device, dtype=torch.float32).contiguous()
+
+
+def _device_nearest(ref: torch.Tensor, queries: torch.Tensor, max_dist: float) -> Dict:
+    """queries against ref on their device -> host d2, idx and the counters; the shape compare_clouds consumes."""
+    index = CloudIndex(ref, max_dist, ref.device)
+    d2, idx = index.nearest(queries)
+    st = index.last_stats
+    return dict(d2=d2.cpu().numpy(), idx=idx.cpu().numpy(), ref_dropped=index.build_stats["dropped"],
+                counters={k: st[k] for k in ("dropped", "matched", "beyond")}, evaluations=st["evaluations"],
+                cells=index.build_stats["cells"], largest_cell=index.build_stats["largest_cell"])
+
+
+# ------------------------------------------------------------------------------------------------------ statistics
+def distance_stats(dist, thresholds: Sequence[float], max_dist: float) -> Dict:
+    """dist: distances (any shape), inf = no neighbour within max_dist.  -> matched, beyond, over the matched
+    distances mean / median / rmse / p90 / max (None when nothing matched), and within[tau_key(t)] = the share of ALL
+    points with d <= t (0 for an empty array).  A threshold above max_dist cannot be answered (the search stopped at
+    max_dist): ValueError."""
+    d = np.asarray(dist, np.float64).reshape(-1)
+    if np.isnan(d).any():
+        raise ValueError("distance_stats: NaN among the distances (inf marks a point without a neighbour)")
+    md = float(max_dist)
+    for t in thresholds:
+        if not (0.0 <= float(t) <= md):
+            raise ValueError(f"threshold {t} is outside [0, max_dist = {md}]: distances beyond max_dist were not searched")
+    near = d[np.isfinite(d)]
+    out = {"points": int(d.size), "matched": int(near.size), "beyond": int(d.size - near.size)}
+    if near.size:
+        out.update(mean=float(near.mean()), median=float(np.median(near)), rmse=float(np.sqrt(np.mean(near * near))),
+                   p90=float(np.percentile(near, 90.0)), max=float(near.max()))
+    else:
+        out.update(mean=None, median=None, rmse=None, p90=None, max=None)
+    out["within"] = {tau_key(t): (float(np.count_nonzero(d <= float(t))) / d.size if d.size else 0.0)
+                     for t in thresholds}
+    return out
+
+
+def fscore(precision: float, recall: float) -> float:
+    return 2.0 * precision * recall / (precision + recall) if precision + recall > 0.0 else 0.0
+
+
+def error_colors(dist, max_dist: float) -> np.ndarray:
+    """u8 (V,3): green at distance 0 through yellow at max_dist / 2 to red at max_dist (and above), the same ramp
+    whatever the thresholds; magenta for a point without a neighbour (inf)."""
+    d = np.asarray(dist, np.float64).reshape(-1)
+    t = np.clip(np.where(np.isfinite(d), d, 0.0) / float(max_dist), 0.0, 1.0)
+    rgb = np.stack([np.minimum(1.0, 2.0 * t), np.minimum(1.0, 2.0 * (1.0 - t)), np.zeros_like(t)], 1)
+    out = np.rint(rgb * 255.0).astype(np.uint8)
+    out[~np.isfinite(d)] = BEYOND_COLOR
+    return out
+
+
+def resample(points: torch.Tensor, voxel_size: float) -> torch.Tensor:
+    """One point per occupied voxel (the centroid; VoxelFuser.fuse_points + extract, ascending key order), on the
+    points' device: densely sampled regions stop outweighing sparse ones."""
+    from .dense_map import VoxelFuser
+    fz = VoxelFuser(float(voxel_size), points.device)
+    fz.fuse_points(points, None, None)
+    return torch.from_numpy(fz.extract()["points"]).to(points.device) if fz.bound else points[:0].clone()
+
+
+def compare_clouds(est, ref, thresholds: Sequence[float], max_dist: Optional[float] = None, transform=None,
+                   voxel_size: Optional[float] = None, device="cuda", _nearest: Optional[Callable] = None) -> Dict:
+    """est, ref: (n,3) clouds.  transform: a 4x4 similarity applied to est on the device (ops.sim3_apply).  voxel_size:
+    both clouds are first resampled to one point per voxel.  max_dist: the search radius, 2 max(thresholds) by default;
+    every threshold must be <= max_dist.  -> {'points', 'dropped', 'accuracy', 'completeness', 'precision', 'recall',
+    'fscore', 'search', 'settings', '_distances'}: the statistics of distance_stats in both directions, the three
+    scores per tau_key(threshold), and under '_distances' the per-point distance arrays ('estimate' row for row with
+    the (resampled, transformed) estimate under '_points', 'reference' likewise).  A dropped point (not finite, or
+    outside the grid's 2^20 cells per axis) counts as beyond.  _nearest: the search itself, for tests that drive this
+    function with a reference implementation: (ref, queries, max_dist) device tensors -> _device_nearest's dict."""
+    ths = [float(t) for t in thresholds]
+    if not ths:
+        raise ValueError("compare_clouds needs at least one threshold")
+    md = 2.0 * max(ths) if max_dist is None else float(max_dist)
+    dev = torch.device(device)
+    e, r = _device_points(est, dev), _device_points(ref, dev)
+    counts = {"estimate": int(e.shape[0]), "reference": int(r.shape[0])}
+    if transform is not None:
+        M = np.asarray(torch.as_tensor(transform, dtype=torch.float64).cpu().numpy(), np.float64).reshape(4, 4)
+        e = e.clone()
+        ops.sim3_apply(torch.from_numpy(M).to(dev).contiguous(), e, None)
+    if voxel_size is not None:
+        e, r = resample(e, voxel_size), resample(r, voxel_size)
+    counts.update(estimate_used=int(e.shape[0]), reference_used=int(r.shape[0]))
+    search = _nearest or _device_nearest
+    er, re_ = search(r, e, md), search(e, r, md)
+    for a, b, who in ((er, re_, "estimate"), (re_, er, "reference")):
+        n_q = counts[who + "_used"]
+        c = a["counters"]
+        if c["dropped"] + c["matched"] + c["beyond"] != n_q:
+            raise RuntimeError(f"cloud search: the counters of the {who}'s queries do not add up to {n_q}: {c}")
+        if n_q and len(b["d2"]) and c["dropped"] != b["ref_dropped"]:
+            raise RuntimeError(f"cloud search: {c['dropped']} of the {who}'s points dropped as queries, "
+                               f"{b['ref_dropped']} as indexed points")
+    d_er, d_re = np.sqrt(er["d2"]), np.sqrt(re_["d2"])
+    acc, comp = distance_stats(d_er, ths, md), distance_stats(d_re, ths, md)
+    out = {"points": counts,
+           "dropped": {"estimate": er["counters"]["dropped"], "reference": re_["counters"]["dropped"]},
+           "accuracy": acc, "completeness": comp, "precision": {}, "recall": {}, "fscore": {},
+           "search": {k: {"evaluations": s.get("evaluations"), "cells": s.get("cells"),
+                          "largest_cell": s.get("largest_cell")} for k, s in (("accuracy", er), ("completeness", re_))},
+           "settings": {"thresholds": ths, "max_dist": md, "voxel_size": None if voxel_size is None else float(voxel_size),
+                        "transform": None if transform is None else [[float(x) for x in row] for row in M],
+                        "cell": ops.CLOUD_CELL_FACTOR * md}}
+    for t in ths:
+        k = tau_key(t)
+        p, rc = acc["within"][k], comp["within"][k]
+        out["precision"][k], out["recall"][k], out["fscore"][k] = p, rc, fscore(p, rc)
+    out["_distances"] = {"estimate": d_er, "reference": d_re}
+    out["_points"] = {"estimate": e.cpu().numpy(), "reference": r.cpu().numpy()}
+    return out
+
+
+def public(result: Dict) -> Dict:
+    """The result without its per-point arrays: what --json prints."""
+    return {k: v for k, v in result.items() if not k.startswith("_")}
+
+
+# ------------------------------------------------------------------------------------------------------ PLY reader
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2",
+              "uint16": "u2", "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4",
+              "double": "f8", "float64": "f8"}
+
+
+def _ply_header(f, path: str):
+    if f.readline().strip() != b"ply":
+        raise ValueError(f"{path}: not a PLY file (the first line is not 'ply')")
+    fmt, elements = None, []
+    while True:
+        raw = f.readline()
+        if not raw:
+            raise ValueError(f"{path}: the PLY header has no end_header")
+        w = raw.decode("ascii", "replace").split()
+        if not w or w[0] in ("comment", "obj_info"):
+            continue
+        if w[0] == "end_header":
+            break
+        if w[0] == "format":
+            fmt = w[1] if len(w) > 1 else ""
+        elif w[0] == "element" and len(w) == 3:
+            elements.append({"name": w[1], "count": int(w[2]), "props": []})
+        elif w[0] == "property" and elements:
+            if w[1] == "list":
+                if len(w) != 5 or w[2] not in _PLY_TYPES or w[3] not in _PLY_TYPES:
+                    raise ValueError(f"{path}: cannot read the property line {' '.join(w)!r}")
+                elements[-1]["props"].append((w[4], "list", _PLY_TYPES[w[2]], _PLY_TYPES[w[3]]))
+            else:
+                if len(w) != 3 or w[1] not in _PLY_TYPES:
+                    raise ValueError(f"{path}: cannot read the property line {' '.join(w)!r}")
+                elements[-1]["props"].append((w[2], _PLY_TYPES[w[1]]))
+        else:
+            raise ValueError(f"{path}: unexpected PLY header line {' '.join(w)!r}")
+    if fmt not in ("binary_little_endian", "ascii"):
+        raise ValueError(f"{path}: PLY format {fmt!r} is not supported (binary_little_endian and ascii are)")
+    return fmt, elements
+
+
+def read_ply_points(path: str) -> Tuple[np.ndarray, Optional[np.ndarray]]:
+    """-> (points f32 (V,3), colors u8 (V,3) or None) of the file's vertex element.  binary_little_endian or ascii; the
+    vertex properties in any order and of any scalar type, x y z float or double; red green blue taken when all three
+    are uchar; elements after the vertices (faces) are not read; an element before them is skipped when its size
+    is known from the header (no list property)."""
+    with open(path, "rb") as f:
+        fmt, elements = _ply_header(f, path)
+        names = [e["name"] for e in elements]
+        if "vertex" not in names:
+            raise ValueError(f"{path}: no vertex element (found: {', '.join(names) or 'no elements'})")
+        vi = names.index("vertex")
+        vert = elements[vi]
+        if any(p[1] == "list" for p in vert["props"]):
+            raise ValueError(f"{path}: the vertex element has a list property")
+        pnames = [p[0] for p in vert["props"]]
+        if len(set(pnames)) != len(pnames):
+            raise ValueError(f"{path}: the vertex element names a property twice: {pnames}")
+        kinds = dict(vert["props"])
+        for a in "xyz":
+            if kinds.get(a) not in ("f4", "f8"):
+                raise ValueError(f"{path}: vertex property {a} must be float or double, found "
+                                 f"{kinds.get(a, 'no such property')} (vertex properties: {pnames})")
+        for e in elements[:vi]:
+            if any(p[1] == "list" for p in e["props"]) and e["count"]:
+                raise ValueError(f"{path}: element {e['name']} with a list property comes before the vertices")
+        V = vert["count"]
+        if fmt == "binary_little_endian":
+            for e in elements[:vi]:
+                f.seek(e["count"] * sum(np.dtype(p[1]).itemsize for p in e["props"]), os.SEEK_CUR)
+            dt = np.dtype([(n, "<" + k) for n, k in vert["props"]])
+            raw = f.read(V * dt.itemsize)
+            if len(raw) != V * dt.itemsize:
+                raise ValueError(f"{path}: {V} vertices of {dt.itemsize} bytes announced, {len(raw)} bytes found")
+            rec = np.frombuffer(raw, dtype=dt)
+            col = {n: rec[n] for n in pnames}
+        else:
+            for e in elements[:vi]:
+                for _ in range(e["count"]):
+                    f.readline()
+            rows = [f.readline().split() for _ in range(V)]
+            if any(len(r) != len(pnames) for r in rows):
+                raise ValueError(f"{path}: an ascii vertex line does not have {len(pnames)} entries (or the file ends early)")
+            tab = np.array(rows, dtype=np.float64).reshape(V, len(pnames))
+            col = {n: tab[:, i] for i, n in enumerate(pnames)}
+    pts = np.stack([np.asarray(col[a], np.float64) for a in "xyz"], 1).astype(np.float32).reshape(V, 3)
+    colors = None
+    if all(kinds.get(c) == "u1" for c in ("red", "green", "blue")):
+        colors = np.stack([np.asarray(col[c]).astype(np.uint8) for c in ("red", "green", "blue")], 1).reshape(V, 3)
+    return pts, colors
+
+
+# ------------------------------------------------------------------------------------------------------ alignment
+def _eval_ape():
+    """tools/eval_ape.py (the association and the Umeyama alignment of `evo_ape -as`), imported, not restated."""
+    try:
+        import eval_ape
+    except ImportError:
+        import importlib.util
+        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", "eval_ape.py")
+        if not os.path.exists(path):
+            raise ImportError(f"trajectory alignment needs tools/eval_ape.py of the source tree ({path} not found)")
+        spec = importlib.util.spec_from_file_location("eval_ape", path)
+        eval_ape = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(eval_ape)
+    return eval_ape
+
+
+def trajectory_alignment(est_tum: str, ref_tum: str, max_diff: float = 0.01) -> np.ndarray:
+    """The 4x4 similarity that `tools/eval_ape.py REF EST` (evo_ape -as) applies to the estimate: timestamps associated,
+    Umeyama with scale of the estimate's positions onto the reference's."""
+    ea = _eval_ape()
+    s_ref, p_ref, _ = ea.read_tum(ref_tum)
+    s_est, p_est, _ = ea.read_tum(est_tum)
+    i_ref, i_est = ea.associate(s_ref, s_est, max_diff)
+    r, t, c = ea.umeyama(p_est[i_est], p_ref[i_ref], True)
+    M = np.eye(4)
+    M[:3, :3], M[:3, 3] = c * r, t
+    return M
+
+
+def read_transform(path: str) -> np.ndarray:
+    """A text file with the 16 numbers of a row-major 4x4 similarity."""
+    M = np.loadtxt(path, dtype=np.float64).reshape(-1)
+    if M.size != 16:
+        raise ValueError(f"{path}: a transform file holds the 16 numbers of a 4x4 matrix, found {M.size}")
+    return M.reshape(4, 4)
+
+
+# ------------------------------------------------------------------------------------------------------ report
+def format_table(res: Dict) -> str:
+    s, pts = res["settings"], res["points"]
+    lines = [f"estimate  {pts['estimate']:>10d} points" + (f" -> {pts['estimate_used']} voxels" if s["voxel_size"] else "")
+             + f", {res['dropped']['estimate']} dropped",
+             f"reference {pts['reference']:>10d} points" + (f" -> {pts['reference_used']} voxels" if s["voxel_size"] else "")
+             + f", {res['dropped']['reference']} dropped",
+             f"search radius {s['max_dist']:g}" + (f", voxel size {s['voxel_size']:g}" if s["voxel_size"] else "")
+             + (", estimate transformed" if s["transform"] else ""), "",
+             f"{'':<14s}{'matched':>10s}{'beyond':>10s}{'mean':>10s}{'median':>10s}{'rmse':>10s}{'p90':>10s}{'max':>10s}"]
+    for name in ("accuracy", "completeness"):
+        st = res[name]
+        nums = "".join(f"{st[k]:>10.5f}" if st[k] is not None else f"{'-':>10s}" for k in ("mean", "median", "rmse", "p90", "max"))
+        lines.append(f"{name:<14s}{st['matched']:>10d}{st['beyond']:>10d}{nums}")
+    lines += ["", f"{'threshold':<14s}{'precision':>10s}{'recall':>10s}{'fscore':>10s}"]
+    for t in s["thresholds"]:
+        k = tau_key(t)
+        lines.append(f"{t:<14g}{res['precision'][k]:>10.4f}{res['recall'][k]:>10.4f}{res['fscore'][k]:>10.4f}")
+    return "\n".join(lines)

@@ -880,6 +880,63 @@ def voxel_carve(table: torch.Tensor, voxel_size: float, views: torch.Tensor, pla
     _L.check(rc, "pi3_voxel_carve")
 
 
+# ---- nearest neighbours between two clouds (csrc/cloud_nn.hip)
+CLOUD_INDEX_COUNTERS = ("dropped", "cells", "no_slot", "largest_cell")
+CLOUD_NEAREST_COUNTERS = ("dropped", "matched", "beyond", "evaluations")
+CLOUD_CELL_FACTOR = 1.25    # cell edge in units of max_dist: the 27 cells around a query then hold every candidate
+
+
+def cloud_inv_cell(max_dist: float) -> float:
+    """The fp32 inverse cell edge for a search radius: cells of CLOUD_CELL_FACTOR * max_dist."""
+    md = float(max_dist)
+    if not (md > 0.0 and math.isfinite(md)):
+        raise ValueError(f"max_dist must be finite and positive, got {max_dist}")
+    inv = C.c_float(1.0 / (CLOUD_CELL_FACTOR * md)).value          # rounded to fp32, as the kernels receive it
+    if not (inv > 0.0 and math.isfinite(inv)):
+        raise ValueError(f"max_dist {max_dist}: 1 / cell is not a positive finite float32")
+    return inv
+
+
+def cloud_index_build(points: torch.Tensor, inv_cell: float, table: torch.Tensor, cells: torch.Tensor,
+                      counters: torch.Tensor) -> None:
+    """points f32 (n,3) -> table int64 (8 capacity,) (64-byte slots: key, count, start, fill, cursor; capacity =
+    voxel_capacity(n)) and cells int32 (n,4) = x y z bits + original index, grouped by cell; counters int64 (4,) =
+    CLOUD_INDEX_COUNTERS (zeroed by the call)."""
+    lib = _L.load()
+    dev = table.device
+    assert points.dtype == torch.float32 and points.is_contiguous() and points.ndim == 2 and points.shape[1] == 3
+    n = int(points.shape[0])
+    assert table.dtype == torch.int64 and table.is_contiguous() and table.numel() % 8 == 0 and table.is_cuda
+    assert cells.dtype == torch.int32 and cells.is_contiguous() and tuple(cells.shape) == (n, 4)
+    assert counters.dtype == torch.int64 and counters.is_contiguous() and counters.numel() >= 4
+    assert points.device == dev and cells.device == dev and counters.device == dev
+    rc = lib.pi3_cloud_index_build(points.data_ptr() if n else None, n, float(inv_cell), table.data_ptr(),
+                                   table.numel() // 8, cells.data_ptr() if n else None, counters.data_ptr(),
+                                   _L.stream_ptr())
+    _L.check(rc, "pi3_cloud_index_build")
+
+
+def cloud_nearest(table: torch.Tensor, cells: torch.Tensor, inv_cell: float, queries: torch.Tensor, max_dist: float,
+                  d2: torch.Tensor, idx: torch.Tensor, counters: torch.Tensor) -> None:
+    """queries f32 (m,3) against cloud_index_build's table and cells: d2 f64 (m,) = (dx dx + dy dy) + dz dz of the
+    nearest indexed point within max_dist (inclusive; ties: the smallest original index), idx int32 (m,) its index;
+    +inf / -1 without one; counters int64 (4,) = CLOUD_NEAREST_COUNTERS (zeroed by the call)."""
+    lib = _L.load()
+    dev = table.device
+    assert table.dtype == torch.int64 and table.is_contiguous() and table.numel() % 8 == 0 and table.is_cuda
+    assert cells.dtype == torch.int32 and cells.is_contiguous() and cells.ndim == 2 and cells.shape[1] == 4
+    assert queries.dtype == torch.float32 and queries.is_contiguous() and queries.ndim == 2 and queries.shape[1] == 3
+    n, m = int(cells.shape[0]), int(queries.shape[0])
+    assert d2.dtype == torch.float64 and d2.is_contiguous() and d2.numel() == m
+    assert idx.dtype == torch.int32 and idx.is_contiguous() and idx.numel() == m
+    assert counters.dtype == torch.int64 and counters.is_contiguous() and counters.numel() >= 4
+    assert all(t.device == dev for t in (cells, queries, d2, idx, counters))
+    rc = lib.pi3_cloud_nearest(table.data_ptr(), table.numel() // 8, cells.data_ptr() if n else None, n, float(inv_cell),
+                               queries.data_ptr() if m else None, m, float(max_dist), d2.data_ptr() if m else None,
+                               idx.data_ptr() if m else None, counters.data_ptr(), _L.stream_ptr())
+    _L.check(rc, "pi3_cloud_nearest")
+
+
 # ---------------------------------------------------------------------------------------------------- map renderer
 RENDER_CAM_DOUBLES = 20     # world->camera 3x4 row-major, fx, fy, cx, cy, ortho flag, 3 spare (csrc/render.hip)
 

@@ -1,0 +1,139 @@
+"""The numbers of DESIGN.md 7d: what the cloud search (csrc/cloud_nn.hip) costs and what map scoring says about the
+dense map's cleaning and carving flags on the synthetic room.  Needs the GPU.
+
+    python tools/map_eval_timing.py --timing      # build / query time at 1 M x 1 M and 4 M x 4 M reference_cloud points
+    python tools/map_eval_timing.py --example     # F-score of the plain, cleaned, carved and carved + cleaned map
+
+--timing: cloud A = reference_cloud(frame_step=2, pixel_stride=2), cloud B = reference_cloud(frame_step=1,
+pixel_stride=4) of the 1 000-frame chess-room sequence, n random points of each (in frame order, and shuffled), index
+A, query B, max_dist = 4 voxels of 2 cm; hip events around the ops calls, median and minimum of 5 after one warm-up.
+--example: 180 frames at 308 x 406 in chunks of 100 / 20 through the real creator (2 cm voxels, confidence 0.7,
+--dense-min-views 2, depth keyframes every 2nd frame at stride 2) and OfflineReconstructor without bundle adjustment;
+dense_points.ply against reference_cloud() after the trajectory pair's alignment, both resampled at 2 cm."""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import tempfile
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import synth_sequence as ss  # noqa: E402
+
+GT = os.path.join(ROOT, "tests", "golden", "gt_7scenes_chess.txt")
+VOXEL = 0.02
+MAX_DIST = 4 * VOXEL
+THRESHOLDS = (0.02, 0.05)
+VARIANTS = {"plain": {},
+            "cleaned (--dense-min-support 4 --dense-min-component 50)": dict(dense_min_support=4, dense_min_component=50),
+            "carved (--dense-carve-min-conflicts 3)": dict(dense_carve_min_conflicts=3),
+            "carved + cleaned": dict(dense_carve_min_conflicts=3, dense_min_support=4, dense_min_component=50)}
+
+
+def timed(fn, reps=5):
+    fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        ts.append(e0.elapsed_time(e1))
+    return float(np.median(ts)), float(min(ts))
+
+
+def pick(cloud, n, gen, shuffle):
+    idx = torch.randperm(len(cloud), device=cloud.device, generator=gen)[:n]
+    if not shuffle:
+        idx = idx.sort().values
+    return cloud[idx].contiguous()
+
+
+def timing(dev):
+    from pi3_slam_amd import ops
+    seq = ss.SyntheticSequence(GT)
+    a = seq.reference_cloud(frame_step=2, pixel_stride=2, device=dev)
+    b = seq.reference_cloud(frame_step=1, pixel_stride=4, device=dev)
+    print(f"cloud A: {len(a)} points; cloud B: {len(b)} points", flush=True)
+    gen = torch.Generator(device=dev).manual_seed(1)
+    inv = ops.cloud_inv_cell(MAX_DIST)
+    for n in (1_000_000, 4_000_000):
+        for shuffle in (False, True):
+            p, q = pick(a, n, gen, shuffle), pick(b, n, gen, shuffle)
+            table = torch.empty(ops.voxel_capacity(n) * 8, dtype=torch.int64, device=dev)
+            cells = torch.empty((n, 4), dtype=torch.int32, device=dev)
+            d2 = torch.empty(n, dtype=torch.float64, device=dev)
+            idx = torch.empty(n, dtype=torch.int32, device=dev)
+            cb, cq = torch.zeros(4, dtype=torch.int64, device=dev), torch.zeros(4, dtype=torch.int64, device=dev)
+            tb = timed(lambda: ops.cloud_index_build(p, inv, table, cells, cb))
+            tq = timed(lambda: ops.cloud_nearest(table, cells, inv, q, MAX_DIST, d2, idx, cq))
+            bs = dict(zip(ops.CLOUD_INDEX_COUNTERS, cb.tolist()))
+            qs = dict(zip(ops.CLOUD_NEAREST_COUNTERS, cq.tolist()))
+            print(json.dumps(dict(n=n, m=n, order="shuffled" if shuffle else "frame order", max_dist=MAX_DIST,
+                                  build_ms_median=tb[0], build_ms_min=tb[1], query_ms_median=tq[0], query_ms_min=tq[1],
+                                  build=bs, query=qs, evaluations_per_query=qs["evaluations"] / n,
+                                  points_per_cell=(n - bs["dropped"]) / max(bs["cells"], 1))), flush=True)
+            del table, cells, d2, idx, p, q
+
+
+def items(seq, dev):
+    for c, (a, b) in enumerate(seq.chunks):
+        yield {"frames": seq.frames(c, dev), "kind": "float", "paths": [seq.frame_name(i) for i in range(a, b)],
+               "meta": {"chunk_index": c, "start_idx": a, "end_idx": b}}
+
+
+def create(seq, out_dir, dev):
+    from pi3_slam_amd.chunk_creator import OfflineChunkCreator, OfflineCreatorConfig
+    cfg = OfflineCreatorConfig(model_path="recipe", output_dir=out_dir, chunk_length=seq.chunk_length, overlap=seq.overlap,
+                               device=dev, do_metric_depth=False, keypoint_type="grid", max_num_keypoints=seq.max_kp,
+                               estimate_camera_params=True, num_loader_workers=0, dense_voxel_size=VOXEL,
+                               dense_conf_threshold=0.7, dense_min_views=2, dense_depth_every=2, dense_depth_stride=2)
+    cr = OfflineChunkCreator(cfg, model=ss.SceneEngine(seq))
+    cr.target_size = (seq.H, seq.W)
+    _, manifest, _ = cr.write_chunks(cr.process_chunks(items(seq, cr.device)))
+    cr.write_run_metadata(manifest)
+
+
+def example(dev):
+    from pi3_slam_amd import map_eval
+    from pi3_slam_amd.reconstructor import OfflineReconstructor
+    tmp = tempfile.mkdtemp()
+    for noise in ("NOISE_BF16", "NOISE_NONE"):
+        seq = ss.SyntheticSequence(GT, noise=dict(getattr(ss, noise)), n_frames=180)
+        ref = seq.reference_cloud(device=dev)
+        cdir = os.path.join(tmp, noise)
+        create(seq, cdir, dev)
+        for i, (name, kw) in enumerate(VARIANTS.items()):
+            rdir = os.path.join(cdir, f"rec_{i}")
+            OfflineReconstructor(chunk_dir=cdir, output_dir=rdir, bundle_adjust=False, device=dev, **kw).run()
+            est, _ = map_eval.read_ply_points(os.path.join(rdir, "dense_points.ply"))
+            T = map_eval.trajectory_alignment(os.path.join(rdir, "trajectory_tum.txt"), GT)
+            res = map_eval.compare_clouds(est, ref, THRESHOLDS, transform=T, voxel_size=VOXEL, device=dev)
+            print(f"==== {noise} / {name}\n{map_eval.format_table(res)}", flush=True)
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--timing", action="store_true")
+    ap.add_argument("--example", action="store_true")
+    ap.add_argument("--device", default="cuda:0")
+    a = ap.parse_args(argv)
+    if not (a.timing or a.example):
+        ap.error("give --timing and / or --example")
+    if a.timing:
+        timing(a.device)
+    if a.example:
+        example(a.device)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

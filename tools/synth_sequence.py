@@ -182,6 +182,27 @@ class SyntheticSequence:
         conf = 3.0 + 0.5 * torch.randn(z.shape, generator=gen, **f64) - 6.0 * low_conf.to(torch.float64)
         return dict(points=points32, local_points=local32, conf=conf.to(torch.float32)[..., None], camera_poses=pose32)
 
+    def reference_cloud(self, frame_step: int = 1, pixel_stride: int = 1, device="cpu") -> torch.Tensor:
+        """The room as the ground-truth cameras see it: the world-frame, noise-free hit point of every pixel_stride-th
+        pixel (rows and columns) of every frame_step-th frame, ray-cast in f64, returned as f32 (P,3) on `device`.
+        Hits on sphere 0 are left out: it is the low-confidence object, which a map's confidence filter removes on
+        purpose.  The ground truth for scoring a dense map of this sequence (pi3_slam_amd/map_eval.py)."""
+        f64 = dict(dtype=torch.float64, device=device)
+        v, u = torch.meshgrid(torch.arange(0, self.H, int(pixel_stride), **f64),
+                              torch.arange(0, self.W, int(pixel_stride), **f64), indexing="ij")
+        d_cam = torch.stack([(u.reshape(-1) - self.cx) / self.fx, (v.reshape(-1) - self.cy) / self.fy,
+                             torch.ones(u.numel(), **f64)], dim=-1)                      # (P,3), z = 1
+        ids = np.arange(0, self.n, int(frame_step))
+        out = []
+        for a in range(0, len(ids), 16):
+            Pw = torch.as_tensor(self.poses_gt[ids[a:a + 16]], **f64)
+            R, o = Pw[:, :3, :3], Pw[:, :3, 3]
+            d_w = torch.einsum("nij,pj->npi", R, d_cam)
+            t, low_conf = self._cast(o[:, None, :], d_w)
+            X = o[:, None, :] + t[..., None] * d_w
+            out.append(X[~low_conf].to(torch.float32))
+        return torch.cat(out, 0) if out else torch.zeros(0, 3, dtype=torch.float32, device=device)
+
     def intrinsics(self, n: int) -> torch.Tensor:
         """What a chunk file says about this camera: the true focal, the principal point as the reference writes it
         (utils/camera_estimation.py:52-53: W // 2, H // 2)."""

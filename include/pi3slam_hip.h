@@ -507,6 +507,30 @@ int pi3_cloud_index_build(const float* points, long n, float inv_cell, void* tab
  * call.  m == 0 launches nothing; n == 0: every query is beyond (none is dropped), cells may be NULL. */
 int pi3_cloud_nearest(const void* table, long capacity, const void* cells, long n, float inv_cell, const float* queries,
                       long m, double max_dist, double* d2, int* idx, unsigned long long* counters, void* stream);
+/* pi3_cloud_pair_equations (csrc/cloud_icp.hip): the normal equations of one ICP step from the pairs of a search.
+ * queries f32 [m][3]: the estimate, already moved by the current transform (the rows pi3_cloud_nearest was given);
+ * points f32 [n][3]: the indexed cloud in its original order; idx int32 [m], d2 f64 [m] as pi3_cloud_nearest wrote them.
+ * centre HOST f64 [3] (finite); Rn HOST f64 [9] row-major or NULL (= identity), read in mode 2 only; both are read
+ * during the call.  normals_of: 0 point to point (normals ignored); 1 normals f32 [n][3] read at idx[i] (the target's);
+ * 2 normals f32 [m][3] read at i (the source's), each first rotated by Rn.
+ * Pair i takes part when 0 <= idx[i] < n (else "unmatched"), d2[i] <= trim_dist trim_dist (inclusive, the product formed
+ * once in f64; else "trimmed") and, in modes 1 and 2, the (rotated) normal a has 0 < (a0 a0 + a1 a1) + a2 a2 < inf (else
+ * "normal rejected": zero, NaN, inf); n = a / sqrt(that), in f64.  With p = query, q = points[idx], x = p - centre,
+ * e = p - q (f64), the motion p' = p + w x x + l x + t about centre and J = [ -[x]x | x | I ] (parameters w (3), l, t (3)):
+ *   mode 0:     A += J^T J,  b += J^T e,  r2 += e.e;
+ *   modes 1, 2: j = J^T n = (x x n, x.n, n),  r = n.e:   A += j j^T,  b += j r,  r2 += r r.
+ * out DEVICE f64 [40] = the 28 entries of A's upper triangle row-major, the 7 of b, r2, the sum of e.e (in every mode),
+ * 3 zeros.  counters DEVICE uint64 [4] = pairs used, unmatched, trimmed, normal rejected; zeroed by the call.
+ * The sums are bitwise reproducible (no floating-point atomics): a workgroup covers 4096 consecutive queries and writes
+ * one row of 40 doubles into partials (DEVICE f64 [partial_rows][40], partial_rows >= ceil(m / 4096):
+ * ops.cloud_icp_partial_rows; fewer: PI3_ERR_WORKSPACE), a second launch of one workgroup adds the rows in a fixed
+ * order.  m == 0 launches nothing and writes zeros.  Bad arguments (a negative size, normals_of outside 0..2, NULL
+ * where a row array is needed, trim_dist not finite or < 0, a centre or Rn that is not finite) launch nothing and leave
+ * out and counters untouched.  No allocation, no synchronisation. */
+int pi3_cloud_pair_equations(const float* queries, long m, const float* points, long n, const int* idx,
+                             const double* d2, double trim_dist, const double* centre, const float* normals,
+                             int normals_of, const double* Rn, double* partials, long partial_rows, double* out,
+                             unsigned long long* counters, void* stream);
 
 /* ---- dense map -> camera views (csrc/render.hip): a z-buffered splat renderer for the voxel map.
  * points f32 [V][3] (the voxel centroids, in ascending key order), weights int32 [V] (or NULL: every voxel counts),

@@ -16,7 +16,7 @@ from __future__ import annotations
 import argparse
 import glob
 import os
-from typing import Dict, List, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 # (flag, kwargs) - names, types and defaults follow the reference scripts; REQ marks what has a personal default path there
 REQ = dict(required=True)
@@ -204,9 +204,18 @@ EVAL_FLAGS: Sequence[Tuple[str, Dict]] = (
     ("--reference-trajectory", dict(default=None, help="TUM trajectory of the reference")),
     ("--error-ply", dict(default=None, help="write the (resampled, transformed) estimate coloured by its distance to "
                                             "the reference: green 0, red max-dist, magenta beyond")),
+    ("--icp", dict(default=None, choices=("point", "plane"), help="refine the alignment by ICP on the (resampled) clouds "
+                   "before scoring: point to point, or point to plane (the reference's nx ny nz when its PLY has them, "
+                   "otherwise the estimate's); default: off")),
+    ("--icp-iterations", dict(type=int, default=30, help="with --icp: the iteration limit")),
+    ("--icp-max-dist", dict(type=float, default=None, help="with --icp: pairs farther apart take no part "
+                                                           "(default: the search's --max-dist)")),
+    ("--save-transform", dict(default=None, help="write the similarity that was applied to the estimate (after --icp: "
+                                                 "the refined one) in the form --transform reads")),
     ("--device", dict(default="cuda")),
 )
-EVAL_SWITCHES = (("--json", "print the result as one JSON line instead of the table"),)
+EVAL_SWITCHES = (("--json", "print the result as one JSON line instead of the table"),
+                 ("--icp-scale", "with --icp: refine the scale too (a similarity instead of a rigid motion)"))
 
 
 def list_images(root: str) -> List[str]:
@@ -367,15 +376,42 @@ def evaluate_map_transform(a: argparse.Namespace):
     return None
 
 
+def evaluate_map_icp(a: argparse.Namespace, est: Dict, ref: Dict) -> Optional[Dict]:
+    """compare_clouds' icp argument from the --icp flags and the two PLYs' vertices; None without --icp."""
+    if a.icp is None:
+        if a.icp_scale:
+            raise SystemExit("evaluate-map: --icp-scale needs --icp point|plane")
+        return None
+    if a.icp_iterations < 1:
+        raise SystemExit("evaluate-map: --icp-iterations must be at least 1")
+    icp = dict(mode=a.icp, with_scale=bool(a.icp_scale), iterations=a.icp_iterations, max_dist=a.icp_max_dist)
+    if a.icp == "plane":
+        if ref["normals"] is not None:
+            icp["ref_normals"] = ref["normals"]
+        elif est["normals"] is not None:
+            icp["est_normals"] = est["normals"]
+        else:
+            raise SystemExit("evaluate-map: --icp plane needs nx ny nz in the reference's or the estimate's PLY")
+    return icp
+
+
 def run_evaluate_map(a: argparse.Namespace) -> None:
     import json
 
+    import numpy as np
+
     from . import map_eval
     from .export import write_ply
-    est, _ = map_eval.read_ply_points(a.estimate)
-    ref, _ = map_eval.read_ply_points(a.reference)
+    if a.icp is None and a.icp_scale:              # refused before anything is read
+        raise SystemExit("evaluate-map: --icp-scale needs --icp point|plane")
+    ev, rv = map_eval.read_ply_vertices(a.estimate), map_eval.read_ply_vertices(a.reference)
+    est, ref = ev["points"], rv["points"]
+    icp = evaluate_map_icp(a, ev, rv)
     res = map_eval.compare_clouds(est, ref, a.thresholds, max_dist=a.max_dist, transform=evaluate_map_transform(a),
-                                  voxel_size=a.voxel_size, device=a.device)
+                                  voxel_size=a.voxel_size, device=a.device, **({} if icp is None else {"icp": icp}))
+    if a.save_transform:
+        applied = res["settings"]["transform"]
+        map_eval.write_transform(a.save_transform, np.eye(4) if applied is None else applied)
     if a.error_ply:
         write_ply(res["_points"]["estimate"],
                   map_eval.error_colors(res["_distances"]["estimate"], res["settings"]["max_dist"]), a.error_ply)

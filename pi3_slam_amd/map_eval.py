@@ -11,7 +11,12 @@ The distances are exact nearest neighbours within `max_dist` (csrc/cloud_nn.hip:
 cells of 1.25 max_dist, f64 distances, ties to the smallest index); a point with no neighbour that close is "beyond" and
 carries inf.  The statistics are numpy f64 on the host.  There is no CPU fallback for the search.
 
+The estimate is placed on the reference by a given similarity or by the trajectory pair's; icp_refine then refines that
+placement on the geometry (point to point or point to plane, rigid or with scale): the search and the reduction of the
+pairs to normal equations run on the device (csrc/cloud_icp.hip), the 7 x 7 solve on the host.
+
     python -m pi3_slam_amd.cli evaluate-map --estimate dense_points.ply --reference GT.ply --thresholds 0.02 0.05
+                                            [--icp plane] [--save-transform T.txt]
 """
 from __future__ import annotations
 
@@ -58,9 +63,15 @@ class CloudIndex:
         d2 = torch.empty(m, dtype=torch.float64, device=self.device)
         idx = torch.empty(m, dtype=torch.int32, device=self.device)
         counters = torch.zeros(4, dtype=torch.int64, device=self.device)
-        ops.cloud_nearest(self.table, self.cells, self.inv_cell, q, self.max_dist, d2, idx, counters)
+        self.nearest_into(q, d2, idx, counters)
         self.last_stats = dict(zip(ops.CLOUD_NEAREST_COUNTERS, (int(x) for x in counters.tolist())), queries=m)
         return d2, idx.long()
+
+    def nearest_into(self, q: torch.Tensor, d2: torch.Tensor, idx: torch.Tensor, counters: torch.Tensor) -> None:
+        """The same search into the caller's buffers (q f32 (m,3), d2 f64 (m,), idx int32 (m,), counters int64 (4,) on
+        the index's device), as the kernel writes them and without a copy to the host: what icp_refine hands on to
+        ops.cloud_pair_equations every iteration."""
+        ops.cloud_nearest(self.table, self.cells, self.inv_cell, q, self.max_dist, d2, idx, counters)
 
 
 def _device_points(points, device) -> torch.Tensor:
@@ -132,7 +143,8 @@ def resample(points: torch.Tensor, voxel_size: float) -> torch.Tensor:
 
 
 def compare_clouds(est, ref, thresholds: Sequence[float], max_dist: Optional[float] = None, transform=None,
-                   voxel_size: Optional[float] = None, device="cuda", _nearest: Optional[Callable] = None) -> Dict:
+                   voxel_size: Optional[float] = None, device="cuda", _nearest: Optional[Callable] = None,
+                   icp: Optional[Dict] = None) -> Dict:
     """est, ref: (n,3) clouds.  transform: a 4x4 similarity applied to est on the device (ops.sim3_apply).  voxel_size:
     both clouds are first resampled to one point per voxel.  max_dist: the search radius, 2 max(thresholds) by default;
     every threshold must be <= max_dist.  -> {'points', 'dropped', 'accuracy', 'completeness', 'precision', 'recall',
@@ -140,7 +152,15 @@ def compare_clouds(est, ref, thresholds: Sequence[float], max_dist: Optional[flo
     scores per tau_key(threshold), and under '_distances' the per-point distance arrays ('estimate' row for row with
     the (resampled, transformed) estimate under '_points', 'reference' likewise).  A dropped point (not finite, or
     outside the grid's 2^20 cells per axis) counts as beyond.  _nearest: the search itself, for tests that drive this
-    function with a reference implementation: (ref, queries, max_dist) device tensors -> _device_nearest's dict."""
+    function with a reference implementation: (ref, queries, max_dist) device tensors -> _device_nearest's dict.
+    icp: icp_refine's keyword arguments (mode, est_normals, ref_normals, with_scale, max_dist (default: the search's),
+    iterations, tolerance; normals row for row with est / ref as given, the estimate's in its own frame).  The
+    refinement runs after `transform` and the resampling, on the resampled clouds; a resampled point takes the normal
+    of the nearest original point (nearest_normals), not an average.  The refined similarity (the ICP's increment times
+    `transform`) is then applied to the original estimate and the scoring proceeds as if it had been given as
+    `transform`: 'settings'['transform'] reports it, and passing it back as `transform` without icp reproduces the
+    scores.  The result gains 'icp': status, iterations, history, transform (the final matrix), increment.  Without
+    icp the result has no such key and is what it was."""
     ths = [float(t) for t in thresholds]
     if not ths:
         raise ValueError("compare_clouds needs at least one threshold")
@@ -151,6 +171,12 @@ def compare_clouds(est, ref, thresholds: Sequence[float], max_dist: Optional[flo
     if transform is not None:
         M = np.asarray(torch.as_tensor(transform, dtype=torch.float64).cpu().numpy(), np.float64).reshape(4, 4)
         e = e.clone()
+        ops.sim3_apply(torch.from_numpy(M).to(dev).contiguous(), e, None)
+    refined = None
+    if icp is not None:
+        refined = _refine_alignment(_device_points(est, dev), e, r, None if transform is None else M, voxel_size, md, icp)
+        transform = M = refined["transform"]
+        e = _device_points(est, dev).clone()
         ops.sim3_apply(torch.from_numpy(M).to(dev).contiguous(), e, None)
     if voxel_size is not None:
         e, r = resample(e, voxel_size), resample(r, voxel_size)
@@ -179,9 +205,179 @@ def compare_clouds(est, ref, thresholds: Sequence[float], max_dist: Optional[flo
         k = tau_key(t)
         p, rc = acc["within"][k], comp["within"][k]
         out["precision"][k], out["recall"][k], out["fscore"][k] = p, rc, fscore(p, rc)
+    if refined is not None:
+        out["icp"] = {"status": refined["status"], "iterations": refined["iterations"], "history": refined["history"],
+                      "transform": [[float(x) for x in row] for row in refined["transform"]],
+                      "increment": [[float(x) for x in row] for row in refined["increment"]]}
     out["_distances"] = {"estimate": d_er, "reference": d_re}
     out["_points"] = {"estimate": e.cpu().numpy(), "reference": r.cpu().numpy()}
     return out
+
+
+# ------------------------------------------------------------------------------------------------------ ICP
+ICP_MIN_PAIRS = 16
+ICP_MIN_EIGEN_RATIO = 1e-9
+_ICP_KEYS = ("mode", "est_normals", "ref_normals", "with_scale", "max_dist", "iterations", "tolerance")
+
+
+def unpack_equations(out40) -> Tuple[np.ndarray, np.ndarray, float, float]:
+    """The 40 doubles of ops.cloud_pair_equations -> (A 7x7 symmetric, b (7,), r2, the sum of e.e)."""
+    v = np.asarray(out40, np.float64).reshape(-1)
+    A = np.zeros((7, 7))
+    A[np.triu_indices(7)] = v[:28]
+    A = A + np.triu(A, 1).T
+    return A, v[28:35].copy(), float(v[35]), float(v[36])
+
+
+def sim3_increment(x, centre) -> np.ndarray:
+    """x = (w (3), l, t (3)): the 4x4 similarity D = [ s R | centre + t - s R centre ] with R = exp([w]x) (Rodrigues)
+    and s = exp(l): the finite form of p' = p + w x (p - centre) + l (p - centre) + t.  x = 0 gives the identity
+    exactly."""
+    x = np.asarray(x, np.float64).reshape(7)
+    c = np.asarray(centre, np.float64).reshape(3)
+    w, lam, t = x[:3], float(x[3]), x[4:]
+    th = float(np.sqrt(w @ w))
+    R = np.eye(3)
+    if th > 0.0:
+        K = np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]]) / th
+        R = R + np.sin(th) * K + (1.0 - np.cos(th)) * (K @ K)
+    sR = np.exp(lam) * R
+    D = np.eye(4)
+    D[:3, :3] = sR
+    D[:3, 3] = (c + t) - sR @ c
+    return D
+
+
+def _rotation_of(M: np.ndarray) -> np.ndarray:
+    """The rotation part of a similarity: M[:3,:3] / cbrt(det)."""
+    return M[:3, :3] / np.cbrt(np.linalg.det(M[:3, :3]))
+
+
+def _device_normals(normals, rows: int, device) -> torch.Tensor:
+    t = _device_points(normals, device)
+    if int(t.shape[0]) != rows:
+        raise ValueError(f"{int(t.shape[0])} normals for a cloud of {rows} points")
+    return t
+
+
+def icp_refine(est, ref, *, mode: str, est_normals=None, ref_normals=None, with_scale: bool = False, max_dist: float,
+               iterations: int = 30, tolerance: float = 1e-7, init=None, device="cuda") -> Dict:
+    """Refines the 4x4 similarity that places `est` (n,3) on `ref` (m,3) by ICP: point to point (mode="point") or point
+    to plane (mode="plane": the reference's normals when given, otherwise the estimate's, rotated by the current
+    transform's rotation; with neither: ValueError).  Rigid, or with `with_scale` a similarity.
+    Once: CloudIndex(ref, max_dist); centre = the reference's f64 centroid.  Per iteration: M applied to the ORIGINAL
+    estimate (ops.sim3_apply; moving the previous iteration's rows instead would compound fp32 rounding), the exact
+    nearest neighbours within max_dist, ops.cloud_pair_equations on those rows, the 40 doubles to the host, numpy f64
+    solves A x = -b on the 7 parameters (6 without scale: row and column l removed), M <- sim3_increment(x, centre) M.
+    status: 'converged' (|x| < tolerance; that step is applied), 'max_iterations', 'too_few_pairs' (fewer than 16 pairs
+    used), 'degenerate' (the solved block of A / pairs, scaled to unit diagonal, has eigenvalue ratio min / max below
+    1e-9: a single plane under point to plane, a line); the last two keep the M from before that iteration.
+    -> transform, increment (= transform init^-1), status, iterations, history (per iteration: pairs, counters, rms =
+    sqrt(r2 / pairs), point_rms = sqrt(sum e.e / pairs), step = |x|; None where nothing was solved)."""
+    if mode not in ("point", "plane"):
+        raise ValueError(f"icp mode must be 'point' or 'plane', got {mode!r}")
+    if mode == "plane" and est_normals is None and ref_normals is None:
+        raise ValueError("icp mode 'plane' needs normals: the reference's, or the estimate's")
+    md = float(max_dist)
+    dev = torch.device(device)
+    e0, r = _device_points(est, dev), _device_points(ref, dev)
+    m, n = int(e0.shape[0]), int(r.shape[0])
+    normals, normals_of = None, 0
+    if mode == "plane":
+        if ref_normals is not None:
+            normals, normals_of = _device_normals(ref_normals, n, dev), 1
+        else:
+            normals, normals_of = _device_normals(est_normals, m, dev), 2
+    M0 = np.eye(4) if init is None else np.array(torch.as_tensor(init, dtype=torch.float64).cpu().numpy(), np.float64).reshape(4, 4)
+    M = M0.copy()
+    index = CloudIndex(r, md, dev)
+    ok = torch.isfinite(r).all(1)
+    centre = r[ok].double().mean(0).cpu().numpy() if bool(ok.any()) else np.zeros(3)
+    d2 = torch.empty(m, dtype=torch.float64, device=dev)
+    idx = torch.empty(m, dtype=torch.int32, device=dev)
+    nn_counters = torch.zeros(4, dtype=torch.int64, device=dev)
+    counters = torch.zeros(4, dtype=torch.int64, device=dev)
+    partials = torch.empty((ops.cloud_icp_partial_rows(m), ops.CLOUD_ICP_DOUBLES), dtype=torch.float64, device=dev)
+    out = torch.zeros(ops.CLOUD_ICP_DOUBLES, dtype=torch.float64, device=dev)
+    sel = np.arange(7) if with_scale else np.array([0, 1, 2, 4, 5, 6])
+    history, status = [], "max_iterations"
+    for _ in range(int(iterations)):
+        moved = e0.clone()
+        if m:
+            ops.sim3_apply(torch.from_numpy(M).to(dev).contiguous(), moved, None)
+        index.nearest_into(moved, d2, idx, nn_counters)
+        Rn = _rotation_of(M) if normals_of == 2 else None
+        ops.cloud_pair_equations(moved, index.points, idx, d2, md, centre, normals, normals_of, Rn, partials, out, counters)
+        A, b, r2, ee = unpack_equations(out.cpu().numpy())
+        cnt = dict(zip(ops.CLOUD_ICP_COUNTERS, (int(v) for v in counters.tolist())))
+        pairs = cnt["used"]
+        entry = {"pairs": pairs, "counters": cnt, "rms": float(np.sqrt(r2 / pairs)) if pairs else None,
+                 "point_rms": float(np.sqrt(ee / pairs)) if pairs else None, "step": None}
+        history.append(entry)
+        if pairs < ICP_MIN_PAIRS:
+            status = "too_few_pairs"
+            break
+        As, bs = A[np.ix_(sel, sel)], b[sel]
+        dg = np.sqrt(np.diag(As) / pairs)
+        if not (np.isfinite(As).all() and np.isfinite(bs).all() and (dg > 0.0).all()):
+            status = "degenerate"
+            break
+        ev = np.linalg.eigvalsh((As / pairs) / np.outer(dg, dg))
+        if not (ev[-1] > 0.0 and ev[0] / ev[-1] >= ICP_MIN_EIGEN_RATIO):
+            status = "degenerate"
+            break
+        x = np.zeros(7)
+        x[sel] = np.linalg.solve(As, -bs)
+        if not np.isfinite(x).all():
+            status = "degenerate"
+            break
+        M = sim3_increment(x, centre) @ M
+        entry["step"] = float(np.sqrt(x @ x))
+        if entry["step"] < float(tolerance):
+            status = "converged"
+            break
+    return {"transform": M, "increment": M @ np.linalg.inv(M0) if init is not None else M.copy(), "status": status,
+            "iterations": len(history), "history": history}
+
+
+def nearest_normals(points: torch.Tensor, normals, kept: torch.Tensor, radius: float) -> torch.Tensor:
+    """The normals of a resampled cloud: every kept voxel's centroid takes the normal of the nearest original point
+    (CloudIndex over `points`, radius = 2 voxel edges: a centroid lies within sqrt(3) edges of its voxel's members); a
+    centroid without one gets a zero normal, which the ICP kernel rejects."""
+    nrm = _device_normals(normals, int(points.shape[0]), points.device)
+    _, idx = CloudIndex(points, radius, points.device).nearest(kept)
+    got = nrm[idx.clamp(min=0)]
+    got[idx < 0] = 0.0
+    return got.contiguous()
+
+
+def _refine_alignment(est0: torch.Tensor, e: torch.Tensor, r: torch.Tensor, T: Optional[np.ndarray],
+                      voxel_size: Optional[float], md: float, icp: Dict) -> Dict:
+    """compare_clouds' ICP step.  est0: the estimate as given, e: the same moved by T (or est0 itself), r: the
+    reference.  -> icp_refine's result with transform = increment T."""
+    unknown = sorted(set(icp) - set(_ICP_KEYS))
+    if unknown or "mode" not in icp:
+        raise ValueError(f"compare_clouds: icp takes {_ICP_KEYS} and needs 'mode'; got {sorted(icp)}")
+    kw = {k: v for k, v in icp.items() if k not in ("est_normals", "ref_normals", "max_dist")}
+    kw["max_dist"] = md if icp.get("max_dist") is None else float(icp["max_dist"])
+    en, rn = icp.get("est_normals"), icp.get("ref_normals")
+    if en is not None:
+        en = _device_normals(en, int(est0.shape[0]), e.device)
+        if T is not None:                      # into the frame the moved estimate is in
+            en = (en.double() @ torch.from_numpy(_rotation_of(T)).to(e.device).T).float().contiguous()
+    if rn is not None:
+        rn = _device_normals(rn, int(r.shape[0]), r.device)
+    pe, pr = e, r
+    if voxel_size is not None:
+        pe, pr = resample(e, voxel_size), resample(r, voxel_size)
+        if en is not None:
+            en = nearest_normals(e, en, pe, 2.0 * float(voxel_size))
+        if rn is not None:
+            rn = nearest_normals(r, rn, pr, 2.0 * float(voxel_size))
+    res = icp_refine(pe, pr, est_normals=en, ref_normals=rn, init=None, device=e.device, **kw)
+    res["increment"] = res["transform"]
+    res["transform"] = res["increment"] @ T if T is not None else res["increment"].copy()
+    return res
 
 
 def public(result: Dict) -> Dict:
@@ -229,10 +425,18 @@ def _ply_header(f, path: str):
 
 
 def read_ply_points(path: str) -> Tuple[np.ndarray, Optional[np.ndarray]]:
-    """-> (points f32 (V,3), colors u8 (V,3) or None) of the file's vertex element.  binary_little_endian or ascii; the
-    vertex properties in any order and of any scalar type, x y z float or double; red green blue taken when all three
-    are uchar; elements after the vertices (faces) are not read; an element before them is skipped when its size
-    is known from the header (no list property)."""
+    """-> (points f32 (V,3), colors u8 (V,3) or None) of the file's vertex element: read_ply_vertices without the
+    normals."""
+    v = read_ply_vertices(path)
+    return v["points"], v["colors"]
+
+
+def read_ply_vertices(path: str) -> Dict:
+    """-> {'points' f32 (V,3), 'colors' u8 (V,3) or None, 'normals' f32 (V,3) or None} of the file's vertex element.
+    binary_little_endian or ascii; the vertex properties in any order and of any scalar type, x y z float or double;
+    red green blue taken when all three are uchar, nx ny nz when all three are float or double; elements after the
+    vertices (faces) are not read; an element before them is skipped when its size is known from the header (no list
+    property)."""
     with open(path, "rb") as f:
         fmt, elements = _ply_header(f, path)
         names = [e["name"] for e in elements]
@@ -276,7 +480,10 @@ def read_ply_points(path: str) -> Tuple[np.ndarray, Optional[np.ndarray]]:
     colors = None
     if all(kinds.get(c) == "u1" for c in ("red", "green", "blue")):
         colors = np.stack([np.asarray(col[c]).astype(np.uint8) for c in ("red", "green", "blue")], 1).reshape(V, 3)
-    return pts, colors
+    normals = None
+    if all(kinds.get(c) in ("f4", "f8") for c in ("nx", "ny", "nz")):
+        normals = np.stack([np.asarray(col[c], np.float64) for c in ("nx", "ny", "nz")], 1).astype(np.float32).reshape(V, 3)
+    return {"points": pts, "colors": colors, "normals": normals}
 
 
 # ------------------------------------------------------------------------------------------------------ alignment
@@ -308,6 +515,15 @@ def trajectory_alignment(est_tum: str, ref_tum: str, max_diff: float = 0.01) -> 
     return M
 
 
+def write_transform(path: str, M) -> None:
+    """The 16 numbers of a 4x4 similarity, four per line, each with the digits that read back to the same double: what
+    read_transform (--transform) reads."""
+    M = np.asarray(M, np.float64).reshape(4, 4)
+    with open(path, "w") as f:
+        for row in M:
+            f.write(" ".join(repr(float(x)) for x in row) + "\n")
+
+
 def read_transform(path: str) -> np.ndarray:
     """A text file with the 16 numbers of a row-major 4x4 similarity."""
     M = np.loadtxt(path, dtype=np.float64).reshape(-1)
@@ -334,4 +550,15 @@ def format_table(res: Dict) -> str:
     for t in s["thresholds"]:
         k = tau_key(t)
         lines.append(f"{t:<14g}{res['precision'][k]:>10.4f}{res['recall'][k]:>10.4f}{res['fscore'][k]:>10.4f}")
+    if "icp" in res:
+        lines += ["", format_icp_line(res["icp"])]
     return "\n".join(lines)
+
+
+def format_icp_line(icp: Dict) -> str:
+    """The table's line about the refinement: status, iterations, the last iteration's pairs, rms before -> after."""
+    h = icp["history"]
+    first, last = (h[0]["rms"], h[-1]["rms"]) if h else (None, None)
+    num = lambda v: "-" if v is None else f"{v:.5f}"                                  # noqa: E731
+    return (f"icp: {icp['status']} after {icp['iterations']} iterations, {h[-1]['pairs'] if h else 0} pairs, "
+            f"rms {num(first)} -> {num(last)}")

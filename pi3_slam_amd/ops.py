@@ -937,6 +937,53 @@ def cloud_nearest(table: torch.Tensor, cells: torch.Tensor, inv_cell: float, que
     _L.check(rc, "pi3_cloud_nearest")
 
 
+# ---- the normal equations of one ICP step from a search's pairs (csrc/cloud_icp.hip)
+CLOUD_ICP_COUNTERS = ("used", "unmatched", "trimmed", "normal_rejected")
+CLOUD_ICP_SPAN = 4096       # queries per workgroup = per row of partials (kSpan of the kernel)
+CLOUD_ICP_DOUBLES = 40      # A's upper triangle (28), b (7), r2, the sum of e.e, 3 spare
+
+
+def cloud_icp_partial_rows(m: int) -> int:
+    """Rows of CLOUD_ICP_DOUBLES doubles that cloud_pair_equations needs in `partials` for m queries."""
+    return (max(int(m), 0) + CLOUD_ICP_SPAN - 1) // CLOUD_ICP_SPAN
+
+
+def cloud_pair_equations(queries: torch.Tensor, points: torch.Tensor, idx: torch.Tensor, d2: torch.Tensor,
+                         trim_dist: float, centre, normals: Optional[torch.Tensor], normals_of: int, Rn,
+                         partials: torch.Tensor, out: torch.Tensor, counters: torch.Tensor) -> None:
+    """queries f32 (m,3) (the moved estimate, the rows cloud_nearest was given), points f32 (n,3) (the indexed cloud),
+    idx int32 (m,), d2 f64 (m,) as cloud_nearest wrote them -> out f64 (40,) = A's upper triangle row-major (28), b (7),
+    r2, the sum of e.e, 3 zeros, about `centre` (3 host floats) with parameters w (3), l, t (3); counters int64 (4,) =
+    CLOUD_ICP_COUNTERS (zeroed by the call).  normals_of 0: point to point; 1: normals f32 (n,3), the target's; 2:
+    normals f32 (m,3), the source's, rotated by Rn (9 host floats row-major, or None = identity).  partials f64
+    (>= cloud_icp_partial_rows(m), 40): workspace.  Bitwise reproducible."""
+    lib = _L.load()
+    dev = out.device
+    assert queries.dtype == torch.float32 and queries.is_contiguous() and queries.ndim == 2 and queries.shape[1] == 3
+    assert points.dtype == torch.float32 and points.is_contiguous() and points.ndim == 2 and points.shape[1] == 3
+    m, n = int(queries.shape[0]), int(points.shape[0])
+    assert idx.dtype == torch.int32 and idx.is_contiguous() and idx.numel() == m
+    assert d2.dtype == torch.float64 and d2.is_contiguous() and d2.numel() == m
+    assert out.dtype == torch.float64 and out.is_contiguous() and out.numel() >= CLOUD_ICP_DOUBLES and out.is_cuda
+    assert counters.dtype == torch.int64 and counters.is_contiguous() and counters.numel() >= 4
+    assert partials.dtype == torch.float64 and partials.is_contiguous() and partials.numel() % CLOUD_ICP_DOUBLES == 0
+    assert all(t.device == dev for t in (queries, points, idx, d2, counters, partials))
+    if normals_of in (1, 2):
+        assert normals is not None and normals.dtype == torch.float32 and normals.is_contiguous() and normals.device == dev
+        assert tuple(normals.shape) == ((n, 3) if normals_of == 1 else (m, 3)), (tuple(normals.shape), n, m, normals_of)
+    c3 = (C.c_double * 3)(*torch.as_tensor(centre, dtype=torch.float64).reshape(3).tolist())
+    r9 = None if Rn is None else (C.c_double * 9)(*torch.as_tensor(Rn, dtype=torch.float64).reshape(9).tolist())
+    has_normals = normals_of in (1, 2) and normals.numel() > 0
+    rc = lib.pi3_cloud_pair_equations(queries.data_ptr() if m else None, m, points.data_ptr() if n else None, n,
+                                      idx.data_ptr() if m else None, d2.data_ptr() if m else None, float(trim_dist),
+                                      C.cast(c3, C.c_void_p), normals.data_ptr() if has_normals else None,
+                                      int(normals_of), None if r9 is None else C.cast(r9, C.c_void_p),
+                                      partials.data_ptr() if partials.numel() else None,
+                                      partials.numel() // CLOUD_ICP_DOUBLES, out.data_ptr(), counters.data_ptr(),
+                                      _L.stream_ptr())
+    _L.check(rc, "pi3_cloud_pair_equations")
+
+
 # ---------------------------------------------------------------------------------------------------- map renderer
 RENDER_CAM_DOUBLES = 20     # world->camera 3x4 row-major, fx, fy, cx, cy, ortho flag, 3 spare (csrc/render.hip)
 

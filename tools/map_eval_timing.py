@@ -3,13 +3,16 @@ dense map's cleaning and carving flags on the synthetic room.  Needs the GPU.
 
     python tools/map_eval_timing.py --timing      # build / query time at 1 M x 1 M and 4 M x 4 M reference_cloud points
     python tools/map_eval_timing.py --example     # F-score of the plain, cleaned, carved and carved + cleaned map
+    python tools/map_eval_timing.py --icp         # the ICP reduction (csrc/cloud_icp.hip) beside the search, 1 M x 1 M
 
 --timing: cloud A = reference_cloud(frame_step=2, pixel_stride=2), cloud B = reference_cloud(frame_step=1,
 pixel_stride=4) of the 1 000-frame chess-room sequence, n random points of each (in frame order, and shuffled), index
 A, query B, max_dist = 4 voxels of 2 cm; hip events around the ops calls, median and minimum of 5 after one warm-up.
 --example: 180 frames at 308 x 406 in chunks of 100 / 20 through the real creator (2 cm voxels, confidence 0.7,
 --dense-min-views 2, depth keyframes every 2nd frame at stride 2) and OfflineReconstructor without bundle adjustment;
-dense_points.ply against reference_cloud() after the trajectory pair's alignment, both resampled at 2 cm."""
+dense_points.ply against reference_cloud() after the trajectory pair's alignment, both resampled at 2 cm.
+--icp: the clouds and the search of --timing at n = m = 1 M (and 4 M) in frame order, then ops.cloud_pair_equations on
+the search's idx / d2 in each normals_of mode (random normals; mode 2 with a rotation), timed the same way."""
 from __future__ import annotations
 
 import argparse
@@ -84,6 +87,37 @@ def timing(dev):
             del table, cells, d2, idx, p, q
 
 
+def icp_timing(dev):
+    from pi3_slam_amd import ops
+    seq = ss.SyntheticSequence(GT)
+    a = seq.reference_cloud(frame_step=2, pixel_stride=2, device=dev)
+    b = seq.reference_cloud(frame_step=1, pixel_stride=4, device=dev)
+    gen = torch.Generator(device=dev).manual_seed(1)
+    inv = ops.cloud_inv_cell(MAX_DIST)
+    rot = [[0.8, -0.6, 0.0], [0.6, 0.8, 0.0], [0.0, 0.0, 1.0]]
+    for n in (1_000_000, 4_000_000):
+        p, q = pick(a, n, gen, False), pick(b, n, gen, False)
+        table = torch.empty(ops.voxel_capacity(n) * 8, dtype=torch.int64, device=dev)
+        cells = torch.empty((n, 4), dtype=torch.int32, device=dev)
+        d2 = torch.empty(n, dtype=torch.float64, device=dev)
+        idx = torch.empty(n, dtype=torch.int32, device=dev)
+        cb, cq = torch.zeros(4, dtype=torch.int64, device=dev), torch.zeros(4, dtype=torch.int64, device=dev)
+        ops.cloud_index_build(p, inv, table, cells, cb)
+        tq = timed(lambda: ops.cloud_nearest(table, cells, inv, q, MAX_DIST, d2, idx, cq))
+        normals = torch.randn((n, 3), device=dev, generator=gen)
+        partials = torch.empty((ops.cloud_icp_partial_rows(n), ops.CLOUD_ICP_DOUBLES), dtype=torch.float64, device=dev)
+        out = torch.zeros(ops.CLOUD_ICP_DOUBLES, dtype=torch.float64, device=dev)
+        ce = torch.zeros(4, dtype=torch.int64, device=dev)
+        centre = p.double().mean(0).tolist()
+        for mode in (0, 1, 2):
+            te = timed(lambda: ops.cloud_pair_equations(q, p, idx, d2, MAX_DIST, centre, normals if mode else None, mode,
+                                                        rot if mode == 2 else None, partials, out, ce))
+            print(json.dumps(dict(n=n, m=n, normals_of=mode, query_ms_median=tq[0], equations_ms_median=te[0],
+                                  equations_ms_min=te[1], counters=dict(zip(ops.CLOUD_ICP_COUNTERS, ce.tolist())),
+                                  rows=int(partials.shape[0]))), flush=True)
+        del table, cells, d2, idx, p, q, normals, partials
+
+
 def items(seq, dev):
     for c, (a, b) in enumerate(seq.chunks):
         yield {"frames": seq.frames(c, dev), "kind": "float", "paths": [seq.frame_name(i) for i in range(a, b)],
@@ -124,12 +158,15 @@ def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--timing", action="store_true")
     ap.add_argument("--example", action="store_true")
+    ap.add_argument("--icp", action="store_true")
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args(argv)
-    if not (a.timing or a.example):
-        ap.error("give --timing and / or --example")
+    if not (a.timing or a.example or a.icp):
+        ap.error("give --timing, --example and / or --icp")
     if a.timing:
         timing(a.device)
+    if a.icp:
+        icp_timing(a.device)
     if a.example:
         example(a.device)
     return 0

@@ -24,6 +24,12 @@ int pi3_check_launch(const char* what) {
   return PI3_OK;
 }
 
+int pi3_zero_words(const char* who, void* ptr, long n, void* stream) {
+  if (hipMemsetAsync(ptr, 0, (size_t)n * sizeof(unsigned long long), (hipStream_t)stream) == hipSuccess) return PI3_OK;
+  pi3_set_error("%s: hipMemsetAsync failed", who);
+  return PI3_ERR_LAUNCH;
+}
+
 int pi3_lds_optin(const void* kern, int bytes, unsigned long long* done_mask, const char* what) {
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) dev = 0;

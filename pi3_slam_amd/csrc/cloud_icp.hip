@@ -207,11 +207,9 @@ extern "C" int pi3_cloud_pair_equations(const float* queries, long m, const floa
     return PI3_ERR_WORKSPACE;
   }
   hipStream_t st = (hipStream_t)stream;
-  if (hipMemsetAsync(counters, 0, 4 * sizeof(unsigned long long), st) != hipSuccess ||
-      (m == 0 && hipMemsetAsync(out, 0, kRow * sizeof(double), st) != hipSuccess)) {
-    pi3_set_error("pi3_cloud_pair_equations: hipMemsetAsync failed");
+  if (pi3_zero_words("pi3_cloud_pair_equations", counters, 4, stream) != PI3_OK ||
+      (m == 0 && pi3_zero_words("pi3_cloud_pair_equations", out, kRow, stream) != PI3_OK))
     return PI3_ERR_LAUNCH;
-  }
   if (m > 0) {
     PairFrame f;
     for (int k = 0; k < 3; ++k) f.c[k] = centre[k];

@@ -8,8 +8,8 @@
 //                      rows of the cell in a slot are cells[start .. start + count).
 // Index build (pi3_cloud_index_build), all on the stream, no allocation, no synchronisation:
 //   clear   every slot empty with zero words;
-//   (a)     every point finds or claims the slot of its cell key (64-bit CAS on the key word, as voxel.hip) and adds 1
-//           to the slot's count;
+//   (a)     every point finds or claims the slot of its cell key (slot_claim, as voxel.hip) and adds 1 to the slot's
+//           count;
 //   (b)     every occupied slot claims `count` contiguous rows: an exclusive scan of the counts over the workgroup and
 //           ONE atomic add per workgroup on the cursor (word 4 of slot 0; after the pass it holds the number of rows);
 //   (c)     every point finds its slot again, takes row start + atomicAdd(fill, 1) and writes its 16 bytes.
@@ -37,17 +37,13 @@ namespace {
 
 using namespace voxel_table;
 using wave_block::block_count;
+using wave_block::block_exclusive_scan;
 
 constexpr int kCursorAt = 4;            // word of slot 0 that holds the row cursor
 
 __global__ __launch_bounds__(256) void cloud_clear_kernel(u64* __restrict__ table, long capacity) {
   const long s = (long)blockIdx.x * 256 + threadIdx.x;
-  if (s >= capacity) return;
-  ulonglong2* p = reinterpret_cast<ulonglong2*>(table + 8 * s);
-  p[0] = make_ulonglong2(kEmpty, 0ull);
-  p[1] = make_ulonglong2(0ull, 0ull);
-  p[2] = make_ulonglong2(0ull, 0ull);
-  p[3] = make_ulonglong2(0ull, 0ull);
+  if (s < capacity) slot_reset(table + 8 * s);
 }
 
 // pass (a).  counters[0] += dropped points, counters[2] += points that found no slot within `capacity` probes
@@ -59,22 +55,10 @@ __global__ __launch_bounds__(256) void cloud_count_kernel(u64* __restrict__ tabl
   if (i < n) {
     u64 key;
     if (point_key(points + 3 * i, inv_cell, key)) {
-      lost = true;
-      u64 h = mix64(key) & mask;
-      for (u64 probe = 0; probe <= mask; ++probe) {
-        u64* s = table + 8 * h;
-        u64 cur = __hip_atomic_load(s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (cur == kEmpty) {
-          const u64 old = atomicCAS(s, kEmpty, key);
-          cur = old == kEmpty ? key : old;
-        }
-        if (cur == key) {
-          atomicAdd(s + 1, 1ull);
-          lost = false;
-          break;
-        }
-        h = (h + 1) & mask;
-      }
+      bool fresh;
+      const long h = slot_claim<8>(table, mask, mask, key, fresh);
+      lost = h < 0;
+      if (!lost) atomicAdd(table + 8 * h + 1, 1ull);
     } else {
       dropped = true;
     }
@@ -87,40 +71,29 @@ __global__ __launch_bounds__(256) void cloud_count_kernel(u64* __restrict__ tabl
 // pass (b): one thread per slot.  counters[1] += occupied slots, counters[3] = max(count)
 __global__ __launch_bounds__(256) void cloud_offsets_kernel(u64* __restrict__ table, long capacity,
                                                             u64* __restrict__ counters) {
-  __shared__ u64 wave_tot[4];
   __shared__ u64 wave_max[4];
   __shared__ u64 block_base;
-  const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int tid = (int)threadIdx.x;
   const long s = (long)blockIdx.x * 256 + tid;
   const bool occupied = s < capacity && table[8 * s] != kEmpty;
   const u64 cnt = occupied ? table[8 * s + 1] : 0ull;
-  u64 incl = cnt, big = cnt;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const u64 o = __shfl_up(incl, d, 64);
-    if (lane >= d) incl += o;
-  }
+  u64 big = cnt;
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     const u64 other = __shfl_xor(big, o, 64);
     big = other > big ? other : big;
   }
-  if (lane == 63) wave_tot[wv] = incl;
-  if (lane == 0) wave_max[wv] = big;
-  __syncthreads();
+  if ((tid & 63) == 0) wave_max[tid >> 6] = big;     // read after the scan's __syncthreads()
+  u64 tot;
+  const u64 before = block_exclusive_scan(cnt, tot);
   if (tid == 0) {
-    const u64 tot = wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
     block_base = tot ? atomicAdd(table + kCursorAt, tot) : 0ull;
     u64 m = wave_max[0];
     for (int w = 1; w < 4; ++w) m = wave_max[w] > m ? wave_max[w] : m;
     if (m) atomicMax(counters + 3, m);
   }
   __syncthreads();
-  if (occupied) {
-    u64 at = block_base + incl - cnt;
-    for (int w = 0; w < wv; ++w) at += wave_tot[w];
-    table[8 * s + 2] = at;             // fill (word 3) is still the zero of the clear
-  }
+  if (occupied) table[8 * s + 2] = block_base + before;     // fill (word 3) is still the zero of the clear
   const bool flags[1] = {occupied};
   const int at1[1] = {1};
   block_count<1>(flags, counters, at1);
@@ -180,15 +153,11 @@ __global__ __launch_bounds__(256) void cloud_nearest_kernel(const u64* __restric
       dropped = true;
     } else {
       const double qx = (double)qxf, qy = (double)qyf, qz = (double)qzf;
-      for (int c = 0; c < 27; ++c) {
-        uint32_t cx, cy, cz;
-        if (!(field_offset(kx, c / 9 - 1, cx) && field_offset(ky, (c / 3) % 3 - 1, cy) &&
-              field_offset(kz, c % 3 - 1, cz)))
-          continue;
-        const long h = slot_find(table, mask, pack_key(cx, cy, cz));
-        if (h < 0) continue;
+      for_each_neighbour<1, true>(kx, ky, kz, [&](int, int, int, u64 cell) __attribute__((always_inline)) {
+        const long h = slot_find(table, mask, cell);
+        if (h < 0) return;
         const u64 start = table[8 * h + 2], count = table[8 * h + 1];
-        if (start >= (u64)n || count > (u64)n - start) continue;       // a table this index build did not write
+        if (start >= (u64)n || count > (u64)n - start) return;         // a table this index build did not write
         const uint4* __restrict__ row = cells + start;
         for (u64 j = 0; j < count; ++j) {
           const uint4 p = row[j];
@@ -203,15 +172,14 @@ __global__ __launch_bounds__(256) void cloud_nearest_kernel(const u64* __restric
           }
         }
         evals += count;
-      }
+      });
       matched = best_idx >= 0;
       beyond = !matched;
     }
     d2_out[i] = best;
     idx_out[i] = best_idx;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) evals += __shfl_xor(evals, o, 64);
+  evals = wave_sum_u64(evals);
   if ((threadIdx.x & 63) == 0) wave_evals[threadIdx.x >> 6] = evals;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -223,8 +191,6 @@ __global__ __launch_bounds__(256) void cloud_nearest_kernel(const u64* __restric
   block_count<3>(flags, counters, at);
 }
 
-inline bool positive_finite(double v) { return v > 0.0 && __builtin_isfinite(v); }
-
 }  // namespace
 
 extern "C" int pi3_cloud_index_build(const float* points, long n, float inv_cell, void* table, long capacity,
@@ -235,11 +201,8 @@ extern "C" int pi3_cloud_index_build(const float* points, long n, float inv_cell
                   "inv_cell=%g (finite, > 0), or a null pointer", n, capacity, (double)inv_cell);
     return PI3_ERR_ARG;
   }
+  if (pi3_zero_words("pi3_cloud_index_build", counters, 4, stream) != PI3_OK) return PI3_ERR_LAUNCH;
   hipStream_t st = (hipStream_t)stream;
-  if (hipMemsetAsync(counters, 0, 4 * sizeof(unsigned long long), st) != hipSuccess) {
-    pi3_set_error("pi3_cloud_index_build: hipMemsetAsync failed");
-    return PI3_ERR_LAUNCH;
-  }
   u64* t = (u64*)table;
   const u64 mask = (u64)capacity - 1;
   hipLaunchKernelGGL(cloud_clear_kernel, dim3(blocks_for(capacity)), dim3(256), 0, st, t, capacity);
@@ -265,13 +228,9 @@ extern "C" int pi3_cloud_nearest(const void* table, long capacity, const void* c
                   "for cells of at least 1.112 max_dist), or a null pointer", n, m, capacity, (double)inv_cell, max_dist);
     return PI3_ERR_ARG;
   }
-  hipStream_t st = (hipStream_t)stream;
-  if (hipMemsetAsync(counters, 0, 4 * sizeof(unsigned long long), st) != hipSuccess) {
-    pi3_set_error("pi3_cloud_nearest: hipMemsetAsync failed");
-    return PI3_ERR_LAUNCH;
-  }
+  if (pi3_zero_words("pi3_cloud_nearest", counters, 4, stream) != PI3_OK) return PI3_ERR_LAUNCH;
   if (m > 0)
-    hipLaunchKernelGGL(cloud_nearest_kernel, dim3(blocks_for(m)), dim3(256), 0, st, (const u64*)table,
+    hipLaunchKernelGGL(cloud_nearest_kernel, dim3(blocks_for(m)), dim3(256), 0, (hipStream_t)stream, (const u64*)table,
                        (u64)capacity - 1, (const uint4*)cells, n, inv_cell, queries, m, max_dist * max_dist, d2, idx,
                        (u64*)counters);
   return pi3_check_launch("cloud_nearest");

@@ -27,6 +27,11 @@ enum {
 
 void pi3_set_error(const char* fmt, ...);
 int pi3_check_launch(const char* what);
+// An entry point zeroes its own counters: n 64-bit words at ptr, on the stream.  PI3_OK, or PI3_ERR_LAUNCH with
+// "<who>: hipMemsetAsync failed" in pi3_last_error().
+int pi3_zero_words(const char* who, void* ptr, long n, void* stream);
+// the argument test of a scale, a size or a tolerance: finite and > 0 (false for NaN)
+inline bool positive_finite(double v) { return v > 0.0 && __builtin_isfinite(v); }
 // Opt `kern` into `bytes` of dynamic LDS (above the 64 KB default) on the CURRENT device, once per device: the attribute
 // is per device, so `done_mask` (one function-local static per kernel instance) carries one bit per device ordinal.
 // Returns PI3_OK or PI3_ERR_LAUNCH with the runtime's message in pi3_last_error().
@@ -108,6 +113,11 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 __device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;

@@ -171,16 +171,13 @@ extern "C" int pi3_dense_consistency(const float* points, const float* local_poi
   const long n = (long)N * H * W;
   if (!points || !local_points || !poses || !fxfycxcy || !zplane || !out_mask || !stats || N < 0 || H <= 0 ||
       W <= 0 || n > 0x7fffffffL || radius < 1 || radius > 16 || stride < 1 || min_views < 1 ||
-      min_views > 2 * radius || !(rel_tol > 0.0f) || !__builtin_isfinite(rel_tol)) {
+      min_views > 2 * radius || !positive_finite(rel_tol)) {
     pi3_set_error("pi3_dense_consistency: bad arguments N=%d H=%d W=%d radius=%d (1..16) stride=%d (>= 1) "
                   "min_views=%d (1..2 radius) rel_tol=%g (finite, > 0), or a null pointer",
                   N, H, W, radius, stride, min_views, (double)rel_tol);
     return PI3_ERR_ARG;
   }
-  if (hipMemsetAsync(stats, 0, 2 * sizeof(unsigned long long), (hipStream_t)stream) != hipSuccess) {
-    pi3_set_error("pi3_dense_consistency: hipMemsetAsync failed");
-    return PI3_ERR_LAUNCH;
-  }
+  if (pi3_zero_words("pi3_dense_consistency", stats, 2, stream) != PI3_OK) return PI3_ERR_LAUNCH;
   if (N == 0) return PI3_OK;
   const unsigned nb = (unsigned)((n + 255) / 256);
   hipLaunchKernelGGL(dense_candidates_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, points, local_points, conf,
@@ -201,10 +198,7 @@ extern "C" int pi3_dense_depth_planes(const float* points, const float* local_po
                   "a null pointer", N, H, W, every, pixel_stride);
     return PI3_ERR_ARG;
   }
-  if (hipMemsetAsync(count, 0, sizeof(unsigned long long), (hipStream_t)stream) != hipSuccess) {
-    pi3_set_error("pi3_dense_depth_planes: hipMemsetAsync failed");
-    return PI3_ERR_LAUNCH;
-  }
+  if (pi3_zero_words("pi3_dense_depth_planes", count, 1, stream) != PI3_OK) return PI3_ERR_LAUNCH;
   if (N == 0) return PI3_OK;
   const int Nk = (int)(((long)N + every - 1) / every);
   const int Hp = (H + pixel_stride - 1) / pixel_stride, Wp = (W + pixel_stride - 1) / pixel_stride;

@@ -106,7 +106,7 @@ __global__ __launch_bounds__(256) void render_splat_kernel(
     }
   }
 #ifdef PI3_DEV_VARIANTS
-  for (int o = 32; o > 0; o >>= 1) issued += __shfl_xor(issued, o, 64);
+  issued = wave_sum_u64(issued);
   if (lane == 0 && issued) atomicAdd(stats + 3, issued);
 #else
   (void)issued;
@@ -155,8 +155,7 @@ extern "C" int pi3_render_splat(const float* points, const int* weights, long V,
                                 double voxel_size, double splat_scale, int min_weight, double near, double far,
                                 unsigned long long* zbuf, unsigned long long* stats, void* stream) {
   if ((V > 0 && !points) || V < 0 || V >= (1L << 31) || !cams || !zbuf || !stats || M <= 0 || M > 65535 || H <= 0 ||
-      W <= 0 || !(voxel_size > 0.0) || !__builtin_isfinite(voxel_size) || !(splat_scale > 0.0) ||
-      !__builtin_isfinite(splat_scale) || !(near >= 0.0) || far != far) {
+      W <= 0 || !positive_finite(voxel_size) || !positive_finite(splat_scale) || !(near >= 0.0) || far != far) {
     pi3_set_error("pi3_render_splat: bad arguments V=%ld M=%d H=%d W=%d voxel_size=%g splat_scale=%g near=%g far=%g", V,
                   M, H, W, voxel_size, splat_scale, near, far);
     return PI3_ERR_ARG;

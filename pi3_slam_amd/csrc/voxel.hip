@@ -20,34 +20,26 @@
 
 namespace {
 
-using namespace voxel_table;      // u64, kEmpty, kBias, mix64, pack_key, quantise, claim_rows, pow2, blocks_for
+using namespace voxel_table;      // u64, kEmpty, pack_key, quantise, slot_claim, slot_reset, slot_centre, slot_colour,
+                                  // claim_rows, kExtractPer, pow2, blocks_for
 using wave_block::block_sum;
 using wave_block::wave_merge_runs;
 
 // add (w, U, C) to the slot of `key`; false when no slot was found within `capacity` probes
 __device__ __forceinline__ bool slot_add(u64* __restrict__ table, u64 mask, u64 key, u64 w, u64 u0, u64 u1, u64 u2,
                                          u64 c0, u64 c1, u64 c2) {
-  u64 h = mix64(key) & mask;
-  for (u64 probe = 0; probe <= mask; ++probe) {
-    u64* s = table + 8 * h;
-    u64 cur = __hip_atomic_load(s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (cur == kEmpty) {
-      const u64 old = atomicCAS(s, kEmpty, key);
-      cur = old == kEmpty ? key : old;
-    }
-    if (cur == key) {
-      atomicAdd(s + 1, w);
-      if (u0) atomicAdd(s + 2, u0);
-      if (u1) atomicAdd(s + 3, u1);
-      if (u2) atomicAdd(s + 4, u2);
-      if (c0) atomicAdd(s + 5, c0);
-      if (c1) atomicAdd(s + 6, c1);
-      if (c2) atomicAdd(s + 7, c2);
-      return true;
-    }
-    h = (h + 1) & mask;
-  }
-  return false;
+  bool fresh;
+  const long h = slot_claim<8>(table, mask, mask, key, fresh);
+  if (h < 0) return false;
+  u64* s = table + 8 * h;
+  atomicAdd(s + 1, w);
+  if (u0) atomicAdd(s + 2, u0);
+  if (u1) atomicAdd(s + 3, u1);
+  if (u2) atomicAdd(s + 4, u2);
+  if (c0) atomicAdd(s + 5, c0);
+  if (c1) atomicAdd(s + 6, c1);
+  if (c2) atomicAdd(s + 7, c2);
+  return true;
 }
 
 // Every lane of the wave calls this (invalid lanes with valid = false).  v = w, U0 U1 U2, C0 C1 C2 of this lane's
@@ -72,13 +64,7 @@ __device__ __forceinline__ uint32_t colour_u8(float c) {
 __global__ __launch_bounds__(256) void voxel_clear_kernel(u64* __restrict__ table, long capacity,
                                                           u64* __restrict__ stats) {
   const long stride = (long)gridDim.x * 256;
-  for (long s = (long)blockIdx.x * 256 + threadIdx.x; s < capacity; s += stride) {
-    ulonglong2* p = reinterpret_cast<ulonglong2*>(table + 8 * s);
-    p[0] = make_ulonglong2(kEmpty, 0ull);
-    p[1] = make_ulonglong2(0ull, 0ull);
-    p[2] = make_ulonglong2(0ull, 0ull);
-    p[3] = make_ulonglong2(0ull, 0ull);
-  }
+  for (long s = (long)blockIdx.x * 256 + threadIdx.x; s < capacity; s += stride) slot_reset(table + 8 * s);
   if (stats && blockIdx.x == 0 && threadIdx.x < 4) stats[threadIdx.x] = 0ull;
 }
 
@@ -171,16 +157,13 @@ __global__ __launch_bounds__(256) void voxel_extract_kernel(const u64* __restric
       continue;
     }
     const u64* q = table + 8 * (s0 + 256L * j);
-    const u64 key = q[0], W = q[1];
-    const double den = (double)W * 16777216.0;
+    const u64 W = q[1];
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-      const int k = (int)((key >> (42 - 21 * a)) & 0x1FFFFFull) - kBias;
-      const double frac = (double)q[2 + a] / den;
-      points[3 * at + a] = (float)(vsize * ((double)k + frac));
-      colors[3 * at + a] = (unsigned char)((q[5 + a] + W / 2) / W);
+      points[3 * at + a] = (float)(vsize * slot_centre(q, a));
+      colors[3 * at + a] = (unsigned char)slot_colour(q, a);
     }
-    keys[at] = key;
+    keys[at] = q[0];
     weights[at] = W > 0x7FFFFFFFull ? 0x7FFFFFFF : (int)W;     // saturated (the centroid and colour use the full W)
     ++at;
   }
@@ -206,7 +189,7 @@ extern "C" int pi3_voxel_fuse_pixels(void* table, long capacity, const float* po
                                      float conf_logit_thr, float inv_voxel, unsigned long long* stats, void* stream) {
   const long n = (long)N * H * W;
   if (!table || !pow2(capacity) || (n > 0 && !points) || !stats || N < 0 || H <= 0 || W <= 0 || capacity < 2 * n ||
-      !(inv_voxel > 0.0f) || !__builtin_isfinite(inv_voxel)) {
+      !positive_finite(inv_voxel)) {
     pi3_set_error("pi3_voxel_fuse_pixels: bad arguments N=%d H=%d W=%d capacity=%ld inv_voxel=%g", N, H, W, capacity,
                   (double)inv_voxel);
     return PI3_ERR_ARG;
@@ -222,7 +205,7 @@ extern "C" int pi3_voxel_fuse_points(void* table, long capacity, const float* po
                                      const int* weights, long n, float inv_voxel, unsigned long long* stats,
                                      void* stream) {
   if (!table || !pow2(capacity) || (n > 0 && !points) || !stats || n < 0 || capacity < 2 * n ||
-      !(inv_voxel > 0.0f) || !__builtin_isfinite(inv_voxel)) {
+      !positive_finite(inv_voxel)) {
     pi3_set_error("pi3_voxel_fuse_points: bad arguments n=%ld capacity=%ld inv_voxel=%g", n, capacity,
                   (double)inv_voxel);
     return PI3_ERR_ARG;
@@ -251,14 +234,11 @@ int extract_launch(const char* what, const void* table, long capacity, const uns
                    double voxel_size, unsigned long long* keys, float* points, unsigned char* colors, int* weights,
                    long max_out, unsigned long long* stats, void* stream) {
   if (!table || !pow2(capacity) || (masked && !keep) || !keys || !points || !colors || !weights || !stats ||
-      max_out < 0 || !(voxel_size > 0.0) || !__builtin_isfinite(voxel_size)) {
+      max_out < 0 || !positive_finite(voxel_size)) {
     pi3_set_error("%s: bad arguments capacity=%ld max_out=%ld", what, capacity, max_out);
     return PI3_ERR_ARG;
   }
-  if (hipMemsetAsync(stats + 2, 0, 2 * sizeof(unsigned long long), (hipStream_t)stream) != hipSuccess) {
-    pi3_set_error("%s: hipMemsetAsync failed", what);
-    return PI3_ERR_LAUNCH;
-  }
+  if (pi3_zero_words(what, stats + 2, 2, stream) != PI3_OK) return PI3_ERR_LAUNCH;
   const long span = 256L * kExtractPer;
   const dim3 grid((unsigned)((capacity + span - 1) / span));
   if (masked)

@@ -48,17 +48,11 @@ __global__ __launch_bounds__(256) void voxel_carve_kernel(
   double x = 0.0, y = 0.0, z = 0.0;
   if (s < capacity) {
     const u64* q = table + 8 * s;
-    const u64 key = q[0];
-    occupied = key != kEmpty;
+    occupied = q[0] != kEmpty;
     if (occupied) {
-      const double den = (double)q[1] * 16777216.0;
-      double c[3];
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        const int k = (int)key_field(key, a) - kBias;
-        c[a] = (double)(float)(vsize * ((double)k + (double)q[2 + a] / den));
-      }
-      x = c[0], y = c[1], z = c[2];
+      x = (double)(float)(vsize * slot_centre(q, 0));
+      y = (double)(float)(vsize * slot_centre(q, 1));
+      z = (double)(float)(vsize * slot_centre(q, 2));
     }
   }
   unsigned agree = 0, conflict = 0;
@@ -103,18 +97,14 @@ extern "C" int pi3_voxel_carve(const void* table, long capacity, double voxel_si
                                double margin, int min_conflicts, unsigned char* carved, unsigned* agree,
                                unsigned* conflict, unsigned long long* counters, void* stream) {
   if (!table || !pow2(capacity) || !carved || !counters || M < 0 || (M > 0 && (!views || !planes)) || Hp <= 0 ||
-      Wp <= 0 || (pixel_stride != 1 && pixel_stride != 2 && pixel_stride != 4) || !(voxel_size > 0.0) ||
-      !__builtin_isfinite(voxel_size) || !(rel_tol > 0.0) || !__builtin_isfinite(rel_tol) || !(margin >= 0.0) ||
-      !__builtin_isfinite(margin) || min_conflicts < 1) {
+      Wp <= 0 || (pixel_stride != 1 && pixel_stride != 2 && pixel_stride != 4) || !positive_finite(voxel_size) ||
+      !positive_finite(rel_tol) || !(margin >= 0.0) || !__builtin_isfinite(margin) || min_conflicts < 1) {
     pi3_set_error("pi3_voxel_carve: bad arguments capacity=%ld M=%d Hp=%d Wp=%d pixel_stride=%d (1, 2 or 4) "
                   "voxel_size=%g rel_tol=%g (finite, > 0) margin=%g (finite, >= 0) min_conflicts=%d (>= 1), or a null "
                   "pointer", capacity, M, Hp, Wp, pixel_stride, voxel_size, rel_tol, margin, min_conflicts);
     return PI3_ERR_ARG;
   }
-  if (hipMemsetAsync(counters, 0, 4 * sizeof(unsigned long long), (hipStream_t)stream) != hipSuccess) {
-    pi3_set_error("pi3_voxel_carve: hipMemsetAsync failed");
-    return PI3_ERR_LAUNCH;
-  }
+  if (pi3_zero_words("pi3_voxel_carve", counters, 4, stream) != PI3_OK) return PI3_ERR_LAUNCH;
   hipLaunchKernelGGL(voxel_carve_kernel, dim3(blocks_for(capacity)), dim3(256), 0, (hipStream_t)stream,
                      (const u64*)table, capacity, voxel_size, views, M, (const _Float16*)planes, Hp, Wp,
                      1.0 / (double)pixel_stride, rel_tol, margin, (unsigned)min_conflicts, carved, agree, conflict,

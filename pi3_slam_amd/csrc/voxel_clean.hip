@@ -73,20 +73,12 @@ __global__ __launch_bounds__(256) void voxel_support_kernel(const u64* __restric
     eligible = occupied && !excluded && table[8 * s + 1] >= min_weight;
     int n = -1;
     if (eligible && probe) {
-      const uint32_t kx = key_field(key, 0), ky = key_field(key, 1), kz = key_field(key, 2);
       n = 0;
-      for (int dx = -kRadius; dx <= kRadius; ++dx) {
-        uint32_t nx, ny, nz;
-        if (!field_offset(kx, dx, nx)) continue;
-        for (int dy = -kRadius; dy <= kRadius; ++dy) {
-          if (!field_offset(ky, dy, ny)) continue;
-          for (int dz = -kRadius; dz <= kRadius; ++dz) {
-            if ((dx | dy | dz) == 0 || !field_offset(kz, dz, nz)) continue;
-            const long t = slot_find(table, mask, pack_key(nx, ny, nz));
-            if (t >= 0 && table[8 * t + 1] >= min_weight && (!kExcl || !exclude[t])) ++n;
-          }
-        }
-      }
+      for_each_neighbour<kRadius, false>(key_field(key, 0), key_field(key, 1), key_field(key, 2),
+                                         [&](int, int, int, u64 other) __attribute__((always_inline)) {
+        const long t = slot_find(table, mask, other);
+        if (t >= 0 && table[8 * t + 1] >= min_weight && (!kExcl || !exclude[t])) ++n;
+      });
     }
     kept = eligible && (!probe || n >= min_support);
     keep[s] = kept ? 1 : 0;
@@ -120,22 +112,14 @@ __global__ __launch_bounds__(256) void voxel_label_sweep_kernel(const u64* __res
   const u64 own = s < capacity ? load_relaxed(label + s) : kEmpty;
   if (own != kEmpty) {                                   // a survivor (empty and dropped slots carry all ones)
     const u64 key = table[8 * s];
-    const uint32_t kx = key_field(key, 0), ky = key_field(key, 1), kz = key_field(key, 2);
     u64 m = own;
-    for (int dx = -1; dx <= 1; ++dx) {
-      uint32_t nx, ny, nz;
-      if (!field_offset(kx, dx, nx)) continue;
-      for (int dy = -1; dy <= 1; ++dy) {
-        if (!field_offset(ky, dy, ny)) continue;
-        for (int dz = -1; dz <= 1; ++dz) {
-          if ((dx | dy | dz) == 0 || !field_offset(kz, dz, nz)) continue;
-          const long t = slot_find(table, mask, pack_key(nx, ny, nz));
-          if (t < 0) continue;
-          const u64 l = load_relaxed(label + t);
-          m = l < m ? l : m;
-        }
-      }
-    }
+    for_each_neighbour<1, false>(key_field(key, 0), key_field(key, 1), key_field(key, 2),
+                                 [&](int, int, int, u64 other) __attribute__((always_inline)) {
+      const long t = slot_find(table, mask, other);
+      if (t < 0) return;
+      const u64 l = load_relaxed(label + t);
+      m = l < m ? l : m;
+    });
     for (int hop = 0; hop < kHops; ++hop) {              // m names a voxel of this component: follow its label
       const long r = slot_find(table, mask, m);
       if (r < 0) break;
@@ -246,10 +230,7 @@ int support_launch(const char* what, const void* table, long capacity, unsigned 
     pi3_set_error("%s: bad arguments capacity=%ld radius=%d min_support=%d", what, capacity, radius, min_support);
     return PI3_ERR_ARG;
   }
-  if (hipMemsetAsync(counters, 0, 8 * sizeof(unsigned long long), (hipStream_t)stream) != hipSuccess) {
-    pi3_set_error("%s: hipMemsetAsync failed", what);
-    return PI3_ERR_LAUNCH;
-  }
+  if (pi3_zero_words(what, counters, 8, stream) != PI3_OK) return PI3_ERR_LAUNCH;
   const bool probe = min_support > 0 || support != nullptr;
   if (radius == 1)
     hipLaunchKernelGGL((voxel_support_kernel<1, kExcl>), dim3(blocks_for(capacity)), dim3(256), 0, (hipStream_t)stream,
@@ -323,10 +304,7 @@ extern "C" int pi3_voxel_component_filter(const void* table, long capacity, cons
     pi3_set_error("pi3_voxel_component_filter: bad arguments capacity=%ld min_component=%ld", capacity, min_component);
     return PI3_ERR_ARG;
   }
-  if (hipMemsetAsync(counters + 3, 0, 3 * sizeof(unsigned long long), (hipStream_t)stream) != hipSuccess) {
-    pi3_set_error("pi3_voxel_component_filter: hipMemsetAsync failed");
-    return PI3_ERR_LAUNCH;
-  }
+  if (pi3_zero_words("pi3_voxel_component_filter", counters + 3, 3, stream) != PI3_OK) return PI3_ERR_LAUNCH;
   hipLaunchKernelGGL(voxel_component_filter_kernel, dim3(blocks_for(capacity)), dim3(256), 0, (hipStream_t)stream,
                      (const u64*)table, capacity, (const u64*)label, size, (unsigned)min_component, keep,
                      (u64*)counters);

@@ -72,8 +72,7 @@ __device__ __forceinline__ void wave_add_normals(const u64* __restrict__ table, 
       atomicAdd(q + 3, v[3]);
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) lost += __shfl_xor(lost, o, 64);
+  lost = wave_sum_u64(lost);
   const u64 nc = __ballot(contributes), ns = __ballot(skipped), nd = __ballot(degenerate);
   if ((threadIdx.x & 63) == 0) {
     if (nc) atomicAdd(stats + 0, (u64)__popcll(nc));
@@ -269,7 +268,7 @@ extern "C" int pi3_voxel_fuse_pixel_normals(const void* table, long capacity, lo
                                             void* stream) {
   const long n = (long)N * H * W;
   if (!table || !pow2(capacity) || !nacc || (n > 0 && !points) || !stats || N < 0 || H <= 0 || W <= 0 ||
-      capacity < 2 * n || !(inv_voxel > 0.0f) || !__builtin_isfinite(inv_voxel)) {
+      capacity < 2 * n || !positive_finite(inv_voxel)) {
     pi3_set_error("pi3_voxel_fuse_pixel_normals: bad arguments N=%d H=%d W=%d capacity=%ld inv_voxel=%g", N, H, W,
                   capacity, (double)inv_voxel);
     return PI3_ERR_ARG;
@@ -285,7 +284,7 @@ extern "C" int pi3_voxel_fuse_point_normals(const void* table, long capacity, lo
                                             const float* normals, const int* nweights, const double* rot9, long n,
                                             float inv_voxel, unsigned long long* stats, void* stream) {
   if (!table || !pow2(capacity) || !nacc || (n > 0 && (!points || !normals || !nweights)) || !rot9 || !stats || n < 0 ||
-      capacity < 2 * n || !(inv_voxel > 0.0f) || !__builtin_isfinite(inv_voxel)) {
+      capacity < 2 * n || !positive_finite(inv_voxel)) {
     pi3_set_error("pi3_voxel_fuse_point_normals: bad arguments n=%ld capacity=%ld inv_voxel=%g", n, capacity,
                   (double)inv_voxel);
     return PI3_ERR_ARG;
@@ -304,10 +303,7 @@ extern "C" int pi3_voxel_extract_normals(const void* table, long capacity, const
     pi3_set_error("pi3_voxel_extract_normals: bad arguments capacity=%ld max_out=%ld", capacity, max_out);
     return PI3_ERR_ARG;
   }
-  if (hipMemsetAsync(stats, 0, 4 * sizeof(unsigned long long), (hipStream_t)stream) != hipSuccess) {
-    pi3_set_error("pi3_voxel_extract_normals: hipMemsetAsync failed");
-    return PI3_ERR_LAUNCH;
-  }
+  if (pi3_zero_words("pi3_voxel_extract_normals", stats, 4, stream) != PI3_OK) return PI3_ERR_LAUNCH;
   const long span = 256L * kExtractPer;
   const dim3 grid((unsigned)((capacity + span - 1) / span));
   if (keep_or_null)

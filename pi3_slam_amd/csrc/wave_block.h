@@ -1,5 +1,6 @@
-// Wave (64 lanes) and workgroup (256 threads = 4 waves) helpers shared by the voxel and render kernels: the merge of
-// runs of equal keys over a wave, and the per-workgroup counters.  Nothing here knows a table or an image.
+// Wave (64 lanes) and workgroup (256 threads = 4 waves) helpers shared by the voxel, cloud and render kernels: the merge
+// of runs of equal keys over a wave, the per-workgroup counters and the workgroup's exclusive scan.  Nothing here knows
+// a table or an image.
 //
 // Counters: a count is summed per workgroup in LDS and costs ONE global atomic per workgroup and counter (a per-wave
 // atomic on one address once serialised voxel_extract at ~700 k voxels).  block_count and block_sum keep their LDS
@@ -41,6 +42,28 @@ __device__ __forceinline__ void block_sum(unsigned n, u64* __restrict__ counter)
     const unsigned tot = wave_n[0] + wave_n[1] + wave_n[2] + wave_n[3];
     if (tot) atomicAdd(counter, (u64)tot);
   }
+}
+
+// The workgroup-exclusive prefix of cnt in thread order (the sum over the threads before this one), and in `total` the
+// workgroup's sum, the same in every thread: what a kernel needs to hand each thread its rows after ONE atomic per
+// workgroup on the row counter (that atomic, by thread 0 and only when total != 0, stays with the caller).  The same
+// LDS contract as block_count and block_sum: the per-wave totals are read after the one __syncthreads() inside, so a
+// kernel that calls this twice puts a __syncthreads() between the calls.  Every thread of the workgroup calls this.
+__device__ __forceinline__ u64 block_exclusive_scan(u64 cnt, u64& total) {
+  __shared__ u64 wave_tot[4];
+  const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  u64 incl = cnt;                                  // inclusive prefix over the wave
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const u64 o = __shfl_up(incl, d, 64);
+    if (lane >= d) incl += o;
+  }
+  if (lane == 63) wave_tot[wv] = incl;
+  __syncthreads();
+  u64 before = incl - cnt;
+  for (int w = 0; w < wv; ++w) before += wave_tot[w];
+  total = wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
+  return before;
 }
 
 // Contention scheme of the fusion kernels: a wave's 64 lanes hold 64 consecutive candidates (for the pixel forms: 64

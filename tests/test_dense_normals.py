@@ -281,12 +281,20 @@ def test_entry_points_are_declared_bound_and_check_their_arguments(built_lib):
 
 def test_makefile_compiles_the_normals_without_contraction():
     from conftest import ROOT
-    mk = open(os.path.join(ROOT, "pi3_slam_amd", "csrc", "Makefile")).read()
+    import subprocess
+    csrc = os.path.join(ROOT, "pi3_slam_amd", "csrc")
+    mk = open(os.path.join(csrc, "Makefile")).read()
     assert "voxel_normals.hip" in mk.split("SRCS =")[1].split("\n")[0]
     rule = [blk for blk in mk.replace("\\\n", " ").split("\n") if "-ffp-contract=off" in blk and not blk.startswith("#")]
     assert len(rule) == 1
-    for d in ("build", "build_asan", "build_dev"):
-        assert f"{d}/voxel_normals.o" in rule[0] and f"{d}/dense_filter.o" in rule[0]
+    # what make itself would run (a dry run: nothing is compiled): the object of every build, =off after =fast
+    objs = [f"{d}/{s}.o" for d in ("build", "build_asan", "build_dev") for s in ("voxel_normals", "dense_filter")]
+    said = subprocess.run(["make", "-C", csrc, "-n", "-B"] + objs, check=True, capture_output=True, text=True).stdout
+    for o in objs:
+        cmd = [ln for ln in said.split("\n") if ln.rstrip().endswith(f"-o {o}")]
+        assert len(cmd) == 1 and cmd[0].rfind("-ffp-contract=off") > cmd[0].rfind("-ffp-contract=fast") >= 0, (o, cmd)
+    plain = subprocess.run(["make", "-C", csrc, "-n", "-B", "build/voxel.o"], check=True, capture_output=True, text=True)
+    assert "-ffp-contract=off" not in plain.stdout and "-ffp-contract=fast" in plain.stdout
 
 
 def test_option_in_config_cli_and_online_signature(capsys):

@@ -198,6 +198,50 @@ def test_tiny_table_where_probing_wraps():
     assert bs["cells"] == 4 and exp["idx"][:8].tolist() == [0, 1, 2, 3] * 2 and qs["matched"] >= 8
 
 
+def test_a_table_without_a_free_slot():
+    """Nine cells into a table of eight slots: the arm of the shared slot claim (voxel_table.h, slot_claim) that gives
+    up after `capacity` probes, and the lookups of a table that has no empty slot to stop at.  The fusion entry points
+    refuse capacity < 2 n, so only the cloud index gets there.  Which point loses its slot depends on scheduling;
+    nothing asserted here does."""
+    from pi3_slam_amd import ops
+    md, cap, sentinel = 0.05, 8, -7
+    inv = ops.cloud_inv_cell(md)
+    p = np.array([[(3 * j + 0.5) / inv, 3.5 / inv, 5.5 / inv] for j in range(9)], np.float32)   # 3 cells apart on x
+    ok, keys, _ = mref.quantise(p, inv)
+    assert ok.all() and np.diff(np.sort(keys >> np.uint64(42)).astype(np.int64)).min() >= 3
+    pts = torch.from_numpy(p).to(DEV)
+    seen = []
+    for _ in range(2):
+        table = torch.full((cap * 8,), 5, dtype=torch.int64, device=DEV)
+        cells = torch.full((9, 4), sentinel, dtype=torch.int32, device=DEV)
+        built = torch.full((4,), 11, dtype=torch.int64, device=DEV)
+        ops.cloud_index_build(pts, inv, table, cells, built)
+        d2 = torch.full((9,), 5.0, dtype=torch.float64, device=DEV)
+        idx = torch.full((9,), 5, dtype=torch.int32, device=DEV)
+        asked = torch.full((4,), 11, dtype=torch.int64, device=DEV)
+        ops.cloud_nearest(table, cells, inv, pts, md, d2, idx, asked)
+        torch.cuda.synchronize()
+        bs = dict(zip(ops.CLOUD_INDEX_COUNTERS, built.tolist()))
+        assert bs == dict(dropped=0, cells=8, no_slot=1, largest_cell=1)
+        t = table.cpu().numpy().view(np.uint64).reshape(cap, 8)
+        assert (t[:, 0] != EMPTY).all() and int(t[0, 4]) == 8                          # full; the cursor: 8 rows
+        assert (t[:, 1] == 1).all() and (t[:, 3] == 1).all() and sorted(t[:, 2].tolist()) == list(range(8))
+        rows = cells.cpu().numpy()
+        orig = rows[:8, 3]
+        assert sorted(set(orig.tolist())) == sorted(orig.tolist()) and set(orig.tolist()) < set(range(9))
+        assert rows[:8, :3].tobytes() == p[orig].tobytes() and (rows[8] == sentinel).all()
+        assert set(keys[orig].tolist()) == set(t[:, 0].tolist())
+        lost = (set(range(9)) - set(orig.tolist())).pop()
+        got_d2, got_idx = d2.cpu().numpy(), idx.cpu().numpy()
+        exp_d2, exp_idx = np.zeros(9), np.arange(9, dtype=np.int32)
+        exp_d2[lost], exp_idx[lost] = np.inf, -1
+        assert got_d2.tobytes() == exp_d2.tobytes() and np.array_equal(got_idx, exp_idx)
+        qs = dict(zip(ops.CLOUD_NEAREST_COUNTERS, asked.tolist()))
+        assert {k: qs[k] for k in ("matched", "beyond", "dropped")} == dict(matched=8, beyond=1, dropped=0)
+        seen.append((bs, qs))
+    assert seen[0] == seen[1]
+
+
 # ------------------------------------------------------------------------------------------------ e. large coordinates
 def test_large_coordinates():
     rng = np.random.default_rng(1000 * 5000 + 5000)

@@ -16,6 +16,7 @@ from __future__ import annotations
 import argparse
 import glob
 import os
+import re
 from typing import Dict, List, Optional, Sequence, Tuple
 
 # (flag, kwargs) - names, types and defaults follow the reference scripts; REQ marks what has a personal default path there
@@ -37,6 +38,16 @@ CREATE_FLAGS: Sequence[Tuple[str, Dict]] = (
     # this build's additions
     ("--moge-model-path", dict(default=None, help="local MoGe-2 model.pt; 'recipe' = synthetic weights")),
     ("--keypoint-seed", dict(type=int, default=0, help="seed of the grid subsampling, -1 = unseeded")),
+)
+CREATE_SWITCHES = (("--device-resize", "Resize + ToTensor on the GPU (loader workers decode only)"),
+                   ("--hip-graph", "replay the per-chunk forward as one captured hipGraph"),
+                   ("--reuse-overlap-encoder", "overlap frames take their encoder output from the previous chunk "
+                                               "(bit-identical; single-GPU streams)"))
+# The dense map's flags, declared once, spelled with hyphens.  The chunk stage (dense_map.ChunkCloudBuilder) belongs to
+# `create`, the map stage (dense_map.fuse_chunks: MapCarver, MapCleaner, MapMesher) to `reconstruct`; `online` runs both
+# and takes both tables through underscored().
+SWITCH = dict(action="store_true")
+DENSE_CHUNK_FLAGS: Sequence[Tuple[str, Dict]] = (
     ("--dense-voxel-size", dict(type=float, default=None, help="also fuse each chunk's dense pointmap into voxels of this "
                                                                "edge length (metres): chunk['dense_cloud']")),
     ("--dense-conf-threshold", dict(type=float, default=0.5, help="pixels with sigmoid(conf) above this enter the dense map")),
@@ -45,19 +56,58 @@ CREATE_FLAGS: Sequence[Tuple[str, Dict]] = (
     ("--dense-view-radius", dict(type=int, default=3, help="neighbours i +- s * stride, s = 1..radius (1..16)")),
     ("--dense-view-stride", dict(type=int, default=2, help="frame step between the neighbours")),
     ("--dense-depth-tolerance", dict(type=float, default=0.03, help="relative depth difference that still agrees")),
-    ("--dense-depth-every", dict(type=int, default=None, help="with --dense-voxel-size: keep the depth of every K-th frame "
-                                                              "in the chunk file (chunk['dense_depth'], fp16) so that "
-                                                              "`reconstruct --dense-carve-min-conflicts` can carve the "
-                                                              "fused map with the views of every chunk")),
+    ("--dense-depth-every", dict(type=int, default=None, help="with --dense-voxel-size: every chunk keeps the depth of "
+                                                              "every K-th frame (chunk['dense_depth'], fp16) so that "
+                                                              "--dense-carve-min-conflicts can carve the fused map with "
+                                                              "the views of every chunk")),
     ("--dense-depth-stride", dict(type=int, default=2, choices=(1, 2, 4), help="those depth planes keep every S-th row "
                                                                                "and column")),
+    ("--dense-normals", dict(SWITCH, help="with --dense-voxel-size: every voxel of the dense cloud also gets a surface "
+                                          "normal facing the cameras that saw it (dense_points.ply with nx ny nz, "
+                                          "normal / shaded images under renders/)")),
 )
-CREATE_SWITCHES = (("--device-resize", "Resize + ToTensor on the GPU (loader workers decode only)"),
-                   ("--hip-graph", "replay the per-chunk forward as one captured hipGraph"),
-                   ("--reuse-overlap-encoder", "overlap frames take their encoder output from the previous chunk "
-                                               "(bit-identical; single-GPU streams)"),
-                   ("--dense-normals", "with --dense-voxel-size: every voxel of the dense cloud also gets a surface normal "
-                                       "facing the cameras that saw it (dense_points.ply with nx ny nz, shaded renders)"))
+DENSE_MAP_FLAGS: Sequence[Tuple[str, Dict]] = (
+    ("--dense-min-weight", dict(type=int, default=None, help="dense map: drop voxels whose fused weight is below N "
+                                                             "(from dense_points.ply and the renders; e.g. 2 as a "
+                                                             "starting point, not a measured optimum)")),
+    ("--dense-min-support", dict(type=int, default=None, help="dense map: drop voxels with fewer than N occupied cells "
+                                                              "among their neighbours (26 at radius 1; e.g. 4 as a "
+                                                              "starting point, not a measured optimum)")),
+    ("--dense-support-radius", dict(type=int, default=1, choices=(1, 2), help="neighbourhood of --dense-min-support "
+                                                                               "in voxels: 26 or 124 cells")),
+    ("--dense-min-component", dict(type=int, default=None, help="dense map: then drop 26-connected components of fewer "
+                                                                "than N voxels (e.g. 50 as a starting point, not a "
+                                                                "measured optimum)")),
+    ("--dense-carve-min-conflicts", dict(type=int, default=None, help="dense map: first drop the voxels that at least N "
+                                                                      "depth keyframes of any chunk looked through, "
+                                                                      "and more than agree with them (needs chunks "
+                                                                      "created with --dense-depth-every; use with "
+                                                                      "--no-bundle-adjust; e.g. 3 as a starting point, "
+                                                                      "not a measured optimum)")),
+    ("--dense-carve-tolerance", dict(type=float, default=0.03, help="relative depth difference (plus one voxel size) "
+                                                                    "within which a keyframe agrees with a voxel")),
+    ("--dense-mesh", dict(SWITCH, help="write dense_mesh.ply: a triangle mesh of the fused dense map (surface nets on its "
+                                       "voxel lattice; the chunks must have been created with --dense-voxel-size and "
+                                       "--dense-normals)")),
+)
+
+
+def option_names(table: Sequence[Tuple[str, Dict]]) -> Tuple[str, ...]:
+    """The attributes a flag table's arguments parse into: --dense-min-views or --dense_min_views -> dense_min_views."""
+    return tuple(flag[2:].replace("-", "_") for flag, _ in table)
+
+
+def underscored(table: Sequence[Tuple[str, Dict]]) -> Tuple[Tuple[str, Dict], ...]:
+    """A flag table in `online`'s spelling: --dense-min-views -> --dense_min_views, in the flags themselves and wherever
+    a help text names one."""
+    def respell(flag: str) -> str:
+        return "--" + flag[2:].replace("-", "_")
+
+    def respell_text(text: str) -> str:
+        return re.sub(r"--[a-z]+(?:-[a-z]+)+", lambda m: respell(m.group(0)), text)
+    return tuple((respell(flag), dict(kw, help=respell_text(kw["help"]))) for flag, kw in table)
+
+
 RECON_FLAGS: Sequence[Tuple[str, Dict]] = (
     ("--chunks", dict(REQ, help="directory holding chunks/chunk_*.pt and chunk_metadata.json")),
     ("--output", dict(REQ, help="directory for trajectory_tum.txt and the ply files")),
@@ -70,33 +120,8 @@ RECON_FLAGS: Sequence[Tuple[str, Dict]] = (
                                                          "color_<frame>.png of the dense map for every N-th view")),
     ("--render-min-weight", dict(type=int, default=1, help="voxels below this fused weight are not drawn")),
     ("--render-splat-scale", dict(type=float, default=1.0, help="half-width of a drawn voxel in voxel sizes")),
-    ("--dense-min-weight", dict(type=int, default=None, help="dense map: drop voxels whose fused weight is below N "
-                                                             "(from dense_points.ply and the renders; e.g. 2 as a "
-                                                             "starting point, not a measured optimum)")),
-    ("--dense-min-support", dict(type=int, default=None, help="dense map: drop voxels with fewer than N occupied cells "
-                                                              "among their neighbours (26 at radius 1; e.g. 4 as a "
-                                                              "starting point, not a measured optimum)")),
-    ("--dense-support-radius", dict(type=int, default=1, choices=(1, 2), help="neighbourhood of --dense-min-support "
-                                                                               "in voxels: 26 or 124 cells")),
-    ("--dense-min-component", dict(type=int, default=None, help="dense map: then drop 26-connected components of fewer "
-                                                                "than N voxels (e.g. 50 as a starting point, not a "
-                                                                "measured optimum)")),
-)
-# carving the fused dense map with the chunks' depth keyframes (dense_map.MapCarver): a table of its own beside the
-# cleaning flags above, added to the same sub-command
-RECON_CARVE_FLAGS: Sequence[Tuple[str, Dict]] = (
-    ("--dense-carve-min-conflicts", dict(type=int, default=None, help="dense map: first drop the voxels that at least N "
-                                                                      "depth keyframes of any chunk looked through, "
-                                                                      "and more than agree with them (chunks created "
-                                                                      "with --dense-depth-every; use with "
-                                                                      "--no-bundle-adjust; e.g. 3 as a starting point, "
-                                                                      "not a measured optimum)")),
-    ("--dense-carve-tolerance", dict(type=float, default=0.03, help="relative depth difference (plus one voxel size) "
-                                                                    "within which a keyframe agrees with a voxel")),
 )
 RECON_SWITCHES = (("--save-per-chunk", "per-chunk ply files as well"),
-                  ("--dense-mesh", "write dense_mesh.ply: a triangle mesh of the fused dense map (surface nets on its "
-                                   "voxel lattice; the chunks must have been created with --dense-normals)"),
                   ("--render-overview", "write renders/overview.png: the dense map from above with the trajectory in red"),
                   ("--use-inverse-depth", "one inverse depth per track along its reference keypoint's ray in both bundle "
                                          "adjustments (utils/chunk_reconstruction.py:187-204; pi3_bundle_adjust_inverse_depth)"),
@@ -137,48 +162,18 @@ ONLINE_FLAGS: Sequence[Tuple[str, Dict]] = (
     ("--num_workers", dict(type=int, default=4, help="decode threads")),
     ("--dense_voxel_size", dict(type=float, default=None, help="write dense_points.ply: the dense maps filtered by "
                                                                "--conf_threshold, fused into voxels of this size (metres)")),
-    ("--dense_min_views", dict(type=int, default=None, help="with --dense_voxel_size: keep a pixel only when this many "
-                                                            "neighbouring frames of its chunk agree with its depth")),
-    ("--dense_view_radius", dict(type=int, default=3, help="neighbours i +- s * stride, s = 1..radius (1..16)")),
-    ("--dense_view_stride", dict(type=int, default=2, help="frame step between the neighbours")),
-    ("--dense_depth_tolerance", dict(type=float, default=0.03, help="relative depth difference that still agrees")),
     ("--render_every", dict(type=int, default=None, help="with --dense_voxel_size: renders/ with depth and colour images "
                                                          "of the dense map for every N-th view and an overview")),
-    ("--dense_min_weight", dict(type=int, default=None, help="dense map: drop voxels whose fused weight is below N "
-                                                             "(from dense_points.ply and the renders; e.g. 2 as a "
-                                                             "starting point, not a measured optimum)")),
-    ("--dense_min_support", dict(type=int, default=None, help="dense map: drop voxels with fewer than N occupied cells "
-                                                              "among their neighbours (26 at radius 1; e.g. 4 as a "
-                                                              "starting point, not a measured optimum)")),
-    ("--dense_support_radius", dict(type=int, default=1, choices=(1, 2), help="neighbourhood of --dense_min_support "
-                                                                               "in voxels: 26 or 124 cells")),
-    ("--dense_min_component", dict(type=int, default=None, help="dense map: then drop 26-connected components of fewer "
-                                                                "than N voxels (e.g. 50 as a starting point, not a "
-                                                                "measured optimum)")),
 )
-ONLINE_CARVE_FLAGS: Sequence[Tuple[str, Dict]] = (
-    ("--dense_depth_every", dict(type=int, default=None, help="with --dense_voxel_size: every chunk keeps the depth of "
-                                                              "every K-th frame for --dense_carve_min_conflicts")),
-    ("--dense_depth_stride", dict(type=int, default=2, choices=(1, 2, 4), help="those depth planes keep every S-th row "
-                                                                               "and column")),
-    ("--dense_carve_min_conflicts", dict(type=int, default=None, help="dense map: first drop the voxels that at least N "
-                                                                      "depth keyframes of any chunk looked through, "
-                                                                      "and more than agree with them (needs "
-                                                                      "--dense_depth_every; use with --no_bundle_adjust; "
-                                                                      "e.g. 3 as a starting point, not a measured "
-                                                                      "optimum)")),
-    ("--dense_carve_tolerance", dict(type=float, default=0.03, help="relative depth difference (plus one voxel size) "
-                                                                    "within which a keyframe agrees with a voxel")),
-)
+# both dense stages; --dense_voxel_size has its text above (here it writes dense_points.ply) and --conf_threshold is the
+# pixel test's threshold
+ONLINE_DENSE_FLAGS = underscored([row for row in tuple(DENSE_CHUNK_FLAGS) + tuple(DENSE_MAP_FLAGS)
+                                  if row[0] not in ("--dense-voxel-size", "--dense-conf-threshold")])
 ONLINE_SWITCHES = (("--save_chunk_reconstructions", "save each chunk reconstruction to disk"),
                    ("--save_transformed_reconstructions", "save transformed reconstructions as PLY files"),
                    ("--save_debug_reconstructions", "accepted for compatibility"),
                    ("--save_debug_projections", "accepted for compatibility"),
                    ("--use_inverse_depth", "inverse-depth parametrization in both bundle adjustments"),
-                   ("--dense_normals", "with --dense_voxel_size: surface normals in dense_points.ply (nx ny nz) and "
-                                       "normal / shaded images under renders/"),
-                   ("--dense_mesh", "with --dense_voxel_size and --dense_normals: write dense_mesh.ply, a triangle mesh "
-                                    "of the fused dense map"),
                    ("--no_visualization", "accepted for compatibility (there is never a window)"),
                    ("--keep_viz_open", "accepted for compatibility"),
                    ("--save_tum", "save the trajectory in TUM format"),
@@ -231,9 +226,9 @@ def list_images(root: str) -> List[str]:
 def build_parser() -> argparse.ArgumentParser:
     top = argparse.ArgumentParser(prog="pi3_slam_amd.cli", description=__doc__.split("\n")[0])
     sub = top.add_subparsers(dest="command", required=True)
-    for name, flags, switches in (("create", CREATE_FLAGS, CREATE_SWITCHES),
-                                  ("reconstruct", tuple(RECON_FLAGS) + tuple(RECON_CARVE_FLAGS), RECON_SWITCHES),
-                                  ("online", tuple(ONLINE_FLAGS) + tuple(ONLINE_CARVE_FLAGS), ONLINE_SWITCHES),
+    for name, flags, switches in (("create", tuple(CREATE_FLAGS) + tuple(DENSE_CHUNK_FLAGS), CREATE_SWITCHES),
+                                  ("reconstruct", tuple(RECON_FLAGS) + tuple(DENSE_MAP_FLAGS), RECON_SWITCHES),
+                                  ("online", tuple(ONLINE_FLAGS) + ONLINE_DENSE_FLAGS, ONLINE_SWITCHES),
                                   ("evaluate-map", EVAL_FLAGS, EVAL_SWITCHES)):
         p = sub.add_parser(name)
         for flag, kw in flags:
@@ -266,11 +261,8 @@ def run_create(a: argparse.Namespace) -> None:
         keypoint_detection_threshold=a.kp_threshold, estimate_camera_params=a.estimate_intrinsics,
         num_loader_workers=a.num_workers, cam_dist_path=a.cam_dist_path, moge_model_path=a.moge_model_path,
         keypoint_seed=None if a.keypoint_seed < 0 else a.keypoint_seed, device_resize=a.device_resize,
-        hip_graph=a.hip_graph, reuse_overlap_encoder=a.reuse_overlap_encoder, dense_voxel_size=a.dense_voxel_size,
-        dense_conf_threshold=a.dense_conf_threshold, dense_min_views=a.dense_min_views,
-        dense_view_radius=a.dense_view_radius, dense_view_stride=a.dense_view_stride,
-        dense_depth_tolerance=a.dense_depth_tolerance, dense_normals=a.dense_normals,
-        dense_depth_every=a.dense_depth_every, dense_depth_stride=a.dense_depth_stride)
+        hip_graph=a.hip_graph, reuse_overlap_encoder=a.reuse_overlap_encoder,
+        **{name: getattr(a, name) for name in option_names(DENSE_CHUNK_FLAGS)})
     OfflineChunkCreator(cfg).process_and_save(paths[lo:hi])
 
 
@@ -283,11 +275,8 @@ def run_reconstruct(a: argparse.Namespace) -> None:
                          save_observations=a.save_observations, bundle_adjust=not a.no_bundle_adjust,
                          ba_sanity_gate=not a.no_ba_sanity_gate, render_every=a.render_every,
                          render_overview=a.render_overview, render_min_weight=a.render_min_weight,
-                         render_splat_scale=a.render_splat_scale, dense_min_weight=a.dense_min_weight,
-                         dense_min_support=a.dense_min_support, dense_support_radius=a.dense_support_radius,
-                         dense_min_component=a.dense_min_component, dense_mesh=a.dense_mesh,
-                         dense_carve_min_conflicts=a.dense_carve_min_conflicts,
-                         dense_carve_tolerance=a.dense_carve_tolerance).run()
+                         render_splat_scale=a.render_splat_scale,
+                         **{name: getattr(a, name) for name in option_names(DENSE_MAP_FLAGS)}).run()
 
 
 def online_image_paths(a: argparse.Namespace) -> List[str]:
@@ -328,12 +317,8 @@ def run_online(a: argparse.Namespace) -> None:
         use_inverse_depth=a.use_inverse_depth, moge_model_path=a.moge_model_path, hip_graph=not a.no_hip_graph,
         output_dir=out_dir, num_loader_workers=a.num_workers, bundle_adjust=not a.no_bundle_adjust,
         reuse_overlap_encoder=a.reuse_overlap_encoder, dense_voxel_size=a.dense_voxel_size,
-        dense_min_views=a.dense_min_views, dense_view_radius=a.dense_view_radius,
-        dense_view_stride=a.dense_view_stride, dense_depth_tolerance=a.dense_depth_tolerance,
-        dense_min_weight=a.dense_min_weight, dense_min_support=a.dense_min_support,
-        dense_support_radius=a.dense_support_radius, dense_min_component=a.dense_min_component,
-        dense_normals=a.dense_normals, dense_depth_every=a.dense_depth_every, dense_depth_stride=a.dense_depth_stride,
-        dense_carve_min_conflicts=a.dense_carve_min_conflicts, dense_carve_tolerance=a.dense_carve_tolerance)
+        # --dense_mesh is no option of the object: it asks for save_dense_mesh() below
+        **{name: getattr(a, name) for name in option_names(ONLINE_DENSE_FLAGS) if name != "dense_mesh"})
     slam.save_transformed_reconstructions = a.save_transformed_reconstructions
     slam.save_debug_reconstructions = a.save_debug_reconstructions
     slam.process_chunks(paths)

@@ -6,7 +6,7 @@ tracks.  Here the dense maps are fused on the device into one voxel per occupied
   stage 1   OfflineChunkCreator (dense_voxel_size set): each chunk's metric pointmap, masked by the creator's masks and
             `conf > logit(dense_conf_threshold)`, becomes chunk['dense_cloud'] = {points f32 (V,3), colors u8 (V,3),
             weights i32 (V,), voxel_size, conf_threshold} in the chunk's own frame (ChunkCloudBuilder);
-  stage 2   fuse_chunk_clouds: every cloud moved by its chunk's accumulated similarity (ops.sim3_apply) and fused again,
+  stage 2   fuse_chunks: every cloud moved by its chunk's accumulated similarity (ops.sim3_apply) and fused again,
             weighted by W, into the world frame (= chunk 0's frame) -> dense_points.ply.
 
 Optionally (ConsistencyFilter, csrc/dense_filter.hip) a pixel of stage 1 must also be confirmed by the depth maps of
@@ -588,7 +588,6 @@ class MapMesher:
             cell_capacity = c
         self.cell_capacity = cell_capacity
         self.last_stats: Optional[Dict[str, int]] = None
-        self.error: Optional[Exception] = None      # try_apply's failure, for the caller that wanted the mesh
 
     def _cell_table(self, table, nacc, keep, stats) -> torch.Tensor:
         """The filled cell table; stats[:3] are its counters."""
@@ -643,16 +642,6 @@ class MapMesher:
         order = np.lexsort((qc & 3, qk))
         return {"vertices": xyz, "normals": nrm, "colors": rgb, "faces": quad_faces(keys, qk[order], qc[order]),
                 "keys": keys}
-
-    def try_apply(self, fuser: "VoxelFuser", normals_acc, keep: Optional[torch.Tensor] = None) -> Optional[Dict]:
-        """apply() for a caller that fuses the map and the mesh in one go: a failure is kept in self.error (None after
-        a success) and None returned, so the map is still delivered; whoever consumes the mesh raises it."""
-        self.error = None
-        try:
-            return self.apply(fuser, normals_acc, keep)
-        except Exception as e:  # noqa: BLE001
-            self.error = e
-            return None
 
     def summary(self) -> str:
         st = self.last_stats
@@ -834,23 +823,23 @@ def chunk_transform(chunk: Dict) -> torch.Tensor:
     return torch.eye(4, dtype=torch.float64) if G is None else torch.as_tensor(G, dtype=torch.float64).reshape(4, 4)
 
 
-def fuse_chunk_clouds_with_mesh(chunks: Iterable[Dict], voxel_size: float, device="cuda",
-                                cleaner: Optional[MapCleaner] = None, mesher: Optional[MapMesher] = None,
-                                carver: Optional[MapCarver] = None
-                                ) -> Tuple[np.ndarray, np.ndarray, np.ndarray, Optional[np.ndarray], Optional[Dict]]:
-    """Every chunk's dense_cloud moved by chunk_transform() and fused, weighted by its voxel weights ->
-    (points f32 (V,3), colors u8 (V,3), weights i32 (V,), normals f32 (V,3) or None, mesh or None), the map in ascending
-    key order.  Chunks without a cloud are skipped.  cleaner: its filters decide on the fused table which voxels are
-    extracted (one line with the counts is printed).  Normals: when every cloud carries `normals`, each cloud's are
-    rotated by its similarity's rotation and fused weighted by its `normal_weights`; when only some do, one line says so
-    and the map has none.  mesher: MapMesher.apply's mesh of the same fused table, after the same keep mask; without
-    normals one line says so and the mesh is None; when the mesher fails the mesh is None and mesher.error holds why.
-    carver: MapCarver.apply on the fused table with the chunks' depth keyframes, before the cleaner (one line with the
-    counts is printed, the cleaner's follows): a carved voxel is not extracted, is nobody's neighbour and belongs to no
-    component.  Without a cleaner the keep mask is "every voxel that was not carved"."""
-    device = torch.device(device)
-    chunks = list(chunks)
-    clouds = [(c["dense_cloud"], chunk_transform(c)) for c in chunks if c.get("dense_cloud") is not None]
+@dataclass
+class DenseMap:
+    """The fused dense map of a sequence (fuse_chunks): one row per voxel, in ascending key order."""
+    points: np.ndarray                          # f32 (V,3)
+    colors: np.ndarray                          # u8 (V,3)
+    weights: np.ndarray                         # i32 (V,)
+    voxel_size: float
+    normals: Optional[np.ndarray] = None        # f32 (V,3), row for row; None when the clouds carry none
+    mesh: Optional[Dict] = None                 # MapMesher.apply's mesh of the same table after the same keep mask
+    mesh_error: Optional[Exception] = None      # why a mesh that was asked for is missing; its consumer raises it
+
+
+def _fuse_clouds(clouds, voxel_size: float, device: torch.device) -> Tuple[VoxelFuser, Optional[NormalAccumulator]]:
+    """clouds: (dense_cloud, chunk_transform) pairs.  Every cloud is moved by its similarity and fused, weighted by its
+    voxel weights -> (the table, its normal sums).  Normals: when every cloud carries `normals`, each cloud's are rotated
+    by its similarity's rotation and fused weighted by its `normal_weights`; when only some do, one line says so and
+    there are no sums."""
     fuser = VoxelFuser(voxel_size, device)
     fuser.reserve(sum(int(cl["points"].shape[0]) for cl, _ in clouds))
     with_normals = sum(1 for cl, _ in clouds if cl.get("normals") is not None)
@@ -873,7 +862,15 @@ def fuse_chunk_clouds_with_mesh(chunks: Iterable[Dict], voxel_size: float, devic
             nw = upload(torch.as_tensor(cl["normal_weights"]).reshape(-1), device).to(torch.int32).contiguous()
             rot = upload(torch.from_numpy(similarity_rotation(G).reshape(9).copy()), device).contiguous()
             acc.add_points(pts, nrm, nw, rot)
-    keep = exclude = None
+    return fuser, acc
+
+
+def _keep_mask(fuser: VoxelFuser, chunks, cleaner: Optional[MapCleaner], carver: Optional[MapCarver]
+               ) -> Optional[torch.Tensor]:
+    """Which voxels of the fused table are extracted (None: all).  The carver goes first, with the chunks' depth
+    keyframes (one line with the counts, the cleaner's follows): a carved voxel is nobody's neighbour and belongs to no
+    component.  Without a cleaner the mask is "every voxel that was not carved"."""
+    exclude = None
     if carver is not None:
         exclude = carver.apply(fuser, chunks)
         if exclude is not None:
@@ -881,40 +878,47 @@ def fuse_chunk_clouds_with_mesh(chunks: Iterable[Dict], voxel_size: float, devic
     if cleaner is not None:
         keep = cleaner.apply(fuser, exclude=exclude)
         print(f"   🧹 Dense map cleaned: {cleaner.summary()}")
-    elif exclude is not None:
-        keep = MapCleaner(min_weight=1, min_support=0).apply(fuser, exclude=exclude)
+        return keep
+    if exclude is not None:
+        return MapCleaner(min_weight=1, min_support=0).apply(fuser, exclude=exclude)
+    return None
+
+
+def _extract_map(fuser: VoxelFuser, acc: Optional[NormalAccumulator], keep: Optional[torch.Tensor],
+                 mesher: Optional[MapMesher]) -> DenseMap:
+    """The kept voxels, their normals (acc) and, with a mesher, the mesh of the same table after the same keep mask.
+    Without normals one line says why there is no mesh; a mesher that fails leaves its exception in mesh_error, so the
+    map is still delivered."""
     out = fuser.extract(keep)
-    normals = None
+    dense = DenseMap(out["points"], out["colors"], out["weights"], fuser.voxel_size)
     if acc is not None:
         nout = acc.extract(keep)
         if not np.array_equal(nout["keys"], out["keys"]):
             raise RuntimeError("dense normals: the normal rows have other keys than the map's")
-        normals = nout["normals"]
-    mesh = None
+        dense.normals = nout["normals"]
     if mesher is not None and acc is not None:
-        mesh = mesher.try_apply(fuser, acc, keep)
-        if mesh is not None:
+        try:
+            dense.mesh = mesher.apply(fuser, acc, keep)
             print(f"   🕸️  Dense mesh: {mesher.summary()}")
+        except Exception as e:  # noqa: BLE001
+            dense.mesh_error = e
     elif mesher is not None:
         print("   ℹ️  The dense clouds carry no normals (create the chunks with dense_normals): no dense mesh")
-    return out["points"], out["colors"], out["weights"], normals, mesh
+    return dense
 
 
-def fuse_chunk_clouds_with_normals(chunks: Iterable[Dict], voxel_size: float, device="cuda",
-                                   cleaner: Optional[MapCleaner] = None, carver: Optional[MapCarver] = None
-                                   ) -> Tuple[np.ndarray, np.ndarray, np.ndarray, Optional[np.ndarray]]:
-    """fuse_chunk_clouds_with_mesh without the mesh: (points f32 (V,3), colors u8 (V,3), weights i32 (V,), normals f32
-    (V,3) or None when the clouds carry none)."""
-    return fuse_chunk_clouds_with_mesh(chunks, voxel_size, device, cleaner, carver=carver)[:4]
-
-
-def fuse_chunk_clouds(chunks: Iterable[Dict], voxel_size: float, device="cuda",
-                      cleaner: Optional[MapCleaner] = None, carver: Optional[MapCarver] = None
-                      ) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
-    """fuse_chunk_clouds_with_normals without the normals: (points f32 (V,3), colors u8 (V,3), weights i32 (V,))."""
-    return fuse_chunk_clouds_with_normals(chunks, voxel_size, device, cleaner, carver)[:3]
-
-
-def write_dense_ply(points: np.ndarray, colors: np.ndarray, path: str) -> None:
-    from .export import write_ply
-    write_ply(points, np.asarray(colors, np.uint8), path)
+def fuse_chunks(chunks: Iterable[Dict], device="cuda", *, voxel_size: Optional[float] = None,
+                cleaner: Optional[MapCleaner] = None, carver: Optional[MapCarver] = None,
+                mesher: Optional[MapMesher] = None) -> Optional[DenseMap]:
+    """Stage 2: every chunk's dense_cloud moved by chunk_transform() and fused in the world frame (chunk 0's) -> the
+    DenseMap; None when no chunk carries a cloud.  voxel_size: None takes the first cloud's.  carver (MapCarver) and
+    cleaner (MapCleaner) choose, in that order, on the fused table which voxels the map keeps; mesher (MapMesher) also
+    meshes them, which needs the clouds' normals."""
+    chunks = list(chunks)
+    clouds = [(c["dense_cloud"], chunk_transform(c)) for c in chunks if c.get("dense_cloud") is not None]
+    if not clouds:
+        return None
+    if voxel_size is None:
+        voxel_size = float(clouds[0][0]["voxel_size"])
+    fuser, acc = _fuse_clouds(clouds, voxel_size, torch.device(device))
+    return _extract_map(fuser, acc, _keep_mask(fuser, chunks, cleaner, carver), mesher)

@@ -4,7 +4,7 @@ Pi3SLAMOnline.chunk_reconstructions).  Files and formats mirror slam/offline_rec
   final_points.ply        every track of every chunk (sparse_points_colors)
   final_camera_poses.ply  every view's camera centre, overlap views twice (all_views)
   trajectory_tum.txt      the de-duplicated trajectory: first occurrence of a view name wins (unique_views)
-  dense_points.ply        the chunks' dense clouds fused in the world frame (fuse_dense_map; dense_map.py), carved by a
+  dense_points.ply        the chunks' dense clouds fused in the world frame (dense_map.fuse_chunks), carved by a
                           dense_map.MapCarver and cleaned by a dense_map.MapCleaner when one is given; with nx ny nz
                           when the clouds carry normals
   dense_mesh.ply          (dense_mesh) a triangle mesh of the same fused table, after the same cleaner
@@ -22,6 +22,8 @@ from typing import Dict, Iterator, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
+
+from .dense_map import DenseMap, MapMesher, fuse_chunks
 
 
 def view_name(p) -> str:
@@ -177,49 +179,13 @@ def render_views(chunks: Sequence[Dict]) -> List[Dict]:
     return views
 
 
-class DenseMap(NamedTuple):
-    points: np.ndarray      # f32 (V,3), ascending key order
-    colors: np.ndarray      # u8 (V,3)
-    weights: np.ndarray     # i32 (V,)
-    voxel_size: float
-
-
-def fuse_dense_map_mesh(chunks: Sequence[Dict], device, cleaner=None, mesher=None, carver=None
-                        ) -> Tuple[Optional[DenseMap], Optional[np.ndarray], Optional[Dict]]:
-    """The chunks' dense clouds (chunks created with a dense voxel size) fused in the world frame -> (the map, its
-    normals f32 (V,3) row for row, or None when the clouds carry none, the mesh); (None, None, None) when no chunk
-    carries a cloud.  The voxel size is the first cloud's: the world frame is chunk 0's frame.  cleaner: a
-    dense_map.MapCleaner whose filters choose the voxels of the map (None: all of them).  mesher: a dense_map.MapMesher;
-    the mesh is its apply() on the same fused table after the same filters, None without one, without normals (one
-    line says so) or when it failed (mesher.error).  carver: a dense_map.MapCarver; the fused table is carved with the
-    chunks' depth keyframes before the cleaner sees it."""
-    first = next((d["dense_cloud"] for d in chunks if d.get("dense_cloud") is not None), None)
-    if first is None:
-        return None, None, None
-    from .dense_map import fuse_chunk_clouds_with_mesh
-    voxel = float(first["voxel_size"])
-    pts, cols, w, normals, mesh = fuse_chunk_clouds_with_mesh(chunks, voxel, device, cleaner, mesher, carver=carver)
-    return DenseMap(pts, cols, w, voxel), normals, mesh
-
-
-def fuse_dense_map_normals(chunks: Sequence[Dict], device, cleaner=None, carver=None
-                           ) -> Tuple[Optional[DenseMap], Optional[np.ndarray]]:
-    """fuse_dense_map_mesh without the mesh: (the map, its normals or None); (None, None) without dense clouds."""
-    return fuse_dense_map_mesh(chunks, device, cleaner, carver=carver)[:2]
-
-
-def fuse_dense_map(chunks: Sequence[Dict], device, cleaner=None, carver=None) -> Optional[DenseMap]:
-    """fuse_dense_map_normals without the normals: the map, or None when no chunk carries a dense cloud."""
-    return fuse_dense_map_normals(chunks, device, cleaner, carver)[0]
-
-
-def write_dense_points(dense: DenseMap, path: str, normals: Optional[np.ndarray] = None) -> int:
+def write_dense_points(dense: DenseMap, path: str) -> int:
     """dense_points.ply, with nx ny nz when the map has normals; returns the voxel count."""
-    if normals is None:
+    if dense.normals is None:
         write_ply(dense.points, np.asarray(dense.colors, np.uint8), path)
         print(f"✅ Saved dense map with {len(dense.points)} voxels ({dense.voxel_size} m) to: {path}")
     else:
-        write_ply_normals(dense.points, normals, np.asarray(dense.colors, np.uint8), path)
+        write_ply_normals(dense.points, dense.normals, np.asarray(dense.colors, np.uint8), path)
         print(f"✅ Saved dense map with {len(dense.points)} voxels ({dense.voxel_size} m) and normals to: {path}")
     return len(dense.points)
 
@@ -233,22 +199,21 @@ def write_dense_mesh(mesh: Dict, path: str) -> int:
 
 def write_renders(chunks: Sequence[Dict], dense: Optional[DenseMap], out_dir: str, every: Optional[int], overview: bool,
                   min_weight: int = 1, splat_scale: float = 1.0, device="cuda",
-                  dense_cleaner=None, normals: Optional[np.ndarray] = None, dense_carver=None
-                  ) -> Optional[Tuple[int, Dict[str, float]]]:
+                  dense_cleaner=None, dense_carver=None) -> Optional[Tuple[int, Dict[str, float]]]:
     """<out_dir>/depth_<frame>.png (16 bit, millimetres, 0 = empty) and color_<frame>.png of the dense map for every
     `every`-th view of the de-duplicated trajectory, overview.png (a top-down orthographic view with the trajectory
     in red) and cameras.json -> (rendered views, {'total', 'png'} seconds).  `dense`: the map a caller has already fused
-    (else it is fused here, through `dense_carver` and `dense_cleaner`).  Without dense clouds in the chunks: one line, no directory, None.
-    normals: that map's normals; then every view also gets normal_<frame>.png (the camera-frame normal as RGB) and
-    shaded_<frame>.png (headlight shading, greyscale), and the overview overview_shaded.png."""
+    (else it is fused here, through `dense_carver` and `dense_cleaner`).  Without dense clouds in the chunks: one line,
+    no directory, None.  When the map has normals every view also gets normal_<frame>.png (the camera-frame normal as
+    RGB) and shaded_<frame>.png (headlight shading, greyscale), and the overview overview_shaded.png."""
     if dense is None:
-        dense, normals = fuse_dense_map_normals(chunks, device, dense_cleaner, dense_carver)
+        dense = fuse_chunks(chunks, device, cleaner=dense_cleaner, carver=dense_carver)
     if dense is None:
         print("   ℹ️  No dense clouds in the chunks (create them with a dense voxel size): no renders")
         return None
     from .render import (DEPTH_PNG_SCALE, MapRenderer, pack_cameras, render_overview, write_color_png, write_depth_png,
                          write_grey_png)
-    pts, cols, w, voxel = dense
+    pts, cols, w, voxel, normals = dense.points, dense.colors, dense.weights, dense.voxel_size, dense.normals
     views = render_views(chunks)
     chosen = [v for v in views[:: int(every)] if v["K"] is not None] if every else []
     if every and not chosen:
@@ -329,32 +294,30 @@ def write_outputs(chunks: Sequence[Dict], output_dir: str, device="cuda", render
         save_trajectory_tum(chunks, os.path.join(output_dir, "trajectory_tum.txt"), integer_timestamp=True)
     except Exception as e:  # noqa: BLE001
         print(f"❌ Failed to save TUM trajectory: {e}")
-    dense = normals = mesh = mesher = None
-    if dense_mesh:
-        from .dense_map import MapMesher
-        mesher = MapMesher()
+    dense = None
     try:
-        dense, normals, mesh = fuse_dense_map_mesh(chunks, device, dense_cleaner, mesher, dense_carver)
+        dense = fuse_chunks(chunks, device, cleaner=dense_cleaner, carver=dense_carver,
+                            mesher=MapMesher() if dense_mesh else None)
         if dense is not None:
-            write_dense_points(dense, os.path.join(output_dir, "dense_points.ply"), normals)
+            write_dense_points(dense, os.path.join(output_dir, "dense_points.ply"))
     except Exception as e:  # noqa: BLE001
         print(f"❌ Failed to save the dense map: {e}")
         if dense is None:
-            mesher = None       # the fusion itself failed: no table, no mesh, and the line above says why
-    if mesher is not None:
+            dense_mesh = False  # the fusion itself failed: no table, no mesh, and the line above says why
+    if dense_mesh:
         try:
-            if mesher.error is not None:
-                raise mesher.error
-            if mesh is not None:
-                write_dense_mesh(mesh, os.path.join(output_dir, "dense_mesh.ply"))
-            elif dense is None:
+            if dense is None:
                 print("   ℹ️  No dense clouds in the chunks (create them with a dense voxel size): no dense mesh")
+            elif dense.mesh_error is not None:
+                raise dense.mesh_error
+            elif dense.mesh is not None:
+                write_dense_mesh(dense.mesh, os.path.join(output_dir, "dense_mesh.ply"))
         except Exception as e:  # noqa: BLE001
             print(f"❌ Failed to save the dense mesh: {e}")
     if render_every is not None or render_overview:
         try:       # the renders draw the map that was just fused for the PLY
             done = write_renders(chunks, dense, os.path.join(output_dir, "renders"), render_every, render_overview,
-                                 render_min_weight, render_splat_scale, device, dense_cleaner, normals, dense_carver)
+                                 render_min_weight, render_splat_scale, device, dense_cleaner, dense_carver)
             return done[1] if done else None
         except Exception as e:  # noqa: BLE001
             print(f"❌ Failed to save the renders of the dense map: {e}")

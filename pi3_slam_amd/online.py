@@ -28,6 +28,7 @@ from . import export
 from .alignment import align_and_refine_reconstructions, create_view_graph_matches, transform_chunk
 from .bundle_adjust import bundle_adjust_new_chunk, chunk_ba_args
 from .chunk_creator import OfflineChunkCreator, OfflineCreatorConfig
+from .dense_map import DenseMap, MapCarver, MapCleaner, MapMesher, fuse_chunks
 from .image_io import ChunkImageDataset, calculate_target_size
 
 
@@ -72,7 +73,6 @@ class Pi3SLAMOnline:
                  dense_support_radius: int = 1, dense_min_component: Optional[int] = None, dense_normals: bool = False,
                  dense_depth_every: Optional[int] = None, dense_depth_stride: int = 2,
                  dense_carve_min_conflicts: Optional[int] = None, dense_carve_tolerance: float = 0.03):
-        from .dense_map import MapCarver, MapCleaner
         # dense_depth_every: the chunks keep depth keyframes; dense_carve_min_conflicts: the fused dense map of
         # save_dense_map / save_dense_mesh / save_renders is carved with them first (dense_map.MapCarver; off by default)
         self.dense_carver = MapCarver.from_options(dense_carve_min_conflicts, dense_carve_tolerance)
@@ -302,39 +302,33 @@ class Pi3SLAMOnline:
             pts, cols = pts[sel], (cols[sel] if cols.size else cols)
         export.write_ply(pts, cols if cols.size else np.ones_like(pts), save_path)
 
-    def _fused_map(self):
-        """-> (the fused dense map, its normals or None: dense_normals)."""
-        dense, normals = export.fuse_dense_map_normals(self.chunk_reconstructions, str(self.device), self.dense_cleaner,
-                                                       self.dense_carver)
+    def _fused_map(self, mesher=None) -> DenseMap:
+        """The chunks' dense clouds fused, carved and cleaned as this object's options say (with normals under
+        dense_normals; mesher: and its mesh).  Fused anew on every call."""
+        dense = fuse_chunks(self.chunk_reconstructions, str(self.device), cleaner=self.dense_cleaner,
+                            carver=self.dense_carver, mesher=mesher)
         if dense is None:
             raise RuntimeError("no dense clouds: construct Pi3SLAMOnline with dense_voxel_size")
-        return dense, normals
+        return dense
 
     def save_dense_map(self, save_path: str) -> int:
         """The chunks' dense clouds (dense_voxel_size set) fused in the world frame, carved with the chunks' depth
         keyframes under dense_carve_min_conflicts, cleaned by the dense_min_* options
         when one is set -> a PLY (with normals under dense_normals); returns the voxel count."""
-        dense, normals = self._fused_map()
-        return export.write_dense_points(dense, save_path, normals)
+        return export.write_dense_points(self._fused_map(), save_path)
 
     def save_dense_mesh(self, save_path: str) -> Optional[int]:
         """A triangle mesh of the fused dense map (dense_map.MapMesher: surface nets on the voxel lattice, after the
         dense_min_* filters) -> a PLY with vertex normals and colours; returns the triangle count.  The clouds must
         carry normals (dense_normals): without them one line says so, no file is written and None is returned."""
-        from .dense_map import MapMesher
-        mesher = MapMesher()
-        dense, _, mesh = export.fuse_dense_map_mesh(self.chunk_reconstructions, str(self.device), self.dense_cleaner,
-                                                    mesher, self.dense_carver)
-        if dense is None:
-            raise RuntimeError("no dense clouds: construct Pi3SLAMOnline with dense_voxel_size")
-        if mesher.error is not None:
-            raise mesher.error
-        return export.write_dense_mesh(mesh, save_path) if mesh is not None else None
+        dense = self._fused_map(MapMesher())
+        if dense.mesh_error is not None:
+            raise dense.mesh_error
+        return export.write_dense_mesh(dense.mesh, save_path) if dense.mesh is not None else None
 
     def save_renders(self, out_dir: str, every: Optional[int] = 10, overview: bool = True, min_weight: int = 1,
                      splat_scale: float = 1.0) -> int:
         """Depth / colour images of the dense map from every `every`-th view, overview.png and cameras.json under
         `out_dir` (export.write_renders); returns the number of rendered views."""
-        dense, normals = self._fused_map()
-        return export.write_renders(self.chunk_reconstructions, dense, out_dir, every, overview, min_weight, splat_scale,
-                                    str(self.device), normals=normals)[0]
+        return export.write_renders(self.chunk_reconstructions, self._fused_map(), out_dir, every, overview, min_weight,
+                                    splat_scale, str(self.device))[0]

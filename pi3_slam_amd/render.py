@@ -1,6 +1,6 @@
 """Camera views of the dense voxel map (csrc/render.hip): depth, colour and a top-down overview.
 
-The fused map of dense_map.fuse_chunk_clouds is projected into cameras with correct occlusion by a z-buffered splat
+The fused map of dense_map.fuse_chunks is projected into cameras with correct occlusion by a z-buffered splat
 renderer on the device: every voxel is drawn as a square of half-width `splat_scale * voxel_size * fx / z` pixels and
 each pixel keeps the nearest voxel (64-bit atomicMin of depth bits | row).  The result does not depend on the order in
 which the atomics land; tests/render_ref.py reproduces it bit for bit.

@@ -118,7 +118,7 @@ def fuse_points(points, colors, weights, voxel_size: float) -> Dict[str, np.ndar
 
 
 def fuse_point_sets(sets, voxel_size: float) -> Dict[str, np.ndarray]:
-    """Several (points, colors, weights) lists into one table (fuse_chunk_clouds after the transforms)."""
+    """Several (points, colors, weights) lists into one table (dense_map.fuse_chunks after the transforms)."""
     parts = [contributions_points(p, c, w, inv_voxel(voxel_size)) for p, c, w in sets]
     if not parts:
         return finalise(merge(np.zeros(0, np.uint64), None, None, None), voxel_size)

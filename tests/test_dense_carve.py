@@ -209,7 +209,7 @@ def test_map_carver_validates_and_reports():
 def test_everything_is_off_by_default(tmp_path, capsys):
     from pi3_slam_amd.chunk_creator import OfflineCreatorConfig
     from pi3_slam_amd.cli import build_parser
-    from pi3_slam_amd.dense_map import ChunkCloudBuilder, MapCleaner, fuse_chunk_clouds_with_mesh
+    from pi3_slam_amd.dense_map import ChunkCloudBuilder, MapCleaner, fuse_chunks
     from pi3_slam_amd.online import Pi3SLAMOnline
     from pi3_slam_amd.reconstructor import OfflineReconstructor
     from pi3_slam_amd import export
@@ -231,11 +231,12 @@ def test_everything_is_off_by_default(tmp_path, capsys):
     rec = OfflineReconstructor(str(tmp_path), str(tmp_path / "out"), dense_carve_min_conflicts=3)
     assert rec.dense_carver.settings() == {"min_conflicts": 3, "rel_tol": 0.03} and rec.dense_cleaner is None
     # trailing keywords, None by default
-    for fn, name in ((fuse_chunk_clouds_with_mesh, "carver"), (export.fuse_dense_map_mesh, "carver"),
-                     (export.fuse_dense_map_normals, "carver"), (export.fuse_dense_map, "carver"),
-                     (export.write_outputs, "dense_carver"), (export.write_renders, "dense_carver")):
+    for fn, name in ((export.write_outputs, "dense_carver"), (export.write_renders, "dense_carver")):
         params = list(inspect.signature(fn).parameters.values())
         assert params[-1].name == name and params[-1].default is None, fn.__name__
+    params = inspect.signature(fuse_chunks).parameters
+    for name in ("cleaner", "carver", "mesher"):
+        assert params[name].kind is inspect.Parameter.KEYWORD_ONLY and params[name].default is None, name
     assert list(inspect.signature(MapCleaner.apply).parameters)[-1] == "exclude"
     # the creator's options need the dense map
     capsys.readouterr()
@@ -273,6 +274,31 @@ def test_flags_parse():
     assert (a.dense_depth_every, a.dense_depth_stride, a.dense_carve_min_conflicts, a.dense_carve_tolerance) == (3, 1, 2, 0.04)
     text = p._subparsers._group_actions[0].choices["reconstruct"].format_help()
     assert "starting point" in re.sub(r"\s+", " ", text.split("--dense-carve-min-conflicts")[2])
+
+
+def test_online_takes_the_dense_flags_of_create_and_reconstruct_respelled():
+    """One table, two spellings: every --dense-* flag of create or reconstruct except --dense-conf-threshold (online
+    has --conf_threshold for it) is a flag of online with underscores and the same type, default and choices; and no
+    help text names a dense flag in the other commands' spelling."""
+    from pi3_slam_amd.cli import build_parser
+    sub = build_parser()._subparsers._group_actions[0].choices
+
+    def dense(cmd):
+        return {a.option_strings[0]: a for a in sub[cmd]._actions if a.option_strings[0].startswith("--dense")}
+    online = dense("online")
+    hyphened = {**dense("create"), **dense("reconstruct")}
+    assert len(hyphened) == len(dense("create")) + len(dense("reconstruct")) == 16
+    assert "--dense-conf-threshold" in hyphened and "--dense_conf_threshold" not in online
+    del hyphened["--dense-conf-threshold"]
+    assert {"--" + f[2:].replace("-", "_") for f in hyphened} == set(online)
+    for flag, a in hyphened.items():
+        b = online["--" + flag[2:].replace("-", "_")]
+        assert (type(a), a.dest, a.type, a.default, a.choices, a.nargs) == \
+            (type(b), b.dest, b.type, b.default, b.choices, b.nargs), flag
+        assert a.help and b.help
+    for cmd, wrong in (("online", r"--dense-"), ("create", r"--dense_"), ("reconstruct", r"--dense_")):
+        for a in sub[cmd]._actions:
+            assert not re.search(wrong, a.help or ""), (cmd, a.option_strings, a.help)
 
 
 def test_new_symbols_are_declared_bound_and_refuse_bad_arguments(built_lib):

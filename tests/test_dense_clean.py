@@ -158,9 +158,9 @@ def test_online_flags_reach_the_facade(tmp_path, monkeypatch):
 
 def test_help_texts_call_their_examples_starting_points():
     from pi3_slam_amd import cli
-    for table in (cli.RECON_FLAGS, cli.ONLINE_FLAGS):
+    for table in (cli.DENSE_MAP_FLAGS, cli.ONLINE_DENSE_FLAGS):     # the cleaner's three thresholds and the carver's
         helps = {f: kw["help"] for f, kw in table if "min" in f and "dense" in f and "views" not in f}
-        assert len(helps) == 3
+        assert len(helps) == 4 and sum("carve" in f for f in helps) == 1
         assert all("starting point" in h and "not a measured optimum" in h for h in helps.values())
 
 

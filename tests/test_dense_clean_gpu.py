@@ -306,7 +306,7 @@ def _green(png):
 
 def test_end_to_end_cleaned_ply_and_renders(tmp_path, capsys):
     from pi3_slam_amd import export
-    from pi3_slam_amd.dense_map import MapCleaner, fuse_chunk_clouds
+    from pi3_slam_amd.dense_map import MapCleaner, fuse_chunks
     scene = ref.planted_scene()
     chunks = _scene_chunks(scene)
     world = _oracle_world(chunks)
@@ -323,8 +323,9 @@ def test_end_to_end_cleaned_ply_and_renders(tmp_path, capsys):
     assert off == open(tmp_path / "off2" / "dense_points.ply", "rb").read()
     assert open(tmp_path / "off" / "renders" / "overview.png", "rb").read() == \
         open(tmp_path / "off2" / "renders" / "overview.png", "rb").read()
-    p0, c0, w0 = fuse_chunk_clouds(chunks, V, DEV)
-    assert p0.tobytes() == world["points"].tobytes() and w0.tobytes() == world["weights"].tobytes()
+    fused = fuse_chunks(chunks, DEV, voxel_size=V)
+    assert fused.points.tobytes() == world["points"].tobytes()
+    assert fused.weights.tobytes() == world["weights"].tobytes()
     assert _green(tmp_path / "off" / "renders" / "overview.png") > 0        # the strays show in the uncleaned map
     capsys.readouterr()
 

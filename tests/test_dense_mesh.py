@@ -195,24 +195,27 @@ def test_option_plumbing(tmp_path, monkeypatch):
     assert seen["dense_mesh"] is False
 
 
+class NoTable:
+    """Stands in for dense_map.VoxelFuser: an empty table, no device."""
+
+    def __init__(self, voxel_size, device="cpu", out_sets=1):
+        self.voxel_size, self.device = float(voxel_size), device
+
+    def reserve(self, n):
+        pass
+
+    def extract(self, keep=None):
+        return dict(keys=np.zeros(0, np.uint64), points=np.zeros((0, 3), np.float32),
+                    colors=np.zeros((0, 3), np.uint8), weights=np.zeros(0, np.int32))
+
+
 def test_clouds_without_normals_give_one_notice_and_no_file(tmp_path, monkeypatch, capsys):
     """write_outputs with dense_mesh on chunks whose clouds carry no normals: the fused map is written as ever, one
     line says why there is no mesh, no dense_mesh.ply, nothing raised.  The clouds are empty and the device table is a
-    stand-in, so the real fuse_chunk_clouds_with_mesh runs without a GPU."""
+    stand-in, so the real fuse_chunks runs without a GPU."""
     import torch
 
     from pi3_slam_amd import dense_map, export
-
-    class NoTable:
-        def __init__(self, voxel_size, device="cpu", out_sets=1):
-            self.voxel_size, self.device = float(voxel_size), device
-
-        def reserve(self, n):
-            pass
-
-        def extract(self, keep=None):
-            return dict(keys=np.zeros(0, np.uint64), points=np.zeros((0, 3), np.float32),
-                        colors=np.zeros((0, 3), np.uint8), weights=np.zeros(0, np.int32))
     monkeypatch.setattr(dense_map, "VoxelFuser", NoTable)
     cloud = {"points": torch.zeros(0, 3), "colors": torch.zeros(0, 3, dtype=torch.uint8),
              "weights": torch.zeros(0, dtype=torch.int32), "voxel_size": 0.05}
@@ -230,3 +233,54 @@ def test_clouds_without_normals_give_one_notice_and_no_file(tmp_path, monkeypatc
     # without the option nothing about a mesh is printed
     export.write_outputs(chunks, str(tmp_path), device="cpu")
     assert "mesh" not in capsys.readouterr().out
+
+
+def test_a_failed_mesh_travels_with_the_map_and_the_points_are_still_written(tmp_path, monkeypatch, capsys):
+    """A mesher whose apply() raises: fuse_chunks still returns the map, with mesh None and the exception in
+    mesh_error; write_outputs writes dense_points.ply (with the normals) and reports the mesh once.  Empty clouds that
+    carry normals, stand-ins for the device table and its normal sums."""
+    import torch
+
+    from pi3_slam_amd import dense_map, export
+
+    class NoSums:
+        def __init__(self, fuser, out_sets=1):
+            pass
+
+        def clear(self):
+            pass
+
+        def extract(self, keep=None):
+            return dict(keys=np.zeros(0, np.uint64), normals=np.zeros((0, 3), np.float32),
+                        normal_weights=np.zeros(0, np.int32))
+
+    boom = RuntimeError("dense mesh: the cell table of 8 slots is too small")
+
+    class FailingMesher:
+        calls = 0
+
+        def apply(self, fuser, normals_acc, keep=None):
+            assert isinstance(fuser, NoTable) and isinstance(normals_acc, NoSums) and keep is None
+            FailingMesher.calls += 1
+            raise boom
+    monkeypatch.setattr(dense_map, "VoxelFuser", NoTable)
+    monkeypatch.setattr(dense_map, "NormalAccumulator", NoSums)
+    cloud = {"points": torch.zeros(0, 3), "colors": torch.zeros(0, 3, dtype=torch.uint8),
+             "weights": torch.zeros(0, dtype=torch.int32), "voxel_size": 0.05,
+             "normals": torch.zeros(0, 3), "normal_weights": torch.zeros(0, dtype=torch.int32)}
+    chunks = [{"dense_cloud": dict(cloud), "camera_poses": torch.eye(4)[None]} for _ in range(2)]
+    dense = dense_map.fuse_chunks(chunks, "cpu", mesher=FailingMesher())
+    assert isinstance(dense, dense_map.DenseMap) and export.DenseMap is dense_map.DenseMap
+    assert dense.mesh is None and dense.mesh_error is boom and FailingMesher.calls == 1
+    assert dense.voxel_size == 0.05 and dense.normals.shape == (0, 3) and dense.points.shape == (0, 3)
+    assert "Dense mesh" not in capsys.readouterr().out
+    assert dense_map.fuse_chunks([{"camera_poses": torch.eye(4)[None]}], "cpu", mesher=FailingMesher()) is None
+
+    monkeypatch.setattr(export, "MapMesher", FailingMesher)
+    export.write_outputs(chunks, str(tmp_path), device="cpu", dense_mesh=True)
+    text = capsys.readouterr().out
+    assert text.count("Failed to save the dense mesh") == 1 and "the cell table of 8 slots is too small" in text
+    assert "Failed to save the dense map" not in text and "no dense mesh" not in text
+    assert "and normals to:" in text and FailingMesher.calls == 2
+    assert os.path.exists(tmp_path / "dense_points.ply") and not os.path.exists(tmp_path / "dense_mesh.ply")
+    assert b"property float nx" in open(tmp_path / "dense_points.ply", "rb").read()

@@ -285,7 +285,7 @@ def test_option_end_to_end_on_the_tiny_engine(tmp_path, capsys):
     """Two chunks of 56 x 70 frames created with dense_normals: reconstruct with dense_mesh writes a dense_mesh.ply that
     parses, indexes valid vertices and equals MapMesher on the same fused table; without the option the output
     directory and dense_points.ply are what they were.  Chunks without normals: one line, no file."""
-    from pi3_slam_amd.dense_map import MapMesher, fuse_chunk_clouds_with_mesh
+    from pi3_slam_amd.dense_map import MapMesher, fuse_chunks
     from pi3_slam_amd.engine import Pi3Engine
     from pi3_slam_amd.reconstructor import OfflineReconstructor
     from pi3_slam_amd.weights import Pi3Config
@@ -329,8 +329,9 @@ def test_option_end_to_end_on_the_tiny_engine(tmp_path, capsys):
     ln = np.linalg.norm(got["normals"].astype(np.float64), axis=1)
     assert np.all((np.abs(ln - 1.0) <= 1e-6) | (ln == 0.0)) and (ln > 0).any()
     mesher = MapMesher()
-    again = fuse_chunk_clouds_with_mesh(rec.reconstructions, 0.05, DEV, None, mesher)[4]
-    assert mesher.error is None
+    fused = fuse_chunks(rec.reconstructions, DEV, voxel_size=0.05, mesher=mesher)
+    again = fused.mesh
+    assert fused.mesh_error is None
     for k in ("vertices", "normals", "colors", "faces"):
         assert got[k].tobytes() == again[k].tobytes(), k
 
@@ -342,10 +343,11 @@ def test_option_end_to_end_on_the_tiny_engine(tmp_path, capsys):
     assert slam.save_dense_mesh(str(tmp_path / "online_mesh.ply")) == nf
     assert open(tmp_path / "online_mesh.ply", "rb").read() == open(out_mesh / "dense_mesh.ply", "rb").read()
     cleaner = MapCleaner(min_weight=2)
-    cut = fuse_chunk_clouds_with_mesh(rec.reconstructions, 0.05, DEV, cleaner, mesher)[4]
+    fused = fuse_chunks(rec.reconstructions, DEV, voxel_size=0.05, cleaner=cleaner, mesher=mesher)
+    cut = fused.mesh
     print(f"cleaned: {cleaner.last_stats['after_components']} of {cleaner.last_stats['voxels']} voxels kept, "
           f"{mesher.last_stats['sources']} sources, {len(cut['faces'])} triangles")
-    assert mesher.error is None and mesher.last_stats["sources"] <= cleaner.last_stats["after_components"]
+    assert fused.mesh_error is None and mesher.last_stats["sources"] <= cleaner.last_stats["after_components"]
     assert cut["faces"].size == 0 or cut["faces"].max() < len(cut["vertices"])
     capsys.readouterr()
 

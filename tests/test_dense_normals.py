@@ -14,6 +14,7 @@ Error terms shared by the geometry tests (angles in radians, small enough that s
         K cos A, the summed errors at most K e_q).
   e_o   the output is fp32: each component of the unit normal is off by at most 2^-24, the vector by sqrt(3) 2^-24."""
 import ctypes as C
+import dataclasses
 import math
 import os
 
@@ -344,5 +345,5 @@ def test_write_ply_normals_header_and_round_trip(tmp_path):
     write_dense_points(dense, str(tmp_path / "a.ply"))
     write_ply(pts, rgb, str(tmp_path / "b.ply"))
     assert open(tmp_path / "a.ply", "rb").read() == open(tmp_path / "b.ply", "rb").read()
-    write_dense_points(dense, str(tmp_path / "c.ply"), nr)
+    write_dense_points(dataclasses.replace(dense, normals=nr), str(tmp_path / "c.ply"))
     assert open(tmp_path / "c.ply", "rb").read() == data

@@ -331,7 +331,7 @@ def test_chess_room_end_to_end_renders(tmp_path):
 def test_online_save_renders_writes_the_same_files(tmp_path):
     from PIL import Image
 
-    from pi3_slam_amd.dense_map import fuse_chunk_clouds
+    from pi3_slam_amd.dense_map import fuse_chunks
     from pi3_slam_amd.engine import Pi3Engine
     from pi3_slam_amd.online import Pi3SLAMOnline
     from pi3_slam_amd.render import pack_cameras
@@ -364,7 +364,8 @@ def test_online_save_renders_writes_the_same_files(tmp_path):
     assert n == len(rec["views"]) == 4 and [vw["frame"] for vw in rec["views"]] == [f"frame_{i:05d}.png" for i in (0, 5, 10, 15)]
     expected = {"cameras.json", "overview.png"} | {vw["depth"] for vw in rec["views"]} | {vw["color"] for vw in rec["views"]}
     assert set(os.listdir(rd)) == expected and rec["overview"]["ortho"] is True
-    pts, cols, w = fuse_chunk_clouds(slam.chunk_reconstructions, 0.05, DEV)
+    fused = fuse_chunks(slam.chunk_reconstructions, DEV, voxel_size=0.05)
+    pts, cols, w = fused.points, fused.colors, fused.weights
     poses = np.array([vw["pose"] for vw in rec["views"]])
     Ks = np.array([[[vw["fx"], 0, vw["cx"]], [0, vw["fy"], vw["cy"]], [0, 0, 1]] for vw in rec["views"]])
     H, W = rec["views"][0]["H"], rec["views"][0]["W"]

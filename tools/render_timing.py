@@ -85,8 +85,10 @@ def footprint_pixels(points: np.ndarray, cams: np.ndarray, H: int, W: int, sv: f
 
 def kernel_times(rec, dev: str, reps: int):
     from pi3_slam_amd import export, lib, ops
+    from pi3_slam_amd.dense_map import fuse_chunks
     from pi3_slam_amd.render import MapRenderer, default_batch, pack_cameras
-    pts, cols, w, voxel = export.fuse_dense_map(rec.reconstructions, dev)
+    dense = fuse_chunks(rec.reconstructions, dev)
+    pts, cols, w, voxel = dense.points, dense.colors, dense.weights, dense.voxel_size
     views = [v for v in export.render_views(rec.reconstructions)[::50] if v["K"] is not None]
     H, W = views[0]["H"], views[0]["W"]
     cams = pack_cameras(np.stack([v["pose"] for v in views]), np.stack([v["K"] for v in views]))

@@ -532,6 +532,47 @@ int pi3_cloud_pair_equations(const float* queries, long m, const float* points, 
                              int normals_of, const double* Rn, double* partials, long partial_rows, double* out,
                              unsigned long long* counters, void* stream);
 
+/* ---- nearest triangle of a mesh (csrc/mesh_nn.hip): the exact radius-bounded point-to-surface distance, through the
+ * cell grid of pi3_cloud_index_build (same table form, quantiser and inv_cell).  vertices f32 [V][3], faces int32 [F][3].
+ * A triangle gets a row (its face index, int32) in every cell of its axis-aligned bounding box; it is dropped (counted,
+ * no row, never returned) when a vertex index is outside [0, V), a vertex is not finite or outside the quantiser's
+ * |k| < 2^20, or the f64 squared norm of ab x ac is 0.  The number of rows is not known in advance: two calls.
+ * pi3_mesh_index_count: clears the table (capacity slots of 64 B, a power of two, more than the cells the mesh covers),
+ * writes packed f32 [F][12] = a, b, c, 2 spare, the face index as int32 (-1 = dropped), and counts the rows per cell
+ * unless their total exceeds max_rows (1 .. 2^31 - 1; then the table stays clear).  counters: DEVICE uint64 [8], zeroed
+ * by the call = dropped triangles, cells, (triangle, cell) pairs that found no free slot, largest cell (written by the
+ * fill), total rows (a box of 2^32 cells or more counts as 2^32), 3 spare.  F == 0 leaves an empty table.
+ * pi3_mesh_index_fill: table, packed, F, inv_cell as the count call left them, rows int32 [n_rows] with n_rows the
+ * count call's total; gives every occupied cell its rows and writes them; writes the largest cell into `counters` (the
+ * count call's array, not zeroed).  The order of the rows is not defined.
+ * pi3_mesh_nearest: queries f32 [m][3] -> d2 f64 [m], face int32 [m], closest f32 [m][3]: over the triangles in the 27
+ * cells around the query, the closest point by Ericson's region tests (Real-Time Collision Detection 5.1.5) in f64
+ * without contraction, the exact operation order stated at the top of mesh_nn.hip; candidate when d2 <= max_dist^2
+ * (inclusive; a d2 that is not finite never is); the smallest d2 wins, among equal d2 the smallest face index.  Without
+ * a candidate, or for a dropped query: +inf, -1, (0, 0, 0).  NaN is written nowhere.  max_dist * inv_cell <= 0.9 as
+ * for pi3_cloud_nearest.  counters: DEVICE uint64 [4] = dropped queries, matched, beyond, triangle evaluations; zeroed
+ * by the call.  m == 0 launches nothing; F == 0: every query is beyond.  Bad arguments launch nothing.  No
+ * allocation, no synchronisation. */
+int pi3_mesh_index_count(const float* vertices, long V, const int* faces, long F, float inv_cell, void* table,
+                         long capacity, float* packed, long max_rows, unsigned long long* counters, void* stream);
+int pi3_mesh_index_fill(void* table, long capacity, const float* packed, long F, float inv_cell, int* rows, long n_rows,
+                        unsigned long long* counters, void* stream);
+int pi3_mesh_nearest(const void* table, long capacity, const int* rows, long n_rows, const float* packed, long F,
+                     float inv_cell, const float* queries, long m, double max_dist, double* d2, int* face,
+                     float* closest, unsigned long long* counters, void* stream);
+/* ---- area-weighted samples of a mesh's surface (csrc/mesh_sample.hip), a function of the mesh, the spacing and the
+ * seed, bit for bit (the hash and the operation order are stated at the top of the file).
+ * pi3_mesh_sample_counts: counts int64 [F] = floor(area / spacing^2 + u_f) with u_f in [0, 1) from (seed, face), at
+ * most 2^31 - 1; 0 for a dropped face (index outside [0, V), a coordinate not finite, zero area).  counters: DEVICE
+ * uint64 [4], zeroed by the call = dropped faces, 3 spare.
+ * pi3_mesh_sample_points: offsets int64 [F + 1] = the exclusive prefix sums of counts (offsets[F] = n); sample
+ * offsets[f] + j is sample j of face f: points f32 [n][3] uniform on the triangle, face int32 [n], normals f32 [n][3] =
+ * the unit face normal by the winding.  F >= 1.  n == 0 launches nothing. */
+int pi3_mesh_sample_counts(const float* vertices, long V, const int* faces, long F, double spacing,
+                           unsigned long long seed, long long* counts, unsigned long long* counters, void* stream);
+int pi3_mesh_sample_points(const float* vertices, long V, const int* faces, long F, const long long* offsets, long n,
+                           unsigned long long seed, float* points, int* face, float* normals, void* stream);
+
 /* ---- dense map -> camera views (csrc/render.hip): a z-buffered splat renderer for the voxel map.
  * points f32 [V][3] (the voxel centroids, in ascending key order), weights int32 [V] (or NULL: every voxel counts),
  * cams f64 [M][20] = world->camera 3x4 row-major (12), fx, fy, cx, cy, ortho flag (0 / 1), 3 spare.  zbuf uint64

@@ -184,8 +184,9 @@ ONLINE_SWITCHES = (("--save_chunk_reconstructions", "save each chunk reconstruct
 
 # evaluate-map: this build's own sub-command (map_eval.py), no counterpart in the reference
 EVAL_FLAGS: Sequence[Tuple[str, Dict]] = (
-    ("--estimate", dict(REQ, help="the map to score: dense_points.ply, or dense_mesh.ply (its vertices)")),
-    ("--reference", dict(REQ, help="the reference cloud (PLY)")),
+    ("--estimate", dict(REQ, help="the map to score: dense_points.ply, or dense_mesh.ply (its vertices; its surface "
+                                  "with --mesh-surface)")),
+    ("--reference", dict(REQ, help="the reference cloud or mesh (PLY)")),
     ("--thresholds", dict(REQ, type=float, nargs="+", help="distances at which precision / recall / F-score are taken")),
     ("--max-dist", dict(type=float, default=None, help="search radius; farther points count as beyond "
                                                        "(default: twice the largest threshold)")),
@@ -198,7 +199,8 @@ EVAL_FLAGS: Sequence[Tuple[str, Dict]] = (
                                                       "Umeyama over associated stamps)")),
     ("--reference-trajectory", dict(default=None, help="TUM trajectory of the reference")),
     ("--error-ply", dict(default=None, help="write the (resampled, transformed) estimate coloured by its distance to "
-                                            "the reference: green 0, red max-dist, magenta beyond")),
+                                            "the reference: green 0, red max-dist, magenta beyond (with --mesh-surface "
+                                            "and a mesh estimate: its surface samples)")),
     ("--icp", dict(default=None, choices=("point", "plane"), help="refine the alignment by ICP on the (resampled) clouds "
                    "before scoring: point to point, or point to plane (the reference's nx ny nz when its PLY has them, "
                    "otherwise the estimate's); default: off")),
@@ -207,10 +209,15 @@ EVAL_FLAGS: Sequence[Tuple[str, Dict]] = (
                                                            "(default: the search's --max-dist)")),
     ("--save-transform", dict(default=None, help="write the similarity that was applied to the estimate (after --icp: "
                                                  "the refined one) in the form --transform reads")),
+    ("--mesh-sample-spacing", dict(type=float, default=None, help="with --mesh-surface: one surface sample per this "
+                                   "length squared of area (default: --voxel-size, otherwise half the smallest threshold)")),
+    ("--mesh-sample-seed", dict(type=int, default=0, help="with --mesh-surface: the seed of the surface samples")),
     ("--device", dict(default="cuda")),
 )
 EVAL_SWITCHES = (("--json", "print the result as one JSON line instead of the table"),
-                 ("--icp-scale", "with --icp: refine the scale too (a similarity instead of a rigid motion)"))
+                 ("--icp-scale", "with --icp: refine the scale too (a similarity instead of a rigid motion)"),
+                 ("--mesh-surface", "score every input that has faces by its surface: area-weighted samples as queries, "
+                                    "exact point-to-triangle distance as target (default: by its vertices)"))
 
 
 def list_images(root: str) -> List[str]:
@@ -375,6 +382,8 @@ def evaluate_map_icp(a: argparse.Namespace, est: Dict, ref: Dict) -> Optional[Di
             icp["ref_normals"] = ref["normals"]
         elif est["normals"] is not None:
             icp["est_normals"] = est["normals"]
+        elif a.mesh_surface and (est.get("faces") is not None or ref.get("faces") is not None):
+            pass                                   # a mesh side's surface samples carry their face normals
         else:
             raise SystemExit("evaluate-map: --icp plane needs nx ny nz in the reference's or the estimate's PLY")
     return icp
@@ -389,11 +398,22 @@ def run_evaluate_map(a: argparse.Namespace) -> None:
     from .export import write_ply
     if a.icp is None and a.icp_scale:              # refused before anything is read
         raise SystemExit("evaluate-map: --icp-scale needs --icp point|plane")
-    ev, rv = map_eval.read_ply_vertices(a.estimate), map_eval.read_ply_vertices(a.reference)
+    mesh = {}
+    if a.mesh_surface:
+        ev, rv = map_eval.read_ply_mesh(a.estimate), map_eval.read_ply_mesh(a.reference)
+        if ev["faces"] is None and rv["faces"] is None:
+            raise SystemExit("evaluate-map: --mesh-surface needs faces in the estimate's or the reference's PLY")
+        mesh = dict(est_faces=ev["faces"], ref_faces=rv["faces"], sample_spacing=a.mesh_sample_spacing,
+                    sample_seed=a.mesh_sample_seed)
+    else:
+        if a.mesh_sample_spacing is not None or a.mesh_sample_seed:
+            raise SystemExit("evaluate-map: --mesh-sample-spacing and --mesh-sample-seed need --mesh-surface")
+        ev, rv = map_eval.read_ply_vertices(a.estimate), map_eval.read_ply_vertices(a.reference)
     est, ref = ev["points"], rv["points"]
     icp = evaluate_map_icp(a, ev, rv)
     res = map_eval.compare_clouds(est, ref, a.thresholds, max_dist=a.max_dist, transform=evaluate_map_transform(a),
-                                  voxel_size=a.voxel_size, device=a.device, **({} if icp is None else {"icp": icp}))
+                                  voxel_size=a.voxel_size, device=a.device, **({} if icp is None else {"icp": icp}),
+                                  **mesh)
     if a.save_transform:
         applied = res["settings"]["transform"]
         map_eval.write_transform(a.save_transform, np.eye(4) if applied is None else applied)

@@ -81,6 +81,11 @@ SIGNATURES = {
     "pi3_cloud_index_build": [_vp, _l, _f, _vp, _l, _vp, _vp, _vp],
     "pi3_cloud_nearest": [_vp, _l, _vp, _l, _f, _vp, _l, _d, _vp, _vp, _vp, _vp],
     "pi3_cloud_pair_equations": [_vp, _l, _vp, _l, _vp, _vp, _d, _vp, _vp, _i, _vp, _vp, _l, _vp, _vp, _vp],
+    "pi3_mesh_index_count": [_vp, _l, _vp, _l, _f, _vp, _l, _vp, _l, _vp, _vp],
+    "pi3_mesh_index_fill": [_vp, _l, _vp, _l, _f, _vp, _l, _vp, _vp],
+    "pi3_mesh_nearest": [_vp, _l, _vp, _l, _vp, _l, _f, _vp, _l, _d, _vp, _vp, _vp, _vp, _vp],
+    "pi3_mesh_sample_counts": [_vp, _l, _vp, _l, _d, _u64, _vp, _vp, _vp],
+    "pi3_mesh_sample_points": [_vp, _l, _vp, _l, _vp, _l, _u64, _vp, _vp, _vp, _vp],
     "pi3_render_splat": [_vp, _vp, _l, _vp, _i, _i, _i, _d, _d, _i, _d, _d, _vp, _vp, _vp],
     "pi3_render_resolve": [_vp, _vp, _l, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
     "pi3_voxel_fuse_pixel_normals": [_vp, _l, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp],

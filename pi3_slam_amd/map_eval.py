@@ -11,12 +11,17 @@ The distances are exact nearest neighbours within `max_dist` (csrc/cloud_nn.hip:
 cells of 1.25 max_dist, f64 distances, ties to the smallest index); a point with no neighbour that close is "beyond" and
 carries inf.  The statistics are numpy f64 on the host.  There is no CPU fallback for the search.
 
+A side given with its faces (a ground-truth mesh, dense_mesh.ply) is scored by its surface instead of its vertices, as
+the Tanks and Temples evaluation does: where it is the query it is sampled uniformly by area (sample_surface,
+csrc/mesh_sample.hip: deterministic in the seed), where it is the target the distance is the exact point-to-triangle
+distance (MeshIndex, csrc/mesh_nn.hip: the same cell grid, every triangle in every cell of its bounding box).
+
 The estimate is placed on the reference by a given similarity or by the trajectory pair's; icp_refine then refines that
 placement on the geometry (point to point or point to plane, rigid or with scale): the search and the reduction of the
 pairs to normal equations run on the device (csrc/cloud_icp.hip), the 7 x 7 solve on the host.
 
     python -m pi3_slam_amd.cli evaluate-map --estimate dense_points.ply --reference GT.ply --thresholds 0.02 0.05
-                                            [--icp plane] [--save-transform T.txt]
+                                            [--icp plane] [--save-transform T.txt] [--mesh-surface]
 """
 from __future__ import annotations
 
@@ -93,6 +98,129 @@ def _device_nearest(ref: torch.Tensor, queries: torch.Tensor, max_dist: float) -
                 cells=index.build_stats["cells"], largest_cell=index.build_stats["largest_cell"])
 
 
+# ------------------------------------------------------------------------------------------------------ meshes
+def _device_faces(faces, device) -> torch.Tensor:
+    t = faces if torch.is_tensor(faces) else torch.from_numpy(np.ascontiguousarray(np.asarray(faces)))
+    if t.ndim != 2 or t.shape[1] != 3:
+        if t.numel() % 3:
+            raise ValueError(f"triangle faces are (F, 3), got {tuple(t.shape)}")
+        t = t.reshape(-1, 3)
+    if t.is_floating_point():
+        raise ValueError("triangle faces are integer vertex indices")
+    return t.to(device=device, dtype=torch.int32).contiguous()
+
+
+class MeshIndex:
+    """The cell grid of a triangle mesh on the device (csrc/mesh_nn.hip).  vertices (V,3) (used as fp32), faces (F,3)
+    integer; every triangle has a row in each cell of its bounding box, cells of 1.25 max_dist.  nearest(queries) ->
+    (d2 f64 (M,), face int64 (M,), closest f32 (M,3)) device tensors: the squared distance to the nearest triangle
+    within max_dist, its face index and the point on it; inf / -1 / 0 without one.  max_rows: the most rows the index
+    may take (4 bytes each); a mesh that needs more raises with the counts.  capacity: the cell table's slots (a power
+    of two); by default a first guess of F / 2 slots (a fine mesh has far fewer cells than triangles), at least
+    FIRST_SLOTS, and when the count pass finds that more than half full (or too small) a second table of at least twice
+    the cells.
+    build_stats: dropped triangles, cells, no_slot, largest_cell, rows, faces."""
+
+    FIRST_SLOTS = 65536         # the least first guess: 4 MiB, so a few wall-sized triangles do not need a second pass
+
+    def __init__(self, vertices, faces, max_dist: float, device="cuda", max_rows: int = 2 ** 28,
+                 capacity: Optional[int] = None):
+        self.device = torch.device(device)
+        self.max_dist = float(max_dist)
+        self.inv_cell = ops.cloud_inv_cell(self.max_dist)
+        self.vertices = _device_points(vertices, self.device)
+        self.faces = _device_faces(faces, self.device)
+        F = int(self.faces.shape[0])
+        if not (1 <= int(max_rows) <= ops.MESH_MAX_ROWS):
+            raise ValueError(f"max_rows must be in 1 .. {ops.MESH_MAX_ROWS}, got {max_rows}")
+        self.packed = torch.empty((F, 12), dtype=torch.float32, device=self.device)
+        self._counters = torch.zeros(8, dtype=torch.int64, device=self.device)
+        sized = capacity is not None
+        cap = int(capacity) if sized else ops.voxel_capacity(max(F // 4, self.FIRST_SLOTS // 2))
+        while True:
+            self.table = torch.empty(cap * 8, dtype=torch.int64, device=self.device)
+            ops.mesh_index_count(self.vertices, self.faces, self.inv_cell, self.table, self.packed, int(max_rows),
+                                 self._counters)
+            st = dict(zip(ops.MESH_INDEX_COUNTERS, (int(x) for x in self._counters.tolist())), faces=F)    # the one sync
+            if st["rows"] > int(max_rows):
+                raise RuntimeError(f"mesh index: {st['rows']} rows for {F} triangles ({st['dropped']} dropped) at cells of "
+                                   f"{ops.CLOUD_CELL_FACTOR * self.max_dist:g} exceed max_rows = {int(max_rows)}")
+            if st["no_slot"] and (sized or cap >= ops.voxel_capacity(st["rows"])):
+                raise RuntimeError(f"mesh index: cell table overflow at {cap} slots: {st}")
+            want = ops.voxel_capacity(st["rows"] if st["no_slot"] else st["cells"])      # cells <= rows
+            if sized or want <= cap:
+                break
+            cap = want                                    # at most half full: cannot overflow, lookups stay short
+        self.rows = torch.empty(st["rows"], dtype=torch.int32, device=self.device)
+        ops.mesh_index_fill(self.table, self.packed, self.inv_cell, self.rows, self._counters)
+        self._build_stats = None
+        self.last_stats: Dict = {}
+
+    @property
+    def build_stats(self) -> Dict:
+        """Read on first use: 'largest_cell' comes from the fill, which the constructor does not wait for."""
+        if self._build_stats is None:
+            self._build_stats = dict(zip(ops.MESH_INDEX_COUNTERS, (int(x) for x in self._counters.tolist())),
+                                     faces=int(self.faces.shape[0]))
+        return self._build_stats
+
+    def nearest(self, queries) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        q = _device_points(queries, self.device)
+        m = int(q.shape[0])
+        d2 = torch.empty(m, dtype=torch.float64, device=self.device)
+        face = torch.empty(m, dtype=torch.int32, device=self.device)
+        closest = torch.empty((m, 3), dtype=torch.float32, device=self.device)
+        counters = torch.zeros(4, dtype=torch.int64, device=self.device)
+        ops.mesh_nearest(self.table, self.rows, self.packed, self.inv_cell, q, self.max_dist, d2, face, closest, counters)
+        self.last_stats = dict(zip(ops.MESH_NEAREST_COUNTERS, (int(x) for x in counters.tolist())), queries=m)
+        return d2, face.long(), closest
+
+
+def _device_mesh_nearest(vertices: torch.Tensor, faces: torch.Tensor, queries: torch.Tensor, max_dist: float) -> Dict:
+    """queries against the triangles on their device -> _device_nearest's dict ('idx' = the face, 'ref_dropped' = the
+    dropped triangles) with 'closest' and 'rows' besides."""
+    index = MeshIndex(vertices, faces, max_dist, vertices.device)
+    d2, face, closest = index.nearest(queries)
+    st, bs = index.last_stats, index.build_stats
+    return dict(d2=d2.cpu().numpy(), idx=face.cpu().numpy(), closest=closest.cpu().numpy(), ref_dropped=bs["dropped"],
+                counters={k: st[k] for k in ("dropped", "matched", "beyond")}, evaluations=st["evaluations"],
+                cells=bs["cells"], largest_cell=bs["largest_cell"], rows=bs["rows"])
+
+
+def _device_sampler(vertices: torch.Tensor, faces: torch.Tensor, spacing: float, seed: int,
+                    max_samples: int = 2 ** 28) -> Dict:
+    """Area-weighted samples of the mesh on its device (csrc/mesh_sample.hip) -> points f32 (n,3), face int32 (n,),
+    normals f32 (n,3) device tensors and 'dropped', the faces that took no part."""
+    sp = float(spacing)
+    if not (sp > 0.0 and np.isfinite(sp)):
+        raise ValueError(f"the sample spacing must be finite and positive, got {spacing}")
+    dev = vertices.device
+    F = int(faces.shape[0])
+    counts = torch.zeros(F, dtype=torch.int64, device=dev)
+    counters = torch.zeros(4, dtype=torch.int64, device=dev)
+    ops.mesh_sample_counts(vertices, faces, sp, seed, counts, counters)
+    offsets = torch.zeros(F + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(counts, 0, out=offsets[1:])
+    n, dropped = int(offsets[-1]), int(counters[0])
+    if n > int(max_samples):
+        raise RuntimeError(f"mesh sampling: {n} samples at spacing {sp:g} exceed max_samples = {int(max_samples)}")
+    points = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    normals = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    face = torch.empty(n, dtype=torch.int32, device=dev)
+    if n:
+        ops.mesh_sample_points(vertices, faces, offsets, seed, points, face, normals)
+    return dict(points=points, face=face, normals=normals, dropped=dropped)
+
+
+def sample_surface(vertices, faces, spacing: float, seed: int = 0, device="cuda"):
+    """One sample per spacing^2 of surface on average, uniform by area, the same bytes for the same mesh, spacing and
+    seed -> (points f32 (n,3), faces int32 (n,) the face of each sample, normals f32 (n,3) the unit face normals),
+    device tensors, in face order."""
+    dev = torch.device(device)
+    s = _device_sampler(_device_points(vertices, dev), _device_faces(faces, dev), spacing, seed)
+    return s["points"], s["face"], s["normals"]
+
+
 # ------------------------------------------------------------------------------------------------------ statistics
 def distance_stats(dist, thresholds: Sequence[float], max_dist: float) -> Dict:
     """dist: distances (any shape), inf = no neighbour within max_dist.  -> matched, beyond, over the matched
@@ -144,7 +272,9 @@ def resample(points: torch.Tensor, voxel_size: float) -> torch.Tensor:
 
 def compare_clouds(est, ref, thresholds: Sequence[float], max_dist: Optional[float] = None, transform=None,
                    voxel_size: Optional[float] = None, device="cuda", _nearest: Optional[Callable] = None,
-                   icp: Optional[Dict] = None) -> Dict:
+                   icp: Optional[Dict] = None, est_faces=None, ref_faces=None, sample_spacing: Optional[float] = None,
+                   sample_seed: int = 0, _mesh_nearest: Optional[Callable] = None,
+                   _sampler: Optional[Callable] = None) -> Dict:
     """est, ref: (n,3) clouds.  transform: a 4x4 similarity applied to est on the device (ops.sim3_apply).  voxel_size:
     both clouds are first resampled to one point per voxel.  max_dist: the search radius, 2 max(thresholds) by default;
     every threshold must be <= max_dist.  -> {'points', 'dropped', 'accuracy', 'completeness', 'precision', 'recall',
@@ -160,7 +290,17 @@ def compare_clouds(est, ref, thresholds: Sequence[float], max_dist: Optional[flo
     `transform`) is then applied to the original estimate and the scoring proceeds as if it had been given as
     `transform`: 'settings'['transform'] reports it, and passing it back as `transform` without icp reproduces the
     scores.  The result gains 'icp': status, iterations, history, transform (the final matrix), increment.  Without
-    icp the result has no such key and is what it was."""
+    icp the result has no such key and is what it was.
+    est_faces / ref_faces: (F,3) integer triangles over est / ref, which are then that side's vertices: the side is
+    scored by its SURFACE.  As queries it is its area-weighted samples (sample_surface: one per sample_spacing^2, default
+    voxel_size when given, otherwise half the smallest threshold; drawn after `transform`, so the spacing is in the
+    reference's units; resampled by voxel_size like any cloud).  As target it is its triangles, with the exact
+    point-to-triangle distance (MeshIndex), never resampled.  ICP runs on the query clouds, and a mesh side's samples
+    carry their face normals for mode 'plane' (normals given for its vertices are not used).  'settings' gains
+    'mesh_sample_spacing' and 'mesh_sample_seed', 'points' gains per mesh side <side>_faces, <side>_faces_dropped and
+    <side>_samples; 'points'[<side>] stays the number of vertices.  _mesh_nearest, _sampler: the triangle search and
+    the sampler, for tests: (vertices, faces, queries, max_dist) -> _device_mesh_nearest's dict, (vertices, faces,
+    spacing, seed) -> _device_sampler's dict.  Without faces nothing of this applies and the result is what it was."""
     ths = [float(t) for t in thresholds]
     if not ths:
         raise ValueError("compare_clouds needs at least one threshold")
@@ -172,23 +312,49 @@ def compare_clouds(est, ref, thresholds: Sequence[float], max_dist: Optional[flo
         M = np.asarray(torch.as_tensor(transform, dtype=torch.float64).cpu().numpy(), np.float64).reshape(4, 4)
         e = e.clone()
         ops.sim3_apply(torch.from_numpy(M).to(dev).contiguous(), e, None)
+    fe = None if est_faces is None else _device_faces(est_faces, dev)
+    fr = None if ref_faces is None else _device_faces(ref_faces, dev)
+    meshes = fe is not None or fr is not None
+    spacing = None
+    if meshes:
+        spacing = float(sample_spacing) if sample_spacing is not None else (
+            float(voxel_size) if voxel_size is not None else 0.5 * min(ths))
+        sampler = _sampler or _device_sampler
     refined = None
     if icp is not None:
-        refined = _refine_alignment(_device_points(est, dev), e, r, None if transform is None else M, voxel_size, md, icp)
+        T = None if transform is None else M
+        if meshes:
+            refined = _refine_mesh_alignment(e, fe, r, fr, T, voxel_size, md, icp,
+                                             lambda v, f: sampler(v, f, spacing, int(sample_seed)), _device_points(est, dev))
+        else:
+            refined = _refine_alignment(_device_points(est, dev), e, r, T, voxel_size, md, icp)
         transform = M = refined["transform"]
         e = _device_points(est, dev).clone()
         ops.sim3_apply(torch.from_numpy(M).to(dev).contiguous(), e, None)
+    ve, vr = e, r                                  # the vertices of a mesh side: its triangles are never resampled
+    if fe is not None:
+        se = sampler(ve, fe, spacing, int(sample_seed))
+        e = se["points"]
+        counts.update(estimate_faces=int(fe.shape[0]), estimate_faces_dropped=int(se["dropped"]),
+                      estimate_samples=int(e.shape[0]))
+    if fr is not None:
+        sr = sampler(vr, fr, spacing, int(sample_seed))
+        r = sr["points"]
+        counts.update(reference_faces=int(fr.shape[0]), reference_faces_dropped=int(sr["dropped"]),
+                      reference_samples=int(r.shape[0]))
     if voxel_size is not None:
         e, r = resample(e, voxel_size), resample(r, voxel_size)
     counts.update(estimate_used=int(e.shape[0]), reference_used=int(r.shape[0]))
     search = _nearest or _device_nearest
-    er, re_ = search(r, e, md), search(e, r, md)
-    for a, b, who in ((er, re_, "estimate"), (re_, er, "reference")):
+    mesh_search = _mesh_nearest or _device_mesh_nearest
+    er = mesh_search(vr, fr, e, md) if fr is not None else search(r, e, md)
+    re_ = mesh_search(ve, fe, r, md) if fe is not None else search(e, r, md)
+    for a, b, who, as_cloud in ((er, re_, "estimate", fe is None), (re_, er, "reference", fr is None)):
         n_q = counts[who + "_used"]
         c = a["counters"]
         if c["dropped"] + c["matched"] + c["beyond"] != n_q:
             raise RuntimeError(f"cloud search: the counters of the {who}'s queries do not add up to {n_q}: {c}")
-        if n_q and len(b["d2"]) and c["dropped"] != b["ref_dropped"]:
+        if as_cloud and n_q and len(b["d2"]) and c["dropped"] != b["ref_dropped"]:     # a mesh is indexed as triangles
             raise RuntimeError(f"cloud search: {c['dropped']} of the {who}'s points dropped as queries, "
                                f"{b['ref_dropped']} as indexed points")
     d_er, d_re = np.sqrt(er["d2"]), np.sqrt(re_["d2"])
@@ -201,6 +367,11 @@ def compare_clouds(est, ref, thresholds: Sequence[float], max_dist: Optional[flo
            "settings": {"thresholds": ths, "max_dist": md, "voxel_size": None if voxel_size is None else float(voxel_size),
                         "transform": None if transform is None else [[float(x) for x in row] for row in M],
                         "cell": ops.CLOUD_CELL_FACTOR * md}}
+    if meshes:
+        out["settings"].update(mesh_sample_spacing=spacing, mesh_sample_seed=int(sample_seed))
+        for k, s_ in (("accuracy", er), ("completeness", re_)):
+            if "rows" in s_:
+                out["search"][k]["rows"] = s_["rows"]
     for t in ths:
         k = tau_key(t)
         p, rc = acc["within"][k], comp["within"][k]
@@ -380,6 +551,33 @@ def _refine_alignment(est0: torch.Tensor, e: torch.Tensor, r: torch.Tensor, T: O
     return res
 
 
+def _refine_mesh_alignment(e: torch.Tensor, fe: Optional[torch.Tensor], r: torch.Tensor, fr: Optional[torch.Tensor],
+                           T: Optional[np.ndarray], voxel_size: Optional[float], md: float, icp: Dict, sample: Callable,
+                           est0: torch.Tensor) -> Dict:
+    """compare_clouds' ICP step when a side is a mesh: the refinement runs on the query clouds, a mesh side's being its
+    surface samples with their face normals.  e: the estimate's points or vertices moved by T, est0: as given; sample:
+    (vertices, faces) -> _device_sampler's dict.  -> _refine_alignment's result."""
+    kw = dict(icp)
+    plane = kw.get("mode") == "plane"
+    qr = r
+    if fr is not None:
+        s = sample(r, fr)
+        qr = s["points"]
+        kw.pop("ref_normals", None)                      # given for the vertices: not the samples' rows
+        if plane:
+            kw["ref_normals"] = s["normals"]
+    if fe is None:
+        return _refine_alignment(est0, e, qr, T, voxel_size, md, kw)
+    s = sample(e, fe)                                    # drawn from the moved vertices: already in T's frame
+    kw.pop("est_normals", None)
+    if plane:
+        kw["est_normals"] = s["normals"]
+    res = _refine_alignment(s["points"], s["points"], qr, None, voxel_size, md, kw)
+    if T is not None:
+        res["transform"] = res["increment"] @ T
+    return res
+
+
 def public(result: Dict) -> Dict:
     """The result without its per-point arrays: what --json prints."""
     return {k: v for k, v in result.items() if not k.startswith("_")}
@@ -486,6 +684,90 @@ def read_ply_vertices(path: str) -> Dict:
     return {"points": pts, "colors": colors, "normals": normals}
 
 
+def _fan_triangles(polygons) -> np.ndarray:
+    """A list of index arrays (one polygon each) -> int64 (F,3): polygon (v0 .. vk-1) gives (v0, vi, vi+1), i = 1 ..
+    k-2; fewer than 3 corners give nothing."""
+    tris = [np.stack([np.full(len(p) - 2, p[0], np.int64), p[1:-1], p[2:]], 1) for p in polygons if len(p) >= 3]
+    return np.concatenate(tris) if tris else np.zeros((0, 3), np.int64)
+
+
+def read_ply_mesh(path: str) -> Dict:
+    """read_ply_vertices' dict with 'faces': int32 (F,3), or None for a file without a face element.  The face
+    element's list property is vertex_indices or vertex_index, with any integer count and index types, beside any scalar
+    properties; binary_little_endian or ascii; a polygon of more than 3 corners is fan-triangulated from its corner 0.
+    An index that does not fit int32 becomes -1 (no vertex: the kernels drop such a triangle).  The elements before the
+    faces must have a size known from the header (no list property).  Reads what export.write_mesh_ply writes."""
+    out = read_ply_vertices(path)
+    out["faces"] = None
+    with open(path, "rb") as f:
+        fmt, elements = _ply_header(f, path)
+        names = [e["name"] for e in elements]
+        if "face" not in names:
+            return out
+        fi = names.index("face")
+        face = elements[fi]
+        lists = [p for p in face["props"] if p[1] == "list"]
+        if len(lists) != 1 or lists[0][0] not in ("vertex_indices", "vertex_index") or \
+                lists[0][2][0] not in "iu" or lists[0][3][0] not in "iu":
+            raise ValueError(f"{path}: the face element needs one list property vertex_indices (or vertex_index) of "
+                             f"integer type, found {[p[0] for p in face['props']]}")
+        for e in elements[:fi]:
+            if any(p[1] == "list" for p in e["props"]) and e["count"]:
+                raise ValueError(f"{path}: element {e['name']} with a list property comes before the faces")
+        F = face["count"]
+        polygons = []
+        if fmt == "binary_little_endian":
+            for e in elements[:fi]:
+                f.seek(e["count"] * sum(np.dtype(p[1]).itemsize for p in e["props"]), os.SEEK_CUR)
+            raw = f.read()
+            ct, it = np.dtype("<" + lists[0][2]), np.dtype("<" + lists[0][3])
+            before = sum(np.dtype(p[1]).itemsize for p in face["props"][:face["props"].index(lists[0])])
+            if F and len(raw) >= before + ct.itemsize:           # every face with the first one's corner count: one view
+                k = int(np.frombuffer(raw, ct, 1, before)[0])
+                dt = np.dtype([x for p in face["props"] for x in
+                               ([("_n", ct), ("_v", it, (k,))] if p[1] == "list" else [("s_" + p[0], "<" + p[1])])])
+                if k >= 0 and len(raw) >= F * dt.itemsize:
+                    rec = np.frombuffer(raw, dt, F)
+                    if (rec["_n"] == k).all():
+                        polygons = None
+                        v = rec["_v"].astype(np.int64).reshape(F, k)
+                        tri = (np.stack([np.repeat(v[:, :1], k - 2, 1), v[:, 1:-1], v[:, 2:]], 2).reshape(-1, 3)
+                               if k >= 3 else np.zeros((0, 3), np.int64))
+            if polygons is not None:                             # mixed corner counts: face by face
+                at = 0
+                for _ in range(F):
+                    for p in face["props"]:
+                        if p[1] != "list":
+                            at += np.dtype(p[1]).itemsize
+                            continue
+                        if at + ct.itemsize > len(raw):
+                            raise ValueError(f"{path}: the file ends inside the faces")
+                        k = int(np.frombuffer(raw, ct, 1, at)[0])
+                        at += ct.itemsize
+                        if k < 0 or at + k * it.itemsize > len(raw):
+                            raise ValueError(f"{path}: the file ends inside the faces")
+                        polygons.append(np.frombuffer(raw, it, k, at).astype(np.int64))
+                        at += k * it.itemsize
+                tri = _fan_triangles(polygons)
+        else:
+            for e in elements[:fi]:
+                for _ in range(e["count"]):
+                    f.readline()
+            li = face["props"].index(lists[0])
+            for _ in range(F):
+                w = f.readline().split()
+                if len(w) <= li:
+                    raise ValueError(f"{path}: an ascii face line is too short (or the file ends early)")
+                k = int(w[li])
+                if k < 0 or len(w) < li + 1 + k:
+                    raise ValueError(f"{path}: an ascii face line announces {k} indices and holds fewer")
+                polygons.append(np.array(w[li + 1:li + 1 + k], dtype=np.int64))
+            tri = _fan_triangles(polygons)
+    tri = np.where((tri < -2 ** 31) | (tri >= 2 ** 31), -1, tri)
+    out["faces"] = np.ascontiguousarray(tri.astype(np.int32)).reshape(-1, 3)
+    return out
+
+
 # ------------------------------------------------------------------------------------------------------ alignment
 def _eval_ape():
     """tools/eval_ape.py (the association and the Umeyama alignment of `evo_ape -as`), imported, not restated."""
@@ -540,7 +822,13 @@ def format_table(res: Dict) -> str:
              f"reference {pts['reference']:>10d} points" + (f" -> {pts['reference_used']} voxels" if s["voxel_size"] else "")
              + f", {res['dropped']['reference']} dropped",
              f"search radius {s['max_dist']:g}" + (f", voxel size {s['voxel_size']:g}" if s["voxel_size"] else "")
-             + (", estimate transformed" if s["transform"] else ""), "",
+             + (", estimate transformed" if s["transform"] else "")]
+    for side in ("estimate", "reference"):
+        if side + "_faces" in pts:
+            lines.append(f"{side + ' mesh':<14s} {pts[side + '_faces']} faces, {pts[side + '_faces_dropped']} dropped, "
+                         f"{pts[side + '_samples']} samples at spacing {s['mesh_sample_spacing']:g} "
+                         f"(seed {s['mesh_sample_seed']})")
+    lines += ["",
              f"{'':<14s}{'matched':>10s}{'beyond':>10s}{'mean':>10s}{'median':>10s}{'rmse':>10s}{'p90':>10s}{'max':>10s}"]
     for name in ("accuracy", "completeness"):
         st = res[name]

@@ -937,6 +937,114 @@ def cloud_nearest(table: torch.Tensor, cells: torch.Tensor, inv_cell: float, que
     _L.check(rc, "pi3_cloud_nearest")
 
 
+# ---- nearest triangle of a mesh (csrc/mesh_nn.hip)
+MESH_INDEX_COUNTERS = ("dropped", "cells", "no_slot", "largest_cell", "rows")
+MESH_NEAREST_COUNTERS = ("dropped", "matched", "beyond", "evaluations")
+MESH_MAX_ROWS = 2 ** 31 - 1
+
+
+def _mesh_args(vertices: torch.Tensor, faces: torch.Tensor) -> Tuple[int, int]:
+    assert vertices.dtype == torch.float32 and vertices.is_contiguous() and vertices.ndim == 2 and vertices.shape[1] == 3
+    assert faces.dtype == torch.int32 and faces.is_contiguous() and faces.ndim == 2 and faces.shape[1] == 3
+    assert vertices.is_cuda and faces.device == vertices.device
+    return int(vertices.shape[0]), int(faces.shape[0])
+
+
+def mesh_index_count(vertices: torch.Tensor, faces: torch.Tensor, inv_cell: float, table: torch.Tensor,
+                     packed: torch.Tensor, max_rows: int, counters: torch.Tensor) -> None:
+    """vertices f32 (V,3), faces int32 (F,3) -> table int64 (8 capacity,) cleared and, unless the row total exceeds
+    max_rows, holding the rows per cell; packed f32 (F,12) = a, b, c, 2 spare, face index (-1 = dropped); counters
+    int64 (8,) = MESH_INDEX_COUNTERS + 3 spare (zeroed by the call; 'largest_cell' comes from the fill)."""
+    lib = _L.load()
+    V, F = _mesh_args(vertices, faces)
+    dev = vertices.device
+    assert table.dtype == torch.int64 and table.is_contiguous() and table.numel() % 8 == 0
+    assert packed.dtype == torch.float32 and packed.is_contiguous() and tuple(packed.shape) == (F, 12)
+    assert counters.dtype == torch.int64 and counters.is_contiguous() and counters.numel() >= 8
+    assert table.device == dev and packed.device == dev and counters.device == dev
+    rc = lib.pi3_mesh_index_count(vertices.data_ptr() if V else None, V, faces.data_ptr() if F else None, F,
+                                  float(inv_cell), table.data_ptr(), table.numel() // 8, packed.data_ptr() if F else None,
+                                  int(max_rows), counters.data_ptr(), _L.stream_ptr())
+    _L.check(rc, "pi3_mesh_index_count")
+
+
+def mesh_index_fill(table: torch.Tensor, packed: torch.Tensor, inv_cell: float, rows: torch.Tensor,
+                    counters: torch.Tensor) -> None:
+    """After mesh_index_count with the same table, packed and inv_cell: rows int32 (counters['rows'],) = the face
+    indices grouped by cell; counters (the count call's) gains 'largest_cell'."""
+    lib = _L.load()
+    dev = table.device
+    assert table.dtype == torch.int64 and table.is_contiguous() and table.numel() % 8 == 0 and table.is_cuda
+    assert packed.dtype == torch.float32 and packed.is_contiguous() and packed.ndim == 2 and packed.shape[1] == 12
+    assert rows.dtype == torch.int32 and rows.is_contiguous() and rows.ndim == 1
+    assert counters.dtype == torch.int64 and counters.is_contiguous() and counters.numel() >= 8
+    assert packed.device == dev and rows.device == dev and counters.device == dev
+    F, n = int(packed.shape[0]), int(rows.numel())
+    rc = lib.pi3_mesh_index_fill(table.data_ptr(), table.numel() // 8, packed.data_ptr() if F else None, F,
+                                 float(inv_cell), rows.data_ptr() if n else None, n, counters.data_ptr(), _L.stream_ptr())
+    _L.check(rc, "pi3_mesh_index_fill")
+
+
+def mesh_nearest(table: torch.Tensor, rows: torch.Tensor, packed: torch.Tensor, inv_cell: float, queries: torch.Tensor,
+                 max_dist: float, d2: torch.Tensor, face: torch.Tensor, closest: torch.Tensor,
+                 counters: torch.Tensor) -> None:
+    """queries f32 (m,3) against the index of mesh_index_count / mesh_index_fill: d2 f64 (m,) to the nearest triangle
+    within max_dist (inclusive; ties: the smallest face index), face int32 (m,), closest f32 (m,3) the point of that
+    triangle; +inf / -1 / 0 without one; counters int64 (4,) = MESH_NEAREST_COUNTERS (zeroed by the call)."""
+    lib = _L.load()
+    dev = table.device
+    assert table.dtype == torch.int64 and table.is_contiguous() and table.numel() % 8 == 0 and table.is_cuda
+    assert rows.dtype == torch.int32 and rows.is_contiguous() and rows.ndim == 1
+    assert packed.dtype == torch.float32 and packed.is_contiguous() and packed.ndim == 2 and packed.shape[1] == 12
+    assert queries.dtype == torch.float32 and queries.is_contiguous() and queries.ndim == 2 and queries.shape[1] == 3
+    F, n, m = int(packed.shape[0]), int(rows.numel()), int(queries.shape[0])
+    assert d2.dtype == torch.float64 and d2.is_contiguous() and d2.numel() == m
+    assert face.dtype == torch.int32 and face.is_contiguous() and face.numel() == m
+    assert closest.dtype == torch.float32 and closest.is_contiguous() and tuple(closest.shape) == (m, 3)
+    assert counters.dtype == torch.int64 and counters.is_contiguous() and counters.numel() >= 4
+    assert all(t.device == dev for t in (rows, packed, queries, d2, face, closest, counters))
+    rc = lib.pi3_mesh_nearest(table.data_ptr(), table.numel() // 8, rows.data_ptr() if n else None, n,
+                              packed.data_ptr() if F else None, F, float(inv_cell), queries.data_ptr() if m else None, m,
+                              float(max_dist), d2.data_ptr() if m else None, face.data_ptr() if m else None,
+                              closest.data_ptr() if m else None, counters.data_ptr(), _L.stream_ptr())
+    _L.check(rc, "pi3_mesh_nearest")
+
+
+# ---- area-weighted samples of a mesh's surface (csrc/mesh_sample.hip)
+def mesh_sample_counts(vertices: torch.Tensor, faces: torch.Tensor, spacing: float, seed: int, counts: torch.Tensor,
+                       counters: torch.Tensor) -> None:
+    """counts int64 (F,) = samples per face at one per spacing^2 of area on average (0 for a dropped face); counters
+    int64 (4,) = dropped faces + 3 spare (zeroed by the call)."""
+    lib = _L.load()
+    V, F = _mesh_args(vertices, faces)
+    dev = vertices.device
+    assert counts.dtype == torch.int64 and counts.is_contiguous() and counts.numel() == F and counts.device == dev
+    assert counters.dtype == torch.int64 and counters.is_contiguous() and counters.numel() >= 4 and counters.device == dev
+    rc = lib.pi3_mesh_sample_counts(vertices.data_ptr() if V else None, V, faces.data_ptr() if F else None, F,
+                                    float(spacing), int(seed) & (2 ** 64 - 1), counts.data_ptr() if F else None,
+                                    counters.data_ptr(), _L.stream_ptr())
+    _L.check(rc, "pi3_mesh_sample_counts")
+
+
+def mesh_sample_points(vertices: torch.Tensor, faces: torch.Tensor, offsets: torch.Tensor, seed: int,
+                       points: torch.Tensor, face: torch.Tensor, normals: torch.Tensor) -> None:
+    """offsets int64 (F+1,) = the exclusive prefix sums of mesh_sample_counts' counts -> points f32 (n,3), face int32
+    (n,), normals f32 (n,3) with n = points.shape[0] = offsets[F]."""
+    lib = _L.load()
+    V, F = _mesh_args(vertices, faces)
+    dev = vertices.device
+    n = int(points.shape[0])
+    assert offsets.dtype == torch.int64 and offsets.is_contiguous() and offsets.numel() == F + 1 and offsets.device == dev
+    assert points.dtype == torch.float32 and points.is_contiguous() and tuple(points.shape) == (n, 3)
+    assert normals.dtype == torch.float32 and normals.is_contiguous() and tuple(normals.shape) == (n, 3)
+    assert face.dtype == torch.int32 and face.is_contiguous() and face.numel() == n
+    assert points.device == dev and normals.device == dev and face.device == dev
+    rc = lib.pi3_mesh_sample_points(vertices.data_ptr() if V else None, V, faces.data_ptr(), F, offsets.data_ptr(), n,
+                                    int(seed) & (2 ** 64 - 1), points.data_ptr() if n else None,
+                                    face.data_ptr() if n else None, normals.data_ptr() if n else None, _L.stream_ptr())
+    _L.check(rc, "pi3_mesh_sample_points")
+
+
 # ---- the normal equations of one ICP step from a search's pairs (csrc/cloud_icp.hip)
 CLOUD_ICP_COUNTERS = ("used", "unmatched", "trimmed", "normal_rejected")
 CLOUD_ICP_SPAN = 4096       # queries per workgroup = per row of partials (kSpan of the kernel)

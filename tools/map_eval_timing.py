@@ -4,6 +4,7 @@ dense map's cleaning and carving flags on the synthetic room.  Needs the GPU.
     python tools/map_eval_timing.py --timing      # build / query time at 1 M x 1 M and 4 M x 4 M reference_cloud points
     python tools/map_eval_timing.py --example     # F-score of the plain, cleaned, carved and carved + cleaned map
     python tools/map_eval_timing.py --icp         # the ICP reduction (csrc/cloud_icp.hip) beside the search, 1 M x 1 M
+    python tools/map_eval_timing.py --mesh        # the triangle search (csrc/mesh_nn.hip) and the sampler, 1 M queries
 
 --timing: cloud A = reference_cloud(frame_step=2, pixel_stride=2), cloud B = reference_cloud(frame_step=1,
 pixel_stride=4) of the 1 000-frame chess-room sequence, n random points of each (in frame order, and shuffled), index
@@ -12,7 +13,12 @@ A, query B, max_dist = 4 voxels of 2 cm; hip events around the ops calls, median
 --dense-min-views 2, depth keyframes every 2nd frame at stride 2) and OfflineReconstructor without bundle adjustment;
 dense_points.ply against reference_cloud() after the trajectory pair's alignment, both resampled at 2 cm.
 --icp: the clouds and the search of --timing at n = m = 1 M (and 4 M) in frame order, then ops.cloud_pair_equations on
-the search's idx / d2 in each normals_of mode (random normals; mode 2 with a rotation), timed the same way."""
+the search's idx / d2 in each normals_of mode (random normals; mode 2 with a rotation), timed the same way.
+--mesh: the planted room of tests/cloud_icp_ref.py (4 x 3 x 2.5 m with a cabinet).  Mesh 1: surface nets (MapMesher) of
+4 M of its points with their normals fused at 1.1 cm voxels, about 1 M triangles; mesh 2: the same room as 22 wall-sized
+triangles (tests/test_mesh_eval.py: room_mesh).  Queries: 1 M further points of the room with 5 mm Gaussian noise, in
+sampling order.  max_dist as above; count + fill (with the host's read between them), the search, and the sampler at
+one sample per (1 cm)^2 timed with hip events, median and minimum of 5 after one warm-up."""
 from __future__ import annotations
 
 import argparse
@@ -118,6 +124,56 @@ def icp_timing(dev):
         del table, cells, d2, idx, p, q, normals, partials
 
 
+def mesh_timing(dev):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import cloud_icp_ref as icpref
+    from test_mesh_eval import room_mesh
+    from pi3_slam_amd import map_eval, ops
+    from pi3_slam_amd.dense_map import MapMesher, NormalAccumulator, VoxelFuser
+    rng = np.random.default_rng(3)
+    pts, nrm = icpref.sample_room(4_000_000, rng)
+    P, N = torch.from_numpy(pts.astype(np.float32)).to(dev), torch.from_numpy(nrm.astype(np.float32)).to(dev)
+    fz = VoxelFuser(0.011, dev)
+    fz.reserve(len(P))
+    fz.fuse_points(P, None, None)
+    acc = NormalAccumulator(fz)
+    acc.clear()
+    acc.add_points(P, N, torch.ones(len(P), dtype=torch.int32, device=dev),
+                   torch.eye(3, dtype=torch.float64, device=dev).reshape(9).contiguous())
+    mesher = MapMesher()
+    nets = mesher.apply(fz, acc)
+    print(f"surface nets: {mesher.summary()}", flush=True)
+    del fz, acc, P, N
+    q = icpref.sample_room(1_000_000, rng)[0] + 0.005 * rng.standard_normal((1_000_000, 3))
+    q = torch.from_numpy(q.astype(np.float32)).to(dev)
+    wall_v, wall_f = room_mesh()
+    for name, v, f in (("surface nets", nets["vertices"], nets["faces"]), ("22 triangles", wall_v, wall_f)):
+        v, f = torch.from_numpy(np.ascontiguousarray(v)).to(dev), torch.from_numpy(np.ascontiguousarray(f)).to(dev)
+        holder = {}
+
+        def build():
+            holder["index"] = map_eval.MeshIndex(v, f, MAX_DIST, dev)
+        tb = timed(build)
+        index = holder["index"]
+        m = len(q)
+        d2 = torch.empty(m, dtype=torch.float64, device=dev)
+        face = torch.empty(m, dtype=torch.int32, device=dev)
+        closest = torch.empty((m, 3), dtype=torch.float32, device=dev)
+        cq = torch.zeros(4, dtype=torch.int64, device=dev)
+        tq = timed(lambda: ops.mesh_nearest(index.table, index.rows, index.packed, index.inv_cell, q, MAX_DIST, d2, face,
+                                            closest, cq))
+        ts = timed(lambda: map_eval.sample_surface(v, f, 0.01, 0, dev))
+        samples = int(map_eval.sample_surface(v, f, 0.01, 0, dev)[0].shape[0])
+        bs, qs = index.build_stats, dict(zip(ops.MESH_NEAREST_COUNTERS, cq.tolist()))
+        kept = max(bs["faces"] - bs["dropped"], 1)
+        print(json.dumps(dict(mesh=name, faces=bs["faces"], queries=m, max_dist=MAX_DIST, build_ms_median=tb[0],
+                              build_ms_min=tb[1], query_ms_median=tq[0], query_ms_min=tq[1], sample_ms_median=ts[0],
+                              sample_ms_min=ts[1], samples=samples, build=bs, query=qs, rows_per_triangle=bs["rows"] / kept,
+                              evaluations_per_query=qs["evaluations"] / m,
+                              mean_distance_mm=float(d2[torch.isfinite(d2)].sqrt().mean()) * 1e3)), flush=True)
+        del index, holder
+
+
 def items(seq, dev):
     for c, (a, b) in enumerate(seq.chunks):
         yield {"frames": seq.frames(c, dev), "kind": "float", "paths": [seq.frame_name(i) for i in range(a, b)],
@@ -159,14 +215,17 @@ def main(argv=None) -> int:
     ap.add_argument("--timing", action="store_true")
     ap.add_argument("--example", action="store_true")
     ap.add_argument("--icp", action="store_true")
+    ap.add_argument("--mesh", action="store_true")
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args(argv)
-    if not (a.timing or a.example or a.icp):
-        ap.error("give --timing, --example and / or --icp")
+    if not (a.timing or a.example or a.icp or a.mesh):
+        ap.error("give --timing, --example, --icp and / or --mesh")
     if a.timing:
         timing(a.device)
     if a.icp:
         icp_timing(a.device)
+    if a.mesh:
+        mesh_timing(a.device)
     if a.example:
         example(a.device)
     return 0

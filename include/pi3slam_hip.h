@@ -478,6 +478,33 @@ int pi3_voxel_carve(const void* table, long capacity, double voxel_size, const d
                     int min_conflicts, unsigned char* carved, unsigned* agree, unsigned* conflict,
                     unsigned long long* counters, void* stream);
 
+/* ---- moving a chunk's dense cloud with the views that saw it (csrc/cloud_follow.hip): one blend of per-view moves per
+ * point, f64 without contraction, every product and sum rounded on its own in the order written.
+ *   points f32 [P][3], normals f32 [P][3] or NULL;  views f64 [M][20] in pi3_voxel_carve's layout (rigid frame->camera
+ *   3x4 row-major, fx, fy, cx, cy, 0, views[m][17] = the unit of plane m in the points' units);  moves f64 [M][12]: D_m,
+ *   3x4 row-major;  planes fp16 bits [M][Hp][Wp] (pi3_dense_depth_planes), S = pixel_stride in {1, 2, 4}.
+ *   Per point X = (x, y, z) widened to f64.  X not finite: the outputs are the inputs, level 0, support 0, counters[0].
+ *   Else for m = 0 .. M-1 in order, d = moves[m]:
+ *     Y = (((d0 x + d1 y) + d2 z) + d3, ((d4 x + d5 y) + d6 z) + d7, ((d8 x + d9 y) + d10 z) + d11);
+ *     Nn = ((d0 nx + d1 ny) + d2 nz, (d4 nx + d5 ny) + d6 nz, (d8 nx + d9 ny) + d10 nz);
+ *     level 3 takes every view:  S3 += Y, N3 += Nn;
+ *     xc, yc, zc, u, v, pu, pv as pi3_voxel_carve forms them;  next view unless zc > 0, xc yc zc finite and
+ *     0 <= pu <= Wp - 1, 0 <= pv <= Hp - 1;
+ *     w = 1.0 / (zc zc);  level 2:  S2 += w Y, W2 += w, N2 += w Nn, ++n2;
+ *     zo = views[m][17] (double)plane[m][pv][pu];  next view when zo is 0 or not finite;
+ *     |zc - zo| <= rel_tol zo + margin:  level 1:  S1 += w Y, W1 += w, N1 += w Nn, ++n1;
+ *   level uint8 [P] (or NULL) = 1 when n1 > 0, else 2 when n2 > 0, else 3;  support int32 [P] (or NULL) = n1;
+ *   out_points f32 [P][3] = S_l / W_l per component (level 3: S3 / (double)M);  out_normals f32 [P][3] = N_l /
+ *   sqrt((Nx Nx + Ny Ny) + Nz Nz) when that sum is positive and finite, else 0.  out_points may be points, out_normals
+ *   may be normals; normals and out_normals are both given or both NULL.
+ *   counters: DEVICE uint64 [4] = points not finite, points of level 1, 2, 3; zeroed by the call.
+ * M >= 1, rel_tol finite and > 0, margin finite and >= 0, 0 <= P < 2^39.  P == 0 zeroes the counters and launches no
+ * kernel; points and out_points may then be NULL. */
+int pi3_cloud_follow_views(const float* points, const float* normals, long P, const double* views, const double* moves,
+                           int M, const unsigned short* planes, int Hp, int Wp, int pixel_stride, double rel_tol,
+                           double margin, float* out_points, float* out_normals, unsigned char* level, int* support,
+                           unsigned long long* counters, void* stream);
+
 /* ---- nearest neighbours between two point clouds (csrc/cloud_nn.hip): an exact radius-bounded search through a
  * uniform grid of cells, for scoring a map against a reference cloud (map_eval.py).  The grid is a hash table of cells
  * in the voxel table's form: `capacity` slots of 64 B (a power of two, at least 2 n: ops.voxel_capacity), keyed by the

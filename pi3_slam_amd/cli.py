@@ -120,7 +120,14 @@ RECON_FLAGS: Sequence[Tuple[str, Dict]] = (
                                                          "color_<frame>.png of the dense map for every N-th view")),
     ("--render-min-weight", dict(type=int, default=1, help="voxels below this fused weight are not drawn")),
     ("--render-splat-scale", dict(type=float, default=1.0, help="half-width of a drawn voxel in voxel sizes")),
+    ("--map-follow-tolerance", dict(type=float, default=0.03, help="with --map-follow-poses: relative depth difference "
+                                                                   "(plus one voxel size) within which a keyframe saw a "
+                                                                   "point of its chunk's cloud")),
 )
+MAP_FOLLOW_SWITCH = ("--map-follow-poses", "the dense map follows the bundle-adjusted poses: every point of a chunk's cloud "
+                                           "moves with the depth keyframes of its chunk that saw it, each from the pose it "
+                                           "was created with to its final pose (needs chunks created with "
+                                           "--dense-depth-every; chunks without keyframes keep their similarity)")
 RECON_SWITCHES = (("--save-per-chunk", "per-chunk ply files as well"),
                   ("--render-overview", "write renders/overview.png: the dense map from above with the trajectory in red"),
                   ("--use-inverse-depth", "one inverse depth per track along its reference keypoint's ray in both bundle "
@@ -131,7 +138,8 @@ RECON_SWITCHES = (("--save-per-chunk", "per-chunk ply files as well"),
                                          "utils/reconstruction_alignment.py:107-171)"),
                   ("--no-ba-sanity-gate", "apply every bundle adjustment that ends without a numerical failure, as the "
                                           "reference does (default: keep the input when fewer than 3 tracks survive or a "
-                                          "camera moved by more than the scene extent)"))
+                                          "camera moved by more than the scene extent)"),
+                  MAP_FOLLOW_SWITCH)
 
 
 # pi3_slam_online_modular.py:117-183: same names (underscores), types and defaults; the reference's personal default paths
@@ -169,6 +177,9 @@ ONLINE_FLAGS: Sequence[Tuple[str, Dict]] = (
 # pixel test's threshold
 ONLINE_DENSE_FLAGS = underscored([row for row in tuple(DENSE_CHUNK_FLAGS) + tuple(DENSE_MAP_FLAGS)
                                   if row[0] not in ("--dense-voxel-size", "--dense-conf-threshold")])
+# the two map-follow options of reconstruct, respelled
+ONLINE_FOLLOW_FLAGS = underscored([row for row in RECON_FLAGS if row[0] == "--map-follow-tolerance"])
+ONLINE_FOLLOW_SWITCH = underscored([(MAP_FOLLOW_SWITCH[0], dict(help=MAP_FOLLOW_SWITCH[1]))])[0]
 ONLINE_SWITCHES = (("--save_chunk_reconstructions", "save each chunk reconstruction to disk"),
                    ("--save_transformed_reconstructions", "save transformed reconstructions as PLY files"),
                    ("--save_debug_reconstructions", "accepted for compatibility"),
@@ -180,7 +191,8 @@ ONLINE_SWITCHES = (("--save_chunk_reconstructions", "save each chunk reconstruct
                    ("--tum_integer_timestamp", "integer timestamps in the TUM file (7-Scenes)"),
                    ("--no_bundle_adjust", "closed-form Sim(3) chain only"),
                    ("--no_hip_graph", "plain kernel launches instead of the captured per-chunk graph"),
-                   ("--reuse_overlap_encoder", "overlap frames take their encoder output from the previous chunk"))
+                   ("--reuse_overlap_encoder", "overlap frames take their encoder output from the previous chunk"),
+                   (ONLINE_FOLLOW_SWITCH[0], ONLINE_FOLLOW_SWITCH[1]["help"]))
 
 # evaluate-map: this build's own sub-command (map_eval.py), no counterpart in the reference
 EVAL_FLAGS: Sequence[Tuple[str, Dict]] = (
@@ -235,7 +247,8 @@ def build_parser() -> argparse.ArgumentParser:
     sub = top.add_subparsers(dest="command", required=True)
     for name, flags, switches in (("create", tuple(CREATE_FLAGS) + tuple(DENSE_CHUNK_FLAGS), CREATE_SWITCHES),
                                   ("reconstruct", tuple(RECON_FLAGS) + tuple(DENSE_MAP_FLAGS), RECON_SWITCHES),
-                                  ("online", tuple(ONLINE_FLAGS) + ONLINE_DENSE_FLAGS, ONLINE_SWITCHES),
+                                  ("online", tuple(ONLINE_FLAGS) + ONLINE_DENSE_FLAGS + ONLINE_FOLLOW_FLAGS,
+                                   ONLINE_SWITCHES),
                                   ("evaluate-map", EVAL_FLAGS, EVAL_SWITCHES)):
         p = sub.add_parser(name)
         for flag, kw in flags:
@@ -282,7 +295,8 @@ def run_reconstruct(a: argparse.Namespace) -> None:
                          save_observations=a.save_observations, bundle_adjust=not a.no_bundle_adjust,
                          ba_sanity_gate=not a.no_ba_sanity_gate, render_every=a.render_every,
                          render_overview=a.render_overview, render_min_weight=a.render_min_weight,
-                         render_splat_scale=a.render_splat_scale,
+                         render_splat_scale=a.render_splat_scale, map_follow_poses=a.map_follow_poses,
+                         map_follow_tolerance=a.map_follow_tolerance,
                          **{name: getattr(a, name) for name in option_names(DENSE_MAP_FLAGS)}).run()
 
 
@@ -324,6 +338,7 @@ def run_online(a: argparse.Namespace) -> None:
         use_inverse_depth=a.use_inverse_depth, moge_model_path=a.moge_model_path, hip_graph=not a.no_hip_graph,
         output_dir=out_dir, num_loader_workers=a.num_workers, bundle_adjust=not a.no_bundle_adjust,
         reuse_overlap_encoder=a.reuse_overlap_encoder, dense_voxel_size=a.dense_voxel_size,
+        map_follow_poses=a.map_follow_poses, map_follow_tolerance=a.map_follow_tolerance,
         # --dense_mesh is no option of the object: it asks for save_dense_mesh() below
         **{name: getattr(a, name) for name in option_names(ONLINE_DENSE_FLAGS) if name != "dense_mesh"})
     slam.save_transformed_reconstructions = a.save_transformed_reconstructions

@@ -28,7 +28,10 @@ voxels' centroids and normals, surface nets on the table's lattice -> dense_mesh
 
 The accumulators are integers, so a map is bitwise reproducible and tests/dense_map_ref.py reproduces it bit for bit
 (tests/dense_normals_ref.py the normals, tests/dense_mesh_ref.py the mesh).
-Limitation: a cloud follows its chunk's similarity; per-view corrections of a bundle adjustment do not reach it.
+Optionally (MapFollower, csrc/cloud_follow.hip; map_follow_poses) stage 2 moves a cloud not by its chunk's similarity but
+point by point with the depth keyframes that saw the point, each by the move from its created to its final pose: the map
+then follows the per-view corrections of a bundle adjustment (tests/dense_follow_ref.py reproduces it byte for byte).
+Limitation without it: a cloud follows its chunk's similarity; per-view corrections of a bundle adjustment do not reach it.
 """
 from __future__ import annotations
 
@@ -273,8 +276,8 @@ class MapCarver:
     min_conflicts has no default: it switches the feature on (3 is a starting point, not a measured optimum).
 
     Limitations: a view sits where its chunk's similarity puts it, so with bundle adjustment on the carving is as
-    misplaced as the map (use it without); a surface only ever seen from one side by one pass has nobody to contradict
-    it; the planes are nearest-sampled, not interpolated."""
+    misplaced as the map (use it without, or with a MapFollower); a surface only ever seen from one side by one pass
+    has nobody to contradict it; the planes are nearest-sampled, not interpolated."""
     min_conflicts: int
     rel_tol: float = 0.03
 
@@ -370,6 +373,123 @@ class MapCarver:
         st = self.last_stats
         return (f"{st['views']} views, {st['carved']} of {st['voxels']} voxels carved (conflicts >= {self.min_conflicts}), "
                 f"{st['unvoted']} voxels no view voted on")
+
+
+def _scaled_rotations(poses: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """cam->frame poses (M,4,4) f64 -> (R (M,3,3): the 3x3 blocks with their scale divided out as render.pack_cameras
+    does, c (M,3): the centres)."""
+    A = poses[:, :3, :3]
+    det = np.linalg.det(A)
+    if not np.all(np.isfinite(det)) or np.any(det <= 0.0):
+        raise ValueError("a pose's 3x3 block is not a scaled rotation (determinant <= 0 or not finite)")
+    return A / np.cbrt(det)[:, None, None], poses[:, :3, 3]
+
+
+@dataclass
+class MapFollower:
+    """Move a chunk's dense cloud with the views that saw it (csrc/cloud_follow.hip; f64, reproduced byte for byte by
+    tests/dense_follow_ref.py), so that the map follows a bundle adjustment that moved the chunk's views one by one.
+
+    A cloud, the chunk file's camera_poses (kept as '_poses_created' by stage 2 when this is on) and its `dense_depth`
+    keyframes share the chunk file's frame.  Keyframe m of the chunk has the move
+        D_m = P_final_m . diag(s, s, s, 1) . P_created_m^-1
+    (s the chunk's depth scale, MapCarver.chunk_views' slot 17): it takes a point of the cloud to where that view's
+    pixels ended up.  A point is projected into every keyframe at its created pose with the carver's arithmetic; it is
+    moved by the mean, weighted by 1 / zc^2, of D_m X over the keyframes whose depth agrees with it (|zc - zo| <= rel_tol
+    zo + margin: level 1), else over the keyframes it projects into (level 2), else by the plain mean over all of the
+    chunk's keyframes (level 3).  The normals are moved by the same blend of the moves' 3x3 parts and normalised.
+
+    margin is MARGIN_VOXELS of the cloud's own voxel size and rel_tol the carver's tolerance, with the same meaning.
+    A chunk without depth keyframes (dense_depth_every) or without created poses keeps its similarity.
+
+    Limitations: only keyframes vote, a view between two of them moves nothing; the blend is linear in the moved points,
+    not in the motions; a level-3 point follows the chunk's mean move; the keyframes' planes themselves are not moved."""
+    rel_tol: float = 0.03
+
+    MARGIN_VOXELS = 1.0         # the absolute part of the tolerance, in voxel sizes of the cloud
+
+    def __post_init__(self):
+        self.rel_tol = float(self.rel_tol)
+        if not (self.rel_tol > 0.0 and math.isfinite(self.rel_tol)):
+            raise ValueError(f"rel_tol must be a positive finite number, got {self.rel_tol!r}")
+        self.last_stats: Dict[str, int] = {}
+        self.begin()
+
+    @classmethod
+    def from_options(cls, follow: bool = False, rel_tol: float = 0.03) -> Optional["MapFollower"]:
+        """The follower the map_follow_poses / map_follow_tolerance options ask for; None without the first (the
+        tolerance alone asks for nothing)."""
+        return cls(rel_tol) if follow else None
+
+    def settings(self) -> Dict:
+        return {"rel_tol": self.rel_tol}
+
+    def begin(self) -> None:
+        """Zero last_stats: fuse_chunks calls this before the first cloud."""
+        self.last_stats = dict.fromkeys(("chunks_followed", "chunks_fallen_back", "points", "dropped", "level1",
+                                         "level2", "level3"), 0)
+
+    @staticmethod
+    def chunk_moves(chunk: Dict) -> Optional[Tuple[np.ndarray, np.ndarray, torch.Tensor, int]]:
+        """-> (views f64 (M,20): render.pack_cameras' rows of the chunk's CREATED poses at its keyframes with the
+        planes' own intrinsics, [17] = 1 (cloud and planes share a unit); moves f64 (M,12): D_m; planes fp16 (M,H',W')
+        on the host; the pixel stride).  None when the chunk has no `dense_depth` with at least one keyframe or no
+        '_poses_created'.  With (Rt_o, t_o) the rigid frame->camera of the created pose and (R_f, c_f) the rotation
+        and centre of the final camera_poses (a scale in a 3x3 block is divided out): D = [s R_f Rt_o | s R_f t_o + c_f]."""
+        from .render import pack_cameras
+        dd, created = chunk.get("dense_depth"), chunk.get("_poses_created")
+        if dd is None or created is None:
+            return None
+        frames = np.asarray(torch.as_tensor(dd["frames"]).numpy(), np.int64)
+        if len(frames) == 0:
+            return None
+        f = np.asarray(torch.as_tensor(dd["fxfycxcy"]).numpy(), np.float64).reshape(-1, 4)
+        K = np.zeros((len(frames), 3, 3))
+        K[:, 0, 0], K[:, 1, 1], K[:, 0, 2], K[:, 1, 2], K[:, 2, 2] = f[:, 0], f[:, 1], f[:, 2], f[:, 3], 1.0
+        views = pack_cameras(torch.as_tensor(created).double().numpy().reshape(-1, 4, 4)[frames], K)
+        views[:, ops.CARVE_DEPTH_SCALE_AT] = 1.0
+        det = float(np.linalg.det(chunk_transform(chunk).numpy()[:3, :3]))
+        if not (math.isfinite(det) and det > 0.0):
+            raise ValueError(f"a chunk's transform is not a similarity (determinant {det!r} of its 3x3 block)")
+        s = float(np.cbrt(det))
+        rigid = views[:, :12].reshape(-1, 3, 4)
+        Rf, cf = _scaled_rotations(torch.as_tensor(chunk["camera_poses"]).double().numpy().reshape(-1, 4, 4)[frames])
+        sR = s * Rf
+        moves = np.zeros((len(frames), 3, 4))
+        moves[:, :, :3] = np.einsum("mij,mjk->mik", sR, rigid[:, :, :3])
+        moves[:, :, 3] = np.einsum("mij,mj->mi", sR, rigid[:, :, 3]) + cf
+        planes = torch.as_tensor(dd["depth"]).to(torch.float16).contiguous()
+        return views, moves.reshape(-1, ops.FOLLOW_MOVE_DOUBLES), planes, int(dd["pixel_stride"])
+
+    def apply(self, chunk: Dict, points_dev: torch.Tensor, normals_dev: Optional[torch.Tensor] = None
+              ) -> Optional[Tuple[torch.Tensor, Optional[torch.Tensor]]]:
+        """The chunk's cloud points f32 (P,3) on the device (overwritten) and its normals f32 (P,3) or None -> (the moved
+        points, the moved normals or None) in the world frame; None, with chunks_fallen_back counted, when chunk_moves
+        gives nothing for the chunk.  Adds to last_stats."""
+        st = self.last_stats
+        got = self.chunk_moves(chunk)
+        if got is None:
+            st["chunks_fallen_back"] += 1
+            return None
+        views, moves, planes, stride = got
+        dev = points_dev.device
+        out_n = None if normals_dev is None else torch.empty_like(normals_dev)
+        counters = torch.zeros(4, dtype=torch.int64, device=dev)
+        ops.cloud_follow_views(points_dev, normals_dev, upload(torch.from_numpy(views), dev).contiguous(),
+                               upload(torch.from_numpy(moves), dev).contiguous(), upload(planes, dev).contiguous(),
+                               stride, self.rel_tol, self.MARGIN_VOXELS * float(chunk["dense_cloud"]["voxel_size"]),
+                               points_dev, out_n, None, None, counters)
+        st["chunks_followed"] += 1
+        st["points"] += int(points_dev.shape[0])
+        for k, v in zip(ops.CLOUD_FOLLOW_COUNTERS, counters.tolist()):
+            st[k] += int(v)
+        return points_dev, out_n
+
+    def summary(self) -> str:
+        st = self.last_stats
+        return (f"{st['chunks_followed']} clouds follow their keyframes ({st['chunks_fallen_back']} keep their "
+                f"similarity): of {st['points']} points {st['level1']} follow views that agree in depth, {st['level2']} "
+                f"views that see them, {st['level3']} the chunk's mean move, {st['dropped']} are not finite")
 
 
 class VoxelFuser:
@@ -835,11 +955,14 @@ class DenseMap:
     mesh_error: Optional[Exception] = None      # why a mesh that was asked for is missing; its consumer raises it
 
 
-def _fuse_clouds(clouds, voxel_size: float, device: torch.device) -> Tuple[VoxelFuser, Optional[NormalAccumulator]]:
+def _fuse_clouds(clouds, voxel_size: float, device: torch.device, follower: Optional[MapFollower] = None,
+                 owners=None) -> Tuple[VoxelFuser, Optional[NormalAccumulator]]:
     """clouds: (dense_cloud, chunk_transform) pairs.  Every cloud is moved by its similarity and fused, weighted by its
     voxel weights -> (the table, its normal sums).  Normals: when every cloud carries `normals`, each cloud's are rotated
     by its similarity's rotation and fused weighted by its `normal_weights`; when only some do, one line says so and
-    there are no sums."""
+    there are no sums.  follower (with owners, the clouds' chunks): a cloud whose chunk it can follow is moved by it
+    instead, normals included (they arrive in the world frame: the identity is their rotation); one line counts the
+    clouds that keep their similarity."""
     fuser = VoxelFuser(voxel_size, device)
     fuser.reserve(sum(int(cl["points"].shape[0]) for cl, _ in clouds))
     with_normals = sum(1 for cl, _ in clouds if cl.get("normals") is not None)
@@ -849,10 +972,25 @@ def _fuse_clouds(clouds, voxel_size: float, device: torch.device) -> Tuple[Voxel
         acc.clear()
     elif with_normals:
         print(f"   ℹ️  Only {with_normals} of {len(clouds)} dense clouds carry normals: the dense map has none")
-    for cl, G in clouds:
+    if follower is not None:
+        follower.begin()
+    for (cl, G), owner in zip(clouds, owners if follower is not None else [None] * len(clouds)):
         if int(cl["points"].shape[0]) == 0:
             continue
         pts = fresh_upload(torch.as_tensor(cl["points"]).reshape(-1, 3), device, torch.float32)
+        if follower is not None:
+            nrm = None
+            if acc is not None:
+                nrm = upload(torch.as_tensor(cl["normals"]).reshape(-1, 3), device).to(torch.float32).contiguous()
+            moved = follower.apply(owner, pts, nrm)
+            if moved is not None:
+                cols = upload(torch.as_tensor(cl["colors"]).reshape(-1, 3), device).contiguous()
+                w = upload(torch.as_tensor(cl["weights"]).reshape(-1), device).contiguous()
+                fuser.fuse_points(moved[0], cols, w)
+                if acc is not None:
+                    nw = upload(torch.as_tensor(cl["normal_weights"]).reshape(-1), device).to(torch.int32).contiguous()
+                    acc.add_points(moved[0], moved[1], nw, upload(torch.eye(3, dtype=torch.float64).reshape(9), device))
+                continue
         ops.sim3_apply(upload(G.reshape(16).contiguous(), device).contiguous(), pts, None)
         cols = upload(torch.as_tensor(cl["colors"]).reshape(-1, 3), device).contiguous()
         w = upload(torch.as_tensor(cl["weights"]).reshape(-1), device).contiguous()
@@ -862,6 +1000,14 @@ def _fuse_clouds(clouds, voxel_size: float, device: torch.device) -> Tuple[Voxel
             nw = upload(torch.as_tensor(cl["normal_weights"]).reshape(-1), device).to(torch.int32).contiguous()
             rot = upload(torch.from_numpy(similarity_rotation(G).reshape(9).copy()), device).contiguous()
             acc.add_points(pts, nrm, nw, rot)
+    if follower is not None:
+        st = follower.last_stats
+        if st["chunks_fallen_back"]:
+            fell = st["chunks_fallen_back"]
+            print(f"   ℹ️  {fell} of {fell + st['chunks_followed']} dense clouds "
+                  "have no depth keyframes (create the chunks with dense_depth_every) or no created poses: they keep "
+                  "their chunk's similarity")
+        print(f"   🧭 Dense map follows the poses: {follower.summary()}")
     return fuser, acc
 
 
@@ -909,16 +1055,18 @@ def _extract_map(fuser: VoxelFuser, acc: Optional[NormalAccumulator], keep: Opti
 
 def fuse_chunks(chunks: Iterable[Dict], device="cuda", *, voxel_size: Optional[float] = None,
                 cleaner: Optional[MapCleaner] = None, carver: Optional[MapCarver] = None,
-                mesher: Optional[MapMesher] = None) -> Optional[DenseMap]:
+                mesher: Optional[MapMesher] = None, follower: Optional[MapFollower] = None) -> Optional[DenseMap]:
     """Stage 2: every chunk's dense_cloud moved by chunk_transform() and fused in the world frame (chunk 0's) -> the
     DenseMap; None when no chunk carries a cloud.  voxel_size: None takes the first cloud's.  carver (MapCarver) and
     cleaner (MapCleaner) choose, in that order, on the fused table which voxels the map keeps; mesher (MapMesher) also
-    meshes them, which needs the clouds' normals."""
+    meshes them, which needs the clouds' normals.  follower (MapFollower): a cloud whose chunk carries depth keyframes
+    and its created poses follows its views' final poses instead of chunk_transform()."""
     chunks = list(chunks)
-    clouds = [(c["dense_cloud"], chunk_transform(c)) for c in chunks if c.get("dense_cloud") is not None]
+    owners = [c for c in chunks if c.get("dense_cloud") is not None]
+    clouds = [(c["dense_cloud"], chunk_transform(c)) for c in owners]
     if not clouds:
         return None
     if voxel_size is None:
         voxel_size = float(clouds[0][0]["voxel_size"])
-    fuser, acc = _fuse_clouds(clouds, voxel_size, torch.device(device))
+    fuser, acc = _fuse_clouds(clouds, voxel_size, torch.device(device), follower, owners)
     return _extract_map(fuser, acc, _keep_mask(fuser, chunks, cleaner, carver), mesher)

@@ -319,7 +319,7 @@ CHAIN_KEYS = ("points", "keypoints", "masks", "camera_poses", "_chunk_frame", "_
 # what rank 0 collects of every chunk: all that export.py reads to write any output (the intrinsics and the image size
 # are a few hundred bytes per chunk) and the online results' bookkeeping; keys a chunk does not have are skipped
 COLLECT_KEYS = ("points", "colors", "keypoints", "masks", "camera_poses", "image_paths", "chunk_order", "alignment_ok",
-                "dense_cloud", "dense_depth", "_sim3_global", "_sim3_dense", "intrinsics", "original_width", "original_height", "_metrics")
+                "dense_cloud", "dense_depth", "_sim3_global", "_sim3_dense", "_poses_created", "intrinsics", "original_width", "original_height", "_metrics")
 
 
 def chain_payload(chunk: Optional[Dict]) -> Optional[Dict]:

@@ -199,15 +199,15 @@ def write_dense_mesh(mesh: Dict, path: str) -> int:
 
 def write_renders(chunks: Sequence[Dict], dense: Optional[DenseMap], out_dir: str, every: Optional[int], overview: bool,
                   min_weight: int = 1, splat_scale: float = 1.0, device="cuda",
-                  dense_cleaner=None, dense_carver=None) -> Optional[Tuple[int, Dict[str, float]]]:
+                  dense_cleaner=None, dense_follower=None, dense_carver=None) -> Optional[Tuple[int, Dict[str, float]]]:
     """<out_dir>/depth_<frame>.png (16 bit, millimetres, 0 = empty) and color_<frame>.png of the dense map for every
     `every`-th view of the de-duplicated trajectory, overview.png (a top-down orthographic view with the trajectory
     in red) and cameras.json -> (rendered views, {'total', 'png'} seconds).  `dense`: the map a caller has already fused
-    (else it is fused here, through `dense_carver` and `dense_cleaner`).  Without dense clouds in the chunks: one line,
-    no directory, None.  When the map has normals every view also gets normal_<frame>.png (the camera-frame normal as
+    (else it is fused here, through `dense_follower`, `dense_carver` and `dense_cleaner`).  Without dense clouds in the
+    chunks: one line, no directory, None.  When the map has normals every view also gets normal_<frame>.png (the camera-frame normal as
     RGB) and shaded_<frame>.png (headlight shading, greyscale), and the overview overview_shaded.png."""
     if dense is None:
-        dense = fuse_chunks(chunks, device, cleaner=dense_cleaner, carver=dense_carver)
+        dense = fuse_chunks(chunks, device, cleaner=dense_cleaner, carver=dense_carver, follower=dense_follower)
     if dense is None:
         print("   ℹ️  No dense clouds in the chunks (create them with a dense voxel size): no renders")
         return None
@@ -272,11 +272,12 @@ def write_renders(chunks: Sequence[Dict], dense: Optional[DenseMap], out_dir: st
 def write_outputs(chunks: Sequence[Dict], output_dir: str, device="cuda", render_every: Optional[int] = None,
                   render_overview: bool = False, render_min_weight: int = 1,
                   render_splat_scale: float = 1.0, dense_cleaner=None,
-                  dense_mesh: bool = False, dense_carver=None) -> Optional[Dict[str, float]]:
+                  dense_mesh: bool = False, dense_follower=None, dense_carver=None) -> Optional[Dict[str, float]]:
     """Every output file of stage 2 under output_dir; a file that fails is reported and the others are still written.
     Returns the seconds of write_renders when renders were written.  dense_cleaner (dense_map.MapCleaner): the dense
     map of the PLY and of the renders is the cleaned one.  dense_mesh: also dense_mesh.ply, the mesh of that map.
-    dense_carver (dense_map.MapCarver): that map is first carved with the chunks' depth keyframes."""
+    dense_carver (dense_map.MapCarver): that map is first carved with the chunks' depth keyframes.  dense_follower
+    (dense_map.MapFollower): the chunks' clouds follow their keyframes' final poses instead of the chunks' similarities."""
     try:
         pts, cols = sparse_points_colors(chunks)
         if pts.size > 0:
@@ -297,7 +298,7 @@ def write_outputs(chunks: Sequence[Dict], output_dir: str, device="cuda", render
     dense = None
     try:
         dense = fuse_chunks(chunks, device, cleaner=dense_cleaner, carver=dense_carver,
-                            mesher=MapMesher() if dense_mesh else None)
+                            mesher=MapMesher() if dense_mesh else None, follower=dense_follower)
         if dense is not None:
             write_dense_points(dense, os.path.join(output_dir, "dense_points.ply"))
     except Exception as e:  # noqa: BLE001
@@ -317,7 +318,8 @@ def write_outputs(chunks: Sequence[Dict], output_dir: str, device="cuda", render
     if render_every is not None or render_overview:
         try:       # the renders draw the map that was just fused for the PLY
             done = write_renders(chunks, dense, os.path.join(output_dir, "renders"), render_every, render_overview,
-                                 render_min_weight, render_splat_scale, device, dense_cleaner, dense_carver)
+                                 render_min_weight, render_splat_scale, device, dense_cleaner,
+                                 dense_follower=dense_follower, dense_carver=dense_carver)
             return done[1] if done else None
         except Exception as e:  # noqa: BLE001
             print(f"❌ Failed to save the renders of the dense map: {e}")

@@ -78,6 +78,7 @@ SIGNATURES = {
     "pi3_dense_consistency": [_vp] * 6 + [_i, _i, _i, _f, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp],
     "pi3_dense_depth_planes": [_vp] * 4 + [_i, _i, _i, _f, _i, _i, _vp, _vp, _vp],
     "pi3_voxel_carve": [_vp, _l, _d, _vp, _i, _vp, _i, _i, _i, _d, _d, _i, _vp, _vp, _vp, _vp, _vp],
+    "pi3_cloud_follow_views": [_vp, _vp, _l, _vp, _vp, _i, _vp, _i, _i, _i, _d, _d, _vp, _vp, _vp, _vp, _vp, _vp],
     "pi3_cloud_index_build": [_vp, _l, _f, _vp, _l, _vp, _vp, _vp],
     "pi3_cloud_nearest": [_vp, _l, _vp, _l, _f, _vp, _l, _d, _vp, _vp, _vp, _vp],
     "pi3_cloud_pair_equations": [_vp, _l, _vp, _l, _vp, _vp, _d, _vp, _vp, _i, _vp, _vp, _l, _vp, _vp, _vp],

@@ -28,7 +28,7 @@ from . import export
 from .alignment import align_and_refine_reconstructions, create_view_graph_matches, transform_chunk
 from .bundle_adjust import bundle_adjust_new_chunk, chunk_ba_args
 from .chunk_creator import OfflineChunkCreator, OfflineCreatorConfig
-from .dense_map import DenseMap, MapCarver, MapCleaner, MapMesher, fuse_chunks
+from .dense_map import DenseMap, MapCarver, MapCleaner, MapFollower, MapMesher, fuse_chunks
 from .image_io import ChunkImageDataset, calculate_target_size
 
 
@@ -57,6 +57,7 @@ class InOrderDrain:
 
 class Pi3SLAMOnline:
     dense_carver = None     # class default: the export methods also serve objects whose __init__ did not run (tests)
+    dense_follower = None
 
     def __init__(self, model=None, chunk_length: int = 100, overlap: int = 10, device: str = "cuda",
                  conf_threshold: float = 0.5, undistortion_maps=None, cam_scale: float = 1.0,
@@ -72,10 +73,14 @@ class Pi3SLAMOnline:
                  dense_min_weight: Optional[int] = None, dense_min_support: Optional[int] = None,
                  dense_support_radius: int = 1, dense_min_component: Optional[int] = None, dense_normals: bool = False,
                  dense_depth_every: Optional[int] = None, dense_depth_stride: int = 2,
-                 dense_carve_min_conflicts: Optional[int] = None, dense_carve_tolerance: float = 0.03):
+                 dense_carve_min_conflicts: Optional[int] = None, dense_carve_tolerance: float = 0.03,
+                 map_follow_poses: bool = False, map_follow_tolerance: float = 0.03):
         # dense_depth_every: the chunks keep depth keyframes; dense_carve_min_conflicts: the fused dense map of
         # save_dense_map / save_dense_mesh / save_renders is carved with them first (dense_map.MapCarver; off by default)
         self.dense_carver = MapCarver.from_options(dense_carve_min_conflicts, dense_carve_tolerance)
+        # map_follow_poses: the fused dense map follows the final poses view by view (dense_map.MapFollower; needs
+        # dense_depth_every): every chunk keeps the poses it was created with as '_poses_created'.  Off by default
+        self.dense_follower = MapFollower.from_options(map_follow_poses, map_follow_tolerance)
         # filters on the fused dense map of save_dense_map / save_renders (all off by default: no cleaner)
         self.dense_cleaner = MapCleaner.from_options(dense_min_weight, dense_min_support, dense_support_radius,
                                                      dense_min_component)
@@ -137,6 +142,8 @@ class Pi3SLAMOnline:
         return chunk_ba_args(chunk, self.max_observations_per_track, inverse_depth=self.use_inverse_depth)
 
     def _refine_new_chunk(self, chunk: Dict) -> None:
+        if self.dense_follower is not None:     # the frame the chunk's dense cloud and depth keyframes stay in
+            chunk["_poses_created"] = chunk["camera_poses"].clone()
         args = self._ba_args(chunk)
         if args is None:
             return
@@ -306,7 +313,7 @@ class Pi3SLAMOnline:
         """The chunks' dense clouds fused, carved and cleaned as this object's options say (with normals under
         dense_normals; mesher: and its mesh).  Fused anew on every call."""
         dense = fuse_chunks(self.chunk_reconstructions, str(self.device), cleaner=self.dense_cleaner,
-                            carver=self.dense_carver, mesher=mesher)
+                            carver=self.dense_carver, mesher=mesher, follower=self.dense_follower)
         if dense is None:
             raise RuntimeError("no dense clouds: construct Pi3SLAMOnline with dense_voxel_size")
         return dense

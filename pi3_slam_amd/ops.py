@@ -880,6 +880,55 @@ def voxel_carve(table: torch.Tensor, voxel_size: float, views: torch.Tensor, pla
     _L.check(rc, "pi3_voxel_carve")
 
 
+# ---- moving a chunk's cloud with the views that saw it (csrc/cloud_follow.hip)
+CLOUD_FOLLOW_COUNTERS = ("dropped", "level1", "level2", "level3")
+FOLLOW_MOVE_DOUBLES = 12    # D_m, 3x4 row-major
+
+
+def cloud_follow_views(points: torch.Tensor, normals: Optional[torch.Tensor], views: torch.Tensor, moves: torch.Tensor,
+                       planes: torch.Tensor, pixel_stride: int, rel_tol: float, margin: float, out_points: torch.Tensor,
+                       out_normals: Optional[torch.Tensor], level: Optional[torch.Tensor],
+                       support: Optional[torch.Tensor], counters: torch.Tensor) -> None:
+    """Per point X of points f32 (P,3) (normals f32 (P,3) or None) and per view m in order (views f64 (M,20) as
+    voxel_carve's, moves f64 (M,12) = D_m 3x4 row-major, planes fp16 (M,H',W')): Y = D_m X, Nn = the 3x3 part of D_m
+    times the normal; every view adds to level 3; a view in whose plane the point projects (the carver's xc, yc, zc, u,
+    v, pu, pv) adds with w = 1 / zc^2 to level 2; a view whose depth zo = views[m,17] plane[m,pv,pu] is non-zero, finite
+    and has |zc - zo| <= rel_tol zo + margin adds with w to level 1.  out_points (may be points) = S_l / W_l of the first
+    level that has a view (level 3: S3 / M), out_normals (may be normals) = N_l normalised (0 when it has no length);
+    level uint8 (P,) or None; support int32 (P,) or None = the level-1 views; counters int64 (4,) =
+    CLOUD_FOLLOW_COUNTERS (zeroed by the call).  A point that is not finite is copied, level 0, counted as dropped."""
+    lib = _L.load()
+    dev = points.device
+    assert points.dtype == torch.float32 and points.is_contiguous() and points.ndim == 2 and points.shape[1] == 3
+    P = int(points.shape[0])
+    assert out_points.dtype == torch.float32 and out_points.is_contiguous() and out_points.shape == points.shape
+    assert out_points.device == dev
+    assert (normals is None) == (out_normals is None)
+    for t in (normals, out_normals):
+        if t is not None:
+            assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == points.shape and t.device == dev
+    assert views.dtype == torch.float64 and views.is_contiguous() and views.ndim == 2
+    assert views.shape[1] == CARVE_VIEW_DOUBLES and views.device == dev
+    M = int(views.shape[0])
+    assert moves.dtype == torch.float64 and moves.is_contiguous() and tuple(moves.shape) == (M, FOLLOW_MOVE_DOUBLES)
+    assert moves.device == dev
+    assert planes.dtype == torch.float16 and planes.is_contiguous() and planes.ndim == 3 and planes.device == dev
+    assert int(planes.shape[0]) == M and 1 <= M < 1 << 31
+    Hp, Wp = int(planes.shape[1]), int(planes.shape[2])
+    if level is not None:
+        assert level.dtype == torch.uint8 and level.is_contiguous() and level.numel() == P and level.device == dev
+    if support is not None:
+        assert support.dtype == torch.int32 and support.is_contiguous() and support.numel() == P and support.device == dev
+    assert counters.dtype == torch.int64 and counters.is_contiguous() and counters.numel() >= 4 and counters.device == dev
+    empty = P == 0              # empty tensors have no address to pass
+    rc = lib.pi3_cloud_follow_views(None if empty else points.data_ptr(), None if empty else _L.ptr(normals), P,
+                                    views.data_ptr(), moves.data_ptr(), M, planes.data_ptr(), Hp, Wp, int(pixel_stride),
+                                    float(rel_tol), float(margin), None if empty else out_points.data_ptr(),
+                                    None if empty else _L.ptr(out_normals), None if empty else _L.ptr(level),
+                                    None if empty else _L.ptr(support), counters.data_ptr(), _L.stream_ptr())
+    _L.check(rc, "pi3_cloud_follow_views")
+
+
 # ---- nearest neighbours between two clouds (csrc/cloud_nn.hip)
 CLOUD_INDEX_COUNTERS = ("dropped", "cells", "no_slot", "largest_cell")
 CLOUD_NEAREST_COUNTERS = ("dropped", "matched", "beyond", "evaluations")

@@ -36,7 +36,8 @@ class OfflineReconstructor:
                  render_splat_scale: float = 1.0, dense_min_weight: Optional[int] = None,
                  dense_min_support: Optional[int] = None, dense_support_radius: int = 1,
                  dense_min_component: Optional[int] = None, dense_mesh: bool = False,
-                 dense_carve_min_conflicts: Optional[int] = None, dense_carve_tolerance: float = 0.03):
+                 dense_carve_min_conflicts: Optional[int] = None, dense_carve_tolerance: float = 0.03,
+                 map_follow_poses: bool = False, map_follow_tolerance: float = 0.03):
         self.chunk_dir, self.output_dir = chunk_dir, output_dir
         # dense_mesh: after dense_points.ply also dense_mesh.ply, a triangle mesh of the same fused (and cleaned) table
         # (dense_map.MapMesher); the chunks must carry normals (created with dense_normals)
@@ -48,8 +49,14 @@ class OfflineReconstructor:
                                                      dense_min_component)
         # dense_carve_min_conflicts: before those filters, drop the voxels of the fused map that this many depth keyframes
         # (chunks created with dense_depth_every) looked through (dense_map.MapCarver); off by default: no carver.  The
-        # keyframes sit where the chunks' similarities put them: use it with bundle_adjust=False, like the map itself
+        # keyframes sit where the chunks' similarities put them: use it with bundle_adjust=False or map_follow_poses
         self.dense_carver = MapCarver.from_options(dense_carve_min_conflicts, dense_carve_tolerance)
+        # map_follow_poses: the dense map follows the final poses view by view (dense_map.MapFollower): every chunk keeps
+        # the camera_poses of its file as '_poses_created', and a cloud point moves with the depth keyframes (chunks
+        # created with dense_depth_every) that saw it; chunks without keyframes keep their similarity.  Off by
+        # default: no follower, and nothing is kept
+        from .dense_map import MapFollower
+        self.dense_follower = MapFollower.from_options(map_follow_poses, map_follow_tolerance)
         # render_every / render_overview: after dense_points.ply, depth + colour images of the dense map from every N-th
         # view of the trajectory and a top-down overview, under <output>/renders (pi3_slam_amd/render.py); off by default
         if render_every is not None and int(render_every) <= 0:
@@ -134,6 +141,8 @@ class OfflineReconstructor:
             print(f"\n📦 Loading {os.path.basename(files[idx])} ({idx + 1}/{len(files)})")
         data: Dict = torch.load(files[idx], map_location="cpu", weights_only=False)
         t0 = time.time()
+        if self.dense_follower is not None:     # the frame the chunk's dense cloud and depth keyframes stay in
+            data["_poses_created"] = data["camera_poses"].clone()
         args = self._ba_args(data)
         if args is not None:
             try:
@@ -184,7 +193,8 @@ class OfflineReconstructor:
             self.reconstructions = done
             seconds = export.write_outputs(done, self.output_dir, self.device, self.render_every, self.render_overview,
                                            self.render_min_weight, self.render_splat_scale, self.dense_cleaner,
-                                           self.dense_mesh, dense_carver=self.dense_carver)
+                                           self.dense_mesh, dense_carver=self.dense_carver,
+                                           dense_follower=self.dense_follower)
             if seconds is not None:
                 self.render_seconds = seconds
         if grouped:

@@ -690,6 +690,50 @@ int pi3_voxel_mesh_extract(const unsigned long long* cells, long cell_capacity, 
                            unsigned long long* qkeys, int* qcodes, long max_quads, unsigned long long* stats,
                            void* stream);
 
+/* ---- loop closure: which chunks see the same surface (csrc/chunk_overlap.hip).  Exact integers.
+ * points f32 [P][3]: the dense clouds of all C chunks, already in the world frame, one after the other; offsets DEVICE
+ * int64 [C + 1]: chunk c owns the rows offsets[c] .. offsets[c + 1] - 1 (a row before offsets[0] or from offsets[C] on
+ * belongs to no chunk and is dropped).  table: caller-owned DEVICE memory of `capacity` 64-byte slots (a power of two,
+ * >= 2 P), cleared by the call: key | seven 64-bit words of chunk bits, so C <= 448 (more: PI3_ERR_ARG).
+ * Pass 1: every point is quantised as the voxel map quantises it, at inv_cell (k = floor(p * inv_cell) per axis in fp32;
+ * dropped when not finite or |k| >= 2^20), claims the slot of its cell and ORs its chunk's bit into the words (64-bit
+ * integer atomics).  Pass 2: for every occupied cell and every unordered pair i <= j of its bits, counts[i][j] and
+ * counts[j][i] += 1; the diagonal is counted once: counts[i][i] = the cells chunk i occupies.  counts DEVICE uint64
+ * [C][C] and counters DEVICE uint64 [4] = dropped points, occupied cells, points that found no slot (0 under the
+ * capacity rule), the largest number of chunks in one cell; both zeroed by the call.  The result does not depend on the
+ * order of the atomics nor on how pass 2 aggregates (in LDS up to 64 chunks, in global memory above).
+ * P == 0 or C == 0 clears counts and counters and launches no pass.  Bad arguments (a negative size, C > 448, inv_cell
+ * not finite or <= 0, a capacity that is no power of two or below 2 P, NULL where an array is needed) launch nothing and
+ * leave the outputs untouched.  No allocation, no synchronisation. */
+int pi3_chunk_cooccupancy(const float* points, long P, const long* offsets, int C, float inv_cell, void* table,
+                          long capacity, unsigned long long* counts, unsigned long long* counters, void* stream);
+
+/* ---- loop closure: the Sim(3) pose graph over the chunks (csrc/pose_graph.hip), f64, every array on the DEVICE.
+ * nodes f64 [C][16] in / out: W_c, the row-major 4x4 similarity chunk c -> world (its fourth row is written 0 0 0 1).
+ * centres f64 [C][3]: g_c, the point a node's step turns and scales about (the world centroid of its cloud).
+ * Edge e = (i, j) = edges int32 [E][2]:  Z f64 [E][16] the measured similarity chunk j -> chunk i, edge_centres f64
+ * [E][3] a centre c_e in chunk i's frame, info f64 [E][28] the upper triangle, row-major, of the symmetric 7x7
+ * information matrix O_e, in the parameter order w (3), l, t (3) of pi3_cloud_pair_equations.
+ *   chart([sR | tau], c) = (rotation vector of R, ln s, tau - c + sR c);  r_e = chart(W_i^-1 W_j Z_e^-1, c_e);
+ *   F = sum_e r_e^T O_e r_e.       An edge with an index outside [0, C) or with i == j is left out.
+ * Levenberg-Marquardt with analytic Jacobians: node k steps by d_k in R^7 as W_k <- inc(d_k, g_k) W_k,
+ * inc(x, g) = [ e^l exp([w]x) | g + t - e^l exp([w]x) g ].  fixed uint8 [C]: a node with fixed[c] != 0, and a free node
+ * without an edge, keeps its value (identity rows in the system).  The dense 7C x 7C normal matrix is written one block
+ * row per node with the edges in index order (no floating-point atomics: two runs give the same bits);
+ * (H + lambda diag H) d = -g by Cholesky.  Per iteration: a factorisation that fails multiplies lambda by 10 (status 2
+ * when lambda is 1e12 already); max |d| < 1e-9 converges and applies that last d; a candidate whose F differs from the
+ * current one by no more than 1e-12 F converges and is applied; one with a smaller F is accepted (lambda / 10, at
+ * least 1e-12); else lambda * 10 (at most 1e12).  lambda starts at 1e-4; decision and lambda live in the workspace, the call never waits for the device.
+ * out f64 [16] = final F, initial F, iterations, accepted steps, final lambda, status (0 converged, 1 max_iterations
+ * reached, 2 factorisation failed at the largest lambda: the nodes then hold their input values), 10 zeros.
+ * max_iterations == 0 leaves the nodes as they are (status 1).  workspace: DEVICE f64 [workspace_doubles], at least
+ * what pi3_pose_graph_workspace reports through *doubles (fewer: PI3_ERR_WORKSPACE); 49 C^2 of it is the matrix.
+ * 1 <= C <= 448, E >= 0.  Bad arguments launch nothing and leave nodes and out untouched.  No allocation. */
+int pi3_pose_graph_workspace(int C, int E, long* doubles);
+int pi3_pose_graph_sim3(double* nodes, const double* centres, int C, const int* edges, const double* Z,
+                        const double* edge_centres, const double* info, int E, const unsigned char* fixed,
+                        int max_iterations, double* workspace, long workspace_doubles, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

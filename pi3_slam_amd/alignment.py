@@ -167,6 +167,30 @@ def transform_chunk(chunk: Dict, M4: torch.Tensor, device="cuda:0", absolute: bo
     chunk["camera_poses"] = poses.to(src["camera_poses"].device)
 
 
+def apply_world_correction(chunk: Dict, D: torch.Tensor, device="cuda:0") -> None:
+    """A correction D (4x4 f64 similarity, world -> world) on a finished chunk, in place: what loop closure applies.
+    chunk['points'] and ['camera_poses'] move by D from their CURRENT world values (as fp32); '_sim3_global', and
+    '_sim3_dense' when present, become D times what they were (pi3_sim3_compose_prefix), so the dense cloud follows
+    through dense_map.chunk_transform.  '_poses_created', '_chunk_frame' and the dense cloud's rows stay as they are.
+    Not transform_chunk: that rebuilds the world values from '_chunk_frame', and a chunk that was collected from another
+    rank carries '_sim3_global' but no '_chunk_frame' - its world values would get the accumulated similarity twice."""
+    D = upload(torch.as_tensor(D).detach().to(torch.float64).reshape(4, 4).contiguous(), device, torch.float64).contiguous()
+    pts = fresh_upload(chunk["points"], device, torch.float32)
+    poses = fresh_upload(chunk["camera_poses"], device, torch.float32)
+    ops.sim3_apply(D, pts, poses)
+    chunk["points"] = pts.to(chunk["points"].device)
+    chunk["camera_poses"] = poses.to(chunk["camera_poses"].device)
+    for key in ("_sim3_global", "_sim3_dense"):
+        G = chunk.get(key)
+        if G is None and key == "_sim3_dense":
+            continue
+        if G is None:            # a chunk that was never transformed sits at the identity
+            chunk[key] = D.cpu().clone()
+            continue
+        G = upload(torch.as_tensor(G, dtype=torch.float64).reshape(16), device, torch.float64)
+        chunk[key] = ops.sim3_compose_prefix(torch.stack([D.reshape(16), G]).contiguous())[1].reshape(4, 4).cpu()
+
+
 def align_and_refine_reconstructions(chunk_ref: Dict, chunk_qry: Dict, view_graph_matches: List[Tuple[int, int]],
                                      use_inverse_depth: bool = False, device="cuda:0",
                                      use_masks: bool = False, bundle_adjust: Optional[Dict] = None,

@@ -128,6 +128,20 @@ MAP_FOLLOW_SWITCH = ("--map-follow-poses", "the dense map follows the bundle-adj
                                            "moves with the depth keyframes of its chunk that saw it, each from the pose it "
                                            "was created with to its final pose (needs chunks created with "
                                            "--dense-depth-every; chunks without keyframes keep their similarity)")
+# loop closure (loop_closure.close_loops); the defaults are starting points, not measured optima
+LOOP_FLAGS: Sequence[Tuple[str, Dict]] = (
+    ("--loop-min-gap", dict(type=int, default=2, help="with --loop-closure: chunks i and j are a candidate from j - i >= this")),
+    ("--loop-min-overlap", dict(type=float, default=0.3, help="cells both chunks occupy / cells of the smaller one, at least")),
+    ("--loop-max-edges", dict(type=int, default=3, help="loop edges per chunk, the best overlaps first")),
+    ("--loop-max-dist", dict(type=float, default=0.1, help="ICP search radius in world units: the drift a loop may close")),
+    ("--loop-max-rms", dict(type=float, default=0.03, help="an edge is accepted up to this ICP rms (world units)")),
+    ("--loop-min-pair-fraction", dict(type=float, default=0.2, help="and from this share of the smaller cloud in ICP pairs")),
+    ("--loop-cell", dict(type=float, default=0.16, help="edge of the co-occupancy cells (world units)")),
+)
+LOOP_SWITCH = ("--loop-closure", "close loops before the outputs are written: chunks that see the same surface (co-occupancy "
+                                 "of their dense clouds) are aligned by ICP and a Sim(3) pose graph spreads the chain's "
+                                 "error over the loops (needs chunks created with --dense-voxel-size; writes "
+                                 "loop_closure.json)")
 RECON_SWITCHES = (("--save-per-chunk", "per-chunk ply files as well"),
                   ("--render-overview", "write renders/overview.png: the dense map from above with the trajectory in red"),
                   ("--use-inverse-depth", "one inverse depth per track along its reference keypoint's ray in both bundle "
@@ -139,7 +153,7 @@ RECON_SWITCHES = (("--save-per-chunk", "per-chunk ply files as well"),
                   ("--no-ba-sanity-gate", "apply every bundle adjustment that ends without a numerical failure, as the "
                                           "reference does (default: keep the input when fewer than 3 tracks survive or a "
                                           "camera moved by more than the scene extent)"),
-                  MAP_FOLLOW_SWITCH)
+                  MAP_FOLLOW_SWITCH, LOOP_SWITCH)
 
 
 # pi3_slam_online_modular.py:117-183: same names (underscores), types and defaults; the reference's personal default paths
@@ -246,7 +260,7 @@ def build_parser() -> argparse.ArgumentParser:
     top = argparse.ArgumentParser(prog="pi3_slam_amd.cli", description=__doc__.split("\n")[0])
     sub = top.add_subparsers(dest="command", required=True)
     for name, flags, switches in (("create", tuple(CREATE_FLAGS) + tuple(DENSE_CHUNK_FLAGS), CREATE_SWITCHES),
-                                  ("reconstruct", tuple(RECON_FLAGS) + tuple(DENSE_MAP_FLAGS), RECON_SWITCHES),
+                                  ("reconstruct", tuple(RECON_FLAGS) + tuple(DENSE_MAP_FLAGS) + tuple(LOOP_FLAGS), RECON_SWITCHES),
                                   ("online", tuple(ONLINE_FLAGS) + ONLINE_DENSE_FLAGS + ONLINE_FOLLOW_FLAGS,
                                    ONLINE_SWITCHES),
                                   ("evaluate-map", EVAL_FLAGS, EVAL_SWITCHES)):
@@ -296,8 +310,8 @@ def run_reconstruct(a: argparse.Namespace) -> None:
                          ba_sanity_gate=not a.no_ba_sanity_gate, render_every=a.render_every,
                          render_overview=a.render_overview, render_min_weight=a.render_min_weight,
                          render_splat_scale=a.render_splat_scale, map_follow_poses=a.map_follow_poses,
-                         map_follow_tolerance=a.map_follow_tolerance,
-                         **{name: getattr(a, name) for name in option_names(DENSE_MAP_FLAGS)}).run()
+                         map_follow_tolerance=a.map_follow_tolerance, loop_closure=a.loop_closure,
+                         **{name: getattr(a, name) for name in option_names(tuple(DENSE_MAP_FLAGS) + tuple(LOOP_FLAGS))}).run()
 
 
 def online_image_paths(a: argparse.Namespace) -> List[str]:

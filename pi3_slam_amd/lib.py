@@ -96,6 +96,9 @@ SIGNATURES = {
     "pi3_voxel_mesh_cells": [_vp, _l, _vp, _vp, _vp, _l, _vp, _vp],
     "pi3_voxel_mesh_vertices": [_vp, _l, _vp, _vp, _vp, _l, _d, _vp, _vp, _vp],
     "pi3_voxel_mesh_extract": [_vp, _l, _vp, _vp, _vp, _vp, _vp, _l, _vp, _vp, _l, _vp, _vp],
+    "pi3_chunk_cooccupancy": [_vp, _l, _vp, _i, _f, _vp, _l, _vp, _vp, _vp],
+    "pi3_pose_graph_workspace": [_i, _i, C.POINTER(_l)],
+    "pi3_pose_graph_sim3": [_vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _l, _vp, _vp],
     "pi3_set_knob": [C.c_char_p, _l],
     "pi3_get_knob": [C.c_char_p, C.POINTER(_l)],
     "pi3_unset_knob": [C.c_char_p],

@@ -432,7 +432,8 @@ def _device_normals(normals, rows: int, device) -> torch.Tensor:
 
 
 def icp_refine(est, ref, *, mode: str, est_normals=None, ref_normals=None, with_scale: bool = False, max_dist: float,
-               iterations: int = 30, tolerance: float = 1e-7, init=None, device="cuda") -> Dict:
+               iterations: int = 30, tolerance: float = 1e-7, init=None, device="cuda",
+               truncate: Optional[float] = None) -> Dict:
     """Refines the 4x4 similarity that places `est` (n,3) on `ref` (m,3) by ICP: point to point (mode="point") or point
     to plane (mode="plane": the reference's normals when given, otherwise the estimate's, rotated by the current
     transform's rotation; with neither: ValueError).  Rigid, or with `with_scale` a similarity.
@@ -444,7 +445,12 @@ def icp_refine(est, ref, *, mode: str, est_normals=None, ref_normals=None, with_
     used), 'degenerate' (the solved block of A / pairs, scaled to unit diagonal, has eigenvalue ratio min / max below
     1e-9: a single plane under point to plane, a line); the last two keep the M from before that iteration.
     -> transform, increment (= transform init^-1), status, iterations, history (per iteration: pairs, counters, rms =
-    sqrt(r2 / pairs), point_rms = sqrt(sum e.e / pairs), step = |x|; None where nothing was solved)."""
+    sqrt(r2 / pairs), point_rms = sqrt(sum e.e / pairs), step = |x|; None where nothing was solved).
+    truncate (None: the plain solve above, unchanged): the step is solved only along the eigen-directions of the solved
+    block of A / pairs, scaled to unit diagonal, whose eigenvalue is at least truncate x the largest; along the others
+    the transform keeps what it had (surfaces that leave a motion free - three planes leave the scaling about their
+    common point free - otherwise send the step along it on the residuals' noise, iteration after iteration).  The
+    entries of history then also carry 'kept', the number of directions solved."""
     if mode not in ("point", "plane"):
         raise ValueError(f"icp mode must be 'point' or 'plane', got {mode!r}")
     if mode == "plane" and est_normals is None and ref_normals is None:
@@ -498,7 +504,14 @@ def icp_refine(est, ref, *, mode: str, est_normals=None, ref_normals=None, with_
             status = "degenerate"
             break
         x = np.zeros(7)
-        x[sel] = np.linalg.solve(As, -bs)
+        if truncate is None:
+            x[sel] = np.linalg.solve(As, -bs)
+        else:
+            ev, V = np.linalg.eigh((As / pairs) / np.outer(dg, dg))
+            keep = ev >= float(truncate) * ev[-1]
+            y = -(bs / pairs) / dg
+            x[sel] = (V[:, keep] @ ((V[:, keep].T @ y) / ev[keep])) / dg
+            entry["kept"] = int(keep.sum())
         if not np.isfinite(x).all():
             status = "degenerate"
             break

@@ -1141,6 +1141,71 @@ def cloud_pair_equations(queries: torch.Tensor, points: torch.Tensor, idx: torch
     _L.check(rc, "pi3_cloud_pair_equations")
 
 
+# ---- loop closure: co-occupancy of the chunks' clouds (csrc/chunk_overlap.hip), the pose graph (csrc/pose_graph.hip)
+CHUNK_OVERLAP_COUNTERS = ("dropped", "cells", "no_slot", "most_chunks")
+CHUNK_OVERLAP_MAX_CHUNKS = 448      # seven 64-bit mask words per cell
+POSE_GRAPH_OUT = ("final_cost", "initial_cost", "iterations", "accepted_steps", "lambda", "status")
+POSE_GRAPH_STATUS = ("converged", "max_iterations", "factorisation_failed")
+
+
+def chunk_cooccupancy(points: torch.Tensor, offsets: torch.Tensor, inv_cell: float, table: torch.Tensor,
+                      counts: torch.Tensor, counters: torch.Tensor) -> None:
+    """points f32 (P,3): all chunks' clouds in the world frame, chunk c the rows offsets[c] .. offsets[c+1]-1 (offsets
+    int64 (C+1,) on the device) -> counts int64 (C,C): the cells (edge 1 / inv_cell) that chunks i and j both occupy,
+    the diagonal the cells of chunk i; counters int64 (4,) = CHUNK_OVERLAP_COUNTERS.  table int64 (8 capacity,),
+    capacity = voxel_capacity(P): workspace.  Everything is written by the call; exact integers."""
+    lib = _L.load()
+    dev = counts.device
+    assert points.dtype == torch.float32 and points.is_contiguous() and points.ndim == 2 and points.shape[1] == 3
+    assert offsets.dtype == torch.int64 and offsets.is_contiguous() and offsets.ndim == 1 and offsets.numel() >= 1
+    P, C = int(points.shape[0]), int(offsets.numel()) - 1
+    assert table.dtype == torch.int64 and table.is_contiguous() and table.numel() % 8 == 0
+    assert counts.dtype == torch.int64 and counts.is_contiguous() and tuple(counts.shape) == (C, C) and counts.is_cuda
+    assert counters.dtype == torch.int64 and counters.is_contiguous() and counters.numel() >= 4
+    assert all(t.device == dev for t in (points, offsets, table, counters))
+    rc = lib.pi3_chunk_cooccupancy(points.data_ptr() if P else None, P, offsets.data_ptr(), C, float(inv_cell),
+                                   table.data_ptr() if table.numel() else None, table.numel() // 8,
+                                   counts.data_ptr() if C else None, counters.data_ptr(), _L.stream_ptr())
+    _L.check(rc, "pi3_chunk_cooccupancy")
+
+
+def pose_graph_workspace(n_nodes: int, n_edges: int) -> int:
+    """Doubles of workspace pose_graph_sim3 needs for that many nodes and edges."""
+    n = C.c_long(0)
+    _L.check(_L.load(False).pi3_pose_graph_workspace(int(n_nodes), int(n_edges), C.byref(n)), "pi3_pose_graph_workspace")
+    return int(n.value)
+
+
+def pose_graph_sim3(nodes: torch.Tensor, centres: torch.Tensor, edges: torch.Tensor, Z: torch.Tensor,
+                    edge_centres: torch.Tensor, info: torch.Tensor, fixed: torch.Tensor, max_iterations: int,
+                    workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Levenberg-Marquardt on the Sim(3) pose graph, in place on nodes f64 (C,4,4) (include/pi3slam_hip.h states the
+    model): centres f64 (C,3), edges int32 (E,2), Z f64 (E,4,4), edge_centres f64 (E,3), info f64 (E,28), fixed uint8
+    (C,) -> out f64 (16,) on the device = POSE_GRAPH_OUT, ten zeros.  No synchronisation."""
+    lib = _L.load()
+    dev = nodes.device
+    C, E = int(nodes.numel() // 16), int(edges.numel() // 2)
+    assert nodes.dtype == torch.float64 and nodes.is_contiguous() and nodes.numel() == 16 * C and nodes.is_cuda
+    assert centres.dtype == torch.float64 and centres.is_contiguous() and centres.numel() == 3 * C
+    assert edges.dtype == torch.int32 and edges.is_contiguous() and edges.numel() == 2 * E
+    assert Z.dtype == torch.float64 and Z.is_contiguous() and Z.numel() == 16 * E
+    assert edge_centres.dtype == torch.float64 and edge_centres.is_contiguous() and edge_centres.numel() == 3 * E
+    assert info.dtype == torch.float64 and info.is_contiguous() and info.numel() == 28 * E
+    assert fixed.dtype == torch.uint8 and fixed.is_contiguous() and fixed.numel() == C
+    assert all(t.device == dev for t in (centres, edges, Z, edge_centres, info, fixed))
+    need = pose_graph_workspace(C, E)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.float64, device=dev)
+    assert workspace.dtype == torch.float64 and workspace.is_contiguous() and workspace.device == dev
+    out = torch.empty(16, dtype=torch.float64, device=dev)
+    rc = lib.pi3_pose_graph_sim3(nodes.data_ptr(), centres.data_ptr(), C, edges.data_ptr() if E else None,
+                                 Z.data_ptr() if E else None, edge_centres.data_ptr() if E else None,
+                                 info.data_ptr() if E else None, E, fixed.data_ptr(), int(max_iterations),
+                                 workspace.data_ptr(), workspace.numel(), out.data_ptr(), _L.stream_ptr())
+    _L.check(rc, "pi3_pose_graph_sim3")
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------- map renderer
 RENDER_CAM_DOUBLES = 20     # world->camera 3x4 row-major, fx, fy, cx, cy, ortho flag, 3 spare (csrc/render.hip)
 

@@ -37,8 +37,21 @@ class OfflineReconstructor:
                  dense_min_support: Optional[int] = None, dense_support_radius: int = 1,
                  dense_min_component: Optional[int] = None, dense_mesh: bool = False,
                  dense_carve_min_conflicts: Optional[int] = None, dense_carve_tolerance: float = 0.03,
+                 loop_closure: bool = False, loop_min_gap: int = 2, loop_min_overlap: float = 0.3,
+                 loop_max_edges: int = 3, loop_max_dist: float = 0.1, loop_max_rms: float = 0.03,
+                 loop_min_pair_fraction: float = 0.2, loop_cell: float = 0.16,
                  map_follow_poses: bool = False, map_follow_tolerance: float = 0.03):
         self.chunk_dir, self.output_dir = chunk_dir, output_dir
+        # loop_closure: before the outputs are written, chunks that see the same surface are found by the co-occupancy
+        # of their dense clouds, measured against each other by ICP and reconciled with the chain in a Sim(3) pose graph
+        # (loop_closure.close_loops; the chunks must carry dense clouds).  Off by default: nothing is imported or run.
+        # The loop_* defaults are starting points, not measured optima
+        self.loop_closure = bool(loop_closure)
+        self.loop_options = dict(loop_min_gap=int(loop_min_gap), loop_min_overlap=float(loop_min_overlap),
+                                 loop_max_edges=int(loop_max_edges), loop_max_dist=float(loop_max_dist),
+                                 loop_max_rms=float(loop_max_rms), loop_min_pair_fraction=float(loop_min_pair_fraction),
+                                 loop_cell=float(loop_cell))
+        self.loop_closure_info: Optional[Dict] = None
         # dense_mesh: after dense_points.ply also dense_mesh.ply, a triangle mesh of the same fused (and cleaned) table
         # (dense_map.MapMesher); the chunks must carry normals (created with dense_normals)
         self.dense_mesh = bool(dense_mesh)
@@ -191,6 +204,12 @@ class OfflineReconstructor:
             done = sorted((d for part in parts or [] for d in part), key=lambda d: d["chunk_order"])
         if rank == 0:
             self.reconstructions = done
+            if self.loop_closure:
+                from .loop_closure import close_loops
+                self.loop_closure_info = close_loops(done, self.device, **self.loop_options)
+                if self.loop_closure_info["skipped"] != "fewer_than_three_participants":
+                    with open(os.path.join(self.output_dir, "loop_closure.json"), "w") as f:
+                        json.dump(self.loop_closure_info, f, indent=1, default=float)
             seconds = export.write_outputs(done, self.output_dir, self.device, self.render_every, self.render_overview,
                                            self.render_min_weight, self.render_splat_scale, self.dense_cleaner,
                                            self.dense_mesh, dense_carver=self.dense_carver,

@@ -505,6 +505,43 @@ int pi3_cloud_follow_views(const float* points, const float* normals, long P, co
                            double margin, float* out_points, float* out_normals, unsigned char* level, int* support,
                            unsigned long long* counters, void* stream);
 
+/* ---- occupancy grid and clearance field of the dense map (csrc/occupancy.hip).  A grid of cells of edge c with the
+ * integer origin (ox, oy, oz) and the dimensions (nx, ny, nz): cell (ix, iy, iz) covers [c (o + i), c (o + i + 1)) per
+ * axis and lies at the linear index (iz ny + iy) nx + ix (x fastest).  state uint8 [nz][ny][nx]: 0 unknown, 1 free,
+ * 2 occupied.  |o| < 2^21 and 1 <= n < 2^21 per axis.
+ * pi3_occupancy_mark: zeroes the grid, then per row of points f32 [P][3] (the extracted map): every axis through the
+ *   voxel quantiser at inv_cell = (float)(1 / c) (k = floor(p * inv_cell) in fp32; dropped when not finite or
+ *   |k| >= 2^20), i = k - o, state = 2 when the cell is inside the grid.  counters: DEVICE uint64 [4] = points marked,
+ *   points dropped by the quantiser, points outside the grid, spare; zeroed by the call.  0 <= P < 2^39; P == 0 leaves
+ *   an all-unknown grid.
+ * pi3_occupancy_observe: per cell that is not occupied (state != 2; an occupied cell keeps its byte), the centre
+ *   X = c ((double)(o + i) + 0.5) per axis, f64, and per view m in order pi3_voxel_carve's arithmetic, operation for
+ *   operation (views f64 [M][20] with views[m][17] the depth scale, planes fp16 bits [M][Hp][Wp], S = pixel_stride):
+ *   xc, yc, zc, u, v, pu, pv, zo and the same "no vote" cases;  r = zc - zo, lim = rel_tol zo + margin;  r < -lim is a
+ *   free vote (the view measured a surface behind the centre), |r| <= lim a hit vote;
+ *   state = 1 when free >= min_free_views && free > hit, else 0.
+ *   Then, for the views in order, the cell a camera stands in: centre_j = -((r0j t0 + r1j t1) + r2j t2),
+ *   k = floor(centre / c) per axis in f64; when that cell lies inside the grid and is unknown it becomes free (a view
+ *   cannot look through its own position, but a camera stood there).  The votes are left as they are.
+ *   free_votes, hit_votes uint32 [cells] (or NULL): the votes, 0 for an occupied cell;
+ *   counters: DEVICE uint64 [8] = cells, occupied, free, unknown, cells that are not occupied and no view voted on,
+ *   the unknown cells a camera's position made free (counted in free, not in unknown), 2 spare; zeroed by the call.  rel_tol finite and > 0, margin finite and >= 0, min_free_views >= 1, M >= 0 (0: no
+ *   cell is free), at most 2^39 cells.
+ * pi3_grid_edt: the exact squared Euclidean distance transform in cells, truncated at radius R in 1..255.  Sites are the
+ *   cells with state == 2 and, when unknown_is_obstacle != 0, those with state == 0.  d2 uint16 [cells] = the squared
+ *   distance to the nearest site when it is <= R^2, else 0xFFFF.  Three separable passes (x, y, z), each
+ *   out[i] = min over |d| <= R of in[i + d] + d^2 in integers with values above R^2 clamped to 0xFFFF; the passes
+ *   ping-pong between d2 and workspace (uint16 [cells], caller-owned, not d2), never in place.
+ * Bad arguments launch nothing and leave the outputs untouched.  No allocation, no synchronisation. */
+int pi3_occupancy_mark(const float* points, long P, float inv_cell, int ox, int oy, int oz, int nx, int ny, int nz,
+                       unsigned char* state, unsigned long long* counters, void* stream);
+int pi3_occupancy_observe(unsigned char* state, int nx, int ny, int nz, int ox, int oy, int oz, double cell,
+                          const double* views, int M, const unsigned short* planes, int Hp, int Wp, int pixel_stride,
+                          double rel_tol, double margin, int min_free_views, unsigned* free_votes, unsigned* hit_votes,
+                          unsigned long long* counters, void* stream);
+int pi3_grid_edt(const unsigned char* state, int nx, int ny, int nz, int radius, int unknown_is_obstacle,
+                 unsigned short* d2, unsigned short* workspace, void* stream);
+
 /* ---- nearest neighbours between two point clouds (csrc/cloud_nn.hip): an exact radius-bounded search through a
  * uniform grid of cells, for scoring a map against a reference cloud (map_eval.py).  The grid is a hash table of cells
  * in the voxel table's form: `capacity` slots of 64 B (a power of two, at least 2 n: ops.voxel_capacity), keyed by the

@@ -89,6 +89,24 @@ DENSE_MAP_FLAGS: Sequence[Tuple[str, Dict]] = (
     ("--dense-mesh", dict(SWITCH, help="write dense_mesh.ply: a triangle mesh of the fused dense map (surface nets on its "
                                        "voxel lattice; the chunks must have been created with --dense-voxel-size and "
                                        "--dense-normals)")),
+    # the occupancy grid (dense_map.MapOccupancy); the defaults are starting points, not measured optima
+    ("--occupancy-cell", dict(type=float, default=None, help="write occupancy.npz: the occupied / free / unknown grid of "
+                              "cells of this edge length (metres) around the dense map; a cell is free when enough depth "
+                              "keyframes looked through it (needs chunks created with --dense-voxel-size and "
+                              "--dense-depth-every; the keyframes sit where their chunk's similarity puts them: with "
+                              "bundle adjustment on use --map-follow-poses, or --no-bundle-adjust)")),
+    ("--occupancy-min-free-views", dict(type=int, default=2, help="keyframes that must have looked through a cell, and "
+                                        "more than measured a surface in it (2 is a starting point, not a measured "
+                                        "optimum)")),
+    ("--occupancy-tolerance", dict(type=float, default=0.03, help="relative depth difference (plus one cell) within "
+                                   "which a keyframe measured a surface in a cell (a starting point, not a measured "
+                                   "optimum)")),
+    ("--occupancy-clearance", dict(type=float, default=None, help="also the clearance field: the exact distance "
+                                   "(metres) from every cell to the nearest occupied cell, up to this many metres "
+                                   "(inf beyond; at most 255 cells)")),
+    ("--occupancy-unknown-obstacle", dict(SWITCH, help="unknown cells are obstacles of the clearance field too")),
+    ("--occupancy-max-cells", dict(type=int, default=1 << 27, help="refuse a grid of more cells than this (the message "
+                                   "names the cell size that fits)")),
 )
 
 
@@ -375,6 +393,11 @@ def run_online(a: argparse.Namespace) -> None:
             print("--dense_mesh needs --dense_voxel_size: no dense mesh")
         else:
             slam.save_dense_mesh(os.path.join(out_dir or ".", "dense_mesh.ply"))
+    if a.occupancy_cell is not None:
+        if a.dense_voxel_size is None:
+            print("--occupancy_cell needs --dense_voxel_size: no occupancy grid")
+        else:
+            slam.save_occupancy(os.path.join(out_dir or ".", "occupancy.npz"))
     if a.render_every is not None:
         if a.dense_voxel_size is None:
             print("--render_every needs --dense_voxel_size: no renders")

@@ -2,7 +2,8 @@
 // over the cells around a key, a slot's centroid and colour, and the row claim of the extractions.  Shared by voxel.hip
 // (fusion, extraction), voxel_normals.hip (the normals beside the table), voxel_clean.hip (neighbour-support and
 // component filters), voxel_mesh.hip (surface nets; its cell table is claimed with the same loop), voxel_carve.hip
-// (depth-keyframe carving) and cloud_nn.hip (a cell grid in the table's form).
+// (depth-keyframe carving), cloud_nn.hip (a cell grid in the table's form) and occupancy.hip (the quantiser alone: its
+// grid is dense).
 //
 // Slot (64 B, 8 x uint64): key | W | U0 U1 U2 | C0 C1 C2.
 //   key   the three voxel indices, each biased by 2^20 and packed at 21 bits (x << 42 | y << 21 | z); all ones = empty.

@@ -32,6 +32,11 @@ Optionally (MapFollower, csrc/cloud_follow.hip; map_follow_poses) stage 2 moves 
 point by point with the depth keyframes that saw the point, each by the move from its created to its final pose: the map
 then follows the per-view corrections of a bundle adjustment (tests/dense_follow_ref.py reproduces it byte for byte).
 Limitation without it: a cloud follows its chunk's similarity; per-view corrections of a bundle adjustment do not reach it.
+
+Optionally (MapOccupancy, csrc/occupancy.hip; occupancy_cell) stage 2 also reports the complement of the surface: a
+three-state grid (occupied / free / unknown) around the extracted map, voted on by the same depth keyframes, and with
+occupancy_clearance the exact distance from every cell to the nearest obstacle (tests/occupancy_ref.py reproduces both
+byte for byte) -> occupancy.npz.
 """
 from __future__ import annotations
 
@@ -373,6 +378,208 @@ class MapCarver:
         st = self.last_stats
         return (f"{st['views']} views, {st['carved']} of {st['voxels']} voxels carved (conflicts >= {self.min_conflicts}), "
                 f"{st['unvoted']} voxels no view voted on")
+
+
+@dataclass
+class OccupancyGrid:
+    """The three-state grid around a dense map (MapOccupancy.apply) and its clearance field.  Cell (ix, iy, iz) covers
+    cell (index_origin + i) .. cell (index_origin + i + 1) per axis; the arrays are (nz, ny, nx), x fastest."""
+    state: np.ndarray                           # u8 (nz,ny,nx): 0 unknown, 1 free, 2 occupied
+    index_origin: np.ndarray                    # i64 (3,): the cell index (x, y, z) of state[0, 0, 0]
+    cell: float
+    clearance: Optional[np.ndarray] = None      # f32 (nz,ny,nx): metres to the nearest obstacle's centre, inf beyond the radius
+    counts: Optional[Dict[str, int]] = None
+    settings: Optional[Dict] = None
+
+    @property
+    def origin(self) -> np.ndarray:
+        """The world corner of cell (0, 0, 0), f64 (3,)."""
+        return float(self.cell) * np.asarray(self.index_origin, np.float64)
+
+
+@dataclass
+class MapOccupancy:
+    """Where the dense map has verified empty space (csrc/occupancy.hip; reproduced byte for byte by
+    tests/occupancy_ref.py): a regular grid of `cell`-sized cells around the extracted map and the cameras.  A cell
+    that holds a map point is occupied.  Every other cell's centre is projected into every depth keyframe of every
+    chunk with the carver's arithmetic: a view that measured a surface BEHIND the centre (zc - zo < -(rel_tol zo +
+    margin)) looked through the cell and votes free, a view whose depth agrees within that limit votes hit.  Free:
+    free >= min_free_views and free > hit; everything else stays unknown.  margin is MARGIN_CELLS cells.  The cell a
+    camera stands in is free as well unless it is occupied: no view can look through its own position.
+
+    clearance (metres) also asks for the clearance field: the exact Euclidean distance from every cell's centre to the
+    nearest obstacle cell's centre (occupied; with unknown_is_obstacle also unknown), truncated at
+    R = ceil(clearance / cell) <= 255 cells (inf beyond).  The defaults are starting points, not measured optima.
+
+    Limitations, the carver's: a view sits where its chunk's similarity puts it, so with bundle adjustment on use a
+    MapFollower or run without; the planes are nearest-sampled; a cell only one view looked through stays unknown."""
+    cell: float
+    min_free_views: int = 2
+    rel_tol: float = 0.03
+    clearance: Optional[float] = None
+    unknown_is_obstacle: bool = False
+    max_cells: int = 1 << 27
+
+    MARGIN_CELLS = 1.0          # the absolute part of the tolerance, in cells
+
+    def __post_init__(self):
+        self.cell = float(self.cell)
+        if not (self.cell > 0.0 and math.isfinite(self.cell)):
+            raise ValueError(f"the occupancy cell must be a positive finite length, got {self.cell!r}")
+        for name in ("min_free_views", "max_cells"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer, float)) or int(v) != v:
+                raise ValueError(f"{name} must be an integer, got {v!r}")
+            setattr(self, name, int(v))
+        if not 1 <= self.min_free_views < 1 << 31:
+            raise ValueError(f"min_free_views must be in 1..2^31 - 1, got {self.min_free_views}")
+        if self.max_cells < 1:
+            raise ValueError(f"max_cells must be at least 1, got {self.max_cells}")
+        self.rel_tol = float(self.rel_tol)
+        if not (self.rel_tol > 0.0 and math.isfinite(self.rel_tol)):
+            raise ValueError(f"rel_tol must be a positive finite number, got {self.rel_tol!r}")
+        self.unknown_is_obstacle = bool(self.unknown_is_obstacle)
+        self.radius: Optional[int] = None
+        if self.clearance is not None:
+            self.clearance = float(self.clearance)
+            if not (self.clearance > 0.0 and math.isfinite(self.clearance)):
+                raise ValueError(f"the clearance must be a positive finite length, got {self.clearance!r}")
+            self.radius = int(math.ceil(self.clearance / self.cell))
+            if self.radius > ops.EDT_MAX_RADIUS:
+                raise ValueError(f"a clearance of {self.clearance} at cells of {self.cell} is {self.radius} cells: at "
+                                 f"most {ops.EDT_MAX_RADIUS} (clearance <= {ops.EDT_MAX_RADIUS * self.cell:g} or a "
+                                 "larger cell)")
+        self.last_stats: Optional[Dict[str, int]] = None
+        self.last_arrays: Optional[Dict[str, torch.Tensor]] = None
+
+    @classmethod
+    def from_options(cls, cell: Optional[float] = None, min_free_views: int = 2, rel_tol: float = 0.03,
+                     clearance: Optional[float] = None, unknown_is_obstacle: bool = False,
+                     max_cells: int = 1 << 27) -> Optional["MapOccupancy"]:
+        """The stage the occupancy_* options ask for; None without a cell size (the others alone ask for nothing)."""
+        return None if cell is None else cls(cell, min_free_views, rel_tol, clearance, unknown_is_obstacle, max_cells)
+
+    def settings(self) -> Dict:
+        return {"cell": self.cell, "min_free_views": self.min_free_views, "rel_tol": self.rel_tol,
+                "margin": self.MARGIN_CELLS * self.cell, "clearance": self.clearance, "radius": self.radius,
+                "unknown_is_obstacle": self.unknown_is_obstacle, "max_cells": self.max_cells}
+
+    @property
+    def pad(self) -> int:
+        """Cells around the bounding box: one, or R + 1 with a clearance field (a free cell at the box's edge then
+        still has its whole neighbourhood inside the grid)."""
+        return 1 if self.radius is None else self.radius + 1
+
+    @staticmethod
+    def point_cells(points: np.ndarray, cell: float) -> np.ndarray:
+        """The cells the mark kernel puts the rows of points f32 (P,3) in: floor(p * (float)(1 / cell)) per axis in
+        fp32, without the rows the quantiser drops (not finite, |k| >= 2^20) -> i64 (P',3)."""
+        p = np.asarray(points, np.float32).reshape(-1, 3)
+        with np.errstate(all="ignore"):
+            k = np.floor(p * np.float32(inverse_voxel(cell)))
+            ok = np.isfinite(p).all(1) & (np.abs(k) < np.float32(1 << 20)).all(1)
+        return k[ok].astype(np.int64)
+
+    @staticmethod
+    def view_cells(views: np.ndarray, cell: float) -> np.ndarray:
+        """The cells that hold the camera centres -R^T t of render.pack_cameras rows: floor(centre / cell), i64 (M,3)."""
+        v = np.asarray(views, np.float64).reshape(-1, ops.CARVE_VIEW_DOUBLES)
+        t0, t1, t2 = v[:, 3:4], v[:, 7:8], v[:, 11:12]
+        centres = -((v[:, 0:3] * t0 + v[:, 4:7] * t1) + v[:, 8:11] * t2)         # the kernel's order of operations
+        return np.floor(centres / float(cell)).astype(np.int64)
+
+    def _box(self, points: np.ndarray, views: np.ndarray, cell: float, pad: int) -> Tuple[np.ndarray, np.ndarray]:
+        ks = np.concatenate([self.point_cells(points, cell), self.view_cells(views, cell)])
+        if not len(ks) or not np.all(np.abs(ks) < 1 << 20):
+            raise ValueError("occupancy grid: no map point and no camera centre to put a grid around, or a camera "
+                             "centre beyond 2^20 cells")
+        lo, hi = ks.min(0) - pad, ks.max(0) + pad
+        return lo, hi - lo + 1
+
+    def bounds(self, points: np.ndarray, views: np.ndarray) -> Tuple[np.ndarray, Tuple[int, int, int]]:
+        """-> (index_origin i64 (3,), (nx, ny, nz)): the integer bounding box of the occupied cells and of the cells
+        holding the views' camera centres, padded by `pad` cells.  More than max_cells: ValueError naming the smallest
+        cell size (to three significant digits) that fits."""
+        lo, n = self._box(points, views, self.cell, self.pad)
+        total = int(n[0]) * int(n[1]) * int(n[2])
+        if total > self.max_cells:
+            raise ValueError(f"occupancy grid: {int(n[0])} x {int(n[1])} x {int(n[2])} = {total} cells of {self.cell:g} "
+                             f"exceed max_cells = {self.max_cells}; the smallest cell size that fits is "
+                             f"{self.smallest_cell(points, views):g}")
+        return lo, (int(n[0]), int(n[1]), int(n[2]))
+
+    def _fits(self, points: np.ndarray, views: np.ndarray, cell: float) -> bool:
+        pad = 1 if self.clearance is None else int(math.ceil(self.clearance / cell)) + 1
+        try:
+            _, n = self._box(points, views, cell, pad)
+        except ValueError:
+            return False
+        return int(n[0]) * int(n[1]) * int(n[2]) <= self.max_cells
+
+    def smallest_cell(self, points: np.ndarray, views: np.ndarray) -> float:
+        """The smallest cell size, rounded up to three significant digits, whose grid has at most max_cells cells."""
+        lo = hi = self.cell
+        while not self._fits(points, views, hi):
+            lo, hi = hi, hi * 2.0
+            if hi > self.cell * 2.0 ** 40:
+                raise ValueError("occupancy grid: no cell size fits max_cells")
+        for _ in range(40):
+            mid = 0.5 * (lo + hi)
+            lo, hi = (lo, mid) if self._fits(points, views, mid) else (mid, hi)
+        step = 10.0 ** (math.floor(math.log10(hi)) - 2)
+        out = math.ceil(hi / step) * step
+        while not self._fits(points, views, out):          # the count is not monotone in the cell size at this scale
+            out += step
+        return float(f"{out:.3g}")
+
+    def apply(self, points: np.ndarray, chunks: Iterable[Dict], device="cuda", arrays: bool = False
+              ) -> Optional[OccupancyGrid]:
+        """points f32 (V,3): the extracted map's rows.  -> the grid; None (after one notice line) when no chunk carries
+        depth planes.  Sets last_stats = the counts; arrays=True (tests) also keeps last_arrays = {free, hit} int32
+        per cell and d2 int16 with a clearance."""
+        views, planes, stride = MapCarver.chunk_views(chunks)
+        self.last_arrays = None
+        if planes is None:
+            print("   ℹ️  No depth keyframes in the chunks (create them with dense_depth_every): no occupancy grid")
+            self.last_stats = {"views": 0}
+            return None
+        points = np.ascontiguousarray(np.asarray(points, np.float32).reshape(-1, 3))
+        origin, (nx, ny, nz) = self.bounds(points, views)
+        dev = torch.device(device)
+        state = torch.empty((nz, ny, nx), dtype=torch.uint8, device=dev)
+        counters = torch.zeros(12, dtype=torch.int64, device=dev)
+        free = torch.empty((nz, ny, nx), dtype=torch.int32, device=dev) if arrays else None
+        hit = torch.empty((nz, ny, nx), dtype=torch.int32, device=dev) if arrays else None
+        pts = upload(torch.from_numpy(points), dev).contiguous()
+        ops.occupancy_mark(pts, inverse_voxel(self.cell), origin.tolist(), state, counters[:4])
+        ops.occupancy_observe(state, origin.tolist(), self.cell, upload(torch.from_numpy(views), dev).contiguous(),
+                              upload(planes, dev).contiguous(), stride, self.rel_tol, self.MARGIN_CELLS * self.cell,
+                              self.min_free_views, free, hit, counters[4:])
+        d2 = None
+        if self.radius is not None:
+            d2 = torch.empty((nz, ny, nx), dtype=torch.int16, device=dev)
+            ops.grid_edt(state, self.radius, self.unknown_is_obstacle, d2, torch.empty_like(d2))
+        c = [int(x) for x in counters.tolist()]
+        st = dict(views=int(len(views)), **dict(zip(ops.OCCUPANCY_MARK_COUNTERS, c[:3])),
+                  **dict(zip(ops.OCCUPANCY_OBSERVE_COUNTERS, c[4:10])))
+        self.last_stats = st
+        if arrays:
+            self.last_arrays = {"free": free, "hit": hit}
+            if d2 is not None:
+                self.last_arrays["d2"] = d2
+        clear = None
+        if d2 is not None:
+            raw = d2.cpu().numpy().view(np.uint16)
+            clear = (self.cell * np.sqrt(raw.astype(np.float64))).astype(np.float32)
+            clear[raw == ops.EDT_FAR] = np.float32(np.inf)
+        return OccupancyGrid(state.cpu().numpy(), np.asarray(origin, np.int64), self.cell, clear, dict(st),
+                             self.settings())
+
+    def summary(self) -> str:
+        st = self.last_stats
+        text = (f"{st['cells']} cells of {self.cell:g} from {st['views']} views: {st['occupied']} occupied, {st['free']} "
+                f"free (free views >= {self.min_free_views}), {st['unknown']} unknown, {st['unvoted']} no view voted on")
+        return text + (f"; clearance to {self.radius} cells" if self.radius is not None else "")
 
 
 def _scaled_rotations(poses: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
@@ -953,6 +1160,8 @@ class DenseMap:
     normals: Optional[np.ndarray] = None        # f32 (V,3), row for row; None when the clouds carry none
     mesh: Optional[Dict] = None                 # MapMesher.apply's mesh of the same table after the same keep mask
     mesh_error: Optional[Exception] = None      # why a mesh that was asked for is missing; its consumer raises it
+    occupancy: Optional[OccupancyGrid] = None   # MapOccupancy.apply's grid around these rows
+    occupancy_error: Optional[Exception] = None  # why a grid that was asked for is missing; its consumer raises it
 
 
 def _fuse_clouds(clouds, voxel_size: float, device: torch.device, follower: Optional[MapFollower] = None,
@@ -1055,12 +1264,15 @@ def _extract_map(fuser: VoxelFuser, acc: Optional[NormalAccumulator], keep: Opti
 
 def fuse_chunks(chunks: Iterable[Dict], device="cuda", *, voxel_size: Optional[float] = None,
                 cleaner: Optional[MapCleaner] = None, carver: Optional[MapCarver] = None,
-                mesher: Optional[MapMesher] = None, follower: Optional[MapFollower] = None) -> Optional[DenseMap]:
+                mesher: Optional[MapMesher] = None, occupancy: Optional[MapOccupancy] = None,
+                follower: Optional[MapFollower] = None) -> Optional[DenseMap]:
     """Stage 2: every chunk's dense_cloud moved by chunk_transform() and fused in the world frame (chunk 0's) -> the
     DenseMap; None when no chunk carries a cloud.  voxel_size: None takes the first cloud's.  carver (MapCarver) and
     cleaner (MapCleaner) choose, in that order, on the fused table which voxels the map keeps; mesher (MapMesher) also
     meshes them, which needs the clouds' normals.  follower (MapFollower): a cloud whose chunk carries depth keyframes
-    and its created poses follows its views' final poses instead of chunk_transform()."""
+    and its created poses follows its views' final poses instead of chunk_transform().  occupancy (MapOccupancy): the
+    extracted rows, after the keep mask, also get their occupancy grid (DenseMap.occupancy): it describes the map the PLY
+    shows.  A grid that fails leaves its exception in occupancy_error, so the map is still delivered."""
     chunks = list(chunks)
     owners = [c for c in chunks if c.get("dense_cloud") is not None]
     clouds = [(c["dense_cloud"], chunk_transform(c)) for c in owners]
@@ -1069,4 +1281,12 @@ def fuse_chunks(chunks: Iterable[Dict], device="cuda", *, voxel_size: Optional[f
     if voxel_size is None:
         voxel_size = float(clouds[0][0]["voxel_size"])
     fuser, acc = _fuse_clouds(clouds, voxel_size, torch.device(device), follower, owners)
-    return _extract_map(fuser, acc, _keep_mask(fuser, chunks, cleaner, carver), mesher)
+    dense = _extract_map(fuser, acc, _keep_mask(fuser, chunks, cleaner, carver), mesher)
+    if occupancy is not None:
+        try:
+            dense.occupancy = occupancy.apply(dense.points, chunks, device)
+            if dense.occupancy is not None:
+                print(f"   🧊 Occupancy grid: {occupancy.summary()}")
+        except Exception as e:  # noqa: BLE001
+            dense.occupancy_error = e
+    return dense

@@ -9,6 +9,8 @@ Pi3SLAMOnline.chunk_reconstructions).  Files and formats mirror slam/offline_rec
                           when the clouds carry normals
   dense_mesh.ply          (dense_mesh) a triangle mesh of the same fused table, after the same cleaner
                           (dense_map.MapMesher); needs the normals
+  occupancy.npz           (dense_occupancy) the occupied / free / unknown grid around that map and, when asked for, its
+                          clearance field (dense_map.MapOccupancy; write_occupancy)
   renders/                depth / colour images of that map, overview.png, cameras.json (write_renders; render.py); with
                           normals also normal_<frame>.png, shaded_<frame>.png and overview_shaded.png
 
@@ -197,6 +199,26 @@ def write_dense_mesh(mesh: Dict, path: str) -> int:
     return len(mesh["faces"])
 
 
+def write_occupancy(grid, path: str) -> int:
+    """A dense_map.OccupancyGrid -> a compressed .npz: state u8 (nz,ny,nx) (0 unknown, 1 free, 2 occupied; cell (ix, iy,
+    iz) covers origin + cell (i .. i + 1) per axis), index_origin i64 (3,) (x, y, z), origin f64 (3,) = cell index_origin
+    (the world corner of cell (0, 0, 0)), cell f64, clearance f32 (nz,ny,nx) in metres (inf beyond the radius) when the
+    grid has one, settings and counts as JSON strings; returns the number of free cells."""
+    arrays = {"state": np.asarray(grid.state, np.uint8), "index_origin": np.asarray(grid.index_origin, np.int64),
+              "origin": float(grid.cell) * np.asarray(grid.index_origin, np.float64), "cell": np.float64(grid.cell),
+              "settings": np.array(json.dumps(grid.settings or {}, sort_keys=True)),
+              "counts": np.array(json.dumps(grid.counts or {}, sort_keys=True))}
+    if grid.clearance is not None:
+        arrays["clearance"] = np.asarray(grid.clearance, np.float32)
+    with open(path, "wb") as f:         # (a file object: savez would append .npz to another suffix)
+        np.savez_compressed(f, **arrays)
+    n_free = int((arrays["state"] == 1).sum())
+    nz, ny, nx = arrays["state"].shape
+    print(f"✅ Saved the occupancy grid ({nx} x {ny} x {nz} cells of {float(grid.cell):g}, {n_free} free"
+          + (", with clearance" if grid.clearance is not None else "") + f") to: {path}")
+    return n_free
+
+
 def write_renders(chunks: Sequence[Dict], dense: Optional[DenseMap], out_dir: str, every: Optional[int], overview: bool,
                   min_weight: int = 1, splat_scale: float = 1.0, device="cuda",
                   dense_cleaner=None, dense_follower=None, dense_carver=None) -> Optional[Tuple[int, Dict[str, float]]]:
@@ -272,12 +294,14 @@ def write_renders(chunks: Sequence[Dict], dense: Optional[DenseMap], out_dir: st
 def write_outputs(chunks: Sequence[Dict], output_dir: str, device="cuda", render_every: Optional[int] = None,
                   render_overview: bool = False, render_min_weight: int = 1,
                   render_splat_scale: float = 1.0, dense_cleaner=None,
-                  dense_mesh: bool = False, dense_follower=None, dense_carver=None) -> Optional[Dict[str, float]]:
+                  dense_mesh: bool = False, dense_occupancy=None, dense_follower=None,
+                  dense_carver=None) -> Optional[Dict[str, float]]:
     """Every output file of stage 2 under output_dir; a file that fails is reported and the others are still written.
     Returns the seconds of write_renders when renders were written.  dense_cleaner (dense_map.MapCleaner): the dense
     map of the PLY and of the renders is the cleaned one.  dense_mesh: also dense_mesh.ply, the mesh of that map.
     dense_carver (dense_map.MapCarver): that map is first carved with the chunks' depth keyframes.  dense_follower
-    (dense_map.MapFollower): the chunks' clouds follow their keyframes' final poses instead of the chunks' similarities."""
+    (dense_map.MapFollower): the chunks' clouds follow their keyframes' final poses instead of the chunks' similarities.
+    dense_occupancy (dense_map.MapOccupancy): also occupancy.npz, the occupied / free / unknown grid around that map."""
     try:
         pts, cols = sparse_points_colors(chunks)
         if pts.size > 0:
@@ -298,7 +322,8 @@ def write_outputs(chunks: Sequence[Dict], output_dir: str, device="cuda", render
     dense = None
     try:
         dense = fuse_chunks(chunks, device, cleaner=dense_cleaner, carver=dense_carver,
-                            mesher=MapMesher() if dense_mesh else None, follower=dense_follower)
+                            mesher=MapMesher() if dense_mesh else None, occupancy=dense_occupancy,
+                            follower=dense_follower)
         if dense is not None:
             write_dense_points(dense, os.path.join(output_dir, "dense_points.ply"))
     except Exception as e:  # noqa: BLE001
@@ -315,6 +340,14 @@ def write_outputs(chunks: Sequence[Dict], output_dir: str, device="cuda", render
                 write_dense_mesh(dense.mesh, os.path.join(output_dir, "dense_mesh.ply"))
         except Exception as e:  # noqa: BLE001
             print(f"❌ Failed to save the dense mesh: {e}")
+    if dense_occupancy is not None and dense is not None:
+        try:
+            if dense.occupancy_error is not None:
+                raise dense.occupancy_error
+            if dense.occupancy is not None:
+                write_occupancy(dense.occupancy, os.path.join(output_dir, "occupancy.npz"))
+        except Exception as e:  # noqa: BLE001
+            print(f"❌ Failed to save the occupancy grid: {e}")
     if render_every is not None or render_overview:
         try:       # the renders draw the map that was just fused for the PLY
             done = write_renders(chunks, dense, os.path.join(output_dir, "renders"), render_every, render_overview,

@@ -28,7 +28,7 @@ from . import export
 from .alignment import align_and_refine_reconstructions, create_view_graph_matches, transform_chunk
 from .bundle_adjust import bundle_adjust_new_chunk, chunk_ba_args
 from .chunk_creator import OfflineChunkCreator, OfflineCreatorConfig
-from .dense_map import DenseMap, MapCarver, MapCleaner, MapFollower, MapMesher, fuse_chunks
+from .dense_map import DenseMap, MapCarver, MapCleaner, MapFollower, MapMesher, MapOccupancy, fuse_chunks
 from .image_io import ChunkImageDataset, calculate_target_size
 
 
@@ -58,6 +58,7 @@ class InOrderDrain:
 class Pi3SLAMOnline:
     dense_carver = None     # class default: the export methods also serve objects whose __init__ did not run (tests)
     dense_follower = None
+    dense_occupancy = None
 
     def __init__(self, model=None, chunk_length: int = 100, overlap: int = 10, device: str = "cuda",
                  conf_threshold: float = 0.5, undistortion_maps=None, cam_scale: float = 1.0,
@@ -74,7 +75,16 @@ class Pi3SLAMOnline:
                  dense_support_radius: int = 1, dense_min_component: Optional[int] = None, dense_normals: bool = False,
                  dense_depth_every: Optional[int] = None, dense_depth_stride: int = 2,
                  dense_carve_min_conflicts: Optional[int] = None, dense_carve_tolerance: float = 0.03,
+                 occupancy_cell: Optional[float] = None, occupancy_min_free_views: int = 2,
+                 occupancy_tolerance: float = 0.03, occupancy_clearance: Optional[float] = None,
+                 occupancy_unknown_obstacle: bool = False, occupancy_max_cells: int = 1 << 27,
                  map_follow_poses: bool = False, map_follow_tolerance: float = 0.03):
+        # occupancy_cell: save_occupancy writes the occupied / free / unknown grid around the fused dense map, voted on by
+        # the chunks' depth keyframes (dense_depth_every), with occupancy_clearance its clearance field
+        # (dense_map.MapOccupancy; off by default).  The defaults are starting points, not measured optima
+        self.dense_occupancy = MapOccupancy.from_options(occupancy_cell, occupancy_min_free_views, occupancy_tolerance,
+                                                         occupancy_clearance, occupancy_unknown_obstacle,
+                                                         occupancy_max_cells)
         # dense_depth_every: the chunks keep depth keyframes; dense_carve_min_conflicts: the fused dense map of
         # save_dense_map / save_dense_mesh / save_renders is carved with them first (dense_map.MapCarver; off by default)
         self.dense_carver = MapCarver.from_options(dense_carve_min_conflicts, dense_carve_tolerance)
@@ -309,11 +319,12 @@ class Pi3SLAMOnline:
             pts, cols = pts[sel], (cols[sel] if cols.size else cols)
         export.write_ply(pts, cols if cols.size else np.ones_like(pts), save_path)
 
-    def _fused_map(self, mesher=None) -> DenseMap:
+    def _fused_map(self, mesher=None, occupancy=None) -> DenseMap:
         """The chunks' dense clouds fused, carved and cleaned as this object's options say (with normals under
         dense_normals; mesher: and its mesh).  Fused anew on every call."""
         dense = fuse_chunks(self.chunk_reconstructions, str(self.device), cleaner=self.dense_cleaner,
-                            carver=self.dense_carver, mesher=mesher, follower=self.dense_follower)
+                            carver=self.dense_carver, mesher=mesher, occupancy=occupancy,
+                            follower=self.dense_follower)
         if dense is None:
             raise RuntimeError("no dense clouds: construct Pi3SLAMOnline with dense_voxel_size")
         return dense
@@ -332,6 +343,18 @@ class Pi3SLAMOnline:
         if dense.mesh_error is not None:
             raise dense.mesh_error
         return export.write_dense_mesh(dense.mesh, save_path) if dense.mesh is not None else None
+
+    def save_occupancy(self, save_path: str) -> Optional[int]:
+        """The occupancy grid of the fused dense map (dense_map.MapOccupancy: occupancy_cell, with occupancy_clearance
+        its clearance field) -> a compressed .npz (export.write_occupancy); returns the number of free cells.  The chunks
+        must carry depth keyframes (dense_depth_every): without them one line says so, no file is written and None is
+        returned."""
+        if self.dense_occupancy is None:
+            raise RuntimeError("no occupancy stage: construct Pi3SLAMOnline with occupancy_cell")
+        dense = self._fused_map(occupancy=self.dense_occupancy)
+        if dense.occupancy_error is not None:
+            raise dense.occupancy_error
+        return export.write_occupancy(dense.occupancy, save_path) if dense.occupancy is not None else None
 
     def save_renders(self, out_dir: str, every: Optional[int] = 10, overview: bool = True, min_weight: int = 1,
                      splat_scale: float = 1.0) -> int:

@@ -929,6 +929,92 @@ def cloud_follow_views(points: torch.Tensor, normals: Optional[torch.Tensor], vi
     _L.check(rc, "pi3_cloud_follow_views")
 
 
+# ---- occupancy grid and clearance field of the dense map (csrc/occupancy.hip)
+OCCUPANCY_UNKNOWN, OCCUPANCY_FREE, OCCUPANCY_OCCUPIED = 0, 1, 2
+OCCUPANCY_MARK_COUNTERS = ("marked", "dropped", "outside")
+OCCUPANCY_OBSERVE_COUNTERS = ("cells", "occupied", "free", "unknown", "unvoted", "camera_cells_freed")
+EDT_MAX_RADIUS = 255
+EDT_FAR = 0xFFFF
+
+
+def _grid_state(state: torch.Tensor) -> Tuple[int, int, int]:
+    assert state.dtype == torch.uint8 and state.is_contiguous() and state.ndim == 3
+    return int(state.shape[2]), int(state.shape[1]), int(state.shape[0])
+
+
+def occupancy_mark(points: torch.Tensor, inv_cell: float, origin, state: torch.Tensor, counters: torch.Tensor) -> None:
+    """state uint8 (nz,ny,nx) is zeroed, then every row of points f32 (P,3) goes through the voxel quantiser at inv_cell
+    per axis (k = floor(p * inv_cell) in fp32) and the cell k - origin, when it is inside the grid, becomes 2 (occupied).
+    origin: three integers (ox, oy, oz).  counters int64 (4,) = OCCUPANCY_MARK_COUNTERS (zeroed by the call)."""
+    lib = _L.load()
+    nx, ny, nz = _grid_state(state)
+    dev = state.device
+    assert points.dtype == torch.float32 and points.is_contiguous() and points.ndim == 2 and points.shape[1] == 3
+    assert points.device == dev
+    assert counters.dtype == torch.int64 and counters.is_contiguous() and counters.numel() >= 4 and counters.device == dev
+    ox, oy, oz = (int(v) for v in origin)
+    if state.numel() == 0:      # empty tensors have no address to pass
+        counters[:4] = 0
+        return
+    P = int(points.shape[0])
+    rc = lib.pi3_occupancy_mark(points.data_ptr() if P else None, P, float(inv_cell), ox, oy, oz, nx, ny, nz,
+                                state.data_ptr(), counters.data_ptr(), _L.stream_ptr())
+    _L.check(rc, "pi3_occupancy_mark")
+
+
+def occupancy_observe(state: torch.Tensor, origin, cell: float, views: torch.Tensor, planes: torch.Tensor,
+                      pixel_stride: int, rel_tol: float, margin: float, min_free_views: int,
+                      free_votes: Optional[torch.Tensor], hit_votes: Optional[torch.Tensor],
+                      counters: torch.Tensor) -> None:
+    """Per cell of state uint8 (nz,ny,nx) that is not occupied (!= 2): the centre cell ((origin + i) + 0.5) per axis is
+    projected into every view with voxel_carve's arithmetic (views f64 (M,20), planes fp16 (M,H',W')); r = zc - zo,
+    lim = rel_tol zo + margin; r < -lim is a free vote, |r| <= lim a hit vote; the cell becomes 1 (free) when free >=
+    min_free_views and free > hit, else 0 (unknown); after the vote an unknown cell that holds a view's camera centre
+    (floor(-R^T t / cell)) becomes free as well.  free_votes / hit_votes int32 (nz,ny,nx) (the uint32 votes) or
+    None; counters int64 (8,) = OCCUPANCY_OBSERVE_COUNTERS (zeroed by the call)."""
+    lib = _L.load()
+    nx, ny, nz = _grid_state(state)
+    dev = state.device
+    assert views.dtype == torch.float64 and views.is_contiguous() and views.ndim == 2
+    assert views.shape[1] == CARVE_VIEW_DOUBLES and views.device == dev
+    M = int(views.shape[0])
+    assert planes.dtype == torch.float16 and planes.is_contiguous() and planes.ndim == 3 and planes.device == dev
+    assert int(planes.shape[0]) == M and M < 1 << 31
+    Hp, Wp = int(planes.shape[1]), int(planes.shape[2])
+    for t in (free_votes, hit_votes):
+        if t is not None:
+            assert t.dtype == torch.int32 and t.is_contiguous() and t.shape == state.shape and t.device == dev
+    assert counters.dtype == torch.int64 and counters.is_contiguous() and counters.numel() >= 8 and counters.device == dev
+    ox, oy, oz = (int(v) for v in origin)
+    if state.numel() == 0:      # empty tensors have no address to pass
+        counters[:8] = 0
+        return
+    rc = lib.pi3_occupancy_observe(state.data_ptr(), nx, ny, nz, ox, oy, oz, float(cell), views.data_ptr() if M else None,
+                                   M, planes.data_ptr() if M else None, Hp, Wp, int(pixel_stride), float(rel_tol),
+                                   float(margin), int(min_free_views), _L.ptr(free_votes), _L.ptr(hit_votes),
+                                   counters.data_ptr(), _L.stream_ptr())
+    _L.check(rc, "pi3_occupancy_observe")
+
+
+def grid_edt(state: torch.Tensor, radius: int, unknown_is_obstacle: bool, d2: torch.Tensor,
+             workspace: torch.Tensor) -> None:
+    """The exact squared Euclidean distance transform of state uint8 (nz,ny,nx), in cells, truncated at `radius` cells
+    (1..EDT_MAX_RADIUS): d2 int16 (nz,ny,nx) (the uint16 values) = the squared distance to the nearest site (state 2,
+    and state 0 when unknown_is_obstacle) when it is <= radius^2, else EDT_FAR.  workspace: int16, the same size, not
+    d2 (the three passes ping-pong between the two)."""
+    lib = _L.load()
+    nx, ny, nz = _grid_state(state)
+    dev = state.device
+    for t in (d2, workspace):
+        assert t.dtype == torch.int16 and t.is_contiguous() and t.numel() == state.numel() and t.device == dev
+    assert d2.data_ptr() != workspace.data_ptr() or state.numel() == 0
+    if state.numel() == 0:      # empty tensors have no address to pass
+        return
+    rc = lib.pi3_grid_edt(state.data_ptr(), nx, ny, nz, int(radius), 1 if unknown_is_obstacle else 0, d2.data_ptr(),
+                          workspace.data_ptr(), _L.stream_ptr())
+    _L.check(rc, "pi3_grid_edt")
+
+
 # ---- nearest neighbours between two clouds (csrc/cloud_nn.hip)
 CLOUD_INDEX_COUNTERS = ("dropped", "cells", "no_slot", "largest_cell")
 CLOUD_NEAREST_COUNTERS = ("dropped", "matched", "beyond", "evaluations")

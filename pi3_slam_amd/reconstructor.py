@@ -40,6 +40,9 @@ class OfflineReconstructor:
                  loop_closure: bool = False, loop_min_gap: int = 2, loop_min_overlap: float = 0.3,
                  loop_max_edges: int = 3, loop_max_dist: float = 0.1, loop_max_rms: float = 0.03,
                  loop_min_pair_fraction: float = 0.2, loop_cell: float = 0.16,
+                 occupancy_cell: Optional[float] = None, occupancy_min_free_views: int = 2,
+                 occupancy_tolerance: float = 0.03, occupancy_clearance: Optional[float] = None,
+                 occupancy_unknown_obstacle: bool = False, occupancy_max_cells: int = 1 << 27,
                  map_follow_poses: bool = False, map_follow_tolerance: float = 0.03):
         self.chunk_dir, self.output_dir = chunk_dir, output_dir
         # loop_closure: before the outputs are written, chunks that see the same surface are found by the co-occupancy
@@ -64,6 +67,14 @@ class OfflineReconstructor:
         # (chunks created with dense_depth_every) looked through (dense_map.MapCarver); off by default: no carver.  The
         # keyframes sit where the chunks' similarities put them: use it with bundle_adjust=False or map_follow_poses
         self.dense_carver = MapCarver.from_options(dense_carve_min_conflicts, dense_carve_tolerance)
+        # occupancy_cell: also occupancy.npz, the occupied / free / unknown grid of cells of this size around the dense
+        # map, voted on by the same depth keyframes, and with occupancy_clearance (metres) its clearance field
+        # (dense_map.MapOccupancy); off by default: no stage.  The same caveat: bundle_adjust=False or map_follow_poses.
+        # The defaults are starting points, not measured optima
+        from .dense_map import MapOccupancy
+        self.dense_occupancy = MapOccupancy.from_options(occupancy_cell, occupancy_min_free_views, occupancy_tolerance,
+                                                         occupancy_clearance, occupancy_unknown_obstacle,
+                                                         occupancy_max_cells)
         # map_follow_poses: the dense map follows the final poses view by view (dense_map.MapFollower): every chunk keeps
         # the camera_poses of its file as '_poses_created', and a cloud point moves with the depth keyframes (chunks
         # created with dense_depth_every) that saw it; chunks without keyframes keep their similarity.  Off by
@@ -212,7 +223,8 @@ class OfflineReconstructor:
                         json.dump(self.loop_closure_info, f, indent=1, default=float)
             seconds = export.write_outputs(done, self.output_dir, self.device, self.render_every, self.render_overview,
                                            self.render_min_weight, self.render_splat_scale, self.dense_cleaner,
-                                           self.dense_mesh, dense_carver=self.dense_carver,
+                                           self.dense_mesh, dense_occupancy=self.dense_occupancy,
+                                           dense_carver=self.dense_carver,
                                            dense_follower=self.dense_follower)
             if seconds is not None:
                 self.render_seconds = seconds

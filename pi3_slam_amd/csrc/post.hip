@@ -320,8 +320,12 @@ extern "C" int pi3_apply_scale(const float* scale_dev, float* local_points, floa
     pi3_set_error("pi3_apply_scale: bad arguments");
     return PI3_ERR_ARG;
   }
-  long blocks = (n3 + 255) / 256;
+  // the grid covers the 3 F translation entries as well as the n3 floats (one thread each; the maps go by stride):
+  // sized from n3 alone, a call with n3 < 3 F left the later poses unscaled
+  const long work = n3 > 3L * F ? n3 : 3L * F;
+  long blocks = (work + 255) / 256;
   if (blocks > 256 * 16) blocks = 256 * 16;
+  if (blocks * 256 < 3L * F) blocks = (3L * F + 255) / 256;
   hipLaunchKernelGGL(apply_scale_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, scale_dev,
                      local_points, points, n3, poses, F);
   return pi3_check_launch("apply_scale");

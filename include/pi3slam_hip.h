@@ -542,6 +542,36 @@ int pi3_occupancy_observe(unsigned char* state, int nx, int ny, int nz, int ox, 
 int pi3_grid_edt(const unsigned char* state, int nx, int ny, int nz, int radius, int unknown_is_obstacle,
                  unsigned short* d2, unsigned short* workspace, void* stream);
 
+/* ---- routes through the occupancy grid (csrc/grid_route.hip): the same grid layout; integers only.  walk uint8 [cells]:
+ * 1 = traversable.  The graph: the 26 moves d in {-1, 0, 1}^3 \ {0} at the costs 12, 17, 21 for one, two, three non-zero
+ * components; a move c -> c + d is allowed only when every cell c + (a dx, b dy, e dz), a, b, e in {0, 1}, lies inside the
+ * grid and is traversable (no corner is cut; the rule is symmetric).  dist uint32 [cells]: the cheapest move sequence
+ * from any source, 0xFFFFFFFF when there is none.  1 <= n < 2^21 per axis and at most 2^27 cells, so that 21 (cells - 1)
+ * stays below the far mark.
+ * pi3_grid_route_init: walk = (state == 1; with through_unknown != 0: state != 2) and, when d2 is given (pi3_grid_edt's
+ *   field, uint16 [cells]), d2 >= min_d2 (0 .. 65 025; the field's far mark 0xFFFF passes; min_d2 > 0 needs d2).
+ *   dist = 0xFFFFFFFF everywhere, then 0 at every source: sources int64 [Ns] are linear indices; one outside [0, cells)
+ *   or on a cell that is not traversable is only counted.  counters: DEVICE uint64 [4] = traversable cells, sources
+ *   accepted (a duplicate counts again), sources not traversable, sources outside; zeroed by the call.  0 <= Ns < 2^39;
+ *   Ns == 0 leaves an all-far field and sources may be NULL.
+ * pi3_grid_route_sweep: one relaxation sweep, a workgroup per tile of 8 x 8 x 8 cells: the tile's cells are relaxed to
+ *   their fixed point against each other and against the tile's one-cell halo as it is read; cells that got lower are
+ *   stored, and *changed (DEVICE int32, never cleared here) becomes 1 when any did.  The caller repeats the call until a
+ *   sweep leaves its `changed` word 0: dist is then the shortest-distance field, whatever order the tiles ran in (values
+ *   are costs of real move sequences, only decrease, and 32-bit words do not tear).
+ * pi3_grid_route_trace: one wave walks from `goal` (a linear index) back to a source over a settled dist: at every cell
+ *   the neighbour n with an allowed move and dist[n] + w == dist[cur] that has the smallest linear index.  path int64
+ *   [cap]: the linear indices from the goal to the source; *length (DEVICE int64) = their number, 0 when the goal is not
+ *   traversable or not reachable (or dist is not settled), -needed when cap is too small: path is then left untouched.
+ *   cap = dist[goal] / 12 + 1 always suffices.
+ * Bad arguments launch nothing and leave the outputs untouched.  No allocation, no synchronisation. */
+int pi3_grid_route_init(const unsigned char* state, const unsigned short* d2, int min_d2, int through_unknown, int nx,
+                        int ny, int nz, const long* sources, long Ns, unsigned char* walk, unsigned* dist,
+                        unsigned long long* counters, void* stream);
+int pi3_grid_route_sweep(const unsigned char* walk, int nx, int ny, int nz, unsigned* dist, int* changed, void* stream);
+int pi3_grid_route_trace(const unsigned char* walk, const unsigned* dist, int nx, int ny, int nz, long goal, long* path,
+                         long cap, long* length, void* stream);
+
 /* ---- nearest neighbours between two point clouds (csrc/cloud_nn.hip): an exact radius-bounded search through a
  * uniform grid of cells, for scoring a map against a reference cloud (map_eval.py).  The grid is a hash table of cells
  * in the voxel table's form: `capacity` slots of 64 B (a power of two, at least 2 n: ops.voxel_capacity), keyed by the

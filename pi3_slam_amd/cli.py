@@ -8,6 +8,8 @@
 
   python -m pi3_slam_amd.cli online --image_dir /data/seq --output_path /data/seq_result --chunk_length 100 --overlap 20 \
          --model_path /ckpt/pi3 --save_tum [--cam_dist_path calib.json] [--use_inverse_depth]
+  python -m pi3_slam_amd.cli route --occupancy OUT/occupancy.npz --output DIR --from-trajectory OUT/trajectory_tum.txt \\
+         [--goal X Y Z] [--radius 0.2]
 
 Under `python -m torch.distributed.run --nproc-per-node G -m pi3_slam_amd.cli ...` every stage shards over the G GPUs.
 """
@@ -264,6 +266,23 @@ EVAL_SWITCHES = (("--json", "print the result as one JSON line instead of the ta
                                     "exact point-to-triangle distance as target (default: by its vertices)"))
 
 
+# route: this build's own sub-command (grid_route.py) on the occupancy.npz of reconstruct or online
+ROUTE_FLAGS: Sequence[Tuple[str, Dict]] = (
+    ("--occupancy", dict(REQ, help="occupancy.npz of `reconstruct` or `online` (--occupancy-cell)")),
+    ("--output", dict(REQ, help="directory for route.npz and, with --goal, route.json and route.ply")),
+    ("--start", dict(type=float, nargs=3, default=None, metavar=("X", "Y", "Z"), help="the source: one world point")),
+    ("--from-trajectory", dict(default=None, help="the sources: the position of every pose of this TUM trajectory "
+                                                  "(poses on cells that are not traversable are skipped and counted)")),
+    ("--goal", dict(type=float, nargs=3, default=None, metavar=("X", "Y", "Z"), help="also the shortest safe way to this "
+                                                                                   "world point")),
+    ("--radius", dict(type=float, default=0.0, help="the body's radius in metres: only cells with at least this "
+                                                    "clearance are traversable (default 0: every free cell)")),
+    ("--device", dict(default="cuda")),
+)
+ROUTE_SWITCHES = (("--through-unknown", "unknown cells are traversable too, and no obstacles of the clearance "
+                                        "(default: only verified free space, kept away from unknown space)"),)
+
+
 def list_images(root: str) -> List[str]:
     """Folder -> its png, jpg, jpeg, bmp files (each extension group sorted, groups in that order); file -> its
     non-empty lines; anything else is a glob pattern."""
@@ -281,7 +300,7 @@ def build_parser() -> argparse.ArgumentParser:
                                   ("reconstruct", tuple(RECON_FLAGS) + tuple(DENSE_MAP_FLAGS) + tuple(LOOP_FLAGS), RECON_SWITCHES),
                                   ("online", tuple(ONLINE_FLAGS) + ONLINE_DENSE_FLAGS + ONLINE_FOLLOW_FLAGS,
                                    ONLINE_SWITCHES),
-                                  ("evaluate-map", EVAL_FLAGS, EVAL_SWITCHES)):
+                                  ("evaluate-map", EVAL_FLAGS, EVAL_SWITCHES), ("route", ROUTE_FLAGS, ROUTE_SWITCHES)):
         p = sub.add_parser(name)
         for flag, kw in flags:
             p.add_argument(flag, **kw)
@@ -475,10 +494,37 @@ def run_evaluate_map(a: argparse.Namespace) -> None:
     print(json.dumps(map_eval.public(res)) if a.json else map_eval.format_table(res))
 
 
+def run_route(a: argparse.Namespace) -> None:
+    from . import export
+    from .grid_route import GridRouter, read_tum_positions
+    if (a.start is None) == (a.from_trajectory is None):
+        raise SystemExit("route: give --start X Y Z or --from-trajectory TRAJ.tum (one of them)")
+    try:
+        router = GridRouter(a.radius, a.through_unknown)
+        grid = export.read_occupancy(a.occupancy)
+        sources = [a.start] if a.start is not None else read_tum_positions(a.from_trajectory)
+        field = router.field(grid, sources, a.device)
+        route = router.path(field, a.goal) if a.goal is not None else None
+    except (ValueError, OSError) as e:
+        raise SystemExit(f"route: {e}")
+    export.write_route(field, route, a.output)
+    c = field.counts
+    text = (f"route: {c['traversable']} traversable cells, {c['reachable']} reachable from {c['sources_accepted']} "
+            f"sources ({c['sources_blocked']} not traversable, {c['sources_outside']} outside) in {c['sweeps']} sweeps")
+    if a.goal is not None:
+        if route is None:
+            text += "; the goal cannot be reached"
+        else:
+            text += f"; {len(route.waypoints)} waypoints, {route.length_m:.3f} m"
+            if route.min_clearance_m is not None:
+                text += f", clearance >= {route.min_clearance_m:.3f} m"
+    print(text)
+
+
 def main(argv=None) -> None:
     a = build_parser().parse_args(argv)
     {"create": run_create, "reconstruct": run_reconstruct, "online": run_online,
-     "evaluate-map": run_evaluate_map}[a.command](a)
+     "evaluate-map": run_evaluate_map, "route": run_route}[a.command](a)
 
 
 if __name__ == "__main__":

@@ -14,7 +14,10 @@ Pi3SLAMOnline.chunk_reconstructions).  Files and formats mirror slam/offline_rec
   renders/                depth / colour images of that map, overview.png, cameras.json (write_renders; render.py); with
                           normals also normal_<frame>.png, shaded_<frame>.png and overview_shaded.png
 
-write_outputs writes them all, in that order.  A chunk needs dist.COLLECT_KEYS for it, nothing else."""
+write_outputs writes them all, in that order.  A chunk needs dist.COLLECT_KEYS for it, nothing else.
+
+Outside stage 2, for `cli route` (grid_route.py): read_occupancy reads occupancy.npz back, write_route writes route.npz
+(the distance field) and, with a goal, route.json and route.ply."""
 from __future__ import annotations
 
 import json
@@ -217,6 +220,54 @@ def write_occupancy(grid, path: str) -> int:
     print(f"✅ Saved the occupancy grid ({nx} x {ny} x {nz} cells of {float(grid.cell):g}, {n_free} free"
           + (", with clearance" if grid.clearance is not None else "") + f") to: {path}")
     return n_free
+
+
+def read_occupancy(path: str):
+    """The inverse of write_occupancy: occupancy.npz -> a dense_map.OccupancyGrid (state, index_origin, cell, the
+    clearance when the file has one, settings, counts)."""
+    from .dense_map import OccupancyGrid
+    with np.load(path) as z:
+        for name in ("state", "index_origin", "cell"):
+            if name not in z.files:
+                raise ValueError(f"{path}: no '{name}' array: not an occupancy grid written by write_occupancy")
+        state = np.ascontiguousarray(z["state"], np.uint8)
+        if state.ndim != 3:
+            raise ValueError(f"{path}: state must be (nz, ny, nx), got {state.shape}")
+        clear = np.asarray(z["clearance"], np.float32) if "clearance" in z.files else None
+        text = {k: json.loads(str(z[k])) if k in z.files else None for k in ("counts", "settings")}
+        return OccupancyGrid(state, np.asarray(z["index_origin"], np.int64).reshape(3), float(z["cell"]), clear,
+                             text["counts"] or None, text["settings"] or None)
+
+
+ROUTE_COLOR = (255, 64, 0)          # route.ply's waypoints
+
+
+def write_route(field, route, out_dir: str) -> None:
+    """A grid_route.RouteField -> <out_dir>/route.npz: distance f32 (nz,ny,nx) in metres (inf when unreachable), cost
+    u32 (12 per cell edge, 0xFFFFFFFF when unreachable), index_origin i64 (3,), origin f64 (3,), cell f64, settings and
+    counts as JSON strings.  With a grid_route.Route also route.json (waypoints source -> goal, cost, length_m,
+    min_clearance_m, settings) and route.ply, the waypoints as coloured points for viewing next to dense_points.ply."""
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(out_dir, "route.npz"), "wb") as f:
+        np.savez_compressed(f, distance=np.asarray(field.distance, np.float32), cost=np.asarray(field.cost, np.uint32),
+                            index_origin=np.asarray(field.index_origin, np.int64),
+                            origin=float(field.cell) * np.asarray(field.index_origin, np.float64),
+                            cell=np.float64(field.cell),
+                            settings=np.array(json.dumps(field.settings or {}, sort_keys=True)),
+                            counts=np.array(json.dumps(field.counts or {}, sort_keys=True)))
+    text = f"✅ Saved the route field ({field.counts.get('reachable')} reachable cells) to: {out_dir}/route.npz"
+    if route is not None:
+        clear = route.min_clearance_m
+        record = {"waypoints": [[float(v) for v in p] for p in route.waypoints], "cost": int(route.cost),
+                  "length_m": float(route.length_m),
+                  "min_clearance_m": None if clear is None else (float(clear) if np.isfinite(clear) else "inf"),
+                  "settings": route.settings}
+        with open(os.path.join(out_dir, "route.json"), "w") as f:
+            json.dump(record, f, indent=1)
+        write_ply(route.waypoints, np.tile(np.array(ROUTE_COLOR, np.uint8), (len(route.waypoints), 1)),
+                  os.path.join(out_dir, "route.ply"))
+        text += f", the route of {len(route.waypoints)} waypoints to route.json and route.ply"
+    print(text)
 
 
 def write_renders(chunks: Sequence[Dict], dense: Optional[DenseMap], out_dir: str, every: Optional[int], overview: bool,

@@ -100,6 +100,9 @@ SIGNATURES = {
     "pi3_occupancy_mark": [_vp, _l, _f] + [_i] * 6 + [_vp, _vp, _vp],
     "pi3_occupancy_observe": [_vp] + [_i] * 6 + [_d, _vp, _i, _vp, _i, _i, _i, _d, _d, _i, _vp, _vp, _vp, _vp],
     "pi3_grid_edt": [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp],
+    "pi3_grid_route_init": [_vp, _vp, _i, _i, _i, _i, _i, _vp, _l, _vp, _vp, _vp, _vp],
+    "pi3_grid_route_sweep": [_vp, _i, _i, _i, _vp, _vp, _vp],
+    "pi3_grid_route_trace": [_vp, _vp, _i, _i, _i, _l, _vp, _l, _vp, _vp],
     "pi3_pose_graph_workspace": [_i, _i, C.POINTER(_l)],
     "pi3_pose_graph_sim3": [_vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _l, _vp, _vp],
     "pi3_set_knob": [C.c_char_p, _l],

@@ -1015,6 +1015,67 @@ def grid_edt(state: torch.Tensor, radius: int, unknown_is_obstacle: bool, d2: to
     _L.check(rc, "pi3_grid_edt")
 
 
+# ---- routes through the occupancy grid (csrc/grid_route.hip)
+ROUTE_FAR = 0xFFFFFFFF
+ROUTE_COSTS = (12, 17, 21)              # a move along one, two, three axes
+ROUTE_MAX_CELLS = 1 << 27               # 21 (cells - 1) stays below ROUTE_FAR
+ROUTE_INIT_COUNTERS = ("traversable", "sources_accepted", "sources_blocked", "sources_outside")
+
+
+def _route_grid(walk: torch.Tensor, dist: torch.Tensor) -> Tuple[int, int, int]:
+    nx, ny, nz = _grid_state(walk)
+    assert dist.dtype == torch.int32 and dist.is_contiguous() and dist.shape == walk.shape and dist.device == walk.device
+    assert 0 < walk.numel() <= ROUTE_MAX_CELLS, f"{walk.numel()} cells: 1 .. 2^27"
+    return nx, ny, nz
+
+
+def grid_route_init(state: torch.Tensor, d2: Optional[torch.Tensor], min_d2: int, through_unknown: bool,
+                    sources: torch.Tensor, walk: torch.Tensor, dist: torch.Tensor, counters: torch.Tensor) -> None:
+    """walk uint8 (nz,ny,nx) = 1 where state uint8 (nz,ny,nx) is free (with through_unknown: not occupied) and, with
+    d2 int16 (nz,ny,nx) (grid_edt's field, the uint16 values), d2 >= min_d2; dist int32 (nz,ny,nx) (the uint32 values)
+    = ROUTE_FAR everywhere, then 0 at every entry of sources int64 (Ns,) (linear indices) that lies inside the grid on
+    a traversable cell.  counters int64 (4,) = ROUTE_INIT_COUNTERS (zeroed by the call)."""
+    lib = _L.load()
+    nx, ny, nz = _route_grid(walk, dist)
+    dev = state.device
+    assert state.dtype == torch.uint8 and state.is_contiguous() and state.shape == walk.shape and walk.device == dev
+    if d2 is not None:
+        assert d2.dtype == torch.int16 and d2.is_contiguous() and d2.shape == state.shape and d2.device == dev
+    assert d2 is not None or int(min_d2) == 0, "min_d2 needs the clearance field d2"
+    assert sources.dtype == torch.int64 and sources.is_contiguous() and sources.ndim == 1 and sources.device == dev
+    assert counters.dtype == torch.int64 and counters.is_contiguous() and counters.numel() >= 4 and counters.device == dev
+    Ns = int(sources.shape[0])
+    rc = lib.pi3_grid_route_init(state.data_ptr(), _L.ptr(d2), int(min_d2), 1 if through_unknown else 0, nx, ny, nz,
+                                 sources.data_ptr() if Ns else None, Ns, walk.data_ptr(), dist.data_ptr(),
+                                 counters.data_ptr(), _L.stream_ptr())
+    _L.check(rc, "pi3_grid_route_init")
+
+
+def grid_route_sweep(walk: torch.Tensor, dist: torch.Tensor, changed: torch.Tensor) -> None:
+    """One relaxation sweep over dist int32 (nz,ny,nx) (tiles of 8 x 8 x 8 cells, each relaxed to its fixed point);
+    changed int32 (1,) becomes 1 when a cell got lower (the caller zeroes it)."""
+    lib = _L.load()
+    nx, ny, nz = _route_grid(walk, dist)
+    assert changed.dtype == torch.int32 and changed.numel() == 1 and changed.device == walk.device
+    rc = lib.pi3_grid_route_sweep(walk.data_ptr(), nx, ny, nz, dist.data_ptr(), changed.data_ptr(), _L.stream_ptr())
+    _L.check(rc, "pi3_grid_route_sweep")
+
+
+def grid_route_trace(walk: torch.Tensor, dist: torch.Tensor, goal: int, path: torch.Tensor, length: torch.Tensor) -> None:
+    """The cheapest way from the cell `goal` (a linear index inside the grid) back to a source over the settled dist:
+    path int64 (cap,) gets the linear indices goal .. source, length int64 (1,) their number: 0 when there is no way,
+    -needed when path is too short (it is then left untouched)."""
+    lib = _L.load()
+    nx, ny, nz = _route_grid(walk, dist)
+    dev = walk.device
+    assert path.dtype == torch.int64 and path.is_contiguous() and path.ndim == 1 and path.numel() >= 1 and path.device == dev
+    assert length.dtype == torch.int64 and length.numel() == 1 and length.device == dev
+    assert 0 <= int(goal) < walk.numel(), f"goal {goal} outside the grid's {walk.numel()} cells"
+    rc = lib.pi3_grid_route_trace(walk.data_ptr(), dist.data_ptr(), nx, ny, nz, int(goal), path.data_ptr(),
+                                  int(path.numel()), length.data_ptr(), _L.stream_ptr())
+    _L.check(rc, "pi3_grid_route_trace")
+
+
 # ---- nearest neighbours between two clouds (csrc/cloud_nn.hip)
 CLOUD_INDEX_COUNTERS = ("dropped", "cells", "no_slot", "largest_cell")
 CLOUD_NEAREST_COUNTERS = ("dropped", "matched", "beyond", "evaluations")

@@ -572,6 +572,42 @@ int pi3_grid_route_sweep(const unsigned char* walk, int nx, int ny, int nz, unsi
 int pi3_grid_route_trace(const unsigned char* walk, const unsigned* dist, int nx, int ny, int nz, long goal, long* path,
                          long cap, long* length, void* stream);
 
+/* ---- frontiers of the occupancy grid (csrc/grid_frontier.hip): the same grid layout and limits (1 <= n < 2^21 per
+ * axis, at most 2^27 cells); integers only.  A frontier cell is a cell with state == 1 of whose 6 face neighbours at
+ * least one is unknown (state == 0); a neighbour outside the grid counts as unknown (the box only bounds where points
+ * and cameras were: nothing beyond it was ever voted on).  label uint32 [cells]: 0xFFFFFFFF for a cell that is no
+ * frontier cell.
+ * pi3_grid_frontier_mark: label[c] = c for a frontier cell, else 0xFFFFFFFF.  counters: DEVICE uint64 [4] = frontier
+ *   cells, unknown faces over all frontier cells (1..6 each), 2 spare; zeroed by the call.
+ * pi3_grid_frontier_sweep: one sweep of minimum-label propagation over plain 26-connectivity among the labelled cells
+ *   (no corner rule), a workgroup per tile of 8 x 8 x 8 cells: the tile's cells are relaxed to their fixed point against
+ *   each other and against the tile's one-cell halo as it is read; cells that got lower are stored, and *changed
+ *   (DEVICE int32, never cleared here) becomes 1 when any did.  A tile without a labelled cell writes nothing.  The
+ *   caller repeats the call until a sweep leaves its `changed` word 0: every labelled cell then carries the smallest
+ *   linear index of its component, whatever order the tiles ran in (values are indices of cells of the same component,
+ *   only decrease, and 32-bit words do not tear).
+ * pi3_grid_frontier_roots: the cells with label[c] == c, compacted in any order into roots int64 [cap]; *count (DEVICE
+ *   int64, zeroed by the call) = their number even when it exceeds cap: the first cap slots claimed are then written and
+ *   the caller must check.  cap >= 0; roots may be NULL at cap == 0.
+ * pi3_grid_frontier_stats: roots_sorted int64 [K] ascending (pi3_grid_frontier_roots' output, sorted by the host).  The
+ *   call initialises stats int64 [K][12] and every frontier cell (label != 0xFFFFFFFF) reduces into the row whose root is
+ *   its label: cells, unknown faces, the sums of x, y, z, the minima of x, y, z (initially INT64_MAX), the maxima of x,
+ *   y, z (initially -1), and `best`, as uint64 the smallest (dist[c] << 27) | c over the cells with dist[c] !=
+ *   0xFFFFFFFF: the cheapest reachable cell and, among equals, the smallest index; all ones when there is none or dist
+ *   (uint32 [cells], pi3_grid_route_sweep's settled field) is NULL.  Integer atomics: the bytes do not depend on the
+ *   order.  counters: DEVICE uint64 [4] = cells reduced, cells whose label is not in roots_sorted (0 from a correct
+ *   caller; they are reduced nowhere), cells with a finite dist, 1 spare; zeroed by the call.  0 <= K <= cells; K == 0
+ *   zeroes the counters and launches no kernel, roots_sorted and stats may then be NULL.
+ * Bad arguments launch nothing and leave the outputs untouched.  No allocation, no synchronisation. */
+int pi3_grid_frontier_mark(const unsigned char* state, int nx, int ny, int nz, unsigned* label,
+                           unsigned long long* counters, void* stream);
+int pi3_grid_frontier_sweep(int nx, int ny, int nz, unsigned* label, int* changed, void* stream);
+int pi3_grid_frontier_roots(const unsigned* label, int nx, int ny, int nz, long* roots, long cap, long* count,
+                            void* stream);
+int pi3_grid_frontier_stats(const unsigned char* state, const unsigned* label, const unsigned* dist, int nx, int ny,
+                            int nz, const long* roots_sorted, long K, long* stats, unsigned long long* counters,
+                            void* stream);
+
 /* ---- nearest neighbours between two point clouds (csrc/cloud_nn.hip): an exact radius-bounded search through a
  * uniform grid of cells, for scoring a map against a reference cloud (map_eval.py).  The grid is a hash table of cells
  * in the voxel table's form: `capacity` slots of 64 B (a power of two, at least 2 n: ops.voxel_capacity), keyed by the

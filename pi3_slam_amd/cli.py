@@ -10,6 +10,8 @@
          --model_path /ckpt/pi3 --save_tum [--cam_dist_path calib.json] [--use_inverse_depth]
   python -m pi3_slam_amd.cli route --occupancy OUT/occupancy.npz --output DIR --from-trajectory OUT/trajectory_tum.txt \\
          [--goal X Y Z] [--radius 0.2]
+  python -m pi3_slam_amd.cli frontiers --occupancy OUT/occupancy.npz --output DIR --from-trajectory OUT/trajectory_tum.txt \\
+         [--radius 0.2] [--min-cells 20] [--route-to 0]
 
 Under `python -m torch.distributed.run --nproc-per-node G -m pi3_slam_amd.cli ...` every stage shards over the G GPUs.
 """
@@ -280,7 +282,31 @@ ROUTE_FLAGS: Sequence[Tuple[str, Dict]] = (
     ("--device", dict(default="cuda")),
 )
 ROUTE_SWITCHES = (("--through-unknown", "unknown cells are traversable too, and no obstacles of the clearance "
-                                        "(default: only verified free space, kept away from unknown space)"),)
+                                        "(default: only verified free space, kept away from unknown space)"),
+                  ("--approach-unknown", "only free cells are traversable, but --radius is kept from occupied cells alone: "
+                                         "the body may come up to the edge of unknown space, as a goal of `frontiers` "
+                                         "needs (not with --through-unknown)"))
+
+
+# frontiers: this build's own sub-command (frontier.py) on the same file
+FRONTIER_FLAGS: Sequence[Tuple[str, Dict]] = (
+    ("--occupancy", dict(REQ, help="occupancy.npz of `reconstruct` or `online` (--occupancy-cell)")),
+    ("--output", dict(REQ, help="directory for frontiers.json, frontiers.npz and frontiers.ply and, with --route-to, "
+                                "route.json, route.ply and route.npz")),
+    ("--start", dict(type=float, nargs=3, default=None, metavar=("X", "Y", "Z"), help="rank the clusters by the route "
+                                                                                    "from this world point")),
+    ("--from-trajectory", dict(default=None, help="rank the clusters by the route from the nearest pose of this TUM "
+                                                  "trajectory (poses on cells that are not traversable are skipped and "
+                                                  "counted); without a source the clusters are ordered by size")),
+    ("--radius", dict(type=float, default=0.0, help="the body's radius in metres for that route, kept from occupied "
+                                                    "cells only (default 0: every free cell)")),
+    ("--min-cells", dict(type=int, default=1, help="drop clusters of fewer frontier cells (default 1: none; a few tens "
+                                                   "hide single-cell holes of the vote: a starting point, not a "
+                                                   "measured optimum)")),
+    ("--route-to", dict(type=int, default=None, metavar="RANK", help="also the way to the goal of the cluster of this "
+                                                                     "rank (0 = the nearest), as `route` writes it")),
+    ("--device", dict(default="cuda")),
+)
 
 
 def list_images(root: str) -> List[str]:
@@ -300,7 +326,8 @@ def build_parser() -> argparse.ArgumentParser:
                                   ("reconstruct", tuple(RECON_FLAGS) + tuple(DENSE_MAP_FLAGS) + tuple(LOOP_FLAGS), RECON_SWITCHES),
                                   ("online", tuple(ONLINE_FLAGS) + ONLINE_DENSE_FLAGS + ONLINE_FOLLOW_FLAGS,
                                    ONLINE_SWITCHES),
-                                  ("evaluate-map", EVAL_FLAGS, EVAL_SWITCHES), ("route", ROUTE_FLAGS, ROUTE_SWITCHES)):
+                                  ("evaluate-map", EVAL_FLAGS, EVAL_SWITCHES), ("route", ROUTE_FLAGS, ROUTE_SWITCHES),
+                                  ("frontiers", FRONTIER_FLAGS, ())):
         p = sub.add_parser(name)
         for flag, kw in flags:
             p.add_argument(flag, **kw)
@@ -500,7 +527,7 @@ def run_route(a: argparse.Namespace) -> None:
     if (a.start is None) == (a.from_trajectory is None):
         raise SystemExit("route: give --start X Y Z or --from-trajectory TRAJ.tum (one of them)")
     try:
-        router = GridRouter(a.radius, a.through_unknown)
+        router = GridRouter(a.radius, a.through_unknown, a.approach_unknown)
         grid = export.read_occupancy(a.occupancy)
         sources = [a.start] if a.start is not None else read_tum_positions(a.from_trajectory)
         field = router.field(grid, sources, a.device)
@@ -521,10 +548,43 @@ def run_route(a: argparse.Namespace) -> None:
     print(text)
 
 
+def run_frontiers(a: argparse.Namespace) -> None:
+    from . import export
+    from .frontier import FrontierFinder
+    from .grid_route import read_tum_positions
+    if a.start is not None and a.from_trajectory is not None:
+        raise SystemExit("frontiers: give --start X Y Z or --from-trajectory TRAJ.tum, not both")
+    if a.route_to is not None and a.start is None and a.from_trajectory is None:
+        raise SystemExit("frontiers: --route-to needs a source: --start X Y Z or --from-trajectory TRAJ.tum")
+    try:
+        finder = FrontierFinder(a.radius, a.min_cells)
+        grid = export.read_occupancy(a.occupancy)
+        sources = None
+        if a.start is not None:
+            sources = [a.start]
+        elif a.from_trajectory is not None:
+            sources = read_tum_positions(a.from_trajectory)
+        found = finder.find(grid, sources, a.device)
+        route = found.route_to(a.route_to) if a.route_to is not None else None
+    except (ValueError, OSError) as e:
+        raise SystemExit(f"frontiers: {e}")
+    export.write_frontiers(found, a.output)
+    if route is not None:
+        export.write_route(found.field, route, a.output)
+    c = found.counts
+    text = (f"frontiers: {c['frontier_cells']} frontier cells in {c['clusters']} clusters ({c['clusters_dropped']} "
+            f"dropped), {c['reachable_clusters']} reachable, {c['sweeps']} sweeps")
+    if found.clusters:
+        best = found.clusters[0]
+        text += f"; the best: {best.cells} cells"
+        text += f" at {best.distance_m:.3f} m" if best.reachable else ", not reachable" if sources is not None else ""
+    print(text)
+
+
 def main(argv=None) -> None:
     a = build_parser().parse_args(argv)
     {"create": run_create, "reconstruct": run_reconstruct, "online": run_online,
-     "evaluate-map": run_evaluate_map, "route": run_route}[a.command](a)
+     "evaluate-map": run_evaluate_map, "route": run_route, "frontiers": run_frontiers}[a.command](a)
 
 
 if __name__ == "__main__":

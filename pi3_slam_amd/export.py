@@ -270,6 +270,39 @@ def write_route(field, route, out_dir: str) -> None:
     print(text)
 
 
+FRONTIER_PALETTE = ((230, 25, 75), (60, 180, 75), (0, 130, 200), (245, 130, 48), (145, 30, 180), (70, 240, 240),
+                    (240, 50, 230), (210, 245, 60))        # frontiers.ply: reachable clusters by rank modulo 8
+FRONTIER_UNREACHABLE_COLOR = (128, 128, 128)
+
+
+def write_frontiers(fset, out_dir: str) -> int:
+    """A frontier.FrontierSet -> <out_dir>/frontiers.json (settings, counts and the cluster records in rank order),
+    frontiers.npz (rank i32 (nz,ny,nx): the cluster's rank per frontier cell, -1 elsewhere; index_origin i64 (3,),
+    origin f64 (3,), cell f64) and frontiers.ply: the centres of the frontier cells of the kept clusters, coloured from
+    a fixed palette by rank, grey for clusters that cannot be reached, for viewing next to dense_points.ply.  Returns
+    the number of vertices."""
+    os.makedirs(out_dir, exist_ok=True)
+    record = {"settings": fset.settings, "counts": fset.counts, "clusters": [c.record() for c in fset.clusters]}
+    with open(os.path.join(out_dir, "frontiers.json"), "w") as f:
+        json.dump(record, f, indent=1)
+    rank = np.asarray(fset.rank, np.int32)
+    with open(os.path.join(out_dir, "frontiers.npz"), "wb") as f:
+        np.savez_compressed(f, rank=rank, index_origin=np.asarray(fset.index_origin, np.int64),
+                            origin=float(fset.cell) * np.asarray(fset.index_origin, np.float64),
+                            cell=np.float64(fset.cell))
+    nz, ny, nx = rank.shape
+    cells = np.flatnonzero(rank.reshape(-1) >= 0)
+    xyz = np.stack([cells % nx, (cells // nx) % ny, cells // (nx * ny)], 1)
+    pts = float(fset.cell) * ((xyz + np.asarray(fset.index_origin, np.int64)[None, :]).astype(np.float64) + 0.5)
+    table = np.array([FRONTIER_UNREACHABLE_COLOR if c.reachable is False else
+                      FRONTIER_PALETTE[c.rank % len(FRONTIER_PALETTE)] for c in fset.clusters], np.uint8).reshape(-1, 3)
+    colors = table[rank.reshape(-1)[cells]] if len(cells) else np.zeros((0, 3), np.uint8)
+    write_ply(pts, colors, os.path.join(out_dir, "frontiers.ply"))
+    print(f"✅ Saved {len(fset.clusters)} frontier clusters ({len(cells)} cells) to: {out_dir}/frontiers.json, "
+          "frontiers.npz and frontiers.ply")
+    return int(len(cells))
+
+
 def write_renders(chunks: Sequence[Dict], dense: Optional[DenseMap], out_dir: str, every: Optional[int], overview: bool,
                   min_weight: int = 1, splat_scale: float = 1.0, device="cuda",
                   dense_cleaner=None, dense_follower=None, dense_carver=None) -> Optional[Tuple[int, Dict[str, float]]]:

@@ -3,10 +3,10 @@ where the camera has been, which space can a body of radius r reach, and what is
 
 The graph is exact in integers.  A cell is traversable when it is free (with through_unknown: not occupied) and, with a
 body radius, its clearance is at least the radius: d2 >= ceil((radius / cell)^2) on the exact distance transform
-(ops.grid_edt at R = ceil(radius / cell) cells, with unknown cells as obstacles unless through_unknown: space that is
-not verified empty is kept at a distance unless the user says otherwise).  The 26 moves to the neighbours cost 12, 17,
-21 (12 times 1, sqrt 2, sqrt 3, rounded: +0.17 % / +1.04 %) and cut no corner: every cell of the 2, 4 or 8 the move
-passes between must be traversable.  distance = cell cost / 12 metres.
+(ops.grid_edt at R = ceil(radius / cell) cells, with unknown cells as obstacles unless through_unknown or
+approach_unknown: space that is not verified empty is kept at a distance unless the user says otherwise).  The 26
+moves to the neighbours cost 12, 17, 21 (12 times 1, sqrt 2, sqrt 3, rounded: +0.17 % / +1.04 %) and cut no corner:
+every cell of the 2, 4 or 8 the move passes between must be traversable.  distance = cell cost / 12 metres.
 
 Limitations: a chamfer metric, not the Euclidean one (a straight way at an odd angle is measured up to a few per cent
 long); ways run through cell centres and are not smoothed; a start or a goal on a blocked cell is refused, not
@@ -76,9 +76,12 @@ class Route:
 @dataclass
 class GridRouter:
     """radius (metres): the body's; 0 asks for no clearance.  through_unknown: unknown cells are traversable too (and
-    no obstacles of the clearance)."""
+    no obstacles of the clearance).  approach_unknown: only free cells are traversable, but the clearance is kept from
+    occupied cells alone, so a body may come up to the edge of unknown space (what frontier.py needs: a free cell that
+    borders unknown space has clearance 1 cell at most otherwise).  The two switches together are refused."""
     radius: float = 0.0
     through_unknown: bool = False
+    approach_unknown: bool = False
 
     SWEEPS_PER_READ = 4         # relaxation sweeps queued between two reads of their `changed` words
 
@@ -87,9 +90,14 @@ class GridRouter:
         if not (self.radius >= 0.0 and math.isfinite(self.radius)):
             raise ValueError(f"the radius must be a finite length >= 0, got {self.radius!r}")
         self.through_unknown = bool(self.through_unknown)
+        self.approach_unknown = bool(self.approach_unknown)
+        if self.through_unknown and self.approach_unknown:
+            raise ValueError("through_unknown and approach_unknown exclude each other: a body that walks through "
+                             "unknown space is not kept away from it either way")
 
     def settings(self) -> Dict:
-        return {"radius": self.radius, "through_unknown": self.through_unknown, "costs": list(ops.ROUTE_COSTS)}
+        return {"radius": self.radius, "through_unknown": self.through_unknown,
+                "approach_unknown": self.approach_unknown, "costs": list(ops.ROUTE_COSTS)}
 
     def clearance_cells(self, cell: float):
         """-> (R, min_d2) for cells of this size: the distance transform's radius and the smallest passing d2; (None, 0)
@@ -151,7 +159,7 @@ class GridRouter:
         d2 = None
         if R is not None:
             d2 = torch.empty(state.shape, dtype=torch.int16, device=dev)
-            ops.grid_edt(state, R, not self.through_unknown, d2, torch.empty_like(d2))
+            ops.grid_edt(state, R, not (self.through_unknown or self.approach_unknown), d2, torch.empty_like(d2))
         walk = torch.empty_like(state)
         dist = torch.empty(state.shape, dtype=torch.int32, device=dev)
         counters = torch.zeros(4, dtype=torch.int64, device=dev)

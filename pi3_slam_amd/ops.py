@@ -1076,6 +1076,83 @@ def grid_route_trace(walk: torch.Tensor, dist: torch.Tensor, goal: int, path: to
     _L.check(rc, "pi3_grid_route_trace")
 
 
+# ---- frontiers of the occupancy grid (csrc/grid_frontier.hip)
+FRONTIER_NONE = 0xFFFFFFFF              # the label of a cell that is no frontier cell
+FRONTIER_MARK_COUNTERS = ("frontier_cells", "unknown_faces")
+FRONTIER_STATS_COUNTERS = ("cells_reduced", "cells_without_root", "cells_reachable")
+FRONTIER_STATS_FIELDS = ("cells", "unknown_faces", "sum_x", "sum_y", "sum_z", "min_x", "min_y", "min_z", "max_x",
+                         "max_y", "max_z", "best")
+FRONTIER_KEY_SHIFT = 27                 # best = (cost << 27) | cell as uint64, all ones when no cell is reachable
+
+
+def _frontier_grid(label: torch.Tensor) -> Tuple[int, int, int]:
+    assert label.dtype == torch.int32 and label.is_contiguous() and label.ndim == 3
+    assert 0 < label.numel() <= ROUTE_MAX_CELLS, f"{label.numel()} cells: 1 .. 2^27"
+    return int(label.shape[2]), int(label.shape[1]), int(label.shape[0])
+
+
+def grid_frontier_mark(state: torch.Tensor, label: torch.Tensor, counters: torch.Tensor) -> None:
+    """label int32 (nz,ny,nx) (the uint32 values) = the cell's own linear index where state uint8 (nz,ny,nx) is free
+    and one of the 6 face neighbours is unknown (outside the grid counts as unknown), else FRONTIER_NONE.  counters
+    int64 (4,) = FRONTIER_MARK_COUNTERS (zeroed by the call)."""
+    lib = _L.load()
+    nx, ny, nz = _frontier_grid(label)
+    dev = label.device
+    assert state.dtype == torch.uint8 and state.is_contiguous() and state.shape == label.shape and state.device == dev
+    assert counters.dtype == torch.int64 and counters.is_contiguous() and counters.numel() >= 4 and counters.device == dev
+    rc = lib.pi3_grid_frontier_mark(state.data_ptr(), nx, ny, nz, label.data_ptr(), counters.data_ptr(), _L.stream_ptr())
+    _L.check(rc, "pi3_grid_frontier_mark")
+
+
+def grid_frontier_sweep(label: torch.Tensor, changed: torch.Tensor) -> None:
+    """One sweep of minimum-label propagation over the 26-connected labelled cells of label int32 (nz,ny,nx) (tiles of
+    8 x 8 x 8 cells, each relaxed to its fixed point); changed int32 (1,) becomes 1 when a cell got lower (the caller
+    zeroes it)."""
+    lib = _L.load()
+    nx, ny, nz = _frontier_grid(label)
+    assert changed.dtype == torch.int32 and changed.numel() == 1 and changed.device == label.device
+    rc = lib.pi3_grid_frontier_sweep(nx, ny, nz, label.data_ptr(), changed.data_ptr(), _L.stream_ptr())
+    _L.check(rc, "pi3_grid_frontier_sweep")
+
+
+def grid_frontier_roots(label: torch.Tensor, roots: torch.Tensor, count: torch.Tensor) -> None:
+    """The cells with label[c] == c into roots int64 (cap,), in any order; count int64 (1,) = their number, also when
+    it exceeds cap (the caller checks)."""
+    lib = _L.load()
+    nx, ny, nz = _frontier_grid(label)
+    dev = label.device
+    assert roots.dtype == torch.int64 and roots.is_contiguous() and roots.ndim == 1 and roots.device == dev
+    assert count.dtype == torch.int64 and count.numel() == 1 and count.device == dev
+    cap = int(roots.numel())
+    rc = lib.pi3_grid_frontier_roots(label.data_ptr(), nx, ny, nz, roots.data_ptr() if cap else None, cap,
+                                     count.data_ptr(), _L.stream_ptr())
+    _L.check(rc, "pi3_grid_frontier_roots")
+
+
+def grid_frontier_stats(state: torch.Tensor, label: torch.Tensor, dist: Optional[torch.Tensor],
+                        roots_sorted: torch.Tensor, stats: torch.Tensor, counters: torch.Tensor) -> None:
+    """stats int64 (K,12) = FRONTIER_STATS_FIELDS per cluster of the settled label int32 (nz,ny,nx): row k reduces the
+    cells whose label is roots_sorted[k] (int64 (K,), ascending).  dist int32 (nz,ny,nx) (a settled route field, the
+    uint32 values) or None: `best` is then all ones.  counters int64 (4,) = FRONTIER_STATS_COUNTERS (zeroed by the
+    call)."""
+    lib = _L.load()
+    nx, ny, nz = _frontier_grid(label)
+    dev = label.device
+    assert state.dtype == torch.uint8 and state.is_contiguous() and state.shape == label.shape and state.device == dev
+    if dist is not None:
+        assert dist.dtype == torch.int32 and dist.is_contiguous() and dist.shape == label.shape and dist.device == dev
+    assert roots_sorted.dtype == torch.int64 and roots_sorted.is_contiguous() and roots_sorted.ndim == 1
+    assert roots_sorted.device == dev
+    K = int(roots_sorted.numel())
+    assert stats.dtype == torch.int64 and stats.is_contiguous() and tuple(stats.shape) == (K, len(FRONTIER_STATS_FIELDS))
+    assert stats.device == dev
+    assert counters.dtype == torch.int64 and counters.is_contiguous() and counters.numel() >= 4 and counters.device == dev
+    rc = lib.pi3_grid_frontier_stats(state.data_ptr(), label.data_ptr(), _L.ptr(dist), nx, ny, nz,
+                                     roots_sorted.data_ptr() if K else None, K, stats.data_ptr() if K else None,
+                                     counters.data_ptr(), _L.stream_ptr())
+    _L.check(rc, "pi3_grid_frontier_stats")
+
+
 # ---- nearest neighbours between two clouds (csrc/cloud_nn.hip)
 CLOUD_INDEX_COUNTERS = ("dropped", "cells", "no_slot", "largest_cell")
 CLOUD_NEAREST_COUNTERS = ("dropped", "matched", "beyond", "evaluations")

@@ -9,29 +9,17 @@
 //   pi3_grid_frontier_mark   a thread per cell: label = the cell's own linear index when it is a frontier cell.
 //                            Counted: the frontier cells and their unknown faces (1..6 each).
 //   pi3_grid_frontier_sweep  one sweep of minimum-label propagation over plain 26-connectivity among the labelled
-//                            cells (connectivity of a surface, not motion: no corner rule).  grid_route.hip's sweep in
-//                            structure: a workgroup of 512 threads per tile of 8 x 8 x 8 cells, the tile and its
-//                            one-cell halo of label staged in LDS (0xFFFFFFFF outside the grid), the tile's own cells
-//                            relaxed against the 26 words around them until no thread lowered anything
-//                            (__syncthreads_or), only own cells that got lower written back, as plain 32-bit stores,
-//                            and *changed = 1 when any did.  A tile without a labelled cell returns after one load per
-//                            thread and writes nothing.  The loop that repeats the launch lives with the caller
-//                            (frontier.py).
-//                            Why the fixed point is the answer, whatever order the tiles ran in: a workgroup reads its
-//                            halo while the neighbour that owns those cells may be writing them.  (1) Every value ever
-//                            stored in a labelled cell is the linear index of a cell of the same component: its own, or
-//                            a value taken from a labelled neighbour, which is such an index by induction.  (2) A cell
-//                            is written only by its own thread of its own workgroup, and only with a smaller value.
-//                            (3) A 32-bit word cannot tear: a reader sees the old or the new value, both of them
-//                            indices of the component.  So the cell m with the smallest index of its component keeps
-//                            label m for ever (nothing in the component is smaller), and a state in which a sweep
-//                            changes nothing has label[c] <= label[n] for every pair of labelled neighbours, in both
-//                            directions: label is constant on the component, and the constant is label[m] = m.
-//                            LDS layout: grid_route.hip's, rows 16 and planes 168 words apart (1 680 words, 6.7 KB),
-//                            for which all 26 neighbour reads of a 32-lane half (8 x by 2 y by 2 z) are conflict free.
-//                            The tile geometry is a local copy of that file's few lines, not a shared header: moving
-//                            them would rebuild the route kernel, whose register and LDS figures and byte-for-byte
-//                            tests are pinned, for the sake of four constants and one index expression.
+//                            cells (connectivity of a surface, not motion: no corner rule), in grid_tile.h's scheme
+//                            (tiles of 8 x 8 x 8 cells, each relaxed in LDS to its own fixed point; the layout and why
+//                            the order of the tiles does not matter are argued there; 0xFFFFFFFF outside the grid).
+//                            That argument's step (1) here: every value ever stored in a labelled cell is the linear
+//                            index of a cell of the same component, its own or a value taken from a labelled neighbour,
+//                            which is such an index by induction.  So the cell m with the smallest index of its
+//                            component keeps label m for ever (nothing in the component is smaller), and a state in
+//                            which a sweep changes nothing has label[c] <= label[n] for every pair of labelled
+//                            neighbours, in both directions: label is constant on the component, and the constant is
+//                            label[m] = m.  A tile without a labelled cell returns after one load per thread and writes
+//                            nothing.  The loop that repeats the launch lives with the caller (frontier.py).
 //   pi3_grid_frontier_roots  compacts the cells with label[c] == c (after the fixed point: one per component), in any
 //                            order: a workgroup scans its flags and claims its slots with one atomic add on *count.
 //   pi3_grid_frontier_stats  a thread per cell; a frontier cell finds its row by binary search of its label in
@@ -40,6 +28,7 @@
 //                            adds for them; every other lane adds for itself.  All reductions are integer sums, minima
 //                            and maxima, so the atomics give the same bytes in any order.
 #include "common.h"
+#include "grid_tile.h"
 #include "voxel_table.h"
 #include "wave_block.h"
 
@@ -47,6 +36,8 @@
 
 namespace {
 
+using grid_tile::grid_ok;
+using grid_tile::kMaxIndex;
 using voxel_table::u64;
 using wave_block::block_count;
 using wave_block::block_exclusive_scan;
@@ -55,12 +46,6 @@ using wave_block::block_sum;
 typedef long long i64;
 
 constexpr unsigned kNone = 0xFFFFFFFFu;
-constexpr long kMaxCells = 1L << 27;    // grid_route.hip's limit: a label and a cost key share it
-constexpr int kMaxIndex = 1 << 21;      // occupancy.hip's limit per dimension
-constexpr int kT = 8;                   // tile edge
-constexpr int kH = kT + 2;              // with the halo
-constexpr int kRow = 16, kPlane = 168;  // LDS strides in words (grid_route.hip)
-constexpr int kLds = kH * kPlane;
 constexpr int kStats = 12;              // i64 per row
 constexpr i64 kMinInit = 0x7FFFFFFFFFFFFFFFll;
 
@@ -96,57 +81,25 @@ __global__ __launch_bounds__(256) void frontier_mark_kernel(const unsigned char*
   block_sum((unsigned)faces, counters + 1);
 }
 
-__global__ __launch_bounds__(512) void frontier_sweep_kernel(int nx, int ny, int nz, int tx, int ty, unsigned* label,
-                                                             int* __restrict__ changed) {
-  __shared__ unsigned sl[kLds];
-  const int t = (int)threadIdx.x;
-  int b = (int)blockIdx.x;
-  const int bx = b % tx;
-  b /= tx;
-  const int by = b % ty, bz = b / ty;                         // < the z tiles by the grid's size
-  const int x0 = bx * kT, y0 = by * kT, z0 = bz * kT;
-  // a 32-lane half = 8 x by 2 y by 2 z: rows at 0, 16, 168, 184 words
-  const int lx = t & 7, ly = ((t >> 3) & 1) | (((t >> 5) & 3) << 1), lz = ((t >> 4) & 1) | (((t >> 7) & 3) << 1);
-  const int gx = x0 + lx, gy = y0 + ly, gz = z0 + lz;
-  const bool own = gx < nx && gy < ny && gz < nz;
-  const int g = own ? (gz * ny + gy) * nx + gx : 0;
-  const int c = (lz + 1) * kPlane + (ly + 1) * kRow + (lx + 1);
-
-  const unsigned first = own ? label[g] : kNone;              // only this thread ever writes this word
+__global__ __launch_bounds__(grid_tile::kThreads) void frontier_sweep_kernel(int nx, int ny, int nz, int tx, int ty,
+                                                                             unsigned* label,
+                                                                             int* __restrict__ changed) {
+  __shared__ unsigned sl[grid_tile::kLds];
+  const grid_tile::Tile tile(nx, ny, nz, tx, ty);
+  const unsigned first = tile.own ? label[tile.g] : kNone;    // == sl[c] once staged: nobody else writes this cell's word
   const bool labelled = first != kNone;
   if (!__syncthreads_or(labelled)) return;                    // no frontier here: nothing is written
-  for (int j = t; j < kH * kH * kH; j += 512) {
-    const int hx = j % kH, hy = (j / kH) % kH, hz = j / (kH * kH);
-    const int sx = x0 - 1 + hx, sy = y0 - 1 + hy, sz = z0 - 1 + hz;
-    const bool in = sx >= 0 && sx < nx && sy >= 0 && sy < ny && sz >= 0 && sz < nz;
-    sl[hz * kPlane + hy * kRow + hx] = in ? label[(sz * ny + sy) * nx + sx] : kNone;
-  }
+  tile.stage(sl, (const unsigned*)label, kNone);
   __syncthreads();
-  unsigned mine = first;                                      // == sl[c]: nobody else writes this cell's word
-  for (;;) {
-    unsigned best = mine;
-    if (labelled) {
-#pragma unroll
-      for (int dz = -1; dz <= 1; ++dz)
-#pragma unroll
-        for (int dy = -1; dy <= 1; ++dy)
-#pragma unroll
-          for (int dx = -1; dx <= 1; ++dx) {
-            if (dx == 0 && dy == 0 && dz == 0) continue;
-            const unsigned l = sl[c + dz * kPlane + dy * kRow + dx];   // 0xFFFFFFFF where there is no label
-            if (l < best) best = l;
-          }
-    }
-    const bool lower = best < mine;
-    if (lower) {
-      mine = best;
-      sl[c] = best;
-    }
-    if (!__syncthreads_or(lower)) break;                      // the barrier also publishes this round's LDS stores
-  }
-  const bool lowered = mine < first;                          // then the cell is labelled, so inside the grid
-  if (lowered) label[g] = mine;
-  if (__syncthreads_or(lowered) && t == 0) *changed = 1;
+  const int c = tile.c;
+  grid_tile::settle(tile, sl, label, first, changed, [&](unsigned best) {
+    if (labelled)
+      grid_tile::for_hood([&](int, int, int, int off, int) {
+        const unsigned l = sl[c + off];                       // 0xFFFFFFFF where there is no label
+        if (l < best) best = l;
+      });
+    return best;
+  });
 }
 
 __global__ __launch_bounds__(256) void frontier_roots_kernel(const unsigned* __restrict__ label, int cells,
@@ -269,20 +222,12 @@ __global__ __launch_bounds__(256) void frontier_stats_kernel(const unsigned char
   block_count<3>(flags, counters, at);
 }
 
-inline bool frontier_grid_ok(int nx, int ny, int nz, long& cells) {
-  if (nx <= 0 || ny <= 0 || nz <= 0 || nx >= kMaxIndex || ny >= kMaxIndex || nz >= kMaxIndex) return false;
-  cells = (long)nx * ny;                      // < 2^42
-  if (cells > kMaxCells / nz) return false;
-  cells *= nz;
-  return true;
-}
-
 }  // namespace
 
 extern "C" int pi3_grid_frontier_mark(const unsigned char* state, int nx, int ny, int nz, unsigned* label,
                                       unsigned long long* counters, void* stream) {
   long cells = 0;
-  if (!state || !label || !counters || !frontier_grid_ok(nx, ny, nz, cells)) {
+  if (!state || !label || !counters || !grid_ok(nx, ny, nz, cells)) {
     pi3_set_error("pi3_grid_frontier_mark: bad arguments dims=(%d, %d, %d) (1 .. 2^21 - 1 each, at most 2^27 cells), or "
                   "a null pointer", nx, ny, nz);
     return PI3_ERR_ARG;
@@ -295,22 +240,22 @@ extern "C" int pi3_grid_frontier_mark(const unsigned char* state, int nx, int ny
 
 extern "C" int pi3_grid_frontier_sweep(int nx, int ny, int nz, unsigned* label, int* changed, void* stream) {
   long cells = 0;
-  if (!label || !changed || !frontier_grid_ok(nx, ny, nz, cells)) {
+  if (!label || !changed || !grid_ok(nx, ny, nz, cells)) {
     pi3_set_error("pi3_grid_frontier_sweep: bad arguments dims=(%d, %d, %d) (1 .. 2^21 - 1 each, at most 2^27 cells), "
                   "or a null pointer", nx, ny, nz);
     return PI3_ERR_ARG;
   }
-  const int tx = (nx + kT - 1) / kT, ty = (ny + kT - 1) / kT, tz = (nz + kT - 1) / kT;
-  const long tiles = (long)tx * ty * tz;      // every tile holds a cell: <= 2^27
-  hipLaunchKernelGGL(frontier_sweep_kernel, dim3((unsigned)tiles), dim3(512), 0, (hipStream_t)stream, nx, ny, nz, tx, ty,
-                     label, changed);
+  int tx, ty;
+  const unsigned tiles = grid_tile::tiles(nx, ny, nz, tx, ty);
+  hipLaunchKernelGGL(frontier_sweep_kernel, dim3(tiles), dim3(grid_tile::kThreads), 0, (hipStream_t)stream, nx, ny, nz,
+                     tx, ty, label, changed);
   return pi3_check_launch("grid_frontier_sweep");
 }
 
 extern "C" int pi3_grid_frontier_roots(const unsigned* label, int nx, int ny, int nz, long* roots, long cap,
                                        long* count, void* stream) {
   long cells = 0;
-  if (!label || !count || !frontier_grid_ok(nx, ny, nz, cells) || cap < 0 || (cap > 0 && !roots)) {
+  if (!label || !count || !grid_ok(nx, ny, nz, cells) || cap < 0 || (cap > 0 && !roots)) {
     pi3_set_error("pi3_grid_frontier_roots: bad arguments dims=(%d, %d, %d) (1 .. 2^21 - 1 each, at most 2^27 cells) "
                   "cap=%ld (>= 0; roots may be NULL at 0), or a null pointer", nx, ny, nz, cap);
     return PI3_ERR_ARG;
@@ -325,7 +270,7 @@ extern "C" int pi3_grid_frontier_stats(const unsigned char* state, const unsigne
                                        int ny, int nz, const long* roots_sorted, long K, long* stats,
                                        unsigned long long* counters, void* stream) {
   long cells = 0;
-  if (!state || !label || !counters || !frontier_grid_ok(nx, ny, nz, cells) || K < 0 || K > cells ||
+  if (!state || !label || !counters || !grid_ok(nx, ny, nz, cells) || K < 0 || K > cells ||
       (K > 0 && (!roots_sorted || !stats))) {
     pi3_set_error("pi3_grid_frontier_stats: bad arguments dims=(%d, %d, %d) (1 .. 2^21 - 1 each, at most 2^27 cells) "
                   "K=%ld (0 .. cells; roots_sorted and stats may be NULL at 0), or a null pointer", nx, ny, nz, K);

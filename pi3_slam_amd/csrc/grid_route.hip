@@ -12,36 +12,23 @@
 //                         clearance field, d2 >= min_d2 (the field's far mark 0xFFFF passes); dist = far.  Then a thread
 //                         per source: a linear index outside [0, cells) is counted as outside, one on a cell that is
 //                         not traversable as such, every other gets dist = 0 (duplicates store the same word).
-//   pi3_grid_route_sweep  a workgroup of 512 threads per tile of 8 x 8 x 8 cells, a thread per cell.  The tile and its
-//                         one-cell halo of walk and dist are staged in LDS (10^3 entries each; outside the grid is not
-//                         traversable), every thread folds the 27 walk bytes around its cell into the mask of its
-//                         allowed moves once, and then the tile's own cells are relaxed in LDS against those moves
-//                         until no thread lowered anything (__syncthreads_or).  Only own cells that got lower are
-//                         written back, as plain 32-bit stores, and *changed = 1 when any did.  The loop that repeats
-//                         the launch until a sweep changes nothing lives with the caller (grid_route.py).
-//                         Why the order of the tiles does not matter: a workgroup reads its halo while the neighbour
-//                         that owns those cells may be writing them, and inside a tile a thread reads its neighbours'
-//                         LDS words while they write them.  (1) Every value ever stored is the cost of a real move
-//                         sequence from a source: a source's 0, or an allowed move added to such a value.  (2) A cell is
-//                         written only by its own thread of its own workgroup, and only with a smaller value: values
-//                         only decrease.  (3) A 32-bit word cannot tear: a reader sees the old or the new value, both
-//                         of them real costs that are not below the shortest distance.  So no value ever drops below
+//   pi3_grid_route_sweep  one relaxation sweep in grid_tile.h's scheme (tiles of 8 x 8 x 8 cells, each relaxed in LDS to
+//                         its own fixed point; the layout and why the order of the tiles does not matter are argued
+//                         there).  Besides dist the tile's walk bytes are staged (outside the grid is not traversable),
+//                         and every thread folds the 27 around its cell into the mask of its allowed moves once.  That
+//                         argument's step (1) here: every value ever stored is the cost of a real move sequence from a
+//                         source, a source's 0 or an allowed move added to such a value.  So no value ever drops below
 //                         the shortest distance, and a state in which a sweep changes nothing satisfies
-//                         dist[c] <= dist[n] + w for every allowed move: it is the unique shortest-distance field,
-//                         whatever order the tiles ran in and whichever halo values they happened to read.  A tile with
-//                         no traversable cell returns before it touches dist.
-//                         LDS layout: the 10 x 10 x 10 block is stored with rows 16 words and planes 168 words apart
-//                         (1 680 words of dist, as many bytes of walk: 8.4 KB).  ds_read_b32 banks are (a / 4) mod 32
-//                         per 32-lane half; a half holds 8 x by 2 y by 2 z cells, whose words start at 0, 16, 168 = 8
-//                         and 184 = 24 (mod 32): the four rows of 8 tile the 32 banks, and a neighbour offset shifts
-//                         them all alike, so all 26 reads are conflict free.  (Dense rows of 10 put the fourth row of
-//                         any 8 x 4 arrangement on the first row's banks: 2-way on every read.)
+//                         dist[c] <= dist[n] + w for every allowed move: it is the unique shortest-distance field.  A
+//                         tile with no traversable cell returns before it touches dist.  The loop that repeats the
+//                         launch until a sweep changes nothing lives with the caller (grid_route.py).
 //   pi3_grid_route_trace  one wave walks from the goal back to a source.  Lanes 0..25 each test one neighbour n, in the
 //                         order of (dz, dy, dx): the move is allowed and dist[n] + w == dist[cur].  Inside the grid
 //                         that order is the order of the linear indices, so the lowest qualifying lane holds the
 //                         smallest index: one ballot.  dist falls by at least 12 per step, so the walk ends.  Two
 //                         passes, the first only counts: a path that does not fit leaves `path` untouched.
 #include "common.h"
+#include "grid_tile.h"
 #include "voxel_table.h"
 #include "wave_block.h"
 
@@ -49,18 +36,16 @@
 
 namespace {
 
+using grid_tile::grid_ok;
+using grid_tile::kLds;
+using grid_tile::kPlane;
+using grid_tile::kRow;
 using voxel_table::u64;
 using wave_block::block_count;
 
 constexpr unsigned kFar = 0xFFFFFFFFu;
 constexpr int kD2Far = 0xFFFF;
 constexpr int kMaxMinD2 = 255 * 255;    // the clearance field's largest finite value
-constexpr long kMaxCells = 1L << 27;    // 21 (2^27 - 1) < 2^32 - 1
-constexpr int kMaxIndex = 1 << 21;      // occupancy.hip's limit per dimension
-constexpr int kT = 8;                   // tile edge
-constexpr int kH = kT + 2;              // with the halo
-constexpr int kRow = 16, kPlane = 168;  // LDS strides in entries (see above)
-constexpr int kLds = kH * kPlane;
 
 __host__ __device__ constexpr int move_cost(int dx, int dy, int dz) {
   const int n = (dx != 0) + (dy != 0) + (dz != 0);
@@ -119,38 +104,18 @@ __global__ __launch_bounds__(256) void route_sources_kernel(const long* __restri
   block_count<3>(flags, counters, at);
 }
 
-__global__ __launch_bounds__(512) void route_sweep_kernel(const unsigned char* __restrict__ walk, int nx, int ny, int nz,
-                                                          int tx, int ty, unsigned* dist, int* __restrict__ changed) {
+__global__ __launch_bounds__(grid_tile::kThreads) void route_sweep_kernel(const unsigned char* __restrict__ walk, int nx,
+                                                                          int ny, int nz, int tx, int ty, unsigned* dist,
+                                                                          int* __restrict__ changed) {
   __shared__ unsigned sd[kLds];
   __shared__ unsigned char sw[kLds];
-  const int t = (int)threadIdx.x;
-  int b = (int)blockIdx.x;
-  const int bx = b % tx;
-  b /= tx;
-  const int by = b % ty, bz = b / ty;                         // < the z tiles by the grid's size
-  const int x0 = bx * kT, y0 = by * kT, z0 = bz * kT;
-  // a 32-lane half = 8 x by 2 y by 2 z: rows at 0, 16, 168, 184 words
-  const int lx = t & 7, ly = ((t >> 3) & 1) | (((t >> 5) & 3) << 1), lz = ((t >> 4) & 1) | (((t >> 7) & 3) << 1);
-  const int gx = x0 + lx, gy = y0 + ly, gz = z0 + lz;
-  const bool own = gx < nx && gy < ny && gz < nz;
-  const int g = own ? (gz * ny + gy) * nx + gx : 0;
-  const int c = (lz + 1) * kPlane + (ly + 1) * kRow + (lx + 1);
-
-  for (int j = t; j < kH * kH * kH; j += 512) {
-    const int hx = j % kH, hy = (j / kH) % kH, hz = j / (kH * kH);
-    const int sx = x0 - 1 + hx, sy = y0 - 1 + hy, sz = z0 - 1 + hz;
-    const bool in = sx >= 0 && sx < nx && sy >= 0 && sy < ny && sz >= 0 && sz < nz;
-    sw[hz * kPlane + hy * kRow + hx] = in ? walk[(sz * ny + sy) * nx + sx] : (unsigned char)0;
-  }
+  const grid_tile::Tile tile(nx, ny, nz, tx, ty);
+  const int c = tile.c;
+  tile.stage(sw, walk, (unsigned char)0);
   __syncthreads();
   const bool open = sw[c] != 0;                               // 0 outside the grid: `own` is implied
   if (!__syncthreads_or(open)) return;                        // nothing to relax here: dist is not touched
-  for (int j = t; j < kH * kH * kH; j += 512) {
-    const int hx = j % kH, hy = (j / kH) % kH, hz = j / (kH * kH);
-    const int sx = x0 - 1 + hx, sy = y0 - 1 + hy, sz = z0 - 1 + hz;
-    const bool in = sx >= 0 && sx < nx && sy >= 0 && sy < ny && sz >= 0 && sz < nz;
-    sd[hz * kPlane + hy * kRow + hx] = in ? dist[(sz * ny + sy) * nx + sx] : kFar;
-  }
+  tile.stage(sd, (const unsigned*)dist, kFar);
   // the allowed moves of this cell: the 27 walk bytes around it, once
   unsigned moves = 0;
   if (open) {
@@ -162,6 +127,8 @@ __global__ __launch_bounds__(512) void route_sweep_kernel(const unsigned char* _
 #pragma unroll
         for (int dx = -1; dx <= 1; ++dx)
           if (sw[c + dz * kPlane + dy * kRow + dx]) hood |= hood_bit(dx, dy, dz);
+    // for_hood's walk and numbering, written out: as a lambda here the compiler waits for the 27 byte reads above in
+    // batches of 8 instead of issuing them together (24 for 43 VGPRs, and a sweep measured 1 % slower)
     int k = 0;
 #pragma unroll
     for (int dz = -1; dz <= 1; ++dz)
@@ -176,35 +143,16 @@ __global__ __launch_bounds__(512) void route_sweep_kernel(const unsigned char* _
         }
   }
   __syncthreads();
-  const unsigned first = sd[c];                               // only this thread ever writes this word
-  unsigned mine = first;
-  for (;;) {
-    unsigned best = mine;
-    int k = 0;
-#pragma unroll
-    for (int dz = -1; dz <= 1; ++dz)
-#pragma unroll
-      for (int dy = -1; dy <= 1; ++dy)
-#pragma unroll
-        for (int dx = -1; dx <= 1; ++dx) {
-          if (dx == 0 && dy == 0 && dz == 0) continue;
-          if (moves & (1u << k)) {
-            const unsigned d = sd[c + dz * kPlane + dy * kRow + dx];
-            const unsigned cand = d + (unsigned)move_cost(dx, dy, dz);
-            if (d != kFar && cand < best) best = cand;        // far + w would wrap
-          }
-          ++k;
-        }
-    const bool lower = best < mine;
-    if (lower) {
-      mine = best;
-      sd[c] = best;
-    }
-    if (!__syncthreads_or(lower)) break;                      // the barrier also publishes this round's LDS stores
-  }
-  const bool lowered = mine < first;                          // then the cell is open, so inside the grid
-  if (lowered) dist[g] = mine;
-  if (__syncthreads_or(lowered) && t == 0) *changed = 1;
+  grid_tile::settle(tile, sd, dist, sd[c], changed, [&](unsigned best) {
+    grid_tile::for_hood([&](int dx, int dy, int dz, int off, int k) {
+      if (moves & (1u << k)) {
+        const unsigned d = sd[c + off];
+        const unsigned cand = d + (unsigned)move_cost(dx, dy, dz);
+        if (d != kFar && cand < best) best = cand;            // far + w would wrap
+      }
+    });
+    return best;
+  });
 }
 
 __global__ __launch_bounds__(64) void route_trace_kernel(const unsigned char* __restrict__ walk,
@@ -260,21 +208,13 @@ __global__ __launch_bounds__(64) void route_trace_kernel(const unsigned char* __
   }
 }
 
-inline bool route_grid_ok(int nx, int ny, int nz, long& cells) {
-  if (nx <= 0 || ny <= 0 || nz <= 0 || nx >= kMaxIndex || ny >= kMaxIndex || nz >= kMaxIndex) return false;
-  cells = (long)nx * ny;                      // < 2^42
-  if (cells > kMaxCells / nz) return false;
-  cells *= nz;
-  return true;
-}
-
 }  // namespace
 
 extern "C" int pi3_grid_route_init(const unsigned char* state, const unsigned short* d2, int min_d2, int through_unknown,
                                    int nx, int ny, int nz, const long* sources, long Ns, unsigned char* walk,
                                    unsigned* dist, unsigned long long* counters, void* stream) {
   long cells = 0;
-  if (!state || !walk || !dist || !counters || !route_grid_ok(nx, ny, nz, cells) || min_d2 < 0 || min_d2 > kMaxMinD2 ||
+  if (!state || !walk || !dist || !counters || !grid_ok(nx, ny, nz, cells) || min_d2 < 0 || min_d2 > kMaxMinD2 ||
       (min_d2 > 0 && !d2) || Ns < 0 || Ns >= (1L << 39) || (Ns > 0 && !sources)) {
     pi3_set_error("pi3_grid_route_init: bad arguments dims=(%d, %d, %d) (1 .. 2^21 - 1 each, at most 2^27 cells) "
                   "min_d2=%d (0 .. %d, 0 without d2) Ns=%ld (0 .. 2^39 - 1), or a null pointer", nx, ny, nz, min_d2,
@@ -294,22 +234,22 @@ extern "C" int pi3_grid_route_init(const unsigned char* state, const unsigned sh
 extern "C" int pi3_grid_route_sweep(const unsigned char* walk, int nx, int ny, int nz, unsigned* dist, int* changed,
                                     void* stream) {
   long cells = 0;
-  if (!walk || !dist || !changed || !route_grid_ok(nx, ny, nz, cells)) {
+  if (!walk || !dist || !changed || !grid_ok(nx, ny, nz, cells)) {
     pi3_set_error("pi3_grid_route_sweep: bad arguments dims=(%d, %d, %d) (1 .. 2^21 - 1 each, at most 2^27 cells), or "
                   "a null pointer", nx, ny, nz);
     return PI3_ERR_ARG;
   }
-  const int tx = (nx + kT - 1) / kT, ty = (ny + kT - 1) / kT, tz = (nz + kT - 1) / kT;
-  const long tiles = (long)tx * ty * tz;      // every tile holds a cell: <= 2^27
-  hipLaunchKernelGGL(route_sweep_kernel, dim3((unsigned)tiles), dim3(512), 0, (hipStream_t)stream, walk, nx, ny, nz, tx,
-                     ty, dist, changed);
+  int tx, ty;
+  const unsigned tiles = grid_tile::tiles(nx, ny, nz, tx, ty);
+  hipLaunchKernelGGL(route_sweep_kernel, dim3(tiles), dim3(grid_tile::kThreads), 0, (hipStream_t)stream, walk, nx, ny,
+                     nz, tx, ty, dist, changed);
   return pi3_check_launch("grid_route_sweep");
 }
 
 extern "C" int pi3_grid_route_trace(const unsigned char* walk, const unsigned* dist, int nx, int ny, int nz, long goal,
                                     long* path, long cap, long* length, void* stream) {
   long cells = 0;
-  if (!walk || !dist || !path || !length || !route_grid_ok(nx, ny, nz, cells) || goal < 0 || goal >= cells || cap < 1) {
+  if (!walk || !dist || !path || !length || !grid_ok(nx, ny, nz, cells) || goal < 0 || goal >= cells || cap < 1) {
     pi3_set_error("pi3_grid_route_trace: bad arguments dims=(%d, %d, %d) (1 .. 2^21 - 1 each, at most 2^27 cells) "
                   "goal=%ld (0 .. cells - 1) cap=%ld (>= 1), or a null pointer", nx, ny, nz, goal, cap);
     return PI3_ERR_ARG;

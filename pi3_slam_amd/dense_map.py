@@ -238,26 +238,16 @@ class MapCleaner:
 
     def label_components(self, fuser: "VoxelFuser", keep: torch.Tensor, survivors: int) -> Tuple[torch.Tensor, int]:
         """Stage B's labels for the stage-A mask `keep` with `survivors` voxels set: -> (label int64 (capacity,): the
-        smallest key of the slot's component, all ones for a slot that did not survive; the sweeps run).  The kernels
-        only launch; the loop is here: SWEEPS_PER_READ sweeps, one read of their `changed` words, until a sweep changed
-        nothing.  Raises when that takes more sweeps than neighbour propagation alone can need."""
+        smallest key of the slot's component, all ones for a slot that did not survive; the sweeps run).  Raises when
+        the fixed point (ops.sweep_until_quiet) takes more sweeps than neighbour propagation alone can need."""
         table, dev = fuser.table, fuser.device
         label = torch.empty(fuser.capacity, dtype=torch.int64, device=dev)
         ops.voxel_label_init(table, keep, label)
-        changed = torch.empty(self.SWEEPS_PER_READ, dtype=torch.int32, device=dev)
         # a sweep moves a component's smallest key at least one voxel further along every path (it reads what the
         # previous launch wrote, or something newer), so `survivors` sweeps reach the fixed point; one more sees no change
-        bound, sweeps = int(survivors) + 1, 0
-        while True:
-            changed.zero_()
-            for j in range(self.SWEEPS_PER_READ):
-                ops.voxel_label_sweep(table, label, changed[j:j + 1])
-            quiet = np.flatnonzero(changed.cpu().numpy() == 0)
-            if len(quiet):
-                return label, sweeps + int(quiet[0]) + 1
-            sweeps += self.SWEEPS_PER_READ
-            if sweeps > bound:
-                raise RuntimeError(f"component labelling did not settle in {sweeps} sweeps over {survivors} voxels")
+        what = "component labelling did not settle in {sweeps} sweeps over %d voxels" % survivors
+        return label, ops.sweep_until_quiet(lambda flag: ops.voxel_label_sweep(table, label, flag), dev,
+                                            int(survivors) + 1, what, self.SWEEPS_PER_READ)
 
     def summary(self) -> str:
         st = self.last_stats

@@ -123,22 +123,13 @@ class FrontierFinder:
                 "router": self.router.settings()}
 
     def settle(self, label: torch.Tensor, frontier_cells: int) -> int:
-        """Sweeps label to its fixed point -> the sweeps run, the quiet one included."""
-        changed = torch.empty(self.SWEEPS_PER_READ, dtype=torch.int32, device=label.device)
+        """Sweeps label to its fixed point -> the sweeps run, the quiet one included (ops.sweep_until_quiet)."""
         # a launch lowers at least one more cell of a component to its final label (a tile relaxes its cells against
         # what the previous launch left, or something newer): frontier_cells sweeps reach the fixed point and one more
         # sees no change, so the bound cannot be reached legitimately
-        bound, sweeps = int(frontier_cells) + 1, 0
-        while True:
-            changed.zero_()
-            for j in range(self.SWEEPS_PER_READ):
-                ops.grid_frontier_sweep(label, changed[j:j + 1])
-            quiet = np.flatnonzero(changed.cpu().numpy() == 0)
-            if len(quiet):
-                return sweeps + int(quiet[0]) + 1
-            sweeps += self.SWEEPS_PER_READ
-            if sweeps > bound:
-                raise RuntimeError(f"the frontier labels did not settle in {sweeps} sweeps over {frontier_cells} cells")
+        what = "the frontier labels did not settle in {sweeps} sweeps over %d cells" % frontier_cells
+        return ops.sweep_until_quiet(lambda flag: ops.grid_frontier_sweep(label, flag), label.device,
+                                     int(frontier_cells) + 1, what, self.SWEEPS_PER_READ)
 
     def roots(self, label: torch.Tensor, frontier_cells: int) -> torch.Tensor:
         """The roots of the settled label, ascending, int64 (K,) on the device."""

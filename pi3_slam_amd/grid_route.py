@@ -188,23 +188,13 @@ class GridRouter:
         return out
 
     def relax(self, walk: torch.Tensor, dist: torch.Tensor, traversable: int) -> int:
-        """Sweeps dist to its fixed point -> the sweeps run, the quiet one included.  The kernels only launch; the loop
-        is here: SWEEPS_PER_READ sweeps, one read of their `changed` words, until a sweep changed nothing."""
-        changed = torch.empty(self.SWEEPS_PER_READ, dtype=torch.int32, device=walk.device)
+        """Sweeps dist to its fixed point -> the sweeps run, the quiet one included (ops.sweep_until_quiet)."""
         # a launch settles at least one more cell of every shortest path (a tile relaxes its cells against what the
         # previous launch left, or something newer), and a path has at most `traversable` cells: that many sweeps reach
         # the fixed point and one more sees no change, so the bound cannot be reached legitimately
-        bound, sweeps = int(traversable) + 1, 0
-        while True:
-            changed.zero_()
-            for j in range(self.SWEEPS_PER_READ):
-                ops.grid_route_sweep(walk, dist, changed[j:j + 1])
-            quiet = np.flatnonzero(changed.cpu().numpy() == 0)
-            if len(quiet):
-                return sweeps + int(quiet[0]) + 1
-            sweeps += self.SWEEPS_PER_READ
-            if sweeps > bound:
-                raise RuntimeError(f"the route field did not settle in {sweeps} sweeps over {traversable} cells")
+        what = "the route field did not settle in {sweeps} sweeps over %d cells" % traversable
+        return ops.sweep_until_quiet(lambda flag: ops.grid_route_sweep(walk, dist, flag), walk.device,
+                                     int(traversable) + 1, what, self.SWEEPS_PER_READ)
 
     def path(self, field: RouteField, goal_xyz) -> Optional[Route]:
         """The cheapest way from a source to the world point goal_xyz; None when the goal cannot be reached.  A goal

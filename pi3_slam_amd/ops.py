@@ -1022,11 +1022,32 @@ ROUTE_MAX_CELLS = 1 << 27               # 21 (cells - 1) stays below ROUTE_FAR
 ROUTE_INIT_COUNTERS = ("traversable", "sources_accepted", "sources_blocked", "sources_outside")
 
 
-def _route_grid(walk: torch.Tensor, dist: torch.Tensor) -> Tuple[int, int, int]:
-    nx, ny, nz = _grid_state(walk)
-    assert dist.dtype == torch.int32 and dist.is_contiguous() and dist.shape == walk.shape and dist.device == walk.device
-    assert 0 < walk.numel() <= ROUTE_MAX_CELLS, f"{walk.numel()} cells: 1 .. 2^27"
-    return nx, ny, nz
+def _grid_field(field: torch.Tensor, walk: Optional[torch.Tensor] = None) -> Tuple[int, int, int]:
+    """(nx, ny, nz) of a grid field of 32-bit words, int32 (nz,ny,nx): dist, with its walk uint8 (nz,ny,nx), or label."""
+    assert field.dtype == torch.int32 and field.is_contiguous() and field.ndim == 3
+    if walk is not None:
+        assert _grid_state(walk) and walk.shape == field.shape and walk.device == field.device
+    assert 0 < field.numel() <= ROUTE_MAX_CELLS, f"{field.numel()} cells: 1 .. 2^27"
+    return int(field.shape[2]), int(field.shape[1]), int(field.shape[0])
+
+
+def sweep_until_quiet(launch, device, bound: int, what: str, per_read: int) -> int:
+    """Repeats a fixed-point sweep until one changes nothing -> the sweeps run, the quiet one included.  launch(flag)
+    queues one sweep that sets the int32 (1,) `flag` when it changed something.  The kernels only launch; the loop is
+    here: per_read sweeps, one read of their flags.  More than `bound` sweeps without a quiet one raise the RuntimeError
+    `what`, a text with a place for {sweeps}."""
+    changed = torch.empty(per_read, dtype=torch.int32, device=device)
+    sweeps = 0
+    while True:
+        changed.zero_()
+        for j in range(per_read):
+            launch(changed[j:j + 1])
+        flags = changed.tolist()
+        if 0 in flags:
+            return sweeps + flags.index(0) + 1
+        sweeps += per_read
+        if sweeps > bound:
+            raise RuntimeError(what.format(sweeps=sweeps))
 
 
 def grid_route_init(state: torch.Tensor, d2: Optional[torch.Tensor], min_d2: int, through_unknown: bool,
@@ -1036,7 +1057,7 @@ def grid_route_init(state: torch.Tensor, d2: Optional[torch.Tensor], min_d2: int
     = ROUTE_FAR everywhere, then 0 at every entry of sources int64 (Ns,) (linear indices) that lies inside the grid on
     a traversable cell.  counters int64 (4,) = ROUTE_INIT_COUNTERS (zeroed by the call)."""
     lib = _L.load()
-    nx, ny, nz = _route_grid(walk, dist)
+    nx, ny, nz = _grid_field(dist, walk)
     dev = state.device
     assert state.dtype == torch.uint8 and state.is_contiguous() and state.shape == walk.shape and walk.device == dev
     if d2 is not None:
@@ -1055,7 +1076,7 @@ def grid_route_sweep(walk: torch.Tensor, dist: torch.Tensor, changed: torch.Tens
     """One relaxation sweep over dist int32 (nz,ny,nx) (tiles of 8 x 8 x 8 cells, each relaxed to its fixed point);
     changed int32 (1,) becomes 1 when a cell got lower (the caller zeroes it)."""
     lib = _L.load()
-    nx, ny, nz = _route_grid(walk, dist)
+    nx, ny, nz = _grid_field(dist, walk)
     assert changed.dtype == torch.int32 and changed.numel() == 1 and changed.device == walk.device
     rc = lib.pi3_grid_route_sweep(walk.data_ptr(), nx, ny, nz, dist.data_ptr(), changed.data_ptr(), _L.stream_ptr())
     _L.check(rc, "pi3_grid_route_sweep")
@@ -1066,7 +1087,7 @@ def grid_route_trace(walk: torch.Tensor, dist: torch.Tensor, goal: int, path: to
     path int64 (cap,) gets the linear indices goal .. source, length int64 (1,) their number: 0 when there is no way,
     -needed when path is too short (it is then left untouched)."""
     lib = _L.load()
-    nx, ny, nz = _route_grid(walk, dist)
+    nx, ny, nz = _grid_field(dist, walk)
     dev = walk.device
     assert path.dtype == torch.int64 and path.is_contiguous() and path.ndim == 1 and path.numel() >= 1 and path.device == dev
     assert length.dtype == torch.int64 and length.numel() == 1 and length.device == dev
@@ -1085,18 +1106,12 @@ FRONTIER_STATS_FIELDS = ("cells", "unknown_faces", "sum_x", "sum_y", "sum_z", "m
 FRONTIER_KEY_SHIFT = 27                 # best = (cost << 27) | cell as uint64, all ones when no cell is reachable
 
 
-def _frontier_grid(label: torch.Tensor) -> Tuple[int, int, int]:
-    assert label.dtype == torch.int32 and label.is_contiguous() and label.ndim == 3
-    assert 0 < label.numel() <= ROUTE_MAX_CELLS, f"{label.numel()} cells: 1 .. 2^27"
-    return int(label.shape[2]), int(label.shape[1]), int(label.shape[0])
-
-
 def grid_frontier_mark(state: torch.Tensor, label: torch.Tensor, counters: torch.Tensor) -> None:
     """label int32 (nz,ny,nx) (the uint32 values) = the cell's own linear index where state uint8 (nz,ny,nx) is free
     and one of the 6 face neighbours is unknown (outside the grid counts as unknown), else FRONTIER_NONE.  counters
     int64 (4,) = FRONTIER_MARK_COUNTERS (zeroed by the call)."""
     lib = _L.load()
-    nx, ny, nz = _frontier_grid(label)
+    nx, ny, nz = _grid_field(label)
     dev = label.device
     assert state.dtype == torch.uint8 and state.is_contiguous() and state.shape == label.shape and state.device == dev
     assert counters.dtype == torch.int64 and counters.is_contiguous() and counters.numel() >= 4 and counters.device == dev
@@ -1109,7 +1124,7 @@ def grid_frontier_sweep(label: torch.Tensor, changed: torch.Tensor) -> None:
     8 x 8 x 8 cells, each relaxed to its fixed point); changed int32 (1,) becomes 1 when a cell got lower (the caller
     zeroes it)."""
     lib = _L.load()
-    nx, ny, nz = _frontier_grid(label)
+    nx, ny, nz = _grid_field(label)
     assert changed.dtype == torch.int32 and changed.numel() == 1 and changed.device == label.device
     rc = lib.pi3_grid_frontier_sweep(nx, ny, nz, label.data_ptr(), changed.data_ptr(), _L.stream_ptr())
     _L.check(rc, "pi3_grid_frontier_sweep")
@@ -1119,7 +1134,7 @@ def grid_frontier_roots(label: torch.Tensor, roots: torch.Tensor, count: torch.T
     """The cells with label[c] == c into roots int64 (cap,), in any order; count int64 (1,) = their number, also when
     it exceeds cap (the caller checks)."""
     lib = _L.load()
-    nx, ny, nz = _frontier_grid(label)
+    nx, ny, nz = _grid_field(label)
     dev = label.device
     assert roots.dtype == torch.int64 and roots.is_contiguous() and roots.ndim == 1 and roots.device == dev
     assert count.dtype == torch.int64 and count.numel() == 1 and count.device == dev
@@ -1136,7 +1151,7 @@ def grid_frontier_stats(state: torch.Tensor, label: torch.Tensor, dist: Optional
     uint32 values) or None: `best` is then all ones.  counters int64 (4,) = FRONTIER_STATS_COUNTERS (zeroed by the
     call)."""
     lib = _L.load()
-    nx, ny, nz = _frontier_grid(label)
+    nx, ny, nz = _grid_field(label)
     dev = label.device
     assert state.dtype == torch.uint8 and state.is_contiguous() and state.shape == label.shape and state.device == dev
     if dist is not None:

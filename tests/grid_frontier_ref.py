@@ -13,9 +13,7 @@
              reachable, 0];
   order      the ranking: clusters below min_cells dropped; reachable ones by (cost, root), then the rest by
              (-cells, root);
-  tile_sweeps  the kernel's schedule with the slowest halo it may see: per launch every 8 x 8 x 8 tile is relaxed to
-             its own fixed point against the halo values of the previous launch.  The device reads those or newer
-             (lower) ones, so it needs at most as many launches.
+  tile_sweeps  the kernel's schedule with the slowest halo it may see (grid_tile_ref.tile_schedule).
 Test infrastructure only: the product never imports it."""
 from __future__ import annotations
 
@@ -23,20 +21,13 @@ from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
+from grid_tile_ref import BIG, HOOD, shift as _shift, tile_schedule
+
 NONE = 0xFFFFFFFF
 ALL_ONES = 0xFFFFFFFFFFFFFFFF
 FAR = 0xFFFFFFFF
 KEY_SHIFT = 27
-TILE = 8
 MIN_INIT = 0x7FFFFFFFFFFFFFFF
-HOOD: List[Tuple[int, int, int]] = [(dx, dy, dz) for dz in (-1, 0, 1) for dy in (-1, 0, 1) for dx in (-1, 0, 1)
-                                    if (dx, dy, dz) != (0, 0, 0)]
-
-
-def _shift(padded: np.ndarray, dx: int, dy: int, dz: int) -> np.ndarray:
-    """The view of a one-cell-padded array that holds, at c, the value at c + (dx, dy, dz)."""
-    nz, ny, nx = (n - 2 for n in padded.shape)
-    return padded[1 + dz:1 + dz + nz, 1 + dy:1 + dy + ny, 1 + dx:1 + dx + nx]
 
 
 def faces(state) -> np.ndarray:
@@ -166,32 +157,11 @@ def tile_sweeps(label0, max_sweeps: int = 100000) -> Tuple[np.ndarray, int, int]
     """From mark's label -> (label u32 at the fixed point, launches, launches that changed something): `launches`
     includes the last, quiet one."""
     label0 = np.asarray(label0, np.uint32)
-    nz, ny, nx = label0.shape
-    big = np.int64(1) << 40
     on = label0 != NONE
-    z, y, x = np.meshgrid(np.arange(nz) // TILE, np.arange(ny) // TILE, np.arange(nx) // TILE, indexing="ij")
-    tile = np.pad((z * ((ny + TILE - 1) // TILE) + y) * ((nx + TILE - 1) // TILE) + x, 1, constant_values=-1)
-    same = [_shift(tile, *d) == _shift(tile, 0, 0, 0) for d in HOOD]
-    lab = np.where(on, label0.astype(np.int64), big)
-    launches = 0
-    while True:
-        launches += 1
-        assert launches <= max_sweeps
-        halo = np.pad(lab, 1, constant_values=big)             # what the previous launch left
-        cur = lab.copy()
-        while True:                                            # every tile to its own fixed point
-            cp = np.pad(cur, 1, constant_values=big)
-            new = cur.copy()
-            for k, d in enumerate(HOOD):
-                np.minimum(new, np.where(same[k], _shift(cp, *d), _shift(halo, *d)), out=new)
-            new = np.where(on, new, big)                       # a cell without a label takes none
-            if (new == cur).all():
-                break
-            cur = new
-        if (cur == lab).all():
-            break
-        lab = cur
-    return np.where(on, lab, NONE).astype(np.uint32), launches, launches - 1
+    # a labelled cell may take any neighbour's label; a cell without a label takes none
+    lab, launches, changing = tile_schedule(np.where(on, label0.astype(np.int64), BIG),
+                                            lambda k, v: np.where(on, v, BIG), max_sweeps)
+    return np.where(on, lab, NONE).astype(np.uint32), launches, changing
 
 
 def three_state(shape_zyx, unknown: float, occupied: float, seed: int) -> np.ndarray:

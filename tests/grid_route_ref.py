@@ -6,9 +6,7 @@
              is allowed only when every cell c + (a dx, b dy, e dz), a, b, e in {0, 1}, is inside the grid and walkable;
   distances  scipy's Dijkstra (min_only) on exactly this graph: integer costs are exact in f64;
   trace      from the goal, the allowed neighbour with dist[n] + w == dist[cur] that has the smallest linear index;
-  tile_sweeps  the kernel's schedule with the slowest halo it may see: per launch every 8 x 8 x 8 tile is relaxed to
-             its own fixed point against the halo values of the previous launch.  The device reads those or newer
-             (lower) ones, so it needs at most as many launches.
+  tile_sweeps  the kernel's schedule with the slowest halo it may see (grid_tile_ref.tile_schedule).
 Test infrastructure only: the product never imports it."""
 from __future__ import annotations
 
@@ -16,12 +14,12 @@ from typing import Dict, List, Sequence, Tuple
 
 import numpy as np
 
+from grid_tile_ref import BIG, HOOD, shift as _shift, tile_schedule
+
 FAR = 0xFFFFFFFF
 D2_FAR = 0xFFFF
-TILE = 8
 MOVES: List[Tuple[int, int, int, int]] = [(dx, dy, dz, (0, 12, 17, 21)[(dx != 0) + (dy != 0) + (dz != 0)])
-                                          for dz in (-1, 0, 1) for dy in (-1, 0, 1) for dx in (-1, 0, 1)
-                                          if (dx, dy, dz) != (0, 0, 0)]          # in the order of the linear index
+                                          for dx, dy, dz in HOOD]                # in the order of the linear index
 
 
 def walk_mask(state, d2=None, min_d2: int = 0, through_unknown: bool = False) -> np.ndarray:
@@ -30,12 +28,6 @@ def walk_mask(state, d2=None, min_d2: int = 0, through_unknown: bool = False) ->
     if d2 is not None:
         walk = walk & (np.asarray(d2, np.uint16).astype(np.int64) >= int(min_d2))
     return walk.astype(np.uint8)
-
-
-def _shift(padded: np.ndarray, dx: int, dy: int, dz: int) -> np.ndarray:
-    """The view of a one-cell-padded array that holds, at c, the value at c + (dx, dy, dz)."""
-    nz, ny, nx = (n - 2 for n in padded.shape)
-    return padded[1 + dz:1 + dz + nz, 1 + dy:1 + dy + ny, 1 + dx:1 + dx + nx]
 
 
 def allowed_moves(walk) -> np.ndarray:
@@ -124,37 +116,15 @@ def trace(walk, dist, goal: int) -> List[int]:
 def tile_sweeps(walk, sources: Sequence[int], max_sweeps: int = 100000) -> Tuple[np.ndarray, int, int]:
     """-> (dist u32, launches, launches that changed something): `launches` includes the last, quiet one."""
     walk = np.asarray(walk, np.uint8)
-    nz, ny, nx = walk.shape
     ok = allowed_moves(walk)
-    big = np.int64(1) << 40
-    z, y, x = np.meshgrid(np.arange(nz) // TILE, np.arange(ny) // TILE, np.arange(nx) // TILE, indexing="ij")
-    tile = np.pad((z * ((ny + TILE - 1) // TILE) + y) * ((nx + TILE - 1) // TILE) + x, 1, constant_values=-1)
-    same = [_shift(tile, dx, dy, dz) == _shift(tile, 0, 0, 0) for dx, dy, dz, _ in MOVES]
-    dist = np.full(walk.shape, big, np.int64)
+    dist = np.full(walk.shape, BIG, np.int64)
     s = np.asarray(sources, np.int64).reshape(-1)
     s = s[(s >= 0) & (s < walk.size)]
     s = s[walk.reshape(-1)[s] != 0]
     dist.reshape(-1)[s] = 0
-    launches = 0
-    while True:
-        launches += 1
-        assert launches <= max_sweeps
-        halo = np.pad(dist, 1, constant_values=big)           # what the previous launch left
-        cur = dist.copy()
-        while True:                                           # every tile to its own fixed point
-            cp = np.pad(cur, 1, constant_values=big)
-            new = cur.copy()
-            for k, (dx, dy, dz, w) in enumerate(MOVES):
-                cand = np.where(same[k], _shift(cp, dx, dy, dz), _shift(halo, dx, dy, dz)) + w
-                np.minimum(new, np.where(ok[k], cand, big), out=new)
-            if (new == cur).all():
-                break
-            cur = new
-        if (cur == dist).all():
-            break
-        dist = cur
-    out = np.where(dist >= big, FAR, dist).astype(np.uint32)
-    return out, launches, launches - 1
+    # neighbour k allows its value plus the move's cost where the move is allowed
+    dist, launches, changing = tile_schedule(dist, lambda k, v: np.where(ok[k], v + MOVES[k][3], BIG), max_sweeps)
+    return np.where(dist >= BIG, FAR, dist).astype(np.uint32), launches, changing
 
 
 def open_box_distance(a, b) -> int:

@@ -51,7 +51,9 @@ int pi3_device_count(void);
  *   orow(m) = rpg ? (m / rpg) * gstride + goff + m % rpg : m.   bias/gamma/resid/addtab may be NULL.
  * A [M][K] and W [N][K] share in_dtype (0: bf16 MFMA, 1: exact-fp32 MFMA, 2: f16 MFMA - then out_dtype is 2 or 1);
  * N % 128 == 0, or with 16-bit operands any N % 32 == 0 (32 / 64-column tiles: the narrow maps of the MoGe pyramid); K % 64 (bf16) / 32 (f32).
- * act: 0 none, 1 GELU(erf), 2 ReLU. */
+ * act: 0 none, 1 GELU(erf), 2 ReLU.
+ * qcols: a multiple of 4 with 0 <= qcols <= N (the epilogue scales whole groups of 4 columns); anything else is
+ * refused with PI3_ERR_ARG before any launch. */
 int pi3_gemm(const void* A, long lda, const void* W, long ldw, int M, int N, int K, int in_dtype, const float* bias,
              const float* gamma, const float* resid, long ldr, void* out, long ldo, int out_dtype, int act, int rpg,
              int gstride, int goff, const float* addtab, long ldadd, float qscale, int qcols, void* stream);

@@ -345,6 +345,12 @@ extern "C" int pi3_gemm(const void* A, long lda, const void* W, long ldw, int M,
     pi3_set_error("pi3_gemm: operands must be 16-byte aligned with 16-byte-multiple row strides");
     return PI3_ERR_ARG;
   }
+  // the epilogues decide n < qcols once per group of 4 columns (one lane's f32x4): a boundary inside a group would
+  // scale the whole group
+  if (qcols < 0 || qcols > N || (qcols % 4) != 0) {
+    pi3_set_error("pi3_gemm: qcols=%d must be a multiple of 4 in [0, N=%d]", qcols, N);
+    return PI3_ERR_ARG;
+  }
   GemmParams p;
   p.A = A; p.lda = lda; p.W = W; p.ldw = ldw; p.M = M; p.N = N; p.K = K;
   p.bias = bias; p.gamma = gamma; p.resid = resid; p.ldr = ldr; p.out = out; p.ldo = ldo;

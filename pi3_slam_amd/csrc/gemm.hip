@@ -12,12 +12,65 @@
 // columns of one output row: 8/16-byte stores and float4 bias loads in the epilogue.
 // The f32 variant uses v_mfma_f32_16x16x4_f32 (exact fp32, runs at the vector rate) for the heads the reference
 // computes with autocast disabled (pi3/models/pi3.py:192-209).
+//
+// Host side: pi3_gemm, pi3_gemm_qkv and pi3_conv3x3 check their arguments, fill a GemmParams that starts from its
+// defaults and map (out_dtype, act) to an instance with gemm_dispatch; launch_gemm / launch_narrow size the grid and go
+// through gemm_launch (gemm_common.h).  Large bf16 problems are offered to pi3_gemm256_try (gemm256.hip) first.
 #include "gemm_common.h"
 #include <stdlib.h>
 
 #define BM 128
 #define BN 128
 #define TILE_BYTES (128 * 128)
+
+// Swizzled LDS image of every kernel here: a 1 KiB segment is 8 tile rows of 128 B, lane l fills the 16-byte slot l & 7 of
+// row seg * 8 + (l >> 3), and chunk c of row r lives in slot c ^ ((r >> 1) & 7): the source chunk that lands in l's slot
+__device__ __forceinline__ int swz_src_chunk(int row, int lane) { return (lane & 7) ^ ((row >> 1) & 7); }
+
+// 3x3 convolution: tap 0..8 -> (ky, kx) in -1..1
+__device__ __forceinline__ void conv_tap_offsets(int tap, int& ky, int& kx) {
+  ky = tap / 3 - 1;
+  kx = tap - (tap / 3) * 3 - 1;
+}
+
+// K-step t of the convolution with cC % 64 == 0 covers one tap and one 64-channel block starting at channel c0
+__device__ __forceinline__ void conv_kstep(const GemmParams& p, int t, int& c0, int& ky, int& kx) {
+  const int cblocks = p.cC >> 6;
+  const int tap = t / cblocks;
+  c0 = (t - tap * cblocks) << 6;
+  conv_tap_offsets(tap, ky, kx);
+}
+
+// Source pixel of output pixel m = (b * cH + y) * cW + x under tap (ky, kx): the neighbour, clamped to its own image
+__device__ __forceinline__ long conv_src_pixel(const GemmParams& p, int m, int ky, int kx) {
+  const int x = m % p.cW;
+  const int by = m / p.cW;  // b * cH + y
+  const int y = by % p.cH;
+  int yy = y + ky, xx = x + kx;
+  yy = yy < 0 ? 0 : (yy >= p.cH ? p.cH - 1 : yy);
+  xx = xx < 0 ? 0 : (xx >= p.cW ? p.cW - 1 : xx);
+  return (long)(by - y + yy) * p.cW + xx;
+}
+
+// One 32-deep MFMA step over NI x 4 tiles: fw weight rows x fa activation rows; p.f16 (wave-uniform): as IEEE half
+template <int NI>
+__device__ __forceinline__ void mfma_step16(const GemmParams& p, const bf16x8 (&fw)[NI], const bf16x8 (&fa)[4],
+                                            f32x4 (&acc)[NI][4]) {
+  if (p.f16) {
+#pragma unroll
+    for (int ni = 0; ni < NI; ++ni)
+#pragma unroll
+      for (int mi = 0; mi < 4; ++mi)
+        acc[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, fw[ni]),
+                                                             __builtin_bit_cast(f16x8, fa[mi]), acc[ni][mi], 0, 0, 0);
+  } else {
+#pragma unroll
+    for (int ni = 0; ni < NI; ++ni)
+#pragma unroll
+      for (int mi = 0; mi < 4; ++mi)
+        acc[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[ni], fa[mi], acc[ni][mi], 0, 0, 0);
+  }
+}
 
 template <int ESZ>
 __device__ __forceinline__ void stage_tile(const char* gbase, long ld_bytes, int row0, int rows, long k0_bytes,
@@ -26,8 +79,7 @@ __device__ __forceinline__ void stage_tile(const char* gbase, long ld_bytes, int
   for (int i = 0; i < 4; ++i) {
     const int seg = wave * 4 + i;           // 1 KiB segment = 8 rows of 128 B
     const int row = seg * 8 + (lane >> 3);  // tile row 0..127
-    const int pos = lane & 7;               // 16-byte slot inside the LDS row
-    const int c = pos ^ ((row >> 1) & 7);   // source chunk that must land in this slot
+    const int c = swz_src_chunk(row, lane);
     int grow = row0 + row;
     grow = grow < rows ? grow : rows - 1;   // clamp: tail rows re-read the last valid row, results are discarded
     const char* src = gbase + (long)grow * ld_bytes + k0_bytes + c * 16;
@@ -39,24 +91,16 @@ __device__ __forceinline__ void stage_tile(const char* gbase, long ld_bytes, int
 // tile row r is the replicate-clamped neighbour pixel of pixel (row0 + r).
 __device__ __forceinline__ void stage_tile_conv(const GemmParams& p, int row0, int t, char* lds_tile, int wave,
                                                 int lane) {
-  const int cblocks = p.cC >> 6;
-  const int tap = t / cblocks, c0 = (t - tap * cblocks) << 6;
-  const int ky = tap / 3 - 1, kx = tap - (tap / 3) * 3 - 1;
+  int c0, ky, kx;
+  conv_kstep(p, t, c0, ky, kx);
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int seg = wave * 4 + i;
     const int row = seg * 8 + (lane >> 3);
-    const int pos = lane & 7;
-    const int c = pos ^ ((row >> 1) & 7);
+    const int c = swz_src_chunk(row, lane);
     int m = row0 + row;
     m = m < p.M ? m : p.M - 1;
-    const int x = m % p.cW;
-    const int by = m / p.cW;  // b * cH + y
-    const int y = by % p.cH;
-    int yy = y + ky, xx = x + kx;
-    yy = yy < 0 ? 0 : (yy >= p.cH ? p.cH - 1 : yy);
-    xx = xx < 0 ? 0 : (xx >= p.cW ? p.cW - 1 : xx);
-    const long pix = (long)(by - y + yy) * p.cW + xx;
+    const long pix = conv_src_pixel(p, m, ky, kx);
     const char* src = (const char*)p.A + (pix * p.lda + c0) * 2 + c * 16;
     __builtin_amdgcn_global_load_lds(GLB_PTR(src), LDS_PTR(lds_tile + seg * 1024), 16, 0, 0);
   }
@@ -125,20 +169,7 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(GemmParams p) {
           fa[i] = *(const bf16x8*)(la + i * 16 * 128 + off);
           fw[i] = *(const bf16x8*)(lw + i * 16 * 128 + off);
         }
-        if (p.f16) {       // wave-uniform: the same fragments as IEEE half
-#pragma unroll
-          for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-            for (int mi = 0; mi < 4; ++mi)
-              acc[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, fw[ni]),
-                                                                   __builtin_bit_cast(f16x8, fa[mi]), acc[ni][mi], 0, 0, 0);
-        } else {
-#pragma unroll
-          for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-            for (int mi = 0; mi < 4; ++mi)
-              acc[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[ni], fa[mi], acc[ni][mi], 0, 0, 0);
-        }
+        mfma_step16<4>(p, fw, fa, acc);
       } else {
         f32x4 fa[4], fw[4];
 #pragma unroll
@@ -167,11 +198,7 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(GemmParams p) {
 template <bool IS_BF16, bool OUT_BF16, int ACT, bool CONV = false>
 static int launch_gemm(const GemmParams& p, hipStream_t stream) {
   const int nbm = (p.M + BM - 1) / BM, nbn = p.N / BN;
-  auto kern = gemm_tn_kernel<IS_BF16, OUT_BF16, ACT, CONV>;
-  static unsigned long long optin = 0;
-  if (int rc = pi3_lds_optin((const void*)kern, 4 * TILE_BYTES, &optin, "gemm_tn")) return rc;
-  hipLaunchKernelGGL(kern, dim3(nbm * nbn), dim3(256), 4 * TILE_BYTES, stream, p);
-  return pi3_check_launch("gemm_tn");
+  return gemm_launch<gemm_tn_kernel<IS_BF16, OUT_BF16, ACT, CONV>>("gemm_tn", nbm * nbn, 256, 4 * TILE_BYTES, p, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -188,40 +215,25 @@ static int launch_gemm(const GemmParams& p, hipStream_t stream) {
 template <int NT, bool CONV>
 __device__ __forceinline__ void stage_narrow(const GemmParams& p, int row0, int n0, int t, char* lds_a, char* lds_w,
                                              int wave, int lane) {
-  const int pos = lane & 7;
   // ---- A: segments 8 wave .. 8 wave + 7 (8 rows of 128 B each)
-  int tap = 0, c0 = 0, ky = 0, kx = 0;
+  int c0 = 0, ky = 0, kx = 0;
   const bool half = CONV && p.cC == 32;
-  if (CONV && !half) {
-    const int cblocks = p.cC >> 6;
-    tap = t / cblocks;
-    c0 = (t - tap * cblocks) << 6;
-    ky = tap / 3 - 1;
-    kx = tap - (tap / 3) * 3 - 1;
-  }
+  if (CONV && !half) conv_kstep(p, t, c0, ky, kx);
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
     const int seg = wave * 8 + i;
     const int row = seg * 8 + (lane >> 3);
-    const int c = pos ^ ((row >> 1) & 7);
+    const int c = swz_src_chunk(row, lane);
     int m = row0 + row;
     m = m < p.M ? m : p.M - 1;
     const char* src;
     if constexpr (CONV) {
       int cc = c;
-      if (half) {
-        tap = min(2 * t + (c >> 2), 8);
+      if (half) {      // chunks 0..3: the 32 channels of tap 2t, chunks 4..7: of tap 2t + 1
+        conv_tap_offsets(min(2 * t + (c >> 2), 8), ky, kx);
         cc = c & 3;
-        ky = tap / 3 - 1;
-        kx = tap - (tap / 3) * 3 - 1;
       }
-      const int x = m % p.cW;
-      const int by = m / p.cW;  // b * cH + y
-      const int y = by % p.cH;
-      int yy = y + ky, xx = x + kx;
-      yy = yy < 0 ? 0 : (yy >= p.cH ? p.cH - 1 : yy);
-      xx = xx < 0 ? 0 : (xx >= p.cW ? p.cW - 1 : xx);
-      const long pix = (long)(by - y + yy) * p.cW + xx;
+      const long pix = conv_src_pixel(p, m, ky, kx);
       src = (const char*)p.A + (pix * p.lda + c0) * 2 + cc * 16;
     } else {
       src = (const char*)p.A + ((long)m * p.lda + (long)t * 64) * 2 + c * 16;
@@ -234,7 +246,7 @@ __device__ __forceinline__ void stage_narrow(const GemmParams& p, int row0, int 
     const int seg = wave + 4 * i;
     if (seg < 2 * NT) {
       const int row = seg * 8 + (lane >> 3);
-      const int c = pos ^ ((row >> 1) & 7);
+      const int c = swz_src_chunk(row, lane);
       const char* src = (const char*)p.W + ((long)(n0 + row) * p.ldw + (long)t * 64) * 2 + c * 16;
       __builtin_amdgcn_global_load_lds(GLB_PTR(src), LDS_PTR(lds_w + seg * 1024), 16, 0, 0);
     }
@@ -275,20 +287,7 @@ __global__ __launch_bounds__(256) void gemm_narrow_kernel(GemmParams p) {
       for (int i = 0; i < 4; ++i) fa[i] = *(const bf16x8*)(la + i * 16 * 128 + off);
 #pragma unroll
       for (int i = 0; i < NT; ++i) fw[i] = *(const bf16x8*)(lw + i * 16 * 128 + off);
-      if (p.f16) {
-#pragma unroll
-        for (int ni = 0; ni < NT; ++ni)
-#pragma unroll
-          for (int mi = 0; mi < 4; ++mi)
-            acc[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, fw[ni]),
-                                                                 __builtin_bit_cast(f16x8, fa[mi]), acc[ni][mi], 0, 0, 0);
-      } else {
-#pragma unroll
-        for (int ni = 0; ni < NT; ++ni)
-#pragma unroll
-          for (int mi = 0; mi < 4; ++mi)
-            acc[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[ni], fa[mi], acc[ni][mi], 0, 0, 0);
-      }
+      mfma_step16<NT>(p, fw, fa, acc);
     }
     __syncthreads();
     cur ^= 1;
@@ -299,40 +298,53 @@ __global__ __launch_bounds__(256) void gemm_narrow_kernel(GemmParams p) {
 template <bool OUT_BF16, int ACT, bool CONV>
 static int launch_narrow(const GemmParams& p, hipStream_t stream) {
   const int nbm = (p.M + NBM - 1) / NBM;
-  if (p.N % 64 == 0) {
-    auto kern = gemm_narrow_kernel<4, OUT_BF16, ACT, CONV>;
-    constexpr int lds = 2 * (NBM * 128 + 64 * 128);
-    static unsigned long long optin = 0;
-    if (int rc = pi3_lds_optin((const void*)kern, lds, &optin, "gemm_narrow")) return rc;
-    hipLaunchKernelGGL(kern, dim3(nbm * (p.N / 64)), dim3(256), lds, stream, p);
-  } else {
-    auto kern = gemm_narrow_kernel<2, OUT_BF16, ACT, CONV>;
-    constexpr int lds = 2 * (NBM * 128 + 32 * 128);
-    static unsigned long long optin = 0;
-    if (int rc = pi3_lds_optin((const void*)kern, lds, &optin, "gemm_narrow")) return rc;
-    hipLaunchKernelGGL(kern, dim3(nbm * (p.N / 32)), dim3(256), lds, stream, p);
-  }
-  return pi3_check_launch("gemm_narrow");
+  if (p.N % 64 == 0)
+    return gemm_launch<gemm_narrow_kernel<4, OUT_BF16, ACT, CONV>>("gemm_narrow", nbm * (p.N / 64), 256,
+                                                                   2 * (NBM * 128 + 64 * 128), p, stream);
+  return gemm_launch<gemm_narrow_kernel<2, OUT_BF16, ACT, CONV>>("gemm_narrow", nbm * (p.N / 32), 256,
+                                                                 2 * (NBM * 128 + 32 * 128), p, stream);
 }
 
-int pi3_gemm256_try(const GemmParams& p, int out_dtype, int act, hipStream_t stream);
+// ---- entry points.  The (out_dtype, act) pairs each kernel family instantiates (gemm_dispatch, gemm_common.h):
+using Linear16Pairs = OutActs<OutAct<true, 0>, OutAct<true, 1>, OutAct<false, 0>, OutAct<false, 2>>;   // 16-bit operands
+using LinearF32Pairs = OutActs<OutAct<false, 0>, OutAct<false, 2>, OutAct<true, 0>>;                   // fp32 operands
+using ConvPairs = OutActs<OutAct<true, 0>, OutAct<false, 0>, OutAct<true, 2>>;                         // pi3_conv3x3
+
+int pi3_gemm256_try(GemmParams p, int out_dtype, int act, hipStream_t stream);
+
+// dtype code 2 = IEEE half: the bf16 code paths with the f16 MFMA / conversion selected at run time (GemmParams.f16).
+// Folds the codes to 0 and returns the flag; a 16-bit output has the operands' format (one flag).
+static int fold_half(int& in_dtype, int& out_dtype) {
+  const int f16 = (in_dtype == 2 || out_dtype == 2) ? 1 : 0;
+  if (in_dtype == 2) in_dtype = 0;
+  if (out_dtype == 2) out_dtype = 0;
+  return f16;
+}
+
+// the LDS-DMA moves 16 bytes per lane and the epilogues store 8 / 16 bytes per lane (esz: bytes per operand element)
+static int check_aligned(const char* who, const void* A, long lda, const void* W, long ldw, int esz, const void* out,
+                         long ldo) {
+  if ((lda * esz) % 16 || (ldw * esz) % 16 || ((uintptr_t)A & 15) || ((uintptr_t)W & 15) || ((uintptr_t)out & 15) ||
+      (ldo % 4)) {
+    pi3_set_error("%s: operands must be 16-byte aligned with 16-byte-multiple row strides", who);
+    return PI3_ERR_ARG;
+  }
+  return PI3_OK;
+}
 
 // in_dtype: 0 = bf16 operands, 1 = f32 operands.  out_dtype: 0 = bf16, 1 = f32.  act: 0 none, 1 GELU(erf), 2 ReLU.
 extern "C" int pi3_gemm(const void* A, long lda, const void* W, long ldw, int M, int N, int K, int in_dtype,
                         const float* bias, const float* gamma, const float* resid, long ldr, void* out, long ldo,
                         int out_dtype, int act, int rpg, int gstride, int goff, const float* addtab, long ldadd,
                         float qscale, int qcols, void* stream) {
-  // in_dtype 2 = IEEE-half operands, out_dtype 2 = IEEE-half output: the bf16 code paths with the f16 MFMA / conversion
-  // selected at run time (GemmParams.f16).  A 16-bit output has the operands' format (one flag).
-  const int f16 = (in_dtype == 2 || out_dtype == 2) ? 1 : 0;
-  if (in_dtype < 0 || in_dtype > 2 || out_dtype < 0 || out_dtype > 2 || (f16 && (in_dtype == 0 || out_dtype == 0)) ||
-      (f16 && in_dtype == 1)) {
+  // in_dtype 2 = IEEE-half operands, out_dtype 2 = IEEE-half output; half operands give a half or f32 output, never bf16
+  if (in_dtype < 0 || in_dtype > 2 || out_dtype < 0 || out_dtype > 2 || (in_dtype == 2 && out_dtype == 0) ||
+      (out_dtype == 2 && in_dtype != 2)) {
     pi3_set_error("pi3_gemm: unsupported dtypes in=%d out=%d (0 bf16, 1 f32, 2 f16; f16 operands give f16 or f32 output, "
                   "bf16 operands bf16 or f32)", in_dtype, out_dtype);
     return PI3_ERR_ARG;
   }
-  if (in_dtype == 2) in_dtype = 0;
-  if (out_dtype == 2) out_dtype = 0;
+  const int f16 = fold_half(in_dtype, out_dtype);
   const int bk = in_dtype == 0 ? 64 : 32;
   const bool narrow = in_dtype == 0 && (N % BN) != 0 && (N % 32) == 0;     // bf16 operands, N = 32, 64, 96, 160, ...
   if (!A || !W || !out || M <= 0 || N <= 0 || K <= 0 || ((N % BN) != 0 && !narrow) || (K % bk) != 0 || act < 0 || act > 2) {
@@ -340,51 +352,40 @@ extern "C" int pi3_gemm(const void* A, long lda, const void* W, long ldw, int M,
                   M, N, K, bk);
     return PI3_ERR_ARG;
   }
-  if ((lda * (in_dtype == 0 ? 2 : 4)) % 16 || (ldw * (in_dtype == 0 ? 2 : 4)) % 16 || ((uintptr_t)A & 15) ||
-      ((uintptr_t)W & 15) || ((uintptr_t)out & 15) || (ldo % 4)) {
-    pi3_set_error("pi3_gemm: operands must be 16-byte aligned with 16-byte-multiple row strides");
-    return PI3_ERR_ARG;
-  }
+  if (int rc = check_aligned("pi3_gemm", A, lda, W, ldw, in_dtype == 0 ? 2 : 4, out, ldo)) return rc;
   // the epilogues decide n < qcols once per group of 4 columns (one lane's f32x4): a boundary inside a group would
   // scale the whole group
   if (qcols < 0 || qcols > N || (qcols % 4) != 0) {
     pi3_set_error("pi3_gemm: qcols=%d must be a multiple of 4 in [0, N=%d]", qcols, N);
     return PI3_ERR_ARG;
   }
-  GemmParams p;
+  GemmParams p{};
   p.A = A; p.lda = lda; p.W = W; p.ldw = ldw; p.M = M; p.N = N; p.K = K;
   p.bias = bias; p.gamma = gamma; p.resid = resid; p.ldr = ldr; p.out = out; p.ldo = ldo;
   p.rpg = rpg; p.gstride = gstride; p.goff = goff; p.addtab = addtab; p.ldadd = ldadd;
-  p.qscale = qscale; p.qcols = qcols;
-  p.cH = 0; p.cW = 0; p.cC = 0; p.f16 = f16;
-  p.qk_mode = 0; p.qk_k2max = nullptr; p.tile_gm = 0;
+  p.qscale = qscale; p.qcols = qcols; p.f16 = f16;
   hipStream_t s = (hipStream_t)stream;
   if (narrow) {
-    if (out_dtype == 0 && act == 0) return launch_narrow<true, 0, false>(p, s);
-    if (out_dtype == 0 && act == 1) return launch_narrow<true, 1, false>(p, s);
-    if (out_dtype == 1 && act == 0) return launch_narrow<false, 0, false>(p, s);
-    if (out_dtype == 1 && act == 2) return launch_narrow<false, 2, false>(p, s);
-    pi3_set_error("pi3_gemm: unsupported (out_dtype=%d, act=%d) for a narrow N", out_dtype, act);
+    const int rc = gemm_dispatch(Linear16Pairs{}, out_dtype, act,
+                                 [&](auto oa) { return launch_narrow<oa.OUT16, oa.ACT, false>(p, s); });
+    if (rc == 1) {
+      pi3_set_error("pi3_gemm: unsupported (out_dtype=%d, act=%d) for a narrow N", out_dtype, act);
+      return PI3_ERR_ARG;
+    }
+    return rc;
+  }
+  int rc = 1;   // 1 = not served yet
+  // large bf16 GEMMs: 256x256 pipelined kernel (development switch PI3_GEMM_IMPL=1, common.h, forces the 128x128 kernel)
+  if (in_dtype == 0 && !f16 && PI3_DEV_ENV_INT("PI3_GEMM_IMPL", 0) != 1) rc = pi3_gemm256_try(p, out_dtype, act, s);
+  if (rc == 1 && in_dtype == 0)
+    rc = gemm_dispatch(Linear16Pairs{}, out_dtype, act, [&](auto oa) { return launch_gemm<true, oa.OUT16, oa.ACT>(p, s); });
+  if (rc == 1 && in_dtype == 1)
+    rc = gemm_dispatch(LinearF32Pairs{}, out_dtype, act, [&](auto oa) { return launch_gemm<false, oa.OUT16, oa.ACT>(p, s); });
+  if (rc == 1) {
+    pi3_set_error("pi3_gemm: unsupported (in_dtype=%d,out_dtype=%d,act=%d) combination", in_dtype, out_dtype, act);
     return PI3_ERR_ARG;
   }
-  if (in_dtype == 0 && !f16) {  // large bf16 GEMMs: 256x256 pipelined kernel (development switch PI3_GEMM_IMPL=1 forces the 128x128 kernel)
-    if (PI3_DEV_ENV_INT("PI3_GEMM_IMPL", 0) != 1) {     // (development switch, common.h)
-      const int rc = pi3_gemm256_try(p, out_dtype, act, s);
-      if (rc <= 0) return rc;
-    }
-  }
-#define GEMM_CASE(INB, OUTB, ACTV) \
-  if ((in_dtype == 0) == INB && (out_dtype == 0) == OUTB && act == ACTV) return launch_gemm<INB, OUTB, ACTV>(p, s);
-  GEMM_CASE(true, true, 0)
-  GEMM_CASE(true, true, 1)
-  GEMM_CASE(true, false, 0)
-  GEMM_CASE(true, false, 2)
-  GEMM_CASE(false, false, 0)
-  GEMM_CASE(false, false, 2)
-  GEMM_CASE(false, true, 0)
-#undef GEMM_CASE
-  pi3_set_error("pi3_gemm: unsupported (in_dtype=%d,out_dtype=%d,act=%d) combination", in_dtype, out_dtype, act);
-  return PI3_ERR_ARG;
+  return rc;
 }
 
 // The packed qkv projection of a transformer block with what follows it on q and k fused into the epilogue
@@ -411,33 +412,27 @@ extern "C" int pi3_gemm_qkv(const void* A, long lda, const void* W, long ldw, in
     pi3_set_error("pi3_gemm_qkv: bad arguments M=%d K=%d H=%d T=%d (packed [M][3*H*64] output, K %% 64 == 0)", M, K, H, T);
     return PI3_ERR_ARG;
   }
-  if ((lda * 2) % 16 || (ldw * 2) % 16 || ((uintptr_t)A & 15) || ((uintptr_t)W & 15) || ((uintptr_t)qkv & 15)) {
-    pi3_set_error("pi3_gemm_qkv: operands must be 16-byte aligned with 16-byte-multiple row strides");
-    return PI3_ERR_ARG;
-  }
+  if (int rc = check_aligned("pi3_gemm_qkv", A, lda, W, ldw, 2, qkv, ldo)) return rc;   // (ldo == N: a multiple of 128)
   hipStream_t s = (hipStream_t)stream;
   if (k2max && hipMemsetAsync(k2max, 0, (size_t)attn_B * H * sizeof(float), s) != hipSuccess) {
     pi3_set_error("pi3_gemm_qkv: hipMemsetAsync failed");
     return PI3_ERR_LAUNCH;
   }
-  GemmParams p;
-  p.A = A; p.lda = lda; p.W = W; p.ldw = ldw; p.M = M; p.N = N; p.K = K;
-  p.bias = bias; p.gamma = nullptr; p.resid = nullptr; p.ldr = 0; p.out = qkv; p.ldo = ldo;
-  p.rpg = 0; p.gstride = 0; p.goff = 0; p.addtab = nullptr; p.ldadd = 0; p.qscale = 1.f; p.qcols = 0;
-  p.cH = 0; p.cW = 0; p.cC = 0; p.tile_gm = 0; p.f16 = 0;
-  p.qk_mode = 1; p.qk_H = H; p.qk_T = T; p.qk_pos = pos; p.qk_cs = cs;
-  p.qk_qw = qw; p.qk_qb = qb; p.qk_kw = kw; p.qk_kb = kb; p.qk_eps = eps; p.qk_qscale = qscale;
-  p.qk_k2max = k2max; p.qk_attnS = attn_S > 0 ? attn_S : M;
+  GemmParams p{};          // the plain projection
+  p.A = A; p.lda = lda; p.W = W; p.ldw = ldw; p.M = M; p.N = N; p.K = K; p.bias = bias; p.out = qkv; p.ldo = ldo;
   if (!qw && !pos) {       // no LayerNorm, no RoPE (encoder blocks): the q scale rides in the plain epilogue, as in pi3_gemm
     p.qscale = qscale;
     p.qcols = H * 64;
   }
   if (PI3_DEV_ENV_INT("PI3_QKV_FUSE", 1)) {    // development switch: 0 = always the two-pass form (both forms are correct)
-    const int rc = pi3_gemm256_try(p, 0, 0, s);
+    GemmParams f = p;      // the same projection with the fused q/k epilogue
+    f.qk_mode = 1; f.qk_H = H; f.qk_T = T; f.qk_pos = pos; f.qk_cs = cs;
+    f.qk_qw = qw; f.qk_qb = qb; f.qk_kw = kw; f.qk_kb = kb; f.qk_eps = eps; f.qk_qscale = qscale;
+    f.qk_k2max = k2max; f.qk_attnS = attn_S > 0 ? attn_S : M;
+    const int rc = pi3_gemm256_try(f, 0, 0, s);
     if (rc <= 0) return rc;
   }
   // two-pass form: plain projection, then the in-place q/k pass, then the key-norm pre-pass
-  p.qk_mode = 0; p.qk_k2max = nullptr; p.tile_gm = 0;
   int rc = pi3_gemm256_try(p, 0, 0, s);
   if (rc > 0) rc = launch_gemm<true, true, 0>(p, s);
   if (rc != 0) return rc;
@@ -463,7 +458,7 @@ extern "C" int pi3_conv3x3(const void* img, long ldc, int B, int H, int W, int C
                   out_dtype);
     return PI3_ERR_ARG;
   }
-  if (out_dtype == 2) out_dtype = 0;
+  const int f16 = fold_half(in_dtype, out_dtype);
   const bool narrow = (N % BN) != 0 || C == 32;
   if (!img || !wgt || !out || B <= 0 || H <= 0 || W <= 0 || C <= 0 || ((C % 64) && C != 32) || N <= 0 || (N % 32) ||
       (ldc % 8) || ((uintptr_t)img & 15) || ((uintptr_t)wgt & 15) || ((uintptr_t)out & 15) || (ldo % 4) || act < 0 ||
@@ -471,25 +466,20 @@ extern "C" int pi3_conv3x3(const void* img, long ldc, int B, int H, int W, int C
     pi3_set_error("pi3_conv3x3: bad arguments B=%d H=%d W=%d C=%d N=%d (C %% 64 == 0 or C == 32, N %% 32 == 0)", B, H, W, C, N);
     return PI3_ERR_ARG;
   }
-  GemmParams p;
+  GemmParams p{};
   // C == 32: weight rows are [10 taps][32] (the tenth tap zero), two taps per K-step
   const long kw = C == 32 ? 320 : 9L * C;
   p.A = img; p.lda = ldc; p.W = wgt; p.ldw = kw; p.M = B * H * W; p.N = N; p.K = (int)kw;
-  p.bias = bias; p.gamma = nullptr; p.resid = resid; p.ldr = ldr; p.out = out; p.ldo = ldo;
-  p.rpg = 0; p.gstride = 0; p.goff = 0; p.addtab = nullptr; p.ldadd = 0; p.qscale = 1.f; p.qcols = 0;
-  p.cH = H; p.cW = W; p.cC = C; p.f16 = in_dtype == 2;
-  p.qk_mode = 0; p.qk_k2max = nullptr; p.tile_gm = 0;
+  p.bias = bias; p.resid = resid; p.ldr = ldr; p.out = out; p.ldo = ldo;
+  p.cH = H; p.cW = W; p.cC = C; p.f16 = f16;
   hipStream_t s = (hipStream_t)stream;
-  if (narrow) {
-    if (out_dtype == 0 && act == 0) return launch_narrow<true, 0, true>(p, s);
-    if (out_dtype == 1 && act == 0) return launch_narrow<false, 0, true>(p, s);
-    if (out_dtype == 0 && act == 2) return launch_narrow<true, 2, true>(p, s);
+  const int rc = narrow ? gemm_dispatch(ConvPairs{}, out_dtype, act,
+                                        [&](auto oa) { return launch_narrow<oa.OUT16, oa.ACT, true>(p, s); })
+                        : gemm_dispatch(ConvPairs{}, out_dtype, act,
+                                        [&](auto oa) { return launch_gemm<true, oa.OUT16, oa.ACT, true>(p, s); });
+  if (rc == 1) {
     pi3_set_error("pi3_conv3x3: unsupported (out_dtype=%d, act=%d)", out_dtype, act);
     return PI3_ERR_ARG;
   }
-  if (out_dtype == 0 && act == 0) return launch_gemm<true, true, 0, true>(p, s);
-  if (out_dtype == 1 && act == 0) return launch_gemm<true, false, 0, true>(p, s);
-  if (out_dtype == 0 && act == 2) return launch_gemm<true, true, 2, true>(p, s);
-  pi3_set_error("pi3_conv3x3: unsupported (out_dtype=%d, act=%d)", out_dtype, act);
-  return PI3_ERR_ARG;
+  return rc;
 }

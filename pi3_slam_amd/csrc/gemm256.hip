@@ -31,6 +31,10 @@
 //   no wave priorities / the load segment at priority 1: row "wave priorities of the ping-pong loop"
 //   plain instead of non-temporal stores of the bf16 output: row "non-temporal stores of the bf16 output rows"
 // Development builds (make dev) add the variants of gemm256_dev.inc and the STAG = false / ILVK / M32 instances.
+//
+// Host side: pi3_gemm256_try (called from gemm.hip) declines what the kernel does not serve, sets the launch's own fields
+// in its copy of the block and maps (out_dtype, act) to an instance with gemm_dispatch; launch256 (and launch3 / launch4w
+// of gemm256_dev.inc) size the grid and go through gemm_launch (gemm_common.h).
 #include "gemm_common.h"
 #include <stdlib.h>
 
@@ -64,6 +68,37 @@ __device__ __forceinline__ float g2_sum_rows4(float s) {
 __device__ __forceinline__ void g4_glds16(const char* sbase, unsigned voff, unsigned lds_dst) {
   asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(lds_dst)
                : "memory", "m0");
+}
+
+// ---- pieces of the fused q/k epilogue (g2_epilogue_lds<.., QK>)
+// ksq += the squares of the four bf16 values of one stored u32x2, one packed word (lo^2 + hi^2) at a time: |k|^2 of the
+// STORED values, as the attention kernel will read them.  By reference: the sum keeps its association.
+__device__ __forceinline__ void g2_add_squares(float& ksq, u32x2 o) {
+#pragma unroll
+  for (int e = 0; e < 2; ++e) {
+    const float lo = __uint_as_float(o[e] << 16), hi = __uint_as_float(o[e] & 0xffff0000u);
+    ksq += lo * lo + hi * hi;
+  }
+}
+
+// Row m's |k|^2 (ksq: this lane's 16 of the 64 dims) into the running maximum of its attention batch: k2 for rows below
+// qk_split (the first row of the next batch), k2n from there on
+__device__ __forceinline__ void g2_fold_k2(float ksq, int m, int M, long qk_split, float& k2, float& k2n) {
+  ksq = g2_sum_rows4(ksq);
+  if (m < M) {
+    if (m < qk_split) k2 = fmaxf(k2, ksq);
+    else k2n = fmaxf(k2n, ksq);
+  }
+}
+
+// (cos, sin) of frequencies nq .. nq + 3 at token t's y and x position; pos [T][2] and cs [npos][16][2] are the tables
+// of the launch, in LDS or in global memory
+struct G2Rope { f32x4 cy0, cy1, cx0, cx1; };
+__device__ __forceinline__ G2Rope g2_rope_fetch(const int* pos, const float* cs, int t, int nq) {
+  const int py = pos[2 * t], px = pos[2 * t + 1];
+  const float* ty = cs + ((long)py * 16 + nq) * 2;
+  const float* tx = cs + ((long)px * 16 + nq) * 2;
+  return {*(const f32x4*)ty, *(const f32x4*)(ty + 4), *(const f32x4*)tx, *(const f32x4*)(tx + 4)};
 }
 
 // Epilogue through LDS (all pipeline buffers are dead after the last barrier): each wave transposes its 128 (m) x 64 (n)
@@ -165,25 +200,17 @@ __device__ __forceinline__ void g2_epilogue_lds(const GemmParams& p, f32x4 (&acc
             for (int ni = 0; ni < 4; ++ni) x[ni] = x[ni] * rstd * lnw[ni] + lnb[ni];
           }
           if (p.qk_pos) {
-            f32x4 cy0, cy1, cx0, cx1;
+            G2Rope rc;
             if (pos_l) {     // tables in LDS; the row's token index without a division (rows beyond M: any valid token)
               int t = qk_t0 + pass * ROWS_PER_PASS + mq * 16 + frow;
               if (p.qk_T >= 256) t = t >= p.qk_T ? t - p.qk_T : t;
               else t %= p.qk_T;
-              const int py = pos_l[2 * t], px = pos_l[2 * t + 1];
-              const float* ty = cs_l + (py * 16 + nq) * 2;            // (cos, sin) of freq nq .. nq+3
-              const float* tx = cs_l + (px * 16 + nq) * 2;
-              cy0 = *(const f32x4*)ty; cy1 = *(const f32x4*)(ty + 4);
-              cx0 = *(const f32x4*)tx; cx1 = *(const f32x4*)(tx + 4);
+              rc = g2_rope_fetch(pos_l, cs_l, t, nq);
             } else {
               const int m = m_base + pass * ROWS_PER_PASS + mq * 16 + frow;
-              const int t = (m < p.M ? m : p.M - 1) % p.qk_T;
-              const int py = p.qk_pos[2 * t], px = p.qk_pos[2 * t + 1];
-              const float* ty = p.qk_cs + ((long)py * 16 + nq) * 2;
-              const float* tx = p.qk_cs + ((long)px * 16 + nq) * 2;
-              cy0 = *(const f32x4*)ty; cy1 = *(const f32x4*)(ty + 4);
-              cx0 = *(const f32x4*)tx; cx1 = *(const f32x4*)(tx + 4);
+              rc = g2_rope_fetch(p.qk_pos, p.qk_cs, (m < p.M ? m : p.M - 1) % p.qk_T, nq);
             }
+            const f32x4 cy0 = rc.cy0, cy1 = rc.cy1, cx0 = rc.cx0, cx1 = rc.cx1;
             const float cyv[4] = {cy0[0], cy0[2], cy1[0], cy1[2]}, syv[4] = {cy0[1], cy0[3], cy1[1], cy1[3]};
             const float cxv[4] = {cx0[0], cx0[2], cx1[0], cx1[2]}, sxv[4] = {cx0[1], cx0[3], cx1[1], cx1[3]};
 #pragma unroll
@@ -203,22 +230,10 @@ __device__ __forceinline__ void g2_epilogue_lds(const GemmParams& p, f32x4 (&acc
             o[0] = pack_bf16x2(x[ni][0] * sc, x[ni][1] * sc);
             o[1] = pack_bf16x2(x[ni][2] * sc, x[ni][3] * sc);
             *(u32x2*)(rowp + (ni * 16 + nq) * 2) = o;
-            if (qk_part == 1) {      // |k|^2 of the STORED (bf16) values, as the attention kernel will read them
-#pragma unroll
-              for (int e = 0; e < 2; ++e) {
-                const float lo = __uint_as_float(o[e] << 16), hi = __uint_as_float(o[e] & 0xffff0000u);
-                ksq += lo * lo + hi * hi;
-              }
-            }
+            if (qk_part == 1) g2_add_squares(ksq, o);
           }
-          if (qk_part == 1 && p.qk_k2max) {
-            ksq = g2_sum_rows4(ksq);
-            const int m = m_base + pass * ROWS_PER_PASS + mq * 16 + frow;
-            if (m < p.M) {
-              if (m < qk_split) k2 = fmaxf(k2, ksq);
-              else k2n = fmaxf(k2n, ksq);
-            }
-          }
+          if (qk_part == 1 && p.qk_k2max)
+            g2_fold_k2(ksq, m_base + pass * ROWS_PER_PASS + mq * 16 + frow, p.M, qk_split, k2, k2n);
           continue;
         }
       }
@@ -245,27 +260,15 @@ __device__ __forceinline__ void g2_epilogue_lds(const GemmParams& p, f32x4 (&acc
           o[1] = pack_bf16x2(v[2], v[3]);
           *(u32x2*)(rowp + (ni * 16 + nq) * 2) = o;
           if constexpr (QK) {
-            if (qk_part == 1 && p.qk_k2max) {
-#pragma unroll
-              for (int e = 0; e < 2; ++e) {
-                const float lo = __uint_as_float(o[e] << 16), hi = __uint_as_float(o[e] & 0xffff0000u);
-                ksq_plain += lo * lo + hi * hi;
-              }
-            }
+            if (qk_part == 1 && p.qk_k2max) g2_add_squares(ksq_plain, o);
           }
         } else {
           *(f32x4*)(rowp + (ni * 16 + nq) * 4) = v;
         }
       }
       if constexpr (QK) {
-        if (qk_part == 1 && p.qk_k2max) {
-          ksq_plain = g2_sum_rows4(ksq_plain);
-          const int m = m_base + pass * ROWS_PER_PASS + mq * 16 + frow;
-          if (m < p.M) {
-            if (m < qk_split) k2 = fmaxf(k2, ksq_plain);
-            else k2n = fmaxf(k2n, ksq_plain);
-          }
-        }
+        if (qk_part == 1 && p.qk_k2max)
+          g2_fold_k2(ksq_plain, m_base + pass * ROWS_PER_PASS + mq * 16 + frow, p.M, qk_split, k2, k2n);
       }
     }
     // ---- LDS -> global, whole rows
@@ -730,15 +733,9 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmParams p) {
   }   // tiles of this workgroup
 }
 
-template <bool OUT_BF16, int ACT, bool NOEPI = false, bool STAG = false, bool QK = false, bool ILVK = false, bool M32 = false>
-static int launch256(const GemmParams& p, hipStream_t stream) {
-  const int nbm = (p.M + G2_BM - 1) / G2_BM, nbn = p.N / G2_BN;
-  auto kern = gemm256_kernel<OUT_BF16, ACT, NOEPI, STAG, QK, ILVK, M32>;
-  static unsigned long long optin = 0;
-  constexpr int LDS_BYTES = QK ? G2_LDS_QK : G2_LDS_TOTAL;
-  if (int rc = pi3_lds_optin((const void*)kern, LDS_BYTES, &optin, "gemm256")) return rc;
-  // development switch PI3_GEMM_PERSIST: 1 (default) one workgroup per CU walking tiles | 0 a workgroup per tile
-  const int persist = PI3_DEV_ENV_INT("PI3_GEMM_PERSIST", 1);
+// Grid of the persistent form: one workgroup per CU, the CU count rounded down to a multiple of 8 (a workgroup stays
+// on its XCD), 256 where the device cannot be asked; fewer tiles than that: a workgroup per tile.
+static int g2_persistent_grid(int nwg) {
   static int ncu = 0;
   if (!ncu) {
     int dev = 0;
@@ -747,113 +744,109 @@ static int launch256(const GemmParams& p, hipStream_t stream) {
       ncu = prop.multiProcessorCount & ~7;
     if (ncu <= 0) ncu = 256;
   }
-  const int nwg = nbm * nbn;
-  const int grid = (persist && nwg > ncu) ? ncu : nwg;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), LDS_BYTES, stream, p);
-  return pi3_check_launch("gemm256");
+  return nwg > ncu ? ncu : nwg;
+}
+
+template <bool OUT_BF16, int ACT, bool NOEPI = false, bool STAG = false, bool QK = false, bool ILVK = false, bool M32 = false>
+static int launch256(const GemmParams& p, hipStream_t stream) {
+  const int nwg = ((p.M + G2_BM - 1) / G2_BM) * (p.N / G2_BN);
+  // development switch PI3_GEMM_PERSIST: 1 (default) one workgroup per CU walking tiles | 0 a workgroup per tile
+  const int grid = PI3_DEV_ENV_INT("PI3_GEMM_PERSIST", 1) ? g2_persistent_grid(nwg) : nwg;
+  return gemm_launch<gemm256_kernel<OUT_BF16, ACT, NOEPI, STAG, QK, ILVK, M32>>("gemm256", grid, 512,
+                                                                               QK ? G2_LDS_QK : G2_LDS_TOTAL, p, stream);
 }
 
 #ifdef PI3_DEV_VARIANTS   // gemm3_kernel (PI3_GEMM_IMPL=3) and gemm4w_kernel (knob gemm_4w): measured slower, bit-identical - development builds
 #include "gemm256_dev.inc"
 #endif   // PI3_DEV_VARIANTS
 
-// Used by pi3_gemm (gemm.hip) for bf16 operands when N % 256 == 0 and M is large.  Returns 1 if not applicable.
-int pi3_gemm256_try(const GemmParams& p, int out_dtype, int act, hipStream_t stream) {
+// Used by pi3_gemm / pi3_gemm_qkv (gemm.hip) for bf16 operands when N % 256 == 0 and M is large.  Returns 1 if not
+// applicable.  p is the caller's block by value: what the 256x256 launch adds to it (below) stays in here.
+using G256Pairs = OutActs<OutAct<true, 0>, OutAct<true, 1>, OutAct<true, 3>, OutAct<false, 0>>;
+#ifdef PI3_DEV_VARIANTS
+using G256DevPairs = OutActs<OutAct<true, 0>, OutAct<true, 1>, OutAct<false, 0>>;   // every development family
+#endif
+
+int pi3_gemm256_try(GemmParams p, int out_dtype, int act, hipStream_t stream) {
   if ((p.N % G2_BN) != 0 || (p.K % 64) != 0 || p.M < 1024) return 1;
   if (p.qcols % 16) return 1;          // the bf16 epilogue tests n < qcols per 16-column tile (wave-uniform)
   if (out_dtype == 0 && (p.resid || p.addtab)) return 1;   // the bf16 streaming pass carries no residual / table add
   // the LDS-DMA addresses a row through a 32-bit byte offset from the matrix base
   if ((long)p.M * p.lda * 2 >= (1l << 32) || (long)p.N * p.ldw * 2 >= (1l << 32)) return 1;
-  // development switches (constants in the product build, common.h): PI3_GEMM_GM = m-tiles per scheduling group (any
-  // value gives the same results); PI3_GEMM_ORDER: 0 m-tiles first inside a group | 1 column tiles first | -1: by shape.
-  // With four column tiles (N = 1024: proj, fc2) walking a row panel's column tiles first measured 2 % / 3-4 % faster
-  // (the activation panel of a row is fetched by one round of one XCD's workgroups and the 2-8 MB of weights stay in
-  // L2 anyway); with 12-16 column tiles (qkv, fc1) it is 2-3 % slower.
-  const_cast<GemmParams&>(p).tile_gm = PI3_DEV_ENV_INT("PI3_GEMM_GM", 0);
-  const int order_knob = PI3_DEV_ENV_INT("PI3_GEMM_ORDER", -1);
-  const_cast<GemmParams&>(p).tile_order = order_knob >= 0 ? order_knob : (p.N / G2_BN <= 4 ? 1 : 0);
-  const_cast<GemmParams&>(p).stagger_ns = (int)PI3_DEV_KNOB("gemm_stagger_ns", 0);
-  const_cast<GemmParams&>(p).ilv_prio = 0;
-  const_cast<GemmParams&>(p).rpref = (int)PI3_DEV_KNOB("gemm_rpref", 0);
-  // knob gelu_form (product): 1 = the sigmoid form of GELU's tanh approximation in the fc1 epilogue
-  if (act == 1 && PI3_KNOB("gelu_form", 0) == 1) act = 3;
-#ifdef PI3_DEV_ABLATIONS   // timing-only variant that writes NOTHING: development builds only
-  // knob gemm_abl (bits): 1 = no epilogue at all, 2 = no LDS-DMA issues in the K loop, 4 = no fragment reads
-  const int abl = (int)PI3_KNOB("gemm_abl", 0);
-  const_cast<GemmParams&>(p).abl = abl;
-#endif
   if (p.qk_mode) {   // fused q/k head epilogue: bf16 output, no activation, one head per wave column block
     if (out_dtype != 0 || act != 0 || p.gamma || p.rpg || p.N != 3 * p.qk_H * 64 ||
         (p.qk_k2max && p.qk_attnS < 128))
       return 1;
   }
+  // ---- the fields of the block that belong to this launch (nobody else sets them)
+  // development switches (constants in the product build, common.h): PI3_GEMM_GM = m-tiles per scheduling group (any
+  // value gives the same results); PI3_GEMM_ORDER: 0 m-tiles first inside a group | 1 column tiles first | -1: by shape.
+  // With four column tiles (N = 1024: proj, fc2) walking a row panel's column tiles first measured 2 % / 3-4 % faster
+  // (the activation panel of a row is fetched by one round of one XCD's workgroups and the 2-8 MB of weights stay in
+  // L2 anyway); with 12-16 column tiles (qkv, fc1) it is 2-3 % slower.
+  p.tile_gm = PI3_DEV_ENV_INT("PI3_GEMM_GM", 0);
+  const int order_knob = PI3_DEV_ENV_INT("PI3_GEMM_ORDER", -1);
+  p.tile_order = order_knob >= 0 ? order_knob : (p.N / G2_BN <= 4 ? 1 : 0);
+  p.stagger_ns = (int)PI3_DEV_KNOB("gemm_stagger_ns", 0);
+  p.rpref = (int)PI3_DEV_KNOB("gemm_rpref", 0);
+  const int ilv = (int)PI3_DEV_KNOB("gemm_ilv", 0);      // interleaved K loop (development builds), 2 / 3: wave priorities
+  p.ilv_prio = ilv ? ilv - 1 : 0;
+#ifdef PI3_DEV_ABLATIONS   // timing-only variant that writes NOTHING: development builds only
+  // knob gemm_abl (bits): 1 = no epilogue at all, 2 = no LDS-DMA issues in the K loop, 4 = no fragment reads
+  p.abl = (int)PI3_KNOB("gemm_abl", 0);
+#endif
+  // knob gelu_form (product): 1 = the sigmoid form of GELU's tanh approximation in the fc1 epilogue
+  if (act == 1 && PI3_KNOB("gelu_form", 0) == 1) act = 3;
 #ifdef PI3_DEV_VARIANTS
   // Development variants, every one bit-identical to the shipped kernel (tests/test_dev_variants_gpu.py):
   //   PI3_GEMM_IMPL=3  gemm3_kernel: two 128 x 256 workgroups per CU;
   //   knob gemm_4w     gemm4w_kernel: one wave per SIMD, 128 x 128 per wave (2: reads and DMA issues between the MFMAs);
-  //   knob gemm_ilv    the eight-wave kernel's interleaved K loop (2 / 3: wave priorities);
+  //   knob gemm_ilv    the eight-wave kernel's interleaved K loop;
+  //   knob gemm_mfma32 the 32x32x16 K loop (prototype: see gemm256_kernel);
   //   PI3_GEMM_STAG=0  all eight waves in lockstep.
+  // The first family that is switched on and has the (out_dtype, act) pair serves the call (both GELU forms: its one).
   {
-    const int impl3 = PI3_DEV_ENV_INT("PI3_GEMM_IMPL", 0) == 3;
+    const bool impl3 = PI3_DEV_ENV_INT("PI3_GEMM_IMPL", 0) == 3 && (p.K % 32) == 0;
     const int impl4 = (int)PI3_KNOB("gemm_4w", 0);
-    const int ilv = (int)PI3_KNOB("gemm_ilv", 0);
     if (p.qk_mode) {
       if (impl4 == 2) return launch4w<true, 0, true, true>(p, stream);
       if (impl4) return launch4w<true, 0, true>(p, stream);
-      if (impl3 && (p.K % 32) == 0) return launch3<true, 0, true>(p, stream);
-      if (ilv) {
-        const_cast<GemmParams&>(p).ilv_prio = ilv - 1;
-        return launch256<true, 0, false, false, true, true>(p, stream);
-      }
+      if (impl3) return launch3<true, 0, true>(p, stream);
+      if (ilv) return launch256<true, 0, false, false, true, true>(p, stream);
       return launch256<true, 0, false, true, true>(p, stream);
     }
-    if (impl4 == 2) {      // interleaved K loop (reads and DMA issues between the MFMAs)
-      if (out_dtype == 0 && act == 0) return launch4w<true, 0, false, true>(p, stream);
-      if (out_dtype == 0 && (act == 1 || act == 3)) return launch4w<true, 1, false, true>(p, stream);
-      if (out_dtype == 1 && act == 0) return launch4w<false, 0, false, true>(p, stream);
-    }
-    if (impl4) {
-      if (out_dtype == 0 && act == 0) return launch4w<true, 0>(p, stream);
-      if (out_dtype == 0 && (act == 1 || act == 3)) return launch4w<true, 1>(p, stream);
-      if (out_dtype == 1 && act == 0) return launch4w<false, 0>(p, stream);
-    }
-    if (impl3 && (p.K % 32) == 0) {
-      if (out_dtype == 0 && act == 0) return launch3<true, 0>(p, stream);
-      if (out_dtype == 0 && (act == 1 || act == 3)) return launch3<true, 1>(p, stream);
-      if (out_dtype == 1 && act == 0) return launch3<false, 0>(p, stream);
-    }
 #ifdef PI3_DEV_ABLATIONS
-    const bool noepi = (abl & 1) != 0;
+    const bool noepi = (p.abl & 1) != 0;
 #else
     const bool noepi = false;
 #endif
+    const int dact = act == 3 ? 1 : act;
+    auto family = [&](auto launch) { return gemm_dispatch(G256DevPairs{}, out_dtype, dact, launch); };
+    int rc = 1;
+    if (impl4 == 2) rc = family([&](auto oa) { return launch4w<oa.OUT16, oa.ACT, false, true>(p, stream); });
+    if (rc == 1 && impl4) rc = family([&](auto oa) { return launch4w<oa.OUT16, oa.ACT>(p, stream); });
+    if (rc == 1 && impl3) rc = family([&](auto oa) { return launch3<oa.OUT16, oa.ACT>(p, stream); });
+    if (rc != 1) return rc;
     if (ilv) {
-      const_cast<GemmParams&>(p).ilv_prio = ilv - 1;
       if (noepi) return launch256<true, 0, true, false, false, true>(p, stream);
-      if (out_dtype == 0 && act == 0) return launch256<true, 0, false, false, false, true>(p, stream);
-      if (out_dtype == 0 && (act == 1 || act == 3)) return launch256<true, 1, false, false, false, true>(p, stream);
-      if (out_dtype == 1 && act == 0) return launch256<false, 0, false, false, false, true>(p, stream);
+      rc = family([&](auto oa) { return launch256<oa.OUT16, oa.ACT, false, false, false, true>(p, stream); });
+      if (rc != 1) return rc;
     }
-    if (!p.qk_mode && (int)PI3_KNOB("gemm_mfma32", 0)) {      // 32x32x16 K loop (prototype: see gemm256_kernel)
+    if ((int)PI3_KNOB("gemm_mfma32", 0)) {
       if (noepi) return launch256<true, 0, true, true, false, false, true>(p, stream);
-      if (out_dtype == 0 && act == 0) return launch256<true, 0, false, true, false, false, true>(p, stream);
-      if (out_dtype == 0 && (act == 1 || act == 3)) return launch256<true, 1, false, true, false, false, true>(p, stream);
-      if (out_dtype == 1 && act == 0) return launch256<false, 0, false, true, false, false, true>(p, stream);
+      rc = family([&](auto oa) { return launch256<oa.OUT16, oa.ACT, false, true, false, false, true>(p, stream); });
+      if (rc != 1) return rc;
     }
     const int stag = PI3_DEV_ENV_INT("PI3_GEMM_STAG", 1);
     if (noepi) return stag ? launch256<true, 0, true, true>(p, stream) : launch256<true, 0, true>(p, stream);
     if (!stag) {
-      if (out_dtype == 0 && act == 0) return launch256<true, 0>(p, stream);
-      if (out_dtype == 0 && (act == 1 || act == 3)) return launch256<true, 1>(p, stream);
-      if (out_dtype == 1 && act == 0) return launch256<false, 0>(p, stream);
+      rc = family([&](auto oa) { return launch256<oa.OUT16, oa.ACT>(p, stream); });
+      if (rc != 1) return rc;
     }
   }
 #endif
   // the shipped kernel: eight waves, waves 4-7 one barrier behind waves 0-3 (STAG)
   if (p.qk_mode) return launch256<true, 0, false, true, true>(p, stream);
-  if (out_dtype == 0 && act == 0) return launch256<true, 0, false, true>(p, stream);
-  if (out_dtype == 0 && act == 1) return launch256<true, 1, false, true>(p, stream);
-  if (out_dtype == 0 && act == 3) return launch256<true, 3, false, true>(p, stream);
-  if (out_dtype == 1 && act == 0) return launch256<false, 0, false, true>(p, stream);
-  return 1;
+  return gemm_dispatch(G256Pairs{}, out_dtype, act,
+                       [&](auto oa) { return launch256<oa.OUT16, oa.ACT, false, true>(p, stream); });
 }

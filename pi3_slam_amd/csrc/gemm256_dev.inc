@@ -1,5 +1,6 @@
 // Development-only GEMM kernels: included by gemm256.hip under PI3_DEV_VARIANTS, right after launch256 (same
-// translation unit; they use its g4_glds16, g2_epilogue_lds and G2_* constants).  Never part of the product library.
+// translation unit; they use its g4_glds16, g2_epilogue_lds, g2_persistent_grid and G2_* constants, and launch through
+// gemm_launch of gemm_common.h).  pi3_gemm256_try picks them by knob.  Never part of the product library.
 // ---------------------------------------------------------------------------------------------------------------
 // Two-workgroups-per-CU form (PI3_GEMM_IMPL=3 / per-shape choice): 128 (m) x 256 (n) tile, 256 threads = 4 waves, each
 // wave the same 128 x 64 output block (and therefore the same epilogues) as in gemm256_kernel, BK = 32, a 3-stage
@@ -124,11 +125,7 @@ __global__ __launch_bounds__(256, 2) void gemm3_kernel(GemmParams p) {
 template <bool OUT_BF16, int ACT, bool QK = false>
 static int launch3(const GemmParams& p, hipStream_t stream) {
   const int nbm = (p.M + G3_BM - 1) / G3_BM, nbn = p.N / G3_BN;
-  auto kern = gemm3_kernel<OUT_BF16, ACT, QK>;
-  static unsigned long long optin = 0;
-  if (int rc = pi3_lds_optin((const void*)kern, G3_LDS, &optin, "gemm3")) return rc;
-  hipLaunchKernelGGL(kern, dim3(nbm * nbn), dim3(256), G3_LDS, stream, p);
-  return pi3_check_launch("gemm3");
+  return gemm_launch<gemm3_kernel<OUT_BF16, ACT, QK>>("gemm3", nbm * nbn, 256, G3_LDS, p, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -371,20 +368,7 @@ __global__ __launch_bounds__(256) void gemm4w_kernel(GemmParams p) {
 
 template <bool OUT_BF16, int ACT, bool QK = false, bool ILV = false>
 static int launch4w(const GemmParams& p, hipStream_t stream) {
-  const int nbm = (p.M + G2_BM - 1) / G2_BM, nbn = p.N / G2_BN;
-  auto kern = gemm4w_kernel<OUT_BF16, ACT, QK, ILV>;
-  static unsigned long long optin = 0;
-  constexpr int LDS_BYTES = QK ? G2_LDS_QK : G2_LDS_TOTAL;
-  if (int rc = pi3_lds_optin((const void*)kern, LDS_BYTES, &optin, "gemm4w")) return rc;
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-      ncu = prop.multiProcessorCount & ~7;
-    if (ncu <= 0) ncu = 256;
-  }
-  const int nwg = nbm * nbn;
-  hipLaunchKernelGGL(kern, dim3(nwg > ncu ? ncu : nwg), dim3(256), LDS_BYTES, stream, p);
-  return pi3_check_launch("gemm4w");
+  const int nwg = ((p.M + G2_BM - 1) / G2_BM) * (p.N / G2_BN);
+  return gemm_launch<gemm4w_kernel<OUT_BF16, ACT, QK, ILV>>("gemm4w", g2_persistent_grid(nwg), 256,
+                                                            QK ? G2_LDS_QK : G2_LDS_TOTAL, p, stream);
 }

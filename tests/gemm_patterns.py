@@ -591,8 +591,9 @@ def expected_kernel(M, N, K, in_dtype, out_dtype, act, *, resid=False, addtab=Fa
 
 
 # every (kernel, 16-bit operands, 16-bit output, act) template instance the three entry points dispatch to in the product
-# build: the GEMM_CASE list, launch_narrow from pi3_gemm, both families from pi3_conv3x3 ("conv" appended), and the five
-# launch256 instances at the end of pi3_gemm256_try (act 3 = GELU under the knob gelu_form = 1; "qk" = the fused epilogue)
+# build: the pair lists of csrc/gemm.hip (Linear16Pairs and LinearF32Pairs for launch_gemm, Linear16Pairs for launch_narrow
+# from pi3_gemm, ConvPairs for both families from pi3_conv3x3, "conv" appended) and the five launch256 instances at the end
+# of pi3_gemm256_try (G256Pairs; act 3 = GELU under the knob gelu_form = 1; "qk" = the fused epilogue)
 INSTANCES = (
     ("tn128", True, True, 0), ("tn128", True, True, 1), ("tn128", True, False, 0), ("tn128", True, False, 2),
     ("tn128", False, False, 0), ("tn128", False, False, 2), ("tn128", False, True, 0),

@@ -610,6 +610,34 @@ int pi3_grid_frontier_stats(const unsigned char* state, const unsigned* label, c
                             int nz, const long* roots_sorted, long K, long* stats, unsigned long long* counters,
                             void* stream);
 
+/* ---- views of the occupancy grid (csrc/grid_view.hip): the same grid layout and limits; integers only.  Cell m lies
+ * between cells v and u when the open segment between their centres meets m's open interior (v and u never count; a
+ * cell the segment only touches at a face, edge or corner does not either): the integer DDA from v along o = u - v with
+ * the k-th crossing of axis a at t = (2k - 1) / (2 |o_a|), always the smallest t, all axes tied at that t stepping at
+ * once.  u is visible from v when no cell between them is occupied (state == 2); unknown and free cells are
+ * transparent.  A target of candidate v at range R is a cell u != v inside the grid with |u - v|^2 <= R^2 and
+ * state[u] == 0.  Offset o lies in the cone of heading a when o.a > 0 and (o.a)^2 den >= num |o|^2 |a|^2 (64 bits;
+ * num / den = cos^2 of half the field of view; the boundary is inside).
+ * pi3_grid_view_candidates: the cells of dist uint32 [cells] (pi3_grid_route_sweep's settled field) with dist !=
+ *   0xFFFFFFFF, dist <= max_cost (>= 0) and the ABSOLUTE index (ox + x, oy + y, oz + z) a multiple of stride (>= 1) on
+ *   every axis (floor modulo: the origin may be negative), compacted in any order into cells int64 [cap]; *count (DEVICE
+ *   int64, zeroed by the call) = their number even when it exceeds cap: the first cap slots claimed are then written and
+ *   the caller must check.  cap >= 0; cells may be NULL at cap == 0.
+ * pi3_grid_view_gain: candidates int64 [V] are linear indices, on cells of any state.  headings: HOST int [H][3], 1 <= H
+ *   <= 32, every axis non-zero with components within +-1024 (read during the call and passed to the kernel by value).
+ *   range in 1..32 cells; 0 <= num <= den, 0 < den < 2^31.  Per candidate: visible[v] = the visible targets, gain[v][h]
+ *   (uint32 [V][H]) = those in heading h's cone, best[v] = the smallest h of the largest gain.  A candidate outside
+ *   [0, cells) gets zeros and best = -1 and is not counted.  counters: DEVICE uint64 [4] = candidates inside the grid,
+ *   targets (rays cast), rays blocked, rays visible; zeroed by the call.  0 <= V < 2^31; V == 0 zeroes the counters and
+ *   launches no kernel, the per-candidate arrays may then be NULL.  Integer sums only: the bytes do not depend on the
+ *   order.
+ * Bad arguments launch nothing and leave the outputs untouched.  No allocation, no synchronisation. */
+int pi3_grid_view_candidates(const unsigned* dist, int nx, int ny, int nz, int ox, int oy, int oz, int stride,
+                             long max_cost, long* cells, long cap, long* count, void* stream);
+int pi3_grid_view_gain(const unsigned char* state, int nx, int ny, int nz, const long* candidates, long V, int range,
+                       const int* headings, int H, long cos2_num, long cos2_den, unsigned* gain, unsigned* visible,
+                       int* best, unsigned long long* counters, void* stream);
+
 /* ---- nearest neighbours between two point clouds (csrc/cloud_nn.hip): an exact radius-bounded search through a
  * uniform grid of cells, for scoring a map against a reference cloud (map_eval.py).  The grid is a hash table of cells
  * in the voxel table's form: `capacity` slots of 64 B (a power of two, at least 2 n: ops.voxel_capacity), keyed by the

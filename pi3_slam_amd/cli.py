@@ -12,6 +12,8 @@
          [--goal X Y Z] [--radius 0.2]
   python -m pi3_slam_amd.cli frontiers --occupancy OUT/occupancy.npz --output DIR --from-trajectory OUT/trajectory_tum.txt \\
          [--radius 0.2] [--min-cells 20] [--route-to 0]
+  python -m pi3_slam_amd.cli views --occupancy OUT/occupancy.npz --output DIR --from-trajectory OUT/trajectory_tum.txt \\
+         [--radius 0.2] [--range 1.0] [--fov 90] [--stride 4] [--count 10] [--route-to 0]
 
 Under `python -m torch.distributed.run --nproc-per-node G -m pi3_slam_amd.cli ...` every stage shards over the G GPUs.
 """
@@ -309,6 +311,34 @@ FRONTIER_FLAGS: Sequence[Tuple[str, Dict]] = (
 )
 
 
+# views: this build's own sub-command (view_planner.py) on the same file
+VIEW_FLAGS: Sequence[Tuple[str, Dict]] = (
+    ("--occupancy", dict(REQ, help="occupancy.npz of `reconstruct` or `online` (--occupancy-cell)")),
+    ("--output", dict(REQ, help="directory for views.json, views.npz and views.ply and, with --route-to, route.json, "
+                                "route.ply and route.npz")),
+    ("--start", dict(type=float, nargs=3, default=None, metavar=("X", "Y", "Z"), help="the source: one world point")),
+    ("--from-trajectory", dict(default=None, help="the sources: the position of every pose of this TUM trajectory "
+                                                  "(poses on cells that are not traversable are skipped and counted)")),
+    ("--radius", dict(type=float, default=0.0, help="the body's radius in metres for the route, kept from occupied "
+                                                    "cells only (default 0: every free cell)")),
+    ("--range", dict(type=float, default=1.0, help="how far a view sees, in metres; at most 32 occupancy cells "
+                                                   "(default 1.0: a starting point, not a measured optimum)")),
+    ("--fov", dict(type=float, default=90.0, help="the full opening angle of the viewing cone in degrees, in (0, 180] "
+                                                  "(default 90: a starting point, not a measured optimum)")),
+    ("--stride", dict(type=int, default=4, help="every stride-th reachable cell per axis is a candidate pose (default "
+                                                "4: a starting point, not a measured optimum)")),
+    ("--count", dict(type=int, default=10, help="the views to keep at most (default 10)")),
+    ("--separation", dict(type=float, default=None, help="no two kept views are nearer than this, in metres (default: "
+                                                         "half of --range)")),
+    ("--max-distance", dict(type=float, default=None, help="leave out poses farther than this by route, in metres "
+                                                           "(default: none)")),
+    ("--min-gain", dict(type=int, default=1, help="drop poses whose best heading sees fewer unknown cells (default 1)")),
+    ("--route-to", dict(type=int, default=None, metavar="RANK", help="also the way to the view of this rank (0 = the "
+                                                                     "best), as `route` writes it")),
+    ("--device", dict(default="cuda")),
+)
+
+
 def list_images(root: str) -> List[str]:
     """Folder -> its png, jpg, jpeg, bmp files (each extension group sorted, groups in that order); file -> its
     non-empty lines; anything else is a glob pattern."""
@@ -327,7 +357,7 @@ def build_parser() -> argparse.ArgumentParser:
                                   ("online", tuple(ONLINE_FLAGS) + ONLINE_DENSE_FLAGS + ONLINE_FOLLOW_FLAGS,
                                    ONLINE_SWITCHES),
                                   ("evaluate-map", EVAL_FLAGS, EVAL_SWITCHES), ("route", ROUTE_FLAGS, ROUTE_SWITCHES),
-                                  ("frontiers", FRONTIER_FLAGS, ())):
+                                  ("frontiers", FRONTIER_FLAGS, ()), ("views", VIEW_FLAGS, ())):
         p = sub.add_parser(name)
         for flag, kw in flags:
             p.add_argument(flag, **kw)
@@ -581,10 +611,37 @@ def run_frontiers(a: argparse.Namespace) -> None:
     print(text)
 
 
+def run_views(a: argparse.Namespace) -> None:
+    from . import export
+    from .grid_route import read_tum_positions
+    from .view_planner import ViewPlanner
+    if (a.start is None) == (a.from_trajectory is None):
+        raise SystemExit("views: give --start X Y Z or --from-trajectory TRAJ.tum (one of them)")
+    try:
+        planner = ViewPlanner(a.radius, a.range, a.fov, a.stride, a.count, a.separation, a.max_distance, a.min_gain)
+        grid = export.read_occupancy(a.occupancy)
+        sources = [a.start] if a.start is not None else read_tum_positions(a.from_trajectory)
+        found = planner.find(grid, sources, a.device)
+        route = found.route_to(a.route_to) if a.route_to is not None else None
+    except (ValueError, OSError) as e:
+        raise SystemExit(f"views: {e}")
+    export.write_views(found, a.output)
+    if route is not None:
+        export.write_route(found.field, route, a.output)
+    c = found.counts
+    text = (f"views: {c['candidates']} candidates, {c['rays']} rays ({c['rays_visible']} visible), {c['views']} views "
+            f"kept ({c['low_gain']} candidates below the gain)")
+    if found.views:
+        best = found.views[0]
+        text += f"; the best: {best.gain} cells at {best.distance_m:.3f} m"
+    print(text)
+
+
 def main(argv=None) -> None:
     a = build_parser().parse_args(argv)
     {"create": run_create, "reconstruct": run_reconstruct, "online": run_online,
-     "evaluate-map": run_evaluate_map, "route": run_route, "frontiers": run_frontiers}[a.command](a)
+     "evaluate-map": run_evaluate_map, "route": run_route, "frontiers": run_frontiers,
+     "views": run_views}[a.command](a)
 
 
 if __name__ == "__main__":

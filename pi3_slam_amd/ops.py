@@ -1168,6 +1168,63 @@ def grid_frontier_stats(state: torch.Tensor, label: torch.Tensor, dist: Optional
     _L.check(rc, "pi3_grid_frontier_stats")
 
 
+# ---- views of the occupancy grid (csrc/grid_view.hip)
+VIEW_MAX_RANGE = 32                     # cells: the occupied bits of the (2 R + 1)^3 box live in LDS
+VIEW_MAX_HEADINGS = 32
+VIEW_MAX_AXIS = 1024                    # per component of a heading
+VIEW_COUNTERS = ("candidates", "rays", "rays_blocked", "rays_visible")
+VIEW_COS2_DEN = 1 << 20                 # cos^2 of half the field of view is passed as num / 2^20
+
+
+def grid_view_candidates(dist: torch.Tensor, index_origin, stride: int, max_cost: int, cells: torch.Tensor,
+                         count: torch.Tensor) -> None:
+    """The cells of dist int32 (nz,ny,nx) (a settled route field, the uint32 values) with a finite dist <= max_cost whose
+    absolute index index_origin + (x, y, z) is a multiple of stride on every axis, into cells int64 (cap,), in any
+    order; count int64 (1,) = their number, also when it exceeds cap (the caller checks)."""
+    lib = _L.load()
+    nx, ny, nz = _grid_field(dist)
+    dev = dist.device
+    assert cells.dtype == torch.int64 and cells.is_contiguous() and cells.ndim == 1 and cells.device == dev
+    assert count.dtype == torch.int64 and count.numel() == 1 and count.device == dev
+    ox, oy, oz = (int(v) for v in index_origin)
+    cap = int(cells.numel())
+    rc = lib.pi3_grid_view_candidates(dist.data_ptr(), nx, ny, nz, ox, oy, oz, int(stride), int(max_cost),
+                                      cells.data_ptr() if cap else None, cap, count.data_ptr(), _L.stream_ptr())
+    _L.check(rc, "pi3_grid_view_candidates")
+
+
+def grid_view_gain(state: torch.Tensor, candidates: torch.Tensor, view_range: int, headings, cos2_num: int,
+                   cos2_den: int, gain: torch.Tensor, visible: torch.Tensor, best: torch.Tensor,
+                   counters: torch.Tensor) -> None:
+    """Per entry of candidates int64 (V,) (linear indices into state uint8 (nz,ny,nx)): visible int32 (V,) (the uint32
+    values) = the unknown cells within view_range cells that no occupied cell hides, gain int32 (V,H) = those in the
+    cone of each of the H integer axes `headings` (H,3) (x, y, z) at cos^2 of the half angle cos2_num / cos2_den, best
+    int32 (V,) = the smallest heading of the largest gain (-1 and zeros for a candidate outside the grid).  counters
+    int64 (4,) = VIEW_COUNTERS (zeroed by the call)."""
+    lib = _L.load()
+    nx, ny, nz = _grid_state(state)
+    dev = state.device
+    assert 0 < state.numel() <= ROUTE_MAX_CELLS, f"{state.numel()} cells: 1 .. 2^27"
+    assert candidates.dtype == torch.int64 and candidates.is_contiguous() and candidates.ndim == 1
+    assert candidates.device == dev
+    V = int(candidates.numel())
+    hd = [tuple(int(c) for c in a) for a in headings]
+    H = len(hd)
+    assert 1 <= H <= VIEW_MAX_HEADINGS, f"{H} headings: 1 .. {VIEW_MAX_HEADINGS}"
+    assert all(len(a) == 3 and any(a) and max(abs(c) for c in a) <= VIEW_MAX_AXIS for a in hd), \
+        f"a heading is no non-zero integer axis (x, y, z) within +-{VIEW_MAX_AXIS}"
+    assert gain.dtype == torch.int32 and gain.is_contiguous() and tuple(gain.shape) == (V, H) and gain.device == dev
+    for t in (visible, best):
+        assert t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == (V,) and t.device == dev
+    assert counters.dtype == torch.int64 and counters.is_contiguous() and counters.numel() >= 4 and counters.device == dev
+    flat = (C.c_int * (3 * H))(*[c for a in hd for c in a])
+    rc = lib.pi3_grid_view_gain(state.data_ptr(), nx, ny, nz, candidates.data_ptr() if V else None, V, int(view_range),
+                                flat, H, int(cos2_num), int(cos2_den), gain.data_ptr() if V else None,
+                                visible.data_ptr() if V else None, best.data_ptr() if V else None,
+                                counters.data_ptr(), _L.stream_ptr())
+    _L.check(rc, "pi3_grid_view_gain")
+
+
 # ---- nearest neighbours between two clouds (csrc/cloud_nn.hip)
 CLOUD_INDEX_COUNTERS = ("dropped", "cells", "no_slot", "largest_cell")
 CLOUD_NEAREST_COUNTERS = ("dropped", "matched", "beyond", "evaluations")

@@ -637,6 +637,29 @@ int pi3_grid_view_candidates(const unsigned* dist, int nx, int ny, int nz, int o
 int pi3_grid_view_gain(const unsigned char* state, int nx, int ny, int nz, const long* candidates, long V, int range,
                        const int* headings, int H, long cos2_num, long cos2_den, unsigned* gain, unsigned* visible,
                        int* best, unsigned long long* counters, void* stream);
+/* Views that cover: a mask of the cells that kept views already see.  seen: DEVICE uint32
+ * [(cells + 31) >> 5], cell c (the linear index) is bit c & 31 of word c >> 5; bits at positions >= cells are never set.
+ * pi3_grid_view_gain_unseen: pi3_grid_view_gain with one more condition on a target: its bit of seen is clear.  Every
+ *   output and counter keeps its meaning, counted over those targets; with an all-zero mask the bytes are
+ *   pi3_grid_view_gain's.  seen is read only and must not be NULL.
+ * pi3_grid_view_mark: row i is the view (cells[i], heading_of[i]): cells DEVICE int64 [V], heading_of HOST int [V] with
+ *   every entry in -1 .. H - 1 (read and checked during the call and passed to the kernel by value: one launch when all
+ *   rows share a heading, else 1024 rows per launch).
+ *   A ray is cast to every target of the cell (the mask is ignored here); the bit of every target that is visible and in
+ *   heading_of[i]'s cone (-1: in the cone of at least one of the H headings) is set, by an atomic OR that is issued only
+ *   when the bit read clear.  owner: DEVICE int16 [cells] or NULL; the lane that turned a bit from 0 to 1 writes
+ *   owner[u] = tag, 0 <= tag < 32768; with an owner V must be 1 (rows racing for a cell would not be reproducible).
+ *   counters: DEVICE uint64 [5] = views (rows inside the grid), rays cast, rays visible, visible and in the cone, new
+ *   bits; zeroed by the call.  A cell outside [0, cells) marks nothing and is no view.  V == 0 zeroes the counters and
+ *   launches no kernel; cells and heading_of may then be NULL.  range, headings, H, num, den as pi3_grid_view_gain.
+ * Bad arguments launch nothing and leave the outputs untouched.  No allocation, no synchronisation. */
+int pi3_grid_view_gain_unseen(const unsigned char* state, int nx, int ny, int nz, const unsigned* seen,
+                              const long* candidates, long V, int range, const int* headings, int H, long cos2_num,
+                              long cos2_den, unsigned* gain, unsigned* visible, int* best, unsigned long long* counters,
+                              void* stream);
+int pi3_grid_view_mark(const unsigned char* state, int nx, int ny, int nz, unsigned* seen, const long* cells,
+                       const int* heading_of, long V, int range, const int* headings, int H, long cos2_num,
+                       long cos2_den, short* owner, int tag, unsigned long long* counters, void* stream);
 
 /* ---- nearest neighbours between two point clouds (csrc/cloud_nn.hip): an exact radius-bounded search through a
  * uniform grid of cells, for scoring a map against a reference cloud (map_eval.py).  The grid is a hash table of cells

@@ -13,7 +13,8 @@
   python -m pi3_slam_amd.cli frontiers --occupancy OUT/occupancy.npz --output DIR --from-trajectory OUT/trajectory_tum.txt \\
          [--radius 0.2] [--min-cells 20] [--route-to 0]
   python -m pi3_slam_amd.cli views --occupancy OUT/occupancy.npz --output DIR --from-trajectory OUT/trajectory_tum.txt \\
-         [--radius 0.2] [--range 1.0] [--fov 90] [--stride 4] [--count 10] [--route-to 0]
+         [--radius 0.2] [--range 1.0] [--fov 90] [--stride 4] [--count 10] [--route-to 0] \\
+         [--cover [--cover-until 0.9]]
 
 Under `python -m torch.distributed.run --nproc-per-node G -m pi3_slam_amd.cli ...` every stage shards over the G GPUs.
 """
@@ -335,7 +336,14 @@ VIEW_FLAGS: Sequence[Tuple[str, Dict]] = (
     ("--min-gain", dict(type=int, default=1, help="drop poses whose best heading sees fewer unknown cells (default 1)")),
     ("--route-to", dict(type=int, default=None, metavar="RANK", help="also the way to the view of this rank (0 = the "
                                                                      "best), as `route` writes it")),
+    ("--cover-until", dict(type=float, default=None, metavar="FRACTION",
+                           help="with --cover: stop once this fraction, in (0, 1], of the unknown cells that any pose "
+                                "can see is covered (default: none, --count and --min-gain end the plan)")),
     ("--device", dict(default="cuda")),
+)
+VIEW_SWITCHES: Sequence[Tuple[str, str]] = (
+    ("--cover", "pick the views one after the other, each by the unknown cells the kept ones do not see yet, so that "
+                "the plan adds up; a cell may be kept with several headings, and --separation is refused"),
 )
 
 
@@ -357,7 +365,7 @@ def build_parser() -> argparse.ArgumentParser:
                                   ("online", tuple(ONLINE_FLAGS) + ONLINE_DENSE_FLAGS + ONLINE_FOLLOW_FLAGS,
                                    ONLINE_SWITCHES),
                                   ("evaluate-map", EVAL_FLAGS, EVAL_SWITCHES), ("route", ROUTE_FLAGS, ROUTE_SWITCHES),
-                                  ("frontiers", FRONTIER_FLAGS, ()), ("views", VIEW_FLAGS, ())):
+                                  ("frontiers", FRONTIER_FLAGS, ()), ("views", VIEW_FLAGS, VIEW_SWITCHES)):
         p = sub.add_parser(name)
         for flag, kw in flags:
             p.add_argument(flag, **kw)
@@ -617,11 +625,18 @@ def run_views(a: argparse.Namespace) -> None:
     from .view_planner import ViewPlanner
     if (a.start is None) == (a.from_trajectory is None):
         raise SystemExit("views: give --start X Y Z or --from-trajectory TRAJ.tum (one of them)")
+    if a.cover and a.separation is not None:
+        raise SystemExit("views: --separation has no meaning with --cover (a cover keeps views by what they add)")
+    if a.cover_until is not None and not a.cover:
+        raise SystemExit("views: --cover-until needs --cover")
     try:
         planner = ViewPlanner(a.radius, a.range, a.fov, a.stride, a.count, a.separation, a.max_distance, a.min_gain)
         grid = export.read_occupancy(a.occupancy)
         sources = [a.start] if a.start is not None else read_tum_positions(a.from_trajectory)
-        found = planner.find(grid, sources, a.device)
+        if a.cover:
+            found = planner.cover(grid, sources, a.device, a.cover_until)
+        else:
+            found = planner.find(grid, sources, a.device)
         route = found.route_to(a.route_to) if a.route_to is not None else None
     except (ValueError, OSError) as e:
         raise SystemExit(f"views: {e}")
@@ -634,6 +649,9 @@ def run_views(a: argparse.Namespace) -> None:
     if found.views:
         best = found.views[0]
         text += f"; the best: {best.gain} cells at {best.distance_m:.3f} m"
+    if found.mode == "cover":
+        text += (f"; covered {c['covered']} of {c['seeable']} seeable unknown cells "
+                 f"({100.0 * c['covered'] / max(c['seeable'], 1):.1f} %)")
     print(text)
 
 

@@ -29,8 +29,17 @@
 //                             have ended, every heading is a ballot over the lanes whose ray arrived, and one lane
 //                             adds the count to the heading's LDS word.  Integer sums only: the bytes do not depend on
 //                             the order.
+//
+// Views that cover (tests/grid_cover_ref.py): seen is a bit per cell, cell c at bit c & 31 of word c >> 5, for "a kept
+// view sees it".
+//   pi3_grid_view_gain_unseen the same kernel, instantiated with one more condition in (2): the cell's bit of seen is
+//                             clear.  Lanes along x read the same word: one broadcast load next to the state byte.
+//   pi3_grid_view_mark        a workgroup per row (cell, heading): (1) and (2) with every unknown cell of the ball a
+//                             target, then a lane whose ray arrived inside the heading's cone (-1: any heading's) ORs
+//                             its cell's bit into seen.  The pieces the two kernels share are in grid_view_ray.h.
 #include "common.h"
 #include "grid_tile.h"
+#include "grid_view_ray.h"
 #include "voxel_table.h"
 #include "wave_block.h"
 
@@ -39,20 +48,22 @@
 namespace {
 
 using grid_tile::grid_ok;
+using grid_view_ray::Box;
+using grid_view_ray::Headings;
+using grid_view_ray::kMaxAxis;
+using grid_view_ray::kMaxHeadings;
+using grid_view_ray::kMaxRange;
+using grid_view_ray::kQueue;
 using voxel_table::u64;
 using wave_block::block_exclusive_scan;
 
 constexpr unsigned kFar = 0xFFFFFFFFu;
-constexpr int kMaxRange = 32;
-constexpr int kMaxHeadings = 32;
-constexpr int kMaxAxis = 1024;          // per component of a heading
-constexpr int kNever = 1 << 30;         // the key of an axis the ray does not move along
 constexpr int kTally = kMaxHeadings + 3;                 // LDS words: a gain per heading, visible, targets, blocked
-constexpr int kQueue = 128;             // LDS words per wave: fewer than 64 targets waiting + the 64 of one pass
+constexpr int kMarkTally = 4;                            // LDS words: rays, rays visible, in the cone, new
+constexpr int kMarkRows = 1024;                          // rows of one pi3_grid_view_mark launch
 
-struct Headings {
-  int axis[kMaxHeadings][3];
-  long long norm[kMaxHeadings];         // num |a|^2
+struct MarkRows {
+  signed char heading[kMarkRows];                        // -1: any of the H headings
 };
 
 __device__ __forceinline__ int floor_mod(long v, int m) {
@@ -85,24 +96,10 @@ __global__ __launch_bounds__(256) void view_candidates_kernel(const unsigned* __
   }
 }
 
-// this thread's box cell moves on by 256 cells: (bx, by, bz) += (dx, dy, dz) with carries, 256 = (dz W + dy) W + dx
-__device__ __forceinline__ void box_advance(int& bx, int& by, int& bz, int dx, int dy, int dz, int W) {
-  bx += dx;
-  if (bx >= W) bx -= W, ++by;
-  by += dy;
-  if (by >= W) by -= W, ++bz;
-  bz += dz;
-}
-
-// orders this wave's LDS stores and loads around a hand-over between its lanes (LDS operations of one wave run in
-// order; this keeps the compiler from moving them)
-__device__ __forceinline__ void wave_lds_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
+// kUnseen: a cell is a target only when its bit of `seen` is clear (pi3_grid_view_gain_unseen); `seen` is not read otherwise
+template <bool kUnseen>
 __global__ __launch_bounds__(256) void view_gain_kernel(const unsigned char* __restrict__ state, int nx, int ny, int nz,
+                                                        const unsigned* __restrict__ seen,
                                                         const long* __restrict__ candidates, int R, int H,
                                                         const Headings hd, long long den, unsigned* __restrict__ gain,
                                                         unsigned* __restrict__ visible, int* __restrict__ best,
@@ -121,26 +118,11 @@ __global__ __launch_bounds__(256) void view_gain_kernel(const unsigned char* __r
   }
   const int line = (int)v / nx;
   const int vx = (int)v - line * nx, vy = line % ny, vz = line / ny;
-  const int W = 2 * R + 1, W2 = W * W, box = W2 * W;          // <= 65^3
-  const int dx = 256 % W, dy = (256 / W) % W, dz = 256 / W2;
-  const int passes = (box + 255) >> 8;
+  const Box box(R);
   if (t < kTally) tally[t] = 0u;
 
   // (1) the occupied bits
-  int bx = t % W, by = (t / W) % W, bz = t / W2;
-  for (int p = 0; p < passes; ++p) {
-    const int gx = vx - R + bx, gy = vy - R + by, gz = vz - R + bz;
-    bool occ = false;
-    if (bz < W && gx >= 0 && gx < nx && gy >= 0 && gy < ny && gz >= 0 && gz < nz)
-      occ = state[((long)gz * ny + gy) * nx + gx] == 2;
-    const u64 b = __ballot(occ);
-    if (lane == 0) {
-      const int w = ((p << 8) + t) >> 5;                      // the wave's 64 cells are two whole words
-      bits[w] = (unsigned)b;
-      bits[w + 1] = (unsigned)(b >> 32);
-    }
-    box_advance(bx, by, bz, dx, dy, dz, W);
-  }
+  grid_view_ray::stage_occupied(box, state, nx, ny, nz, vx, vy, vz, t, bits);
   __syncthreads();
 
   // (2) the same walk finds the targets; a wave queues them (box offsets + R, 7 bits each) and walks 64 at a time,
@@ -148,64 +130,41 @@ __global__ __launch_bounds__(256) void view_gain_kernel(const unsigned char* __r
   const int R2 = R * R;
   unsigned* mine = queue + (t >> 6) * kQueue;                 // this wave's queue; the wave alone reads and writes it
   int queued = 0;                                             // the same in every lane of the wave; < 64 between passes
-  bx = t % W, by = (t / W) % W, bz = t / W2;
-  for (int p = 0; p <= passes; ++p) {
-    if (p < passes) {
+  int bx, by, bz;
+  box.first(t, bx, by, bz);
+  for (int p = 0; p <= box.passes; ++p) {
+    if (p < box.passes) {
       const int ox = bx - R, oy = by - R, oz = bz - R;
       const int gx = vx + ox, gy = vy + oy, gz = vz + oz;
       const int o2 = ox * ox + oy * oy + oz * oz;
       bool cast = false;
-      if (bz < W && o2 != 0 && o2 <= R2 && gx >= 0 && gx < nx && gy >= 0 && gy < ny && gz >= 0 && gz < nz)
-        cast = state[((long)gz * ny + gy) * nx + gx] == 0;
-      const u64 cast_b = __ballot(cast);
-      if (cast) mine[queued + __popcll(cast_b & ((1ull << lane) - 1ull))] = (unsigned)(bx | (by << 7) | (bz << 14));
-      queued += __popcll(cast_b);
-      box_advance(bx, by, bz, dx, dy, dz, W);
-    }
-    if (queued < 64 && !(p == passes && queued > 0)) continue;
-    const int take = min(queued, 64);
-    queued -= take;
-    wave_lds_fence();                                         // the lanes' stores above, before other lanes read them
-    const bool cast = lane < take;
-    const unsigned e = cast ? mine[queued + lane] : 0u;
-    wave_lds_fence();                                         // and these reads before the next pass stores there
-    const int ox = (int)(e & 127u) - R, oy = (int)((e >> 7) & 127u) - R, oz = (int)(e >> 14) - R;
-    bool seen = false;
-    if (cast) {
-      const int ax = abs(ox), ay = abs(oy), az = abs(oz);
-      const int mx = max(ax, 1), my = max(ay, 1), mz = max(az, 1);
-      const int px = 2 * my * mz, py = 2 * mx * mz, pz = 2 * mx * my;       // a key grows by 2 P per crossing
-      int kx = ax ? (px >> 1) : kNever, ky = ay ? (py >> 1) : kNever, kz = az ? (pz >> 1) : kNever;
-      const int sx = ox > 0 ? 1 : -1, sy = oy > 0 ? W : -W, sz = oz > 0 ? W2 : -W2;
-      int at = (R * W + R) * W + R;                           // the candidate's own box cell
-      int left = ax + ay + az;                                // crossings to go; 0 at u
-      for (;;) {
-        const int m = min(kx, min(ky, kz));
-        if (kx == m) at += sx, kx += px, --left;
-        if (ky == m) at += sy, ky += py, --left;
-        if (kz == m) at += sz, kz += pz, --left;
-        if (left == 0) {
-          seen = true;
-          break;
-        }
-        if ((bits[at >> 5] >> (at & 31)) & 1u) break;         // an occupied cell between v and u
+      if (bz < box.W && o2 != 0 && o2 <= R2 && gx >= 0 && gx < nx && gy >= 0 && gy < ny && gz >= 0 && gz < nz) {
+        const long u = ((long)gz * ny + gy) * nx + gx;
+        cast = state[u] == 0;
+        if (kUnseen) cast = cast && !((seen[u >> 5] >> (u & 31)) & 1u);     // lanes along x read the same word
       }
+      grid_view_ray::queue_push(mine, queued, cast, lane, bx, by, bz);
+      box.next(bx, by, bz);
     }
-    const u64 seen_b = __ballot(seen);
-    if (seen_b) {                                             // the same in every lane of the wave
+    if (queued < 64 && !(p == box.passes && queued > 0)) continue;
+    int ox, oy, oz;
+    bool holds;
+    const int take = grid_view_ray::queue_take(mine, queued, lane, R, holds, ox, oy, oz);
+    bool arrived = false;
+    if (holds) arrived = grid_view_ray::ray_arrives(bits, R, box.W, box.W2, ox, oy, oz);
+    const u64 arrived_b = __ballot(arrived);
+    if (arrived_b) {                                          // the same in every lane of the wave
       const long long o2l = ox * ox + oy * oy + oz * oz;
       for (int h = 0; h < H; ++h) {
-        const long long dot = (long long)ox * hd.axis[h][0] + (long long)oy * hd.axis[h][1] + (long long)oz * hd.axis[h][2];
-        const bool in = seen && dot > 0 && dot * dot * den >= hd.norm[h] * o2l;
-        const u64 b = __ballot(in);
+        const u64 b = __ballot(grid_view_ray::in_cone(hd, h, den, ox, oy, oz, o2l) && arrived);
         if (lane == 0 && b) atomicAdd(&tally[h], (unsigned)__popcll(b));
       }
     }
     if (lane == 0) {
-      const unsigned arrived = (unsigned)__popcll(seen_b);
-      atomicAdd(&tally[kMaxHeadings], arrived);
+      const unsigned n = (unsigned)__popcll(arrived_b);
+      atomicAdd(&tally[kMaxHeadings], n);
       atomicAdd(&tally[kMaxHeadings + 1], (unsigned)take);
-      atomicAdd(&tally[kMaxHeadings + 2], (unsigned)take - arrived);
+      atomicAdd(&tally[kMaxHeadings + 2], (unsigned)take - n);
     }
   }
   __syncthreads();
@@ -221,6 +180,136 @@ __global__ __launch_bounds__(256) void view_gain_kernel(const unsigned char* __r
     if (tally[kMaxHeadings + 2]) atomicAdd(counters + 2, (u64)tally[kMaxHeadings + 2]);
     if (tally[kMaxHeadings]) atomicAdd(counters + 3, (u64)tally[kMaxHeadings]);
   }
+}
+
+// A workgroup per row (cells[i], rows.heading[same ? 0 : i]): the gain kernel's box, queue and DDA with every unknown cell of the
+// ball a target (the mask does not thin the rays).  A lane whose ray arrived inside the row's cone reads the cell's
+// word of `seen` and, only when the bit is clear, ORs it in; the bit is new when the returned word had it clear, so of
+// several rows that race for one cell exactly one counts it.  owner is written by that lane alone.
+__global__ __launch_bounds__(256) void view_mark_kernel(const unsigned char* __restrict__ state, int nx, int ny, int nz,
+                                                        unsigned* seen, const long* __restrict__ cells_in,
+                                                        const MarkRows rows, int same, int R, int H, const Headings hd,
+                                                        long long den, short* owner, int tag,
+                                                        u64* __restrict__ counters) {
+  extern __shared__ unsigned lds[];                           // kMarkTally words, a queue per wave, the occupied bits
+  unsigned* tally = lds;
+  unsigned* queue = lds + kMarkTally;
+  unsigned* bits = queue + 4 * kQueue;
+  const int t = (int)threadIdx.x, lane = t & 63;
+  const long v = cells_in[blockIdx.x];
+  const long cells = (long)nx * ny * nz;
+  if (v < 0 || v >= cells) return;                            // the same in every thread: no view
+  const int heading = rows.heading[same ? 0 : blockIdx.x];
+  const int line = (int)v / nx;
+  const int vx = (int)v - line * nx, vy = line % ny, vz = line / ny;
+  const Box box(R);
+  if (t < kMarkTally) tally[t] = 0u;
+  grid_view_ray::stage_occupied(box, state, nx, ny, nz, vx, vy, vz, t, bits);
+  __syncthreads();
+
+  const int R2 = R * R;
+  unsigned* mine = queue + (t >> 6) * kQueue;
+  int queued = 0;
+  int bx, by, bz;
+  box.first(t, bx, by, bz);
+  for (int p = 0; p <= box.passes; ++p) {
+    if (p < box.passes) {
+      const int ox = bx - R, oy = by - R, oz = bz - R;
+      const int gx = vx + ox, gy = vy + oy, gz = vz + oz;
+      const int o2 = ox * ox + oy * oy + oz * oz;
+      bool cast = false;
+      if (bz < box.W && o2 != 0 && o2 <= R2 && gx >= 0 && gx < nx && gy >= 0 && gy < ny && gz >= 0 && gz < nz)
+        cast = state[((long)gz * ny + gy) * nx + gx] == 0;
+      grid_view_ray::queue_push(mine, queued, cast, lane, bx, by, bz);
+      box.next(bx, by, bz);
+    }
+    if (queued < 64 && !(p == box.passes && queued > 0)) continue;
+    int ox, oy, oz;
+    bool holds;
+    const int take = grid_view_ray::queue_take(mine, queued, lane, R, holds, ox, oy, oz);
+    bool arrived = false;
+    if (holds) arrived = grid_view_ray::ray_arrives(bits, R, box.W, box.W2, ox, oy, oz);
+    const u64 arrived_b = __ballot(arrived);
+    bool in = false, fresh = false;
+    if (arrived_b) {                                          // the same in every lane of the wave
+      const long long o2l = ox * ox + oy * oy + oz * oz;
+      if (heading >= 0) {
+        in = grid_view_ray::in_cone(hd, heading, den, ox, oy, oz, o2l) && arrived;
+      } else {
+        for (int h = 0; h < H; ++h) in = in || (grid_view_ray::in_cone(hd, h, den, ox, oy, oz, o2l) && arrived);
+      }
+      if (in) {                                               // a target: inside the grid, so u < cells
+        const long u = ((long)(vz + oz) * ny + (vy + oy)) * nx + (vx + ox);
+        const unsigned bit = 1u << (u & 31);
+        unsigned* word = seen + (u >> 5);
+        if (!(__atomic_load_n(word, __ATOMIC_RELAXED) & bit)) {
+          fresh = !(atomicOr(word, bit) & bit);
+          if (fresh && owner) owner[u] = (short)tag;
+        }
+      }
+    }
+    const u64 in_b = __ballot(in), fresh_b = __ballot(fresh);
+    if (lane == 0) {
+      atomicAdd(&tally[0], (unsigned)take);
+      if (arrived_b) atomicAdd(&tally[1], (unsigned)__popcll(arrived_b));
+      if (in_b) atomicAdd(&tally[2], (unsigned)__popcll(in_b));
+      if (fresh_b) atomicAdd(&tally[3], (unsigned)__popcll(fresh_b));
+    }
+  }
+  __syncthreads();
+  if (t == 0) {
+    atomicAdd(counters + 0, 1ull);
+    for (int i = 0; i < kMarkTally; ++i)
+      if (tally[i]) atomicAdd(counters + 1 + i, (u64)tally[i]);
+  }
+}
+
+// the arguments the ray entry points share; fills hd
+bool view_rays_ok(const unsigned char* state, int nx, int ny, int nz, long& cells, long V, int range, const int* headings,
+                  int H, long cos2_num, long cos2_den, const unsigned long long* counters, Headings& hd) {
+  bool ok = state && counters && headings && grid_ok(nx, ny, nz, cells) && V >= 0 && V <= 0x7FFFFFFFl && range >= 1 &&
+            range <= kMaxRange && H >= 1 && H <= kMaxHeadings && cos2_den > 0 && cos2_den < (1l << 31) && cos2_num >= 0 &&
+            cos2_num <= cos2_den;
+  for (int h = 0; ok && h < H; ++h) {
+    long long n2 = 0;
+    for (int a = 0; a < 3; ++a) {
+      const int c = headings[3 * h + a];
+      ok = ok && c >= -kMaxAxis && c <= kMaxAxis;
+      hd.axis[h][a] = c;
+      n2 += (long long)c * c;
+    }
+    ok = ok && n2 != 0;
+    hd.norm[h] = n2 * cos2_num;
+  }
+  return ok;
+}
+
+// pi3_grid_view_gain (seen == nullptr, unseen false) and pi3_grid_view_gain_unseen
+int view_gain(const char* who, bool unseen, const unsigned char* state, int nx, int ny, int nz, const unsigned* seen,
+              const long* candidates, long V, int range, const int* headings, int H, long cos2_num, long cos2_den,
+              unsigned* gain, unsigned* visible, int* best, unsigned long long* counters, void* stream) {
+  long cells = 0;
+  Headings hd = {};
+  const bool ok = view_rays_ok(state, nx, ny, nz, cells, V, range, headings, H, cos2_num, cos2_den, counters, hd) &&
+                  (V == 0 || (candidates && gain && visible && best)) && (!unseen || seen);
+  if (!ok) {
+    pi3_set_error("%s: bad arguments dims=(%d, %d, %d) (1 .. 2^21 - 1 each, at most 2^27 cells) V=%ld "
+                  "(0 .. 2^31 - 1) range=%d (1 .. %d) H=%d (1 .. %d; every axis non-zero, components within +-%d) "
+                  "cos2=%ld/%ld (0 <= num <= den, 0 < den < 2^31), or a null pointer", who, nx, ny, nz, V, range,
+                  kMaxRange, H, kMaxHeadings, kMaxAxis, cos2_num, cos2_den);
+    return PI3_ERR_ARG;
+  }
+  if (pi3_zero_words(who, counters, 4, stream) != PI3_OK) return PI3_ERR_LAUNCH;
+  if (V == 0) return PI3_OK;                  // no candidate: no kernel
+  const size_t bytes = (size_t)(kTally + 4 * kQueue + grid_view_ray::box_words(range)) * sizeof(unsigned);
+  if (unseen)
+    hipLaunchKernelGGL(view_gain_kernel<true>, dim3((unsigned)V), dim3(256), bytes, (hipStream_t)stream, state, nx, ny,
+                       nz, seen, candidates, range, H, hd, (long long)cos2_den, gain, visible, best, (u64*)counters);
+  else
+    hipLaunchKernelGGL(view_gain_kernel<false>, dim3((unsigned)V), dim3(256), bytes, (hipStream_t)stream, state, nx, ny,
+                       nz, (const unsigned*)nullptr, candidates, range, H, hd, (long long)cos2_den, gain, visible, best,
+                       (u64*)counters);
+  return pi3_check_launch(who + 4);           // without "pi3_"
 }
 
 }  // namespace
@@ -244,35 +333,50 @@ extern "C" int pi3_grid_view_candidates(const unsigned* dist, int nx, int ny, in
 extern "C" int pi3_grid_view_gain(const unsigned char* state, int nx, int ny, int nz, const long* candidates, long V,
                                   int range, const int* headings, int H, long cos2_num, long cos2_den, unsigned* gain,
                                   unsigned* visible, int* best, unsigned long long* counters, void* stream) {
+  return view_gain("pi3_grid_view_gain", false, state, nx, ny, nz, nullptr, candidates, V, range, headings, H, cos2_num,
+                   cos2_den, gain, visible, best, counters, stream);
+}
+
+extern "C" int pi3_grid_view_gain_unseen(const unsigned char* state, int nx, int ny, int nz, const unsigned* seen,
+                                         const long* candidates, long V, int range, const int* headings, int H,
+                                         long cos2_num, long cos2_den, unsigned* gain, unsigned* visible, int* best,
+                                         unsigned long long* counters, void* stream) {
+  return view_gain("pi3_grid_view_gain_unseen", true, state, nx, ny, nz, seen, candidates, V, range, headings, H,
+                   cos2_num, cos2_den, gain, visible, best, counters, stream);
+}
+
+extern "C" int pi3_grid_view_mark(const unsigned char* state, int nx, int ny, int nz, unsigned* seen, const long* cells_in,
+                                  const int* heading_of, long V, int range, const int* headings, int H, long cos2_num,
+                                  long cos2_den, short* owner, int tag, unsigned long long* counters, void* stream) {
   long cells = 0;
-  bool ok = state && counters && headings && grid_ok(nx, ny, nz, cells) && V >= 0 && V <= 0x7FFFFFFFl && range >= 1 &&
-            range <= kMaxRange && H >= 1 && H <= kMaxHeadings && cos2_den > 0 && cos2_den < (1l << 31) && cos2_num >= 0 &&
-            cos2_num <= cos2_den && (V == 0 || (candidates && gain && visible && best));
   Headings hd = {};
-  for (int h = 0; ok && h < H; ++h) {
-    long long n2 = 0;
-    for (int a = 0; a < 3; ++a) {
-      const int c = headings[3 * h + a];
-      ok = ok && c >= -kMaxAxis && c <= kMaxAxis;
-      hd.axis[h][a] = c;
-      n2 += (long long)c * c;
-    }
-    ok = ok && n2 != 0;
-    hd.norm[h] = n2 * cos2_num;
-  }
+  bool ok = view_rays_ok(state, nx, ny, nz, cells, V, range, headings, H, cos2_num, cos2_den, counters, hd) && seen &&
+            (V == 0 || (cells_in && heading_of)) && tag >= 0 && tag < 32768 && (!owner || V == 1);
+  for (long i = 0; ok && i < V; ++i) ok = heading_of[i] >= -1 && heading_of[i] < H;
   if (!ok) {
-    pi3_set_error("pi3_grid_view_gain: bad arguments dims=(%d, %d, %d) (1 .. 2^21 - 1 each, at most 2^27 cells) V=%ld "
-                  "(0 .. 2^31 - 1) range=%d (1 .. %d) H=%d (1 .. %d; every axis non-zero, components within +-%d) "
-                  "cos2=%ld/%ld (0 <= num <= den, 0 < den < 2^31), or a null pointer", nx, ny, nz, V, range, kMaxRange, H,
-                  kMaxHeadings, kMaxAxis, cos2_num, cos2_den);
+    pi3_set_error("pi3_grid_view_mark: bad arguments dims=(%d, %d, %d) (1 .. 2^21 - 1 each, at most 2^27 cells) V=%ld "
+                  "(0 .. 2^31 - 1; 1 with an owner) range=%d (1 .. %d) H=%d (1 .. %d; every axis non-zero, components "
+                  "within +-%d; every row's heading in -1 .. H - 1) cos2=%ld/%ld (0 <= num <= den, 0 < den < 2^31) "
+                  "tag=%d (0 .. 32767), or a null pointer", nx, ny, nz, V, range, kMaxRange, H, kMaxHeadings, kMaxAxis,
+                  cos2_num, cos2_den, tag);
     return PI3_ERR_ARG;
   }
-  if (pi3_zero_words("pi3_grid_view_gain", counters, 4, stream) != PI3_OK) return PI3_ERR_LAUNCH;
-  if (V == 0) return PI3_OK;                  // no candidate: no kernel
-  const int W = 2 * range + 1;
-  const int words = kTally + 4 * kQueue + 8 * ((W * W * W + 255) / 256);      // 8 whole words per pass: 35.7 KB at 32
-  hipLaunchKernelGGL(view_gain_kernel, dim3((unsigned)V), dim3(256), (size_t)words * sizeof(unsigned),
-                     (hipStream_t)stream, state, nx, ny, nz, candidates, range, H, hd, (long long)cos2_den, gain, visible,
-                     best, (u64*)counters);
-  return pi3_check_launch("grid_view_gain");
+  if (pi3_zero_words("pi3_grid_view_mark", counters, 1 + kMarkTally, stream) != PI3_OK) return PI3_ERR_LAUNCH;
+  const size_t bytes = (size_t)(kMarkTally + 4 * kQueue + grid_view_ray::box_words(range)) * sizeof(unsigned);
+  // The rows' headings travel by value.  One heading for all rows (a single view, the seeable pass) is one launch;
+  // else kMarkRows rows per launch, which costs a large batch the balance of one grid over all its rows.
+  bool same = true;
+  for (long i = 1; same && i < V; ++i) same = heading_of[i] == heading_of[0];
+  const long step = same ? V : kMarkRows;
+  MarkRows rows;
+  for (long base = 0; base < V; base += step) {
+    const long n = V - base < step ? V - base : step;
+    for (int i = 0; i < kMarkRows; ++i) rows.heading[i] = (signed char)(i < n ? heading_of[base + i] : -1);
+    hipLaunchKernelGGL(view_mark_kernel, dim3((unsigned)n), dim3(256), bytes, (hipStream_t)stream, state, nx, ny, nz,
+                       seen, cells_in + base, rows, same ? 1 : 0, range, H, hd, (long long)cos2_den, owner, tag,
+                       (u64*)counters);
+    const int rc = pi3_check_launch("grid_view_mark");
+    if (rc != PI3_OK) return rc;
+  }
+  return PI3_OK;
 }

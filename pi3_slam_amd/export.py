@@ -306,19 +306,21 @@ def write_frontiers(fset, out_dir: str) -> int:
 def write_views(vset, out_dir: str) -> int:
     """A view_planner.ViewSet -> <out_dir>/views.json (settings, counts and the view records in rank order), views.npz
     (gain i32 (nz,ny,nx): the best gain per candidate cell, -1 elsewhere; heading i8: the row of headings i64 (26,3)
-    that reaches it, -1 elsewhere; index_origin i64 (3,), origin f64 (3,), cell f64) and views.ply: the kept views as
-    points whose normal nx ny nz is the viewing direction, coloured from frontiers.ply's palette by rank, for viewing
-    next to dense_points.ply.  Returns the number of views."""
+    that reaches it, -1 elsewhere; index_origin i64 (3,), origin f64 (3,), cell f64; of a cover also seen_by i16: the
+    rank of the view that first covered the cell, -1 elsewhere, and `new` / `covered` in every record) and views.ply:
+    the kept views as points whose normal nx ny nz is the viewing direction, coloured from frontiers.ply's palette by
+    rank, for viewing next to dense_points.ply.  Returns the number of views."""
     os.makedirs(out_dir, exist_ok=True)
     record = {"settings": vset.settings, "counts": vset.counts, "views": [v.record() for v in vset.views]}
     with open(os.path.join(out_dir, "views.json"), "w") as f:
         json.dump(record, f, indent=1)
+    cover = {} if vset.seen_by is None else {"seen_by": np.asarray(vset.seen_by, np.int16)}
     with open(os.path.join(out_dir, "views.npz"), "wb") as f:
         np.savez_compressed(f, gain=np.asarray(vset.gain, np.int32), heading=np.asarray(vset.heading, np.int8),
                             headings=np.asarray(vset.headings, np.int64),
                             index_origin=np.asarray(vset.index_origin, np.int64),
                             origin=float(vset.cell) * np.asarray(vset.index_origin, np.float64),
-                            cell=np.float64(vset.cell))
+                            cell=np.float64(vset.cell), **cover)
     n = len(vset.views)
     pts = np.array([v.position for v in vset.views], np.float64).reshape(n, 3)
     dirs = np.array([v.direction for v in vset.views], np.float64).reshape(n, 3)

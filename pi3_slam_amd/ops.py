@@ -9,6 +9,7 @@ import ctypes as C
 import math
 from typing import Optional, Tuple
 
+import numpy as np
 import torch
 
 from . import lib as _L
@@ -1223,6 +1224,85 @@ def grid_view_gain(state: torch.Tensor, candidates: torch.Tensor, view_range: in
                                 visible.data_ptr() if V else None, best.data_ptr() if V else None,
                                 counters.data_ptr(), _L.stream_ptr())
     _L.check(rc, "pi3_grid_view_gain")
+
+
+VIEW_MARK_COUNTERS = ("views", "rays", "rays_visible", "in_cone", "new")
+VIEW_MAX_TAG = 32767                    # owner is int16
+
+
+def grid_view_seen_words(cells: int) -> int:
+    """The int32 words of a seen mask over `cells` cells: cell c is bit c & 31 of word c >> 5."""
+    return (int(cells) + 31) >> 5
+
+
+def _view_headings(headings):
+    hd = [tuple(int(c) for c in a) for a in headings]
+    H = len(hd)
+    assert 1 <= H <= VIEW_MAX_HEADINGS, f"{H} headings: 1 .. {VIEW_MAX_HEADINGS}"
+    assert all(len(a) == 3 and any(a) and max(abs(c) for c in a) <= VIEW_MAX_AXIS for a in hd), \
+        f"a heading is no non-zero integer axis (x, y, z) within +-{VIEW_MAX_AXIS}"
+    return (C.c_int * (3 * H))(*[c for a in hd for c in a]), H
+
+
+def _view_seen(seen: torch.Tensor, state: torch.Tensor) -> None:
+    assert seen.dtype == torch.int32 and seen.is_contiguous() and seen.ndim == 1 and seen.device == state.device
+    assert int(seen.numel()) == grid_view_seen_words(state.numel()), \
+        f"a mask of {seen.numel()} words for {state.numel()} cells: {grid_view_seen_words(state.numel())}"
+
+
+def grid_view_gain_unseen(state: torch.Tensor, seen: torch.Tensor, candidates: torch.Tensor, view_range: int, headings,
+                          cos2_num: int, cos2_den: int, gain: torch.Tensor, visible: torch.Tensor, best: torch.Tensor,
+                          counters: torch.Tensor) -> None:
+    """grid_view_gain over the unknown cells whose bit of seen int32 (grid_view_seen_words(cells),) (the uint32 words) is
+    clear; every output keeps its shape and meaning, and with an all-zero mask its bytes."""
+    lib = _L.load()
+    nx, ny, nz = _grid_state(state)
+    dev = state.device
+    assert 0 < state.numel() <= ROUTE_MAX_CELLS, f"{state.numel()} cells: 1 .. 2^27"
+    _view_seen(seen, state)
+    assert candidates.dtype == torch.int64 and candidates.is_contiguous() and candidates.ndim == 1
+    assert candidates.device == dev
+    V = int(candidates.numel())
+    flat, H = _view_headings(headings)
+    assert gain.dtype == torch.int32 and gain.is_contiguous() and tuple(gain.shape) == (V, H) and gain.device == dev
+    for t in (visible, best):
+        assert t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == (V,) and t.device == dev
+    assert counters.dtype == torch.int64 and counters.is_contiguous() and counters.numel() >= 4 and counters.device == dev
+    rc = lib.pi3_grid_view_gain_unseen(state.data_ptr(), nx, ny, nz, seen.data_ptr(),
+                                       candidates.data_ptr() if V else None, V, int(view_range), flat, H, int(cos2_num),
+                                       int(cos2_den), gain.data_ptr() if V else None, visible.data_ptr() if V else None,
+                                       best.data_ptr() if V else None, counters.data_ptr(), _L.stream_ptr())
+    _L.check(rc, "pi3_grid_view_gain_unseen")
+
+
+def grid_view_mark(state: torch.Tensor, seen: torch.Tensor, cells: torch.Tensor, heading_of, view_range: int, headings,
+                   cos2_num: int, cos2_den: int, counters: torch.Tensor, owner: Optional[torch.Tensor] = None,
+                   tag: int = 0) -> None:
+    """Sets in seen int32 (grid_view_seen_words(cells),) the bit of every unknown cell within view_range cells of cells[i]
+    (int64 (V,), linear indices on the device) that no occupied cell hides and that lies in the cone of heading
+    heading_of[i] (V host integers in -1 .. H - 1; -1: in the cone of any heading).  owner int16 (nz,ny,nx), only with
+    V == 1: the cells whose bit this call turned get `tag` (0 .. VIEW_MAX_TAG).  counters int64 (5,) =
+    VIEW_MARK_COUNTERS (zeroed by the call)."""
+    lib = _L.load()
+    nx, ny, nz = _grid_state(state)
+    dev = state.device
+    assert 0 < state.numel() <= ROUTE_MAX_CELLS, f"{state.numel()} cells: 1 .. 2^27"
+    _view_seen(seen, state)
+    assert cells.dtype == torch.int64 and cells.is_contiguous() and cells.ndim == 1 and cells.device == dev
+    V = int(cells.numel())
+    flat, H = _view_headings(headings)
+    hof = np.ascontiguousarray(heading_of, dtype=np.int32).reshape(-1)
+    assert len(hof) == V and bool(((hof >= -1) & (hof < H)).all()), f"{V} rows need {V} headings in -1 .. {H - 1}"
+    assert 0 <= int(tag) <= VIEW_MAX_TAG, f"tag {tag}: 0 .. {VIEW_MAX_TAG}"
+    if owner is not None:
+        assert owner.dtype == torch.int16 and owner.is_contiguous() and owner.shape == state.shape and owner.device == dev
+        assert V == 1, f"an owner takes one row per call, got {V}"
+    assert counters.dtype == torch.int64 and counters.is_contiguous() and counters.numel() >= 5 and counters.device == dev
+    rc = lib.pi3_grid_view_mark(state.data_ptr(), nx, ny, nz, seen.data_ptr(), cells.data_ptr() if V else None,
+                                hof.ctypes.data_as(C.POINTER(C.c_int)) if V else None, V, int(view_range), flat, H,
+                                int(cos2_num), int(cos2_den),
+                                _L.ptr(owner), int(tag), counters.data_ptr(), _L.stream_ptr())
+    _L.check(rc, "pi3_grid_view_mark")
 
 
 # ---- nearest neighbours between two clouds (csrc/cloud_nn.hip)

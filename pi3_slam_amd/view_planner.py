@@ -12,8 +12,14 @@ greedily: gain descending, route cost ascending, cell ascending, no view within 
 
 Limitations: unknown space is transparent, so the gain is an upper bound; poses are cell centres; 26 headings only; a
 cone, not a frustum, and no roll; the range is at most 32 cells (use a larger occupancy cell for more); unknown space
-outside the grid is not counted; nothing is updated incrementally; the gain counts cells, not surface.  range_m, stride
-and fov_deg are starting points, not measured optima."""
+outside the grid is not counted; nothing is updated incrementally in `find` (`cover` below does); the gain counts cells,
+not surface.  range_m, stride and fov_deg are starting points, not measured optima.
+
+ViewPlanner.cover picks the views one after the other, each by what the kept ones leave unseen (DESIGN §7j;
+tests/grid_cover_ref.py): a bit per cell says "a kept view sees it", the gain kernel counts only cells whose bit is clear
+(the marginal gain m), and the mark kernel sets the bits of the view that was picked.  Round k keeps the (cell, heading)
+with the smallest key (-m, cost, cell, heading), so one cell may be kept with several headings: a camera that pans.  Only
+candidates within 2 R cells of the pick share a target with it; the others keep their m."""
 from __future__ import annotations
 
 import math
@@ -47,18 +53,23 @@ class View:
     visible: int                                # visible unknown cells in every direction
     cost: int                                   # the integer route cost (12 per cell edge) from the nearest source
     distance_m: float                           # cell cost / 12
+    new: int = -1                               # cover mode: the cells this view added (= gain, the marginal gain then)
+    covered: int = -1                           # cover mode: the running total after it
 
     def record(self) -> Dict:
-        """The view as JSON types."""
-        return {"rank": self.rank, "cell": self.cell, "position": [float(v) for v in self.position],
-                "heading": self.heading, "axis": [int(v) for v in self.axis],
-                "direction": [float(v) for v in self.direction], "gain": self.gain, "visible": self.visible,
-                "cost": self.cost, "distance_m": self.distance_m}
+        """The view as JSON types (`new` and `covered` in cover mode only)."""
+        rec = {"rank": self.rank, "cell": self.cell, "position": [float(v) for v in self.position],
+               "heading": self.heading, "axis": [int(v) for v in self.axis],
+               "direction": [float(v) for v in self.direction], "gain": self.gain, "visible": self.visible,
+               "cost": self.cost, "distance_m": self.distance_m}
+        if self.new >= 0:
+            rec.update(new=self.new, covered=self.covered)
+        return rec
 
 
 @dataclass
 class ViewSet:
-    """ViewPlanner.find's result."""
+    """ViewPlanner.find's or ViewPlanner.cover's result."""
     views: List[View]                           # in rank order
     gain: np.ndarray                            # i32 (nz,ny,nx): the best gain per candidate cell, -1 elsewhere
     heading: np.ndarray                         # i8 (nz,ny,nx): the best heading per candidate cell, -1 elsewhere
@@ -69,6 +80,9 @@ class ViewSet:
     settings: Dict = dc_field(default_factory=dict)
     field: Optional[RouteField] = dc_field(default=None, repr=False)
     router: Optional[GridRouter] = dc_field(default=None, repr=False)
+    # cover mode: i16 (nz,ny,nx), the rank of the view that first covered the cell, -1 elsewhere
+    seen_by: Optional[np.ndarray] = dc_field(default=None, repr=False)
+    mode: str = "gain"                          # "gain" (find) or "cover"
 
     @property
     def origin(self) -> np.ndarray:
@@ -111,6 +125,68 @@ def select_views(cells, best_gain, cost, shape, count: int, sep_cells: int, min_
     return np.asarray(kept, np.int64), low
 
 
+def cover_target(until: float, seeable: int) -> int:
+    """The cells a cover `until` this fraction has to reach: ceil(until * seeable), the product in binary64."""
+    return int(math.ceil(float(until) * int(seeable)))
+
+
+def cover_views(cells, cost, shape, gain, reach_cells: int, count: Optional[int], min_gain: int, mark, regain,
+                seeable: int = 0, until: Optional[float] = None):
+    """The cover loop's bookkeeping -> (picks [(row, heading, m, new, covered)] in rank order, the rows recomputed).
+    cells i64 (V,) are linear indices into a grid of `shape` (nz, ny, nx), ascending or not; cost (V,) their route cost;
+    gain (V,H) the marginal gains under the empty mask (copied).  Round k picks the (row, heading) with the smallest key
+    (-m, cost, cell, heading) and stops before picking when m < min_gain, k == count (None: no limit; min_gain must then
+    be >= 1) or covered >= cover_target(until, seeable).  mark(k, row, heading) sets the view's bits with tag k and
+    returns the number it turned, which must be m; regain(rows) returns the gains (len(rows), H) of those rows under the
+    mask as it is now.  Only rows within reach_cells (2 R) of the pick are asked for: no other candidate shares a
+    target with it."""
+    cells = np.asarray(cells, np.int64).reshape(-1)
+    cost = np.asarray(cost, np.int64).reshape(-1)
+    m = np.array(gain, np.int64)
+    m = m.reshape(len(cells), m.size // max(len(cells), 1))
+    nz, ny, nx = (int(n) for n in shape)
+    if count is None and int(min_gain) < 1:
+        raise ValueError("a cover without a count needs min_gain >= 1 to end")
+    xyz = np.stack([cells % nx, (cells // nx) % ny, cells // (nx * ny)], 1)
+    goal = None if until is None else cover_target(until, seeable)
+    picks, covered, recomputed = [], 0, 0
+    while m.size:
+        top = int(m.max())
+        if top < int(min_gain) or (count is not None and len(picks) >= int(count)) or (goal is not None and covered >= goal):
+            break
+        rows, hs = np.nonzero(m == top)
+        first = np.lexsort((hs, cells[rows], cost[rows]))[0]
+        r, h = int(rows[first]), int(hs[first])
+        new = int(mark(len(picks), r, h))
+        if new != top:
+            raise RuntimeError(f"view {len(picks)} (cell {int(cells[r])}, heading {h}) marked {new} cells, its gain was {top}")
+        covered += new
+        picks.append((r, h, top, new, covered))
+        d = xyz - xyz[r][None, :]
+        near = np.flatnonzero((d * d).sum(1) <= int(reach_cells) ** 2)
+        m[near] = np.asarray(regain(near), np.int64).reshape(len(near), -1)
+        recomputed += len(near)
+    return picks, recomputed
+
+
+def _pose(c: int, h: int, cost: int, hd, origin, cell: float, shape):
+    """View's arguments for the cell c and heading h -> (cell, position, heading, axis, direction), (cost, distance_m)."""
+    nz, ny, nx = shape
+    ijk = np.array([c % nx, (c // nx) % ny, c // (nx * ny)], np.int64)
+    axis = hd[h]
+    return ((c, cell * ((origin + ijk).astype(np.float64) + 0.5), h, axis.copy(),
+             axis / math.sqrt(float((axis * axis).sum()))), (cost, cell * cost / 12.0))
+
+
+def _best_maps(shape, cells, best_gain, best):
+    """-> (gain i32, heading i8) per cell of the grid: the candidates' best values, -1 elsewhere."""
+    gain_map = np.full(shape, -1, np.int32)
+    gain_map.reshape(-1)[cells] = best_gain
+    heading_map = np.full(shape, -1, np.int8)
+    heading_map.reshape(-1)[cells] = best
+    return gain_map, heading_map
+
+
 @dataclass
 class ViewPlanner:
     """radius (metres): the body's, for the route field (0: every free cell is traversable).  range_m: how far a view
@@ -144,6 +220,7 @@ class ViewPlanner:
             if isinstance(v, bool) or int(v) != v or int(v) < (0 if name == "min_gain" else 1):
                 raise ValueError(f"{name} must be an integer >= {0 if name == 'min_gain' else 1}, got {v!r}")
             setattr(self, name, int(v))
+        self.separation_given = self.separation_m is not None             # cover has no use for one and says so
         self.separation_m = self.range_m / 2.0 if self.separation_m is None else float(self.separation_m)
         if not (self.separation_m >= 0.0 and math.isfinite(self.separation_m)):
             raise ValueError(f"the separation must be a finite length >= 0, got {self.separation_m!r}")
@@ -195,7 +272,6 @@ class ViewPlanner:
         R, sep, max_cost = self.cells_of(cell)
         field = self.router.field(grid, sources_xyz, device)                # checks the grid
         state_np = field.state
-        nz, ny, nx = state_np.shape
         origin = np.asarray(grid.index_origin, np.int64)
         dev = torch.device(device)
         dist = field.device_arrays["cost"]
@@ -218,18 +294,93 @@ class ViewPlanner:
         keep, low = select_views(cells_np, best_gain, cost, state_np.shape, self.count, sep, self.min_gain)
         views = []
         for rank, r in enumerate(keep):
-            c, h = int(cells_np[r]), int(best_np[r])
-            ijk = np.array([c % nx, (c // nx) % ny, c // (nx * ny)], np.int64)
-            axis = hd[h]
-            views.append(View(rank, c, cell * ((origin + ijk).astype(np.float64) + 0.5), h, axis.copy(),
-                              axis / math.sqrt(float((axis * axis).sum())), int(best_gain[r]), int(visible_np[r]),
-                              int(cost[r]), cell * int(cost[r]) / 12.0))
-        gain_map = np.full(state_np.shape, -1, np.int32)
-        gain_map.reshape(-1)[cells_np] = best_gain
-        heading_map = np.full(state_np.shape, -1, np.int8)
-        heading_map.reshape(-1)[cells_np] = best_np
+            at, way = _pose(int(cells_np[r]), int(best_np[r]), int(cost[r]), hd, origin, cell, state_np.shape)
+            views.append(View(rank, *at, int(best_gain[r]), int(visible_np[r]), *way))
+        gain_map, heading_map = _best_maps(state_np.shape, cells_np, best_gain, best_np)
         counts.update(views=len(views), low_gain=low, reachable=field.counts["reachable"],
                       best_gain=int(best_gain.max()) if V else 0)
         st = dict(self.settings(), cell=cell, range_cells=R, separation_cells=sep, max_cost=max_cost,
                   headings=len(hd))
         return ViewSet(views, gain_map, heading_map, hd, origin, cell, counts, st, field, self.router)
+
+    def cover(self, grid: OccupancyGrid, sources_xyz, device="cuda", until: Optional[float] = None) -> ViewSet:
+        """The views that cover: find's field, candidates and range, the views picked one after the other by their
+        marginal gain (cover_views) until `count` are kept, the best marginal gain falls below min_gain or, with
+        `until` in (0, 1], that fraction of the seeable unknown cells is covered.  View.gain is the marginal gain at the
+        time the view was picked (= View.new), View.visible the unseen cells it saw in every direction then;
+        ViewSet.gain and .heading are the first pass's, the arrays find returns.  One device synchronisation per round."""
+        if sources_xyz is None:
+            raise ValueError("views need a source: where the camera has been (--start or --from-trajectory)")
+        if until is not None:
+            until = float(until)
+            if not 0.0 < until <= 1.0:
+                raise ValueError(f"the fraction to cover must lie in (0, 1], got {until!r}")
+        if self.separation_given:
+            raise ValueError("a cover keeps views by what they add, a cell may be kept with several headings: "
+                             "separation has no meaning there, leave it out")
+        cell = float(grid.cell)
+        R, _, max_cost = self.cells_of(cell)
+        field = self.router.field(grid, sources_xyz, device)                # checks the grid
+        state_np = field.state
+        origin = np.asarray(grid.index_origin, np.int64)
+        dev = torch.device(device)
+        state = torch.from_numpy(state_np).to(dev)
+        cells = self.candidates(field.device_arrays["cost"], origin, max_cost)
+        V = int(cells.numel())
+        hd = view_headings()
+        H = len(hd)
+        cone = (R, hd, self.cos2_num, self.cos2_den)
+        words = ops.grid_view_seen_words(state.numel())
+        mark_counters = torch.zeros(len(ops.VIEW_MARK_COUNTERS), dtype=torch.int64, device=dev)
+
+        # what any candidate sees in any heading, into a mask of its own
+        everything = torch.zeros(words, dtype=torch.int32, device=dev)
+        ops.grid_view_mark(state, everything, cells, np.full(V, -1, np.int32), *cone, mark_counters)
+        seeable = int(mark_counters[4].item())
+        del everything
+
+        seen = torch.zeros(words, dtype=torch.int32, device=dev)
+        owner = torch.full(state_np.shape, -1, dtype=torch.int16, device=dev)
+        gain = torch.empty((V, H), dtype=torch.int32, device=dev)
+        visible = torch.empty(V, dtype=torch.int32, device=dev)
+        best = torch.empty(V, dtype=torch.int32, device=dev)
+        counters = torch.zeros(4, dtype=torch.int64, device=dev)
+        ops.grid_view_gain_unseen(state, seen, cells, *cone, gain, visible, best, counters)
+        counts = dict(zip(ops.VIEW_COUNTERS, (int(v) for v in counters.tolist())))
+        if counts["candidates"] != V:
+            raise RuntimeError(f"the gain kernel saw {counts['candidates']} of {V} candidates")
+        cells_np, gain_np = cells.cpu().numpy(), gain.cpu().numpy().astype(np.int64)
+        visible_np, best_np = visible.cpu().numpy().astype(np.int64), best.cpu().numpy()
+        best_gain = gain_np[np.arange(V), best_np] if V else np.zeros(0, np.int64)
+        cost = field.cost.reshape(-1)[cells_np].astype(np.int64)
+        mark_rays, visible_then = [0], []
+
+        def mark(k, row, h):
+            visible_then.append(int(visible_np[row]))                       # under the mask the view was picked by
+            ops.grid_view_mark(state, seen, cells[row:row + 1], [h], *cone, mark_counters, owner, k)
+            c = mark_counters.tolist()                                      # the round's synchronisation
+            mark_rays[0] += c[1]
+            return c[4]
+
+        def regain(rows):
+            n = len(rows)
+            sub = cells[torch.from_numpy(rows).to(dev)]
+            ops.grid_view_gain_unseen(state, seen, sub, *cone, gain[:n], visible[:n], best[:n], counters)
+            visible_np[rows] = visible[:n].cpu().numpy()
+            return gain[:n].cpu().numpy()
+
+        picks, recomputed = cover_views(cells_np, cost, state_np.shape, gain_np, 2 * R, min(self.count, ops.VIEW_MAX_TAG + 1),
+                                        self.min_gain, mark, regain, seeable, until)
+        views = []
+        for rank, (r, h, m, new, covered) in enumerate(picks):
+            at, way = _pose(int(cells_np[r]), h, int(cost[r]), hd, origin, cell, state_np.shape)
+            views.append(View(rank, *at, m, visible_then[rank], *way, new, covered))
+        gain_map, heading_map = _best_maps(state_np.shape, cells_np, best_gain, best_np)
+        counts.update(views=len(views), low_gain=int((best_gain < self.min_gain).sum()),
+                      reachable=field.counts["reachable"], best_gain=int(best_gain.max()) if V else 0, seeable=seeable,
+                      covered=picks[-1][4] if picks else 0, unknown=int((state_np == 0).sum()), rounds=len(picks),
+                      recomputed_rows=recomputed, mark_rays=mark_rays[0])
+        st = dict(self.settings(), cell=cell, range_cells=R, separation_m=None, separation_cells=None, max_cost=max_cost,
+                  headings=H, mode="cover", until=until)
+        return ViewSet(views, gain_map, heading_map, hd, origin, cell, counts, st, field, self.router,
+                       owner.cpu().numpy(), "cover")

@@ -573,6 +573,30 @@ int pi3_grid_route_init(const unsigned char* state, const unsigned short* d2, in
 int pi3_grid_route_sweep(const unsigned char* walk, int nx, int ny, int nz, unsigned* dist, int* changed, void* stream);
 int pi3_grid_route_trace(const unsigned char* walk, const unsigned* dist, int nx, int ny, int nz, long goal, long* path,
                          long cap, long* length, void* stream);
+/* Several fields over one walk: dist uint32 [K][cells], field f the distances from sources[f] alone;
+ * 1 <= K <= 65 535.
+ * pi3_grid_route_fields_init: every field = 0xFFFFFFFF everywhere, then field f gets 0 at sources[f] (DEVICE int64 [K],
+ *   linear indices) when that index lies inside [0, cells) on a traversable cell; a field whose source is refused stays
+ *   all far.  counters: DEVICE uint64 [3] = sources accepted, not traversable, outside; zeroed by the call.
+ * pi3_grid_route_sweep_many: one pi3_grid_route_sweep of every field listed in active (DEVICE int32 [A], distinct field
+ *   numbers in 0 .. K - 1; an entry outside that range is passed over), a workgroup per tile and `group` listed fields:
+ *   the tile's walk bytes are staged once, then field after field.  changed: DEVICE int32 [K], never cleared here;
+ *   changed[f] becomes 1 when a cell of field f got lower.  Fields that are not listed are neither read nor written, and
+ *   neither are their entries of changed.  The fixed point of every field is pi3_grid_route_sweep's.  0 <= A <= K; A == 0
+ *   launches nothing and active may be NULL.  group >= 1 (more than A means A).
+ * pi3_grid_route_trace_many: one wave per leg l < L walks by pi3_grid_route_trace's rules over field field_of[l] from
+ *   goal[l] into path[offset[l] .. offset[l + 1]): field_of DEVICE int32 [L], goal DEVICE int64 [L], offset DEVICE int64
+ *   [L + 1] ascending, length DEVICE int64 [L]; length[l] = the waypoints, 0 when there is no way (or field_of[l] or
+ *   goal[l] is out of range), -needed when the slot is too short: the slot is then left untouched.  L >= 0; L == 0
+ *   launches nothing and the per-leg arrays may be NULL.
+ * Bad arguments launch nothing and leave the outputs untouched.  No allocation, no synchronisation. */
+int pi3_grid_route_fields_init(const unsigned char* walk, int nx, int ny, int nz, const long* sources, int K,
+                               unsigned* dist, unsigned long long* counters, void* stream);
+int pi3_grid_route_sweep_many(const unsigned char* walk, int nx, int ny, int nz, unsigned* dist, int K,
+                              const int* active, int A, int group, int* changed, void* stream);
+int pi3_grid_route_trace_many(const unsigned char* walk, const unsigned* dist, int nx, int ny, int nz, int K,
+                              const int* field_of, const long* goal, const long* offset, long* path, long* length, int L,
+                              void* stream);
 
 /* ---- frontiers of the occupancy grid (csrc/grid_frontier.hip): the same grid layout and limits (1 <= n < 2^21 per
  * axis, at most 2^27 cells); integers only.  A frontier cell is a cell with state == 1 of whose 6 face neighbours at

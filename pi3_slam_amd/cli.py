@@ -14,7 +14,7 @@
          [--radius 0.2] [--min-cells 20] [--route-to 0]
   python -m pi3_slam_amd.cli views --occupancy OUT/occupancy.npz --output DIR --from-trajectory OUT/trajectory_tum.txt \\
          [--radius 0.2] [--range 1.0] [--fov 90] [--stride 4] [--count 10] [--route-to 0] \\
-         [--cover [--cover-until 0.9]]
+         [--cover [--cover-until 0.9]] [--tour [--tour-from X Y Z]]
 
 Under `python -m torch.distributed.run --nproc-per-node G -m pi3_slam_amd.cli ...` every stage shards over the G GPUs.
 """
@@ -316,7 +316,7 @@ FRONTIER_FLAGS: Sequence[Tuple[str, Dict]] = (
 VIEW_FLAGS: Sequence[Tuple[str, Dict]] = (
     ("--occupancy", dict(REQ, help="occupancy.npz of `reconstruct` or `online` (--occupancy-cell)")),
     ("--output", dict(REQ, help="directory for views.json, views.npz and views.ply and, with --route-to, route.json, "
-                                "route.ply and route.npz")),
+                                "route.ply and route.npz, with --tour, tour.json, tour.npz and tour.ply")),
     ("--start", dict(type=float, nargs=3, default=None, metavar=("X", "Y", "Z"), help="the source: one world point")),
     ("--from-trajectory", dict(default=None, help="the sources: the position of every pose of this TUM trajectory "
                                                   "(poses on cells that are not traversable are skipped and counted)")),
@@ -339,11 +339,16 @@ VIEW_FLAGS: Sequence[Tuple[str, Dict]] = (
     ("--cover-until", dict(type=float, default=None, metavar="FRACTION",
                            help="with --cover: stop once this fraction, in (0, 1], of the unknown cells that any pose "
                                 "can see is covered (default: none, --count and --min-gain end the plan)")),
+    ("--tour-from", dict(type=float, nargs=3, default=None, metavar=("X", "Y", "Z"),
+                         help="with --tour: the world point the tour leaves from (default: --start, or the last pose "
+                              "of --from-trajectory)")),
     ("--device", dict(default="cuda")),
 )
 VIEW_SWITCHES: Sequence[Tuple[str, str]] = (
     ("--cover", "pick the views one after the other, each by the unknown cells the kept ones do not see yet, so that "
                 "the plan adds up; a cell may be kept with several headings, and --separation is refused"),
+    ("--tour", "also the order to visit the kept views in and the ways between them (tour.json, tour.npz, tour.ply): "
+               "the shortest open path from the start, exact up to 12 stops, nearest neighbour and 2-opt above"),
 )
 
 
@@ -629,6 +634,8 @@ def run_views(a: argparse.Namespace) -> None:
         raise SystemExit("views: --separation has no meaning with --cover (a cover keeps views by what they add)")
     if a.cover_until is not None and not a.cover:
         raise SystemExit("views: --cover-until needs --cover")
+    if a.tour_from is not None and not a.tour:
+        raise SystemExit("views: --tour-from needs --tour")
     try:
         planner = ViewPlanner(a.radius, a.range, a.fov, a.stride, a.count, a.separation, a.max_distance, a.min_gain)
         grid = export.read_occupancy(a.occupancy)
@@ -638,11 +645,14 @@ def run_views(a: argparse.Namespace) -> None:
         else:
             found = planner.find(grid, sources, a.device)
         route = found.route_to(a.route_to) if a.route_to is not None else None
+        tour = found.tour(a.tour_from) if a.tour else None
     except (ValueError, OSError) as e:
         raise SystemExit(f"views: {e}")
     export.write_views(found, a.output)
     if route is not None:
         export.write_route(found.field, route, a.output)
+    if tour is not None:
+        export.write_tour(tour, a.output)
     c = found.counts
     text = (f"views: {c['candidates']} candidates, {c['rays']} rays ({c['rays_visible']} visible), {c['views']} views "
             f"kept ({c['low_gain']} candidates below the gain)")
@@ -652,6 +662,11 @@ def run_views(a: argparse.Namespace) -> None:
     if found.mode == "cover":
         text += (f"; covered {c['covered']} of {c['seeable']} seeable unknown cells "
                  f"({100.0 * c['covered'] / max(c['seeable'], 1):.1f} %)")
+    if tour is not None:
+        text += (f"; tour: {len(tour.stops)} stops, {tour.distance_m:.2f} m ({tour.rank_order_length_m:.2f} m in rank "
+                 f"order), {tour.method}")
+        if tour.unreachable:
+            text += f", {len(tour.unreachable)} stops not reachable from the start"
     print(text)
 
 

@@ -27,6 +27,21 @@
 //                         that order is the order of the linear indices, so the lowest qualifying lane holds the
 //                         smallest index: one ballot.  dist falls by at least 12 per step, so the walk ends.  Two
 //                         passes, the first only counts: a path that does not fit leaves `path` untouched.
+//
+// Several fields over one walk (the tour of the views, view_tour.py): dist u32 [K][cells], field f from sources[f] alone.
+// They live in this file, not in a header of shared pieces: move_cost, hood_bit, move_needs, the fold of a cell's
+// allowed moves, the relaxation step and the trace walk are each written once here, as __device__ functions that the
+// single-field and the batched kernels both call.
+//   pi3_grid_route_fields_init  a thread per word sets every field far, then a thread per field applies the source
+//                               rule above to sources[f] and field f; a field whose source is refused stays all far.
+//   pi3_grid_route_sweep_many   one workgroup per (tile, group of `group` entries of `active`): the tile's walk bytes
+//                               are staged and every thread's moves mask folded ONCE, then field after field of the
+//                               group is staged into the same LDS block, relaxed by settle and written back.  A field
+//                               whose staged block (tile and halo) holds no finite value is skipped before the
+//                               relaxation: nothing can get lower there.  Fields share nothing but walk, so the
+//                               argument above holds per field, and changed[f] is that field's own word.
+//   pi3_grid_route_trace_many   one wave per leg l: the walk above over field field_of[l] from goal[l], into
+//                               path[offset[l] .. offset[l + 1]).
 #include "common.h"
 #include "grid_tile.h"
 #include "voxel_table.h"
@@ -46,6 +61,7 @@ using wave_block::block_count;
 constexpr unsigned kFar = 0xFFFFFFFFu;
 constexpr int kD2Far = 0xFFFF;
 constexpr int kMaxMinD2 = 255 * 255;    // the clearance field's largest finite value
+constexpr int kMaxFields = 65535;       // fields of one batch: a launch grid's y extent
 
 __host__ __device__ constexpr int move_cost(int dx, int dy, int dz) {
   const int n = (dx != 0) + (dy != 0) + (dz != 0);
@@ -62,6 +78,45 @@ __host__ __device__ constexpr unsigned move_needs(int dx, int dy, int dz) {
     for (int b = 0; b <= (dy != 0); ++b)
       for (int a = 0; a <= (dx != 0); ++a) m |= hood_bit(a * dx, b * dy, e * dz);
   return m;
+}
+
+// The allowed moves of the cell at LDS index c, bit k for move k of for_hood's numbering: the 27 walk bytes around it.
+// for_hood's walk and numbering, written out: as a lambda here the compiler waits for the 27 byte reads in batches of
+// 8 instead of issuing them together (24 for 43 VGPRs, and a sweep measured 1 % slower)
+__device__ __forceinline__ unsigned fold_moves(const unsigned char* sw, int c) {
+  unsigned hood = 0, moves = 0;
+#pragma unroll
+  for (int dz = -1; dz <= 1; ++dz)
+#pragma unroll
+    for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+      for (int dx = -1; dx <= 1; ++dx)
+        if (sw[c + dz * kPlane + dy * kRow + dx]) hood |= hood_bit(dx, dy, dz);
+  int k = 0;
+#pragma unroll
+  for (int dz = -1; dz <= 1; ++dz)
+#pragma unroll
+    for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+      for (int dx = -1; dx <= 1; ++dx) {
+        if (dx == 0 && dy == 0 && dz == 0) continue;
+        const unsigned need = move_needs(dx, dy, dz);
+        if ((hood & need) == need) moves |= 1u << k;
+        ++k;
+      }
+  return moves;
+}
+
+// settle's step: the lowest of `best` and what the allowed moves' neighbours in sd allow the cell at c
+__device__ __forceinline__ unsigned relax_step(const unsigned* sd, int c, unsigned moves, unsigned best) {
+  grid_tile::for_hood([&](int dx, int dy, int dz, int off, int k) {
+    if (moves & (1u << k)) {
+      const unsigned d = sd[c + off];
+      const unsigned cand = d + (unsigned)move_cost(dx, dy, dz);
+      if (d != kFar && cand < best) best = cand;              // far + w would wrap
+    }
+  });
+  return best;
 }
 
 __global__ __launch_bounds__(256) void route_init_kernel(const unsigned char* __restrict__ state,
@@ -116,49 +171,15 @@ __global__ __launch_bounds__(grid_tile::kThreads) void route_sweep_kernel(const 
   const bool open = sw[c] != 0;                               // 0 outside the grid: `own` is implied
   if (!__syncthreads_or(open)) return;                        // nothing to relax here: dist is not touched
   tile.stage(sd, (const unsigned*)dist, kFar);
-  // the allowed moves of this cell: the 27 walk bytes around it, once
-  unsigned moves = 0;
-  if (open) {
-    unsigned hood = 0;
-#pragma unroll
-    for (int dz = -1; dz <= 1; ++dz)
-#pragma unroll
-      for (int dy = -1; dy <= 1; ++dy)
-#pragma unroll
-        for (int dx = -1; dx <= 1; ++dx)
-          if (sw[c + dz * kPlane + dy * kRow + dx]) hood |= hood_bit(dx, dy, dz);
-    // for_hood's walk and numbering, written out: as a lambda here the compiler waits for the 27 byte reads above in
-    // batches of 8 instead of issuing them together (24 for 43 VGPRs, and a sweep measured 1 % slower)
-    int k = 0;
-#pragma unroll
-    for (int dz = -1; dz <= 1; ++dz)
-#pragma unroll
-      for (int dy = -1; dy <= 1; ++dy)
-#pragma unroll
-        for (int dx = -1; dx <= 1; ++dx) {
-          if (dx == 0 && dy == 0 && dz == 0) continue;
-          const unsigned need = move_needs(dx, dy, dz);
-          if ((hood & need) == need) moves |= 1u << k;
-          ++k;
-        }
-  }
+  const unsigned moves = open ? fold_moves(sw, c) : 0u;       // the allowed moves of this cell, once
   __syncthreads();
-  grid_tile::settle(tile, sd, dist, sd[c], changed, [&](unsigned best) {
-    grid_tile::for_hood([&](int dx, int dy, int dz, int off, int k) {
-      if (moves & (1u << k)) {
-        const unsigned d = sd[c + off];
-        const unsigned cand = d + (unsigned)move_cost(dx, dy, dz);
-        if (d != kFar && cand < best) best = cand;            // far + w would wrap
-      }
-    });
-    return best;
-  });
+  grid_tile::settle(tile, sd, dist, sd[c], changed, [&](unsigned best) { return relax_step(sd, c, moves, best); });
 }
 
-__global__ __launch_bounds__(64) void route_trace_kernel(const unsigned char* __restrict__ walk,
-                                                         const unsigned* __restrict__ dist, int nx, int ny, int nz,
-                                                         int goal, long* __restrict__ path, long cap,
-                                                         long* __restrict__ length) {
+// The trace: this wave walks from `goal` back to the field's source (every lane of the wave calls this)
+__device__ __forceinline__ void trace_walk(const unsigned char* __restrict__ walk, const unsigned* __restrict__ dist,
+                                           int nx, int ny, int nz, int goal, long* __restrict__ path, long cap,
+                                           long* __restrict__ length) {
   const int lane = (int)threadIdx.x;
   const int k = lane < 13 ? lane : lane + 1;                  // the 27 offsets in (dz, dy, dx) order without the centre
   const int dx = k % 3 - 1, dy = (k / 3) % 3 - 1, dz = k / 9 - 1;
@@ -206,6 +227,101 @@ __global__ __launch_bounds__(64) void route_trace_kernel(const unsigned char* __
     }
     if (pass && lane == 0) *length = n;
   }
+}
+
+__global__ __launch_bounds__(64) void route_trace_kernel(const unsigned char* __restrict__ walk,
+                                                         const unsigned* __restrict__ dist, int nx, int ny, int nz,
+                                                         int goal, long* __restrict__ path, long cap,
+                                                         long* __restrict__ length) {
+  trace_walk(walk, dist, nx, ny, nz, goal, path, cap, length);
+}
+
+// ---- several fields over one walk
+__global__ __launch_bounds__(256) void route_fields_far_kernel(int cells, unsigned* __restrict__ dist) {
+  const int i = (int)blockIdx.x * 256 + (int)threadIdx.x;      // cells <= 2^27; blockIdx.y = the field
+  if (i < cells) dist[(size_t)blockIdx.y * (size_t)cells + i] = kFar;
+}
+
+__global__ __launch_bounds__(256) void route_fields_sources_kernel(const long* __restrict__ sources, int K, int cells,
+                                                                   const unsigned char* __restrict__ walk,
+                                                                   unsigned* __restrict__ dist,
+                                                                   u64* __restrict__ counters) {
+  const int f = (int)blockIdx.x * 256 + (int)threadIdx.x;
+  bool accepted = false, blocked = false, outside = false;
+  if (f < K) {
+    const long s = sources[f];
+    if (s < 0 || s >= (long)cells) {
+      outside = true;
+    } else if (!walk[s]) {
+      blocked = true;
+    } else {
+      dist[(size_t)f * (size_t)cells + (size_t)s] = 0u;
+      accepted = true;
+    }
+  }
+  const bool flags[3] = {accepted, blocked, outside};
+  const int at[3] = {0, 1, 2};
+  block_count<3>(flags, counters, at);
+}
+
+// blockIdx.x = the tile (grid_tile::Tile reads it), blockIdx.y = the group of `group` entries of active[A].  One LDS
+// block of words serves the group's fields one after the other: settle ends on a barrier after its last LDS read, so
+// the next field may be staged over it.  LDS 8.4 KB and 8 waves per workgroup: the 32 waves of a CU are reached with 4
+// workgroups at 34 KB, so a second block of words (to overlap a field's staging with its predecessor's relaxation)
+// would buy no occupancy and cost a barrier protocol; the loop is the plain one.
+// amdgpu_waves_per_eu(8): left alone the compiler takes 104 SGPRs for the loop's uniform values, which caps a SIMD at 7
+// waves, 3 workgroups per CU instead of 4.  Held to 8 waves it keeps 78 and moves 26 into lanes of one more VGPR (42;
+// no scratch), and the batched sweeps measured 13 to 18 % faster.
+__global__ __launch_bounds__(grid_tile::kThreads) __attribute__((amdgpu_waves_per_eu(8)))
+void route_sweep_many_kernel(const unsigned char* __restrict__ walk, int nx, int ny, int nz, int tx, int ty, size_t cells,
+                             unsigned* dist, int K, const int* __restrict__ active, int A, int group,
+                             int* __restrict__ changed) {
+  __shared__ unsigned sd[kLds];
+  __shared__ unsigned char sw[kLds];
+  const grid_tile::Tile tile(nx, ny, nz, tx, ty);
+  const int c = tile.c;
+  tile.stage(sw, walk, (unsigned char)0);
+  __syncthreads();
+  const bool open = sw[c] != 0;                               // 0 outside the grid: `own` is implied
+  if (!__syncthreads_or(open)) return;                        // nothing to relax here: no field is touched
+  const unsigned moves = open ? fold_moves(sw, c) : 0u;       // once for every field of the group
+  // the two words of the block that Tile::stage has this thread store (entries t and t + 512 of the 1 000)
+  constexpr int kBlock = grid_tile::kH * grid_tile::kH * grid_tile::kH;
+  static_assert(kBlock <= 2 * grid_tile::kThreads, "a thread stages at most two entries");
+  const auto lds_of = [](int j) {
+    return (j / (grid_tile::kH * grid_tile::kH)) * kPlane + ((j / grid_tile::kH) % grid_tile::kH) * kRow + j % grid_tile::kH;
+  };
+  const int mine0 = lds_of(tile.t);
+  const int mine1 = tile.t + grid_tile::kThreads < kBlock ? lds_of(tile.t + grid_tile::kThreads) : mine0;
+  const int first = (int)blockIdx.y * group;
+  const int last = min(first + group, A);
+  for (int a = first; a < last; ++a) {
+    const int f = active[a];
+    if (f < 0 || f >= K) continue;                            // not a field: nothing is read or written (uniform)
+    unsigned* field = dist + (size_t)f * cells;
+    tile.stage(sd, (const unsigned*)field, kFar);
+    const bool finite = sd[mine0] != kFar || sd[mine1] != kFar;
+    // the barrier publishes the staged words; an all-far block has nothing to lower, and nobody reads it again
+    if (!__syncthreads_or(finite)) continue;
+    grid_tile::settle(tile, sd, field, sd[c], changed + f, [&](unsigned best) { return relax_step(sd, c, moves, best); });
+  }
+}
+
+// one wave per leg; a leg whose field or goal is none has no way
+__global__ __launch_bounds__(64) void route_trace_many_kernel(const unsigned char* __restrict__ walk,
+                                                              const unsigned* __restrict__ dist, int nx, int ny, int nz,
+                                                              size_t cells, int K, const int* __restrict__ field_of,
+                                                              const long* __restrict__ goal,
+                                                              const long* __restrict__ offset, long* __restrict__ path,
+                                                              long* __restrict__ length) {
+  const int l = (int)blockIdx.x;
+  const int f = field_of[l];
+  const long g = goal[l];
+  if (f < 0 || f >= K || g < 0 || g >= (long)cells) {
+    if (threadIdx.x == 0) length[l] = 0;
+    return;
+  }
+  trace_walk(walk, dist + (size_t)f * cells, nx, ny, nz, (int)g, path + offset[l], offset[l + 1] - offset[l], length + l);
 }
 
 }  // namespace
@@ -257,4 +373,56 @@ extern "C" int pi3_grid_route_trace(const unsigned char* walk, const unsigned* d
   hipLaunchKernelGGL(route_trace_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, walk, dist, nx, ny, nz, (int)goal,
                      path, cap, length);
   return pi3_check_launch("grid_route_trace");
+}
+
+extern "C" int pi3_grid_route_fields_init(const unsigned char* walk, int nx, int ny, int nz, const long* sources, int K,
+                                          unsigned* dist, unsigned long long* counters, void* stream) {
+  long cells = 0;
+  if (!walk || !sources || !dist || !counters || !grid_ok(nx, ny, nz, cells) || K < 1 || K > kMaxFields) {
+    pi3_set_error("pi3_grid_route_fields_init: bad arguments dims=(%d, %d, %d) (1 .. 2^21 - 1 each, at most 2^27 cells) "
+                  "K=%d (1 .. %d), or a null pointer", nx, ny, nz, K, kMaxFields);
+    return PI3_ERR_ARG;
+  }
+  if (pi3_zero_words("pi3_grid_route_fields_init", counters, 3, stream) != PI3_OK) return PI3_ERR_LAUNCH;
+  hipLaunchKernelGGL(route_fields_far_kernel, dim3(voxel_table::blocks_for(cells), (unsigned)K), dim3(256), 0,
+                     (hipStream_t)stream, (int)cells, dist);
+  hipLaunchKernelGGL(route_fields_sources_kernel, dim3(voxel_table::blocks_for(K)), dim3(256), 0, (hipStream_t)stream,
+                     sources, K, (int)cells, walk, dist, (u64*)counters);
+  return pi3_check_launch("grid_route_fields_init");
+}
+
+extern "C" int pi3_grid_route_sweep_many(const unsigned char* walk, int nx, int ny, int nz, unsigned* dist, int K,
+                                         const int* active, int A, int group, int* changed, void* stream) {
+  long cells = 0;
+  if (!walk || !dist || !changed || !grid_ok(nx, ny, nz, cells) || K < 1 || K > kMaxFields || A < 0 || A > K ||
+      (A > 0 && !active) || group < 1) {
+    pi3_set_error("pi3_grid_route_sweep_many: bad arguments dims=(%d, %d, %d) (1 .. 2^21 - 1 each, at most 2^27 cells) "
+                  "K=%d (1 .. %d) A=%d (0 .. K) group=%d (>= 1), or a null pointer", nx, ny, nz, K, kMaxFields, A,
+                  group);
+    return PI3_ERR_ARG;
+  }
+  if (A == 0) return PI3_OK;                                  // no field is listed: nothing to sweep
+  int tx, ty;
+  const unsigned tiles = grid_tile::tiles(nx, ny, nz, tx, ty);
+  const int per = group < A ? group : A;                      // more than A means A
+  const unsigned groups = (unsigned)((A + per - 1) / per);    // <= K <= 65 535: a launch grid's y extent
+  hipLaunchKernelGGL(route_sweep_many_kernel, dim3(tiles, groups), dim3(grid_tile::kThreads), 0, (hipStream_t)stream,
+                     walk, nx, ny, nz, tx, ty, (size_t)cells, dist, K, active, A, per, changed);
+  return pi3_check_launch("grid_route_sweep_many");
+}
+
+extern "C" int pi3_grid_route_trace_many(const unsigned char* walk, const unsigned* dist, int nx, int ny, int nz, int K,
+                                         const int* field_of, const long* goal, const long* offset, long* path,
+                                         long* length, int L, void* stream) {
+  long cells = 0;
+  if (!walk || !dist || !grid_ok(nx, ny, nz, cells) || K < 1 || K > kMaxFields || L < 0 ||
+      (L > 0 && (!field_of || !goal || !offset || !path || !length))) {
+    pi3_set_error("pi3_grid_route_trace_many: bad arguments dims=(%d, %d, %d) (1 .. 2^21 - 1 each, at most 2^27 cells) "
+                  "K=%d (1 .. %d) L=%d (>= 0), or a null pointer", nx, ny, nz, K, kMaxFields, L);
+    return PI3_ERR_ARG;
+  }
+  if (L == 0) return PI3_OK;                                  // no leg: nothing to trace
+  hipLaunchKernelGGL(route_trace_many_kernel, dim3((unsigned)L), dim3(64), 0, (hipStream_t)stream, walk, dist, nx, ny,
+                     nz, (size_t)cells, K, field_of, goal, offset, path, length);
+  return pi3_check_launch("grid_route_trace_many");
 }

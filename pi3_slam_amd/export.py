@@ -16,6 +16,7 @@ Pi3SLAMOnline.chunk_reconstructions).  Files and formats mirror slam/offline_rec
 
 write_outputs writes them all, in that order.  A chunk needs dist.COLLECT_KEYS for it, nothing else.
 
+write_tour writes the tour of a view set (view_tour.py): tour.json, tour.npz, tour.ply.
 Outside stage 2, for `cli route` (grid_route.py): read_occupancy reads occupancy.npz back, write_route writes route.npz
 (the distance field) and, with a goal, route.json and route.ply."""
 from __future__ import annotations
@@ -329,6 +330,38 @@ def write_views(vset, out_dir: str) -> int:
     print(f"✅ Saved {n} views of {vset.counts.get('candidates')} candidates to: {out_dir}/views.json, views.npz and "
           "views.ply")
     return n
+
+
+def write_tour(tour, out_dir: str) -> int:
+    """A view_tour.Tour -> <out_dir>/tour.json (settings, counts, the totals and the stops in visiting order, each with
+    the views taken there), tour.npz (order i64: the stops' numbers in visiting order; matrix i64 (n + 1, n + 1) and
+    cells i64 (n + 1,): node 0 the start, node s + 1 the stop numbered s; waypoints f64 (P,3), waypoint_cells i64 (P,)
+    and offsets i64 (legs + 1,): leg i is rows offsets[i] .. offsets[i + 1]) and tour.ply: the legs' waypoints as points
+    coloured from frontiers.ply's palette by leg, for viewing next to views.ply.  Returns the number of stops."""
+    os.makedirs(out_dir, exist_ok=True)
+    record = {"settings": tour.settings, "counts": tour.counts, "method": tour.method, "cost": int(tour.cost),
+              "distance_m": float(tour.distance_m), "length_m": float(tour.length_m),
+              "rank_order_cost": int(tour.rank_order_cost), "rank_order_length_m": float(tour.rank_order_length_m),
+              "nn_cost": int(tour.nn_cost), "moves": int(tour.moves), "covered": int(tour.covered),
+              "start": {"cell": int(tour.start_cell), "position": [float(v) for v in tour.start]},
+              "order": [int(s) for s in tour.order], "unreachable": [int(s) for s in tour.unreachable],
+              "stops": [s.record() for s in tour.stops]}
+    with open(os.path.join(out_dir, "tour.json"), "w") as f:
+        json.dump(record, f, indent=1)
+    legs = len(tour.leg_cells)
+    offsets = np.concatenate([[0], np.cumsum([len(c) for c in tour.leg_cells])]).astype(np.int64)
+    way = np.concatenate(tour.leg_waypoints).reshape(-1, 3) if legs else np.zeros((0, 3), np.float64)
+    way_cells = np.concatenate(tour.leg_cells).astype(np.int64) if legs else np.zeros(0, np.int64)
+    with open(os.path.join(out_dir, "tour.npz"), "wb") as f:
+        np.savez_compressed(f, order=np.asarray(tour.order, np.int64), matrix=np.asarray(tour.matrix, np.int64),
+                            cells=np.asarray(tour.cells, np.int64), waypoints=way, waypoint_cells=way_cells,
+                            offsets=offsets)
+    colors = np.concatenate([np.tile(np.array(FRONTIER_PALETTE[i % len(FRONTIER_PALETTE)], np.uint8), (len(c), 1))
+                             for i, c in enumerate(tour.leg_cells)]) if legs else np.zeros((0, 3), np.uint8)
+    write_ply(way, colors, os.path.join(out_dir, "tour.ply"))
+    print(f"✅ Saved the tour of {len(tour.stops)} stops ({len(way)} waypoints) to: {out_dir}/tour.json, tour.npz and "
+          "tour.ply")
+    return len(tour.stops)
 
 
 def write_renders(chunks: Sequence[Dict], dense: Optional[DenseMap], out_dir: str, every: Optional[int], overview: bool,

@@ -103,6 +103,9 @@ SIGNATURES = {
     "pi3_grid_route_init": [_vp, _vp, _i, _i, _i, _i, _i, _vp, _l, _vp, _vp, _vp, _vp],
     "pi3_grid_route_sweep": [_vp, _i, _i, _i, _vp, _vp, _vp],
     "pi3_grid_route_trace": [_vp, _vp, _i, _i, _i, _l, _vp, _l, _vp, _vp],
+    "pi3_grid_route_fields_init": [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp],
+    "pi3_grid_route_sweep_many": [_vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _vp, _vp],
+    "pi3_grid_route_trace_many": [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp],
     "pi3_grid_frontier_mark": [_vp, _i, _i, _i, _vp, _vp, _vp],
     "pi3_grid_frontier_sweep": [_i, _i, _i, _vp, _vp, _vp],
     "pi3_grid_frontier_roots": [_vp, _i, _i, _i, _vp, _l, _vp, _vp],

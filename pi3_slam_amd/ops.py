@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Optional, Tuple
+from typing import List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -1051,6 +1051,38 @@ def sweep_until_quiet(launch, device, bound: int, what: str, per_read: int) -> i
             raise RuntimeError(what.format(sweeps=sweeps))
 
 
+def sweep_many_until_quiet(launch, device, K: int, bound: int, what: str, per_read: int) -> List[int]:
+    """sweep_until_quiet for K fields that settle at different times -> the sweeps run per field, the quiet one included.
+    launch(active, flags) queues one sweep of the fields listed in active int32 (A,) (ascending field numbers) that sets
+    flags[f] of the int32 (K,) `flags` when field f changed.  per_read launches are queued, each with its own row of K
+    flags over the same list, and the rows are read once; a field leaves the list after the first launch in which it was
+    listed and its flag stayed 0 (the launches queued behind that one in the same batch ran it again without effect and
+    are not counted).  More than `bound` sweeps of a field without a quiet one raise the RuntimeError `what`, a text
+    with a place for {sweeps}."""
+    K = int(K)
+    changed = torch.empty((per_read, K), dtype=torch.int32, device=device)
+    sweeps = [0] * K
+    listed = list(range(K))
+    while listed:
+        active = torch.tensor(listed, dtype=torch.int32, device=device)
+        changed.zero_()
+        for j in range(per_read):
+            launch(active, changed[j])
+        rows = changed.tolist()
+        still = []
+        for f in listed:
+            quiet = next((j for j in range(per_read) if rows[j][f] == 0), None)
+            if quiet is None:
+                sweeps[f] += per_read
+                if sweeps[f] > bound:
+                    raise RuntimeError(what.format(sweeps=sweeps[f]))
+                still.append(f)
+            else:
+                sweeps[f] += quiet + 1
+        listed = still
+    return sweeps
+
+
 def grid_route_init(state: torch.Tensor, d2: Optional[torch.Tensor], min_d2: int, through_unknown: bool,
                     sources: torch.Tensor, walk: torch.Tensor, dist: torch.Tensor, counters: torch.Tensor) -> None:
     """walk uint8 (nz,ny,nx) = 1 where state uint8 (nz,ny,nx) is free (with through_unknown: not occupied) and, with
@@ -1096,6 +1128,73 @@ def grid_route_trace(walk: torch.Tensor, dist: torch.Tensor, goal: int, path: to
     rc = lib.pi3_grid_route_trace(walk.data_ptr(), dist.data_ptr(), nx, ny, nz, int(goal), path.data_ptr(),
                                   int(path.numel()), length.data_ptr(), _L.stream_ptr())
     _L.check(rc, "pi3_grid_route_trace")
+
+
+ROUTE_FIELDS_COUNTERS = ("sources_accepted", "sources_blocked", "sources_outside")
+ROUTE_MAX_FIELDS = 65535
+
+
+def _grid_fields(dist: torch.Tensor, walk: torch.Tensor) -> Tuple[int, int, int, int]:
+    """(nx, ny, nz, K) of K fields int32 (K,nz,ny,nx) (the uint32 values) over their walk uint8 (nz,ny,nx)."""
+    assert dist.dtype == torch.int32 and dist.is_contiguous() and dist.ndim == 4
+    assert _grid_state(walk) and walk.shape == dist.shape[1:] and walk.device == dist.device
+    assert 0 < walk.numel() <= ROUTE_MAX_CELLS, f"{walk.numel()} cells: 1 .. 2^27"
+    assert 1 <= int(dist.shape[0]) <= ROUTE_MAX_FIELDS, f"{dist.shape[0]} fields: 1 .. {ROUTE_MAX_FIELDS}"
+    return int(dist.shape[3]), int(dist.shape[2]), int(dist.shape[1]), int(dist.shape[0])
+
+
+def grid_route_fields_init(walk: torch.Tensor, sources: torch.Tensor, dist: torch.Tensor, counters: torch.Tensor) -> None:
+    """dist int32 (K,nz,ny,nx) (the uint32 values) = ROUTE_FAR everywhere, then field f = 0 at sources[f] (int64 (K,),
+    linear indices) when that lies inside the grid on a traversable cell of walk uint8 (nz,ny,nx); a field whose source
+    is refused stays all far.  counters int64 (3,) = ROUTE_FIELDS_COUNTERS (zeroed by the call)."""
+    lib = _L.load()
+    nx, ny, nz, K = _grid_fields(dist, walk)
+    dev = walk.device
+    assert sources.dtype == torch.int64 and sources.is_contiguous() and tuple(sources.shape) == (K,) and sources.device == dev
+    assert counters.dtype == torch.int64 and counters.is_contiguous() and counters.numel() >= 3 and counters.device == dev
+    rc = lib.pi3_grid_route_fields_init(walk.data_ptr(), nx, ny, nz, sources.data_ptr(), K, dist.data_ptr(),
+                                        counters.data_ptr(), _L.stream_ptr())
+    _L.check(rc, "pi3_grid_route_fields_init")
+
+
+def grid_route_sweep_many(walk: torch.Tensor, dist: torch.Tensor, active: torch.Tensor, group: int,
+                          changed: torch.Tensor) -> None:
+    """One relaxation sweep of the fields of dist int32 (K,nz,ny,nx) listed in active int32 (A,) (distinct field numbers,
+    A <= K), a workgroup per tile and `group` listed fields; changed int32 (K,): entry f becomes 1 when a cell of field
+    f got lower (the caller zeroes it).  Fields that are not listed, and their entries, are not touched."""
+    lib = _L.load()
+    nx, ny, nz, K = _grid_fields(dist, walk)
+    dev = walk.device
+    assert active.dtype == torch.int32 and active.is_contiguous() and active.ndim == 1 and active.device == dev
+    A = int(active.numel())
+    assert A <= K, f"{A} listed fields of {K}"
+    assert int(group) >= 1, f"group {group}: >= 1"
+    assert changed.dtype == torch.int32 and changed.is_contiguous() and tuple(changed.shape) == (K,) and changed.device == dev
+    rc = lib.pi3_grid_route_sweep_many(walk.data_ptr(), nx, ny, nz, dist.data_ptr(), K, active.data_ptr() if A else None,
+                                       A, int(group), changed.data_ptr(), _L.stream_ptr())
+    _L.check(rc, "pi3_grid_route_sweep_many")
+
+
+def grid_route_trace_many(walk: torch.Tensor, dist: torch.Tensor, field_of: torch.Tensor, goal: torch.Tensor,
+                          offset: torch.Tensor, path: torch.Tensor, length: torch.Tensor) -> None:
+    """grid_route_trace for L legs at once: leg l walks over field field_of[l] (int32 (L,)) of the settled dist int32
+    (K,nz,ny,nx) from goal[l] (int64 (L,)) into path[offset[l] : offset[l + 1]] (offset int64 (L + 1,), ascending within
+    path int64 (P,): the caller's to keep); length int64 (L,) = the waypoints per leg, 0 when there is no way, -needed
+    when the slot is too short (it is then left untouched).  All on the device."""
+    lib = _L.load()
+    nx, ny, nz, K = _grid_fields(dist, walk)
+    dev = walk.device
+    L = int(field_of.numel())
+    assert field_of.dtype == torch.int32 and field_of.is_contiguous() and field_of.ndim == 1 and field_of.device == dev
+    for t, n in ((goal, L), (offset, L + 1), (length, L)):
+        assert t.dtype == torch.int64 and t.is_contiguous() and tuple(t.shape) == (n,) and t.device == dev
+    assert path.dtype == torch.int64 and path.is_contiguous() and path.ndim == 1 and path.device == dev
+    assert L == 0 or path.numel() >= 1
+    rc = lib.pi3_grid_route_trace_many(walk.data_ptr(), dist.data_ptr(), nx, ny, nz, K,
+                                       field_of.data_ptr() if L else None, goal.data_ptr() if L else None,
+                                       offset.data_ptr() if L else None, path.data_ptr() if L else None,
+                                       length.data_ptr() if L else None, L, _L.stream_ptr())
+    _L.check(rc, "pi3_grid_route_trace_many")
 
 
 # ---- frontiers of the occupancy grid (csrc/grid_frontier.hip)

@@ -19,7 +19,9 @@ ViewPlanner.cover picks the views one after the other, each by what the kept one
 tests/grid_cover_ref.py): a bit per cell says "a kept view sees it", the gain kernel counts only cells whose bit is clear
 (the marginal gain m), and the mark kernel sets the bits of the view that was picked.  Round k keeps the (cell, heading)
 with the smallest key (-m, cost, cell, heading), so one cell may be kept with several headings: a camera that pans.  Only
-candidates within 2 R cells of the pick share a target with it; the others keep their m."""
+candidates within 2 R cells of the pick share a target with it; the others keep their m.
+
+ViewSet.tour orders either result into a way to walk (view_tour.py)."""
 from __future__ import annotations
 
 import math
@@ -83,6 +85,7 @@ class ViewSet:
     # cover mode: i16 (nz,ny,nx), the rank of the view that first covered the cell, -1 elsewhere
     seen_by: Optional[np.ndarray] = dc_field(default=None, repr=False)
     mode: str = "gain"                          # "gain" (find) or "cover"
+    sources: Optional[np.ndarray] = dc_field(default=None, repr=False)     # f64 (N,3): the world points it was found from
 
     @property
     def origin(self) -> np.ndarray:
@@ -98,6 +101,11 @@ class ViewSet:
         if route is None or route.cost != v.cost:
             raise RuntimeError(f"the route to view {rank} does not match its cost {v.cost}")
         return route
+
+    def tour(self, start_xyz=None, **kwargs):
+        """The order to visit the views in and the ways between them (view_tour.plan_tour)."""
+        from .view_tour import plan_tour
+        return plan_tour(self, start_xyz, **kwargs)
 
 
 def select_views(cells, best_gain, cost, shape, count: int, sep_cells: int, min_gain: int):
@@ -301,7 +309,8 @@ class ViewPlanner:
                       best_gain=int(best_gain.max()) if V else 0)
         st = dict(self.settings(), cell=cell, range_cells=R, separation_cells=sep, max_cost=max_cost,
                   headings=len(hd))
-        return ViewSet(views, gain_map, heading_map, hd, origin, cell, counts, st, field, self.router)
+        return ViewSet(views, gain_map, heading_map, hd, origin, cell, counts, st, field, self.router,
+                       sources=np.asarray(sources_xyz, np.float64).reshape(-1, 3))
 
     def cover(self, grid: OccupancyGrid, sources_xyz, device="cuda", until: Optional[float] = None) -> ViewSet:
         """The views that cover: find's field, candidates and range, the views picked one after the other by their
@@ -383,4 +392,4 @@ class ViewPlanner:
         st = dict(self.settings(), cell=cell, range_cells=R, separation_m=None, separation_cells=None, max_cost=max_cost,
                   headings=H, mode="cover", until=until)
         return ViewSet(views, gain_map, heading_map, hd, origin, cell, counts, st, field, self.router,
-                       owner.cpu().numpy(), "cover")
+                       owner.cpu().numpy(), "cover", np.asarray(sources_xyz, np.float64).reshape(-1, 3))

@@ -597,6 +597,25 @@ int pi3_grid_route_sweep_many(const unsigned char* walk, int nx, int ny, int nz,
 int pi3_grid_route_trace_many(const unsigned char* walk, const unsigned* dist, int nx, int ny, int nz, int K,
                               const int* field_of, const long* goal, const long* offset, long* path, long* length, int L,
                               void* stream);
+/* Line of sight over the same walk (csrc/grid_sight.hip).  Cell a SEES cell b when every cell whose closed
+ * cube meets the segment between the two centres is traversable (the closed supercover: where the segment runs through
+ * an edge or a corner of the lattice, all 4 or 8 cells around it are touched).  Exact in 32-bit integers for two cells
+ * of a grid of at most 2^27 cells; symmetric; for two neighbours it is the move rule above.
+ * pi3_grid_route_sight_paths: the cells of `legs` ways one after the other, way l = cells[offsets[l] .. offsets[l + 1])
+ *   (cells DEVICE int64 [P] linear indices, offsets DEVICE int64 [legs + 1] ascending from 0 to P).  vis: DEVICE uint64
+ *   [P][ceil(span / 64)]; bit k of row p is set when p and p + 1 + k lie in the same way, k < span, and cells[p] sees
+ *   cells[p + 1 + k]; every other bit of every word is written 0.  An index outside [0, cells) sees nothing.
+ *   0 <= P < 2^31, legs >= 0, 1 <= span <= 4096; P == 0 or legs == 0 launches nothing and the arrays may be NULL.
+ * pi3_grid_route_sight_pairs: N arbitrary pairs a[i], b[i] (DEVICE int64 [N]).  The whole segment is walked even after
+ *   a blocked cell: sees uint8 [N] = 1 / 0, touched int32 [N] = the cells of the supercover, min_d2 uint16 [N] = the
+ *   smallest d2 (pi3_grid_edt's field, uint16 [cells]) over them, 0xFFFF when d2 is NULL.  An end outside [0, cells)
+ *   gives 0, 0, 0xFFFF.  0 <= N < 2^39; N == 0 launches nothing and the arrays may be NULL.
+ * Bad arguments launch nothing and leave the outputs untouched.  No allocation, no synchronisation. */
+int pi3_grid_route_sight_paths(const unsigned char* walk, int nx, int ny, int nz, const long* cells, long P,
+                               const long* offsets, int legs, int span, unsigned long long* vis, void* stream);
+int pi3_grid_route_sight_pairs(const unsigned char* walk, const unsigned short* d2, int nx, int ny, int nz, const long* a,
+                               const long* b, long N, unsigned char* sees, int* touched, unsigned short* min_d2,
+                               void* stream);
 
 /* ---- frontiers of the occupancy grid (csrc/grid_frontier.hip): the same grid layout and limits (1 <= n < 2^21 per
  * axis, at most 2^27 cells); integers only.  A frontier cell is a cell with state == 1 of whose 6 face neighbours at

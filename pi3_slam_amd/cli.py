@@ -9,12 +9,12 @@
   python -m pi3_slam_amd.cli online --image_dir /data/seq --output_path /data/seq_result --chunk_length 100 --overlap 20 \
          --model_path /ckpt/pi3 --save_tum [--cam_dist_path calib.json] [--use_inverse_depth]
   python -m pi3_slam_amd.cli route --occupancy OUT/occupancy.npz --output DIR --from-trajectory OUT/trajectory_tum.txt \\
-         [--goal X Y Z] [--radius 0.2]
+         [--goal X Y Z [--taut [--taut-span 256]]] [--radius 0.2]
   python -m pi3_slam_amd.cli frontiers --occupancy OUT/occupancy.npz --output DIR --from-trajectory OUT/trajectory_tum.txt \\
-         [--radius 0.2] [--min-cells 20] [--route-to 0]
+         [--radius 0.2] [--min-cells 20] [--route-to 0 [--taut]]
   python -m pi3_slam_amd.cli views --occupancy OUT/occupancy.npz --output DIR --from-trajectory OUT/trajectory_tum.txt \\
          [--radius 0.2] [--range 1.0] [--fov 90] [--stride 4] [--count 10] [--route-to 0] \\
-         [--cover [--cover-until 0.9]] [--tour [--tour-from X Y Z]]
+         [--cover [--cover-until 0.9]] [--tour [--tour-from X Y Z]] [--taut [--taut-span 256]]
 
 Under `python -m torch.distributed.run --nproc-per-node G -m pi3_slam_amd.cli ...` every stage shards over the G GPUs.
 """
@@ -271,6 +271,28 @@ EVAL_SWITCHES = (("--json", "print the result as one JSON line instead of the ta
                                     "exact point-to-triangle distance as target (default: by its vertices)"))
 
 
+# --taut on route, frontiers --route-to and views --route-to / --tour: the way pulled straight by line of sight
+TAUT_FLAG = ("--taut-span", dict(type=int, default=256, metavar="N",
+                                 help="with --taut: two consecutive vertices of the taut way lie at most N trace cells "
+                                      "apart, 1 .. 4096 (default 256: a first guess that no measurement has tuned)"))
+TAUT_SWITCH = ("--taut", "also every way pulled taut: the shortest polyline over cells of the way's own trace whose "
+                         "consecutive vertices see each other (route.json's and tour.json's taut_* keys, route_taut.ply)")
+
+
+def check_taut(a: argparse.Namespace, name: str, needs: str, given: bool) -> None:
+    if a.taut and not given:
+        raise SystemExit(f"{name}: --taut needs {needs}")
+    if a.taut and not 1 <= a.taut_span <= 4096:
+        raise SystemExit(f"{name}: --taut-span is 1 .. 4096 trace cells, got {a.taut_span}")
+
+
+def taut_text(taut) -> str:
+    text = f"; taut {taut.length_m:.3f} m over {len(taut.waypoints)} vertices"
+    if taut.min_clearance_m is not None:
+        text += f", clearance >= {taut.min_clearance_m:.3f} m"
+    return text
+
+
 # route: this build's own sub-command (grid_route.py) on the occupancy.npz of reconstruct or online
 ROUTE_FLAGS: Sequence[Tuple[str, Dict]] = (
     ("--occupancy", dict(REQ, help="occupancy.npz of `reconstruct` or `online` (--occupancy-cell)")),
@@ -282,9 +304,10 @@ ROUTE_FLAGS: Sequence[Tuple[str, Dict]] = (
                                                                                    "world point")),
     ("--radius", dict(type=float, default=0.0, help="the body's radius in metres: only cells with at least this "
                                                     "clearance are traversable (default 0: every free cell)")),
+    TAUT_FLAG,
     ("--device", dict(default="cuda")),
 )
-ROUTE_SWITCHES = (("--through-unknown", "unknown cells are traversable too, and no obstacles of the clearance "
+ROUTE_SWITCHES = (TAUT_SWITCH, ("--through-unknown", "unknown cells are traversable too, and no obstacles of the clearance "
                                         "(default: only verified free space, kept away from unknown space)"),
                   ("--approach-unknown", "only free cells are traversable, but --radius is kept from occupied cells alone: "
                                          "the body may come up to the edge of unknown space, as a goal of `frontiers` "
@@ -308,6 +331,7 @@ FRONTIER_FLAGS: Sequence[Tuple[str, Dict]] = (
                                                    "measured optimum)")),
     ("--route-to", dict(type=int, default=None, metavar="RANK", help="also the way to the goal of the cluster of this "
                                                                      "rank (0 = the nearest), as `route` writes it")),
+    TAUT_FLAG,
     ("--device", dict(default="cuda")),
 )
 
@@ -342,9 +366,11 @@ VIEW_FLAGS: Sequence[Tuple[str, Dict]] = (
     ("--tour-from", dict(type=float, nargs=3, default=None, metavar=("X", "Y", "Z"),
                          help="with --tour: the world point the tour leaves from (default: --start, or the last pose "
                               "of --from-trajectory)")),
+    TAUT_FLAG,
     ("--device", dict(default="cuda")),
 )
 VIEW_SWITCHES: Sequence[Tuple[str, str]] = (
+    TAUT_SWITCH,
     ("--cover", "pick the views one after the other, each by the unknown cells the kept ones do not see yet, so that "
                 "the plan adds up; a cell may be kept with several headings, and --separation is refused"),
     ("--tour", "also the order to visit the kept views in and the ways between them (tour.json, tour.npz, tour.ply): "
@@ -370,7 +396,7 @@ def build_parser() -> argparse.ArgumentParser:
                                   ("online", tuple(ONLINE_FLAGS) + ONLINE_DENSE_FLAGS + ONLINE_FOLLOW_FLAGS,
                                    ONLINE_SWITCHES),
                                   ("evaluate-map", EVAL_FLAGS, EVAL_SWITCHES), ("route", ROUTE_FLAGS, ROUTE_SWITCHES),
-                                  ("frontiers", FRONTIER_FLAGS, ()), ("views", VIEW_FLAGS, VIEW_SWITCHES)):
+                                  ("frontiers", FRONTIER_FLAGS, (TAUT_SWITCH,)), ("views", VIEW_FLAGS, VIEW_SWITCHES)):
         p = sub.add_parser(name)
         for flag, kw in flags:
             p.add_argument(flag, **kw)
@@ -569,15 +595,17 @@ def run_route(a: argparse.Namespace) -> None:
     from .grid_route import GridRouter, read_tum_positions
     if (a.start is None) == (a.from_trajectory is None):
         raise SystemExit("route: give --start X Y Z or --from-trajectory TRAJ.tum (one of them)")
+    check_taut(a, "route", "--goal X Y Z", a.goal is not None)
     try:
         router = GridRouter(a.radius, a.through_unknown, a.approach_unknown)
         grid = export.read_occupancy(a.occupancy)
         sources = [a.start] if a.start is not None else read_tum_positions(a.from_trajectory)
         field = router.field(grid, sources, a.device)
         route = router.path(field, a.goal) if a.goal is not None else None
+        taut = router.taut(field, route, a.taut_span) if a.taut and route is not None else None
     except (ValueError, OSError) as e:
         raise SystemExit(f"route: {e}")
-    export.write_route(field, route, a.output)
+    export.write_route(field, route, a.output, taut)
     c = field.counts
     text = (f"route: {c['traversable']} traversable cells, {c['reachable']} reachable from {c['sources_accepted']} "
             f"sources ({c['sources_blocked']} not traversable, {c['sources_outside']} outside) in {c['sweeps']} sweeps")
@@ -588,6 +616,8 @@ def run_route(a: argparse.Namespace) -> None:
             text += f"; {len(route.waypoints)} waypoints, {route.length_m:.3f} m"
             if route.min_clearance_m is not None:
                 text += f", clearance >= {route.min_clearance_m:.3f} m"
+            if taut is not None:
+                text += taut_text(taut)
     print(text)
 
 
@@ -599,6 +629,7 @@ def run_frontiers(a: argparse.Namespace) -> None:
         raise SystemExit("frontiers: give --start X Y Z or --from-trajectory TRAJ.tum, not both")
     if a.route_to is not None and a.start is None and a.from_trajectory is None:
         raise SystemExit("frontiers: --route-to needs a source: --start X Y Z or --from-trajectory TRAJ.tum")
+    check_taut(a, "frontiers", "--route-to RANK", a.route_to is not None)
     try:
         finder = FrontierFinder(a.radius, a.min_cells)
         grid = export.read_occupancy(a.occupancy)
@@ -609,11 +640,12 @@ def run_frontiers(a: argparse.Namespace) -> None:
             sources = read_tum_positions(a.from_trajectory)
         found = finder.find(grid, sources, a.device)
         route = found.route_to(a.route_to) if a.route_to is not None else None
+        taut = found.router.taut(found.field, route, a.taut_span) if a.taut and route is not None else None
     except (ValueError, OSError) as e:
         raise SystemExit(f"frontiers: {e}")
     export.write_frontiers(found, a.output)
     if route is not None:
-        export.write_route(found.field, route, a.output)
+        export.write_route(found.field, route, a.output, taut)
     c = found.counts
     text = (f"frontiers: {c['frontier_cells']} frontier cells in {c['clusters']} clusters ({c['clusters_dropped']} "
             f"dropped), {c['reachable_clusters']} reachable, {c['sweeps']} sweeps")
@@ -621,6 +653,8 @@ def run_frontiers(a: argparse.Namespace) -> None:
         best = found.clusters[0]
         text += f"; the best: {best.cells} cells"
         text += f" at {best.distance_m:.3f} m" if best.reachable else ", not reachable" if sources is not None else ""
+    if taut is not None:
+        text += f"; the way to cluster {a.route_to}: {route.length_m:.3f} m" + taut_text(taut)
     print(text)
 
 
@@ -636,6 +670,7 @@ def run_views(a: argparse.Namespace) -> None:
         raise SystemExit("views: --cover-until needs --cover")
     if a.tour_from is not None and not a.tour:
         raise SystemExit("views: --tour-from needs --tour")
+    check_taut(a, "views", "--route-to RANK or --tour", a.route_to is not None or a.tour)
     try:
         planner = ViewPlanner(a.radius, a.range, a.fov, a.stride, a.count, a.separation, a.max_distance, a.min_gain)
         grid = export.read_occupancy(a.occupancy)
@@ -645,12 +680,13 @@ def run_views(a: argparse.Namespace) -> None:
         else:
             found = planner.find(grid, sources, a.device)
         route = found.route_to(a.route_to) if a.route_to is not None else None
-        tour = found.tour(a.tour_from) if a.tour else None
+        taut = found.router.taut(found.field, route, a.taut_span) if a.taut and route is not None else None
+        tour = found.tour(a.tour_from, taut=a.taut, taut_span=a.taut_span) if a.tour else None
     except (ValueError, OSError) as e:
         raise SystemExit(f"views: {e}")
     export.write_views(found, a.output)
     if route is not None:
-        export.write_route(found.field, route, a.output)
+        export.write_route(found.field, route, a.output, taut)
     if tour is not None:
         export.write_tour(tour, a.output)
     c = found.counts
@@ -662,9 +698,14 @@ def run_views(a: argparse.Namespace) -> None:
     if found.mode == "cover":
         text += (f"; covered {c['covered']} of {c['seeable']} seeable unknown cells "
                  f"({100.0 * c['covered'] / max(c['seeable'], 1):.1f} %)")
+    if taut is not None:
+        text += f"; the way to view {a.route_to}: {route.length_m:.3f} m" + taut_text(taut)
     if tour is not None:
         text += (f"; tour: {len(tour.stops)} stops, {tour.distance_m:.2f} m ({tour.rank_order_length_m:.2f} m in rank "
                  f"order), {tour.method}")
+        if tour.taut_length_m is not None:
+            text += (f", taut {tour.taut_length_m:.2f} m of {tour.length_m:.2f} m over "
+                     f"{tour.taut_vertices} vertices")
         if tour.unreachable:
             text += f", {len(tour.unreachable)} stops not reachable from the start"
     print(text)

@@ -18,7 +18,8 @@ write_outputs writes them all, in that order.  A chunk needs dist.COLLECT_KEYS f
 
 write_tour writes the tour of a view set (view_tour.py): tour.json, tour.npz, tour.ply.
 Outside stage 2, for `cli route` (grid_route.py): read_occupancy reads occupancy.npz back, write_route writes route.npz
-(the distance field) and, with a goal, route.json and route.ply."""
+(the distance field) and, with a goal, route.json and route.ply; with a taut way route.json and the tour's
+files gain their taut_* keys and route_taut.ply is written, and without one every file is what it was."""
 from __future__ import annotations
 
 import json
@@ -243,11 +244,29 @@ def read_occupancy(path: str):
 ROUTE_COLOR = (255, 64, 0)          # route.ply's waypoints
 
 
-def write_route(field, route, out_dir: str) -> None:
+TAUT_COLOR = (0, 200, 255)          # route_taut.ply's samples
+
+
+def sample_polyline(vertices: np.ndarray, step: float) -> np.ndarray:
+    """Points along the polyline f64 (V,3), `step` apart on every segment from its first vertex on, and the last vertex:
+    a line to look at among points."""
+    v = np.asarray(vertices, np.float64).reshape(-1, 3)
+    out = []
+    for p, q in zip(v[:-1], v[1:]):
+        n = max(int(np.ceil(np.linalg.norm(q - p) / float(step))), 1)
+        out.append(p[None, :] + (np.arange(n, dtype=np.float64) / n)[:, None] * (q - p)[None, :])
+    out.append(v[-1:])
+    return np.concatenate(out) if len(v) else np.zeros((0, 3), np.float64)
+
+
+def write_route(field, route, out_dir: str, taut=None) -> None:
     """A grid_route.RouteField -> <out_dir>/route.npz: distance f32 (nz,ny,nx) in metres (inf when unreachable), cost
     u32 (12 per cell edge, 0xFFFFFFFF when unreachable), index_origin i64 (3,), origin f64 (3,), cell f64, settings and
     counts as JSON strings.  With a grid_route.Route also route.json (waypoints source -> goal, cost, length_m,
-    min_clearance_m, settings) and route.ply, the waypoints as coloured points for viewing next to dense_points.ply."""
+    min_clearance_m, settings) and route.ply, the waypoints as coloured points for viewing next to dense_points.ply.
+    With the route's grid_route.TautRoute route.json gains taut_waypoints, taut_indices (into waypoints), taut_length_m,
+    taut_min_clearance_m and taut_span, and route_taut.ply holds the taut polyline sampled once per cell length; without
+    it every file is what it is without this argument."""
     os.makedirs(out_dir, exist_ok=True)
     with open(os.path.join(out_dir, "route.npz"), "wb") as f:
         np.savez_compressed(f, distance=np.asarray(field.distance, np.float32), cost=np.asarray(field.cost, np.uint32),
@@ -263,11 +282,22 @@ def write_route(field, route, out_dir: str) -> None:
                   "length_m": float(route.length_m),
                   "min_clearance_m": None if clear is None else (float(clear) if np.isfinite(clear) else "inf"),
                   "settings": route.settings}
+        if taut is not None:
+            clear = taut.min_clearance_m
+            record.update(taut_waypoints=[[float(v) for v in p] for p in taut.waypoints],
+                          taut_indices=[int(i) for i in taut.indices], taut_length_m=float(taut.length_m),
+                          taut_min_clearance_m=None if clear is None else (float(clear) if np.isfinite(clear) else "inf"),
+                          taut_span=int(taut.span))
         with open(os.path.join(out_dir, "route.json"), "w") as f:
             json.dump(record, f, indent=1)
         write_ply(route.waypoints, np.tile(np.array(ROUTE_COLOR, np.uint8), (len(route.waypoints), 1)),
                   os.path.join(out_dir, "route.ply"))
         text += f", the route of {len(route.waypoints)} waypoints to route.json and route.ply"
+        if taut is not None:
+            line = sample_polyline(taut.waypoints, float(field.cell))
+            write_ply(line, np.tile(np.array(TAUT_COLOR, np.uint8), (len(line), 1)),
+                      os.path.join(out_dir, "route_taut.ply"))
+            text += f", the taut way of {len(taut.waypoints)} vertices to route_taut.ply"
     print(text)
 
 
@@ -337,7 +367,10 @@ def write_tour(tour, out_dir: str) -> int:
     the views taken there), tour.npz (order i64: the stops' numbers in visiting order; matrix i64 (n + 1, n + 1) and
     cells i64 (n + 1,): node 0 the start, node s + 1 the stop numbered s; waypoints f64 (P,3), waypoint_cells i64 (P,)
     and offsets i64 (legs + 1,): leg i is rows offsets[i] .. offsets[i + 1]) and tour.ply: the legs' waypoints as points
-    coloured from frontiers.ply's palette by leg, for viewing next to views.ply.  Returns the number of stops."""
+    coloured from frontiers.ply's palette by leg, for viewing next to views.ply.  A tour with taut legs adds
+    taut_length_m (in total and per stop, there with taut_min_clearance_m), taut_span and taut_vertices to tour.json and
+    taut_waypoints f64 (V,3), taut_waypoint_cells i64 (V,) and taut_offsets i64 (legs + 1,) to tour.npz; every other key
+    and file is what it is without them.  Returns the number of stops."""
     os.makedirs(out_dir, exist_ok=True)
     record = {"settings": tour.settings, "counts": tour.counts, "method": tour.method, "cost": int(tour.cost),
               "distance_m": float(tour.distance_m), "length_m": float(tour.length_m),
@@ -346,6 +379,15 @@ def write_tour(tour, out_dir: str) -> int:
               "start": {"cell": int(tour.start_cell), "position": [float(v) for v in tour.start]},
               "order": [int(s) for s in tour.order], "unreachable": [int(s) for s in tour.unreachable],
               "stops": [s.record() for s in tour.stops]}
+    taut = {}
+    if tour.taut_length_m is not None:                          # a stop's record carries its own taut_length_m
+        record.update(taut_length_m=float(tour.taut_length_m), taut_span=int(tour.taut_span),
+                      taut_vertices=int(tour.taut_vertices))
+        t = len(tour.taut_leg_cells)
+        taut = dict(
+            taut_waypoints=np.concatenate(tour.taut_leg_waypoints).reshape(-1, 3) if t else np.zeros((0, 3), np.float64),
+            taut_waypoint_cells=np.concatenate(tour.taut_leg_cells).astype(np.int64) if t else np.zeros(0, np.int64),
+            taut_offsets=np.concatenate([[0], np.cumsum([len(c) for c in tour.taut_leg_cells])]).astype(np.int64))
     with open(os.path.join(out_dir, "tour.json"), "w") as f:
         json.dump(record, f, indent=1)
     legs = len(tour.leg_cells)
@@ -355,7 +397,7 @@ def write_tour(tour, out_dir: str) -> int:
     with open(os.path.join(out_dir, "tour.npz"), "wb") as f:
         np.savez_compressed(f, order=np.asarray(tour.order, np.int64), matrix=np.asarray(tour.matrix, np.int64),
                             cells=np.asarray(tour.cells, np.int64), waypoints=way, waypoint_cells=way_cells,
-                            offsets=offsets)
+                            offsets=offsets, **taut)
     colors = np.concatenate([np.tile(np.array(FRONTIER_PALETTE[i % len(FRONTIER_PALETTE)], np.uint8), (len(c), 1))
                              for i, c in enumerate(tour.leg_cells)]) if legs else np.zeros((0, 3), np.uint8)
     write_ply(way, colors, os.path.join(out_dir, "tour.ply"))

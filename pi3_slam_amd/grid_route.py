@@ -9,13 +9,21 @@ moves to the neighbours cost 12, 17, 21 (12 times 1, sqrt 2, sqrt 3, rounded: +0
 every cell of the 2, 4 or 8 the move passes between must be traversable.  distance = cell cost / 12 metres.
 
 Limitations: a chamfer metric, not the Euclidean one (a straight way at an odd angle is measured up to a few per cent
-long); ways run through cell centres and are not smoothed; a start or a goal on a blocked cell is refused, not
-snapped to the nearest traversable one; "reachable" inherits the grid's "free means seen through"."""
+long); ways run through cell centres (GridRouter.taut pulls one straight between the cells it passes); a
+start or a goal on a blocked cell is refused, not snapped to the nearest traversable one; "reachable" inherits the
+grid's "free means seen through".
+
+Line of sight and the taut way (csrc/grid_sight.hip; reproduced by tests/grid_sight_ref.py): cell a sees cell b when
+every cell whose closed cube meets the segment between the two centres is traversable.  GridRouter.taut keeps of a
+trace the subsequence of cells, first and last included, whose polyline is shortest among those whose consecutive
+vertices lie at most `span` trace cells apart and see each other (pull_taut: a dynamic programme in f64, equal lengths
+take the smallest index).  Vertices are trace cells only: shortcutting, not an any-angle search; the default span of
+256 is a starting point, not a measured optimum."""
 from __future__ import annotations
 
 import math
 from dataclasses import dataclass, field as dc_field
-from typing import Dict, Optional
+from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -54,7 +62,8 @@ class RouteField:
     clearance: Optional[np.ndarray] = None      # f32: metres to the nearest obstacle, inf beyond R (with a radius only)
     counts: Dict[str, int] = dc_field(default_factory=dict)
     settings: Dict = dc_field(default_factory=dict)
-    device_arrays: Optional[Dict[str, torch.Tensor]] = dc_field(default=None, repr=False)   # walk, cost for path()
+    # walk, cost for path(); d2 (the clearance field, None without a radius) for taut()
+    device_arrays: Optional[Dict[str, torch.Tensor]] = dc_field(default=None, repr=False)
 
     @property
     def origin(self) -> np.ndarray:
@@ -71,6 +80,124 @@ class Route:
     length_m: float                             # the sum of the Euclidean step lengths
     min_clearance_m: Optional[float] = None     # along the way, with a radius (inf: nothing within R cells)
     settings: Dict = dc_field(default_factory=dict)
+
+
+@dataclass
+class TautRoute:
+    """GridRouter.taut's result: the route pulled straight between cells of its own trace."""
+    waypoints: np.ndarray                       # f64 (V,3): the centres of the vertices, from the source to the goal
+    cells: np.ndarray                           # i64 (V,): their linear indices
+    indices: np.ndarray                         # i64 (V,): their places in the route's trace, 0 and L - 1 included
+    length_m: float                             # the polyline's length: <= the route's length_m
+    min_clearance_m: Optional[float] = None     # over every cell the polyline touches, with a radius (inf: as Route)
+    span: int = 256                             # two consecutive vertices lie at most this many trace cells apart
+    settings: Dict = dc_field(default_factory=dict)
+
+
+TAUT_SPAN = 256             # a starting point, not a measured optimum (DESIGN §7l)
+
+
+def check_span(span) -> int:
+    span = int(span)
+    if not 1 <= span <= ops.SIGHT_MAX_SPAN:
+        raise ValueError(f"the span of a taut way is 1 .. {ops.SIGHT_MAX_SPAN} trace cells, got {span}")
+    return span
+
+
+def pull_taut(vis_words, cells, offsets, span: int, dims) -> List[Tuple[np.ndarray, float]]:
+    """The taut ways of several traces at once; pure numpy.  cells i64 (P,): the traces one after the other, trace l =
+    cells[offsets[l] : offsets[l + 1]]; vis_words (P, ceil(span / 64)) 64-bit words as ops.grid_route_sight_paths
+    writes them; dims: the grid's (nz, ny, nx).  -> per trace (the indices of the vertices into the trace, i64, first
+    and last included; the length in cells, f64).  best[0] = 0, best[j] = min over i of best[i] + sqrt(d2_ij) with
+    0 < j - i <= span and bit j - i - 1 of row i set; d2_ij is the exact integer squared offset, so a term is one square
+    root and one addition and no sum is reordered.  Equal values take the smallest i.  An empty trace gives no vertex
+    and length 0; a cell that no earlier cell sees raises a ValueError (two neighbours of a trace always see each
+    other)."""
+    nz, ny, nx = (int(v) for v in dims)
+    span = int(span)
+    cells = np.asarray(cells, np.int64).reshape(-1)
+    offsets = np.asarray(offsets, np.int64).reshape(-1)
+    P, W = len(cells), (span + 63) // 64
+    words = np.ascontiguousarray(np.asarray(vis_words).reshape(P, W)).view(np.uint64).astype("<u8")
+    xyz_all = np.stack([cells % nx, (cells // nx) % ny, cells // (nx * ny)], 1)
+    out = []
+    for l in range(len(offsets) - 1):
+        lo, hi = int(offsets[l]), int(offsets[l + 1])
+        L = hi - lo
+        if L <= 0:
+            out.append((np.zeros(0, np.int64), 0.0))
+            continue
+        bits = np.unpackbits(words[lo:hi].view(np.uint8).reshape(L, W * 8), axis=1, bitorder="little")
+        xyz = xyz_all[lo:hi]
+        best = np.zeros(L, np.float64)
+        back = np.full(L, -1, np.int64)
+        for j in range(1, L):
+            i = np.arange(max(0, j - span), j)
+            i = i[bits[i, j - i - 1] != 0]
+            if not len(i):
+                raise ValueError(f"trace {l}: cell {j} is seen by none of the {min(span, j)} cells before it")
+            d = xyz[i] - xyz[j]
+            cand = best[i] + np.sqrt((d * d).sum(1).astype(np.float64))
+            k = int(np.argmin(cand))                            # the first of equal values: the smallest i
+            best[j], back[j] = cand[k], i[k]
+        idx = [L - 1]
+        while idx[-1] > 0:
+            idx.append(int(back[idx[-1]]))
+        out.append((np.asarray(idx[::-1], np.int64), float(best[L - 1])))
+    return out
+
+
+def taut_legs(walk: torch.Tensor, d2: Optional[torch.Tensor], legs: List[np.ndarray], span: int):
+    """Several traces (i64 linear indices each) pulled taut together: one ops.grid_route_sight_paths launch over all of
+    them, pull_taut, and one ops.grid_route_sight_pairs launch over the chosen segments, which must all see: a wrong
+    way raises a RuntimeError.  -> per trace (indices i64, length in cells, the smallest d2 over every touched cell or
+    None without d2)."""
+    span = check_span(span)
+    dev = walk.device
+    shape = tuple(int(v) for v in walk.shape)
+    offsets = np.concatenate([[0], np.cumsum([len(c) for c in legs])]).astype(np.int64)
+    P = int(offsets[-1])
+    if P == 0:
+        return [(np.zeros(0, np.int64), 0.0, None) for _ in legs]
+    cells = np.concatenate([np.asarray(c, np.int64) for c in legs])
+    reach = max(1, min(span, max(len(c) for c in legs) - 1))    # no partner lies further along any trace
+    vis = torch.empty((P, ops.grid_sight_words(reach)), dtype=torch.int64, device=dev)
+    ops.grid_route_sight_paths(walk, torch.from_numpy(cells).to(dev), torch.from_numpy(offsets).to(dev), reach, vis)
+    pulled = pull_taut(vis.cpu().numpy(), cells, offsets, reach, shape)
+    a = np.concatenate([cells[offsets[l] + idx[:-1]] for l, (idx, _) in enumerate(pulled)])
+    b = np.concatenate([cells[offsets[l] + idx[1:]] for l, (idx, _) in enumerate(pulled)])
+    N = len(a)
+    sees = torch.empty(N, dtype=torch.uint8, device=dev)
+    touched = torch.empty(N, dtype=torch.int32, device=dev)
+    low = torch.empty(N, dtype=torch.int16, device=dev)
+    ops.grid_route_sight_pairs(walk, d2, torch.from_numpy(a).to(dev), torch.from_numpy(b).to(dev), sees, touched, low)
+    sees_np, low_np = sees.cpu().numpy(), low.cpu().numpy().view(np.uint16)
+    if not sees_np.all():
+        k = int(np.flatnonzero(sees_np == 0)[0])
+        raise RuntimeError(f"a taut segment from cell {int(a[k])} to cell {int(b[k])} does not see: the way is refused")
+    out, at = [], 0
+    for l, (idx, length) in enumerate(pulled):
+        n = max(len(idx) - 1, 0)
+        seg = low_np[at:at + n]
+        at += n
+        if d2 is None:
+            clear = None
+        elif n:
+            clear = int(seg.min())
+        else:                                                   # a trace of one cell touches that cell
+            c = int(legs[l][0])
+            clear = int(d2.reshape(-1)[c:c + 1].cpu().numpy().view(np.uint16)[0])
+        out.append((idx, length, clear))
+    return out
+
+
+def clearance_m(cell: float, d2: Optional[int]) -> Optional[float]:
+    """A d2 of the clearance field in metres, inf for its far mark (RouteField.clearance's rule, in f32)."""
+    if d2 is None:
+        return None
+    if d2 == ops.EDT_FAR:
+        return float("inf")
+    return float(np.float32(float(cell) * np.sqrt(np.float64(d2))))
 
 
 @dataclass
@@ -184,7 +311,7 @@ class GridRouter:
         counts["reachable"] = int(reach.sum())
         out.cost = cost
         out.distance = np.where(reach, float(grid.cell) * cost.astype(np.float64) / 12.0, np.inf).astype(np.float32)
-        out.device_arrays = {"walk": walk, "cost": dist}
+        out.device_arrays = {"walk": walk, "cost": dist, "d2": d2}
         return out
 
     def relax(self, walk: torch.Tensor, dist: torch.Tensor, traversable: int) -> int:
@@ -228,3 +355,46 @@ class GridRouter:
             clear = float(field.clearance.reshape(-1)[cells].min())
         return Route(way, cells, d_goal, float(field.cell) * float(np.sqrt(steps.astype(np.float64)).sum()), clear,
                      dict(field.settings))
+
+    @staticmethod
+    def _device_walk(field: RouteField):
+        arrays = field.device_arrays
+        if arrays is None:
+            raise ValueError("the field carries no device arrays: take it from GridRouter.field")
+        return arrays["walk"], arrays.get("d2")
+
+    def sees(self, field: RouteField, a_xyz, b_xyz) -> bool:
+        """Can the body go straight from the centre of the cell of the world point a_xyz to that of b_xyz: is every
+        cell the segment touches traversable (csrc/grid_sight.hip)?  An end outside the grid raises a ValueError, as
+        path's goal does; an end on a cell that is not traversable sees nothing."""
+        walk, _ = self._device_walk(field)
+        ends = []
+        for name, p in (("start", a_xyz), ("goal", b_xyz)):
+            c = int(self.linear(self.world_cells(p, field), field.walk.shape)[0])
+            if c < 0:
+                raise ValueError(f"the {name} {np.asarray(p, np.float64).reshape(-1).tolist()} lies outside the grid")
+            ends.append(c)
+        dev = walk.device
+        sees = torch.empty(1, dtype=torch.uint8, device=dev)
+        ops.grid_route_sight_pairs(walk, None, torch.tensor(ends[:1], dtype=torch.int64, device=dev),
+                                   torch.tensor(ends[1:], dtype=torch.int64, device=dev), sees,
+                                   torch.empty(1, dtype=torch.int32, device=dev),
+                                   torch.empty(1, dtype=torch.int16, device=dev))
+        return bool(sees.item())
+
+    def taut(self, field: RouteField, route: Route, span: int = TAUT_SPAN) -> TautRoute:
+        """The route pulled taut (module text): the shortest polyline over cells of the route's own trace whose
+        consecutive vertices lie at most `span` trace cells apart (1 .. ops.SIGHT_MAX_SPAN; the default is a starting
+        point, not a measured optimum) and see each other.  Every chosen segment is tested again on the device and
+        min_clearance_m is taken over every cell the polyline touches; a segment that does not see raises a
+        RuntimeError."""
+        span = check_span(span)
+        walk, d2 = self._device_walk(field)
+        cells = np.asarray(route.cells, np.int64)
+        idx, length, low = taut_legs(walk, d2, [cells], span)[0]
+        nz, ny, nx = field.walk.shape
+        kept = cells[idx]
+        xyz = np.stack([kept % nx, (kept // nx) % ny, kept // (nx * ny)], 1)
+        way = float(field.cell) * ((xyz + np.asarray(field.index_origin, np.int64)[None, :]).astype(np.float64) + 0.5)
+        return TautRoute(way, kept, idx, float(field.cell) * length, clearance_m(field.cell, low), span,
+                         dict(field.settings, taut_span=span))

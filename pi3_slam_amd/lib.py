@@ -106,6 +106,8 @@ SIGNATURES = {
     "pi3_grid_route_fields_init": [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp],
     "pi3_grid_route_sweep_many": [_vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _vp, _vp],
     "pi3_grid_route_trace_many": [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp],
+    "pi3_grid_route_sight_paths": [_vp, _i, _i, _i, _vp, _l, _vp, _i, _i, _vp, _vp],
+    "pi3_grid_route_sight_pairs": [_vp, _vp, _i, _i, _i, _vp, _vp, _l, _vp, _vp, _vp, _vp],
     "pi3_grid_frontier_mark": [_vp, _i, _i, _i, _vp, _vp, _vp],
     "pi3_grid_frontier_sweep": [_i, _i, _i, _vp, _vp, _vp],
     "pi3_grid_frontier_roots": [_vp, _i, _i, _i, _vp, _l, _vp, _vp],

@@ -1197,6 +1197,61 @@ def grid_route_trace_many(walk: torch.Tensor, dist: torch.Tensor, field_of: torc
     _L.check(rc, "pi3_grid_route_trace_many")
 
 
+SIGHT_MAX_SPAN = 4096
+
+
+def grid_sight_words(span: int) -> int:
+    """The 64-bit words per row of grid_route_sight_paths' vis."""
+    return (int(span) + 63) // 64
+
+
+def grid_route_sight_paths(walk: torch.Tensor, cells: torch.Tensor, offsets: torch.Tensor, span: int,
+                           vis: torch.Tensor) -> None:
+    """Line of sight along ways (csrc/grid_sight.hip): way l is cells[offsets[l] : offsets[l + 1]] (cells int64 (P,)
+    linear indices, offsets int64 (legs + 1,) ascending from 0 to P).  vis int64 (P, grid_sight_words(span)) (the uint64
+    values): bit k of row p is set when p and p + 1 + k lie in the same way, k < span, and cells[p] sees cells[p + 1 + k]
+    over walk uint8 (nz,ny,nx); every other bit is written 0.  span outside 1 .. SIGHT_MAX_SPAN is refused by the
+    library.  All on the device."""
+    lib = _L.load()
+    nx, ny, nz = _grid_state(walk)
+    dev = walk.device
+    assert 0 < walk.numel() <= ROUTE_MAX_CELLS, f"{walk.numel()} cells: 1 .. 2^27"
+    assert cells.dtype == torch.int64 and cells.is_contiguous() and cells.ndim == 1 and cells.device == dev
+    assert offsets.dtype == torch.int64 and offsets.is_contiguous() and offsets.ndim == 1 and offsets.numel() >= 1
+    assert offsets.device == dev
+    P, legs = int(cells.numel()), int(offsets.numel()) - 1
+    assert vis.dtype == torch.int64 and vis.is_contiguous() and vis.device == dev
+    if 1 <= int(span) <= SIGHT_MAX_SPAN:                        # any other span launches nothing: the library says why
+        W = grid_sight_words(span)
+        assert tuple(vis.shape) == (P, W), f"vis {tuple(vis.shape)}: ({P}, {W})"
+    some = P > 0 and legs > 0
+    rc = lib.pi3_grid_route_sight_paths(walk.data_ptr(), nx, ny, nz, cells.data_ptr() if some else None, P,
+                                        offsets.data_ptr() if some else None, legs, int(span),
+                                        vis.data_ptr() if some else None, _L.stream_ptr())
+    _L.check(rc, "pi3_grid_route_sight_paths")
+
+
+def grid_route_sight_pairs(walk: torch.Tensor, d2: Optional[torch.Tensor], a: torch.Tensor, b: torch.Tensor,
+                           sees: torch.Tensor, touched: torch.Tensor, min_d2: torch.Tensor) -> None:
+    """Line of sight between the cells a[i] and b[i] (int64 (N,) linear indices) over walk uint8 (nz,ny,nx): sees uint8
+    (N,) = 1 when every cell the segment between the two centres touches is traversable, touched int32 (N,) = those
+    cells' number (the whole segment is walked), min_d2 int16 (N,) (the uint16 values) = the smallest entry of d2 int16
+    (nz,ny,nx) (grid_edt's field) over them, EDT_FAR without d2.  An end outside the grid gives 0, 0, EDT_FAR."""
+    lib = _L.load()
+    nx, ny, nz = _grid_state(walk)
+    dev = walk.device
+    assert 0 < walk.numel() <= ROUTE_MAX_CELLS, f"{walk.numel()} cells: 1 .. 2^27"
+    if d2 is not None:
+        assert d2.dtype == torch.int16 and d2.is_contiguous() and d2.shape == walk.shape and d2.device == dev
+    N = int(a.numel())
+    for t, dt in ((a, torch.int64), (b, torch.int64), (sees, torch.uint8), (touched, torch.int32), (min_d2, torch.int16)):
+        assert t.dtype == dt and t.is_contiguous() and tuple(t.shape) == (N,) and t.device == dev
+    p = (lambda t: t.data_ptr() if N else None)
+    rc = lib.pi3_grid_route_sight_pairs(walk.data_ptr(), _L.ptr(d2), nx, ny, nz, p(a), p(b), N, p(sees), p(touched),
+                                        p(min_d2), _L.stream_ptr())
+    _L.check(rc, "pi3_grid_route_sight_pairs")
+
+
 # ---- frontiers of the occupancy grid (csrc/grid_frontier.hip)
 FRONTIER_NONE = 0xFFFFFFFF              # the label of a cell that is no frontier cell
 FRONTIER_MARK_COUNTERS = ("frontier_cells", "unknown_faces")

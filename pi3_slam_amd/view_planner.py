@@ -103,7 +103,8 @@ class ViewSet:
         return route
 
     def tour(self, start_xyz=None, **kwargs):
-        """The order to visit the views in and the ways between them (view_tour.plan_tour)."""
+        """The order to visit the views in and the ways between them (view_tour.plan_tour; taut=True also pulls every
+        leg straight, taut_span its reach along the trace)."""
         from .view_tour import plan_tour
         return plan_tour(self, start_xyz, **kwargs)
 

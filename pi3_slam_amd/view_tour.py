@@ -9,6 +9,8 @@ that cannot be reached from the start are left out and counted.  order_stops fin
 every remaining stop: exact (dynamic programme over subsets, the lexicographically smallest of the cheapest orders) up
 to 12 stops, nearest neighbour and 2-opt above.  The legs are traced together (pi3_grid_route_trace_many), each over
 the field of the stop it leaves, and the views are marked again in tour order to say what each adds on the way.
+With taut=True every leg is also pulled straight between cells of its own trace (grid_route.taut_legs): one
+line-of-sight launch over all legs and one over the chosen segments; the order and the matrix are untouched.
 
 Limitations: the chamfer metric of the router; an open path, nothing weighs the way back; above 12 stops 2-opt ends in
 a local optimum; the order minimises the way alone, a view's gain is not traded against it; all n + 1 fields are held
@@ -23,7 +25,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .grid_route import GridRouter
+from .grid_route import TAUT_SPAN, GridRouter, check_span, clearance_m, taut_legs
 
 FAR = ops.ROUTE_FAR
 EXACT_MAX = 12              # stops up to which the order is exact: 2^12 x 12 states
@@ -182,8 +184,18 @@ class TourStop:
     min_clearance_m: Optional[float]            # the smallest clearance on the leg, with a radius
     tour_new: List[int]                         # per view: the unknown cells it adds, seen in tour order
     tour_covered: List[int]                     # per view: the running total after it
+    taut_length_m: Optional[float] = None       # with taut: the leg pulled straight, <= length_m
+    taut_min_clearance_m: Optional[float] = None    # over every cell the taut leg touches, with a radius
 
     def record(self) -> Dict:
+        out = self._record()
+        if self.taut_length_m is not None:
+            clear = self.taut_min_clearance_m
+            out["taut_length_m"] = self.taut_length_m
+            out["taut_min_clearance_m"] = None if clear is None else (float(clear) if np.isfinite(clear) else "inf")
+        return out
+
+    def _record(self) -> Dict:
         clear = self.min_clearance_m
         return {"number": self.number, "cell": self.cell, "position": [float(v) for v in self.position],
                 "views": [{"rank": r, "tour_new": n, "tour_covered": c}
@@ -213,6 +225,16 @@ class Tour:
     covered: int                                # the unknown cells the visited views see together
     counts: Dict = dc_field(default_factory=dict)
     settings: Dict = dc_field(default_factory=dict)
+    taut_leg_cells: Optional[List[np.ndarray]] = None       # with taut, per leg: i64 the cells of the taut leg's vertices
+    taut_leg_waypoints: Optional[List[np.ndarray]] = None   # per leg: f64 (V,3) their centres
+    taut_leg_indices: Optional[List[np.ndarray]] = None     # per leg: i64 their places in leg_cells
+    taut_length_m: Optional[float] = None                   # the sum over the legs: <= length_m
+    taut_span: Optional[int] = None                         # counts and settings are what they are without taut
+
+    @property
+    def taut_vertices(self) -> Optional[int]:
+        """The vertices of all taut legs together (a stop between two legs counts for both)."""
+        return None if self.taut_leg_cells is None else int(sum(len(c) for c in self.taut_leg_cells))
 
     @property
     def rank_order_length_m(self) -> float:
@@ -254,11 +276,14 @@ def _centres(cells: np.ndarray, f) -> Tuple[np.ndarray, np.ndarray]:
 
 
 def plan_tour(vset, start_xyz=None, device=None, max_field_bytes: int = 2 << 30, exact_max: int = EXACT_MAX,
-              group: int = SWEEP_GROUP) -> Tour:
+              group: int = SWEEP_GROUP, taut: bool = False, taut_span: int = TAUT_SPAN) -> Tour:
     """The tour of a ViewSet's views (module text).  start_xyz: the world point the tour leaves from; default the set's
-    single source, of several the last.  device: default the device of the set's field.  Raises a ValueError for a
-    start outside the grid or on a cell that is not traversable, and when the n + 1 fields need more than
-    max_field_bytes."""
+    single source, of several the last.  device: default the device of the set's field.  taut: every leg is also pulled
+    taut over at most taut_span trace cells per segment (the default is a starting point, not a measured optimum); the
+    order, the matrix and every other field stay what they are without it.  Raises a ValueError for a start outside
+    the grid or on a cell that is not traversable, and when the n + 1 fields need more than max_field_bytes."""
+    if taut:
+        taut_span = check_span(taut_span)
     f = vset.field
     if f is None or f.device_arrays is None:
         raise ValueError("the view set carries no route field: take it from ViewPlanner.find or .cover")
@@ -342,6 +367,19 @@ def plan_tour(vset, start_xyz=None, device=None, max_field_bytes: int = 2 << 30,
         stops.append(TourStop(b - 1, int(cells_np[b]), way[-1].copy(), list(ranks[b - 1]), cost, running, length_m,
                               clear, [], []))
 
+    pulled = {}
+    if taut:
+        # every leg through one sight_paths launch and one sight_pairs launch
+        res = taut_legs(walk, f.device_arrays.get("d2"), legs, taut_span)
+        t_cells, t_ways = [], []
+        for stop, cells, (idx, length, low) in zip(stops, legs, res):
+            stop.taut_length_m = float(f.cell) * length
+            stop.taut_min_clearance_m = clearance_m(f.cell, low)
+            t_cells.append(cells[idx])
+            t_ways.append(_centres(cells[idx], f)[1])
+        pulled = dict(taut_leg_cells=t_cells, taut_leg_waypoints=t_ways, taut_leg_indices=[r[0] for r in res],
+                      taut_length_m=float(sum(s.taut_length_m for s in stops)), taut_span=taut_span)
+
     # what the tour sees in its own order: the views marked again into a fresh mask
     covered = 0
     if stops:
@@ -368,4 +406,4 @@ def plan_tour(vset, start_xyz=None, device=None, max_field_bytes: int = 2 << 30,
     _, start_xyz_c = _centres(np.asarray([start]), f)
     return Tour(stops, [s.number for s in stops], start, start_xyz_c[0], D_all, cells_np, legs, leg_ways, order.cost,
                 total_m, order.rank_order_cost, order.nn_cost, order.moves, order.method, [s - 1 for s in left_out],
-                covered, counts, settings)
+                covered, counts, settings, **pulled)

@@ -703,6 +703,24 @@ int pi3_grid_view_gain_unseen(const unsigned char* state, int nx, int ny, int nz
 int pi3_grid_view_mark(const unsigned char* state, int nx, int ny, int nz, unsigned* seen, const long* cells,
                        const int* heading_of, long V, int range, const int* headings, int H, long cos2_num,
                        long cos2_den, short* owner, int tag, unsigned long long* counters, void* stream);
+/* Views that see farther (csrc/grid_view_far.hip): the three ray entry points with range in 1..64.  Every
+ * argument, rule, output and counter is its namesake's, and for range <= 32 so is every byte.  A workgroup takes one
+ * octant of a pose (a ray never leaves the closed octant of its target; a target o belongs to the octant that is
+ * positive on axis a when o_a >= 0) and adds its counts to gain, visible and the counters with integer atomics, which
+ * the call zeroes first on the stream; best is written by a finishing kernel.  One more argument check: the cone
+ * test's (o.a)^2 den is formed in 64 bits, so a call with range^2 * max_h |a_h|^2 * den >= 2^63 is refused (|a|^2 <= 3
+ * and den = 2^20 are far inside).  Bad arguments launch nothing and leave the outputs untouched.  No allocation, no
+ * synchronisation. */
+int pi3_grid_view_gain_far(const unsigned char* state, int nx, int ny, int nz, const long* candidates, long V, int range,
+                           const int* headings, int H, long cos2_num, long cos2_den, unsigned* gain, unsigned* visible,
+                           int* best, unsigned long long* counters, void* stream);
+int pi3_grid_view_gain_unseen_far(const unsigned char* state, int nx, int ny, int nz, const unsigned* seen,
+                                  const long* candidates, long V, int range, const int* headings, int H, long cos2_num,
+                                  long cos2_den, unsigned* gain, unsigned* visible, int* best,
+                                  unsigned long long* counters, void* stream);
+int pi3_grid_view_mark_far(const unsigned char* state, int nx, int ny, int nz, unsigned* seen, const long* cells,
+                           const int* heading_of, long V, int range, const int* headings, int H, long cos2_num,
+                           long cos2_den, short* owner, int tag, unsigned long long* counters, void* stream);
 
 /* ---- nearest neighbours between two point clouds (csrc/cloud_nn.hip): an exact radius-bounded search through a
  * uniform grid of cells, for scoring a map against a reference cloud (map_eval.py).  The grid is a hash table of cells

@@ -13,7 +13,7 @@
   python -m pi3_slam_amd.cli frontiers --occupancy OUT/occupancy.npz --output DIR --from-trajectory OUT/trajectory_tum.txt \\
          [--radius 0.2] [--min-cells 20] [--route-to 0 [--taut]]
   python -m pi3_slam_amd.cli views --occupancy OUT/occupancy.npz --output DIR --from-trajectory OUT/trajectory_tum.txt \\
-         [--radius 0.2] [--range 1.0] [--fov 90] [--stride 4] [--count 10] [--route-to 0] \\
+         [--radius 0.2] [--range 1.0 [--far]] [--fov 90] [--stride 4] [--count 10] [--route-to 0] \\
          [--cover [--cover-until 0.9]] [--tour [--tour-from X Y Z]] [--taut [--taut-span 256]]
 
 Under `python -m torch.distributed.run --nproc-per-node G -m pi3_slam_amd.cli ...` every stage shards over the G GPUs.
@@ -346,7 +346,7 @@ VIEW_FLAGS: Sequence[Tuple[str, Dict]] = (
                                                   "(poses on cells that are not traversable are skipped and counted)")),
     ("--radius", dict(type=float, default=0.0, help="the body's radius in metres for the route, kept from occupied "
                                                     "cells only (default 0: every free cell)")),
-    ("--range", dict(type=float, default=1.0, help="how far a view sees, in metres; at most 32 occupancy cells "
+    ("--range", dict(type=float, default=1.0, help="how far a view sees, in metres; at most 32 occupancy cells, 64 with --far "
                                                    "(default 1.0: a starting point, not a measured optimum)")),
     ("--fov", dict(type=float, default=90.0, help="the full opening angle of the viewing cone in degrees, in (0, 180] "
                                                   "(default 90: a starting point, not a measured optimum)")),
@@ -375,6 +375,8 @@ VIEW_SWITCHES: Sequence[Tuple[str, str]] = (
                 "the plan adds up; a cell may be kept with several headings, and --separation is refused"),
     ("--tour", "also the order to visit the kept views in and the ways between them (tour.json, tour.npz, tour.ply): "
                "the shortest open path from the start, exact up to 12 stops, nearest neighbour and 2-opt above"),
+    ("--far", "let --range reach 64 occupancy cells instead of 32: the rays are cast octant by octant around the pose, by "
+              "the same rules; twice the range is roughly eight times the rays per pose, so widen --stride with it"),
 )
 
 
@@ -672,7 +674,8 @@ def run_views(a: argparse.Namespace) -> None:
         raise SystemExit("views: --tour-from needs --tour")
     check_taut(a, "views", "--route-to RANK or --tour", a.route_to is not None or a.tour)
     try:
-        planner = ViewPlanner(a.radius, a.range, a.fov, a.stride, a.count, a.separation, a.max_distance, a.min_gain)
+        planner = ViewPlanner(a.radius, a.range, a.fov, a.stride, a.count, a.separation, a.max_distance, a.min_gain,
+                              a.far)
         grid = export.read_occupancy(a.occupancy)
         sources = [a.start] if a.start is not None else read_tum_positions(a.from_trajectory)
         if a.cover:

@@ -50,21 +50,19 @@ namespace {
 using grid_tile::grid_ok;
 using grid_view_ray::Box;
 using grid_view_ray::Headings;
+using grid_view_ray::kMarkRows;
+using grid_view_ray::kMarkTally;
 using grid_view_ray::kMaxAxis;
 using grid_view_ray::kMaxHeadings;
 using grid_view_ray::kMaxRange;
 using grid_view_ray::kQueue;
+using grid_view_ray::kTally;
+using grid_view_ray::MarkRows;
+using grid_view_ray::view_rays_ok;
 using voxel_table::u64;
 using wave_block::block_exclusive_scan;
 
 constexpr unsigned kFar = 0xFFFFFFFFu;
-constexpr int kTally = kMaxHeadings + 3;                 // LDS words: a gain per heading, visible, targets, blocked
-constexpr int kMarkTally = 4;                            // LDS words: rays, rays visible, in the cone, new
-constexpr int kMarkRows = 1024;                          // rows of one pi3_grid_view_mark launch
-
-struct MarkRows {
-  signed char heading[kMarkRows];                        // -1: any of the H headings
-};
 
 __device__ __forceinline__ int floor_mod(long v, int m) {
   const int r = (int)(v % m);
@@ -264,33 +262,14 @@ __global__ __launch_bounds__(256) void view_mark_kernel(const unsigned char* __r
   }
 }
 
-// the arguments the ray entry points share; fills hd
-bool view_rays_ok(const unsigned char* state, int nx, int ny, int nz, long& cells, long V, int range, const int* headings,
-                  int H, long cos2_num, long cos2_den, const unsigned long long* counters, Headings& hd) {
-  bool ok = state && counters && headings && grid_ok(nx, ny, nz, cells) && V >= 0 && V <= 0x7FFFFFFFl && range >= 1 &&
-            range <= kMaxRange && H >= 1 && H <= kMaxHeadings && cos2_den > 0 && cos2_den < (1l << 31) && cos2_num >= 0 &&
-            cos2_num <= cos2_den;
-  for (int h = 0; ok && h < H; ++h) {
-    long long n2 = 0;
-    for (int a = 0; a < 3; ++a) {
-      const int c = headings[3 * h + a];
-      ok = ok && c >= -kMaxAxis && c <= kMaxAxis;
-      hd.axis[h][a] = c;
-      n2 += (long long)c * c;
-    }
-    ok = ok && n2 != 0;
-    hd.norm[h] = n2 * cos2_num;
-  }
-  return ok;
-}
-
 // pi3_grid_view_gain (seen == nullptr, unseen false) and pi3_grid_view_gain_unseen
 int view_gain(const char* who, bool unseen, const unsigned char* state, int nx, int ny, int nz, const unsigned* seen,
               const long* candidates, long V, int range, const int* headings, int H, long cos2_num, long cos2_den,
               unsigned* gain, unsigned* visible, int* best, unsigned long long* counters, void* stream) {
   long cells = 0;
   Headings hd = {};
-  const bool ok = view_rays_ok(state, nx, ny, nz, cells, V, range, headings, H, cos2_num, cos2_den, counters, hd) &&
+  const bool ok = view_rays_ok(state, nx, ny, nz, cells, V, range, kMaxRange, headings, H, cos2_num, cos2_den, counters,
+                               hd) &&
                   (V == 0 || (candidates && gain && visible && best)) && (!unseen || seen);
   if (!ok) {
     pi3_set_error("%s: bad arguments dims=(%d, %d, %d) (1 .. 2^21 - 1 each, at most 2^27 cells) V=%ld "
@@ -350,7 +329,7 @@ extern "C" int pi3_grid_view_mark(const unsigned char* state, int nx, int ny, in
                                   long cos2_den, short* owner, int tag, unsigned long long* counters, void* stream) {
   long cells = 0;
   Headings hd = {};
-  bool ok = view_rays_ok(state, nx, ny, nz, cells, V, range, headings, H, cos2_num, cos2_den, counters, hd) && seen &&
+  bool ok = view_rays_ok(state, nx, ny, nz, cells, V, range, kMaxRange, headings, H, cos2_num, cos2_den, counters, hd) && seen &&
             (V == 0 || (cells_in && heading_of)) && tag >= 0 && tag < 32768 && (!owner || V == 1);
   for (long i = 0; ok && i < V; ++i) ok = heading_of[i] >= -1 && heading_of[i] < H;
   if (!ok) {

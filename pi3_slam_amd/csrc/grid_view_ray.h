@@ -1,22 +1,56 @@
 // What the ray kernels of grid_view.hip share (view_gain_kernel and view_mark_kernel): a workgroup of 256 threads per
 // view pose, the occupied bits of the (2R + 1)^3 box around it in LDS, a queue of targets per wave and the integer DDA
-// on those bits.  grid_view.hip states the rules; every function here is inlined into its kernel.
+// on those bits.  grid_view.hip states the rules; every function here is inlined into its kernel.  The far form
+// (grid_view_far.hip: a workgroup per pose and octant, ranges up to 64) shares the queue, the DDA, the cone, the tallies
+// and the argument check.
 #pragma once
+#include "grid_tile.h"
+
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 namespace grid_view_ray {
 
 constexpr int kMaxRange = 32;
+constexpr int kFarMaxRange = 64;        // grid_view_far.hip: one octant of W = R + 1 cells per axis is 65^3 bits again
 constexpr int kMaxHeadings = 32;
 constexpr int kMaxAxis = 1024;          // per component of a heading
 constexpr int kNever = 1 << 30;         // the key of an axis the ray does not move along
 constexpr int kQueue = 128;             // LDS words per wave: fewer than 64 targets waiting + the 64 of one pass
 
+constexpr int kTally = kMaxHeadings + 3; // LDS words of a gain kernel: a gain per heading, visible, targets, blocked
+constexpr int kMarkTally = 4;           // LDS words of a mark kernel: rays, rays visible, in the cone, new
+constexpr int kMarkRows = 1024;         // rows of one mark launch
+
 struct Headings {
   int axis[kMaxHeadings][3];
   long long norm[kMaxHeadings];         // num |a|^2
 };
+
+struct MarkRows {
+  signed char heading[kMarkRows];       // -1: any of the H headings
+};
+
+// the arguments the ray entry points share (range in 1 .. max_range); fills hd
+inline bool view_rays_ok(const unsigned char* state, int nx, int ny, int nz, long& cells, long V, int range, int max_range,
+                         const int* headings, int H, long cos2_num, long cos2_den, const unsigned long long* counters,
+                         Headings& hd) {
+  bool ok = state && counters && headings && grid_tile::grid_ok(nx, ny, nz, cells) && V >= 0 && V <= 0x7FFFFFFFl &&
+            range >= 1 && range <= max_range && H >= 1 && H <= kMaxHeadings && cos2_den > 0 && cos2_den < (1l << 31) &&
+            cos2_num >= 0 && cos2_num <= cos2_den;
+  for (int h = 0; ok && h < H; ++h) {
+    long long n2 = 0;
+    for (int a = 0; a < 3; ++a) {
+      const int c = headings[3 * h + a];
+      ok = ok && c >= -kMaxAxis && c <= kMaxAxis;
+      hd.axis[h][a] = c;
+      n2 += (long long)c * c;
+    }
+    ok = ok && n2 != 0;
+    hd.norm[h] = n2 * cos2_num;
+  }
+  return ok;
+}
 
 // the words of the box's occupied bits: 8 whole words per pass of 256 cells (35.7 KB with the queues at R = 32)
 inline int box_words(int R) {
@@ -97,15 +131,15 @@ __device__ __forceinline__ int queue_take(unsigned* mine, int& queued, int lane,
   return take;
 }
 
-// The DDA from the pose's own box cell along (ox, oy, oz) != 0 on the box's bits: does the ray arrive?  A step is one
-// LDS word and a handful of integer operations; the box index moves by +-1, +-W, +-W^2.
-__device__ __forceinline__ bool ray_arrives(const unsigned* bits, int R, int W, int W2, int ox, int oy, int oz) {
+// The DDA from the pose's own box cell `at` along (ox, oy, oz) != 0 on the box's bits: does the ray arrive?  A step is
+// one LDS word and a handful of integer operations; the box index moves by +-1, +-W, +-W^2.  Up to |o_a| = 64: a key
+// grows by 2 P <= 8192 per crossing, at most 64 times per axis, and stays below 2^20 < kNever.
+__device__ __forceinline__ bool ray_arrives_from(const unsigned* bits, int at, int W, int W2, int ox, int oy, int oz) {
   const int ax = abs(ox), ay = abs(oy), az = abs(oz);
   const int mx = max(ax, 1), my = max(ay, 1), mz = max(az, 1);
   const int px = 2 * my * mz, py = 2 * mx * mz, pz = 2 * mx * my;       // a key grows by 2 P per crossing
   int kx = ax ? (px >> 1) : kNever, ky = ay ? (py >> 1) : kNever, kz = az ? (pz >> 1) : kNever;
   const int sx = ox > 0 ? 1 : -1, sy = oy > 0 ? W : -W, sz = oz > 0 ? W2 : -W2;
-  int at = (R * W + R) * W + R;                               // the pose's own box cell
   int left = ax + ay + az;                                    // crossings to go; 0 at u
   bool arrives = false;
   for (;;) {
@@ -120,6 +154,11 @@ __device__ __forceinline__ bool ray_arrives(const unsigned* bits, int R, int W, 
     if ((bits[at >> 5] >> (at & 31)) & 1u) break;             // an occupied cell between v and u
   }
   return arrives;
+}
+
+// the pose in the centre of the (2R + 1)^3 box
+__device__ __forceinline__ bool ray_arrives(const unsigned* bits, int R, int W, int W2, int ox, int oy, int oz) {
+  return ray_arrives_from(bits, (R * W + R) * W + R, W, W2, ox, oy, oz);
 }
 
 // offset o with |o|^2 = o2 lies in heading h's cone: o.a > 0 and (o.a)^2 den >= num |a|^2 |o|^2, in 64 bits

@@ -1325,6 +1325,7 @@ def grid_frontier_stats(state: torch.Tensor, label: torch.Tensor, dist: Optional
 
 # ---- views of the occupancy grid (csrc/grid_view.hip)
 VIEW_MAX_RANGE = 32                     # cells: the occupied bits of the (2 R + 1)^3 box live in LDS
+VIEW_FAR_MAX_RANGE = 64                 # cells, csrc/grid_view_far.hip: the bits of one octant's (R + 1)^3 box per workgroup
 VIEW_MAX_HEADINGS = 32
 VIEW_MAX_AXIS = 1024                    # per component of a heading
 VIEW_COUNTERS = ("candidates", "rays", "rays_blocked", "rays_visible")
@@ -1348,14 +1349,23 @@ def grid_view_candidates(dist: torch.Tensor, index_origin, stride: int, max_cost
     _L.check(rc, "pi3_grid_view_candidates")
 
 
+def _view_entry(lib, name: str, view_range: int, far: bool):
+    """The entry point `name`, or its far form (ranges up to VIEW_FAR_MAX_RANGE, the same bytes) when the range needs it
+    or `far` asks for it -> (the function, its name)."""
+    if far or int(view_range) > VIEW_MAX_RANGE:
+        name += "_far"
+    return getattr(lib, name), name
+
+
 def grid_view_gain(state: torch.Tensor, candidates: torch.Tensor, view_range: int, headings, cos2_num: int,
                    cos2_den: int, gain: torch.Tensor, visible: torch.Tensor, best: torch.Tensor,
-                   counters: torch.Tensor) -> None:
+                   counters: torch.Tensor, far: bool = False) -> None:
     """Per entry of candidates int64 (V,) (linear indices into state uint8 (nz,ny,nx)): visible int32 (V,) (the uint32
     values) = the unknown cells within view_range cells that no occupied cell hides, gain int32 (V,H) = those in the
     cone of each of the H integer axes `headings` (H,3) (x, y, z) at cos^2 of the half angle cos2_num / cos2_den, best
     int32 (V,) = the smallest heading of the largest gain (-1 and zeros for a candidate outside the grid).  counters
-    int64 (4,) = VIEW_COUNTERS (zeroed by the call)."""
+    int64 (4,) = VIEW_COUNTERS (zeroed by the call).  A view_range above VIEW_MAX_RANGE, up to VIEW_FAR_MAX_RANGE, goes
+    to the far entry point (csrc/grid_view_far.hip); far=True sends any range there."""
     lib = _L.load()
     nx, ny, nz = _grid_state(state)
     dev = state.device
@@ -1373,11 +1383,11 @@ def grid_view_gain(state: torch.Tensor, candidates: torch.Tensor, view_range: in
         assert t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == (V,) and t.device == dev
     assert counters.dtype == torch.int64 and counters.is_contiguous() and counters.numel() >= 4 and counters.device == dev
     flat = (C.c_int * (3 * H))(*[c for a in hd for c in a])
-    rc = lib.pi3_grid_view_gain(state.data_ptr(), nx, ny, nz, candidates.data_ptr() if V else None, V, int(view_range),
-                                flat, H, int(cos2_num), int(cos2_den), gain.data_ptr() if V else None,
-                                visible.data_ptr() if V else None, best.data_ptr() if V else None,
-                                counters.data_ptr(), _L.stream_ptr())
-    _L.check(rc, "pi3_grid_view_gain")
+    entry, name = _view_entry(lib, "pi3_grid_view_gain", view_range, far)
+    rc = entry(state.data_ptr(), nx, ny, nz, candidates.data_ptr() if V else None, V, int(view_range), flat, H,
+               int(cos2_num), int(cos2_den), gain.data_ptr() if V else None, visible.data_ptr() if V else None,
+               best.data_ptr() if V else None, counters.data_ptr(), _L.stream_ptr())
+    _L.check(rc, name)
 
 
 VIEW_MARK_COUNTERS = ("views", "rays", "rays_visible", "in_cone", "new")
@@ -1406,9 +1416,9 @@ def _view_seen(seen: torch.Tensor, state: torch.Tensor) -> None:
 
 def grid_view_gain_unseen(state: torch.Tensor, seen: torch.Tensor, candidates: torch.Tensor, view_range: int, headings,
                           cos2_num: int, cos2_den: int, gain: torch.Tensor, visible: torch.Tensor, best: torch.Tensor,
-                          counters: torch.Tensor) -> None:
+                          counters: torch.Tensor, far: bool = False) -> None:
     """grid_view_gain over the unknown cells whose bit of seen int32 (grid_view_seen_words(cells),) (the uint32 words) is
-    clear; every output keeps its shape and meaning, and with an all-zero mask its bytes."""
+    clear; every output keeps its shape and meaning, and with an all-zero mask its bytes.  view_range and far as there."""
     lib = _L.load()
     nx, ny, nz = _grid_state(state)
     dev = state.device
@@ -1422,21 +1432,21 @@ def grid_view_gain_unseen(state: torch.Tensor, seen: torch.Tensor, candidates: t
     for t in (visible, best):
         assert t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == (V,) and t.device == dev
     assert counters.dtype == torch.int64 and counters.is_contiguous() and counters.numel() >= 4 and counters.device == dev
-    rc = lib.pi3_grid_view_gain_unseen(state.data_ptr(), nx, ny, nz, seen.data_ptr(),
-                                       candidates.data_ptr() if V else None, V, int(view_range), flat, H, int(cos2_num),
-                                       int(cos2_den), gain.data_ptr() if V else None, visible.data_ptr() if V else None,
-                                       best.data_ptr() if V else None, counters.data_ptr(), _L.stream_ptr())
-    _L.check(rc, "pi3_grid_view_gain_unseen")
+    entry, name = _view_entry(lib, "pi3_grid_view_gain_unseen", view_range, far)
+    rc = entry(state.data_ptr(), nx, ny, nz, seen.data_ptr(), candidates.data_ptr() if V else None, V, int(view_range),
+               flat, H, int(cos2_num), int(cos2_den), gain.data_ptr() if V else None, visible.data_ptr() if V else None,
+               best.data_ptr() if V else None, counters.data_ptr(), _L.stream_ptr())
+    _L.check(rc, name)
 
 
 def grid_view_mark(state: torch.Tensor, seen: torch.Tensor, cells: torch.Tensor, heading_of, view_range: int, headings,
                    cos2_num: int, cos2_den: int, counters: torch.Tensor, owner: Optional[torch.Tensor] = None,
-                   tag: int = 0) -> None:
+                   tag: int = 0, far: bool = False) -> None:
     """Sets in seen int32 (grid_view_seen_words(cells),) the bit of every unknown cell within view_range cells of cells[i]
     (int64 (V,), linear indices on the device) that no occupied cell hides and that lies in the cone of heading
     heading_of[i] (V host integers in -1 .. H - 1; -1: in the cone of any heading).  owner int16 (nz,ny,nx), only with
     V == 1: the cells whose bit this call turned get `tag` (0 .. VIEW_MAX_TAG).  counters int64 (5,) =
-    VIEW_MARK_COUNTERS (zeroed by the call)."""
+    VIEW_MARK_COUNTERS (zeroed by the call).  view_range and far as grid_view_gain's."""
     lib = _L.load()
     nx, ny, nz = _grid_state(state)
     dev = state.device
@@ -1452,11 +1462,11 @@ def grid_view_mark(state: torch.Tensor, seen: torch.Tensor, cells: torch.Tensor,
         assert owner.dtype == torch.int16 and owner.is_contiguous() and owner.shape == state.shape and owner.device == dev
         assert V == 1, f"an owner takes one row per call, got {V}"
     assert counters.dtype == torch.int64 and counters.is_contiguous() and counters.numel() >= 5 and counters.device == dev
-    rc = lib.pi3_grid_view_mark(state.data_ptr(), nx, ny, nz, seen.data_ptr(), cells.data_ptr() if V else None,
-                                hof.ctypes.data_as(C.POINTER(C.c_int)) if V else None, V, int(view_range), flat, H,
-                                int(cos2_num), int(cos2_den),
-                                _L.ptr(owner), int(tag), counters.data_ptr(), _L.stream_ptr())
-    _L.check(rc, "pi3_grid_view_mark")
+    entry, name = _view_entry(lib, "pi3_grid_view_mark", view_range, far)
+    rc = entry(state.data_ptr(), nx, ny, nz, seen.data_ptr(), cells.data_ptr() if V else None,
+               hof.ctypes.data_as(C.POINTER(C.c_int)) if V else None, V, int(view_range), flat, H, int(cos2_num),
+               int(cos2_den), _L.ptr(owner), int(tag), counters.data_ptr(), _L.stream_ptr())
+    _L.check(rc, name)
 
 
 # ---- nearest neighbours between two clouds (csrc/cloud_nn.hip)

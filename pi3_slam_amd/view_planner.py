@@ -11,9 +11,9 @@ directions, `fov_deg` wide); a candidate's best heading is the first of the larg
 greedily: gain descending, route cost ascending, cell ascending, no view within `separation_m` of a kept one.
 
 Limitations: unknown space is transparent, so the gain is an upper bound; poses are cell centres; 26 headings only; a
-cone, not a frustum, and no roll; the range is at most 32 cells (use a larger occupancy cell for more); unknown space
-outside the grid is not counted; nothing is updated incrementally in `find` (`cover` below does); the gain counts cells,
-not surface.  range_m, stride and fov_deg are starting points, not measured optima.
+cone, not a frustum, and no roll; the range is at most 32 cells, 64 with far=True (use a larger occupancy
+cell for more); unknown space outside the grid is not counted; nothing is updated incrementally in `find` (`cover`
+below does); the gain counts cells, not surface.  range_m, stride and fov_deg are starting points, not measured optima.
 
 ViewPlanner.cover picks the views one after the other, each by what the kept ones leave unseen (DESIGN §7j;
 tests/grid_cover_ref.py): a bit per cell says "a kept view sees it", the gain kernel counts only cells whose bit is clear
@@ -203,7 +203,8 @@ class ViewPlanner:
     candidate.  count: the views to keep at most.  separation_m: no two kept views are nearer (default range_m / 2).
     max_distance_m: candidates farther by route are left out (default: none).  min_gain: candidates whose best heading
     sees fewer unknown cells are dropped and counted.  range_m, stride and fov_deg are starting points, not measured
-    optima."""
+    optima.  far: a range of up to 64 cells instead of 32 (the octant kernels of csrc/grid_view_far.hip, DESIGN §7m: the
+    same rules, roughly eight times the rays per pose at twice the range)."""
     radius: float = 0.0
     range_m: float = 1.0
     fov_deg: float = 90.0
@@ -212,6 +213,7 @@ class ViewPlanner:
     separation_m: Optional[float] = None
     max_distance_m: Optional[float] = None
     min_gain: int = 1
+    far: bool = False
 
     CANDIDATES_FIRST_CAP = 1 << 16      # the candidate buffer of the first try; a grid with more asks again
 
@@ -237,14 +239,19 @@ class ViewPlanner:
             self.max_distance_m = float(self.max_distance_m)
             if not (self.max_distance_m >= 0.0 and math.isfinite(self.max_distance_m)):
                 raise ValueError(f"the largest distance must be a finite length >= 0, got {self.max_distance_m!r}")
+        if not isinstance(self.far, bool):
+            raise ValueError(f"far must be True or False, got {self.far!r}")
         self.cos2_den = ops.VIEW_COS2_DEN
         self.cos2_num = int(round(math.cos(math.radians(self.fov_deg) / 2.0) ** 2 * self.cos2_den))
 
     def settings(self) -> Dict:
-        return {"radius": self.radius, "range_m": self.range_m, "fov_deg": self.fov_deg, "stride": self.stride,
-                "count": self.count, "separation_m": self.separation_m, "max_distance_m": self.max_distance_m,
-                "min_gain": self.min_gain, "cos2_num": self.cos2_num, "cos2_den": self.cos2_den,
-                "unknown_is_transparent": True, "outside_is_counted": False, "router": self.router.settings()}
+        st = {"radius": self.radius, "range_m": self.range_m, "fov_deg": self.fov_deg, "stride": self.stride,
+              "count": self.count, "separation_m": self.separation_m, "max_distance_m": self.max_distance_m,
+              "min_gain": self.min_gain, "cos2_num": self.cos2_num, "cos2_den": self.cos2_den,
+              "unknown_is_transparent": True, "outside_is_counted": False, "router": self.router.settings()}
+        if self.far:
+            st["far"] = True                    # only when set: every record written without it keeps its bytes
+        return st
 
     def cells_of(self, cell: float):
         """-> (R, sep_cells, max_cost) for cells of this size."""
@@ -252,7 +259,11 @@ class ViewPlanner:
         if not (cell > 0.0 and math.isfinite(cell)):
             raise ValueError(f"the cell must be a positive finite length, got {cell!r}")
         R = int(math.ceil(self.range_m / cell))
-        if R > ops.VIEW_MAX_RANGE:
+        if self.far and R > ops.VIEW_FAR_MAX_RANGE:
+            raise ValueError(f"a range of {self.range_m} at cells of {cell} is {R} cells: at most "
+                             f"{ops.VIEW_FAR_MAX_RANGE} with far (range <= {ops.VIEW_FAR_MAX_RANGE * cell:g}, or a larger "
+                             f"occupancy cell)")
+        if not self.far and R > ops.VIEW_MAX_RANGE:
             raise ValueError(f"a range of {self.range_m} at cells of {cell} is {R} cells: at most {ops.VIEW_MAX_RANGE} "
                              f"(range <= {ops.VIEW_MAX_RANGE * cell:g}, or a larger occupancy cell)")
         sep = int(math.ceil(self.separation_m / cell))

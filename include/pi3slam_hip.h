@@ -703,7 +703,7 @@ int pi3_grid_view_gain_unseen(const unsigned char* state, int nx, int ny, int nz
 int pi3_grid_view_mark(const unsigned char* state, int nx, int ny, int nz, unsigned* seen, const long* cells,
                        const int* heading_of, long V, int range, const int* headings, int H, long cos2_num,
                        long cos2_den, short* owner, int tag, unsigned long long* counters, void* stream);
-/* Views that see farther (csrc/grid_view_far.hip): the three ray entry points with range in 1..64.  Every
+/* Views that see farther (csrc/grid_view.hip): the three ray entry points with range in 1..64.  Every
  * argument, rule, output and counter is its namesake's, and for range <= 32 so is every byte.  A workgroup takes one
  * octant of a pose (a ray never leaves the closed octant of its target; a target o belongs to the octant that is
  * positive on axis a when o_a >= 0) and adds its counts to gain, visible and the counters with integer atomics, which

@@ -6,7 +6,7 @@
 //           closed supercover of the segment.  With o = b - a, (ax, ay, az) = |o|, m* = max(a*, 1) and the common
 //           denominator 2 mx my mz, the segment crosses its k-th x plane at the key (2k - 1) my mz: kx starts at my mz and
 //           grows by 2 my mz per crossing (y and z alike; an axis with a* = 0 never steps, its key is kNever).  A step
-//           takes m = min(kx, ky, kz) and every axis whose key equals m steps together: grid_view_ray::ray_arrives' keys.
+//           takes m = min(kx, ky, kz) and every axis whose key equals m steps together: grid_view_ray::ray_arrives_from's keys.
 //           The difference is the tie: with s = 2 or 3 axes stepping the segment runs through an edge or a corner, and
 //           all 2^s cells at + (a sx, b sy, e sz), a, b, e in {0, 1} over the stepping axes, are touched, not only the
 //           diagonal one.  For a unit offset that is grid_route.hip's move rule of 2, 4 or 8 cells, so two consecutive

@@ -1,8 +1,20 @@
-// What the ray kernels of grid_view.hip share (view_gain_kernel and view_mark_kernel): a workgroup of 256 threads per
-// view pose, the occupied bits of the (2R + 1)^3 box around it in LDS, a queue of targets per wave and the integer DDA
-// on those bits.  grid_view.hip states the rules; every function here is inlined into its kernel.  The far form
-// (grid_view_far.hip: a workgroup per pose and octant, ranges up to 64) shares the queue, the DDA, the cone, the tallies
-// and the argument check.
+// The ray-casting skeleton of grid_view.hip's gain and mark kernels, each piece once: a workgroup of 256 threads stages
+// the occupied bits of a box around a view pose in LDS, walks the box for targets, queues them per wave and runs the
+// integer DDA on the bits, 64 rays at a time.  grid_view.hip states the rules (between, visible, target, cone); every
+// function here is inlined into its kernel.  The box has two forms, chosen at compile time (kFar):
+//
+//   near      the whole (2R + 1)^3 box with the pose in the centre, R <= 32: a workgroup per pose casts at every target.
+//   octant    a ray from v to u = v + o only touches cells whose offset from v lies, on every axis a, between 0 and o_a:
+//             it never leaves the closed octant of its target.  So the far form stages one of the eight octant boxes of
+//             W = R + 1 cells per axis: octant q (bit a of q set: axis a negative) covers the offsets 0 .. R on a
+//             positive axis and -R .. 0 on a negative one, and the pose sits at box coordinate 0 or R.  At R = 64 that
+//             is 65^3 bits, the 34.3 KB the near form stages at R = 32.
+//   ownership a target o belongs to exactly one octant: axis a is positive when o_a >= 0.  A negative octant stages its
+//             o_a = 0 plane, because its rays pass through it, and never casts at a cell of that plane (RayBox::owns).
+//
+// Arithmetic at R = 64: a DDA key grows by 2 P <= 2 * 64 * 64 = 8192 per crossing and an axis is crossed at most 64
+// times, so a key stays below 2 * 64 * 8192 = 2^20 < kNever = 2^30; the bit index stays below 65^3 = 274 625; box
+// coordinates 0 .. 64 fit the queue's 7-bit fields.  No float, no scratch, no inline assembly.
 #pragma once
 #include "grid_tile.h"
 
@@ -12,7 +24,7 @@
 namespace grid_view_ray {
 
 constexpr int kMaxRange = 32;
-constexpr int kFarMaxRange = 64;        // grid_view_far.hip: one octant of W = R + 1 cells per axis is 65^3 bits again
+constexpr int kFarMaxRange = 64;        // one octant of W = R + 1 cells per axis is 65^3 bits again
 constexpr int kMaxHeadings = 32;
 constexpr int kMaxAxis = 1024;          // per component of a heading
 constexpr int kNever = 1 << 30;         // the key of an axis the ray does not move along
@@ -52,20 +64,31 @@ inline bool view_rays_ok(const unsigned char* state, int nx, int ny, int nz, lon
   return ok;
 }
 
-// the words of the box's occupied bits: 8 whole words per pass of 256 cells (35.7 KB with the queues at R = 32)
-inline int box_words(int R) {
-  const int W = 2 * R + 1;
-  return 8 * ((W * W * W + 255) / 256);
+// The cone test forms (o.a)^2 den <= range^2 |a|^2 den in 64 bits, so range^2 max |a|^2 den must stay below 2^63 (hd
+// as view_rays_ok filled it).  range^2 |a|^2 <= 2^12 * 3 * 2^20 fits easily; the last product is compared by division
+// instead of being formed.  Only a range above 32 can fail it: up to there the product is at most 32^2 * 3 * 2^20 *
+// 2^31 = 3 * 2^61 < 2^63, so the one host path applies the rule to both forms and only the far messages name it.
+inline bool cone_fits(int range, const Headings& hd, int H, long cos2_den) {
+  long long most = 0;
+  for (int h = 0; h < H; ++h) {
+    long long n2 = 0;
+    for (int a = 0; a < 3; ++a) n2 += (long long)hd.axis[h][a] * hd.axis[h][a];
+    most = n2 > most ? n2 : most;
+  }
+  return (long long)range * range * most <= 0x7FFFFFFFFFFFFFFFll / (long long)cos2_den;
 }
 
-// this thread's box cell moves on by 256 cells: (bx, by, bz) += (dx, dy, dz) with carries, 256 = (dz W + dy) W + dx
-__device__ __forceinline__ void box_advance(int& bx, int& by, int& bz, int dx, int dy, int dz, int W) {
-  bx += dx;
-  if (bx >= W) bx -= W, ++by;
-  by += dy;
-  if (by >= W) by -= W, ++bz;
-  bz += dz;
-}
+// cells per axis of the staged box
+__host__ __device__ constexpr int box_width(bool far, int R) { return far ? R + 1 : 2 * R + 1; }
+
+// the words of the box's occupied bits: 8 whole words per pass of 256 cells (W = 65, either form at its largest range:
+// 35.7 KB with the queues)
+inline int box_words(int W) { return 8 * ((W * W * W + 255) / 256); }
+
+// The linear index of cell (gx, gy, gz) inside the grid.  A grid has at most 2^27 cells (grid_tile::grid_ok), so 32
+// bits hold it; the two loops that call this wait for the load it addresses once per pass, and a 64-bit product there
+// is three dependent v_mad_u64_u32 in front of every load.
+__device__ __forceinline__ long cell_index(int nx, int ny, int gx, int gy, int gz) { return (gz * ny + gy) * nx + gx; }
 
 // orders this wave's LDS stores and loads around a hand-over between its lanes (LDS operations of one wave run in
 // order; this keeps the compiler from moving them)
@@ -75,31 +98,58 @@ __device__ __forceinline__ void wave_lds_fence() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// The box around (vx, vy, vz) as 256 threads walk it, 256 cells per pass in box order (z, y, x).
-struct Box {
+// The box of a pose as 256 threads walk it, 256 cells per pass in box order (z, y, x).  Near: the box around the pose.
+// Far: octant q of it, the pose in a corner.
+template <bool kFar>
+struct RayBox {
   int R, W, W2, passes, dx, dy, dz;
-  __device__ __forceinline__ explicit Box(int R_) : R(R_), W(2 * R_ + 1) {
+  int px, py, pz;                                             // the pose's box coordinate; far: 0 or R (a negative axis)
+  __device__ __forceinline__ RayBox(int R_, int q) : R(R_), W(box_width(kFar, R_)) {
     W2 = W * W;
     passes = (W2 * W + 255) >> 8;                              // the box has at most 65^3 cells
     dx = 256 % W, dy = (256 / W) % W, dz = 256 / W2;
+    px = (!kFar || (q & 1)) ? R : 0, py = (!kFar || (q & 2)) ? R : 0, pz = (!kFar || (q & 4)) ? R : 0;
   }
-  __device__ __forceinline__ void first(int t, int& bx, int& by, int& bz) const { bx = t % W, by = (t / W) % W, bz = t / W2; }
-  __device__ __forceinline__ void next(int& bx, int& by, int& bz) const { box_advance(bx, by, bz, dx, dy, dz, W); }
+  __device__ __forceinline__ void first(int t, int& bx, int& by, int& bz) const {
+    bx = t % W, by = (t / W) % W, bz = t / W2;
+  }
+  // this thread's box cell moves on by 256 cells: (bx, by, bz) += (dx, dy, dz) with carries, 256 = (dz W + dy) W + dx
+  __device__ __forceinline__ void next(int& bx, int& by, int& bz) const {
+    bx += dx;
+    if (bx >= W) bx -= W, ++by;
+    by += dy;
+    if (by >= W) by -= W, ++bz;
+    bz += dz;
+  }
+  __device__ __forceinline__ int pose_cell() const { return (pz * W + py) * W + px; }
+  // THE ownership rule: offset o_a = b_a - p_a belongs to the positive side of axis a when o_a >= 0, so a negative
+  // octant (p_a = R) owns b_a < R only.  Its plane b_a = R (o_a = 0) is staged, rays pass through it, but a cell of
+  // it is never a target here: the octant that is positive on that axis casts at it.  Every offset of the ball, the
+  // axes and planes included, is therefore cast at once.  The near box owns all its cells.
+  __device__ __forceinline__ bool owns(int bx, int by, int bz) const {
+    return !kFar || ((px == 0 || bx < R) && (py == 0 || by < R) && (pz == 0 || bz < R));
+  }
+  // no cell this octant owns lies inside the grid: the pose stands on the border its negative axis points across
+  __device__ __forceinline__ bool empty(int vx, int vy, int vz) const {
+    return kFar && ((px && vx == 0) || (py && vy == 0) || (pz && vz == 0));
+  }
 };
 
 // (1) The occupied bits of the box go to `bits`, one bit per cell in box order: thread t of pass i owns box cell
-// 256 i + t, reads its state byte (outside the grid: not occupied) and the wave's ballot is stored as two words, so the
-// bit of box cell j is bit j & 31 of word j >> 5.  The caller's __syncthreads() follows.
-__device__ __forceinline__ void stage_occupied(const Box& b, const unsigned char* __restrict__ state, int nx, int ny,
-                                               int nz, int vx, int vy, int vz, int t, unsigned* bits) {
+// 256 i + t, reads its state byte (rows along x: coalesced; outside the grid: not occupied) and the wave's ballot is
+// stored as two words, so no LDS atomic is needed and the bit of box cell j is bit j & 31 of word j >> 5.  The
+// caller's __syncthreads() follows.
+template <bool kFar>
+__device__ __forceinline__ void stage_occupied(const RayBox<kFar>& b, const unsigned char* __restrict__ state, int nx,
+                                               int ny, int nz, int vx, int vy, int vz, int t, unsigned* bits) {
   const int lane = t & 63;
   int bx, by, bz;
   b.first(t, bx, by, bz);
   for (int p = 0; p < b.passes; ++p) {
-    const int gx = vx - b.R + bx, gy = vy - b.R + by, gz = vz - b.R + bz;
+    const int gx = vx - b.px + bx, gy = vy - b.py + by, gz = vz - b.pz + bz;
     bool occ = false;
     if (bz < b.W && gx >= 0 && gx < nx && gy >= 0 && gy < ny && gz >= 0 && gz < nz)
-      occ = state[((long)gz * ny + gy) * nx + gx] == 2;
+      occ = state[cell_index(nx, ny, gx, gy, gz)] == 2;
     const unsigned long long m = __ballot(occ);
     if (lane == 0) {
       const int w = ((p << 8) + t) >> 5;                      // the wave's 64 cells are two whole words
@@ -110,30 +160,45 @@ __device__ __forceinline__ void stage_occupied(const Box& b, const unsigned char
   }
 }
 
-// (2) A wave's queue of targets (box offsets + R, 7 bits each).  `queued` is the same in every lane and < 64 between
-// passes; the wave alone reads and writes its queue, so a wave-level fence orders it.
+// is box cell (bx, by, bz) a target of the pose?  Inside the box, owned, in the ball, inside the grid and unknown; u is
+// its linear index then.
+template <bool kFar>
+__device__ __forceinline__ bool is_target(const RayBox<kFar>& b, const unsigned char* __restrict__ state, int nx, int ny,
+                                          int nz, int vx, int vy, int vz, int bx, int by, int bz, long& u) {
+  const int ox = bx - b.px, oy = by - b.py, oz = bz - b.pz;
+  const int gx = vx + ox, gy = vy + oy, gz = vz + oz;
+  const int o2 = ox * ox + oy * oy + oz * oz;
+  if (!(bz < b.W && b.owns(bx, by, bz) && o2 != 0 && o2 <= b.R * b.R && gx >= 0 && gx < nx && gy >= 0 && gy < ny &&
+        gz >= 0 && gz < nz))
+    return false;
+  u = cell_index(nx, ny, gx, gy, gz);
+  return state[u] == 0;
+}
+
+// (2) A wave's queue of targets (box coordinates, 7 bits each).  Few lanes of a wave hold a target (3.4 of 64 per pass
+// on tools/view_timing.py's flat at R = 32), so a wave does not walk them where they are found: it appends them to its
+// queue by ballot ranks and walks 64 at a time.  `queued` is the same in every lane and < 64 between passes; the wave
+// alone reads and writes its queue, so a wave-level fence orders it and no atomic is needed.
 __device__ __forceinline__ void queue_push(unsigned* mine, int& queued, bool cast, int lane, int bx, int by, int bz) {
   const unsigned long long cast_b = __ballot(cast);
   if (cast) mine[queued + __popcll(cast_b & ((1ull << lane) - 1ull))] = (unsigned)(bx | (by << 7) | (bz << 14));
   queued += __popcll(cast_b);
 }
 
-// takes up to 64 targets off the queue's end: a lane that `holds` one has its offset from the pose in (ox, oy, oz)
-__device__ __forceinline__ int queue_take(unsigned* mine, int& queued, int lane, int R, bool& holds, int& ox, int& oy,
-                                          int& oz) {
+// takes up to 64 targets off the queue's end: a lane that `holds` one has its box coordinate in (bx, by, bz)
+__device__ __forceinline__ int queue_take(unsigned* mine, int& queued, int lane, bool& holds, int& bx, int& by, int& bz) {
   const int take = min(queued, 64);
   queued -= take;
   wave_lds_fence();                                           // the lanes' stores, before other lanes read them
   holds = lane < take;
   const unsigned e = holds ? mine[queued + lane] : 0u;
   wave_lds_fence();                                           // and these reads before the next pass stores there
-  ox = (int)(e & 127u) - R, oy = (int)((e >> 7) & 127u) - R, oz = (int)(e >> 14) - R;
+  bx = (int)(e & 127u), by = (int)((e >> 7) & 127u), bz = (int)(e >> 14);
   return take;
 }
 
 // The DDA from the pose's own box cell `at` along (ox, oy, oz) != 0 on the box's bits: does the ray arrive?  A step is
-// one LDS word and a handful of integer operations; the box index moves by +-1, +-W, +-W^2.  Up to |o_a| = 64: a key
-// grows by 2 P <= 8192 per crossing, at most 64 times per axis, and stays below 2^20 < kNever.
+// one ds_read_b32 and a handful of integer operations; the box index moves by +-1, +-W, +-W^2.
 __device__ __forceinline__ bool ray_arrives_from(const unsigned* bits, int at, int W, int W2, int ox, int oy, int oz) {
   const int ax = abs(ox), ay = abs(oy), az = abs(oz);
   const int mx = max(ax, 1), my = max(ay, 1), mz = max(az, 1);
@@ -156,15 +221,44 @@ __device__ __forceinline__ bool ray_arrives_from(const unsigned* bits, int at, i
   return arrives;
 }
 
-// the pose in the centre of the (2R + 1)^3 box
-__device__ __forceinline__ bool ray_arrives(const unsigned* bits, int R, int W, int W2, int ox, int oy, int oz) {
-  return ray_arrives_from(bits, (R * W + R) * W + R, W, W2, ox, oy, oz);
-}
-
 // offset o with |o|^2 = o2 lies in heading h's cone: o.a > 0 and (o.a)^2 den >= num |a|^2 |o|^2, in 64 bits
 __device__ __forceinline__ bool in_cone(const Headings& hd, int h, long long den, int ox, int oy, int oz, long long o2) {
   const long long dot = (long long)ox * hd.axis[h][0] + (long long)oy * hd.axis[h][1] + (long long)oz * hd.axis[h][2];
   return dot > 0 && dot * dot * den >= hd.norm[h] * o2;
+}
+
+// (2) and the DDA of (3), after stage_occupied and the caller's __syncthreads(): the same walk over the box finds the
+// targets (kUnseen: only a cell whose bit of `seen` is clear; `seen` is not read otherwise), the wave queues them and,
+// whenever 64 wait, takes them and casts their rays.  Pass `passes` only empties the queue.  on_batch(take, arrived,
+// arrived_b, ox, oy, oz) gets each batch, every lane of the wave at once: `take` rays were cast, this lane's went along
+// (ox, oy, oz) and `arrived` (false in a lane that held none), arrived_b is the ballot of that.
+template <bool kFar, bool kUnseen, class OnBatch>
+__device__ __forceinline__ void cast_rays(const RayBox<kFar>& box, const unsigned char* __restrict__ state, int nx,
+                                          int ny, int nz, const unsigned* __restrict__ seen, int vx, int vy, int vz,
+                                          int t, unsigned* queue, const unsigned* bits, OnBatch on_batch) {
+  const int lane = t & 63;
+  const int home = box.pose_cell();
+  unsigned* mine = queue + (t >> 6) * kQueue;                 // this wave's queue; the wave alone reads and writes it
+  int queued = 0;                                             // the same in every lane of the wave; < 64 between passes
+  int bx, by, bz;
+  box.first(t, bx, by, bz);
+  for (int p = 0; p <= box.passes; ++p) {
+    if (p < box.passes) {
+      long u = 0;
+      bool cast = is_target(box, state, nx, ny, nz, vx, vy, vz, bx, by, bz, u);
+      if (kUnseen) cast = cast && !((seen[u >> 5] >> (u & 31)) & 1u);      // lanes along x read the same word
+      queue_push(mine, queued, cast, lane, bx, by, bz);
+      box.next(bx, by, bz);
+    }
+    if (queued < 64 && !(p == box.passes && queued > 0)) continue;
+    int ox, oy, oz;
+    bool holds;
+    const int take = queue_take(mine, queued, lane, holds, ox, oy, oz);
+    ox -= box.px, oy -= box.py, oz -= box.pz;
+    bool arrived = false;
+    if (holds) arrived = ray_arrives_from(bits, home, box.W, box.W2, ox, oy, oz);
+    on_batch(take, arrived, (unsigned long long)__ballot(arrived), ox, oy, oz);
+  }
 }
 
 }  // namespace grid_view_ray

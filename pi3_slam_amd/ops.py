@@ -1325,7 +1325,7 @@ def grid_frontier_stats(state: torch.Tensor, label: torch.Tensor, dist: Optional
 
 # ---- views of the occupancy grid (csrc/grid_view.hip)
 VIEW_MAX_RANGE = 32                     # cells: the occupied bits of the (2 R + 1)^3 box live in LDS
-VIEW_FAR_MAX_RANGE = 64                 # cells, csrc/grid_view_far.hip: the bits of one octant's (R + 1)^3 box per workgroup
+VIEW_FAR_MAX_RANGE = 64                 # cells, the far form: the bits of one octant's (R + 1)^3 box per workgroup
 VIEW_MAX_HEADINGS = 32
 VIEW_MAX_AXIS = 1024                    # per component of a heading
 VIEW_COUNTERS = ("candidates", "rays", "rays_blocked", "rays_visible")
@@ -1357,39 +1357,6 @@ def _view_entry(lib, name: str, view_range: int, far: bool):
     return getattr(lib, name), name
 
 
-def grid_view_gain(state: torch.Tensor, candidates: torch.Tensor, view_range: int, headings, cos2_num: int,
-                   cos2_den: int, gain: torch.Tensor, visible: torch.Tensor, best: torch.Tensor,
-                   counters: torch.Tensor, far: bool = False) -> None:
-    """Per entry of candidates int64 (V,) (linear indices into state uint8 (nz,ny,nx)): visible int32 (V,) (the uint32
-    values) = the unknown cells within view_range cells that no occupied cell hides, gain int32 (V,H) = those in the
-    cone of each of the H integer axes `headings` (H,3) (x, y, z) at cos^2 of the half angle cos2_num / cos2_den, best
-    int32 (V,) = the smallest heading of the largest gain (-1 and zeros for a candidate outside the grid).  counters
-    int64 (4,) = VIEW_COUNTERS (zeroed by the call).  A view_range above VIEW_MAX_RANGE, up to VIEW_FAR_MAX_RANGE, goes
-    to the far entry point (csrc/grid_view_far.hip); far=True sends any range there."""
-    lib = _L.load()
-    nx, ny, nz = _grid_state(state)
-    dev = state.device
-    assert 0 < state.numel() <= ROUTE_MAX_CELLS, f"{state.numel()} cells: 1 .. 2^27"
-    assert candidates.dtype == torch.int64 and candidates.is_contiguous() and candidates.ndim == 1
-    assert candidates.device == dev
-    V = int(candidates.numel())
-    hd = [tuple(int(c) for c in a) for a in headings]
-    H = len(hd)
-    assert 1 <= H <= VIEW_MAX_HEADINGS, f"{H} headings: 1 .. {VIEW_MAX_HEADINGS}"
-    assert all(len(a) == 3 and any(a) and max(abs(c) for c in a) <= VIEW_MAX_AXIS for a in hd), \
-        f"a heading is no non-zero integer axis (x, y, z) within +-{VIEW_MAX_AXIS}"
-    assert gain.dtype == torch.int32 and gain.is_contiguous() and tuple(gain.shape) == (V, H) and gain.device == dev
-    for t in (visible, best):
-        assert t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == (V,) and t.device == dev
-    assert counters.dtype == torch.int64 and counters.is_contiguous() and counters.numel() >= 4 and counters.device == dev
-    flat = (C.c_int * (3 * H))(*[c for a in hd for c in a])
-    entry, name = _view_entry(lib, "pi3_grid_view_gain", view_range, far)
-    rc = entry(state.data_ptr(), nx, ny, nz, candidates.data_ptr() if V else None, V, int(view_range), flat, H,
-               int(cos2_num), int(cos2_den), gain.data_ptr() if V else None, visible.data_ptr() if V else None,
-               best.data_ptr() if V else None, counters.data_ptr(), _L.stream_ptr())
-    _L.check(rc, name)
-
-
 VIEW_MARK_COUNTERS = ("views", "rays", "rays_visible", "in_cone", "new")
 VIEW_MAX_TAG = 32767                    # owner is int16
 
@@ -1414,16 +1381,21 @@ def _view_seen(seen: torch.Tensor, state: torch.Tensor) -> None:
         f"a mask of {seen.numel()} words for {state.numel()} cells: {grid_view_seen_words(state.numel())}"
 
 
-def grid_view_gain_unseen(state: torch.Tensor, seen: torch.Tensor, candidates: torch.Tensor, view_range: int, headings,
-                          cos2_num: int, cos2_den: int, gain: torch.Tensor, visible: torch.Tensor, best: torch.Tensor,
-                          counters: torch.Tensor, far: bool = False) -> None:
-    """grid_view_gain over the unknown cells whose bit of seen int32 (grid_view_seen_words(cells),) (the uint32 words) is
-    clear; every output keeps its shape and meaning, and with an all-zero mask its bytes.  view_range and far as there."""
-    lib = _L.load()
-    nx, ny, nz = _grid_state(state)
-    dev = state.device
+def _view_grid(state: torch.Tensor, seen: Optional[torch.Tensor]):
+    """What every ray call checks first: the grid and, where the call has one, its mask -> (nx, ny, nz)."""
+    dims = _grid_state(state)
     assert 0 < state.numel() <= ROUTE_MAX_CELLS, f"{state.numel()} cells: 1 .. 2^27"
-    _view_seen(seen, state)
+    if seen is not None:
+        _view_seen(seen, state)
+    return dims
+
+
+def _view_gain(name: str, state, seen, candidates, view_range, headings, cos2_num, cos2_den, gain, visible, best,
+               counters, far) -> None:
+    """grid_view_gain (seen None) and grid_view_gain_unseen: the entry points differ in the mask argument."""
+    lib = _L.load()
+    nx, ny, nz = _view_grid(state, seen)
+    dev = state.device
     assert candidates.dtype == torch.int64 and candidates.is_contiguous() and candidates.ndim == 1
     assert candidates.device == dev
     V = int(candidates.numel())
@@ -1432,11 +1404,34 @@ def grid_view_gain_unseen(state: torch.Tensor, seen: torch.Tensor, candidates: t
     for t in (visible, best):
         assert t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == (V,) and t.device == dev
     assert counters.dtype == torch.int64 and counters.is_contiguous() and counters.numel() >= 4 and counters.device == dev
-    entry, name = _view_entry(lib, "pi3_grid_view_gain_unseen", view_range, far)
-    rc = entry(state.data_ptr(), nx, ny, nz, seen.data_ptr(), candidates.data_ptr() if V else None, V, int(view_range),
-               flat, H, int(cos2_num), int(cos2_den), gain.data_ptr() if V else None, visible.data_ptr() if V else None,
+    entry, name = _view_entry(lib, name, view_range, far)
+    mask = () if seen is None else (seen.data_ptr(),)
+    rc = entry(state.data_ptr(), nx, ny, nz, *mask, candidates.data_ptr() if V else None, V, int(view_range), flat, H,
+               int(cos2_num), int(cos2_den), gain.data_ptr() if V else None, visible.data_ptr() if V else None,
                best.data_ptr() if V else None, counters.data_ptr(), _L.stream_ptr())
     _L.check(rc, name)
+
+
+def grid_view_gain(state: torch.Tensor, candidates: torch.Tensor, view_range: int, headings, cos2_num: int,
+                   cos2_den: int, gain: torch.Tensor, visible: torch.Tensor, best: torch.Tensor,
+                   counters: torch.Tensor, far: bool = False) -> None:
+    """Per entry of candidates int64 (V,) (linear indices into state uint8 (nz,ny,nx)): visible int32 (V,) (the uint32
+    values) = the unknown cells within view_range cells that no occupied cell hides, gain int32 (V,H) = those in the
+    cone of each of the H integer axes `headings` (H,3) (x, y, z) at cos^2 of the half angle cos2_num / cos2_den, best
+    int32 (V,) = the smallest heading of the largest gain (-1 and zeros for a candidate outside the grid).  counters
+    int64 (4,) = VIEW_COUNTERS (zeroed by the call).  A view_range above VIEW_MAX_RANGE, up to VIEW_FAR_MAX_RANGE, goes
+    to the far entry point (the octant form of csrc/grid_view.hip); far=True sends any range there."""
+    _view_gain("pi3_grid_view_gain", state, None, candidates, view_range, headings, cos2_num, cos2_den, gain, visible,
+               best, counters, far)
+
+
+def grid_view_gain_unseen(state: torch.Tensor, seen: torch.Tensor, candidates: torch.Tensor, view_range: int, headings,
+                          cos2_num: int, cos2_den: int, gain: torch.Tensor, visible: torch.Tensor, best: torch.Tensor,
+                          counters: torch.Tensor, far: bool = False) -> None:
+    """grid_view_gain over the unknown cells whose bit of seen int32 (grid_view_seen_words(cells),) (the uint32 words) is
+    clear; every output keeps its shape and meaning, and with an all-zero mask its bytes.  view_range and far as there."""
+    _view_gain("pi3_grid_view_gain_unseen", state, seen, candidates, view_range, headings, cos2_num, cos2_den, gain,
+               visible, best, counters, far)
 
 
 def grid_view_mark(state: torch.Tensor, seen: torch.Tensor, cells: torch.Tensor, heading_of, view_range: int, headings,
@@ -1448,10 +1443,8 @@ def grid_view_mark(state: torch.Tensor, seen: torch.Tensor, cells: torch.Tensor,
     V == 1: the cells whose bit this call turned get `tag` (0 .. VIEW_MAX_TAG).  counters int64 (5,) =
     VIEW_MARK_COUNTERS (zeroed by the call).  view_range and far as grid_view_gain's."""
     lib = _L.load()
-    nx, ny, nz = _grid_state(state)
+    nx, ny, nz = _view_grid(state, seen)
     dev = state.device
-    assert 0 < state.numel() <= ROUTE_MAX_CELLS, f"{state.numel()} cells: 1 .. 2^27"
-    _view_seen(seen, state)
     assert cells.dtype == torch.int64 and cells.is_contiguous() and cells.ndim == 1 and cells.device == dev
     V = int(cells.numel())
     flat, H = _view_headings(headings)

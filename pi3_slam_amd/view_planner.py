@@ -203,7 +203,7 @@ class ViewPlanner:
     candidate.  count: the views to keep at most.  separation_m: no two kept views are nearer (default range_m / 2).
     max_distance_m: candidates farther by route are left out (default: none).  min_gain: candidates whose best heading
     sees fewer unknown cells are dropped and counted.  range_m, stride and fov_deg are starting points, not measured
-    optima.  far: a range of up to 64 cells instead of 32 (the octant kernels of csrc/grid_view_far.hip, DESIGN §7m: the
+    optima.  far: a range of up to 64 cells instead of 32 (the octant form of csrc/grid_view.hip, DESIGN §7m: the
     same rules, roughly eight times the rays per pose at twice the range)."""
     radius: float = 0.0
     range_m: float = 1.0

@@ -1,4 +1,4 @@
-"""Views that see farther, on the CPU (csrc/grid_view_far.hip): the planner's switch, the constants, the
+"""Views that see farther, on the CPU (csrc/grid_view.hip): the planner's switch, the constants, the
 bindings, the `--far` flag, and the octant rule the kernels rest on, held against things the oracle
 (tests/grid_view_ref.py) did not compute."""
 import os
@@ -18,7 +18,7 @@ FAR_NAMES = ("pi3_grid_view_gain_far", "pi3_grid_view_gain_unseen_far", "pi3_gri
 
 def owner(offs):
     """The octant that casts at each offset (N,3): bit a is set when axis a is negative, and axis a is positive when
-    o_a >= 0 (grid_view_far.hip's Octant::owns)."""
+    o_a >= 0 (grid_view_ray.h's RayBox::owns)."""
     o = np.asarray(offs, np.int64).reshape(-1, 3)
     return (o[:, 0] < 0) * 1 + (o[:, 1] < 0) * 2 + (o[:, 2] < 0) * 4
 
@@ -132,7 +132,7 @@ def test_ball_sizes():
 
 
 def test_bounds_at_the_largest_range():
-    """The figures grid_view_far.hip writes next to its code."""
+    """The figures grid_view_ray.h writes next to its code."""
     R = 64
     W = R + 1
     assert W ** 3 == 274625 and 8 * ((W ** 3 + 255) // 256) == 8 * ((65 ** 3 + 255) // 256) == 8584   # = the near form's at 32

@@ -1,4 +1,4 @@
-"""Views that see farther on the GPU (csrc/grid_view_far.hip: pi3_grid_view_gain_far, pi3_grid_view_gain_unseen_far,
+"""Views that see farther on the GPU (csrc/grid_view.hip: pi3_grid_view_gain_far, pi3_grid_view_gain_unseen_far,
 pi3_grid_view_mark_far), byte for byte against the oracles as they stand (tests/grid_view_ref.py,
 tests/grid_cover_ref.py have no range limit), against the near entry points up to 32 cells, against the lattice alone on
 an open ball of 64 cells, and against themselves under the 48 signed axis permutations.  Every output is filled with a

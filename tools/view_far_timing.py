@@ -1,4 +1,4 @@
-"""Time of the far view kernels (csrc/grid_view_far.hip) against the near ones (csrc/grid_view.hip) at one
+"""Time of the far form of the view kernels (csrc/grid_view.hip) against the near form at one
 realistic size, HIP events, the median of the rounds after 3 warm-up rounds, all in the one process of a run.
 
 The workload: tools/view_timing.py's: a grid of `--dims` cells (default 163 x 163 x 103) holding the synthetic flat with

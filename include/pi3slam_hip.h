@@ -721,6 +721,24 @@ int pi3_grid_view_gain_unseen_far(const unsigned char* state, int nx, int ny, in
 int pi3_grid_view_mark_far(const unsigned char* state, int nx, int ny, int nz, unsigned* seen, const long* cells,
                            const int* heading_of, long V, int range, const int* headings, int H, long cos2_num,
                            long cos2_den, short* owner, int tag, unsigned long long* counters, void* stream);
+/* Unknown space that ends a ray (csrc/grid_view.hip): the ray entry points with one more rule.  u is
+ * visible from v at depth K when no cell between them is occupied and at most K cells between them are unknown;
+ * "between" is the rule above, so v, u and the target's own state never count.  depth is 0..255; a ray of the ball of
+ * 64 cells has at most 109 cells between its ends, so depth >= 110 gives the bytes of the entry points above.  far: 0
+ * for the whole box (range 1..32), 1 for the octant form (range 1..64, with the far form's check of the cone).  seen
+ * of pi3_grid_view_gain_depth may be NULL: every unknown cell is then a target (pi3_grid_view_gain), else only those
+ * whose bit is clear (pi3_grid_view_gain_unseen).  Every other argument, output and counter is its namesake's;
+ * "blocked" counts every ray that did not arrive, whichever rule ended it.  Bad arguments return PI3_ERR_ARG with the
+ * depth's bounds in the message and launch nothing; V == 0 launches no kernel.  The first launch per device whose box
+ * needs more than 64 KB of LDS (near range 32, far range 63 and 64) sets the kernel's LDS limit once. */
+int pi3_grid_view_gain_depth(const unsigned char* state, int nx, int ny, int nz, const unsigned* seen,
+                             const long* candidates, long V, int range, int depth, int far, const int* headings, int H,
+                             long cos2_num, long cos2_den, unsigned* gain, unsigned* visible, int* best,
+                             unsigned long long* counters, void* stream);
+int pi3_grid_view_mark_depth(const unsigned char* state, int nx, int ny, int nz, unsigned* seen, const long* cells,
+                             const int* heading_of, long V, int range, int depth, int far, const int* headings, int H,
+                             long cos2_num, long cos2_den, short* owner, int tag, unsigned long long* counters,
+                             void* stream);
 
 /* ---- nearest neighbours between two point clouds (csrc/cloud_nn.hip): an exact radius-bounded search through a
  * uniform grid of cells, for scoring a map against a reference cloud (map_eval.py).  The grid is a hash table of cells

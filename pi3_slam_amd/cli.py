@@ -13,7 +13,7 @@
   python -m pi3_slam_amd.cli frontiers --occupancy OUT/occupancy.npz --output DIR --from-trajectory OUT/trajectory_tum.txt \\
          [--radius 0.2] [--min-cells 20] [--route-to 0 [--taut]]
   python -m pi3_slam_amd.cli views --occupancy OUT/occupancy.npz --output DIR --from-trajectory OUT/trajectory_tum.txt \\
-         [--radius 0.2] [--range 1.0 [--far]] [--fov 90] [--stride 4] [--count 10] [--route-to 0] \\
+         [--radius 0.2] [--range 1.0 [--far]] [--unknown-depth K] [--fov 90] [--stride 4] [--count 10] [--route-to 0] \\
          [--cover [--cover-until 0.9]] [--tour [--tour-from X Y Z]] [--taut [--taut-span 256]]
 
 Under `python -m torch.distributed.run --nproc-per-node G -m pi3_slam_amd.cli ...` every stage shards over the G GPUs.
@@ -348,6 +348,11 @@ VIEW_FLAGS: Sequence[Tuple[str, Dict]] = (
                                                     "cells only (default 0: every free cell)")),
     ("--range", dict(type=float, default=1.0, help="how far a view sees, in metres; at most 32 occupancy cells, 64 with --far "
                                                    "(default 1.0: a starting point, not a measured optimum)")),
+    ("--unknown-depth", dict(type=int, default=None, metavar="K",
+                             help="a ray ends once more than K unknown cells, 0 .. 255, lie between the pose and its "
+                                  "target, so a view counts the first layers of a block of unknown space and not the "
+                                  "whole block (default: none, unknown cells are transparent; whatever K you pick is where "
+                                  "to start, no measured optimum, and 110 or more is the transparent rule)")),
     ("--fov", dict(type=float, default=90.0, help="the full opening angle of the viewing cone in degrees, in (0, 180] "
                                                   "(default 90: a starting point, not a measured optimum)")),
     ("--stride", dict(type=int, default=4, help="every stride-th reachable cell per axis is a candidate pose (default "
@@ -675,7 +680,7 @@ def run_views(a: argparse.Namespace) -> None:
     check_taut(a, "views", "--route-to RANK or --tour", a.route_to is not None or a.tour)
     try:
         planner = ViewPlanner(a.radius, a.range, a.fov, a.stride, a.count, a.separation, a.max_distance, a.min_gain,
-                              a.far)
+                              a.far, a.unknown_depth)
         grid = export.read_occupancy(a.occupancy)
         sources = [a.start] if a.start is not None else read_tum_positions(a.from_trajectory)
         if a.cover:
@@ -695,6 +700,8 @@ def run_views(a: argparse.Namespace) -> None:
     c = found.counts
     text = (f"views: {c['candidates']} candidates, {c['rays']} rays ({c['rays_visible']} visible), {c['views']} views "
             f"kept ({c['low_gain']} candidates below the gain)")
+    if a.unknown_depth is not None:
+        text += f"; rays end after {a.unknown_depth} unknown cells"
     if found.views:
         best = found.views[0]
         text += f"; the best: {best.gain} cells at {best.distance_m:.3f} m"

@@ -39,6 +39,17 @@
 //   sums      every workgroup adds its LDS tally to gain[v][h], visible[v] and the counters with integer atomics: order
 //             free, so the bytes are fixed.  The entry point zeroes them first, on the stream; octant 0 alone counts the
 //             pose; view_best_kernel, a thread per pose, writes best afterwards.  mark needs no finishing.
+//
+// Unknown space that ends a ray (tests/grid_view_depth_ref.py): the _depth entry points run the same kernels,
+// near (far = 0) or far (far = 1), with one more rule.
+//   depth     K in 0 .. 255: u is visible from v when no cell between them is occupied and at most K cells between
+//             them are unknown.  "Between" is the rule above; v and u never count, so the target's own state does not.
+//             A ray has at most |o|_1 - 1 cells between its ends, 109 over the ball of 64 cells: K >= 110 gives the
+//             transparent bytes.  Targets, ball, cone, best, seen, owner and the counters' layout are unchanged;
+//             "blocked" is every ray that did not arrive, whichever rule ended it.
+//   LDS       two bit planes (grid_view_ray.h), twice the box words: above 64 KB from W = 64 on (near R = 32, far
+//             R >= 63), so those launches opt in to their LDS size first (pi3_lds_optin, a done-mask per kernel).
+//   argument  the kernels keep their argument list: the depth form's `R` carries range | K << 8.
 #include "common.h"
 #include "grid_tile.h"
 #include "grid_view_ray.h"
@@ -54,6 +65,7 @@ using grid_view_ray::Headings;
 using grid_view_ray::kFarMaxRange;
 using grid_view_ray::kMarkRows;
 using grid_view_ray::kMarkTally;
+using grid_view_ray::kMaxDepth;
 using grid_view_ray::kMaxAxis;
 using grid_view_ray::kMaxHeadings;
 using grid_view_ray::kMaxRange;
@@ -99,17 +111,20 @@ __global__ __launch_bounds__(256) void view_candidates_kernel(const unsigned* __
 // A workgroup per candidate (blockIdx.x), in the far form per candidate and octant (blockIdx.y).  kUnseen: a cell is a
 // target only when its bit of `seen` is clear (pi3_grid_view_gain_unseen); `seen` is not read otherwise.  Near: gain,
 // visible and best are stored.  Far: gain, visible and the counters were zeroed by the entry point and take atomic
-// sums; best is view_best_kernel's.
-template <bool kUnseen, bool kFar>
+// sums; best is view_best_kernel's.  kDepth: R carries range | K << 8, and the LDS holds two planes (kApart: one
+// behind the other, development build only).
+template <bool kUnseen, bool kFar, bool kDepth = false, bool kApart = false>
 __global__ __launch_bounds__(256) void view_gain_kernel(const unsigned char* __restrict__ state, int nx, int ny, int nz,
                                                         const unsigned* __restrict__ seen,
                                                         const long* __restrict__ candidates, int R, int H,
                                                         const Headings hd, long long den, unsigned* gain,
                                                         unsigned* visible, int* __restrict__ best, u64* counters) {
   extern __shared__ unsigned lds[];                           // kTally words, a queue per wave, the box's occupied bits
-  unsigned* tally = lds;
-  unsigned* queue = lds + kTally;
-  unsigned* bits = queue + 4 * kQueue;
+  const int range = kDepth ? R & 255 : R, depth = kDepth ? R >> 8 : 0;
+  const int planes = kDepth ? 2 * grid_view_ray::box_words(grid_view_ray::box_width(kFar, range)) : 0;
+  unsigned* tally = lds + planes;                             // depth: behind the two planes, which start the LDS
+  unsigned* queue = tally + kTally;
+  unsigned* bits = kDepth ? static_cast<unsigned*>(__builtin_assume_aligned(lds, 16)) : queue + 4 * kQueue;
   const int t = (int)threadIdx.x, lane = t & 63;
   const long v = candidates[blockIdx.x];
   const long cells = (long)nx * ny * nz;
@@ -122,17 +137,17 @@ __global__ __launch_bounds__(256) void view_gain_kernel(const unsigned char* __r
   }
   const int line = (int)v / nx;
   const int vx = (int)v - line * nx, vy = line % ny, vz = line / ny;
-  const RayBox<kFar> box(R, (int)blockIdx.y);
+  const RayBox<kFar> box(range, (int)blockIdx.y);
   if (kFar) {
     if (blockIdx.y == 0 && t == 0) atomicAdd(counters + 0, 1ull);      // the pose is counted once, not per octant
     if (box.empty(vx, vy, vz)) return;                        // the same in every thread
   }
   if (t < kTally) tally[t] = 0u;
-  grid_view_ray::stage_occupied(box, state, nx, ny, nz, vx, vy, vz, t, bits);
+  grid_view_ray::stage_occupied<kFar, kDepth, kApart>(box, state, nx, ny, nz, vx, vy, vz, t, bits);
   __syncthreads();
 
   // (3) the cones of the rays that arrived
-  grid_view_ray::cast_rays<kFar, kUnseen>(
+  grid_view_ray::cast_rays<kFar, kUnseen, kDepth, kApart>(
       box, state, nx, ny, nz, seen, vx, vy, vz, t, queue, bits,
       [&](int take, bool arrived, u64 arrived_b, int ox, int oy, int oz) {
         if (arrived_b) {                                      // the same in every lane of the wave
@@ -148,7 +163,8 @@ __global__ __launch_bounds__(256) void view_gain_kernel(const unsigned char* __r
           atomicAdd(&tally[kMaxHeadings + 1], (unsigned)take);
           atomicAdd(&tally[kMaxHeadings + 2], (unsigned)take - n);
         }
-      });
+      },
+      depth);
   __syncthreads();
   if (kFar) {
     if (t < H && tally[t]) atomicAdd(&gain[(long)blockIdx.x * H + t], tally[t]);
@@ -191,16 +207,18 @@ __global__ __launch_bounds__(256) void view_best_kernel(const long* __restrict__
 // queue and DDA with every unknown cell of the ball a target (the mask does not thin the rays).  A lane whose ray
 // arrived inside the row's cone reads the cell's word of `seen` and, only when the bit is clear, ORs it in; the bit is
 // new when the returned word had it clear, so of several rows that race for one cell exactly one counts it.  owner is
-// written by that lane alone.
-template <bool kFar>
+// written by that lane alone.  kDepth and kApart as the gain kernel's.
+template <bool kFar, bool kDepth = false, bool kApart = false>
 __global__ __launch_bounds__(256) void view_mark_kernel(const unsigned char* __restrict__ state, int nx, int ny, int nz,
                                                         unsigned* seen, const long* __restrict__ cells_in,
                                                         const MarkRows rows, int same, int R, int H, const Headings hd,
                                                         long long den, short* owner, int tag, u64* counters) {
   extern __shared__ unsigned lds[];                           // kMarkTally words, a queue per wave, the occupied bits
-  unsigned* tally = lds;
-  unsigned* queue = lds + kMarkTally;
-  unsigned* bits = queue + 4 * kQueue;
+  const int range = kDepth ? R & 255 : R, depth = kDepth ? R >> 8 : 0;
+  const int planes = kDepth ? 2 * grid_view_ray::box_words(grid_view_ray::box_width(kFar, range)) : 0;
+  unsigned* tally = lds + planes;                             // depth: behind the two planes, which start the LDS
+  unsigned* queue = tally + kMarkTally;
+  unsigned* bits = kDepth ? static_cast<unsigned*>(__builtin_assume_aligned(lds, 16)) : queue + 4 * kQueue;
   const int t = (int)threadIdx.x, lane = t & 63;
   const long v = cells_in[blockIdx.x];
   const long cells = (long)nx * ny * nz;
@@ -208,16 +226,16 @@ __global__ __launch_bounds__(256) void view_mark_kernel(const unsigned char* __r
   const int heading = rows.heading[same ? 0 : blockIdx.x];
   const int line = (int)v / nx;
   const int vx = (int)v - line * nx, vy = line % ny, vz = line / ny;
-  const RayBox<kFar> box(R, (int)blockIdx.y);
+  const RayBox<kFar> box(range, (int)blockIdx.y);
   if (kFar) {
     if (blockIdx.y == 0 && t == 0) atomicAdd(counters + 0, 1ull);      // the view is counted once, not per octant
     if (box.empty(vx, vy, vz)) return;                        // the same in every thread
   }
   if (t < kMarkTally) tally[t] = 0u;
-  grid_view_ray::stage_occupied(box, state, nx, ny, nz, vx, vy, vz, t, bits);
+  grid_view_ray::stage_occupied<kFar, kDepth, kApart>(box, state, nx, ny, nz, vx, vy, vz, t, bits);
   __syncthreads();
 
-  grid_view_ray::cast_rays<kFar, false>(
+  grid_view_ray::cast_rays<kFar, false, kDepth, kApart>(
       box, state, nx, ny, nz, nullptr, vx, vy, vz, t, queue, bits,
       [&](int take, bool arrived, u64 arrived_b, int ox, int oy, int oz) {
         bool in = false, fresh = false;
@@ -245,7 +263,8 @@ __global__ __launch_bounds__(256) void view_mark_kernel(const unsigned char* __r
           if (in_b) atomicAdd(&tally[2], (unsigned)__popcll(in_b));
           if (fresh_b) atomicAdd(&tally[3], (unsigned)__popcll(fresh_b));
         }
-      });
+      },
+      depth);
   __syncthreads();
   if (t == 0) {
     if (!kFar) atomicAdd(counters + 0, 1ull);
@@ -256,19 +275,69 @@ __global__ __launch_bounds__(256) void view_mark_kernel(const unsigned char* __r
 
 // What an entry point's form decides on the host: its name, its largest range, near or far, and what the far messages
 // add about the cone (grid_view_ray::cone_fits is checked for both forms and can fail only above kMaxRange).
+// The depth form (the _depth entry points) adds: its depth K, which its messages name, twice the box words, and the
+// kernels' `R` argument as range | K << 8.  Every other entry point is not `deep`: transparent, and none of that.
 struct Form {
   const char* who;
   bool far;
+  bool deep = false;
+  int depth = 0;
+  char depth_text[40] = "";                                   // " depth=K (0 .. 255)" in the depth form's messages
+  Form(const char* who_, bool far_) : who(who_), far(far_) {}
+  Form(const char* who_, int far_, int depth_) : who(who_), far(far_ != 0), deep(true), depth(depth_) {
+    snprintf(depth_text, sizeof depth_text, " depth=%d (0 .. %d)", depth, kMaxDepth);
+  }
+  bool depth_ok() const { return !deep || (depth >= 0 && depth <= kMaxDepth); }
   int max_range() const { return far ? kFarMaxRange : kMaxRange; }
   const char* cone_rule() const { return far ? "; the cone test's 64 bits: range^2 * max |axis|^2 * den < 2^63" : ""; }
-  size_t lds_bytes(int tally, int range) const {              // the tally, a queue per wave, the box's occupied bits
+  size_t lds_bytes(int tally, int range) const {              // the tally, a queue per wave, the box's bits
     const int words = grid_view_ray::box_words(grid_view_ray::box_width(far, range));
-    return (size_t)(tally + 4 * kQueue + words) * sizeof(unsigned);
+    return (size_t)(tally + 4 * kQueue + (deep ? 2 : 1) * words) * sizeof(unsigned);
   }
+  int kernel_range(int range) const { return deep ? range | (depth << 8) : range; }
   dim3 grid(long n) const { return dim3((unsigned)n, far ? 8 : 1); }
 };
 
-// the four gain entry points: seen == nullptr unless unseen
+// A depth kernel and the opt-in to its LDS size: above the 64 KB every kernel may have, the launch asks for the form's
+// largest size first, once per device (the mask is a static of this instantiation, one per kernel instance).
+constexpr size_t kLdsDefault = 64 * 1024;
+template <auto KERN>
+int depth_optin(size_t bytes, size_t most, const char* what) {
+  static unsigned long long done = 0;
+  return bytes <= kLdsDefault ? PI3_OK : pi3_lds_optin((const void*)KERN, (int)most, &done, what);
+}
+template <class Kernel>
+struct DepthLaunch {
+  Kernel kernel;
+  int (*optin)(size_t bytes, size_t most, const char* what);
+};
+using GainKernel = decltype(&view_gain_kernel<false, false>);
+using MarkKernel = decltype(&view_mark_kernel<false>);
+
+template <bool kApart>
+DepthLaunch<GainKernel> depth_gain(bool unseen, bool far) {
+#define PI3_VIEW_GAIN(U, F) DepthLaunch<GainKernel>{view_gain_kernel<U, F, true, kApart>, depth_optin<view_gain_kernel<U, F, true, kApart>>}
+  return far ? (unseen ? PI3_VIEW_GAIN(true, true) : PI3_VIEW_GAIN(false, true))
+             : (unseen ? PI3_VIEW_GAIN(true, false) : PI3_VIEW_GAIN(false, false));
+#undef PI3_VIEW_GAIN
+}
+
+template <bool kApart>
+DepthLaunch<MarkKernel> depth_mark(bool far) {
+  if (far) return {view_mark_kernel<true, true, kApart>, depth_optin<view_mark_kernel<true, true, kApart>>};
+  return {view_mark_kernel<false, true, kApart>, depth_optin<view_mark_kernel<false, true, kApart>>};
+}
+
+// the planes one behind the other: the development build alone has that form (PI3_VIEW_DEPTH_APART=1); the product
+// library instantiates the interleaved kernels only
+#ifdef PI3_DEV_VARIANTS
+constexpr bool kDevVariants = true;
+#else
+constexpr bool kDevVariants = false;
+#endif
+bool planes_apart() { return PI3_DEV_ENV_INT("PI3_VIEW_DEPTH_APART", 0) != 0; }
+
+// the four gain entry points and the depth form's one: seen == nullptr unless unseen
 int view_gain(Form form, bool unseen, const unsigned char* state, int nx, int ny, int nz, const unsigned* seen,
               const long* candidates, long V, int range, const int* headings, int H, long cos2_num, long cos2_den,
               unsigned* gain, unsigned* visible, int* best, unsigned long long* counters, void* stream) {
@@ -277,12 +346,12 @@ int view_gain(Form form, bool unseen, const unsigned char* state, int nx, int ny
   Headings hd = {};
   const bool ok = grid_view_ray::view_rays_ok(state, nx, ny, nz, cells, V, range, form.max_range(), headings, H, cos2_num,
                                               cos2_den, counters, hd) &&
-                  (V == 0 || (candidates && gain && visible && best)) && (!unseen || seen);
+                  (V == 0 || (candidates && gain && visible && best)) && (!unseen || seen) && form.depth_ok();
   if (!ok || !grid_view_ray::cone_fits(range, hd, H, cos2_den)) {
     pi3_set_error("%s: bad arguments dims=(%d, %d, %d) (1 .. 2^21 - 1 each, at most 2^27 cells) V=%ld "
-                  "(0 .. 2^31 - 1) range=%d (1 .. %d) H=%d (1 .. %d; every axis non-zero, components within +-%d) "
+                  "(0 .. 2^31 - 1) range=%d (1 .. %d)%s H=%d (1 .. %d; every axis non-zero, components within +-%d) "
                   "cos2=%ld/%ld (0 <= num <= den, 0 < den < 2^31%s), or a null pointer", who, nx, ny, nz, V, range,
-                  form.max_range(), H, kMaxHeadings, kMaxAxis, cos2_num, cos2_den, form.cone_rule());
+                  form.max_range(), form.depth_text, H, kMaxHeadings, kMaxAxis, cos2_num, cos2_den, form.cone_rule());
     return PI3_ERR_ARG;
   }
   const hipStream_t s = (hipStream_t)stream;
@@ -293,10 +362,16 @@ int view_gain(Form form, bool unseen, const unsigned char* state, int nx, int ny
     pi3_set_error("%s: hipMemsetAsync failed", who);
     return PI3_ERR_LAUNCH;
   }
-  const auto kernel = form.far ? (unseen ? view_gain_kernel<true, true> : view_gain_kernel<false, true>)
-                               : (unseen ? view_gain_kernel<true, false> : view_gain_kernel<false, false>);
+  auto kernel = form.far ? (unseen ? view_gain_kernel<true, true> : view_gain_kernel<false, true>)
+                         : (unseen ? view_gain_kernel<true, false> : view_gain_kernel<false, false>);
+  if (form.deep) {
+    const auto deep = planes_apart() ? depth_gain<kDevVariants>(unseen, form.far) : depth_gain<false>(unseen, form.far);
+    if (int rc = deep.optin(form.lds_bytes(kTally, range), form.lds_bytes(kTally, form.max_range()), who + 4)) return rc;
+    kernel = deep.kernel;
+  }
   hipLaunchKernelGGL(kernel, form.grid(V), dim3(256), form.lds_bytes(kTally, range), s, state, nx, ny, nz, seen,
-                     candidates, range, H, hd, (long long)cos2_den, gain, visible, best, (u64*)counters);
+                     candidates, form.kernel_range(range), H, hd, (long long)cos2_den, gain, visible, best,
+                     (u64*)counters);
   const int rc = pi3_check_launch(who + 4);   // without "pi3_"
   if (rc != PI3_OK || !form.far) return rc;
   hipLaunchKernelGGL(view_best_kernel, dim3(voxel_table::blocks_for(V)), dim3(256), 0, s, candidates, V, cells, H,
@@ -304,7 +379,7 @@ int view_gain(Form form, bool unseen, const unsigned char* state, int nx, int ny
   return pi3_check_launch(who + 4);
 }
 
-// the two mark entry points
+// the two mark entry points and the depth form's one
 int view_mark(Form form, const unsigned char* state, int nx, int ny, int nz, unsigned* seen, const long* cells_in,
               const int* heading_of, long V, int range, const int* headings, int H, long cos2_num, long cos2_den,
               short* owner, int tag, unsigned long long* counters, void* stream) {
@@ -312,14 +387,15 @@ int view_mark(Form form, const unsigned char* state, int nx, int ny, int nz, uns
   Headings hd = {};
   bool ok = grid_view_ray::view_rays_ok(state, nx, ny, nz, cells, V, range, form.max_range(), headings, H, cos2_num,
                                         cos2_den, counters, hd) &&
-            seen && (V == 0 || (cells_in && heading_of)) && tag >= 0 && tag < 32768 && (!owner || V == 1);
+            seen && (V == 0 || (cells_in && heading_of)) && tag >= 0 && tag < 32768 && (!owner || V == 1) &&
+            form.depth_ok();
   for (long i = 0; ok && i < V; ++i) ok = heading_of[i] >= -1 && heading_of[i] < H;
   if (!ok || !grid_view_ray::cone_fits(range, hd, H, cos2_den)) {
     pi3_set_error("%s: bad arguments dims=(%d, %d, %d) (1 .. 2^21 - 1 each, at most 2^27 cells) V=%ld "
-                  "(0 .. 2^31 - 1; 1 with an owner) range=%d (1 .. %d) H=%d (1 .. %d; every axis non-zero, components "
+                  "(0 .. 2^31 - 1; 1 with an owner) range=%d (1 .. %d)%s H=%d (1 .. %d; every axis non-zero, components "
                   "within +-%d; every row's heading in -1 .. H - 1) cos2=%ld/%ld (0 <= num <= den, 0 < den < 2^31%s) "
-                  "tag=%d (0 .. 32767), or a null pointer", form.who, nx, ny, nz, V, range, form.max_range(), H,
-                  kMaxHeadings, kMaxAxis, cos2_num, cos2_den, form.cone_rule(), tag);
+                  "tag=%d (0 .. 32767), or a null pointer", form.who, nx, ny, nz, V, range, form.max_range(),
+                  form.depth_text, H, kMaxHeadings, kMaxAxis, cos2_num, cos2_den, form.cone_rule(), tag);
     return PI3_ERR_ARG;
   }
   if (pi3_zero_words(form.who, counters, 1 + kMarkTally, stream) != PI3_OK) return PI3_ERR_LAUNCH;
@@ -329,13 +405,19 @@ int view_mark(Form form, const unsigned char* state, int nx, int ny, int nz, uns
   for (long i = 1; same && i < V; ++i) same = heading_of[i] == heading_of[0];
   const long step = same ? V : kMarkRows;
   MarkRows rows;
-  const auto kernel = form.far ? view_mark_kernel<true> : view_mark_kernel<false>;
+  auto kernel = form.far ? view_mark_kernel<true> : view_mark_kernel<false>;
+  if (form.deep && V > 0) {
+    const auto deep = planes_apart() ? depth_mark<kDevVariants>(form.far) : depth_mark<false>(form.far);
+    if (int rc = deep.optin(form.lds_bytes(kMarkTally, range), form.lds_bytes(kMarkTally, form.max_range()), form.who + 4))
+      return rc;
+    kernel = deep.kernel;
+  }
   for (long base = 0; base < V; base += step) {
     const long n = V - base < step ? V - base : step;
     for (int i = 0; i < kMarkRows; ++i) rows.heading[i] = (signed char)(i < n ? heading_of[base + i] : -1);
     hipLaunchKernelGGL(kernel, form.grid(n), dim3(256), form.lds_bytes(kMarkTally, range), (hipStream_t)stream, state,
-                       nx, ny, nz, seen, cells_in + base, rows, same ? 1 : 0, range, H, hd, (long long)cos2_den, owner,
-                       tag, (u64*)counters);
+                       nx, ny, nz, seen, cells_in + base, rows, same ? 1 : 0, form.kernel_range(range), H, hd,
+                       (long long)cos2_den, owner, tag, (u64*)counters);
     const int rc = pi3_check_launch(form.who + 4);            // without "pi3_"
     if (rc != PI3_OK) return rc;
   }
@@ -404,4 +486,20 @@ extern "C" int pi3_grid_view_mark_far(const unsigned char* state, int nx, int ny
                                       unsigned long long* counters, void* stream) {
   return view_mark({"pi3_grid_view_mark_far", true}, state, nx, ny, nz, seen, cells_in, heading_of, V, range, headings, H,
                    cos2_num, cos2_den, owner, tag, counters, stream);
+}
+
+extern "C" int pi3_grid_view_gain_depth(const unsigned char* state, int nx, int ny, int nz, const unsigned* seen,
+                                        const long* candidates, long V, int range, int depth, int far,
+                                        const int* headings, int H, long cos2_num, long cos2_den, unsigned* gain,
+                                        unsigned* visible, int* best, unsigned long long* counters, void* stream) {
+  return view_gain({"pi3_grid_view_gain_depth", far, depth}, seen != nullptr, state, nx, ny, nz, seen, candidates, V,
+                   range, headings, H, cos2_num, cos2_den, gain, visible, best, counters, stream);
+}
+
+extern "C" int pi3_grid_view_mark_depth(const unsigned char* state, int nx, int ny, int nz, unsigned* seen,
+                                        const long* cells_in, const int* heading_of, long V, int range, int depth, int far,
+                                        const int* headings, int H, long cos2_num, long cos2_den, short* owner, int tag,
+                                        unsigned long long* counters, void* stream) {
+  return view_mark({"pi3_grid_view_mark_depth", far, depth}, state, nx, ny, nz, seen, cells_in, heading_of, V, range,
+                   headings, H, cos2_num, cos2_den, owner, tag, counters, stream);
 }

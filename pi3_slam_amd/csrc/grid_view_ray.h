@@ -15,6 +15,14 @@
 // Arithmetic at R = 64: a DDA key grows by 2 P <= 2 * 64 * 64 = 8192 per crossing and an axis is crossed at most 64
 // times, so a key stays below 2 * 64 * 8192 = 2^20 < kNever = 2^30; the bit index stays below 65^3 = 274 625; box
 // coordinates 0 .. 64 fit the queue's 7-bit fields.  No float, no scratch, no inline assembly.
+//
+// The depth form (kDepth; either box form): a ray also ends when more than K cells between its ends are
+// unknown.  The box then has two bit planes, occupied and unknown (state 0 inside the grid), staged from the one read of
+// each state byte and interleaved word by word: words 2w and 2w + 1 are the occupied and the unknown bits of box cells
+// 32w .. 32w + 31, so a DDA step is one aligned 8-byte LDS read and lane 0 stages a wave's 64 cells with one 16-byte
+// write.  The second walk takes its targets from the unknown plane and reads no state byte again.  The count of
+// unknown cells is one more register; keys, bit indices and queue fields are those above.  kApart (development build
+// only): the two planes one behind the other, two reads per step, the form that was measured against this one.
 #pragma once
 #include "grid_tile.h"
 
@@ -25,6 +33,7 @@ namespace grid_view_ray {
 
 constexpr int kMaxRange = 32;
 constexpr int kFarMaxRange = 64;        // one octant of W = R + 1 cells per axis is 65^3 bits again
+constexpr int kMaxDepth = 255;          // the depth form: unknown cells a ray may cross
 constexpr int kMaxHeadings = 32;
 constexpr int kMaxAxis = 1024;          // per component of a heading
 constexpr int kNever = 1 << 30;         // the key of an axis the ray does not move along
@@ -83,7 +92,7 @@ __host__ __device__ constexpr int box_width(bool far, int R) { return far ? R + 
 
 // the words of the box's occupied bits: 8 whole words per pass of 256 cells (W = 65, either form at its largest range:
 // 35.7 KB with the queues)
-inline int box_words(int W) { return 8 * ((W * W * W + 255) / 256); }
+__host__ __device__ inline int box_words(int W) { return 8 * ((W * W * W + 255) / 256); }
 
 // The linear index of cell (gx, gy, gz) inside the grid.  A grid has at most 2^27 cells (grid_tile::grid_ok), so 32
 // bits hold it; the two loops that call this wait for the load it addresses once per pass, and a 64-bit product there
@@ -135,11 +144,19 @@ struct RayBox {
   }
 };
 
+// the occupied and the unknown word of box cell j's 32 cells in the depth form (`words`: those of one plane)
+template <bool kApart>
+__device__ __forceinline__ uint2 plane_words(const unsigned* bits, int words, int j) {
+  if (kApart) return make_uint2(bits[j >> 5], bits[words + (j >> 5)]);
+  return *reinterpret_cast<const uint2*>(bits + ((j >> 5) << 1));        // bits is 16-byte aligned: one ds_read_b64
+}
+
 // (1) The occupied bits of the box go to `bits`, one bit per cell in box order: thread t of pass i owns box cell
 // 256 i + t, reads its state byte (rows along x: coalesced; outside the grid: not occupied) and the wave's ballot is
 // stored as two words, so no LDS atomic is needed and the bit of box cell j is bit j & 31 of word j >> 5.  The
-// caller's __syncthreads() follows.
-template <bool kFar>
+// caller's __syncthreads() follows.  kDepth: the same byte also gives the unknown ballot (outside the grid: not
+// unknown), and the wave's four words go out in one 16-byte store (plane_words is the layout's other end).
+template <bool kFar, bool kDepth = false, bool kApart = false>
 __device__ __forceinline__ void stage_occupied(const RayBox<kFar>& b, const unsigned char* __restrict__ state, int nx,
                                                int ny, int nz, int vx, int vy, int vz, int t, unsigned* bits) {
   const int lane = t & 63;
@@ -147,14 +164,32 @@ __device__ __forceinline__ void stage_occupied(const RayBox<kFar>& b, const unsi
   b.first(t, bx, by, bz);
   for (int p = 0; p < b.passes; ++p) {
     const int gx = vx - b.px + bx, gy = vy - b.py + by, gz = vz - b.pz + bz;
-    bool occ = false;
-    if (bz < b.W && gx >= 0 && gx < nx && gy >= 0 && gy < ny && gz >= 0 && gz < nz)
-      occ = state[cell_index(nx, ny, gx, gy, gz)] == 2;
-    const unsigned long long m = __ballot(occ);
-    if (lane == 0) {
-      const int w = ((p << 8) + t) >> 5;                      // the wave's 64 cells are two whole words
-      bits[w] = (unsigned)m;
-      bits[w + 1] = (unsigned)(m >> 32);
+    if constexpr (!kDepth) {
+      bool occ = false;
+      if (bz < b.W && gx >= 0 && gx < nx && gy >= 0 && gy < ny && gz >= 0 && gz < nz)
+        occ = state[cell_index(nx, ny, gx, gy, gz)] == 2;
+      const unsigned long long m = __ballot(occ);
+      if (lane == 0) {
+        const int w = ((p << 8) + t) >> 5;                    // the wave's 64 cells are two whole words
+        bits[w] = (unsigned)m;
+        bits[w + 1] = (unsigned)(m >> 32);
+      }
+    } else {
+      unsigned char s = 1;                                    // outside the box or the grid: neither plane has it
+      if (bz < b.W && gx >= 0 && gx < nx && gy >= 0 && gy < ny && gz >= 0 && gz < nz)
+        s = state[cell_index(nx, ny, gx, gy, gz)];
+      const unsigned long long m = __ballot(s == 2), k = __ballot(s == 0);
+      if (lane == 0) {
+        const int w = ((p << 8) + t) >> 5;                    // even: the wave's 64 cells are two whole words per plane
+        if (kApart) {
+          unsigned* unknown = bits + 8 * b.passes;
+          bits[w] = (unsigned)m, bits[w + 1] = (unsigned)(m >> 32);
+          unknown[w] = (unsigned)k, unknown[w + 1] = (unsigned)(k >> 32);
+        } else {
+          *reinterpret_cast<uint4*>(bits + 2 * w) =
+              make_uint4((unsigned)m, (unsigned)k, (unsigned)(m >> 32), (unsigned)(k >> 32));
+        }
+      }
     }
     b.next(bx, by, bz);
   }
@@ -173,6 +208,18 @@ __device__ __forceinline__ bool is_target(const RayBox<kFar>& b, const unsigned 
     return false;
   u = cell_index(nx, ny, gx, gy, gz);
   return state[u] == 0;
+}
+
+// the depth form's is_target, from LDS: box cell j = (bx, by, bz) is owned, in the ball, not the pose, and its unknown
+// bit is set, which already says "inside the box, inside the grid and state 0" (the bits behind the box's last cell are
+// staged clear).  No state byte is read again.
+template <bool kFar, bool kApart>
+__device__ __forceinline__ bool is_target_bit(const RayBox<kFar>& b, const unsigned* bits, int words, int j, int bx,
+                                              int by, int bz) {
+  const int ox = bx - b.px, oy = by - b.py, oz = bz - b.pz;
+  const int o2 = ox * ox + oy * oy + oz * oz;
+  if (!(b.owns(bx, by, bz) && o2 != 0 && o2 <= b.R * b.R)) return false;
+  return (plane_words<kApart>(bits, words, j).y >> (j & 31)) & 1u;
 }
 
 // (2) A wave's queue of targets (box coordinates, 7 bits each).  Few lanes of a wave hold a target (3.4 of 64 per pass
@@ -198,8 +245,12 @@ __device__ __forceinline__ int queue_take(unsigned* mine, int& queued, int lane,
 }
 
 // The DDA from the pose's own box cell `at` along (ox, oy, oz) != 0 on the box's bits: does the ray arrive?  A step is
-// one ds_read_b32 and a handful of integer operations; the box index moves by +-1, +-W, +-W^2.
-__device__ __forceinline__ bool ray_arrives_from(const unsigned* bits, int at, int W, int W2, int ox, int oy, int oz) {
+// one ds_read_b32 and a handful of integer operations; the box index moves by +-1, +-W, +-W^2.  kDepth: a step reads
+// the cell's occupied and unknown word at once (plane_words); an unknown cell between the ends takes one off `spare`,
+// which starts at the depth K, and the ray ends at the K + 1st.  The target's own bit is never read.
+template <bool kDepth = false, bool kApart = false>
+__device__ __forceinline__ bool ray_arrives_from(const unsigned* bits, int at, int W, int W2, int ox, int oy, int oz,
+                                                 int words = 0, int spare = 0) {
   const int ax = abs(ox), ay = abs(oy), az = abs(oz);
   const int mx = max(ax, 1), my = max(ay, 1), mz = max(az, 1);
   const int px = 2 * my * mz, py = 2 * mx * mz, pz = 2 * mx * my;       // a key grows by 2 P per crossing
@@ -216,7 +267,14 @@ __device__ __forceinline__ bool ray_arrives_from(const unsigned* bits, int at, i
       arrives = true;
       break;
     }
-    if ((bits[at >> 5] >> (at & 31)) & 1u) break;             // an occupied cell between v and u
+    if constexpr (!kDepth) {
+      if ((bits[at >> 5] >> (at & 31)) & 1u) break;           // an occupied cell between v and u
+    } else {
+      const uint2 w = plane_words<kApart>(bits, words, at);
+      if ((w.x >> (at & 31)) & 1u) break;                     // an occupied cell between v and u
+      spare -= (int)((w.y >> (at & 31)) & 1u);
+      if (spare < 0) break;                                   // more than K unknown cells between them
+    }
   }
   return arrives;
 }
@@ -232,21 +290,29 @@ __device__ __forceinline__ bool in_cone(const Headings& hd, int h, long long den
 // whenever 64 wait, takes them and casts their rays.  Pass `passes` only empties the queue.  on_batch(take, arrived,
 // arrived_b, ox, oy, oz) gets each batch, every lane of the wave at once: `take` rays were cast, this lane's went along
 // (ox, oy, oz) and `arrived` (false in a lane that held none), arrived_b is the ballot of that.
-template <bool kFar, bool kUnseen, class OnBatch>
+template <bool kFar, bool kUnseen, bool kDepth = false, bool kApart = false, class OnBatch>
 __device__ __forceinline__ void cast_rays(const RayBox<kFar>& box, const unsigned char* __restrict__ state, int nx,
                                           int ny, int nz, const unsigned* __restrict__ seen, int vx, int vy, int vz,
-                                          int t, unsigned* queue, const unsigned* bits, OnBatch on_batch) {
+                                          int t, unsigned* queue, const unsigned* bits, OnBatch on_batch, int depth = 0) {
   const int lane = t & 63;
   const int home = box.pose_cell();
   unsigned* mine = queue + (t >> 6) * kQueue;                 // this wave's queue; the wave alone reads and writes it
+  const int words = 8 * box.passes;                           // of one plane (the depth form alone uses it)
   int queued = 0;                                             // the same in every lane of the wave; < 64 between passes
   int bx, by, bz;
   box.first(t, bx, by, bz);
   for (int p = 0; p <= box.passes; ++p) {
     if (p < box.passes) {
       long u = 0;
-      bool cast = is_target(box, state, nx, ny, nz, vx, vy, vz, bx, by, bz, u);
-      if (kUnseen) cast = cast && !((seen[u >> 5] >> (u & 31)) & 1u);      // lanes along x read the same word
+      bool cast = !kDepth && is_target(box, state, nx, ny, nz, vx, vy, vz, bx, by, bz, u);
+      if (kUnseen && !kDepth) cast = cast && !((seen[u >> 5] >> (u & 31)) & 1u);     // lanes along x read the same word
+      if constexpr (kDepth) {
+        cast = is_target_bit<kFar, kApart>(box, bits, words, (p << 8) + t, bx, by, bz);
+        if (kUnseen && cast) {                                // a target lies inside the grid
+          u = cell_index(nx, ny, vx - box.px + bx, vy - box.py + by, vz - box.pz + bz);
+          cast = !((seen[u >> 5] >> (u & 31)) & 1u);
+        }
+      }
       queue_push(mine, queued, cast, lane, bx, by, bz);
       box.next(bx, by, bz);
     }
@@ -256,7 +322,7 @@ __device__ __forceinline__ void cast_rays(const RayBox<kFar>& box, const unsigne
     const int take = queue_take(mine, queued, lane, holds, ox, oy, oz);
     ox -= box.px, oy -= box.py, oz -= box.pz;
     bool arrived = false;
-    if (holds) arrived = ray_arrives_from(bits, home, box.W, box.W2, ox, oy, oz);
+    if (holds) arrived = ray_arrives_from<kDepth, kApart>(bits, home, box.W, box.W2, ox, oy, oz, words, depth);
     on_batch(take, arrived, (unsigned long long)__ballot(arrived), ox, oy, oz);
   }
 }

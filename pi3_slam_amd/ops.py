@@ -1326,6 +1326,7 @@ def grid_frontier_stats(state: torch.Tensor, label: torch.Tensor, dist: Optional
 # ---- views of the occupancy grid (csrc/grid_view.hip)
 VIEW_MAX_RANGE = 32                     # cells: the occupied bits of the (2 R + 1)^3 box live in LDS
 VIEW_FAR_MAX_RANGE = 64                 # cells, the far form: the bits of one octant's (R + 1)^3 box per workgroup
+VIEW_MAX_DEPTH = 255                    # unknown_depth: the unknown cells a ray may cross
 VIEW_MAX_HEADINGS = 32
 VIEW_MAX_AXIS = 1024                    # per component of a heading
 VIEW_COUNTERS = ("candidates", "rays", "rays_blocked", "rays_visible")
@@ -1355,6 +1356,17 @@ def _view_entry(lib, name: str, view_range: int, far: bool):
     if far or int(view_range) > VIEW_MAX_RANGE:
         name += "_far"
     return getattr(lib, name), name
+
+
+def _view_depth(unknown_depth) -> Optional[int]:
+    """unknown_depth as the depth entry points take it: None (the transparent entry points) or an integer in
+    0 .. VIEW_MAX_DEPTH."""
+    if unknown_depth is None:
+        return None
+    assert not isinstance(unknown_depth, bool) and int(unknown_depth) == unknown_depth, \
+        f"unknown_depth {unknown_depth!r}: None or an integer"
+    assert 0 <= int(unknown_depth) <= VIEW_MAX_DEPTH, f"unknown_depth {unknown_depth}: 0 .. {VIEW_MAX_DEPTH}"
+    return int(unknown_depth)
 
 
 VIEW_MARK_COUNTERS = ("views", "rays", "rays_visible", "in_cone", "new")
@@ -1391,8 +1403,9 @@ def _view_grid(state: torch.Tensor, seen: Optional[torch.Tensor]):
 
 
 def _view_gain(name: str, state, seen, candidates, view_range, headings, cos2_num, cos2_den, gain, visible, best,
-               counters, far) -> None:
-    """grid_view_gain (seen None) and grid_view_gain_unseen: the entry points differ in the mask argument."""
+               counters, far, unknown_depth=None) -> None:
+    """grid_view_gain (seen None) and grid_view_gain_unseen: the entry points differ in the mask argument.  With an
+    unknown_depth both go to pi3_grid_view_gain_depth, which takes the mask or NULL, the depth and the form."""
     lib = _L.load()
     nx, ny, nz = _view_grid(state, seen)
     dev = state.device
@@ -1404,44 +1417,52 @@ def _view_gain(name: str, state, seen, candidates, view_range, headings, cos2_nu
     for t in (visible, best):
         assert t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == (V,) and t.device == dev
     assert counters.dtype == torch.int64 and counters.is_contiguous() and counters.numel() >= 4 and counters.device == dev
-    entry, name = _view_entry(lib, name, view_range, far)
-    mask = () if seen is None else (seen.data_ptr(),)
-    rc = entry(state.data_ptr(), nx, ny, nz, *mask, candidates.data_ptr() if V else None, V, int(view_range), flat, H,
-               int(cos2_num), int(cos2_den), gain.data_ptr() if V else None, visible.data_ptr() if V else None,
+    depth = _view_depth(unknown_depth)
+    if depth is None:
+        entry, name = _view_entry(lib, name, view_range, far)
+        mask, form = () if seen is None else (seen.data_ptr(),), ()
+    else:
+        entry, name = lib.pi3_grid_view_gain_depth, "pi3_grid_view_gain_depth"
+        mask, form = (_L.ptr(seen),), (depth, int(bool(far) or int(view_range) > VIEW_MAX_RANGE))
+    rc = entry(state.data_ptr(), nx, ny, nz, *mask, candidates.data_ptr() if V else None, V, int(view_range), *form,
+               flat, H, int(cos2_num), int(cos2_den), gain.data_ptr() if V else None, visible.data_ptr() if V else None,
                best.data_ptr() if V else None, counters.data_ptr(), _L.stream_ptr())
     _L.check(rc, name)
 
 
 def grid_view_gain(state: torch.Tensor, candidates: torch.Tensor, view_range: int, headings, cos2_num: int,
                    cos2_den: int, gain: torch.Tensor, visible: torch.Tensor, best: torch.Tensor,
-                   counters: torch.Tensor, far: bool = False) -> None:
+                   counters: torch.Tensor, far: bool = False, unknown_depth: Optional[int] = None) -> None:
     """Per entry of candidates int64 (V,) (linear indices into state uint8 (nz,ny,nx)): visible int32 (V,) (the uint32
     values) = the unknown cells within view_range cells that no occupied cell hides, gain int32 (V,H) = those in the
     cone of each of the H integer axes `headings` (H,3) (x, y, z) at cos^2 of the half angle cos2_num / cos2_den, best
     int32 (V,) = the smallest heading of the largest gain (-1 and zeros for a candidate outside the grid).  counters
     int64 (4,) = VIEW_COUNTERS (zeroed by the call).  A view_range above VIEW_MAX_RANGE, up to VIEW_FAR_MAX_RANGE, goes
-    to the far entry point (the octant form of csrc/grid_view.hip); far=True sends any range there."""
+    to the far entry point (the octant form of csrc/grid_view.hip); far=True sends any range there.  unknown_depth K in
+    0 .. VIEW_MAX_DEPTH: a cell is visible only when at most K cells between it and the candidate are
+    unknown as well; rays_blocked then counts every ray that did not arrive.  None: unknown cells are transparent."""
     _view_gain("pi3_grid_view_gain", state, None, candidates, view_range, headings, cos2_num, cos2_den, gain, visible,
-               best, counters, far)
+               best, counters, far, unknown_depth)
 
 
 def grid_view_gain_unseen(state: torch.Tensor, seen: torch.Tensor, candidates: torch.Tensor, view_range: int, headings,
                           cos2_num: int, cos2_den: int, gain: torch.Tensor, visible: torch.Tensor, best: torch.Tensor,
-                          counters: torch.Tensor, far: bool = False) -> None:
+                          counters: torch.Tensor, far: bool = False, unknown_depth: Optional[int] = None) -> None:
     """grid_view_gain over the unknown cells whose bit of seen int32 (grid_view_seen_words(cells),) (the uint32 words) is
-    clear; every output keeps its shape and meaning, and with an all-zero mask its bytes.  view_range and far as there."""
+    clear; every output keeps its shape and meaning, and with an all-zero mask its bytes.  view_range, far and
+    unknown_depth as there."""
     _view_gain("pi3_grid_view_gain_unseen", state, seen, candidates, view_range, headings, cos2_num, cos2_den, gain,
-               visible, best, counters, far)
+               visible, best, counters, far, unknown_depth)
 
 
 def grid_view_mark(state: torch.Tensor, seen: torch.Tensor, cells: torch.Tensor, heading_of, view_range: int, headings,
                    cos2_num: int, cos2_den: int, counters: torch.Tensor, owner: Optional[torch.Tensor] = None,
-                   tag: int = 0, far: bool = False) -> None:
+                   tag: int = 0, far: bool = False, unknown_depth: Optional[int] = None) -> None:
     """Sets in seen int32 (grid_view_seen_words(cells),) the bit of every unknown cell within view_range cells of cells[i]
     (int64 (V,), linear indices on the device) that no occupied cell hides and that lies in the cone of heading
     heading_of[i] (V host integers in -1 .. H - 1; -1: in the cone of any heading).  owner int16 (nz,ny,nx), only with
     V == 1: the cells whose bit this call turned get `tag` (0 .. VIEW_MAX_TAG).  counters int64 (5,) =
-    VIEW_MARK_COUNTERS (zeroed by the call).  view_range and far as grid_view_gain's."""
+    VIEW_MARK_COUNTERS (zeroed by the call).  view_range, far and unknown_depth as grid_view_gain's."""
     lib = _L.load()
     nx, ny, nz = _view_grid(state, seen)
     dev = state.device
@@ -1455,9 +1476,14 @@ def grid_view_mark(state: torch.Tensor, seen: torch.Tensor, cells: torch.Tensor,
         assert owner.dtype == torch.int16 and owner.is_contiguous() and owner.shape == state.shape and owner.device == dev
         assert V == 1, f"an owner takes one row per call, got {V}"
     assert counters.dtype == torch.int64 and counters.is_contiguous() and counters.numel() >= 5 and counters.device == dev
-    entry, name = _view_entry(lib, "pi3_grid_view_mark", view_range, far)
+    depth = _view_depth(unknown_depth)
+    if depth is None:
+        (entry, name), form = _view_entry(lib, "pi3_grid_view_mark", view_range, far), ()
+    else:
+        entry, name = lib.pi3_grid_view_mark_depth, "pi3_grid_view_mark_depth"
+        form = (depth, int(bool(far) or int(view_range) > VIEW_MAX_RANGE))
     rc = entry(state.data_ptr(), nx, ny, nz, seen.data_ptr(), cells.data_ptr() if V else None,
-               hof.ctypes.data_as(C.POINTER(C.c_int)) if V else None, V, int(view_range), flat, H, int(cos2_num),
+               hof.ctypes.data_as(C.POINTER(C.c_int)) if V else None, V, int(view_range), *form, flat, H, int(cos2_num),
                int(cos2_den), _L.ptr(owner), int(tag), counters.data_ptr(), _L.stream_ptr())
     _L.check(rc, name)
 

@@ -10,7 +10,11 @@ near cells many times.  The gain of a heading is the number of visible unknown c
 directions, `fov_deg` wide); a candidate's best heading is the first of the largest gain.  The views are chosen
 greedily: gain descending, route cost ascending, cell ascending, no view within `separation_m` of a kept one.
 
-Limitations: unknown space is transparent, so the gain is an upper bound; poses are cell centres; 26 headings only; a
+unknown_depth=K (tests/grid_view_depth_ref.py) replaces the transparent rule: a ray also ends once more than
+K cells between its ends are unknown, so a view into a solid block of unknown space counts its first K + 1 layers and
+not the whole block.  Every step of find, cover and the tour's replay then casts by that rule.
+
+Limitations: unknown space is transparent unless unknown_depth is set, so the gain is an upper bound; poses are cell centres; 26 headings only; a
 cone, not a frustum, and no roll; the range is at most 32 cells, 64 with far=True (use a larger occupancy
 cell for more); unknown space outside the grid is not counted; nothing is updated incrementally in `find` (`cover`
 below does); the gain counts cells, not surface.  range_m, stride and fov_deg are starting points, not measured optima.
@@ -204,7 +208,9 @@ class ViewPlanner:
     max_distance_m: candidates farther by route are left out (default: none).  min_gain: candidates whose best heading
     sees fewer unknown cells are dropped and counted.  range_m, stride and fov_deg are starting points, not measured
     optima.  far: a range of up to 64 cells instead of 32 (the octant form of csrc/grid_view.hip, DESIGN §7m: the
-    same rules, roughly eight times the rays per pose at twice the range)."""
+    same rules, roughly eight times the rays per pose at twice the range).  unknown_depth: None (unknown cells are
+    transparent) or K in 0 .. 255, the unknown cells a ray may cross before it ends (a hard cap, not a decay; K >= 110 is
+    the transparent rule at every range).  A starting point, not a measured optimum; there is no default."""
     radius: float = 0.0
     range_m: float = 1.0
     fov_deg: float = 90.0
@@ -214,6 +220,7 @@ class ViewPlanner:
     max_distance_m: Optional[float] = None
     min_gain: int = 1
     far: bool = False
+    unknown_depth: Optional[int] = None
 
     CANDIDATES_FIRST_CAP = 1 << 16      # the candidate buffer of the first try; a grid with more asks again
 
@@ -241,6 +248,11 @@ class ViewPlanner:
                 raise ValueError(f"the largest distance must be a finite length >= 0, got {self.max_distance_m!r}")
         if not isinstance(self.far, bool):
             raise ValueError(f"far must be True or False, got {self.far!r}")
+        if self.unknown_depth is not None:
+            v = self.unknown_depth
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= ops.VIEW_MAX_DEPTH:
+                raise ValueError(f"unknown_depth must be an integer in 0 .. {ops.VIEW_MAX_DEPTH} or None, got {v!r}")
+            self.unknown_depth = int(v)
         self.cos2_den = ops.VIEW_COS2_DEN
         self.cos2_num = int(round(math.cos(math.radians(self.fov_deg) / 2.0) ** 2 * self.cos2_den))
 
@@ -251,6 +263,8 @@ class ViewPlanner:
               "unknown_is_transparent": True, "outside_is_counted": False, "router": self.router.settings()}
         if self.far:
             st["far"] = True                    # only when set: every record written without it keeps its bytes
+        if self.unknown_depth is not None:      # likewise
+            st.update(unknown_is_transparent=False, unknown_depth=self.unknown_depth)
         return st
 
     def cells_of(self, cell: float):
@@ -303,7 +317,8 @@ class ViewPlanner:
         visible = torch.empty(V, dtype=torch.int32, device=dev)
         best = torch.empty(V, dtype=torch.int32, device=dev)
         counters = torch.zeros(4, dtype=torch.int64, device=dev)
-        ops.grid_view_gain(state, cells, R, hd, self.cos2_num, self.cos2_den, gain, visible, best, counters)
+        ops.grid_view_gain(state, cells, R, hd, self.cos2_num, self.cos2_den, gain, visible, best, counters,
+                           unknown_depth=self.unknown_depth)
         counts = dict(zip(ops.VIEW_COUNTERS, (int(v) for v in counters.tolist())))
         if counts["candidates"] != V:
             raise RuntimeError(f"the gain kernel saw {counts['candidates']} of {V} candidates")
@@ -351,12 +366,13 @@ class ViewPlanner:
         hd = view_headings()
         H = len(hd)
         cone = (R, hd, self.cos2_num, self.cos2_den)
+        rule = dict(unknown_depth=self.unknown_depth)                       # every cast of the cover, by the one rule
         words = ops.grid_view_seen_words(state.numel())
         mark_counters = torch.zeros(len(ops.VIEW_MARK_COUNTERS), dtype=torch.int64, device=dev)
 
         # what any candidate sees in any heading, into a mask of its own
         everything = torch.zeros(words, dtype=torch.int32, device=dev)
-        ops.grid_view_mark(state, everything, cells, np.full(V, -1, np.int32), *cone, mark_counters)
+        ops.grid_view_mark(state, everything, cells, np.full(V, -1, np.int32), *cone, mark_counters, **rule)
         seeable = int(mark_counters[4].item())
         del everything
 
@@ -366,7 +382,7 @@ class ViewPlanner:
         visible = torch.empty(V, dtype=torch.int32, device=dev)
         best = torch.empty(V, dtype=torch.int32, device=dev)
         counters = torch.zeros(4, dtype=torch.int64, device=dev)
-        ops.grid_view_gain_unseen(state, seen, cells, *cone, gain, visible, best, counters)
+        ops.grid_view_gain_unseen(state, seen, cells, *cone, gain, visible, best, counters, **rule)
         counts = dict(zip(ops.VIEW_COUNTERS, (int(v) for v in counters.tolist())))
         if counts["candidates"] != V:
             raise RuntimeError(f"the gain kernel saw {counts['candidates']} of {V} candidates")
@@ -378,7 +394,7 @@ class ViewPlanner:
 
         def mark(k, row, h):
             visible_then.append(int(visible_np[row]))                       # under the mask the view was picked by
-            ops.grid_view_mark(state, seen, cells[row:row + 1], [h], *cone, mark_counters, owner, k)
+            ops.grid_view_mark(state, seen, cells[row:row + 1], [h], *cone, mark_counters, owner, k, **rule)
             c = mark_counters.tolist()                                      # the round's synchronisation
             mark_rays[0] += c[1]
             return c[4]
@@ -386,7 +402,7 @@ class ViewPlanner:
         def regain(rows):
             n = len(rows)
             sub = cells[torch.from_numpy(rows).to(dev)]
-            ops.grid_view_gain_unseen(state, seen, sub, *cone, gain[:n], visible[:n], best[:n], counters)
+            ops.grid_view_gain_unseen(state, seen, sub, *cone, gain[:n], visible[:n], best[:n], counters, **rule)
             visible_np[rows] = visible[:n].cpu().numpy()
             return gain[:n].cpu().numpy()
 

@@ -391,7 +391,8 @@ def plan_tour(vset, start_xyz=None, device=None, max_field_bytes: int = 2 << 30,
         for stop in stops:
             at = nodes[stop.number + 1:stop.number + 2]
             for r in stop.ranks:
-                ops.grid_view_mark(state, seen, at, [vset.views[r].heading], *cone, marks)
+                ops.grid_view_mark(state, seen, at, [vset.views[r].heading], *cone, marks,
+                                   unknown_depth=st.get("unknown_depth"))     # the rule the views were picked by
                 new = int(marks[4].item())
                 covered += new
                 stop.tour_new.append(new)

@@ -739,6 +739,25 @@ int pi3_grid_view_mark_depth(const unsigned char* state, int nx, int ny, int nz,
                              const int* heading_of, long V, int range, int depth, int far, const int* headings, int H,
                              long cos2_num, long cos2_den, short* owner, int tag, unsigned long long* counters,
                              void* stream);
+/* Views through a camera (csrc/grid_view.hip): the ray entry points with a frustum per heading instead of
+ * a cone.  frames: HOST int [H][6], 1 <= H <= 32, row h = f (forward) then r (right): both non-zero, f.r = 0, every
+ * component within +-64 (read during the call and passed to the kernel by value); u = f x r.  Offset o = u_cell - v
+ * lies in frame h's frustum when o.f > 0, (o.r)^2 |f|^2 hd <= hn (o.f)^2 |r|^2 and (o.u)^2 vd <= vn (o.f)^2 |r|^2, in
+ * 64 bits, the faces inclusive: tan^2 of half the horizontal and the vertical field of view are hn / hd and vn / vd
+ * with 0 <= num <= 2^20 and 1 <= den <= 2^20.  Only directions matter: a positive multiple of f or r, or -r, gives
+ * the same bytes.  depth: -1 for transparent unknown space, else 0..255 as pi3_grid_view_gain_depth; far and seen
+ * (NULL: every unknown cell is a target) as there.  Every other argument, output and counter is its namesake's, with
+ * "in the cone" read as "in the frustum"; heading -1 of a mark row is "inside any frame's frustum".  Bad arguments
+ * return PI3_ERR_ARG with every rule in the message and launch nothing; V == 0 launches no kernel.  The LDS opt-in is
+ * the depth entry points'. */
+int pi3_grid_view_gain_frustum(const unsigned char* state, int nx, int ny, int nz, const unsigned* seen,
+                               const long* candidates, long V, int range, int depth, int far, const int* frames, int H,
+                               long tan2_h_num, long tan2_h_den, long tan2_v_num, long tan2_v_den, unsigned* gain,
+                               unsigned* visible, int* best, unsigned long long* counters, void* stream);
+int pi3_grid_view_mark_frustum(const unsigned char* state, int nx, int ny, int nz, unsigned* seen, const long* cells,
+                               const int* heading_of, long V, int range, int depth, int far, const int* frames, int H,
+                               long tan2_h_num, long tan2_h_den, long tan2_v_num, long tan2_v_den, short* owner, int tag,
+                               unsigned long long* counters, void* stream);
 
 /* ---- nearest neighbours between two point clouds (csrc/cloud_nn.hip): an exact radius-bounded search through a
  * uniform grid of cells, for scoring a map against a reference cloud (map_eval.py).  The grid is a hash table of cells

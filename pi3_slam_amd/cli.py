@@ -14,6 +14,7 @@
          [--radius 0.2] [--min-cells 20] [--route-to 0 [--taut]]
   python -m pi3_slam_amd.cli views --occupancy OUT/occupancy.npz --output DIR --from-trajectory OUT/trajectory_tum.txt \\
          [--radius 0.2] [--range 1.0 [--far]] [--unknown-depth K] [--fov 90] [--stride 4] [--count 10] [--route-to 0] \\
+         [--frustum HFOV VFOV [--yaw-steps 8] [--pitch DEG ...] [--up 0 -1 0] [--portrait] [--view-image-width 640]] \\
          [--cover [--cover-until 0.9]] [--tour [--tour-from X Y Z]] [--taut [--taut-span 256]]
 
 Under `python -m torch.distributed.run --nproc-per-node G -m pi3_slam_amd.cli ...` every stage shards over the G GPUs.
@@ -337,6 +338,14 @@ FRONTIER_FLAGS: Sequence[Tuple[str, Dict]] = (
 
 
 # views: this build's own sub-command (view_planner.py) on the same file
+class _Given(argparse.Action):
+    """Stores the value and notes that the flag was given (`<dest>_given`): a default cannot tell."""
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        setattr(namespace, self.dest, values)
+        setattr(namespace, self.dest + "_given", True)
+
+
 VIEW_FLAGS: Sequence[Tuple[str, Dict]] = (
     ("--occupancy", dict(REQ, help="occupancy.npz of `reconstruct` or `online` (--occupancy-cell)")),
     ("--output", dict(REQ, help="directory for views.json, views.npz and views.ply and, with --route-to, route.json, "
@@ -353,8 +362,24 @@ VIEW_FLAGS: Sequence[Tuple[str, Dict]] = (
                                   "target, so a view counts the first layers of a block of unknown space and not the "
                                   "whole block (default: none, unknown cells are transparent; whatever K you pick is where "
                                   "to start, no measured optimum, and 110 or more is the transparent rule)")),
-    ("--fov", dict(type=float, default=90.0, help="the full opening angle of the viewing cone in degrees, in (0, 180] "
-                                                  "(default 90: a starting point, not a measured optimum)")),
+    ("--fov", dict(type=float, default=90.0, action=_Given, help="the full opening angle of the viewing cone in degrees, in (0, 180] "
+                                                  "(default 90: a starting point, not a measured optimum; not with "
+                                                  "--frustum)")),
+    ("--frustum", dict(type=float, nargs=2, default=None, metavar=("HFOV", "VFOV"),
+                       help="views through the camera that will be carried instead of cones: its horizontal and vertical "
+                            "field of view in degrees, each in [2, 170] (90 67.5 is a 4:3 frame).  The headings are "
+                            "--yaw-steps yaws at every --pitch; every view gets a frame and a 4x4 camera-to-world pose, "
+                            "and the settings the intrinsics that go with it (default: none, 26 cones of --fov)")),
+    ("--yaw-steps", dict(type=int, default=8, metavar="N", help="with --frustum: the yaws per pitch, 360 / N degrees apart "
+                                                                 "(default 8; N times the pitches is at most 32)")),
+    ("--pitch", dict(type=float, nargs="+", default=[0.0], metavar="DEG",
+                     help="with --frustum: the pitches in degrees, towards --up (default 0)")),
+    ("--up", dict(type=int, nargs=3, default=[0, -1, 0], metavar=("X", "Y", "Z"),
+                  help="with --frustum: the world's up, one of the six signed axes.  A convention, not a measurement: the "
+                       "world is the first camera's frame, whose y points down (default 0 -1 0)")),
+    ("--view-image-width", dict(type=int, default=640, metavar="W",
+                                help="with --frustum: the width in pixels of the intrinsics written to the settings; the "
+                                     "height follows from the two angles (default 640)")),
     ("--stride", dict(type=int, default=4, help="every stride-th reachable cell per axis is a candidate pose (default "
                                                 "4: a starting point, not a measured optimum)")),
     ("--count", dict(type=int, default=10, help="the views to keep at most (default 10)")),
@@ -382,6 +407,7 @@ VIEW_SWITCHES: Sequence[Tuple[str, str]] = (
                "the shortest open path from the start, exact up to 12 stops, nearest neighbour and 2-opt above"),
     ("--far", "let --range reach 64 occupancy cells instead of 32: the rays are cast octant by octant around the pose, by "
               "the same rules; twice the range is roughly eight times the rays per pose, so widen --stride with it"),
+    ("--portrait", "with --frustum: the camera turned a quarter about its axis, so the two angles change places"),
 )
 
 
@@ -679,8 +705,11 @@ def run_views(a: argparse.Namespace) -> None:
         raise SystemExit("views: --tour-from needs --tour")
     check_taut(a, "views", "--route-to RANK or --tour", a.route_to is not None or a.tour)
     try:
-        planner = ViewPlanner(a.radius, a.range, a.fov, a.stride, a.count, a.separation, a.max_distance, a.min_gain,
-                              a.far, a.unknown_depth)
+        camera = {} if a.frustum is None else dict(frustum=tuple(a.frustum), yaw_steps=a.yaw_steps, pitches_deg=a.pitch,
+                                                   up=a.up, portrait=a.portrait, image_width=a.view_image_width)
+        fov = a.fov if a.frustum is None or getattr(a, "fov_given", False) else None     # a frustum has its own angles
+        planner = ViewPlanner(a.radius, a.range, fov, a.stride, a.count, a.separation, a.max_distance, a.min_gain,
+                              a.far, a.unknown_depth, **camera)
         grid = export.read_occupancy(a.occupancy)
         sources = [a.start] if a.start is not None else read_tum_positions(a.from_trajectory)
         if a.cover:
@@ -702,6 +731,8 @@ def run_views(a: argparse.Namespace) -> None:
             f"kept ({c['low_gain']} candidates below the gain)")
     if a.unknown_depth is not None:
         text += f"; rays end after {a.unknown_depth} unknown cells"
+    if a.frustum is not None:
+        text += f"; {len(planner.frames)} frusta of {a.frustum[0]:g} x {a.frustum[1]:g} degrees"
     if found.views:
         best = found.views[0]
         text += f"; the best: {best.gain} cells at {best.distance_m:.3f} m"

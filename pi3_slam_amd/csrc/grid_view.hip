@@ -61,11 +61,13 @@
 namespace {
 
 using grid_tile::grid_ok;
+using grid_view_ray::Frames;
 using grid_view_ray::Headings;
 using grid_view_ray::kFarMaxRange;
 using grid_view_ray::kMarkRows;
 using grid_view_ray::kMarkTally;
 using grid_view_ray::kMaxDepth;
+using grid_view_ray::kMaxFrame;
 using grid_view_ray::kMaxAxis;
 using grid_view_ray::kMaxHeadings;
 using grid_view_ray::kMaxRange;
@@ -112,12 +114,13 @@ __global__ __launch_bounds__(256) void view_candidates_kernel(const unsigned* __
 // target only when its bit of `seen` is clear (pi3_grid_view_gain_unseen); `seen` is not read otherwise.  Near: gain,
 // visible and best are stored.  Far: gain, visible and the counters were zeroed by the entry point and take atomic
 // sums; best is view_best_kernel's.  kDepth: R carries range | K << 8, and the LDS holds two planes (kApart: one
-// behind the other, development build only).
-template <bool kUnseen, bool kFar, bool kDepth = false, bool kApart = false>
+// behind the other, development build only).  Table: Headings (cones) or Frames (frusta; `den` is then the
+// vertical fraction's denominator); grid_view_ray::in_view is the only place where the two differ.
+template <bool kUnseen, bool kFar, bool kDepth = false, bool kApart = false, class Table = Headings>
 __global__ __launch_bounds__(256) void view_gain_kernel(const unsigned char* __restrict__ state, int nx, int ny, int nz,
                                                         const unsigned* __restrict__ seen,
                                                         const long* __restrict__ candidates, int R, int H,
-                                                        const Headings hd, long long den, unsigned* gain,
+                                                        const Table hd, long long den, unsigned* gain,
                                                         unsigned* visible, int* __restrict__ best, u64* counters) {
   extern __shared__ unsigned lds[];                           // kTally words, a queue per wave, the box's occupied bits
   const int range = kDepth ? R & 255 : R, depth = kDepth ? R >> 8 : 0;
@@ -153,7 +156,7 @@ __global__ __launch_bounds__(256) void view_gain_kernel(const unsigned char* __r
         if (arrived_b) {                                      // the same in every lane of the wave
           const long long o2l = ox * ox + oy * oy + oz * oz;
           for (int h = 0; h < H; ++h) {
-            const u64 b = __ballot(grid_view_ray::in_cone(hd, h, den, ox, oy, oz, o2l) && arrived);
+            const u64 b = __ballot(grid_view_ray::in_view(hd, h, den, ox, oy, oz, o2l) && arrived);
             if (lane == 0 && b) atomicAdd(&tally[h], (unsigned)__popcll(b));
           }
         }
@@ -207,11 +210,11 @@ __global__ __launch_bounds__(256) void view_best_kernel(const long* __restrict__
 // queue and DDA with every unknown cell of the ball a target (the mask does not thin the rays).  A lane whose ray
 // arrived inside the row's cone reads the cell's word of `seen` and, only when the bit is clear, ORs it in; the bit is
 // new when the returned word had it clear, so of several rows that race for one cell exactly one counts it.  owner is
-// written by that lane alone.  kDepth and kApart as the gain kernel's.
-template <bool kFar, bool kDepth = false, bool kApart = false>
+// written by that lane alone.  kDepth, kApart and Table as the gain kernel's.
+template <bool kFar, bool kDepth = false, bool kApart = false, class Table = Headings>
 __global__ __launch_bounds__(256) void view_mark_kernel(const unsigned char* __restrict__ state, int nx, int ny, int nz,
                                                         unsigned* seen, const long* __restrict__ cells_in,
-                                                        const MarkRows rows, int same, int R, int H, const Headings hd,
+                                                        const MarkRows rows, int same, int R, int H, const Table hd,
                                                         long long den, short* owner, int tag, u64* counters) {
   extern __shared__ unsigned lds[];                           // kMarkTally words, a queue per wave, the occupied bits
   const int range = kDepth ? R & 255 : R, depth = kDepth ? R >> 8 : 0;
@@ -242,9 +245,9 @@ __global__ __launch_bounds__(256) void view_mark_kernel(const unsigned char* __r
         if (arrived_b) {                                      // the same in every lane of the wave
           const long long o2l = ox * ox + oy * oy + oz * oz;
           if (heading >= 0) {
-            in = grid_view_ray::in_cone(hd, heading, den, ox, oy, oz, o2l) && arrived;
+            in = grid_view_ray::in_view(hd, heading, den, ox, oy, oz, o2l) && arrived;
           } else {
-            for (int h = 0; h < H; ++h) in = in || (grid_view_ray::in_cone(hd, h, den, ox, oy, oz, o2l) && arrived);
+            for (int h = 0; h < H; ++h) in = in || (grid_view_ray::in_view(hd, h, den, ox, oy, oz, o2l) && arrived);
           }
           if (in) {                                           // a target: inside the grid, so u < cells
             const long u = ((long)(vz + oz) * ny + (vy + oy)) * nx + (vx + ox);
@@ -282,10 +285,17 @@ struct Form {
   bool far;
   bool deep = false;
   int depth = 0;
-  char depth_text[40] = "";                                   // " depth=K (0 .. 255)" in the depth form's messages
+  char depth_text[48] = "";                                   // " depth=K (0 .. 255)" in the depth form's messages
   Form(const char* who_, bool far_) : who(who_), far(far_) {}
   Form(const char* who_, int far_, int depth_) : who(who_), far(far_ != 0), deep(true), depth(depth_) {
     snprintf(depth_text, sizeof depth_text, " depth=%d (0 .. %d)", depth, kMaxDepth);
+  }
+  // the frustum entry points' depth: -1 is the transparent form
+  static Form or_transparent(const char* who_, int far_, int depth_) {
+    Form form(who_, far_, depth_);
+    form.deep = depth_ != -1;
+    snprintf(form.depth_text, sizeof form.depth_text, " depth=%d (-1: transparent, else 0 .. %d)", depth_, kMaxDepth);
+    return form;
   }
   bool depth_ok() const { return !deep || (depth >= 0 && depth <= kMaxDepth); }
   int max_range() const { return far ? kFarMaxRange : kMaxRange; }
@@ -311,21 +321,35 @@ struct DepthLaunch {
   Kernel kernel;
   int (*optin)(size_t bytes, size_t most, const char* what);
 };
-using GainKernel = decltype(&view_gain_kernel<false, false>);
-using MarkKernel = decltype(&view_mark_kernel<false>);
+template <class Table>
+using GainKernel = decltype(&view_gain_kernel<false, false, false, false, Table>);
+template <class Table>
+using MarkKernel = decltype(&view_mark_kernel<false, false, false, Table>);
 
-template <bool kApart>
-DepthLaunch<GainKernel> depth_gain(bool unseen, bool far) {
-#define PI3_VIEW_GAIN(U, F) DepthLaunch<GainKernel>{view_gain_kernel<U, F, true, kApart>, depth_optin<view_gain_kernel<U, F, true, kApart>>}
+template <class Table>
+GainKernel<Table> plain_gain(bool unseen, bool far) {
+  return far ? (unseen ? view_gain_kernel<true, true, false, false, Table> : view_gain_kernel<false, true, false, false, Table>)
+             : (unseen ? view_gain_kernel<true, false, false, false, Table>
+                       : view_gain_kernel<false, false, false, false, Table>);
+}
+
+template <class Table>
+MarkKernel<Table> plain_mark(bool far) {
+  return far ? view_mark_kernel<true, false, false, Table> : view_mark_kernel<false, false, false, Table>;
+}
+
+template <bool kApart, class Table>
+DepthLaunch<GainKernel<Table>> depth_gain(bool unseen, bool far) {
+#define PI3_VIEW_GAIN(U, F) DepthLaunch<GainKernel<Table>>{view_gain_kernel<U, F, true, kApart, Table>, depth_optin<view_gain_kernel<U, F, true, kApart, Table>>}
   return far ? (unseen ? PI3_VIEW_GAIN(true, true) : PI3_VIEW_GAIN(false, true))
              : (unseen ? PI3_VIEW_GAIN(true, false) : PI3_VIEW_GAIN(false, false));
 #undef PI3_VIEW_GAIN
 }
 
-template <bool kApart>
-DepthLaunch<MarkKernel> depth_mark(bool far) {
-  if (far) return {view_mark_kernel<true, true, kApart>, depth_optin<view_mark_kernel<true, true, kApart>>};
-  return {view_mark_kernel<false, true, kApart>, depth_optin<view_mark_kernel<false, true, kApart>>};
+template <bool kApart, class Table>
+DepthLaunch<MarkKernel<Table>> depth_mark(bool far) {
+  if (far) return {view_mark_kernel<true, true, kApart, Table>, depth_optin<view_mark_kernel<true, true, kApart, Table>>};
+  return {view_mark_kernel<false, true, kApart, Table>, depth_optin<view_mark_kernel<false, true, kApart, Table>>};
 }
 
 // the planes one behind the other: the development build alone has that form (PI3_VIEW_DEPTH_APART=1); the product
@@ -337,21 +361,64 @@ constexpr bool kDevVariants = false;
 #endif
 bool planes_apart() { return PI3_DEV_ENV_INT("PI3_VIEW_DEPTH_APART", 0) != 0; }
 
-// the four gain entry points and the depth form's one: seen == nullptr unless unseen
+// What an entry point tests the rays that arrived against, on the host: the kernels' table type, the checks that fill
+// it (with the arguments every ray entry point has), the kernels' `den`, and its part of the error message (`rows`: what
+// mark adds about its rows' headings).  Cones: every entry point but the _frustum ones.
+struct Cones {
+  using Table = Headings;
+  const int* headings;
+  int H;
+  long num, den;
+  bool ok(const Form& form, const unsigned char* state, int nx, int ny, int nz, long& cells, long V, int range,
+          const unsigned long long* counters, Table& hd) const {
+    return grid_view_ray::view_rays_ok(state, nx, ny, nz, cells, V, range, form.max_range(), headings, H, num, den,
+                                       counters, hd) &&
+           grid_view_ray::cone_fits(range, hd, H, den);
+  }
+  long long kernel_den() const { return den; }
+  void rules(char* text, size_t n, const Form& form, const char* rows) const {
+    snprintf(text, n, "H=%d (1 .. %d; every axis non-zero, components within +-%d%s) cos2=%ld/%ld (0 <= num <= den, "
+             "0 < den < 2^31%s)", H, kMaxHeadings, kMaxAxis, rows, num, den, form.cone_rule());
+  }
+};
+
+// Frusta: frames of f then r and the two tan^2 fractions; no rule depends on the range.
+struct Frusta {
+  using Table = Frames;
+  const int* frames;
+  int H;
+  long hn, hd, vn, vd;
+  bool ok(const Form& form, const unsigned char* state, int nx, int ny, int nz, long& cells, long V, int range,
+          const unsigned long long* counters, Table& fr) const {
+    return grid_view_ray::view_grid_ok(state, nx, ny, nz, cells, V, range, form.max_range(), counters) &&
+           grid_view_ray::view_frames_ok(frames, H, hn, hd, vn, vd, fr);
+  }
+  long long kernel_den() const { return vd; }
+  void rules(char* text, size_t n, const Form&, const char* rows) const {
+    snprintf(text, n, "H=%d (1 .. %d; every frame f then r: both non-zero, f.r = 0, components within +-%d%s) "
+             "tan2_h=%ld/%ld tan2_v=%ld/%ld (0 <= num <= 2^20, 1 <= den <= 2^20)", H, kMaxHeadings, kMaxFrame, rows, hn,
+             hd, vn, vd);
+  }
+};
+
+// every gain entry point: seen == nullptr unless unseen
+template <class Shape>
 int view_gain(Form form, bool unseen, const unsigned char* state, int nx, int ny, int nz, const unsigned* seen,
-              const long* candidates, long V, int range, const int* headings, int H, long cos2_num, long cos2_den,
-              unsigned* gain, unsigned* visible, int* best, unsigned long long* counters, void* stream) {
+              const long* candidates, long V, int range, const Shape shape, unsigned* gain, unsigned* visible, int* best,
+              unsigned long long* counters, void* stream) {
+  using Table = typename Shape::Table;
   const char* who = form.who;
+  const int H = shape.H;
   long cells = 0;
-  Headings hd = {};
-  const bool ok = grid_view_ray::view_rays_ok(state, nx, ny, nz, cells, V, range, form.max_range(), headings, H, cos2_num,
-                                              cos2_den, counters, hd) &&
+  Table hd = {};
+  const bool ok = shape.ok(form, state, nx, ny, nz, cells, V, range, counters, hd) &&
                   (V == 0 || (candidates && gain && visible && best)) && (!unseen || seen) && form.depth_ok();
-  if (!ok || !grid_view_ray::cone_fits(range, hd, H, cos2_den)) {
+  if (!ok) {
+    char rules[384];
+    shape.rules(rules, sizeof rules, form, "");
     pi3_set_error("%s: bad arguments dims=(%d, %d, %d) (1 .. 2^21 - 1 each, at most 2^27 cells) V=%ld "
-                  "(0 .. 2^31 - 1) range=%d (1 .. %d)%s H=%d (1 .. %d; every axis non-zero, components within +-%d) "
-                  "cos2=%ld/%ld (0 <= num <= den, 0 < den < 2^31%s), or a null pointer", who, nx, ny, nz, V, range,
-                  form.max_range(), form.depth_text, H, kMaxHeadings, kMaxAxis, cos2_num, cos2_den, form.cone_rule());
+                  "(0 .. 2^31 - 1) range=%d (1 .. %d)%s %s, or a null pointer", who, nx, ny, nz, V, range,
+                  form.max_range(), form.depth_text, rules);
     return PI3_ERR_ARG;
   }
   const hipStream_t s = (hipStream_t)stream;
@@ -362,15 +429,15 @@ int view_gain(Form form, bool unseen, const unsigned char* state, int nx, int ny
     pi3_set_error("%s: hipMemsetAsync failed", who);
     return PI3_ERR_LAUNCH;
   }
-  auto kernel = form.far ? (unseen ? view_gain_kernel<true, true> : view_gain_kernel<false, true>)
-                         : (unseen ? view_gain_kernel<true, false> : view_gain_kernel<false, false>);
+  auto kernel = plain_gain<Table>(unseen, form.far);
   if (form.deep) {
-    const auto deep = planes_apart() ? depth_gain<kDevVariants>(unseen, form.far) : depth_gain<false>(unseen, form.far);
+    const auto deep = planes_apart() ? depth_gain<kDevVariants, Table>(unseen, form.far)
+                                     : depth_gain<false, Table>(unseen, form.far);
     if (int rc = deep.optin(form.lds_bytes(kTally, range), form.lds_bytes(kTally, form.max_range()), who + 4)) return rc;
     kernel = deep.kernel;
   }
   hipLaunchKernelGGL(kernel, form.grid(V), dim3(256), form.lds_bytes(kTally, range), s, state, nx, ny, nz, seen,
-                     candidates, form.kernel_range(range), H, hd, (long long)cos2_den, gain, visible, best,
+                     candidates, form.kernel_range(range), H, hd, shape.kernel_den(), gain, visible, best,
                      (u64*)counters);
   const int rc = pi3_check_launch(who + 4);   // without "pi3_"
   if (rc != PI3_OK || !form.far) return rc;
@@ -379,23 +446,24 @@ int view_gain(Form form, bool unseen, const unsigned char* state, int nx, int ny
   return pi3_check_launch(who + 4);
 }
 
-// the two mark entry points and the depth form's one
+// every mark entry point
+template <class Shape>
 int view_mark(Form form, const unsigned char* state, int nx, int ny, int nz, unsigned* seen, const long* cells_in,
-              const int* heading_of, long V, int range, const int* headings, int H, long cos2_num, long cos2_den,
-              short* owner, int tag, unsigned long long* counters, void* stream) {
+              const int* heading_of, long V, int range, const Shape shape, short* owner, int tag,
+              unsigned long long* counters, void* stream) {
+  using Table = typename Shape::Table;
+  const int H = shape.H;
   long cells = 0;
-  Headings hd = {};
-  bool ok = grid_view_ray::view_rays_ok(state, nx, ny, nz, cells, V, range, form.max_range(), headings, H, cos2_num,
-                                        cos2_den, counters, hd) &&
-            seen && (V == 0 || (cells_in && heading_of)) && tag >= 0 && tag < 32768 && (!owner || V == 1) &&
-            form.depth_ok();
+  Table hd = {};
+  bool ok = shape.ok(form, state, nx, ny, nz, cells, V, range, counters, hd) && seen &&
+            (V == 0 || (cells_in && heading_of)) && tag >= 0 && tag < 32768 && (!owner || V == 1) && form.depth_ok();
   for (long i = 0; ok && i < V; ++i) ok = heading_of[i] >= -1 && heading_of[i] < H;
-  if (!ok || !grid_view_ray::cone_fits(range, hd, H, cos2_den)) {
+  if (!ok) {
+    char rules[384];
+    shape.rules(rules, sizeof rules, form, "; every row's heading in -1 .. H - 1");
     pi3_set_error("%s: bad arguments dims=(%d, %d, %d) (1 .. 2^21 - 1 each, at most 2^27 cells) V=%ld "
-                  "(0 .. 2^31 - 1; 1 with an owner) range=%d (1 .. %d)%s H=%d (1 .. %d; every axis non-zero, components "
-                  "within +-%d; every row's heading in -1 .. H - 1) cos2=%ld/%ld (0 <= num <= den, 0 < den < 2^31%s) "
-                  "tag=%d (0 .. 32767), or a null pointer", form.who, nx, ny, nz, V, range, form.max_range(),
-                  form.depth_text, H, kMaxHeadings, kMaxAxis, cos2_num, cos2_den, form.cone_rule(), tag);
+                  "(0 .. 2^31 - 1; 1 with an owner) range=%d (1 .. %d)%s %s tag=%d (0 .. 32767), or a null pointer",
+                  form.who, nx, ny, nz, V, range, form.max_range(), form.depth_text, rules, tag);
     return PI3_ERR_ARG;
   }
   if (pi3_zero_words(form.who, counters, 1 + kMarkTally, stream) != PI3_OK) return PI3_ERR_LAUNCH;
@@ -405,9 +473,9 @@ int view_mark(Form form, const unsigned char* state, int nx, int ny, int nz, uns
   for (long i = 1; same && i < V; ++i) same = heading_of[i] == heading_of[0];
   const long step = same ? V : kMarkRows;
   MarkRows rows;
-  auto kernel = form.far ? view_mark_kernel<true> : view_mark_kernel<false>;
+  auto kernel = plain_mark<Table>(form.far);
   if (form.deep && V > 0) {
-    const auto deep = planes_apart() ? depth_mark<kDevVariants>(form.far) : depth_mark<false>(form.far);
+    const auto deep = planes_apart() ? depth_mark<kDevVariants, Table>(form.far) : depth_mark<false, Table>(form.far);
     if (int rc = deep.optin(form.lds_bytes(kMarkTally, range), form.lds_bytes(kMarkTally, form.max_range()), form.who + 4))
       return rc;
     kernel = deep.kernel;
@@ -417,7 +485,7 @@ int view_mark(Form form, const unsigned char* state, int nx, int ny, int nz, uns
     for (int i = 0; i < kMarkRows; ++i) rows.heading[i] = (signed char)(i < n ? heading_of[base + i] : -1);
     hipLaunchKernelGGL(kernel, form.grid(n), dim3(256), form.lds_bytes(kMarkTally, range), (hipStream_t)stream, state,
                        nx, ny, nz, seen, cells_in + base, rows, same ? 1 : 0, form.kernel_range(range), H, hd,
-                       (long long)cos2_den, owner, tag, (u64*)counters);
+                       shape.kernel_den(), owner, tag, (u64*)counters);
     const int rc = pi3_check_launch(form.who + 4);            // without "pi3_"
     if (rc != PI3_OK) return rc;
   }
@@ -445,47 +513,41 @@ extern "C" int pi3_grid_view_candidates(const unsigned* dist, int nx, int ny, in
 extern "C" int pi3_grid_view_gain(const unsigned char* state, int nx, int ny, int nz, const long* candidates, long V,
                                   int range, const int* headings, int H, long cos2_num, long cos2_den, unsigned* gain,
                                   unsigned* visible, int* best, unsigned long long* counters, void* stream) {
-  return view_gain({"pi3_grid_view_gain", false}, false, state, nx, ny, nz, nullptr, candidates, V, range, headings, H,
-                   cos2_num, cos2_den, gain, visible, best, counters, stream);
+  return view_gain({"pi3_grid_view_gain", false}, false, state, nx, ny, nz, nullptr, candidates, V, range, Cones{headings, H, cos2_num, cos2_den}, gain, visible, best, counters, stream);
 }
 
 extern "C" int pi3_grid_view_gain_unseen(const unsigned char* state, int nx, int ny, int nz, const unsigned* seen,
                                          const long* candidates, long V, int range, const int* headings, int H,
                                          long cos2_num, long cos2_den, unsigned* gain, unsigned* visible, int* best,
                                          unsigned long long* counters, void* stream) {
-  return view_gain({"pi3_grid_view_gain_unseen", false}, true, state, nx, ny, nz, seen, candidates, V, range, headings, H,
-                   cos2_num, cos2_den, gain, visible, best, counters, stream);
+  return view_gain({"pi3_grid_view_gain_unseen", false}, true, state, nx, ny, nz, seen, candidates, V, range, Cones{headings, H, cos2_num, cos2_den}, gain, visible, best, counters, stream);
 }
 
 extern "C" int pi3_grid_view_mark(const unsigned char* state, int nx, int ny, int nz, unsigned* seen, const long* cells_in,
                                   const int* heading_of, long V, int range, const int* headings, int H, long cos2_num,
                                   long cos2_den, short* owner, int tag, unsigned long long* counters, void* stream) {
-  return view_mark({"pi3_grid_view_mark", false}, state, nx, ny, nz, seen, cells_in, heading_of, V, range, headings, H,
-                   cos2_num, cos2_den, owner, tag, counters, stream);
+  return view_mark({"pi3_grid_view_mark", false}, state, nx, ny, nz, seen, cells_in, heading_of, V, range, Cones{headings, H, cos2_num, cos2_den}, owner, tag, counters, stream);
 }
 
 extern "C" int pi3_grid_view_gain_far(const unsigned char* state, int nx, int ny, int nz, const long* candidates, long V,
                                       int range, const int* headings, int H, long cos2_num, long cos2_den,
                                       unsigned* gain, unsigned* visible, int* best, unsigned long long* counters,
                                       void* stream) {
-  return view_gain({"pi3_grid_view_gain_far", true}, false, state, nx, ny, nz, nullptr, candidates, V, range, headings, H,
-                   cos2_num, cos2_den, gain, visible, best, counters, stream);
+  return view_gain({"pi3_grid_view_gain_far", true}, false, state, nx, ny, nz, nullptr, candidates, V, range, Cones{headings, H, cos2_num, cos2_den}, gain, visible, best, counters, stream);
 }
 
 extern "C" int pi3_grid_view_gain_unseen_far(const unsigned char* state, int nx, int ny, int nz, const unsigned* seen,
                                              const long* candidates, long V, int range, const int* headings, int H,
                                              long cos2_num, long cos2_den, unsigned* gain, unsigned* visible, int* best,
                                              unsigned long long* counters, void* stream) {
-  return view_gain({"pi3_grid_view_gain_unseen_far", true}, true, state, nx, ny, nz, seen, candidates, V, range, headings,
-                   H, cos2_num, cos2_den, gain, visible, best, counters, stream);
+  return view_gain({"pi3_grid_view_gain_unseen_far", true}, true, state, nx, ny, nz, seen, candidates, V, range, Cones{headings, H, cos2_num, cos2_den}, gain, visible, best, counters, stream);
 }
 
 extern "C" int pi3_grid_view_mark_far(const unsigned char* state, int nx, int ny, int nz, unsigned* seen,
                                       const long* cells_in, const int* heading_of, long V, int range, const int* headings,
                                       int H, long cos2_num, long cos2_den, short* owner, int tag,
                                       unsigned long long* counters, void* stream) {
-  return view_mark({"pi3_grid_view_mark_far", true}, state, nx, ny, nz, seen, cells_in, heading_of, V, range, headings, H,
-                   cos2_num, cos2_den, owner, tag, counters, stream);
+  return view_mark({"pi3_grid_view_mark_far", true}, state, nx, ny, nz, seen, cells_in, heading_of, V, range, Cones{headings, H, cos2_num, cos2_den}, owner, tag, counters, stream);
 }
 
 extern "C" int pi3_grid_view_gain_depth(const unsigned char* state, int nx, int ny, int nz, const unsigned* seen,
@@ -493,7 +555,7 @@ extern "C" int pi3_grid_view_gain_depth(const unsigned char* state, int nx, int 
                                         const int* headings, int H, long cos2_num, long cos2_den, unsigned* gain,
                                         unsigned* visible, int* best, unsigned long long* counters, void* stream) {
   return view_gain({"pi3_grid_view_gain_depth", far, depth}, seen != nullptr, state, nx, ny, nz, seen, candidates, V,
-                   range, headings, H, cos2_num, cos2_den, gain, visible, best, counters, stream);
+                   range, Cones{headings, H, cos2_num, cos2_den}, gain, visible, best, counters, stream);
 }
 
 extern "C" int pi3_grid_view_mark_depth(const unsigned char* state, int nx, int ny, int nz, unsigned* seen,
@@ -501,5 +563,25 @@ extern "C" int pi3_grid_view_mark_depth(const unsigned char* state, int nx, int 
                                         const int* headings, int H, long cos2_num, long cos2_den, short* owner, int tag,
                                         unsigned long long* counters, void* stream) {
   return view_mark({"pi3_grid_view_mark_depth", far, depth}, state, nx, ny, nz, seen, cells_in, heading_of, V, range,
-                   headings, H, cos2_num, cos2_den, owner, tag, counters, stream);
+                   Cones{headings, H, cos2_num, cos2_den}, owner, tag, counters, stream);
+}
+
+extern "C" int pi3_grid_view_gain_frustum(const unsigned char* state, int nx, int ny, int nz, const unsigned* seen,
+                                          const long* candidates, long V, int range, int depth, int far, const int* frames,
+                                          int H, long tan2_h_num, long tan2_h_den, long tan2_v_num, long tan2_v_den,
+                                          unsigned* gain, unsigned* visible, int* best, unsigned long long* counters,
+                                          void* stream) {
+  return view_gain(Form::or_transparent("pi3_grid_view_gain_frustum", far, depth), seen != nullptr, state, nx, ny, nz, seen,
+                   candidates, V, range, Frusta{frames, H, tan2_h_num, tan2_h_den, tan2_v_num, tan2_v_den}, gain, visible,
+                   best, counters, stream);
+}
+
+extern "C" int pi3_grid_view_mark_frustum(const unsigned char* state, int nx, int ny, int nz, unsigned* seen,
+                                          const long* cells_in, const int* heading_of, long V, int range, int depth,
+                                          int far, const int* frames, int H, long tan2_h_num, long tan2_h_den,
+                                          long tan2_v_num, long tan2_v_den, short* owner, int tag,
+                                          unsigned long long* counters, void* stream) {
+  return view_mark(Form::or_transparent("pi3_grid_view_mark_frustum", far, depth), state, nx, ny, nz, seen, cells_in,
+                   heading_of, V, range, Frusta{frames, H, tan2_h_num, tan2_h_den, tan2_v_num, tan2_v_den}, owner, tag,
+                   counters, stream);
 }

@@ -48,17 +48,38 @@ struct Headings {
   long long norm[kMaxHeadings];         // num |a|^2
 };
 
+// The frustum form's table: a heading is a frame of two orthogonal integer vectors, f forward and r right,
+// components within +-kMaxFrame; u = f x r is up or down (its sign squares away).  Offset o lies in the frustum when
+//   o.f > 0,  (o.r)^2 |f|^2 hd <= hn (o.f)^2 |r|^2,  (o.u)^2 vd <= vn (o.f)^2 |r|^2   (|u|^2 = |f|^2 |r|^2 divided out)
+// with tan^2 of the half angles hn / hd and vn / vd; the faces are inclusive.  A row holds the three constants that
+// depend on the frame; vd travels in the kernels' `den`.
+constexpr int kMaxFrame = 64;           // per component of f and r
+constexpr long kMaxTan2 = 1l << 20;     // the largest numerator and denominator of a tan^2 fraction
+
+struct Frames {
+  int f[kMaxHeadings][3], r[kMaxHeadings][3], u[kMaxHeadings][3];
+  long long fhd[kMaxHeadings];          // |f|^2 hd
+  long long hnr[kMaxHeadings];          // hn |r|^2
+  long long vnr[kMaxHeadings];          // vn |r|^2
+};
+
 struct MarkRows {
   signed char heading[kMarkRows];       // -1: any of the H headings
 };
 
-// the arguments the ray entry points share (range in 1 .. max_range); fills hd
+// the arguments every ray entry point has, cones or frusta (range in 1 .. max_range)
+inline bool view_grid_ok(const unsigned char* state, int nx, int ny, int nz, long& cells, long V, int range, int max_range,
+                         const unsigned long long* counters) {
+  return state && counters && grid_tile::grid_ok(nx, ny, nz, cells) && V >= 0 && V <= 0x7FFFFFFFl && range >= 1 &&
+         range <= max_range;
+}
+
+// the arguments the cone entry points share (range in 1 .. max_range); fills hd
 inline bool view_rays_ok(const unsigned char* state, int nx, int ny, int nz, long& cells, long V, int range, int max_range,
                          const int* headings, int H, long cos2_num, long cos2_den, const unsigned long long* counters,
                          Headings& hd) {
-  bool ok = state && counters && headings && grid_tile::grid_ok(nx, ny, nz, cells) && V >= 0 && V <= 0x7FFFFFFFl &&
-            range >= 1 && range <= max_range && H >= 1 && H <= kMaxHeadings && cos2_den > 0 && cos2_den < (1l << 31) &&
-            cos2_num >= 0 && cos2_num <= cos2_den;
+  bool ok = view_grid_ok(state, nx, ny, nz, cells, V, range, max_range, counters) && headings && H >= 1 &&
+            H <= kMaxHeadings && cos2_den > 0 && cos2_den < (1l << 31) && cos2_num >= 0 && cos2_num <= cos2_den;
   for (int h = 0; ok && h < H; ++h) {
     long long n2 = 0;
     for (int a = 0; a < 3; ++a) {
@@ -85,6 +106,31 @@ inline bool cone_fits(int range, const Headings& hd, int H, long cos2_den) {
     most = n2 > most ? n2 : most;
   }
   return (long long)range * range * most <= 0x7FFFFFFFFFFFFFFFll / (long long)cos2_den;
+}
+
+// The frames of the frustum entry points: H rows of f then r, with the checks of the table above; fills fr.
+// Why 64 bits hold both sides of both tests without a run-time check: |o|^2 <= 64^2 = 2^12, |f|^2, |r|^2 <= 3 * 64^2 =
+// 12288, so (o.r)^2 <= |o|^2 |r|^2 <= 2^12 * 12288 and (o.r)^2 |f|^2 hd <= 2^12 * 12288 * 12288 * 2^20 = 2.25 * 2^58;
+// (o.u)^2 vd <= |o|^2 |f|^2 |r|^2 vd is the same figure, and so is either right-hand side, hn (o.f)^2 |r|^2 <=
+// 2^20 * 2^12 * 12288 * 12288.  2.25 * 2^58 < 2^63.  The dots fit an int: |o.u| <= 64 * 12288 < 2^20.
+inline bool view_frames_ok(const int* frames, int H, long hn, long hd, long vn, long vd, Frames& fr) {
+  bool ok = frames && H >= 1 && H <= kMaxHeadings && hn >= 0 && hn <= kMaxTan2 && hd >= 1 && hd <= kMaxTan2 && vn >= 0 &&
+            vn <= kMaxTan2 && vd >= 1 && vd <= kMaxTan2;
+  for (int h = 0; ok && h < H; ++h) {
+    const int* f = frames + 6 * h;
+    const int* r = f + 3;
+    long long f2 = 0, r2 = 0, fr_dot = 0;
+    for (int a = 0; a < 3; ++a) {
+      ok = ok && f[a] >= -kMaxFrame && f[a] <= kMaxFrame && r[a] >= -kMaxFrame && r[a] <= kMaxFrame;
+      fr.f[h][a] = f[a], fr.r[h][a] = r[a];
+      f2 += (long long)f[a] * f[a], r2 += (long long)r[a] * r[a], fr_dot += (long long)f[a] * r[a];
+    }
+    ok = ok && f2 != 0 && r2 != 0 && fr_dot == 0;
+    if (!ok) break;
+    fr.u[h][0] = f[1] * r[2] - f[2] * r[1], fr.u[h][1] = f[2] * r[0] - f[0] * r[2], fr.u[h][2] = f[0] * r[1] - f[1] * r[0];
+    fr.fhd[h] = f2 * hd, fr.hnr[h] = hn * r2, fr.vnr[h] = vn * r2;
+  }
+  return ok;
 }
 
 // cells per axis of the staged box
@@ -283,6 +329,24 @@ __device__ __forceinline__ bool ray_arrives_from(const unsigned* bits, int at, i
 __device__ __forceinline__ bool in_cone(const Headings& hd, int h, long long den, int ox, int oy, int oz, long long o2) {
   const long long dot = (long long)ox * hd.axis[h][0] + (long long)oy * hd.axis[h][1] + (long long)oz * hd.axis[h][2];
   return dot > 0 && dot * dot * den >= hd.norm[h] * o2;
+}
+
+// offset o lies in frame h's frustum (Frames; vd is the vertical fraction's denominator): three dots, five 64-bit
+// products, every constant wave-uniform in h.  view_frames_ok is why nothing overflows.
+__device__ __forceinline__ bool in_frustum(const Frames& fr, int h, long long vd, int ox, int oy, int oz) {
+  const int df = ox * fr.f[h][0] + oy * fr.f[h][1] + oz * fr.f[h][2];
+  const int dr = ox * fr.r[h][0] + oy * fr.r[h][1] + oz * fr.r[h][2];
+  const int du = ox * fr.u[h][0] + oy * fr.u[h][1] + oz * fr.u[h][2];
+  const long long df2 = (long long)df * df;
+  return df > 0 && (long long)dr * dr * fr.fhd[h] <= fr.hnr[h] * df2 && (long long)du * du * vd <= fr.vnr[h] * df2;
+}
+
+// the membership test of a kernel's table: the cone of a Headings row, the frustum of a Frames row (den: vd there)
+__device__ __forceinline__ bool in_view(const Headings& hd, int h, long long den, int ox, int oy, int oz, long long o2) {
+  return in_cone(hd, h, den, ox, oy, oz, o2);
+}
+__device__ __forceinline__ bool in_view(const Frames& fr, int h, long long den, int ox, int oy, int oz, long long) {
+  return in_frustum(fr, h, den, ox, oy, oz);
 }
 
 // (2) and the DDA of (3), after stage_occupied and the caller's __syncthreads(): the same walk over the box finds the

@@ -340,12 +340,17 @@ def write_views(vset, out_dir: str) -> int:
     that reaches it, -1 elsewhere; index_origin i64 (3,), origin f64 (3,), cell f64; of a cover also seen_by i16: the
     rank of the view that first covered the cell, -1 elsewhere, and `new` / `covered` in every record) and views.ply:
     the kept views as points whose normal nx ny nz is the viewing direction, coloured from frontiers.ply's palette by
-    rank, for viewing next to dense_points.ply.  Returns the number of views."""
+    rank, for viewing next to dense_points.ply.  A set found with a frustum adds frames i64 (H,6) to
+    views.npz, whose headings is then the frames' f column, `frame` and `pose` (4x4 camera-to-world) to every record and
+    the `frustum` block to the settings; every other key and file is what it is without one.  Returns the number of
+    views."""
     os.makedirs(out_dir, exist_ok=True)
     record = {"settings": vset.settings, "counts": vset.counts, "views": [v.record() for v in vset.views]}
     with open(os.path.join(out_dir, "views.json"), "w") as f:
         json.dump(record, f, indent=1)
     cover = {} if vset.seen_by is None else {"seen_by": np.asarray(vset.seen_by, np.int16)}
+    if getattr(vset, "frames", None) is not None:
+        cover["frames"] = np.asarray(vset.frames, np.int64)
     with open(os.path.join(out_dir, "views.npz"), "wb") as f:
         np.savez_compressed(f, gain=np.asarray(vset.gain, np.int32), heading=np.asarray(vset.heading, np.int8),
                             headings=np.asarray(vset.headings, np.int64),

@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import List, Optional, Tuple
+from typing import List, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -1369,6 +1369,34 @@ def _view_depth(unknown_depth) -> Optional[int]:
     return int(unknown_depth)
 
 
+class ViewFrustum(NamedTuple):
+    """The frustum form of the ray calls: frames (H,6) integers, row h = f (forward) then r (right), both
+    non-zero, orthogonal, components within +-VIEW_MAX_FRAME; tan^2 of half the horizontal and the vertical field of
+    view as fractions, 0 <= num <= VIEW_MAX_TAN2, 1 <= den <= VIEW_MAX_TAN2."""
+    frames: object
+    tan2_h_num: int
+    tan2_h_den: int
+    tan2_v_num: int
+    tan2_v_den: int
+
+
+VIEW_MAX_FRAME = 64                     # per component of a frame's f and r
+VIEW_MAX_TAN2 = 1 << 20                 # the largest numerator and denominator of a tan^2 fraction
+
+
+def _view_frustum(frustum: ViewFrustum, unknown_depth, view_range: int, far: bool):
+    """A frustum call's arguments -> (the frames as a ctypes array, H, what stands between range and frames (depth,
+    far), the four fraction terms).  The entry points check the frames' rules and name them."""
+    fr = np.ascontiguousarray(frustum.frames, dtype=np.int64)
+    assert fr.ndim == 2 and fr.shape[1] == 6 and 1 <= len(fr) <= VIEW_MAX_HEADINGS, \
+        f"frames of shape {fr.shape}: (H, 6) with H in 1 .. {VIEW_MAX_HEADINGS}"
+    assert int(np.abs(fr).max()) <= VIEW_MAX_FRAME, f"a frame's components lie within +-{VIEW_MAX_FRAME}"
+    H = len(fr)
+    depth = _view_depth(unknown_depth)
+    form = (-1 if depth is None else depth, int(bool(far) or int(view_range) > VIEW_MAX_RANGE))
+    return (C.c_int * (6 * H))(*[int(c) for c in fr.reshape(-1)]), H, form, tuple(int(v) for v in frustum[1:])
+
+
 VIEW_MARK_COUNTERS = ("views", "rays", "rays_visible", "in_cone", "new")
 VIEW_MAX_TAG = 32767                    # owner is int16
 
@@ -1403,36 +1431,45 @@ def _view_grid(state: torch.Tensor, seen: Optional[torch.Tensor]):
 
 
 def _view_gain(name: str, state, seen, candidates, view_range, headings, cos2_num, cos2_den, gain, visible, best,
-               counters, far, unknown_depth=None) -> None:
+               counters, far, unknown_depth=None, frustum=None) -> None:
     """grid_view_gain (seen None) and grid_view_gain_unseen: the entry points differ in the mask argument.  With an
-    unknown_depth both go to pi3_grid_view_gain_depth, which takes the mask or NULL, the depth and the form."""
+    unknown_depth both go to pi3_grid_view_gain_depth, which takes the mask or NULL, the depth and the form; with a
+    frustum to pi3_grid_view_gain_frustum, which takes those and the frames instead of the cones."""
     lib = _L.load()
     nx, ny, nz = _view_grid(state, seen)
     dev = state.device
     assert candidates.dtype == torch.int64 and candidates.is_contiguous() and candidates.ndim == 1
     assert candidates.device == dev
     V = int(candidates.numel())
-    flat, H = _view_headings(headings)
+    if frustum is None:
+        flat, H = _view_headings(headings)
+        shape = (int(cos2_num), int(cos2_den))
+    else:
+        flat, H, frustum_form, shape = _view_frustum(frustum, unknown_depth, view_range, far)
     assert gain.dtype == torch.int32 and gain.is_contiguous() and tuple(gain.shape) == (V, H) and gain.device == dev
     for t in (visible, best):
         assert t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == (V,) and t.device == dev
     assert counters.dtype == torch.int64 and counters.is_contiguous() and counters.numel() >= 4 and counters.device == dev
     depth = _view_depth(unknown_depth)
-    if depth is None:
+    if frustum is not None:
+        entry, name = lib.pi3_grid_view_gain_frustum, "pi3_grid_view_gain_frustum"
+        mask, form = (_L.ptr(seen),), frustum_form
+    elif depth is None:
         entry, name = _view_entry(lib, name, view_range, far)
         mask, form = () if seen is None else (seen.data_ptr(),), ()
     else:
         entry, name = lib.pi3_grid_view_gain_depth, "pi3_grid_view_gain_depth"
         mask, form = (_L.ptr(seen),), (depth, int(bool(far) or int(view_range) > VIEW_MAX_RANGE))
     rc = entry(state.data_ptr(), nx, ny, nz, *mask, candidates.data_ptr() if V else None, V, int(view_range), *form,
-               flat, H, int(cos2_num), int(cos2_den), gain.data_ptr() if V else None, visible.data_ptr() if V else None,
+               flat, H, *shape, gain.data_ptr() if V else None, visible.data_ptr() if V else None,
                best.data_ptr() if V else None, counters.data_ptr(), _L.stream_ptr())
     _L.check(rc, name)
 
 
 def grid_view_gain(state: torch.Tensor, candidates: torch.Tensor, view_range: int, headings, cos2_num: int,
                    cos2_den: int, gain: torch.Tensor, visible: torch.Tensor, best: torch.Tensor,
-                   counters: torch.Tensor, far: bool = False, unknown_depth: Optional[int] = None) -> None:
+                   counters: torch.Tensor, far: bool = False, unknown_depth: Optional[int] = None,
+                   frustum: Optional[ViewFrustum] = None) -> None:
     """Per entry of candidates int64 (V,) (linear indices into state uint8 (nz,ny,nx)): visible int32 (V,) (the uint32
     values) = the unknown cells within view_range cells that no occupied cell hides, gain int32 (V,H) = those in the
     cone of each of the H integer axes `headings` (H,3) (x, y, z) at cos^2 of the half angle cos2_num / cos2_den, best
@@ -1440,35 +1477,44 @@ def grid_view_gain(state: torch.Tensor, candidates: torch.Tensor, view_range: in
     int64 (4,) = VIEW_COUNTERS (zeroed by the call).  A view_range above VIEW_MAX_RANGE, up to VIEW_FAR_MAX_RANGE, goes
     to the far entry point (the octant form of csrc/grid_view.hip); far=True sends any range there.  unknown_depth K in
     0 .. VIEW_MAX_DEPTH: a cell is visible only when at most K cells between it and the candidate are
-    unknown as well; rays_blocked then counts every ray that did not arrive.  None: unknown cells are transparent."""
+    unknown as well; rays_blocked then counts every ray that did not arrive.  None: unknown cells are transparent.
+    frustum (a ViewFrustum, DESIGN §7o): heading h is the frustum of frames[h] instead of a cone, H = len(frames);
+    headings, cos2_num and cos2_den are then not read."""
     _view_gain("pi3_grid_view_gain", state, None, candidates, view_range, headings, cos2_num, cos2_den, gain, visible,
-               best, counters, far, unknown_depth)
+               best, counters, far, unknown_depth, frustum)
 
 
 def grid_view_gain_unseen(state: torch.Tensor, seen: torch.Tensor, candidates: torch.Tensor, view_range: int, headings,
                           cos2_num: int, cos2_den: int, gain: torch.Tensor, visible: torch.Tensor, best: torch.Tensor,
-                          counters: torch.Tensor, far: bool = False, unknown_depth: Optional[int] = None) -> None:
+                          counters: torch.Tensor, far: bool = False, unknown_depth: Optional[int] = None,
+                          frustum: Optional[ViewFrustum] = None) -> None:
     """grid_view_gain over the unknown cells whose bit of seen int32 (grid_view_seen_words(cells),) (the uint32 words) is
-    clear; every output keeps its shape and meaning, and with an all-zero mask its bytes.  view_range, far and
-    unknown_depth as there."""
+    clear; every output keeps its shape and meaning, and with an all-zero mask its bytes.  view_range, far,
+    unknown_depth and frustum as there."""
     _view_gain("pi3_grid_view_gain_unseen", state, seen, candidates, view_range, headings, cos2_num, cos2_den, gain,
-               visible, best, counters, far, unknown_depth)
+               visible, best, counters, far, unknown_depth, frustum)
 
 
 def grid_view_mark(state: torch.Tensor, seen: torch.Tensor, cells: torch.Tensor, heading_of, view_range: int, headings,
                    cos2_num: int, cos2_den: int, counters: torch.Tensor, owner: Optional[torch.Tensor] = None,
-                   tag: int = 0, far: bool = False, unknown_depth: Optional[int] = None) -> None:
+                   tag: int = 0, far: bool = False, unknown_depth: Optional[int] = None,
+                   frustum: Optional[ViewFrustum] = None) -> None:
     """Sets in seen int32 (grid_view_seen_words(cells),) the bit of every unknown cell within view_range cells of cells[i]
     (int64 (V,), linear indices on the device) that no occupied cell hides and that lies in the cone of heading
     heading_of[i] (V host integers in -1 .. H - 1; -1: in the cone of any heading).  owner int16 (nz,ny,nx), only with
     V == 1: the cells whose bit this call turned get `tag` (0 .. VIEW_MAX_TAG).  counters int64 (5,) =
-    VIEW_MARK_COUNTERS (zeroed by the call).  view_range, far and unknown_depth as grid_view_gain's."""
+    VIEW_MARK_COUNTERS (zeroed by the call).  view_range, far, unknown_depth and frustum as grid_view_gain's ("cone"
+    then reads "frustum of the frame")."""
     lib = _L.load()
     nx, ny, nz = _view_grid(state, seen)
     dev = state.device
     assert cells.dtype == torch.int64 and cells.is_contiguous() and cells.ndim == 1 and cells.device == dev
     V = int(cells.numel())
-    flat, H = _view_headings(headings)
+    if frustum is None:
+        flat, H = _view_headings(headings)
+        shape = (int(cos2_num), int(cos2_den))
+    else:
+        flat, H, frustum_form, shape = _view_frustum(frustum, unknown_depth, view_range, far)
     hof = np.ascontiguousarray(heading_of, dtype=np.int32).reshape(-1)
     assert len(hof) == V and bool(((hof >= -1) & (hof < H)).all()), f"{V} rows need {V} headings in -1 .. {H - 1}"
     assert 0 <= int(tag) <= VIEW_MAX_TAG, f"tag {tag}: 0 .. {VIEW_MAX_TAG}"
@@ -1477,14 +1523,16 @@ def grid_view_mark(state: torch.Tensor, seen: torch.Tensor, cells: torch.Tensor,
         assert V == 1, f"an owner takes one row per call, got {V}"
     assert counters.dtype == torch.int64 and counters.is_contiguous() and counters.numel() >= 5 and counters.device == dev
     depth = _view_depth(unknown_depth)
-    if depth is None:
+    if frustum is not None:
+        entry, name, form = lib.pi3_grid_view_mark_frustum, "pi3_grid_view_mark_frustum", frustum_form
+    elif depth is None:
         (entry, name), form = _view_entry(lib, "pi3_grid_view_mark", view_range, far), ()
     else:
         entry, name = lib.pi3_grid_view_mark_depth, "pi3_grid_view_mark_depth"
         form = (depth, int(bool(far) or int(view_range) > VIEW_MAX_RANGE))
     rc = entry(state.data_ptr(), nx, ny, nz, seen.data_ptr(), cells.data_ptr() if V else None,
-               hof.ctypes.data_as(C.POINTER(C.c_int)) if V else None, V, int(view_range), *form, flat, H, int(cos2_num),
-               int(cos2_den), _L.ptr(owner), int(tag), counters.data_ptr(), _L.stream_ptr())
+               hof.ctypes.data_as(C.POINTER(C.c_int)) if V else None, V, int(view_range), *form, flat, H, *shape,
+               _L.ptr(owner), int(tag), counters.data_ptr(), _L.stream_ptr())
     _L.check(rc, name)
 
 

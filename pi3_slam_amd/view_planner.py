@@ -14,8 +14,17 @@ unknown_depth=K (tests/grid_view_depth_ref.py) replaces the transpa
 K cells between its ends are unknown, so a view into a solid block of unknown space counts its first K + 1 layers and
 not the whole block.  Every step of find, cover and the tour's replay then casts by that rule.
 
-Limitations: unknown space is transparent unless unknown_depth is set, so the gain is an upper bound; poses are cell centres; 26 headings only; a
-cone, not a frustum, and no roll; the range is at most 32 cells, 64 with far=True (use a larger occupancy
+frustum=(hfov_deg, vfov_deg) (tests/grid_view_frustum_ref.py) replaces the cones by the camera that will be
+carried: the headings are view_frames' integer frames (yaw_steps yaws at every pitch of pitches_deg about `up`,
+portrait: the camera turned a quarter about its axis), the gain of a heading counts the visible unknown cells inside
+the frame's frustum, and every kept view carries its frame and a 4x4 camera-to-world pose for the renderer.  Every step
+of find, cover and the tour's replay then tests by that rule.  `up` is a convention, not a measurement: the world is the
+first camera's frame, whose y points down, hence the default (0, -1, 0).
+
+Limitations: unknown space is transparent unless unknown_depth is set, so the gain is an upper bound; poses are cell
+centres; without frustum the headings are the 26 neighbour directions and the view is a cone; with it the frames have
+components within +-64 (up to about 0.8 degrees off the angle asked for), at most 32 of them, and the view ends at the
+ball of range_m, not at a far plane; the range is at most 32 cells, 64 with far=True (use a larger occupancy
 cell for more); unknown space outside the grid is not counted; nothing is updated incrementally in `find` (`cover`
 below does); the gain counts cells, not surface.  range_m, stride and fov_deg are starting points, not measured optima.
 
@@ -46,6 +55,110 @@ def view_headings() -> np.ndarray:
                      if (dx, dy, dz) != (0, 0, 0)], np.int64)
 
 
+VIEW_TAN2_DEN = 4096                    # tan^2 of half a field of view is passed as round(tan^2 * 4096) / 4096
+VIEW_FOV_MIN, VIEW_FOV_MAX = 2.0, 170.0 # degrees, each angle of a frustum: tan^2 * 4096 is then at most 535 000 < 2^20
+
+
+def _half_away(x: float) -> int:
+    """x rounded to the nearest integer, halves away from zero."""
+    return int(math.floor(abs(x) + 0.5)) * (1 if x >= 0.0 else -1)
+
+
+def _reduced(v) -> np.ndarray:
+    """An integer vector divided by the gcd of its components."""
+    v = [int(c) for c in v]
+    g = math.gcd(math.gcd(abs(v[0]), abs(v[1])), abs(v[2]))
+    return np.array([c // g for c in v], np.int64)
+
+
+def _up_axes(up):
+    """up = s e_k, one of the six signed axes -> (s, i, j, k) with (e_i, e_j, e_k) the cyclic order of the axes."""
+    try:
+        u = [int(c) for c in up]
+        whole = len(u) == 3 and all(float(c) == float(a) for c, a in zip(up, u))
+    except (TypeError, ValueError):
+        whole = False
+    if not whole or sorted(abs(c) for c in u) != [0, 0, 1]:
+        raise ValueError(f"up must be one of the six signed axes such as (0, -1, 0), got {up!r}")
+    k = [abs(c) for c in u].index(1)
+    return u[k], (k + 1) % 3, (k + 2) % 3, k
+
+
+def view_frames(yaw_steps: int = 8, pitches_deg=(0.0,), up=(0, -1, 0), portrait: bool = False) -> np.ndarray:
+    """i64 (H,6), H = yaw_steps * len(pitches_deg) in 1 .. 32: the frames f (forward) then r (right) of a camera that
+    pans in yaw_steps equal steps at every pitch, in the order of the pitches as given, then yaw ascending.  up = s e_k is
+    one of the six signed axes (a convention, not a measurement; the default (0, -1, 0) is the first camera's frame, whose
+    y points down); with (e_i, e_j, e_k) the cyclic order of the axes, yaw n is the angle 2 pi n / yaw_steps from e_i
+    towards s e_j and a pitch is towards up: d = cos p (cos y e_i + sin y s e_j) + sin p s e_k.  f is 64 d / max |d_a|
+    rounded half away from zero per component and divided by its gcd; r = f x up is horizontal, its components are f's.
+    portrait: the frame is (f, r x f divided by its gcd), which must fit +-64.  Deterministic.  A ValueError names a
+    frame that looks along up, two equal f, or an H outside 1 .. 32."""
+    s, i, j, k = _up_axes(up)
+    if isinstance(yaw_steps, bool) or int(yaw_steps) != yaw_steps or int(yaw_steps) < 1:
+        raise ValueError(f"yaw_steps must be an integer >= 1, got {yaw_steps!r}")
+    pitches = [float(p) for p in pitches_deg]
+    if not all(math.isfinite(p) and -90.0 <= p <= 90.0 for p in pitches):
+        raise ValueError(f"every pitch must lie in -90 .. 90 degrees, got {pitches!r}")
+    H = int(yaw_steps) * len(pitches)
+    if not 1 <= H <= ops.VIEW_MAX_HEADINGS:
+        raise ValueError(f"{int(yaw_steps)} yaws at {len(pitches)} pitches are {H} frames: 1 .. {ops.VIEW_MAX_HEADINGS}")
+    upv = np.zeros(3, np.int64)
+    upv[k] = s
+    rows = []
+    for p in pitches:
+        for n in range(int(yaw_steps)):
+            y, t = 2.0 * math.pi * n / int(yaw_steps), math.radians(p)
+            d = [0.0, 0.0, 0.0]
+            d[i], d[j], d[k] = math.cos(t) * math.cos(y), math.cos(t) * math.sin(y) * s, math.sin(t) * s
+            most = max(abs(c) for c in d)
+            f = _reduced([_half_away(ops.VIEW_MAX_FRAME * c / most) for c in d])
+            if f[i] == 0 and f[j] == 0:
+                raise ValueError(f"the frame at pitch {p:g} looks along up {tuple(int(c) for c in upv)}: it has no right")
+            r = np.cross(f, upv)
+            if portrait:
+                r = _reduced(np.cross(r, f))
+                if int(np.abs(r).max()) > ops.VIEW_MAX_FRAME:
+                    raise ValueError(f"portrait: the frame at pitch {p:g}, yaw {n} of {int(yaw_steps)} has the right "
+                                     f"{tuple(int(c) for c in r)}, outside +-{ops.VIEW_MAX_FRAME}")
+            rows.append(np.concatenate([f, r]))
+    frames = np.array(rows, np.int64).reshape(H, 6)
+    seen = {}
+    for h, row in enumerate(frames):
+        first = seen.setdefault(tuple(int(c) for c in row[:3]), h)
+        if first != h:
+            raise ValueError(f"frames {first} and {h} look the same way {tuple(int(c) for c in row[:3])}: give every pitch "
+                             "once and keep the pitches apart")
+    return frames
+
+
+def frame_angles(frames, yaw_steps: int, pitches_deg, up) -> List[Dict]:
+    """Per frame of view_frames(yaw_steps, pitches_deg, up): the yaw and pitch of its f and the angle between f and the
+    direction asked for, in degrees."""
+    s, i, j, k = _up_axes(up)
+    out = []
+    for h, row in enumerate(np.asarray(frames, np.int64).reshape(-1, 6)):
+        f = row[:3].astype(np.float64)
+        y = 2.0 * math.pi * (h % int(yaw_steps)) / int(yaw_steps)
+        t = math.radians(float(list(pitches_deg)[h // int(yaw_steps)]))
+        d = np.zeros(3)
+        d[i], d[j], d[k] = math.cos(t) * math.cos(y), math.cos(t) * math.sin(y) * s, math.sin(t) * s
+        c = float(f @ d) / math.sqrt(float(f @ f))
+        out.append({"yaw_deg": math.degrees(math.atan2(s * f[j], f[i])) % 360.0,
+                    "pitch_deg": math.degrees(math.atan2(s * f[k], math.hypot(f[i], f[j]))),
+                    "error_deg": math.degrees(math.acos(max(-1.0, min(1.0, c))))})
+    return out
+
+
+def view_pose(frame, position) -> np.ndarray:
+    """f64 (4,4): the camera-to-world matrix of a frame f then r at `position`, in the renderer's convention: the columns
+    are right, down and forward at unit length (down = forward x right), the translation is the position."""
+    f, r = (np.asarray(frame, np.float64).reshape(-1)[a:a + 3] for a in (0, 3))
+    f, r = f / math.sqrt(float(f @ f)), r / math.sqrt(float(r @ r))
+    pose = np.eye(4)
+    pose[:3, 0], pose[:3, 1], pose[:3, 2], pose[:3, 3] = r, np.cross(f, r), f, np.asarray(position, np.float64)
+    return pose
+
+
 @dataclass
 class View:
     """One view pose.  Points are world coordinates of cell centres, cell (index_origin + i + 0.5)."""
@@ -61,6 +174,8 @@ class View:
     distance_m: float                           # cell cost / 12
     new: int = -1                               # cover mode: the cells this view added (= gain, the marginal gain then)
     covered: int = -1                           # cover mode: the running total after it
+    frame: Optional[np.ndarray] = None          # frustum: i64 (2,3), the heading's f (= axis) and r
+    pose: Optional[np.ndarray] = None           # frustum: f64 (4,4) camera-to-world, columns right, down, forward
 
     def record(self) -> Dict:
         """The view as JSON types (`new` and `covered` in cover mode only)."""
@@ -70,6 +185,9 @@ class View:
                "cost": self.cost, "distance_m": self.distance_m}
         if self.new >= 0:
             rec.update(new=self.new, covered=self.covered)
+        if self.frame is not None:
+            rec.update(frame=[[int(c) for c in row] for row in self.frame],
+                       pose=[[float(c) for c in row] for row in self.pose])
         return rec
 
 
@@ -90,6 +208,7 @@ class ViewSet:
     seen_by: Optional[np.ndarray] = dc_field(default=None, repr=False)
     mode: str = "gain"                          # "gain" (find) or "cover"
     sources: Optional[np.ndarray] = dc_field(default=None, repr=False)     # f64 (N,3): the world points it was found from
+    frames: Optional[np.ndarray] = dc_field(default=None, repr=False)      # frustum: i64 (H,6); headings is its f column
 
     @property
     def origin(self) -> np.ndarray:
@@ -191,6 +310,13 @@ def _pose(c: int, h: int, cost: int, hd, origin, cell: float, shape):
              axis / math.sqrt(float((axis * axis).sum()))), (cost, cell * cost / 12.0))
 
 
+def _camera(frames, h: int, position) -> Dict:
+    """View's frame and pose for heading h at `position`; nothing without frames."""
+    if frames is None:
+        return {}
+    return dict(frame=frames[h].reshape(2, 3).copy(), pose=view_pose(frames[h], position))
+
+
 def _best_maps(shape, cells, best_gain, best):
     """-> (gain i32, heading i8) per cell of the grid: the candidates' best values, -1 elsewhere."""
     gain_map = np.full(shape, -1, np.int32)
@@ -210,10 +336,14 @@ class ViewPlanner:
     optima.  far: a range of up to 64 cells instead of 32 (the octant form of csrc/grid_view.hip, DESIGN §7m: the
     same rules, roughly eight times the rays per pose at twice the range).  unknown_depth: None (unknown cells are
     transparent) or K in 0 .. 255, the unknown cells a ray may cross before it ends (a hard cap, not a decay; K >= 110 is
-    the transparent rule at every range).  A starting point, not a measured optimum; there is no default."""
+    the transparent rule at every range).  A starting point, not a measured optimum; there is no default.
+    frustum: None (cones, fov_deg wide; 90 degrees when not given) or (hfov_deg, vfov_deg), each in [2, 170] degrees: the
+    headings are view_frames(yaw_steps, pitches_deg, up, portrait) and a heading's gain counts the cells inside its
+    frustum; fov_deg may then not be given.  portrait also swaps the two angles.  image_width: the width in
+    pixels of the intrinsics that settings() records next to the angles."""
     radius: float = 0.0
     range_m: float = 1.0
-    fov_deg: float = 90.0
+    fov_deg: Optional[float] = None
     stride: int = 4
     count: int = 10
     separation_m: Optional[float] = None
@@ -221,6 +351,12 @@ class ViewPlanner:
     min_gain: int = 1
     far: bool = False
     unknown_depth: Optional[int] = None
+    frustum: Optional[tuple] = None
+    yaw_steps: int = 8
+    pitches_deg: tuple = (0.0,)
+    up: tuple = (0, -1, 0)
+    portrait: bool = False
+    image_width: int = 640
 
     CANDIDATES_FIRST_CAP = 1 << 16      # the candidate buffer of the first try; a grid with more asks again
 
@@ -230,9 +366,13 @@ class ViewPlanner:
         self.range_m = float(self.range_m)
         if not (self.range_m > 0.0 and math.isfinite(self.range_m)):
             raise ValueError(f"the range must be a finite length > 0, got {self.range_m!r}")
-        self.fov_deg = float(self.fov_deg)
-        if not 0.0 < self.fov_deg <= 180.0:
-            raise ValueError(f"the field of view must lie in (0, 180] degrees, got {self.fov_deg!r}")
+        self.frames = None
+        if self.frustum is not None:
+            self._init_frustum()
+        else:
+            self.fov_deg = 90.0 if self.fov_deg is None else float(self.fov_deg)
+            if not 0.0 < self.fov_deg <= 180.0:
+                raise ValueError(f"the field of view must lie in (0, 180] degrees, got {self.fov_deg!r}")
         for name in ("stride", "count", "min_gain"):
             v = getattr(self, name)
             if isinstance(v, bool) or int(v) != v or int(v) < (0 if name == "min_gain" else 1):
@@ -253,8 +393,55 @@ class ViewPlanner:
             if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= ops.VIEW_MAX_DEPTH:
                 raise ValueError(f"unknown_depth must be an integer in 0 .. {ops.VIEW_MAX_DEPTH} or None, got {v!r}")
             self.unknown_depth = int(v)
-        self.cos2_den = ops.VIEW_COS2_DEN
-        self.cos2_num = int(round(math.cos(math.radians(self.fov_deg) / 2.0) ** 2 * self.cos2_den))
+        self.cos2_den = None if self.frames is not None else ops.VIEW_COS2_DEN
+        self.cos2_num = None if self.frames is not None else \
+            int(round(math.cos(math.radians(self.fov_deg) / 2.0) ** 2 * self.cos2_den))
+
+    def _init_frustum(self):
+        """Checks frustum, yaw_steps, pitches_deg, up, portrait and image_width; sets frames and the tan^2 fractions."""
+        if self.fov_deg is not None:
+            raise ValueError(f"a frustum has its own two angles: leave fov_deg out, got {self.fov_deg!r}")
+        try:
+            h, v = (float(a) for a in self.frustum)
+        except (TypeError, ValueError):
+            raise ValueError(f"frustum must be (hfov_deg, vfov_deg), got {self.frustum!r}") from None
+        if not all(VIEW_FOV_MIN <= a <= VIEW_FOV_MAX for a in (h, v)):
+            raise ValueError(f"each angle of the frustum must lie in [{VIEW_FOV_MIN:g}, {VIEW_FOV_MAX:g}] degrees, got "
+                             f"{self.frustum!r}")
+        if not isinstance(self.portrait, bool):
+            raise ValueError(f"portrait must be True or False, got {self.portrait!r}")
+        if isinstance(self.image_width, bool) or int(self.image_width) != self.image_width or int(self.image_width) < 1:
+            raise ValueError(f"image_width must be an integer >= 1, got {self.image_width!r}")
+        self.frustum, self.image_width = (h, v), int(self.image_width)
+        self.pitches_deg = tuple(float(p) for p in self.pitches_deg)
+        self.frames = view_frames(self.yaw_steps, self.pitches_deg, self.up, self.portrait)   # checks the three
+        self.yaw_steps, self.up = int(self.yaw_steps), tuple(int(c) for c in self.up)
+        # the angles along the frame's right and its up: a portrait camera has them the other way round
+        self.frustum_angles = (v, h) if self.portrait else (h, v)
+        self.tan2 = tuple((int(round(math.tan(math.radians(a) / 2.0) ** 2 * VIEW_TAN2_DEN)), VIEW_TAN2_DEN)
+                          for a in self.frustum_angles)
+
+    def shape_args(self):
+        """What the ray calls of ops take for the headings -> ((headings, cos2_num, cos2_den), keywords): the cones, or
+        with a frustum the frames' f column and the ViewFrustum keyword."""
+        if self.frames is None:
+            return (view_headings(), self.cos2_num, self.cos2_den), {}
+        (hn, hd), (vn, vd) = self.tan2
+        return (self.frames[:, :3].copy(), None, None), dict(frustum=ops.ViewFrustum(self.frames, hn, hd, vn, vd))
+
+    def frustum_settings(self) -> Dict:
+        """The `frustum` block of settings(): the angles, the fractions, how the frames were made, each frame's realised
+        angles, and the intrinsics of an image image_width wide, which with a view's pose is what render.pack_cameras
+        takes."""
+        h, v = (math.radians(a) / 2.0 for a in self.frustum_angles)
+        W = self.image_width
+        Hpx = int(round(W * math.tan(v) / math.tan(h)))
+        return {"hfov_deg": self.frustum[0], "vfov_deg": self.frustum[1], "tan2_h": list(self.tan2[0]),
+                "tan2_v": list(self.tan2[1]), "yaw_steps": self.yaw_steps, "pitches_deg": list(self.pitches_deg),
+                "up": list(self.up), "portrait": self.portrait,
+                "realised": frame_angles(self.frames, self.yaw_steps, self.pitches_deg, self.up),
+                "intrinsics": {"W": W, "H": Hpx, "fx": (W / 2.0) / math.tan(h), "fy": (Hpx / 2.0) / math.tan(v),
+                               "cx": W / 2.0, "cy": Hpx / 2.0}}
 
     def settings(self) -> Dict:
         st = {"radius": self.radius, "range_m": self.range_m, "fov_deg": self.fov_deg, "stride": self.stride,
@@ -265,6 +452,8 @@ class ViewPlanner:
             st["far"] = True                    # only when set: every record written without it keeps its bytes
         if self.unknown_depth is not None:      # likewise
             st.update(unknown_is_transparent=False, unknown_depth=self.unknown_depth)
+        if self.frames is not None:             # likewise
+            st["frustum"] = self.frustum_settings()
         return st
 
     def cells_of(self, cell: float):
@@ -312,13 +501,13 @@ class ViewPlanner:
         state = torch.from_numpy(state_np).to(dev)
         cells = self.candidates(dist, origin, max_cost)
         V = int(cells.numel())
-        hd = view_headings()
+        (hd, *cos2), shape = self.shape_args()
         gain = torch.empty((V, len(hd)), dtype=torch.int32, device=dev)
         visible = torch.empty(V, dtype=torch.int32, device=dev)
         best = torch.empty(V, dtype=torch.int32, device=dev)
         counters = torch.zeros(4, dtype=torch.int64, device=dev)
-        ops.grid_view_gain(state, cells, R, hd, self.cos2_num, self.cos2_den, gain, visible, best, counters,
-                           unknown_depth=self.unknown_depth)
+        ops.grid_view_gain(state, cells, R, hd, *cos2, gain, visible, best, counters, unknown_depth=self.unknown_depth,
+                           **shape)
         counts = dict(zip(ops.VIEW_COUNTERS, (int(v) for v in counters.tolist())))
         if counts["candidates"] != V:
             raise RuntimeError(f"the gain kernel saw {counts['candidates']} of {V} candidates")
@@ -330,14 +519,15 @@ class ViewPlanner:
         views = []
         for rank, r in enumerate(keep):
             at, way = _pose(int(cells_np[r]), int(best_np[r]), int(cost[r]), hd, origin, cell, state_np.shape)
-            views.append(View(rank, *at, int(best_gain[r]), int(visible_np[r]), *way))
+            views.append(View(rank, *at, int(best_gain[r]), int(visible_np[r]), *way,
+                              **_camera(self.frames, int(best_np[r]), at[1])))
         gain_map, heading_map = _best_maps(state_np.shape, cells_np, best_gain, best_np)
         counts.update(views=len(views), low_gain=low, reachable=field.counts["reachable"],
                       best_gain=int(best_gain.max()) if V else 0)
         st = dict(self.settings(), cell=cell, range_cells=R, separation_cells=sep, max_cost=max_cost,
                   headings=len(hd))
         return ViewSet(views, gain_map, heading_map, hd, origin, cell, counts, st, field, self.router,
-                       sources=np.asarray(sources_xyz, np.float64).reshape(-1, 3))
+                       sources=np.asarray(sources_xyz, np.float64).reshape(-1, 3), frames=self.frames)
 
     def cover(self, grid: OccupancyGrid, sources_xyz, device="cuda", until: Optional[float] = None) -> ViewSet:
         """The views that cover: find's field, candidates and range, the views picked one after the other by their
@@ -363,10 +553,10 @@ class ViewPlanner:
         state = torch.from_numpy(state_np).to(dev)
         cells = self.candidates(field.device_arrays["cost"], origin, max_cost)
         V = int(cells.numel())
-        hd = view_headings()
+        (hd, *cos2), shape = self.shape_args()
         H = len(hd)
-        cone = (R, hd, self.cos2_num, self.cos2_den)
-        rule = dict(unknown_depth=self.unknown_depth)                       # every cast of the cover, by the one rule
+        cone = (R, hd, *cos2)
+        rule = dict(unknown_depth=self.unknown_depth, **shape)              # every cast of the cover, by the one rule
         words = ops.grid_view_seen_words(state.numel())
         mark_counters = torch.zeros(len(ops.VIEW_MARK_COUNTERS), dtype=torch.int64, device=dev)
 
@@ -411,7 +601,7 @@ class ViewPlanner:
         views = []
         for rank, (r, h, m, new, covered) in enumerate(picks):
             at, way = _pose(int(cells_np[r]), h, int(cost[r]), hd, origin, cell, state_np.shape)
-            views.append(View(rank, *at, m, visible_then[rank], *way, new, covered))
+            views.append(View(rank, *at, m, visible_then[rank], *way, new, covered, **_camera(self.frames, h, at[1])))
         gain_map, heading_map = _best_maps(state_np.shape, cells_np, best_gain, best_np)
         counts.update(views=len(views), low_gain=int((best_gain < self.min_gain).sum()),
                       reachable=field.counts["reachable"], best_gain=int(best_gain.max()) if V else 0, seeable=seeable,
@@ -420,4 +610,4 @@ class ViewPlanner:
         st = dict(self.settings(), cell=cell, range_cells=R, separation_m=None, separation_cells=None, max_cost=max_cost,
                   headings=H, mode="cover", until=until)
         return ViewSet(views, gain_map, heading_map, hd, origin, cell, counts, st, field, self.router,
-                       owner.cpu().numpy(), "cover", np.asarray(sources_xyz, np.float64).reshape(-1, 3))
+                       owner.cpu().numpy(), "cover", np.asarray(sources_xyz, np.float64).reshape(-1, 3), self.frames)

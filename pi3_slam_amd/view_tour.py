@@ -384,15 +384,17 @@ def plan_tour(vset, start_xyz=None, device=None, max_field_bytes: int = 2 << 30,
     covered = 0
     if stops:
         st = vset.settings
-        cone = (int(st["range_cells"]), vset.headings, int(st["cos2_num"]), int(st["cos2_den"]))
+        cone = (int(st["range_cells"]), vset.headings, st["cos2_num"], st["cos2_den"])
+        rule = dict(unknown_depth=st.get("unknown_depth"))                    # the rule the views were picked by
+        if vset.frames is not None:                                           # and the shape: frusta, not cones
+            rule["frustum"] = ops.ViewFrustum(vset.frames, *st["frustum"]["tan2_h"], *st["frustum"]["tan2_v"])
         state = torch.from_numpy(np.ascontiguousarray(f.state, np.uint8)).to(dev)
         seen = torch.zeros(ops.grid_view_seen_words(n_cells), dtype=torch.int32, device=dev)
         marks = torch.zeros(len(ops.VIEW_MARK_COUNTERS), dtype=torch.int64, device=dev)
         for stop in stops:
             at = nodes[stop.number + 1:stop.number + 2]
             for r in stop.ranks:
-                ops.grid_view_mark(state, seen, at, [vset.views[r].heading], *cone, marks,
-                                   unknown_depth=st.get("unknown_depth"))     # the rule the views were picked by
+                ops.grid_view_mark(state, seen, at, [vset.views[r].heading], *cone, marks, **rule)
                 new = int(marks[4].item())
                 covered += new
                 stop.tour_new.append(new)

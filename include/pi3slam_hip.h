@@ -759,6 +759,30 @@ int pi3_grid_view_mark_frustum(const unsigned char* state, int nx, int ny, int n
                                long tan2_h_num, long tan2_h_den, long tan2_v_num, long tan2_v_den, short* owner, int tag,
                                unsigned long long* counters, void* stream);
 
+/* ---- routes for a body that stands (csrc/grid_stand.hip): the same grid layout and limits; integers only.
+ * up = up_sign e_up_axis is one of the six signed axes (up_axis 0, 1, 2 = x, y, z; up_sign 1 or -1).  A cell is passable
+ * when state == 1, with through_unknown != 0 when state != 2.
+ * pi3_grid_stand_height: height uint8 [cells], whatever the cell's own state: look at c - j up for j = 1 .. 254 and stop
+ *   at the first cell that is outside the grid or not passable.  Stopped on an occupied cell: j.  Stopped on an unknown
+ *   cell or at the border: 0 (no verified support).  Never stopped: 255.  One pass that reads state along x for every
+ *   direction and writes every byte once.
+ * pi3_grid_route_init_stand: pi3_grid_route_init with one more condition, h_lo <= height <= h_hi (1 <= h_lo <= h_hi <=
+ *   254).  counters: DEVICE uint64 [5], [0 .. 3] as there, [4] = the cells that pi3_grid_route_init's rule alone would
+ *   have opened and the band closed; zeroed by the call.
+ * pi3_grid_view_candidates_stand: pi3_grid_view_candidates with the lattice of a standing planner: on the two axes other
+ *   than up_axis the absolute index is a multiple of stride, along up_axis (height - h_lo) mod stride == 0 (floor modulo;
+ *   1 <= h_lo <= 254), so that every column that stands offers its lowest band cell whatever level its floor is at.
+ * Bad arguments launch nothing and leave the outputs untouched.  No allocation, no synchronisation. */
+int pi3_grid_stand_height(const unsigned char* state, int nx, int ny, int nz, int up_axis, int up_sign,
+                          int through_unknown, unsigned char* height, void* stream);
+int pi3_grid_route_init_stand(const unsigned char* state, const unsigned short* d2, int min_d2, int through_unknown,
+                              const unsigned char* height, int h_lo, int h_hi, int nx, int ny, int nz,
+                              const long* sources, long Ns, unsigned char* walk, unsigned* dist,
+                              unsigned long long* counters, void* stream);
+int pi3_grid_view_candidates_stand(const unsigned* dist, const unsigned char* height, int nx, int ny, int nz, int ox,
+                                   int oy, int oz, int stride, long max_cost, int up_axis, int h_lo, long* cells,
+                                   long cap, long* count, void* stream);
+
 /* ---- nearest neighbours between two point clouds (csrc/cloud_nn.hip): an exact radius-bounded search through a
  * uniform grid of cells, for scoring a map against a reference cloud (map_eval.py).  The grid is a hash table of cells
  * in the voxel table's form: `capacity` slots of 64 B (a power of two, at least 2 n: ops.voxel_capacity), keyed by the

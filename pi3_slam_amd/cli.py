@@ -294,6 +294,23 @@ def taut_text(taut) -> str:
     return text
 
 
+# a body that stands (grid_route.GridRouter's stand and up): route, frontiers and views
+STAND_FLAG = ("--stand", dict(type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                              help="plan for a body that stands: a cell is traversable only when it also lies LO .. HI "
+                                   "metres (ceil(LO / cell) .. floor(HI / cell) cells, centre to centre) above an occupied "
+                                   "cell along --up, with nothing but passable cells in between; the carrying height of the "
+                                   "camera (default: none, a sphere that flies)"))
+UP_FLAG = ("--up", dict(type=int, nargs=3, default=[0, -1, 0], metavar=("X", "Y", "Z"),
+                        help="with --stand: the world's up, one of the six signed axes.  A convention, not a measurement: "
+                             "the world is the first camera's frame, whose y points down (default 0 -1 0)"))
+
+
+def stand_text(counts: Dict, settings: Dict) -> str:
+    """The summary line's part about the band; nothing without --stand."""
+    band = settings.get("stand_cells")
+    return "" if band is None else f"; standing {band[0]} .. {band[1]} cells above a floor ({counts['off_band']} cells off the band)"
+
+
 # route: this build's own sub-command (grid_route.py) on the occupancy.npz of reconstruct or online
 ROUTE_FLAGS: Sequence[Tuple[str, Dict]] = (
     ("--occupancy", dict(REQ, help="occupancy.npz of `reconstruct` or `online` (--occupancy-cell)")),
@@ -305,6 +322,8 @@ ROUTE_FLAGS: Sequence[Tuple[str, Dict]] = (
                                                                                    "world point")),
     ("--radius", dict(type=float, default=0.0, help="the body's radius in metres: only cells with at least this "
                                                     "clearance are traversable (default 0: every free cell)")),
+    STAND_FLAG,
+    UP_FLAG,
     TAUT_FLAG,
     ("--device", dict(default="cuda")),
 )
@@ -332,6 +351,8 @@ FRONTIER_FLAGS: Sequence[Tuple[str, Dict]] = (
                                                    "measured optimum)")),
     ("--route-to", dict(type=int, default=None, metavar="RANK", help="also the way to the goal of the cluster of this "
                                                                      "rank (0 = the nearest), as `route` writes it")),
+    STAND_FLAG,
+    UP_FLAG,
     TAUT_FLAG,
     ("--device", dict(default="cuda")),
 )
@@ -375,8 +396,9 @@ VIEW_FLAGS: Sequence[Tuple[str, Dict]] = (
     ("--pitch", dict(type=float, nargs="+", default=[0.0], metavar="DEG",
                      help="with --frustum: the pitches in degrees, towards --up (default 0)")),
     ("--up", dict(type=int, nargs=3, default=[0, -1, 0], metavar=("X", "Y", "Z"),
-                  help="with --frustum: the world's up, one of the six signed axes.  A convention, not a measurement: the "
-                       "world is the first camera's frame, whose y points down (default 0 -1 0)")),
+                  help="with --frustum or --stand: the world's up, one of the six signed axes.  A convention, not a "
+                       "measurement: the world is the first camera's frame, whose y points down (default 0 -1 0)")),
+    STAND_FLAG,
     ("--view-image-width", dict(type=int, default=640, metavar="W",
                                 help="with --frustum: the width in pixels of the intrinsics written to the settings; the "
                                      "height follows from the two angles (default 640)")),
@@ -630,7 +652,8 @@ def run_route(a: argparse.Namespace) -> None:
         raise SystemExit("route: give --start X Y Z or --from-trajectory TRAJ.tum (one of them)")
     check_taut(a, "route", "--goal X Y Z", a.goal is not None)
     try:
-        router = GridRouter(a.radius, a.through_unknown, a.approach_unknown)
+        router = GridRouter(a.radius, a.through_unknown, a.approach_unknown,
+                            **({} if a.stand is None else dict(stand=tuple(a.stand), up=a.up)))
         grid = export.read_occupancy(a.occupancy)
         sources = [a.start] if a.start is not None else read_tum_positions(a.from_trajectory)
         field = router.field(grid, sources, a.device)
@@ -642,6 +665,7 @@ def run_route(a: argparse.Namespace) -> None:
     c = field.counts
     text = (f"route: {c['traversable']} traversable cells, {c['reachable']} reachable from {c['sources_accepted']} "
             f"sources ({c['sources_blocked']} not traversable, {c['sources_outside']} outside) in {c['sweeps']} sweeps")
+    text += stand_text(c, field.settings)
     if a.goal is not None:
         if route is None:
             text += "; the goal cannot be reached"
@@ -664,7 +688,7 @@ def run_frontiers(a: argparse.Namespace) -> None:
         raise SystemExit("frontiers: --route-to needs a source: --start X Y Z or --from-trajectory TRAJ.tum")
     check_taut(a, "frontiers", "--route-to RANK", a.route_to is not None)
     try:
-        finder = FrontierFinder(a.radius, a.min_cells)
+        finder = FrontierFinder(a.radius, a.min_cells, **({} if a.stand is None else dict(stand=tuple(a.stand), up=a.up)))
         grid = export.read_occupancy(a.occupancy)
         sources = None
         if a.start is not None:
@@ -682,6 +706,8 @@ def run_frontiers(a: argparse.Namespace) -> None:
     c = found.counts
     text = (f"frontiers: {c['frontier_cells']} frontier cells in {c['clusters']} clusters ({c['clusters_dropped']} "
             f"dropped), {c['reachable_clusters']} reachable, {c['sweeps']} sweeps")
+    if found.field is not None:
+        text += stand_text(found.field.counts, found.field.settings)
     if found.clusters:
         best = found.clusters[0]
         text += f"; the best: {best.cells} cells"
@@ -708,6 +734,8 @@ def run_views(a: argparse.Namespace) -> None:
         camera = {} if a.frustum is None else dict(frustum=tuple(a.frustum), yaw_steps=a.yaw_steps, pitches_deg=a.pitch,
                                                    up=a.up, portrait=a.portrait, image_width=a.view_image_width)
         fov = a.fov if a.frustum is None or getattr(a, "fov_given", False) else None     # a frustum has its own angles
+        if a.stand is not None:
+            camera.update(stand=tuple(a.stand), up=a.up)
         planner = ViewPlanner(a.radius, a.range, fov, a.stride, a.count, a.separation, a.max_distance, a.min_gain,
                               a.far, a.unknown_depth, **camera)
         grid = export.read_occupancy(a.occupancy)
@@ -733,6 +761,7 @@ def run_views(a: argparse.Namespace) -> None:
         text += f"; rays end after {a.unknown_depth} unknown cells"
     if a.frustum is not None:
         text += f"; {len(planner.frames)} frusta of {a.frustum[0]:g} x {a.frustum[1]:g} degrees"
+    text += stand_text(found.field.counts, found.field.settings)
     if found.views:
         best = found.views[0]
         text += f"; the best: {best.gain} cells at {best.distance_m:.3f} m"

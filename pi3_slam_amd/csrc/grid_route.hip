@@ -12,6 +12,8 @@
 //                         clearance field, d2 >= min_d2 (the field's far mark 0xFFFF passes); dist = far.  Then a thread
 //                         per source: a linear index outside [0, cells) is counted as outside, one on a cell that is
 //                         not traversable as such, every other gets dist = 0 (duplicates store the same word).
+//   pi3_grid_route_init_stand  the same for a body that stands (grid_stand.hip's height u8 per cell): walk also needs
+//                         h_lo <= height <= h_hi, and counters[4] counts the cells that only the band closed.
 //   pi3_grid_route_sweep  one relaxation sweep in grid_tile.h's scheme (tiles of 8 x 8 x 8 cells, each relaxed in LDS to
 //                         its own fixed point; the layout and why the order of the tiles does not matter are argued
 //                         there).  Besides dist the tile's walk bytes are staged (outside the grid is not traversable),
@@ -62,6 +64,7 @@ constexpr unsigned kFar = 0xFFFFFFFFu;
 constexpr int kD2Far = 0xFFFF;
 constexpr int kMaxMinD2 = 255 * 255;    // the clearance field's largest finite value
 constexpr int kMaxFields = 65535;       // fields of one batch: a launch grid's y extent
+constexpr int kMaxStandHeight = 254;    // grid_stand.hip's largest height of a verified support
 
 __host__ __device__ constexpr int move_cost(int dx, int dy, int dz) {
   const int n = (dx != 0) + (dy != 0) + (dz != 0);
@@ -136,6 +139,31 @@ __global__ __launch_bounds__(256) void route_init_kernel(const unsigned char* __
   const bool flags[1] = {open};
   const int at[1] = {0};
   block_count<1>(flags, counters, at);
+}
+
+// route_init_kernel with the band of a body that stands: height u8 per cell (grid_stand.hip), open also needs
+// h_lo <= height <= h_hi; counters[4] counts the cells the rule above alone would have opened and the band closed
+__global__ __launch_bounds__(256) void route_init_stand_kernel(const unsigned char* __restrict__ state,
+                                                               const unsigned short* __restrict__ d2, int min_d2,
+                                                               int through_unknown,
+                                                               const unsigned char* __restrict__ height, int h_lo,
+                                                               int h_hi, int cells, unsigned char* __restrict__ walk,
+                                                               unsigned* __restrict__ dist, u64* __restrict__ counters) {
+  const int i = (int)blockIdx.x * 256 + (int)threadIdx.x;      // cells <= 2^27
+  bool open = false, off_band = false;
+  if (i < cells) {
+    const unsigned char s = state[i];
+    open = through_unknown ? s != 2 : s == 1;
+    if (d2) open = open && (int)d2[i] >= min_d2;
+    const int h = height[i];
+    off_band = open && (h < h_lo || h > h_hi);
+    open = open && !off_band;
+    walk[i] = open ? 1 : 0;
+    dist[i] = kFar;
+  }
+  const bool flags[2] = {open, off_band};
+  const int at[2] = {0, 4};
+  block_count<2>(flags, counters, at);
 }
 
 __global__ __launch_bounds__(256) void route_sources_kernel(const long* __restrict__ sources, long Ns, int cells,
@@ -345,6 +373,29 @@ extern "C" int pi3_grid_route_init(const unsigned char* state, const unsigned sh
     hipLaunchKernelGGL(route_sources_kernel, dim3(voxel_table::blocks_for(Ns)), dim3(256), 0, (hipStream_t)stream,
                        sources, Ns, (int)cells, (const unsigned char*)walk, dist, (u64*)counters);
   return pi3_check_launch("grid_route_init");
+}
+
+extern "C" int pi3_grid_route_init_stand(const unsigned char* state, const unsigned short* d2, int min_d2,
+                                         int through_unknown, const unsigned char* height, int h_lo, int h_hi, int nx,
+                                         int ny, int nz, const long* sources, long Ns, unsigned char* walk, unsigned* dist,
+                                         unsigned long long* counters, void* stream) {
+  long cells = 0;
+  if (!state || !height || !walk || !dist || !counters || !grid_ok(nx, ny, nz, cells) || min_d2 < 0 ||
+      min_d2 > kMaxMinD2 || (min_d2 > 0 && !d2) || h_lo < 1 || h_hi < h_lo || h_hi > kMaxStandHeight || Ns < 0 ||
+      Ns >= (1L << 39) || (Ns > 0 && !sources)) {
+    pi3_set_error("pi3_grid_route_init_stand: bad arguments dims=(%d, %d, %d) (1 .. 2^21 - 1 each, at most 2^27 cells) "
+                  "min_d2=%d (0 .. %d, 0 without d2) band=(%d, %d) (1 <= h_lo <= h_hi <= %d) Ns=%ld (0 .. 2^39 - 1), or a "
+                  "null pointer", nx, ny, nz, min_d2, kMaxMinD2, h_lo, h_hi, kMaxStandHeight, Ns);
+    return PI3_ERR_ARG;
+  }
+  if (pi3_zero_words("pi3_grid_route_init_stand", counters, 5, stream) != PI3_OK) return PI3_ERR_LAUNCH;
+  hipLaunchKernelGGL(route_init_stand_kernel, dim3(voxel_table::blocks_for(cells)), dim3(256), 0, (hipStream_t)stream,
+                     state, d2, min_d2, through_unknown ? 1 : 0, height, h_lo, h_hi, (int)cells, walk, dist,
+                     (u64*)counters);
+  if (Ns > 0)
+    hipLaunchKernelGGL(route_sources_kernel, dim3(voxel_table::blocks_for(Ns)), dim3(256), 0, (hipStream_t)stream,
+                       sources, Ns, (int)cells, (const unsigned char*)walk, dist, (u64*)counters);
+  return pi3_check_launch("grid_route_init_stand");
 }
 
 extern "C" int pi3_grid_route_sweep(const unsigned char* walk, int nx, int ny, int nz, unsigned* dist, int* changed,

@@ -266,15 +266,17 @@ def write_route(field, route, out_dir: str, taut=None) -> None:
     min_clearance_m, settings) and route.ply, the waypoints as coloured points for viewing next to dense_points.ply.
     With the route's grid_route.TautRoute route.json gains taut_waypoints, taut_indices (into waypoints), taut_length_m,
     taut_min_clearance_m and taut_span, and route_taut.ply holds the taut polyline sampled once per cell length; without
-    it every file is what it is without this argument."""
+    it every file is what it is without this argument.  A field of a body that stands adds height u8
+    (nz,ny,nx): the cells above the support along up, 0 without a verified one, 255 beyond 254."""
     os.makedirs(out_dir, exist_ok=True)
+    stand = {} if getattr(field, "height", None) is None else {"height": np.asarray(field.height, np.uint8)}
     with open(os.path.join(out_dir, "route.npz"), "wb") as f:
         np.savez_compressed(f, distance=np.asarray(field.distance, np.float32), cost=np.asarray(field.cost, np.uint32),
                             index_origin=np.asarray(field.index_origin, np.int64),
                             origin=float(field.cell) * np.asarray(field.index_origin, np.float64),
                             cell=np.float64(field.cell),
                             settings=np.array(json.dumps(field.settings or {}, sort_keys=True)),
-                            counts=np.array(json.dumps(field.counts or {}, sort_keys=True)))
+                            counts=np.array(json.dumps(field.counts or {}, sort_keys=True)), **stand)
     text = f"✅ Saved the route field ({field.counts.get('reachable')} reachable cells) to: {out_dir}/route.npz"
     if route is not None:
         clear = route.min_clearance_m

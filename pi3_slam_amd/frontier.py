@@ -104,15 +104,22 @@ def order_clusters(stats: np.ndarray, roots: np.ndarray, min_cells: int, with_so
 @dataclass
 class FrontierFinder:
     """radius (metres): the body's, for the ranking by route (0: every free cell is traversable).  min_cells: clusters
-    of fewer cells are dropped and counted (1 drops nothing)."""
+    of fewer cells are dropped and counted (1 drops nothing).  stand, up: GridRouter's: with stand=(lo, hi)
+    metres the ranking is by the route of a body that is carried that high above something to stand on."""
     radius: float = 0.0
     min_cells: int = 1
+    stand: Optional[tuple] = None
+    up: tuple = (0, -1, 0)
 
     SWEEPS_PER_READ = 4         # label sweeps queued between two reads of their `changed` words
     ROOTS_FIRST_CAP = 1 << 16   # the roots buffer of the first try; a grid with more clusters asks again
 
     def __post_init__(self):
-        self.router = GridRouter(self.radius, approach_unknown=True)       # checks the radius
+        if self.stand is None:
+            self.router = GridRouter(self.radius, approach_unknown=True)   # checks the radius
+        else:                                                              # and the band and up
+            self.router = GridRouter(self.radius, approach_unknown=True, stand=self.stand, up=self.up)
+            self.stand, self.up = self.router.stand, self.router.up
         self.radius = self.router.radius
         if isinstance(self.min_cells, bool) or int(self.min_cells) != self.min_cells or int(self.min_cells) < 0:
             raise ValueError(f"min_cells must be an integer >= 0, got {self.min_cells!r}")
@@ -206,4 +213,6 @@ class FrontierFinder:
                       reachable_clusters=sum(1 for c in clusters if c.reachable),
                       reachable_cells=reduced["cells_reachable"])
         st = dict(self.settings(), cell=cell, sources=field is not None)
+        if field is not None and self.stand is not None:
+            st["stand_cells"] = list(field.settings["stand_cells"])
         return FrontierSet(clusters, rank, origin, cell, counts, st, field, self.router if field is not None else None)

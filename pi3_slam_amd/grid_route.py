@@ -18,7 +18,15 @@ every cell whose closed cube meets the segment between the two centres is traver
 trace the subsequence of cells, first and last included, whose polyline is shortest among those whose consecutive
 vertices lie at most `span` trace cells apart and see each other (pull_taut: a dynamic programme in f64, equal lengths
 take the smallest index).  Vertices are trace cells only: shortcutting, not an any-angle search; the default span of
-256 is a starting point, not a measured optimum."""
+256 is a starting point, not a measured optimum.
+
+A body that stands (stand=(lo, hi) metres; csrc/grid_stand.hip, reproduced by tests/grid_stand_ref.py): a
+cell is traversable only when it also lies h_lo = ceil(lo / cell) .. h_hi = floor(hi / cell) cells above something to
+stand on, with nothing but passable cells in between: height[c] is the j of the first cell among c - j up, j = 1 .. 254,
+that is outside the grid or not passable, when that cell is occupied; 0 when it is unknown or the grid's border (no
+verified support); 255 when there is none.  Heights are centre to centre: the floor cell's top face is half a cell
+nearer.  `up` is one of the six signed axes, a convention and not a measurement.  Everything downstream reads walk, so
+path, sees and taut stay in the band without a change."""
 from __future__ import annotations
 
 import math
@@ -50,6 +58,19 @@ def read_tum_positions(path: str) -> np.ndarray:
     return np.asarray(rows, np.float64)
 
 
+def up_axes(up):
+    """up = s e_k, one of the six signed axes -> (s, i, j, k) with (e_i, e_j, e_k) the cyclic order of the axes."""
+    try:
+        u = [int(c) for c in up]
+        whole = len(u) == 3 and all(float(c) == float(a) for c, a in zip(up, u))
+    except (TypeError, ValueError):
+        whole = False
+    if not whole or sorted(abs(c) for c in u) != [0, 0, 1]:
+        raise ValueError(f"up must be one of the six signed axes such as (0, -1, 0), got {up!r}")
+    k = [abs(c) for c in u].index(1)
+    return u[k], (k + 1) % 3, (k + 2) % 3, k
+
+
 @dataclass
 class RouteField:
     """GridRouter.field's result; the arrays are (nz, ny, nx), x fastest, on the grid of `index_origin` and `cell`."""
@@ -64,6 +85,7 @@ class RouteField:
     settings: Dict = dc_field(default_factory=dict)
     # walk, cost for path(); d2 (the clearance field, None without a radius) for taut()
     device_arrays: Optional[Dict[str, torch.Tensor]] = dc_field(default=None, repr=False)
+    height: Optional[np.ndarray] = None         # u8: cells above the support along up, 0 none, 255 far (with stand only)
 
     @property
     def origin(self) -> np.ndarray:
@@ -205,10 +227,16 @@ class GridRouter:
     """radius (metres): the body's; 0 asks for no clearance.  through_unknown: unknown cells are traversable too (and
     no obstacles of the clearance).  approach_unknown: only free cells are traversable, but the clearance is kept from
     occupied cells alone, so a body may come up to the edge of unknown space (what frontier.py needs: a free cell that
-    borders unknown space has clearance 1 cell at most otherwise).  The two switches together are refused."""
+    borders unknown space has clearance 1 cell at most otherwise).  The two switches together are refused.
+    stand: None (a sphere that flies) or (lo, hi) in metres: the body is carried that high above something to stand on,
+    so a cell is traversable only when it also lies ceil(lo / cell) .. floor(hi / cell) cells above an occupied cell
+    along `up`, with nothing but passable cells in between (module text).  up: one of the six signed axes, read with
+    stand only; a convention, not a measurement (the world is the first camera's frame, whose y points down)."""
     radius: float = 0.0
     through_unknown: bool = False
     approach_unknown: bool = False
+    stand: Optional[tuple] = None
+    up: tuple = (0, -1, 0)
 
     SWEEPS_PER_READ = 4         # relaxation sweeps queued between two reads of their `changed` words
 
@@ -221,10 +249,39 @@ class GridRouter:
         if self.through_unknown and self.approach_unknown:
             raise ValueError("through_unknown and approach_unknown exclude each other: a body that walks through "
                              "unknown space is not kept away from it either way")
+        if self.stand is not None:
+            try:
+                lo, hi = (float(v) for v in self.stand)
+            except (TypeError, ValueError):
+                raise ValueError(f"stand must be (lo, hi) in metres, got {self.stand!r}") from None
+            if not (math.isfinite(lo) and math.isfinite(hi) and 0.0 < lo <= hi):
+                raise ValueError(f"stand must be two finite heights with 0 < lo <= hi, got {self.stand!r}")
+            self.stand = (lo, hi)
+            up_axes(self.up)                                            # checks it
+            self.up = tuple(int(c) for c in self.up)
 
     def settings(self) -> Dict:
-        return {"radius": self.radius, "through_unknown": self.through_unknown,
-                "approach_unknown": self.approach_unknown, "costs": list(ops.ROUTE_COSTS)}
+        st = {"radius": self.radius, "through_unknown": self.through_unknown,
+              "approach_unknown": self.approach_unknown, "costs": list(ops.ROUTE_COSTS)}
+        if self.stand is not None:              # only when set: every record written without it keeps its bytes
+            st.update(stand=list(self.stand), up=list(self.up))
+        return st
+
+    def stand_cells(self, cell: float):
+        """-> (h_lo, h_hi) = (ceil(lo / cell), floor(hi / cell)) for cells of this size, the band in cells above the
+        support (centre to centre); None without stand.  A band that is empty in cells, below 1 or above
+        ops.STAND_MAX_HEIGHT raises a ValueError."""
+        if self.stand is None:
+            return None
+        cell = float(cell)
+        if not (cell > 0.0 and math.isfinite(cell)):
+            raise ValueError(f"the cell must be a positive finite length, got {cell!r}")
+        lo, hi = self.stand
+        h_lo, h_hi = int(math.ceil(lo / cell)), int(math.floor(hi / cell))
+        if not 1 <= h_lo <= h_hi <= ops.STAND_MAX_HEIGHT:
+            raise ValueError(f"a standing band of lo = {lo:g} .. hi = {hi:g} at cells of {cell:g} is {h_lo} .. {h_hi} "
+                             f"cells: it must hold a cell and lie within 1 .. {ops.STAND_MAX_HEIGHT}")
+        return h_lo, h_hi
 
     def clearance_cells(self, cell: float):
         """-> (R, min_d2) for cells of this size: the distance transform's radius and the smallest passing d2; (None, 0)
@@ -266,6 +323,11 @@ class GridRouter:
             c = float(f.clearance[z, y, x])
             text += (f" with a clearance of {c:g} m" if math.isfinite(c)
                      else f" with nothing within {f.settings.get('radius_cells')} cells")
+        if f.height is not None:
+            h, (lo, hi) = int(f.height[z, y, x]), f.settings["stand_cells"]
+            text += (", and has no verified floor below it" if h == ops.STAND_NONE
+                     else f", and has no floor within {ops.STAND_MAX_HEIGHT} cells below it" if h == ops.STAND_FAR
+                     else f", {h} cells above its floor (band {lo} .. {hi})")
         return text
 
     def field(self, grid: OccupancyGrid, sources_xyz, device="cuda") -> RouteField:
@@ -280,6 +342,7 @@ class GridRouter:
                              "cost of the longest path); use a larger occupancy cell")
         state_np = np.ascontiguousarray(state_np, np.uint8)
         R, min_d2 = self.clearance_cells(grid.cell)
+        band = self.stand_cells(grid.cell)
         src = self.linear(self.world_cells(sources_xyz, grid), state_np.shape)
         dev = torch.device(device)
         state = torch.from_numpy(state_np).to(dev)
@@ -289,17 +352,29 @@ class GridRouter:
             ops.grid_edt(state, R, not (self.through_unknown or self.approach_unknown), d2, torch.empty_like(d2))
         walk = torch.empty_like(state)
         dist = torch.empty(state.shape, dtype=torch.int32, device=dev)
-        counters = torch.zeros(4, dtype=torch.int64, device=dev)
-        ops.grid_route_init(state, d2, min_d2, self.through_unknown, torch.from_numpy(src).to(dev), walk, dist, counters)
-        counts = dict(zip(ops.ROUTE_INIT_COUNTERS, (int(v) for v in counters.tolist())))
+        height = None
+        if band is None:
+            counters = torch.zeros(4, dtype=torch.int64, device=dev)
+            ops.grid_route_init(state, d2, min_d2, self.through_unknown, torch.from_numpy(src).to(dev), walk, dist, counters)
+            counts = dict(zip(ops.ROUTE_INIT_COUNTERS, (int(v) for v in counters.tolist())))
+        else:
+            s, _, _, k = up_axes(self.up)
+            height = torch.empty_like(state)
+            ops.grid_stand_height(state, k, s, self.through_unknown, height)
+            counters = torch.zeros(5, dtype=torch.int64, device=dev)
+            ops.grid_route_init_stand(state, d2, min_d2, self.through_unknown, height, band[0], band[1],
+                                      torch.from_numpy(src).to(dev), walk, dist, counters)
+            counts = dict(zip(ops.ROUTE_INIT_STAND_COUNTERS, (int(v) for v in counters.tolist())))
         clear = None
         if d2 is not None:
             raw = d2.cpu().numpy().view(np.uint16)
             clear = (float(grid.cell) * np.sqrt(raw.astype(np.float64))).astype(np.float32)
             clear[raw == ops.EDT_FAR] = np.float32(np.inf)
         st = dict(self.settings(), cell=float(grid.cell), radius_cells=R, min_d2=min_d2)
+        if band is not None:
+            st["stand_cells"] = list(band)
         out = RouteField(None, None, walk.cpu().numpy(), np.asarray(grid.index_origin, np.int64), float(grid.cell),
-                         state_np, clear, counts, st)
+                         state_np, clear, counts, st, height=None if height is None else height.cpu().numpy())
         if counts["sources_accepted"] == 0:
             if len(src) == 1 and src[0] >= 0:
                 raise ValueError(f"the start is not traversable: {self._describe(out, int(src[0]))}")
@@ -312,6 +387,8 @@ class GridRouter:
         out.cost = cost
         out.distance = np.where(reach, float(grid.cell) * cost.astype(np.float64) / 12.0, np.inf).astype(np.float32)
         out.device_arrays = {"walk": walk, "cost": dist, "d2": d2}
+        if height is not None:
+            out.device_arrays["height"] = height
         return out
 
     def relax(self, walk: torch.Tensor, dist: torch.Tensor, traversable: int) -> int:

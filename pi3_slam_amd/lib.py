@@ -130,6 +130,9 @@ SIGNATURES = {
                                    _vp, _vp, _vp],
     "pi3_grid_view_mark_frustum": [_vp, _i, _i, _i, _vp, _vp, C.POINTER(_i), _l, _i, _i, _i, C.POINTER(_i), _i, _l, _l, _l,
                                    _l, _vp, _i, _vp, _vp],
+    "pi3_grid_stand_height": [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp],
+    "pi3_grid_route_init_stand": [_vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _l, _vp, _vp, _vp, _vp],
+    "pi3_grid_view_candidates_stand": [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _l, _i, _i, _vp, _l, _vp, _vp],
     "pi3_pose_graph_workspace": [_i, _i, C.POINTER(_l)],
     "pi3_pose_graph_sim3": [_vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _l, _vp, _vp],
     "pi3_set_knob": [C.c_char_p, _l],

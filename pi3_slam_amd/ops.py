@@ -1105,6 +1105,52 @@ def grid_route_init(state: torch.Tensor, d2: Optional[torch.Tensor], min_d2: int
     _L.check(rc, "pi3_grid_route_init")
 
 
+# ---- routes for a body that stands (csrc/grid_stand.hip)
+STAND_MAX_HEIGHT = 254                  # cells: how far below a cell its support is looked for
+STAND_NONE = 0                          # no verified support: an unknown cell or the grid's border came first
+STAND_FAR = 255                         # nothing within STAND_MAX_HEIGHT cells
+ROUTE_INIT_STAND_COUNTERS = ROUTE_INIT_COUNTERS + ("off_band",)
+
+
+def grid_stand_height(state: torch.Tensor, up_axis: int, up_sign: int, through_unknown: bool,
+                      height: torch.Tensor) -> None:
+    """height uint8 (nz,ny,nx) of state uint8 (nz,ny,nx) for up = up_sign e_up_axis (up_axis 0, 1, 2 = x, y, z): j when
+    the first cell among c - j up, j = 1 .. STAND_MAX_HEIGHT, that is outside the grid or not passable (state != 1;
+    with through_unknown state == 2) is occupied, STAND_NONE when it is anything else, STAND_FAR when there is none."""
+    lib = _L.load()
+    assert _grid_state(state) and 0 < state.numel() <= ROUTE_MAX_CELLS, f"{state.numel()} cells: 1 .. 2^27"
+    assert height.dtype == torch.uint8 and height.is_contiguous() and height.shape == state.shape
+    assert height.device == state.device and height.data_ptr() != state.data_ptr()
+    nz, ny, nx = (int(v) for v in state.shape)
+    rc = lib.pi3_grid_stand_height(state.data_ptr(), nx, ny, nz, int(up_axis), int(up_sign), 1 if through_unknown else 0,
+                                   height.data_ptr(), _L.stream_ptr())
+    _L.check(rc, "pi3_grid_stand_height")
+
+
+def grid_route_init_stand(state: torch.Tensor, d2: Optional[torch.Tensor], min_d2: int, through_unknown: bool,
+                          height: torch.Tensor, h_lo: int, h_hi: int, sources: torch.Tensor, walk: torch.Tensor,
+                          dist: torch.Tensor, counters: torch.Tensor) -> None:
+    """grid_route_init for a body that stands: walk also needs h_lo <= height <= h_hi on height uint8 (nz,ny,nx)
+    (grid_stand_height's field), 1 <= h_lo <= h_hi <= STAND_MAX_HEIGHT.  counters int64 (5,) =
+    ROUTE_INIT_STAND_COUNTERS (zeroed by the call): off_band counts the cells that only the band closed."""
+    lib = _L.load()
+    nx, ny, nz = _grid_field(dist, walk)
+    dev = state.device
+    assert state.dtype == torch.uint8 and state.is_contiguous() and state.shape == walk.shape and walk.device == dev
+    if d2 is not None:
+        assert d2.dtype == torch.int16 and d2.is_contiguous() and d2.shape == state.shape and d2.device == dev
+    assert d2 is not None or int(min_d2) == 0, "min_d2 needs the clearance field d2"
+    assert height.dtype == torch.uint8 and height.is_contiguous() and height.shape == state.shape and height.device == dev
+    assert sources.dtype == torch.int64 and sources.is_contiguous() and sources.ndim == 1 and sources.device == dev
+    assert counters.dtype == torch.int64 and counters.is_contiguous() and counters.numel() >= 5 and counters.device == dev
+    Ns = int(sources.shape[0])
+    rc = lib.pi3_grid_route_init_stand(state.data_ptr(), _L.ptr(d2), int(min_d2), 1 if through_unknown else 0,
+                                       height.data_ptr(), int(h_lo), int(h_hi), nx, ny, nz,
+                                       sources.data_ptr() if Ns else None, Ns, walk.data_ptr(), dist.data_ptr(),
+                                       counters.data_ptr(), _L.stream_ptr())
+    _L.check(rc, "pi3_grid_route_init_stand")
+
+
 def grid_route_sweep(walk: torch.Tensor, dist: torch.Tensor, changed: torch.Tensor) -> None:
     """One relaxation sweep over dist int32 (nz,ny,nx) (tiles of 8 x 8 x 8 cells, each relaxed to its fixed point);
     changed int32 (1,) becomes 1 when a cell got lower (the caller zeroes it)."""
@@ -1348,6 +1394,25 @@ def grid_view_candidates(dist: torch.Tensor, index_origin, stride: int, max_cost
     rc = lib.pi3_grid_view_candidates(dist.data_ptr(), nx, ny, nz, ox, oy, oz, int(stride), int(max_cost),
                                       cells.data_ptr() if cap else None, cap, count.data_ptr(), _L.stream_ptr())
     _L.check(rc, "pi3_grid_view_candidates")
+
+
+def grid_view_candidates_stand(dist: torch.Tensor, height: torch.Tensor, index_origin, stride: int, max_cost: int,
+                               up_axis: int, h_lo: int, cells: torch.Tensor, count: torch.Tensor) -> None:
+    """grid_view_candidates for a standing planner (csrc/grid_stand.hip): on the two axes other than up_axis (0, 1, 2 =
+    x, y, z) the absolute index is a multiple of stride; along it the lattice follows the floor, (height - h_lo) mod
+    stride == 0 on height uint8 (nz,ny,nx) (grid_stand_height's field), 1 <= h_lo <= STAND_MAX_HEIGHT."""
+    lib = _L.load()
+    nx, ny, nz = _grid_field(dist)
+    dev = dist.device
+    assert height.dtype == torch.uint8 and height.is_contiguous() and height.shape == dist.shape and height.device == dev
+    assert cells.dtype == torch.int64 and cells.is_contiguous() and cells.ndim == 1 and cells.device == dev
+    assert count.dtype == torch.int64 and count.numel() == 1 and count.device == dev
+    ox, oy, oz = (int(v) for v in index_origin)
+    cap = int(cells.numel())
+    rc = lib.pi3_grid_view_candidates_stand(dist.data_ptr(), height.data_ptr(), nx, ny, nz, ox, oy, oz, int(stride),
+                                            int(max_cost), int(up_axis), int(h_lo), cells.data_ptr() if cap else None, cap,
+                                            count.data_ptr(), _L.stream_ptr())
+    _L.check(rc, "pi3_grid_view_candidates_stand")
 
 
 def _view_entry(lib, name: str, view_range: int, far: bool):

@@ -46,7 +46,7 @@ import torch
 
 from . import ops
 from .dense_map import OccupancyGrid
-from .grid_route import GridRouter, Route, RouteField
+from .grid_route import GridRouter, Route, RouteField, up_axes
 
 
 def view_headings() -> np.ndarray:
@@ -71,19 +71,6 @@ def _reduced(v) -> np.ndarray:
     return np.array([c // g for c in v], np.int64)
 
 
-def _up_axes(up):
-    """up = s e_k, one of the six signed axes -> (s, i, j, k) with (e_i, e_j, e_k) the cyclic order of the axes."""
-    try:
-        u = [int(c) for c in up]
-        whole = len(u) == 3 and all(float(c) == float(a) for c, a in zip(up, u))
-    except (TypeError, ValueError):
-        whole = False
-    if not whole or sorted(abs(c) for c in u) != [0, 0, 1]:
-        raise ValueError(f"up must be one of the six signed axes such as (0, -1, 0), got {up!r}")
-    k = [abs(c) for c in u].index(1)
-    return u[k], (k + 1) % 3, (k + 2) % 3, k
-
-
 def view_frames(yaw_steps: int = 8, pitches_deg=(0.0,), up=(0, -1, 0), portrait: bool = False) -> np.ndarray:
     """i64 (H,6), H = yaw_steps * len(pitches_deg) in 1 .. 32: the frames f (forward) then r (right) of a camera that
     pans in yaw_steps equal steps at every pitch, in the order of the pitches as given, then yaw ascending.  up = s e_k is
@@ -93,7 +80,7 @@ def view_frames(yaw_steps: int = 8, pitches_deg=(0.0,), up=(0, -1, 0), portrait:
     rounded half away from zero per component and divided by its gcd; r = f x up is horizontal, its components are f's.
     portrait: the frame is (f, r x f divided by its gcd), which must fit +-64.  Deterministic.  A ValueError names a
     frame that looks along up, two equal f, or an H outside 1 .. 32."""
-    s, i, j, k = _up_axes(up)
+    s, i, j, k = up_axes(up)
     if isinstance(yaw_steps, bool) or int(yaw_steps) != yaw_steps or int(yaw_steps) < 1:
         raise ValueError(f"yaw_steps must be an integer >= 1, got {yaw_steps!r}")
     pitches = [float(p) for p in pitches_deg]
@@ -134,7 +121,7 @@ def view_frames(yaw_steps: int = 8, pitches_deg=(0.0,), up=(0, -1, 0), portrait:
 def frame_angles(frames, yaw_steps: int, pitches_deg, up) -> List[Dict]:
     """Per frame of view_frames(yaw_steps, pitches_deg, up): the yaw and pitch of its f and the angle between f and the
     direction asked for, in degrees."""
-    s, i, j, k = _up_axes(up)
+    s, i, j, k = up_axes(up)
     out = []
     for h, row in enumerate(np.asarray(frames, np.int64).reshape(-1, 6)):
         f = row[:3].astype(np.float64)
@@ -340,7 +327,11 @@ class ViewPlanner:
     frustum: None (cones, fov_deg wide; 90 degrees when not given) or (hfov_deg, vfov_deg), each in [2, 170] degrees: the
     headings are view_frames(yaw_steps, pitches_deg, up, portrait) and a heading's gain counts the cells inside its
     frustum; fov_deg may then not be given.  portrait also swaps the two angles.  image_width: the width in
-    pixels of the intrinsics that settings() records next to the angles."""
+    pixels of the intrinsics that settings() records next to the angles.
+    stand: None or (lo, hi) in metres: the camera is carried that high above something to stand on (GridRouter's stand,
+    DESIGN §7p; `up` is then the router's too, with or without a frustum).  The route field keeps to the band, and the
+    candidates' lattice follows the floor along up: (height - h_lo) mod stride == 0, so every column that stands offers
+    its lowest band cell and a band thinner than the stride is not lost between lattice planes."""
     radius: float = 0.0
     range_m: float = 1.0
     fov_deg: Optional[float] = None
@@ -357,11 +348,16 @@ class ViewPlanner:
     up: tuple = (0, -1, 0)
     portrait: bool = False
     image_width: int = 640
+    stand: Optional[tuple] = None
 
     CANDIDATES_FIRST_CAP = 1 << 16      # the candidate buffer of the first try; a grid with more asks again
 
     def __post_init__(self):
-        self.router = GridRouter(self.radius, approach_unknown=True)       # checks the radius
+        if self.stand is None:
+            self.router = GridRouter(self.radius, approach_unknown=True)   # checks the radius
+        else:                                                              # and the band and up
+            self.router = GridRouter(self.radius, approach_unknown=True, stand=self.stand, up=self.up)
+            self.stand, self.up = self.router.stand, self.router.up
         self.radius = self.router.radius
         self.range_m = float(self.range_m)
         if not (self.range_m > 0.0 and math.isfinite(self.range_m)):
@@ -454,6 +450,8 @@ class ViewPlanner:
             st.update(unknown_is_transparent=False, unknown_depth=self.unknown_depth)
         if self.frames is not None:             # likewise
             st["frustum"] = self.frustum_settings()
+        if self.stand is not None:              # likewise; the router's block carries them too
+            st.update(stand=list(self.stand), up=list(self.up))
         return st
 
     def cells_of(self, cell: float):
@@ -474,17 +472,33 @@ class ViewPlanner:
         max_cost = far if self.max_distance_m is None else min(far, int(math.floor(self.max_distance_m * 12.0 / cell)))
         return R, sep, max_cost
 
-    def candidates(self, dist: torch.Tensor, index_origin, max_cost: int) -> torch.Tensor:
-        """The candidate cells of a settled route field, ascending, int64 (V,) on the device."""
+    def candidates(self, dist: torch.Tensor, index_origin, max_cost: int, height: Optional[torch.Tensor] = None,
+                   h_lo: Optional[int] = None) -> torch.Tensor:
+        """The candidate cells of a settled route field, ascending, int64 (V,) on the device.  height and h_lo (the
+        standing field's device array and its band's lower end): the lattice follows the floor along up."""
         cap = min(int(dist.numel()), self.CANDIDATES_FIRST_CAP)
         count = torch.zeros(1, dtype=torch.int64, device=dist.device)
         while True:
             cells = torch.empty(cap, dtype=torch.int64, device=dist.device)
-            ops.grid_view_candidates(dist, index_origin, self.stride, max_cost, cells, count)
+            if height is None:
+                ops.grid_view_candidates(dist, index_origin, self.stride, max_cost, cells, count)
+            else:
+                ops.grid_view_candidates_stand(dist, height, index_origin, self.stride, max_cost, up_axes(self.up)[3],
+                                               h_lo, cells, count)
             V = int(count.item())
             if V <= cap:
                 return torch.sort(cells[:V]).values.contiguous()
             cap = V
+
+    def _floor_lattice(self, field: RouteField):
+        """candidates' height and h_lo of a standing planner's field; nothing without stand."""
+        if self.stand is None:
+            return ()
+        return field.device_arrays["height"], int(field.settings["stand_cells"][0])
+
+    def _band(self, field: RouteField) -> Dict:
+        """The band in cells for a result's settings; nothing without stand."""
+        return {} if self.stand is None else {"stand_cells": list(field.settings["stand_cells"])}
 
     def find(self, grid: OccupancyGrid, sources_xyz, device="cuda") -> ViewSet:
         """The view poses of the grid, ranked, from the world points sources_xyz (N,3) (GridRouter.field's rules for
@@ -499,7 +513,7 @@ class ViewPlanner:
         dev = torch.device(device)
         dist = field.device_arrays["cost"]
         state = torch.from_numpy(state_np).to(dev)
-        cells = self.candidates(dist, origin, max_cost)
+        cells = self.candidates(dist, origin, max_cost, *self._floor_lattice(field))
         V = int(cells.numel())
         (hd, *cos2), shape = self.shape_args()
         gain = torch.empty((V, len(hd)), dtype=torch.int32, device=dev)
@@ -526,6 +540,7 @@ class ViewPlanner:
                       best_gain=int(best_gain.max()) if V else 0)
         st = dict(self.settings(), cell=cell, range_cells=R, separation_cells=sep, max_cost=max_cost,
                   headings=len(hd))
+        st.update(self._band(field))
         return ViewSet(views, gain_map, heading_map, hd, origin, cell, counts, st, field, self.router,
                        sources=np.asarray(sources_xyz, np.float64).reshape(-1, 3), frames=self.frames)
 
@@ -551,7 +566,7 @@ class ViewPlanner:
         origin = np.asarray(grid.index_origin, np.int64)
         dev = torch.device(device)
         state = torch.from_numpy(state_np).to(dev)
-        cells = self.candidates(field.device_arrays["cost"], origin, max_cost)
+        cells = self.candidates(field.device_arrays["cost"], origin, max_cost, *self._floor_lattice(field))
         V = int(cells.numel())
         (hd, *cos2), shape = self.shape_args()
         H = len(hd)
@@ -609,5 +624,6 @@ class ViewPlanner:
                       recomputed_rows=recomputed, mark_rays=mark_rays[0])
         st = dict(self.settings(), cell=cell, range_cells=R, separation_m=None, separation_cells=None, max_cost=max_cost,
                   headings=H, mode="cover", until=until)
+        st.update(self._band(field))
         return ViewSet(views, gain_map, heading_map, hd, origin, cell, counts, st, field, self.router,
                        owner.cpu().numpy(), "cover", np.asarray(sources_xyz, np.float64).reshape(-1, 3), self.frames)
